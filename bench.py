@@ -34,7 +34,22 @@ pixel and rank r traces its tiles of every sample, i.e. spp films' worth of rays
 `python bench.py --gpus N` with N > 1 starts its own ranks (torch.distributed.run, one per
 GPU) before anything touches the GPU; launched under torchrun it uses the ranks it was given.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scene crown] [--no-cpu-baseline]
+A plain run prints the headline (value, ms_per_step) and the workload's config, and nothing it does
+outside the K timed steps is more than setting up and warming up.  --full adds everything else that is
+measured or checked: per-class kernel rates, the film stage, the roofline record, the film / hit-record
+all-gathers of N > 1, the dependent (wavefront-queue) form of the step, the ray-order probe and the CPU
+baseline with its cross-check against the GPU records.
+
+--dump-outputs DIR writes what the last timed step computed as .npy files (float32 / float64, about
+50 MB at the default size): for each closest-hit class (primary, bounce, bounce2) <class>_hit_f32 = t, b0,
+b1, b2 (0 for a miss, prim = -1: a miss returns no intersection, its record's t is the ray's tMax, often
++inf) and <class>_hit_i = prim, nodes_visited, prim_tests, instance; shadow_occluded; sample_radiance = L
+of each pixel sample; film = the film's rgbSum[3], weightSum after the K steps.  Every value is finite.
+Each array holds a fixed, seeded sample of at most 2^18 rows, in index order (all rows when fewer).  With
+N > 1 every rank writes its own files, prefixed rank<r>_.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--scene crown] [--full] [--dump-outputs DIR]
+       [--no-cpu-baseline]
 """
 import argparse
 import glob
@@ -103,12 +118,20 @@ def parse_args(argv=None):
                          "the pixels in 4x4 tiles (a wavefront's 64 rays = 8 pixels of a 4x2 block); sample = spp "
                          "whole-image passes concatenated")
     ap.add_argument("--overlapped", action="store_true",
-                    help="also time the step with the three batches as concurrent launches on the "
+                    help="with --full: also time the step with the three batches as concurrent launches on the "
                          "library's internal streams (fused_batches off)")
     ap.add_argument("--cpu-sample", type=int, default=1_000_000,
                     help="rays per class timed on the host cores for cpu_baseline")
     ap.add_argument("--cpu-passes", type=int, default=5)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (per-class rates, film stage, "
+                         "roofline, all-gathers, dependent step, ray-order probe, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a seeded sample of what the last timed step computed to DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def free_port():
@@ -181,6 +204,42 @@ def profile_counters(prefix, pattern="r*_final*"):
         except (OSError, ValueError, KeyError, StopIteration):
             continue
     return None
+
+
+DUMP_ROWS = 1 << 18  # rows per array written by --dump-outputs (at most ~52 MB in all)
+
+
+def dump_outputs(out_dir, st, film, prefix=""):
+    """--dump-outputs: a fixed, seeded sample of sample set `st`'s records (traced by the last timed step) and of
+    the film, as out_dir/<prefix><name>.npy in float32 / float64 (integer fields are exact in float64)."""
+    import numpy as np
+    import torch
+    from nn_bvh_amd._lib import HIT_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+
+    def rows(n):
+        if n <= DUMP_ROWS:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+
+    def take(t, n):  # the sampled rows of a device tensor with n rows
+        return t[torch.from_numpy(rows(n)).to(t.device)].cpu().numpy()
+
+    out = {}
+    for cls, key, n in (("primary", "d_hits", st["n_primary"]), ("bounce", "d_bhits", st["n_bounce"]),
+                        ("bounce2", "d_b2hits", st["n_bounce2"])):
+        h = take(st[key].view(-1, HIT_DTYPE.itemsize), n).view(HIT_DTYPE).reshape(-1)
+        floats = np.stack([h[f] for f in ("t", "b0", "b1", "b2")], 1)
+        floats[h["prim"] < 0] = 0  # a miss carries no t or barycentrics (its t field holds the ray's tMax, often +inf)
+        out[cls + "_hit_f32"] = floats
+        out[cls + "_hit_i"] = np.stack([h[f] for f in ("prim", "nodes_visited", "prim_tests", "instance")],
+                                       1).astype(np.float64)
+    out["shadow_occluded"] = take(st["d_occ"], st["n_shadow"]).astype(np.float32)
+    out["sample_radiance"] = take(st["d_L"], st["n_primary"])
+    pixels = film.read()
+    out["film"] = pixels[rows(len(pixels))]
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -328,7 +387,7 @@ def main():
                                          box=(lo + (hi - lo) * [0.3, 0.9, 0.3], lo + (hi - lo) * [0.7, 1.0, 0.7]))
         n_bounce, n_bounce2, n_shadow = len(bounce_t), len(bounce2_t), len(shadow_t)
         gen = torch.Generator(device=cdev).manual_seed(100 + 10 * rank + k)
-        first = k == 0
+        first = k == 0 and args.full  # host copies of set 0: inputs of the --full legs only
         st = {
             "primary": raygen.as_records(primary_t) if first else None,
             "bounce": raygen.as_records(bounce_t) if first else None,
@@ -429,6 +488,68 @@ def main():
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         rays_timed = float(tot.item())
 
+    # ---- what the last timed step computed, for comparing builds output for output
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sets[(args.steps - 1) % len(sets)], film,
+                     f"rank{rank}_" if world > 1 else "")
+
+    n_primary, n_bounce, n_bounce2, n_shadow = s0["n_primary"], s0["n_bounce"], s0["n_bounce2"], s0["n_shadow"]
+    result = None
+    if rank == 0:
+        value = rays_timed / elapsed / 1e6
+        total_spp = world * args.spp
+        result = {
+            "metric": "Mray/s (closest-hit + any-hit)",
+            "value": round(value, 2),
+            "unit": "Mray/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": f"{args.scene}, {xres}x{yres}: one wavefront pass of {total_spp} spp per step "
+                            f"({args.spp} spp per GPU-film) — primary, bounce-1 and bounce-2 closest-hit, shadow "
+                            f"any-hit towards the light quads (batches pre-generated, hence independent: ONE launch; the "
+                            f"dependent form is dependent_step), rays in --ray-order {args.ray_order} (a caller-side "
+                            f"order the reference's integrator does not form: ray_order_probe), "
+                            f"RecordShadowRayResult + RGBFilm::AddSample into a "
+                            f"4-doubles-per-pixel film; {args.steps} steps rotating over {len(sets)} distinct "
+                            f"sample sets; BASELINE's 1024 spp = {1024 // max(1, total_spp)} such passes, "
+                            f"extrapolated per SURVEY §8d (>= 64 M rays per class timed), not traced",
+                "spp_per_step": args.spp,
+                "ray_order": {"tile": "pixel-major, pixels in 4x4 tiles: the spp samples of a pixel are adjacent in every "
+                                      "batch, a wavefront's 64 rays cover a 4x2 block of pixels",
+                              "pixel": "pixel-major: the spp samples of a pixel are adjacent in every batch, pixels in "
+                                       "scanline order",
+                              "sample": "sample-major: spp whole-image passes concatenated"}[args.ray_order],
+                "sample_sets": len(sets),
+                "geometry": source,
+                "tree": args.tree,
+                "triangles": int(len(tris)),
+                "nodes": int(len(tree.nodes)),
+                "rays_primary": int(n_primary),
+                "rays_bounce": int(n_bounce),
+                "rays_bounce2": int(n_bounce2),
+                "rays_shadow": int(n_shadow),
+                "rays_per_step_per_gpu": int(rays_per_step),
+                "parallelism": f"tile-sharded x{world}, BVH replicated, film all-gather after the pass",
+                "launches_per_step": "1 (nnbvh_trace_batches_device, mode-3 kernel)" if fused else "4",
+            },
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), file=result_out, flush=True)
+        film.close()
+        agg.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # ---- the film all-gather that ends the pass (RCCL over xGMI under nccl): every rank packs the
     # accumulators of its tiles, one all_gather_into_tensor, the others' tiles are unpacked
     film_allgather_ms = film_bytes = None
@@ -475,7 +596,6 @@ def main():
         return float(np.mean([a.elapsed_time(b) for a, b in evs]))
 
     reps = max(3, min(args.steps, 10))
-    n_primary, n_bounce, n_bounce2, n_shadow = s0["n_primary"], s0["n_bounce"], s0["n_bounce2"], s0["n_shadow"]
     ms_primary = time_kernel(lambda: agg.intersect_device(s0["d_primary"].data_ptr(), s0["d_hits"].data_ptr(),
                                                           n_primary, stream), reps)
     ms_bounce = time_kernel(lambda: agg.intersect_device(s0["d_bounce"].data_ptr(), s0["d_bhits"].data_ptr(),
@@ -659,52 +779,8 @@ def main():
     traffic = prof["hbm_bytes_per_launch"] if prof else None
     valu_peak = N_SIMD * SHADER_GHZ / 2.0  # G wave-instructions/s: one wave64 VALU instruction per SIMD-32 per 2 cycles
 
-    result = None
     if rank == 0:
-        value = rays_timed / elapsed / 1e6
-        total_spp = world * args.spp
-        result = {
-            "metric": "Mray/s (closest-hit + any-hit)",
-            "value": round(value, 2),
-            "unit": "Mray/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": f"{args.scene}, {xres}x{yres}: one wavefront pass of {total_spp} spp per step "
-                            f"({args.spp} spp per GPU-film) — primary, bounce-1 and bounce-2 closest-hit, shadow "
-                            f"any-hit towards the light quads (batches pre-generated, hence independent: ONE launch; the "
-                            f"dependent form is dependent_step), rays in --ray-order {args.ray_order} (a caller-side "
-                            f"order the reference's integrator does not form: ray_order_probe), "
-                            f"RecordShadowRayResult + RGBFilm::AddSample into a "
-                            f"4-doubles-per-pixel film; {args.steps} steps rotating over {len(sets)} distinct "
-                            f"sample sets; BASELINE's 1024 spp = {1024 // max(1, total_spp)} such passes, "
-                            f"extrapolated per SURVEY §8d (>= 64 M rays per class timed), not traced",
-                "spp_per_step": args.spp,
-                "ray_order": {"tile": "pixel-major, pixels in 4x4 tiles: the spp samples of a pixel are adjacent in every "
-                                      "batch, a wavefront's 64 rays cover a 4x2 block of pixels",
-                              "pixel": "pixel-major: the spp samples of a pixel are adjacent in every batch, pixels in "
-                                       "scanline order",
-                              "sample": "sample-major: spp whole-image passes concatenated"}[args.ray_order],
-                "sample_sets": len(sets),
-                "geometry": source,
-                "tree": args.tree,
-                "triangles": int(len(tris)),
-                "nodes": int(len(tree.nodes)),
-                "rays_primary": int(n_primary),
-                "rays_bounce": int(n_bounce),
-                "rays_bounce2": int(n_bounce2),
-                "rays_shadow": int(n_shadow),
-                "rays_per_step_per_gpu": int(rays_per_step),
-                "parallelism": f"tile-sharded x{world}, BVH replicated, film all-gather after the pass",
-                "launches_per_step": "1 (nnbvh_trace_batches_device, mode-3 kernel)" if fused else "4",
-            },
+        result.update({
             "per_class_mrays": {
                 "primary_closest": round(n_primary / ms_primary / 1e3, 2),
                 "bounce_closest": round(n_bounce / ms_bounce / 1e3, 2),
@@ -758,7 +834,7 @@ def main():
                             "over the kernel's time; cache-served re-reads included, hence not a bound",
                 },
             },
-        }
+        })
         if order_probe is not None:
             result["ray_order_probe"] = order_probe
         if world > 1:

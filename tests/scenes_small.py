@@ -1,7 +1,24 @@
 """Small seeded scenes shared by the parity tests (inputs only)."""
+import os
+
 import numpy as np
 
-from nn_bvh_amd import make_prims
+from nn_bvh_amd import make_prims, scene
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def scene_blob(name):
+    """(verts, tris) of a reference scene: data/<name>.npz where the build made it, else the copy kept under
+    tests/golden/ (killeroos only, tools/make_killeroos.py's output: the larger scenes are not kept in the
+    repository); None if neither exists."""
+    if os.path.exists(scene.blob_path(name)):
+        return scene.load_blob(name)
+    path = os.path.join(GOLDEN, name + ".npz")
+    if not os.path.exists(path):
+        return None
+    with np.load(path) as z:
+        return z["verts"], z["tris"]
 
 
 def random_soup(n_tris=2000, n_patches=0, seed=0, extent=10.0, size=0.6):

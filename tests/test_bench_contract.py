@@ -1,10 +1,12 @@
-"""bench.py's output contract (one JSON line on stdout with the driver's keys plus `roofline` and
-`cpu_baseline`) and its behaviour without a GPU (fails loudly: there is no CPU fallback)."""
+"""bench.py's output contract (one JSON line on stdout with the driver's keys; with --full also `roofline` and
+`cpu_baseline`), its --dump-outputs files, and its behaviour without a GPU (fails loudly: there is no CPU
+fallback)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,7 +20,7 @@ def run_bench(*args, timeout=600):
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = run_bench("--steps", "2", "--warmup", "1", "--scene", "killeroos", "--spp", "1", "--cpu-sample", "20000",
-                    "--cpu-passes", "1")
+                    "--cpu-passes", "1", "--full")
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout
@@ -43,6 +45,31 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     cb = r["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
     assert cb["matches_gpu"] is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run prints only the headline and the config (the rest is --full's); --dump-outputs writes the
+    last timed step's records as finite float32 / float64 arrays within 64 MB, identical from run to run."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = run_bench("--steps", "3", "--warmup", "1", "--scene", "killeroos", "--spp", "1", "--dump-outputs", str(d))
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0 and r["ms_per_step"] > 0
+        assert r["metric"] and r["unit"] == "Mray/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+        assert not {"roofline", "cpu_baseline", "dependent_step", "per_class_mrays", "film"} & set(r)
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert set(a) >= {"primary_hit_f32.npy", "primary_hit_i.npy", "bounce_hit_f32.npy", "bounce2_hit_i.npy",
+                      "shadow_occluded.npy", "sample_radiance.npy", "film.npy"}
+    assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert (a["primary_hit_i.npy"][:, 0] >= 0).any() and a["film.npy"][:, 3].sum() > 0
+    assert set(a) == set(b) and all(a[k].tobytes() == b[k].tobytes() for k in a)
 
 
 def test_bench_fails_loudly_without_a_gpu():
@@ -97,7 +124,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu_prints_one_line_with_the_film_gathe
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env["NNBVH_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--scene", "killeroos", "--spp", "1", "--sample-sets", "2"], capture_output=True, text=True,
+                          "--scene", "killeroos", "--spp", "1", "--sample-sets", "2", "--full"], capture_output=True, text=True,
                          timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]

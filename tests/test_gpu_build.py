@@ -142,9 +142,10 @@ def test_thousands_of_single_leaf_treelets():
 
 @pytest.mark.parametrize("name", ["killeroos", "bathroom", "crown"])
 def test_scene_blobs(name):
-    if not os.path.exists(os.path.join(os.path.dirname(__file__), "..", "data", name + ".npz")):
+    blob = ss.scene_blob(name)
+    if blob is None:
         pytest.skip(f"data/{name}.npz not present")
-    verts, tris = scene.load_blob(name)
+    verts, tris = blob
     host = same_tree(make_prims(tris), verts, what=name)
     assert len(host.nodes) > 1000 and host.nodes["nprims"].sum() == len(tris)
 
@@ -188,9 +189,10 @@ def test_sah_clustered_and_caller_bounds():
 
 @pytest.mark.parametrize("name", ["killeroos", "coffee_maker", "bathroom", "crown"])
 def test_sah_scene_blobs(name):
-    if not os.path.exists(os.path.join(os.path.dirname(__file__), "..", "data", name + ".npz")):
+    blob = ss.scene_blob(name)
+    if blob is None:
         pytest.skip(f"data/{name}.npz not present")
-    verts, tris = scene.load_blob(name)
+    verts, tris = blob
     host = same_tree(make_prims(tris), verts, what=name, method="sah")
     assert host.nodes["nprims"].sum() == len(tris)
 

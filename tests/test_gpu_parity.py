@@ -189,9 +189,10 @@ def test_rays_on_box_planes_with_zero_and_infinite_components():
 def test_reference_scene_blobs_full_size(name):
     """Full-size scenes (when the git-ignored blob travelled): oracle parity on a sample of each
     ray class, plus size-independent properties on the full primary batch."""
-    if not os.path.exists(scene.blob_path(name)):
+    blob = ss.scene_blob(name)
+    if blob is None:
         pytest.skip(f"data/{name}.npz not present")
-    verts, tris = scene.load_blob(name)
+    verts, tris = blob
     from nn_bvh_amd import make_prims
     prims = make_prims(tris)
     tree = build_tree(prims, verts)

@@ -1,13 +1,10 @@
 """KdTreeAggregate construction (cpu/aggregates.cpp:798-971): what the order of EQUAL (t, type) edges can and
 cannot change (CPU: the host builder with libstdc++'s std::sort against the same builder with
 std::stable_sort), and the device builder against the host one byte for byte (GPU)."""
-import os
-
 import numpy as np
 import pytest
 
 import scenes_small as ss
-from nn_bvh_amd import scene
 from nn_bvh_amd.kdtree import build_kd_tree
 
 
@@ -86,9 +83,10 @@ def test_device_kd_build_other_costs_and_host_primitives():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["killeroos", "bathroom"])
 def test_device_kd_build_on_scene_blobs(name):
-    if not os.path.exists(scene.blob_path(name)):
+    blob = ss.scene_blob(name)
+    if blob is None:
         pytest.skip(f"data/{name}.npz not present")
-    verts, tris = scene.load_blob(name)
+    verts, tris = blob
     prims = ss.make_prims(tris)
     h = build_kd_tree(prims, verts, where="host_stable")
     g = build_kd_tree(prims, verts, where="gpu")

@@ -299,10 +299,10 @@ def test_device_kd_traversal_mesh_host_prims_and_deep_stack():
 
 @pytest.mark.gpu
 def test_device_kd_traversal_on_a_scene_blob_and_an_nss_style_tree():
-    import os
-    if not os.path.exists(scene.blob_path("killeroos")):
+    blob = ss.scene_blob("killeroos")
+    if blob is None:
         pytest.skip("data/killeroos.npz not present")
-    verts, tris = scene.load_blob("killeroos")
+    verts, tris = blob
     prims = ss.make_prims(tris)
     tree = build_kd_tree(prims, verts)
     rays = scene.camera_rays("killeroos", subsample=2)
@@ -324,10 +324,10 @@ def test_device_kd_traversal_on_scene_blobs_sampled_per_ray_class(name):
     """bathroom's and crown's kd-trees (KdTreeAggregate::Create's defaults, built on the device; bathroom V = 57.5,
     T = 34 per primary ray): a 60 k-ray sample of each ray class — primary, diffuse bounce, shadow — against the
     oracle, as the BVH blob test does."""
-    import os
-    if not os.path.exists(scene.blob_path(name)):
+    blob = ss.scene_blob(name)
+    if blob is None:
         pytest.skip(f"data/{name}.npz not present")
-    verts, tris = scene.load_blob(name)
+    verts, tris = blob
     prims = ss.make_prims(tris)
     tree = build_kd_tree(prims, verts, where="gpu")
     agg = KdTreeAggregate.from_tree(tree.nodes, tree.prim_indices, prims, verts, tree.bounds)

@@ -143,11 +143,12 @@ def test_reference_aggregates_recorded_in_survey(name, nodes, depth, v_closest, 
     here: DESIGN.md §2); per-ray parity with the reference stays unpinned.  The survey's bounce-ray
     rows are not used: its bounce generator is not specified to the bit, and ours (same recipe,
     own random stream) gives crown V = 93.0 / T = 7.73 against the recorded 89.4 / 6.95.
-    Needs the git-ignored scene blob (build container / GPU box)."""
-    if not os.path.exists(scene.blob_path(name)):
+    Needs the git-ignored scene blob where the build made it (killeroos: its copy under tests/golden/)."""
+    blob = ss.scene_blob(name)
+    if blob is None:
         pytest.skip(f"data/{name}.npz not present")
     from nn_bvh_amd import make_prims
-    verts, tris = scene.load_blob(name)
+    verts, tris = blob
     tree = build_tree(make_prims(tris), verts)
     assert len(tree.nodes) == nodes and tree.depth == depth
     rays = scene.camera_rays(name, jitter=False)

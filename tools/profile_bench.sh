@@ -4,7 +4,7 @@
 #   2. separate --pmc passes (HBM-side traffic: TCC_EA0 read requests by size, FETCH_SIZE, WRITE_SIZE;
 #      SQ issue / wait / lanes; TCP / TCC) — never combined with traces
 # usage: tools/profile_bench.sh <outdir> [--script tools/x.py] [--light] [--passes "sq1 tcc"] [args...]
-#   default command: python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-wavefront --no-order-probe args...
+#   default command: python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-wavefront --no-order-probe args...
 #   --script S: python3 S args...        --light: kernel trace + the three passes the derived figures need
 set -u
 out=$1; shift
@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 mkdir -p "$out"
 light=0
 only=""
-CMD=(python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-wavefront --no-order-probe)
+CMD=(python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-wavefront --no-order-probe)
 while [ $# -gt 0 ]; do
   case "$1" in
     --script) CMD=(python3 "$2"); shift 2;;
