@@ -530,6 +530,72 @@ int nnbvh_triangle_interactions_device(const nnbvh_shading_mesh *m, const void *
                                        int32_t max_items, const int32_t *d_size, void *d_out,
                                        void *stream);
 
+/* ---- IntersectClosest with the work items themselves (wavefront/intersect.h:16-156) ---------------
+ * The *_items calls push what nnbvh_wavefront_intersect_closest pushes and, next to each index, the
+ * work item's payload as the reference's SOA queues lay it out (MaterialEvalWorkItem,
+ * HitAreaLightWorkItem, MediumSampleWorkItem, the spawned ray of an interface surface:
+ * wavefront/workitems.soa:63-75, 118-141, 156-174).  The SurfaceInteraction is computed in the same
+ * kernel, only for the items whose queue stores geometry, and is bit-identical to
+ * nnbvh_triangle_interactions_device's record of the same hit.
+ *
+ * In every queue slot k of each slice belongs to queue.items[k]; a slice's capacity is that of the
+ * matching nnbvh_closest_queues member (pushes beyond it are counted in *size, nothing is stored).
+ * Every pointer is nullable ("not wanted": no store is issued for it).  Fields per queue (others must
+ * be NULL, else NNBVH_ERR_ARG):
+ *   hit_area_light          prim p n uv wo
+ *   basic / universal_eval  prim pi n ns dpdu dpdv dpdus dpdvs dndus dndvs wo uv face_index time
+ *   medium_sample           the material fields + t_max; here wo = -ray.d, NOT normalised (intersect.h:76)
+ *   next_ray                prim ray_o ray_d time (Interaction::SpawnRay(ray.d), interaction.h:98-100)
+ * wo elsewhere is the interaction's Normalize(-ray.d). */
+typedef struct nnbvh_item_slices { /* device pointers, one slice per component */
+    int32_t *prim;       /* the hit record's primitive id: the caller maps it to material / areaLight /
+                            mediumInterface as it maps NNBVH_CLASS_* today */
+    float *pi[6];        /* Point3fi: x.low x.high y.low y.high z.low z.high */
+    float *p[3];         /* Point3f(pi) = per-axis Interval::Midpoint, (low + high) / 2 (util/math.h:851, 862) */
+    float *n[3], *ns[3], *dpdu[3], *dpdv[3], *dpdus[3], *dpdvs[3], *dndus[3], *dndvs[3];
+    float *wo[3], *uv[2];
+    int32_t *face_index;
+    float *time;
+    float *t_max;        /* MediumSampleWorkItem::tMax: the hit's t, +Infinity on a miss */
+    float *ray_o[3], *ray_d[3]; /* next_ray only: the spawned ray */
+} nnbvh_item_slices;
+
+typedef struct nnbvh_closest_items {
+    nnbvh_item_slices hit_area_light, basic_eval_material, universal_eval_material, medium_sample, next_ray;
+    nnbvh_work_queue needs_host; /* indices of the items the device cannot finish; size NULL = dropped */
+} nnbvh_closest_items;
+
+/* Routing: that of nnbvh_wavefront_intersect_closest (the six index queues hold the same sets), except
+ *   - a voided record (instance == -1: a host-only primitive lies on the ray) goes to needs_host only;
+ *   - a hit the shading mesh cannot finish (its interaction status would be NNBVH_INTERACTION_HOST: a
+ *     primitive without vertices in the mesh, a hit inside an instance without an instance table) goes
+ *     to needs_host only;
+ *   - a miss inside a medium goes to medium_sample with prim = -1 and t_max = +Infinity, and no other
+ *     slice is written for it (intersect.h:19-22).
+ * Hit records from any source (BVH, kd-tree, nnbvh_trace_batches_device): d_hits = nnbvh_hit[max_rays];
+ * ray_queue gives the rays' d (time, has_medium optional); n = min(max_rays, *d_size) when d_size != NULL. */
+int nnbvh_wavefront_enqueue_closest_items_device(const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                 const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                                 const void *d_hits, const uint8_t *d_prim_class,
+                                                 int64_t n_prim_class, const nnbvh_closest_queues *out,
+                                                 const nnbvh_closest_items *items, void *stream);
+/* nnbvh_wavefront_intersect_closest, then the enqueue above.  d_hits may be NULL here (a per-stream
+ * workspace of the scene's holds the records). */
+int nnbvh_wavefront_intersect_closest_items(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                            const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                            const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+                                            const nnbvh_closest_queues *out, const nnbvh_closest_items *items,
+                                            void *stream);
+/* nnbvh_wavefront_intersect_closest_and_shadow with the closest side's items (same fallback for scenes
+ * the one-launch form does not cover). */
+int nnbvh_wavefront_intersect_closest_and_shadow_items(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, int32_t max_shadow_rays,
+    const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld, const float *d_r_u,
+    const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_occluded,
+    void *stream);
+
 /* ---- KdTreeAggregate (cpu/aggregates.h:75-105; aggregates.cpp:746-1161) --------------------------
  * The reference's other accelerator ("kdtree" in CreateAccelerator, aggregates.cpp:1163-1178) and the
  * native structure of the learned trees of machine_learning/nss_*.py.

@@ -245,6 +245,32 @@ class HipBVHAggregate {
             fatal("IntersectClosestAndShadowQueues");
     }
 
+    // == IntersectClosest / IntersectClosestAndShadow with the work items themselves: next to each index the
+    //    SOA payload the reference's Push stores (MaterialEvalWorkItem, HitAreaLightWorkItem, MediumSampleWorkItem,
+    //    the spawned ray), computed from `mesh`; dHits may be null (include/nnbvh.h)
+    void IntersectClosestItemsQueues(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &rayQueue,
+                                     const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass, void *dHits,
+                                     const nnbvh_closest_queues &out, const nnbvh_closest_items &items,
+                                     void *stream) const {
+        if (nnbvh_wavefront_intersect_closest_items(scene_, mesh, maxRays, &rayQueue, dSize, dPrimClass, nPrimClass,
+                                                    dHits, &out, &items, stream) != NNBVH_OK)
+            fatal("IntersectClosestItemsQueues");
+    }
+    void IntersectClosestAndShadowItemsQueues(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &rayQueue,
+                                              const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass,
+                                              void *dHits, const nnbvh_closest_queues &out,
+                                              const nnbvh_closest_items &items, int maxShadowRays,
+                                              const nnbvh_ray_soa &shadowQueue, const int32_t *dShadowSize,
+                                              const float *dLd, const float *dRu, const float *dRl,
+                                              const int32_t *dPixelIndex, float *dL, int64_t nPixels, void *stream,
+                                              uint8_t *dOccluded = nullptr) const {
+        if (nnbvh_wavefront_intersect_closest_and_shadow_items(scene_, mesh, maxRays, &rayQueue, dSize, dPrimClass,
+                                                               nPrimClass, dHits, &out, &items, maxShadowRays,
+                                                               &shadowQueue, dShadowSize, dLd, dRu, dRl, dPixelIndex,
+                                                               dL, nPixels, dOccluded, stream) != NNBVH_OK)
+            fatal("IntersectClosestAndShadowItemsQueues");
+    }
+
     // == one wavefront iteration's independent queues as ONE launch (include/nnbvh.h)
     void TraceBatchesDevice(const nnbvh_batch *batches, int nBatches, void *stream) const {
         if (nnbvh_trace_batches_device(scene_, batches, nBatches, stream) != NNBVH_OK)

@@ -37,10 +37,25 @@ INTERACTION_DTYPE = np.dtype([("pi_lo", "<f4", 3), ("pi_hi", "<f4", 3), ("uv", "
                               ("dndus", "<f4", 3), ("dndvs", "<f4", 3), ("dndu", "<f4", 3), ("dndv", "<f4", 3),
                               ("pad0", "<f4"), ("prim", "<i4"), ("status", "<i4"), ("pad1", "<i4", 2)])
 TRI_FLIP_NORMAL, TRI_HAS_UV, TRI_HAS_N, TRI_HAS_S = 1, 2, 4, 8
+# nnbvh_item_slices: one device pointer per slice (0 = not wanted), field name -> number of components
+ITEM_FIELDS = {"prim": 1, "pi": 6, "p": 3, "n": 3, "ns": 3, "dpdu": 3, "dpdv": 3, "dpdus": 3, "dpdvs": 3,
+               "dndus": 3, "dndvs": 3, "wo": 3, "uv": 2, "face_index": 1, "time": 1, "t_max": 1, "ray_o": 3,
+               "ray_d": 3}
+ITEM_SLICES_DTYPE = np.dtype([(k, "<u8") if c == 1 else (k, "<u8", c) for k, c in ITEM_FIELDS.items()])
+ITEM_QUEUES = ("hit_area_light", "basic_eval_material", "universal_eval_material", "medium_sample", "next_ray")
+CLOSEST_ITEMS_DTYPE = np.dtype([(k, ITEM_SLICES_DTYPE) for k in ITEM_QUEUES] + [("needs_host", WORK_QUEUE_DTYPE)])
+# the fields each queue's Push stores (wavefront/intersect.h): any other slice is an NNBVH_ERR_ARG
+_MATERIAL_FIELDS = ("prim", "pi", "n", "ns", "dpdu", "dpdv", "dpdus", "dpdvs", "dndus", "dndvs", "wo", "uv",
+                    "face_index", "time")
+ITEM_QUEUE_FIELDS = {"hit_area_light": ("prim", "p", "n", "uv", "wo"),
+                     "basic_eval_material": _MATERIAL_FIELDS, "universal_eval_material": _MATERIAL_FIELDS,
+                     "medium_sample": _MATERIAL_FIELDS + ("t_max",),
+                     "next_ray": ("prim", "ray_o", "ray_d", "time")}
 assert INTERACTION_DTYPE.itemsize == 192
 assert NODE_DTYPE.itemsize == 32 and PRIM_DTYPE.itemsize == 24
 assert RAY_SOA_DTYPE.itemsize == 72 and CLOSEST_QUEUES_DTYPE.itemsize == 6 * 24
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+assert ITEM_SLICES_DTYPE.itemsize == 48 * 8 and CLOSEST_ITEMS_DTYPE.itemsize == 5 * 48 * 8 + 24
 
 EXPORTS = [
     "nnbvh_last_error", "nnbvh_device_count", "nnbvh_build_create", "nnbvh_build_nodes",
@@ -63,7 +78,8 @@ EXPORTS = [
     "nnbvh_kd_scene_create", "nnbvh_kd_scene_create_with_attributes", "nnbvh_kd_scene_destroy", "nnbvh_kd_intersect_closest", "nnbvh_kd_intersect_any",
     "nnbvh_kd_intersect_closest_device", "nnbvh_kd_intersect_any_device",
     "nnbvh_wavefront_intersect_shadow_tr", "nnbvh_wavefront_intersect_one_random",
-    "nnbvh_scene_create_instanced_animated",
+    "nnbvh_scene_create_instanced_animated", "nnbvh_wavefront_enqueue_closest_items_device",
+    "nnbvh_wavefront_intersect_closest_items", "nnbvh_wavefront_intersect_closest_and_shadow_items",
 ]
 
 _lib = None
@@ -168,6 +184,13 @@ def lib():
     L.nnbvh_wavefront_intersect_closest_and_shadow.restype = i32
     L.nnbvh_wavefront_intersect_closest_and_shadow.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp,
                                                                i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+    L.nnbvh_wavefront_enqueue_closest_items_device.restype = i32
+    L.nnbvh_wavefront_enqueue_closest_items_device.argtypes = [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.nnbvh_wavefront_intersect_closest_items.restype = i32
+    L.nnbvh_wavefront_intersect_closest_items.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.nnbvh_wavefront_intersect_closest_and_shadow_items.restype = i32
+    L.nnbvh_wavefront_intersect_closest_and_shadow_items.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, vp,
+                                                                     vp, vp, vp, vp, vp, vp, i64, vp, vp]
     L.nnbvh_wavefront_record_shadow_device.restype = i32
     L.nnbvh_wavefront_record_shadow_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, i32, vp]
     L.nnbvh_film_create.restype = vp

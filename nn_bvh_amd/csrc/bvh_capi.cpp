@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "interaction.h"
 #include "wavefront.h"
 #include "wavefront2.h"
+#include "wavefront_items.h"
 
 namespace nnbvh {
 
@@ -51,6 +53,8 @@ struct Workspace {
     // grow-only staging for the host-buffer entry points
     void *d_in = nullptr, *d_out = nullptr, *d_aux0 = nullptr, *d_aux1 = nullptr;
     size_t in_bytes = 0, out_bytes = 0, aux_bytes = 0;
+    void *d_hits = nullptr;  // hit records of the *_items calls made without d_hits
+    size_t hits_bytes = 0;
     // grow-only scratch of the multi-pass entry points (IntersectShadowTr / IntersectOneRandom): ping-pong ray and
     // hit buffers, per-item state, counters.  Per stream like the queue heads: the calls are asynchronous on their
     // stream, so two streams must not share them
@@ -767,7 +771,7 @@ void nnbvh_scene_destroy(nnbvh_scene *s) {
     (void)hipDeviceSynchronize();
     for (auto &kv : s->workspaces) {
         Workspace &w = kv.second;
-        void *ptrs[] = {w.queue, w.spill, w.d_in, w.d_out, w.d_aux0, w.d_aux1};
+        void *ptrs[] = {w.queue, w.spill, w.d_in, w.d_out, w.d_aux0, w.d_aux1, w.d_hits};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         for (void *p : w.scratch)
@@ -1178,6 +1182,27 @@ static bool soa_ok(const nnbvh_ray_soa *q) {
     return q && q->ox && q->oy && q->oz && q->dx && q->dy && q->dz;
 }
 
+static bool queues_ok(const nnbvh_closest_queues *out) {
+    const nnbvh_work_queue *qs[6] = {&out->escaped, &out->hit_area_light, &out->basic_eval_material,
+                                     &out->universal_eval_material, &out->medium_sample, &out->next_ray};
+    for (const nnbvh_work_queue *q : qs)
+        if (q->size && (q->capacity < 0 || (q->capacity > 0 && !q->items))) return false;
+    return true;
+}
+
+// the trace half of IntersectClosest: ray queue -> d_hits (the caller holds the scene's lock)
+static int closest_trace(nnbvh_scene *s, Workspace *w, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                         const int32_t *d_size, void *d_hits, hipStream_t stream) {
+    if (scene_runs_lean(s))  // the traversal kernel reads the queue's SOA slices itself (no gather pass into nnbvh_ray records)
+        return launch(s, 0, nullptr, max_rays, d_hits, nullptr, nullptr, nullptr, stream, w, d_size, ray_queue);
+    if (!grow(&w->d_in, &w->in_bytes, (size_t)max_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
+        return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_wf_gather(*ray_queue, WavefrontCount{max_rays, d_size}, w->d_in, s->n_cus * 8, stream),
+                "gather kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return launch(s, 0, w->d_in, max_rays, d_hits, nullptr, nullptr, nullptr, stream, w, d_size);
+}
+
 int nnbvh_wavefront_intersect_closest(nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
                                       const int32_t *d_size, const uint8_t *d_prim_class,
                                       int64_t n_prim_class, void *d_hits,
@@ -1187,14 +1212,10 @@ int nnbvh_wavefront_intersect_closest(nnbvh_scene *s, int32_t max_rays, const nn
         set_error("wavefront_intersect_closest: bad argument");
         return NNBVH_ERR_ARG;
     }
-    const nnbvh_work_queue *qs[6] = {&out->escaped, &out->hit_area_light, &out->basic_eval_material,
-                                     &out->universal_eval_material, &out->medium_sample,
-                                     &out->next_ray};
-    for (const nnbvh_work_queue *q : qs)
-        if (q->size && (q->capacity < 0 || (q->capacity > 0 && !q->items))) {
-            set_error("wavefront_intersect_closest: queue with a size counter but no item storage");
-            return NNBVH_ERR_ARG;
-        }
+    if (!queues_ok(out)) {
+        set_error("wavefront_intersect_closest: queue with a size counter but no item storage");
+        return NNBVH_ERR_ARG;
+    }
     if (max_rays == 0) return NNBVH_OK;
     DeviceGuard guard(s->device);
     if (!guard.ok) return NNBVH_ERR_DEVICE;
@@ -1204,17 +1225,7 @@ int nnbvh_wavefront_intersect_closest(nnbvh_scene *s, int32_t max_rays, const nn
     if (!w) return NNBVH_ERR_DEVICE;
     const WavefrontCount cnt{max_rays, d_size};
     const int max_blocks = s->n_cus * 8;
-    int rc;
-    if (scene_runs_lean(s)) {
-        // the traversal kernel reads the queue's SOA slices itself (no gather pass into nnbvh_ray records)
-        rc = launch(s, 0, nullptr, max_rays, d_hits, nullptr, nullptr, nullptr, stream, w, d_size, ray_queue);
-    } else {
-        if (!grow(&w->d_in, &w->in_bytes, (size_t)max_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
-            return NNBVH_ERR_DEVICE;
-        if (!hip_ok(launch_wf_gather(*ray_queue, cnt, w->d_in, max_blocks, stream), "gather kernel launch"))
-            return NNBVH_ERR_DEVICE;
-        rc = launch(s, 0, w->d_in, max_rays, d_hits, nullptr, nullptr, nullptr, stream, w, d_size);
-    }
+    const int rc = closest_trace(s, w, max_rays, ray_queue, d_size, d_hits, stream);
     if (rc != NNBVH_OK) return rc;
     if (!hip_ok(launch_wf_enqueue_closest(d_hits, cnt, ray_queue->has_medium, d_prim_class,
                                           (long)n_prim_class, *out, max_blocks, stream),
@@ -1268,6 +1279,36 @@ int nnbvh_wavefront_intersect_shadow(nnbvh_scene *s, int32_t max_rays, const nnb
 // IntersectShadow of one depth and IntersectClosest of the next (wavefront/integrator.cpp: TraceShadowRays(depth),
 // then the next iteration's IntersectClosest): both queues are filled by the shading of the same depth and neither
 // reads what the other writes, so they can share ONE launch (mode 3: one ramp-up and one drain instead of two).
+// the trace half of the one-launch form (the caller has checked that the scene allows it and holds its lock)
+static int closest_and_shadow_trace(nnbvh_scene *s, Workspace *w, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                                    const int32_t *d_size, void *d_hits, int32_t max_shadow_rays,
+                                    const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, uint8_t *occ,
+                                    hipStream_t stream) {
+    const int max_blocks = s->n_cus * 8;
+    // the (longer) closest-hit batch first: the shadow rays fill the lanes its tail leaves idle
+    const int32_t *sizes[2] = {d_size, d_shadow_size};
+    if (scene_runs_lean(s)) {  // both queues are read as the SOA slices they are
+        const nnbvh_batch batches[2] = {{NNBVH_BATCH_CLOSEST, 0, nullptr, max_rays, d_hits, nullptr, nullptr},
+                                        {NNBVH_BATCH_ANY, 0, nullptr, max_shadow_rays, occ, nullptr, nullptr}};
+        const nnbvh_ray_soa *soas[2] = {ray_queue, shadow_queue};
+        return launch_fused_batches(s, w, stream, batches, 2, sizes, soas);
+    }
+    const size_t closest_bytes = (size_t)max_rays * sizeof(nnbvh_ray);
+    if (!grow(&w->d_in, &w->in_bytes, closest_bytes + (size_t)max_shadow_rays * sizeof(nnbvh_ray),
+              "hipMalloc(wavefront rays)"))
+        return NNBVH_ERR_DEVICE;
+    void *closest_rays = w->d_in, *shadow_rays = (char *)w->d_in + closest_bytes;
+    if (!hip_ok(launch_wf_gather(*ray_queue, WavefrontCount{max_rays, d_size}, closest_rays, max_blocks, stream),
+                "gather kernel launch") ||
+        !hip_ok(launch_wf_gather(*shadow_queue, WavefrontCount{max_shadow_rays, d_shadow_size}, shadow_rays,
+                                 max_blocks, stream),
+                "gather kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    const nnbvh_batch batches[2] = {{NNBVH_BATCH_CLOSEST, 0, closest_rays, max_rays, d_hits, nullptr, nullptr},
+                                    {NNBVH_BATCH_ANY, 0, shadow_rays, max_shadow_rays, occ, nullptr, nullptr}};
+    return launch_fused_batches(s, w, stream, batches, 2, sizes);
+}
+
 int nnbvh_wavefront_intersect_closest_and_shadow(
     nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
     const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits, const nnbvh_closest_queues *out,
@@ -1289,13 +1330,10 @@ int nnbvh_wavefront_intersect_closest_and_shadow(
         set_error("wavefront_intersect_closest_and_shadow: bad argument");
         return NNBVH_ERR_ARG;
     }
-    const nnbvh_work_queue *qs[6] = {&out->escaped, &out->hit_area_light, &out->basic_eval_material,
-                                     &out->universal_eval_material, &out->medium_sample, &out->next_ray};
-    for (const nnbvh_work_queue *q : qs)
-        if (q->size && (q->capacity < 0 || (q->capacity > 0 && !q->items))) {
-            set_error("wavefront_intersect_closest_and_shadow: queue with a size counter but no item storage");
-            return NNBVH_ERR_ARG;
-        }
+    if (!queues_ok(out)) {
+        set_error("wavefront_intersect_closest_and_shadow: queue with a size counter but no item storage");
+        return NNBVH_ERR_ARG;
+    }
     DeviceGuard guard(s->device);
     if (!guard.ok) return NNBVH_ERR_DEVICE;
     std::lock_guard<std::mutex> lock(s->mu);
@@ -1310,27 +1348,8 @@ int nnbvh_wavefront_intersect_closest_and_shadow(
     }
     const WavefrontCount cnt{max_rays, d_size}, scnt{max_shadow_rays, d_shadow_size};
     const int max_blocks = s->n_cus * 8;
-    // the (longer) closest-hit batch first: the shadow rays fill the lanes its tail leaves idle
-    const int32_t *sizes[2] = {d_size, d_shadow_size};
-    int rc;
-    if (scene_runs_lean(s)) {  // both queues are read as the SOA slices they are
-        const nnbvh_batch batches[2] = {{NNBVH_BATCH_CLOSEST, 0, nullptr, max_rays, d_hits, nullptr, nullptr},
-                                        {NNBVH_BATCH_ANY, 0, nullptr, max_shadow_rays, occ, nullptr, nullptr}};
-        const nnbvh_ray_soa *soas[2] = {ray_queue, shadow_queue};
-        rc = launch_fused_batches(s, w, stream, batches, 2, sizes, soas);
-    } else {
-        const size_t closest_bytes = (size_t)max_rays * sizeof(nnbvh_ray);
-        if (!grow(&w->d_in, &w->in_bytes, closest_bytes + (size_t)max_shadow_rays * sizeof(nnbvh_ray),
-                  "hipMalloc(wavefront rays)"))
-            return NNBVH_ERR_DEVICE;
-        void *closest_rays = w->d_in, *shadow_rays = (char *)w->d_in + closest_bytes;
-        if (!hip_ok(launch_wf_gather(*ray_queue, cnt, closest_rays, max_blocks, stream), "gather kernel launch") ||
-            !hip_ok(launch_wf_gather(*shadow_queue, scnt, shadow_rays, max_blocks, stream), "gather kernel launch"))
-            return NNBVH_ERR_DEVICE;
-        const nnbvh_batch batches[2] = {{NNBVH_BATCH_CLOSEST, 0, closest_rays, max_rays, d_hits, nullptr, nullptr},
-                                        {NNBVH_BATCH_ANY, 0, shadow_rays, max_shadow_rays, occ, nullptr, nullptr}};
-        rc = launch_fused_batches(s, w, stream, batches, 2, sizes);
-    }
+    const int rc = closest_and_shadow_trace(s, w, max_rays, ray_queue, d_size, d_hits, max_shadow_rays, shadow_queue,
+                                            d_shadow_size, occ, stream);
     if (rc != NNBVH_OK) return rc;
     if (!hip_ok(launch_wf_enqueue_closest(d_hits, cnt, ray_queue->has_medium, d_prim_class, (long)n_prim_class, *out,
                                           max_blocks, stream),
@@ -1531,6 +1550,193 @@ int nnbvh_triangle_interactions(const nnbvh_shading_mesh *m, const nnbvh_ray *ra
     for (void *p : {d_rays, d_hits, d_out})
         if (p) (void)hipFree(p);
     return rc;
+}
+
+// ---- IntersectClosest with the work items (wavefront/intersect.h:16-156) --------------------------------
+static_assert(sizeof(nnbvh_item_slices) == 48 * sizeof(void *), "nnbvh_item_slices: 48 pointers");
+
+// every non-null slice must be one its queue's Push stores (include/nnbvh.h), and a wanted needs_host
+// queue needs storage like the others
+static bool items_ok(const nnbvh_closest_items *items, const char **why) {
+    enum { kPrim = 1, kPi = 2, kP = 4, kN = 8, kGeo = 16, kWo = 32, kUv = 64, kFace = 128, kTime = 256, kTMax = 512, kRay = 1024 };
+    struct Field {
+        size_t offset, count;
+        unsigned kind;
+    };
+#define F(name, kind) {offsetof(nnbvh_item_slices, name), sizeof(((nnbvh_item_slices *)0)->name) / sizeof(void *), kind}
+    static const Field fields[] = {F(prim, kPrim), F(pi, kPi), F(p, kP), F(n, kN), F(ns, kGeo), F(dpdu, kGeo),
+                                   F(dpdv, kGeo), F(dpdus, kGeo), F(dpdvs, kGeo), F(dndus, kGeo), F(dndvs, kGeo),
+                                   F(wo, kWo), F(uv, kUv), F(face_index, kFace), F(time, kTime), F(t_max, kTMax),
+                                   F(ray_o, kRay), F(ray_d, kRay)};
+#undef F
+    const unsigned material = kPrim | kPi | kN | kGeo | kWo | kUv | kFace | kTime;
+    const struct {
+        const nnbvh_item_slices *s;
+        unsigned allowed;
+        const char *name;
+    } queues[5] = {{&items->hit_area_light, kPrim | kP | kN | kWo | kUv, "hit_area_light"},
+                   {&items->basic_eval_material, material, "basic_eval_material"},
+                   {&items->universal_eval_material, material, "universal_eval_material"},
+                   {&items->medium_sample, material | kTMax, "medium_sample"},
+                   {&items->next_ray, kPrim | kRay | kTime, "next_ray"}};
+    for (const auto &q : queues) {
+        const char *base = (const char *)q.s;
+        for (const Field &f : fields) {
+            if (q.allowed & f.kind) continue;
+            for (size_t k = 0; k < f.count; ++k)
+                if (((void *const *)(base + f.offset))[k]) {
+                    *why = q.name;
+                    return false;
+                }
+        }
+    }
+    const nnbvh_work_queue &h = items->needs_host;
+    if (h.size && (h.capacity < 0 || (h.capacity > 0 && !h.items))) {
+        *why = "needs_host";
+        return false;
+    }
+    return true;
+}
+
+static bool items_args_ok(const char *fn, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *q,
+                          int64_t n_prim_class, const nnbvh_closest_queues *out, const nnbvh_closest_items *items) {
+    if (!m || max_rays < 0 || !out || !items || n_prim_class < 0 || (max_rays > 0 && !soa_ok(q))) {
+        set_error(std::string(fn) + ": bad argument");
+        return false;
+    }
+    if (!queues_ok(out)) {
+        set_error(std::string(fn) + ": queue with a size counter but no item storage");
+        return false;
+    }
+    const char *why = nullptr;
+    if (!items_ok(items, &why)) {
+        set_error(std::string(fn) + ": slice not carried by queue " + why + ", or needs_host without storage");
+        return false;
+    }
+    return true;
+}
+
+static int launch_items(const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                        const int32_t *d_size, const void *d_hits, const uint8_t *d_prim_class, int64_t n_prim_class,
+                        const nnbvh_closest_queues *out, const nnbvh_closest_items *items, hipStream_t stream) {
+    if (!hip_ok(launch_wf_enqueue_closest_items(m->d, d_hits, WavefrontCount{max_rays, d_size}, *ray_queue,
+                                                d_prim_class, (long)n_prim_class, *out, *items, m->n_cus * 8, stream),
+                "work-item enqueue kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_wavefront_enqueue_closest_items_device(const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                 const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                                 const void *d_hits, const uint8_t *d_prim_class,
+                                                 int64_t n_prim_class, const nnbvh_closest_queues *out,
+                                                 const nnbvh_closest_items *items, void *stream) {
+    if (!items_args_ok("wavefront_enqueue_closest_items_device", m, max_rays, ray_queue, n_prim_class, out, items))
+        return NNBVH_ERR_ARG;
+    if (max_rays > 0 && !d_hits) {
+        set_error("wavefront_enqueue_closest_items_device: no hit records");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0) return NNBVH_OK;
+    DeviceGuard guard(m->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    return launch_items(m, max_rays, ray_queue, d_size, d_hits, d_prim_class, n_prim_class, out, items,
+                        (hipStream_t)stream);
+}
+
+// d_hits == NULL: the records go to a per-stream workspace of the scene's
+static void *items_hits(Workspace *w, void *d_hits, int32_t max_rays) {
+    if (d_hits) return d_hits;
+    if (!grow(&w->d_hits, &w->hits_bytes, (size_t)max_rays * sizeof(nnbvh_hit), "hipMalloc(wavefront hits)"))
+        return nullptr;
+    return w->d_hits;
+}
+
+int nnbvh_wavefront_intersect_closest_items(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                            const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                            const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+                                            const nnbvh_closest_queues *out, const nnbvh_closest_items *items,
+                                            void *stream_) {
+    if (!s) {
+        set_error("wavefront_intersect_closest_items: bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    if (!items_args_ok("wavefront_intersect_closest_items", m, max_rays, ray_queue, n_prim_class, out, items))
+        return NNBVH_ERR_ARG;
+    if (s->device != m->device) {
+        set_error("wavefront_intersect_closest_items: scene and shading mesh live on different devices");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    hipStream_t stream = (hipStream_t)stream_;
+    Workspace *w = workspace_for(s, stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    void *hits = items_hits(w, d_hits, max_rays);
+    if (!hits) return NNBVH_ERR_DEVICE;
+    const int rc = closest_trace(s, w, max_rays, ray_queue, d_size, hits, stream);
+    if (rc != NNBVH_OK) return rc;
+    return launch_items(m, max_rays, ray_queue, d_size, hits, d_prim_class, n_prim_class, out, items, stream);
+}
+
+int nnbvh_wavefront_intersect_closest_and_shadow_items(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, int32_t max_shadow_rays,
+    const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld, const float *d_r_u,
+    const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_occluded,
+    void *stream_) {
+    if (!s) {
+        set_error("wavefront_intersect_closest_and_shadow_items: bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    if (!items_args_ok("wavefront_intersect_closest_and_shadow_items", m, max_rays, ray_queue, n_prim_class, out,
+                       items))
+        return NNBVH_ERR_ARG;
+    if (s->device != m->device) {
+        set_error("wavefront_intersect_closest_and_shadow_items: scene and shading mesh live on different devices");
+        return NNBVH_ERR_ARG;
+    }
+    nnbvh_batch probe[2] = {{NNBVH_BATCH_CLOSEST, 0, nullptr, max_rays, nullptr, nullptr, nullptr},
+                            {NNBVH_BATCH_ANY, 0, nullptr, max_shadow_rays, nullptr, nullptr, nullptr}};
+    if (max_rays <= 0 || max_shadow_rays <= 0 || !batches_fusable(s, probe, 2)) {
+        // the scenes and sizes the one-launch form does not cover: the two calls one after the other
+        int rc = nnbvh_wavefront_intersect_shadow(s, max_shadow_rays, shadow_queue, d_shadow_size, d_Ld, d_r_u, d_r_l,
+                                                  d_pixel_index, d_L, n_pixels, d_occluded, stream_);
+        if (rc != NNBVH_OK) return rc;
+        return nnbvh_wavefront_intersect_closest_items(s, m, max_rays, ray_queue, d_size, d_prim_class, n_prim_class,
+                                                       d_hits, out, items, stream_);
+    }
+    if (n_pixels < 0 || !soa_ok(shadow_queue) || !d_Ld || !d_r_u || !d_r_l || !d_pixel_index || !d_L) {
+        set_error("wavefront_intersect_closest_and_shadow_items: bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    hipStream_t stream = (hipStream_t)stream_;
+    Workspace *w = workspace_for(s, stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    uint8_t *occ = d_occluded;
+    if (!occ) {
+        if (!grow(&w->d_out, &w->out_bytes, (size_t)max_shadow_rays, "hipMalloc(wavefront occluded)"))
+            return NNBVH_ERR_DEVICE;
+        occ = (uint8_t *)w->d_out;
+    }
+    void *hits = items_hits(w, d_hits, max_rays);
+    if (!hits) return NNBVH_ERR_DEVICE;
+    int rc = closest_and_shadow_trace(s, w, max_rays, ray_queue, d_size, hits, max_shadow_rays, shadow_queue,
+                                      d_shadow_size, occ, stream);
+    if (rc != NNBVH_OK) return rc;
+    rc = launch_items(m, max_rays, ray_queue, d_size, hits, d_prim_class, n_prim_class, out, items, stream);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_wf_record_shadow(occ, WavefrontCount{max_shadow_rays, d_shadow_size}, d_Ld, d_r_u, d_r_l,
+                                        d_pixel_index, d_L, (long)n_pixels, s->n_cus * 8, stream),
+                "shadow record kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
 }
 
 // ---- IntersectShadowTr / IntersectOneRandom (wavefront/aggregate.cpp:70-116), media-free -------------

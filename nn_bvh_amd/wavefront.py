@@ -69,6 +69,66 @@ class RayQueue:
         return rec
 
 
+class ItemSlices:
+    """SOA slices of one work-item queue (nnbvh_item_slices): a device tensor per requested field, with
+    `capacity` rows (slot k belongs to the queue's items[k]).  fields: names of _lib.ITEM_FIELDS; "prim" and
+    "face_index" are int32 [capacity], the others float32 [components, capacity] (component c = slice c)."""
+
+    def __init__(self, capacity, fields, device):
+        self.capacity = int(capacity)
+        self.fields = {}
+        for name in fields:
+            comps = _lib.ITEM_FIELDS[name]
+            dtype = torch.int32 if name in ("prim", "face_index") else torch.float32
+            shape = (max(self.capacity, 1),) if comps == 1 else (comps, max(self.capacity, 1))
+            self.fields[name] = torch.empty(shape, dtype=dtype, device=device)
+
+    def __getitem__(self, name):
+        return self.fields[name]
+
+    def _wire(self, rec):
+        for name, t in self.fields.items():
+            if _lib.ITEM_FIELDS[name] == 1:
+                rec[name] = t.data_ptr()
+            else:
+                rec[name] = [t[c].data_ptr() for c in range(t.shape[0])]
+
+
+def _items_record(items, needs_host):
+    rec = np.zeros(1, _lib.CLOSEST_ITEMS_DTYPE)
+    for name, sl in (items or {}).items():
+        assert name in _lib.ITEM_QUEUES, f"no work-item slices for queue {name}"
+        sl._wire(rec[name][0:1])
+    if needs_host is not None:
+        needs_host._wire(rec["needs_host"][0:1])
+    return rec
+
+
+def _queues_record(queues):
+    qrec = np.zeros(1, _lib.CLOSEST_QUEUES_DTYPE)
+    for name, q in queues.items():
+        assert name in CLOSEST_QUEUES, name
+        if q is not None:
+            q._wire(qrec[name][0:1])
+    return qrec
+
+
+def enqueue_closest_items(shading_mesh, max_rays, ray_queue, hits, prim_class=None, items=None, needs_host=None,
+                          **queues):
+    """nnbvh_wavefront_enqueue_closest_items_device: IntersectClosest's enqueue with the work items for hit
+    records from any source (hits: device tensor of HIT_DTYPE rows).  queues: WorkQueues by
+    _lib.CLOSEST_QUEUES name; items: ItemSlices by _lib.ITEM_QUEUES name; needs_host: WorkQueue or None."""
+    dev = ray_queue.o.device
+    pc = prim_class
+    # the records must outlive the call: ptr() does not keep its array alive
+    soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
+    check(_lib.lib().nnbvh_wavefront_enqueue_closest_items_device(
+        shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), hits.data_ptr(),
+        pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), ptr(qrec), ptr(irec),
+        torch.cuda.current_stream(dev).cuda_stream),
+        "nnbvh_wavefront_enqueue_closest_items_device")
+
+
 class WavefrontAggregate:
     """IntersectClosest / IntersectShadow of wavefront/integrator.h:32-54 on one BVHAggregate.
 
@@ -153,6 +213,44 @@ class WavefrontAggregate:
             r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0],
             occluded.data_ptr() if occluded is not None else None,
             torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_closest_and_shadow")
+        return hits
+
+    def IntersectClosestItems(self, max_rays, ray_queue, shading_mesh, items=None, needs_host=None, hits=None,
+                              **queues):
+        """IntersectClosest with the work items themselves (nnbvh_wavefront_intersect_closest_items): the index
+        queues as IntersectClosest fills them (keyword arguments by _lib.CLOSEST_QUEUES name), and for the queues
+        in `items` (ItemSlices by _lib.ITEM_QUEUES name) the SOA payload of each pushed item, computed from
+        shading_mesh.  Voided records and hits the mesh cannot finish go to needs_host (a WorkQueue, or None to
+        drop them).  hits: optional device tensor for the hit records (else a library workspace holds them).
+        Returns hits."""
+        pc = self.prim_class
+        soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
+        check(_lib.lib().nnbvh_wavefront_intersect_closest_items(
+            self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
+            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(),
+            hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec),
+            torch.cuda.current_stream(self.device).cuda_stream),
+            "nnbvh_wavefront_intersect_closest_items")
+        return hits
+
+    def IntersectClosestAndShadowItems(self, max_rays, ray_queue, shading_mesh, max_shadow_rays, shadow_queue, Ld,
+                                       r_u, r_l, pixel_index, L, items=None, needs_host=None, hits=None,
+                                       occluded=None, **queues):
+        """IntersectClosestAndShadow with the closest side's work items (see IntersectClosestItems)."""
+        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
+        for t in (Ld, r_u, r_l, L):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
+        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        pc = self.prim_class
+        soa, ssoa = ray_queue._wire(), shadow_queue._wire()
+        qrec, irec = _queues_record(queues), _items_record(items, needs_host)
+        check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow_items(
+            self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
+            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(),
+            hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec), int(max_shadow_rays), ptr(ssoa),
+            shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(),
+            L.data_ptr(), L.shape[0], occluded.data_ptr() if occluded is not None else None,
+            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_closest_and_shadow_items")
         return hits
 
     def IntersectShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None):
