@@ -125,7 +125,8 @@ typedef struct nnbvh_hit {
     float b0, b1, b2; /* triangle barycentrics; patch: b0 = u, b1 = v, b2 = 0 */
     int32_t nodes_visited;
     int32_t prim_tests;
-    int32_t instance; /* -1: the ray reached a host-only primitive: record void, re-trace on the CPU;
+    int32_t instance; /* -1: the ray reached a host-only primitive: record void, re-trace on the CPU
+                         (or use nnbvh_intersect_closest_candidates, which lists those primitives);
                          0: hit in the top-level tree (or miss); k + 1: inside instance k, and
                          then `prim` is the child tree's primitive id and t, b* are those of the
                          instance-space ray, exactly what TransformedPrimitive::Intersect returns */
@@ -298,6 +299,66 @@ int nnbvh_intersect_closest_device(nnbvh_scene *s, const void *d_rays, int64_t n
                                    void *stream);
 int nnbvh_intersect_any_device(nnbvh_scene *s, const void *d_rays, int64_t n, void *d_occluded,
                                void *d_nodes_visited, void *d_prim_tests, void *stream);
+
+/* ---- host-only primitives as candidates instead of void records -----------------------
+ * The plain calls void a ray that reaches an NNBVH_PRIM_HOST primitive (instance == -1 / occluded == 2) and the
+ * caller re-traces it through a CPU aggregate of the whole scene.  A host-only primitive never changes the device's
+ * tMax, so the device walk of such a ray is the walk that skips it, and its record already holds the closest DEVICE
+ * hit.  These calls return that record with its real instance, plus the list of host-only primitives the ray
+ * reached, in traversal order; the caller tests those few shapes itself (pbrt: primitives[id].Intersect(ray, tMax))
+ * and merges them with the device hit by the rule below.  No CPU BVH is needed.
+ *
+ * Per ray i, K = capacity:
+ *   count[i]     0..K candidates; -1: more than K (record void, instance == -1, as the plain call);
+ *                -2: an alpha re-trace voided the ray (record void as the plain call; candidates cannot fix it)
+ *   before[i]    closest hit only: how many of the candidates came before the device hit that stands (0 when there
+ *                is no device hit, or when every candidate came after it)
+ *   prim[i*K+j]  nnbvh_prim.id of candidate j < count[i] (the value nnbvh_hit.prim would carry)
+ *   instance[i*K+j]  0 = top-level tree, k + 1 = inside instance k: the caller transforms the render-space ray
+ *                into the instance's space itself, as TransformedPrimitive::Intersect does
+ * Entries of prim / instance beyond count[i] are left as they were.  A ray that meets no host-only primitive has
+ * count 0 and exactly the plain call's record.  With count > 0 the record's nodes_visited and prim_tests count
+ * the device walk, not the reference's (which also tests the host shapes: "exact counts" is a follow-up).
+ * Any hit: occluded 1 (a device primitive occludes; the list may be partial), 0 (no occluder, no candidate),
+ * 2 with count 1..K (the caller tests the candidates with ray.tmax), 2 with count < 0 (void, as the plain call).
+ *
+ * The merge rule (closest hit) replays the reference's order of acceptance (aggregates.cpp:529-624: a later hit
+ * replaces the earlier one and sets tMax = tHit):
+ *   1. tMax = ray.tmax;
+ *   2. test candidates 0 .. before-1 with the current tMax; each hit replaces the result and sets tMax;
+ *   3. the device hit (prim >= 0): if no candidate hit in step 2 it stands unchanged; else it is accepted iff
+ *      t <= tMax for a triangle (Triangle::Intersect rejects only tScaled > tMax * det, shapes.cpp:239-242, so an
+ *      equal t is accepted) and iff t < tMax for a bilinear patch (IntersectBilinearPatch rejects t >= tMax,
+ *      shapes.h:1344).  The record does not carry the kind: the caller looks `prim` up in its primitive table.
+ *      The comparison on t stands in for the triangle's test on tScaled: both agree except when t is within an
+ *      ulp or two of tMax (e.g. a duplicated triangle; DESIGN.md "Host-only primitives as candidates");
+ *   4. test candidates before .. count-1 as in step 2.
+ * Any hit: occluded = device occluded || some candidate hits with ray.tmax.
+ *
+ * Scope: BVH scenes (flat, two-level static and animated, with or without alpha-tested kinds), closest hit and
+ * occlusion-only any hit.  Follow-ups, not covered: shape math for spheres / disks / cylinders on the device,
+ * nnbvh_trace_batches_device (mode-3 fused batches), the wavefront queue entry points (their needs_host queue
+ * is unchanged), kd-tree scenes, exact node / test counts for rays with candidates.
+ * NNBVH_ERR_ARG for capacity outside 1..16, a NULL count / prim / instance, or a NULL before on a closest call. */
+typedef struct nnbvh_host_candidates {
+    int32_t capacity;   /* K, 1..16 */
+    int32_t *count;     /* int32[n]: 0..K candidates; -1 more than K; -2 alpha re-trace: record void */
+    int32_t *before;    /* int32[n], closest only (NULL for any-hit): candidates met before the device hit */
+    int32_t *prim;      /* int32[n * K]: nnbvh_prim.id of each candidate, traversal order */
+    int32_t *instance;  /* int32[n * K]: 0 = top level, k + 1 = inside instance k */
+} nnbvh_host_candidates;
+
+/* device buffers (asynchronous on `stream`; the pointers in `c` are device pointers too) */
+int nnbvh_intersect_closest_candidates_device(nnbvh_scene *s, const void *d_rays, int64_t n, void *d_hits,
+                                              const nnbvh_host_candidates *c, void *stream);
+int nnbvh_intersect_any_candidates_device(nnbvh_scene *s, const void *d_rays, int64_t n, void *d_occluded,
+                                          const nnbvh_host_candidates *c, void *stream);
+/* host buffers (the pointers in `c` are host pointers): a plain synchronous staged copy, not the three-stream
+ * pipeline of nnbvh_intersect_closest */
+int nnbvh_intersect_closest_candidates(nnbvh_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits,
+                                       const nnbvh_host_candidates *c);
+int nnbvh_intersect_any_candidates(nnbvh_scene *s, const nnbvh_ray *rays, int64_t n, uint8_t *occluded,
+                                   const nnbvh_host_candidates *c);
 
 /* ---- several independent batches at once --------------------------------------------------
  * One call traces n_batches independent ray batches (e.g. the closest-hit queue and the

@@ -23,6 +23,7 @@
 // pbrt's ParallelFor2D (util/parallel.cpp:301-330) that are inside Intersect() at the same moment are
 // traced as ONE batch.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +34,7 @@
 #include <mutex>
 #include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "nnbvh.h"
@@ -65,6 +67,23 @@ struct HitRecord {
 // textured alpha ...) lay on its way, so neither "hit", "miss" nor "occluded" is known and the caller must
 // re-trace it on the CPU (nnbvh_hit.instance == -1 / occluded == 2).  The single-ray adapters report it
 // through the optional `needsHost` out-parameter; without one such a ray is fatal, never a silent answer.
+//
+// The overloads that take a `hostIntersect` callable do without the CPU re-trace: the device lists the host-only
+// primitives each ray reached (nnbvh_host_candidates) and the adapter asks the callable about those few, merging
+// the answers with the device hit by the rule of include/nnbvh.h.  hostIntersect(prim, instance, ray, tMax) ->
+// std::optional<HostHit> is the embedder's primitives[prim].Intersect(ray, tMax) (prim = nnbvh_prim.id); for
+// instance > 0 the render-space ray must be taken into instance instance - 1's space, as TransformedPrimitive
+// does.  A ray the list cannot settle (more candidates than the capacity, an alpha re-trace: count < 0) goes the
+// needsHost / fatal way above.
+struct HostHit {
+    float tHit;
+    float b0 = 0, b1 = 0, b2 = 0;  // whatever the embedder wants back for its own shapes
+};
+// the merged closest hit and which primitive won it
+struct ResolvedHit {
+    HitRecord hit;      // prim / instance name the winner, device primitive or host candidate
+    bool host = false;  // true: a host candidate (the embedder's shape) won
+};
 
 class HipBVHAggregate {
   public:
@@ -103,6 +122,7 @@ class HipBVHAggregate {
             tagged = prims;
             for (size_t i = 0; i < tagged.size(); ++i) tagged[i].id = (int32_t)i;
         }
+        note_patches(prims.data(), (int)prims.size());
         const nnbvh_prim *in = primAlpha ? tagged.data() : prims.data();
         nnbvh_build *b = primBounds
                              ? nnbvh_build_create_with_bounds(in, (int)prims.size(), verts.data(),
@@ -150,6 +170,7 @@ class HipBVHAggregate {
                                                           primAlpha, nVerts, device)
                      : nnbvh_scene_create(nodes, nNodes, orderedPrims, nPrims, verts, nVerts, device);
         if (!scene_) fatal("HipBVHAggregate: scene_create");
+        note_patches(orderedPrims, nPrims);
     }
 
     HipBVHAggregate(const HipBVHAggregate &) = delete;
@@ -187,6 +208,81 @@ class HipBVHAggregate {
         if (occ == 2 && !needsHost)
             fatal("IntersectP: the ray met a host-only primitive (pass needsHost and re-trace it on the CPU)");
         return occ == 1;
+    }
+
+    // ---- ... with host-only primitives as candidates (no CPU aggregate needed) -----------
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    std::optional<ResolvedHit> Intersect(const Ray &ray, float tMax, F &&hostIntersect, bool *needsHost = nullptr,
+                                         int capacity = 8) const {
+        std::optional<ResolvedHit> out;
+        uint8_t voided = 0;
+        nnbvh_ray r = wire(ray, tMax);
+        IntersectClosest(&r, 1, &out, hostIntersect, needsHost ? &voided : nullptr, capacity);
+        if (needsHost) *needsHost = voided != 0;
+        return out;
+    }
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    bool IntersectP(const Ray &ray, float tMax, F &&hostIntersect, bool *needsHost = nullptr, int capacity = 8) const {
+        uint8_t occ = 0, voided = 0;
+        nnbvh_ray r = wire(ray, tMax);
+        IntersectShadow(&r, 1, &occ, hostIntersect, needsHost ? &voided : nullptr, capacity);
+        if (needsHost) *needsHost = voided != 0;
+        return occ != 0;
+    }
+    // batches (host buffers; synchronous).  needsHost (nullable, uint8_t[n]): 1 for a ray the candidates cannot
+    // settle (its hits[i] / occluded[i] is then empty / 0); without it such a ray is fatal
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    void IntersectClosest(const nnbvh_ray *rays, int64_t n, std::optional<ResolvedHit> *hits, F &&hostIntersect,
+                          uint8_t *needsHost = nullptr, int capacity = 8) const {
+        std::vector<nnbvh_hit> rec((size_t)n);
+        std::vector<int32_t> count((size_t)n), before((size_t)n), prim((size_t)n * capacity), inst((size_t)n * capacity);
+        nnbvh_host_candidates c{capacity, count.data(), before.data(), prim.data(), inst.data()};
+        if (nnbvh_intersect_closest_candidates(scene_, rays, n, rec.data(), &c) != NNBVH_OK) fatal("IntersectClosest");
+        for (int64_t i = 0; i < n; ++i) {
+            const size_t at = (size_t)i * capacity;
+            hits[i].reset();
+            if (!settled(count[i], needsHost ? needsHost + i : nullptr, "IntersectClosest")) continue;
+            const Ray ray = unwire(rays[i]);
+            float tMax = rays[i].tmax;
+            auto test = [&](int j) {  // a hit replaces the result and sets tMax (aggregates.cpp:529-579)
+                if (std::optional<HostHit> hh = hostIntersect(prim[at + j], inst[at + j], ray, tMax)) {
+                    hits[i] = ResolvedHit{HitRecord{prim[at + j], hh->tHit, hh->b0, hh->b1, hh->b2, inst[at + j]}, true};
+                    tMax = hh->tHit;
+                }
+            };
+            for (int j = 0; j < before[i]; ++j) test(j);
+            const nnbvh_hit &h = rec[(size_t)i];
+            if (h.prim >= 0) {
+                // after a candidate's hit: accepted iff t <= tMax (triangle) / t < tMax (patch), include/nnbvh.h
+                const bool patch = std::binary_search(patchIds_.begin(), patchIds_.end(), h.prim);
+                if (!hits[i] || (patch ? h.t < tMax : h.t <= tMax)) {
+                    hits[i] = ResolvedHit{HitRecord{h.prim, h.t, h.b0, h.b1, h.b2, h.instance}, false};
+                    tMax = h.t;
+                }
+            }
+            for (int j = before[i]; j < count[i]; ++j) test(j);
+        }
+    }
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    void IntersectShadow(const nnbvh_ray *rays, int64_t n, uint8_t *occluded, F &&hostIntersect,
+                         uint8_t *needsHost = nullptr, int capacity = 8) const {
+        std::vector<int32_t> count((size_t)n), prim((size_t)n * capacity), inst((size_t)n * capacity);
+        nnbvh_host_candidates c{capacity, count.data(), nullptr, prim.data(), inst.data()};
+        if (nnbvh_intersect_any_candidates(scene_, rays, n, occluded, &c) != NNBVH_OK) fatal("IntersectShadow");
+        for (int64_t i = 0; i < n; ++i) {
+            if (needsHost) needsHost[i] = 0;
+            if (occluded[i] != 2) continue;
+            occluded[i] = 0;
+            if (!settled(count[i], needsHost ? needsHost + i : nullptr, "IntersectShadow")) continue;
+            const Ray ray = unwire(rays[i]);
+            for (int j = 0; j < count[i] && !occluded[i]; ++j)
+                occluded[i] = hostIntersect(prim[(size_t)i * capacity + j], inst[(size_t)i * capacity + j], ray,
+                                            rays[i].tmax).has_value();
+        }
     }
 
     // ---- WavefrontAggregate-shaped batches (host buffers; synchronous) -------------------
@@ -305,7 +401,23 @@ class HipBVHAggregate {
     static nnbvh_ray wire(const Ray &ray, float tMax) {
         return nnbvh_ray{{ray.o.x, ray.o.y, ray.o.z}, tMax, {ray.d.x, ray.d.y, ray.d.z}, ray.time};
     }
+    static Ray unwire(const nnbvh_ray &r) { return Ray{{r.o[0], r.o[1], r.o[2]}, {r.d[0], r.d[1], r.d[2]}, r.time}; }
+    // count < 0: the candidates cannot settle the ray (more than the capacity, or an alpha re-trace)
+    static bool settled(int32_t count, uint8_t *needsHost, const char *what) {
+        if (needsHost) *needsHost = count < 0;
+        if (count < 0 && !needsHost)
+            fatal(std::string(what) + ": the ray's host candidates cannot settle it (pass needsHost and re-trace it on the CPU)");
+        return count >= 0;
+    }
+    // the ids of the bilinear patches: the merge rule's comparison for a device hit depends on its kind
+    void note_patches(const nnbvh_prim *prims, int n) {
+        for (int i = 0; i < n; ++i)
+            if (prims[i].kind == NNBVH_PRIM_BILINEAR_PATCH || (prims[i].kind >= NNBVH_PRIM_ALPHA_PATCH && prims[i].kind <= NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH_FLIPPED))
+                patchIds_.push_back(prims[i].id);
+        std::sort(patchIds_.begin(), patchIds_.end());
+    }
     nnbvh_scene *scene_ = nullptr;
+    std::vector<int32_t> patchIds_;
 };
 
 // Triangle:: / BilinearPatch::InteractionFromIntersection (shapes.h:884-1010, 1396-1489) for batches of hit records: the mesh

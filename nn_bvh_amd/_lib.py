@@ -80,7 +80,18 @@ EXPORTS = [
     "nnbvh_wavefront_intersect_shadow_tr", "nnbvh_wavefront_intersect_one_random",
     "nnbvh_scene_create_instanced_animated", "nnbvh_wavefront_enqueue_closest_items_device",
     "nnbvh_wavefront_intersect_closest_items", "nnbvh_wavefront_intersect_closest_and_shadow_items",
+    "nnbvh_intersect_closest_candidates", "nnbvh_intersect_any_candidates",
+    "nnbvh_intersect_closest_candidates_device", "nnbvh_intersect_any_candidates_device",
 ]
+
+
+class HostCandidates(ctypes.Structure):
+    """nnbvh_host_candidates (include/nnbvh.h): host or device pointers, as the entry point expects."""
+    _fields_ = [("capacity", ctypes.c_int32), ("count", ctypes.c_void_p), ("before", ctypes.c_void_p),
+                ("prim", ctypes.c_void_p), ("instance", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(HostCandidates) == 40
 
 _lib = None
 
@@ -244,6 +255,15 @@ def lib():
     L.nnbvh_wavefront_intersect_shadow_tr.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp]
     L.nnbvh_wavefront_intersect_one_random.restype = i32
     L.nnbvh_wavefront_intersect_one_random.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    hc = ctypes.POINTER(HostCandidates)
+    L.nnbvh_intersect_closest_candidates.restype = i32
+    L.nnbvh_intersect_closest_candidates.argtypes = [vp, vp, i64, vp, hc]
+    L.nnbvh_intersect_any_candidates.restype = i32
+    L.nnbvh_intersect_any_candidates.argtypes = [vp, vp, i64, vp, hc]
+    L.nnbvh_intersect_closest_candidates_device.restype = i32
+    L.nnbvh_intersect_closest_candidates_device.argtypes = [vp, vp, i64, vp, hc, vp]
+    L.nnbvh_intersect_any_candidates_device.restype = i32
+    L.nnbvh_intersect_any_candidates_device.argtypes = [vp, vp, i64, vp, hc, vp]
     L.nnbvh_scene_sched_stats.restype = i32
     L.nnbvh_scene_sched_stats.argtypes = [vp, vp, i32]
     _lib = L

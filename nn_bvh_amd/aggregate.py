@@ -298,3 +298,145 @@ class BVHAggregate:
     def intersect_p_device(self, d_rays, d_occ, n, d_visited=None, d_tests=None, stream=0):
         check(_lib.lib().nnbvh_intersect_any_device(self._h, d_rays, n, d_occ, d_visited, d_tests,
                                                     stream), "nnbvh_intersect_any_device")
+
+    # -- host-only primitives as candidates (include/nnbvh.h nnbvh_host_candidates) -----------
+    def intersect_with_host_candidates(self, rays, capacity=8):
+        """Closest hit that lists the host-only primitives each ray reached instead of voiding it.
+        Returns (hits, cands): hits as Intersect (the closest DEVICE hit, its real instance unless
+        cands["count"] < 0), cands a candidates_dtype(capacity) array; merge with resolve_host_candidates."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        cnt, before, prim, inst = _candidate_arrays(len(rays), capacity)
+        c = _lib.HostCandidates(int(capacity), cnt.ctypes.data, before.ctypes.data, prim.ctypes.data, inst.ctypes.data)
+        check(_lib.lib().nnbvh_intersect_closest_candidates(self._h, ptr(rays), len(rays), ptr(hits), ctypes.byref(c)),
+              "nnbvh_intersect_closest_candidates")
+        return hits, _pack_candidates(cnt, before, prim, inst)
+
+    def intersect_p_with_host_candidates(self, rays, capacity=8):
+        """Occlusion-only any hit with candidates -> (occluded uint8, cands); cands["before"] is 0.
+        occluded 2 with count > 0: test the candidates (resolve_host_candidates_any)."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        occ = np.zeros(len(rays), np.uint8)
+        cnt, before, prim, inst = _candidate_arrays(len(rays), capacity)
+        c = _lib.HostCandidates(int(capacity), cnt.ctypes.data, None, prim.ctypes.data, inst.ctypes.data)
+        check(_lib.lib().nnbvh_intersect_any_candidates(self._h, ptr(rays), len(rays), ptr(occ), ctypes.byref(c)),
+              "nnbvh_intersect_any_candidates")
+        return occ, _pack_candidates(cnt, before, prim, inst)
+
+    def intersect_candidates_device(self, d_rays, d_hits, n, capacity, d_count, d_before, d_prim, d_instance,
+                                    stream=0):
+        """intersect_device with candidates: device pointers int32[n] count / before, int32[n * capacity]
+        prim / instance (nnbvh_intersect_closest_candidates_device)."""
+        c = _lib.HostCandidates(int(capacity), d_count, d_before, d_prim, d_instance)
+        check(_lib.lib().nnbvh_intersect_closest_candidates_device(self._h, d_rays, n, d_hits, ctypes.byref(c), stream),
+              "nnbvh_intersect_closest_candidates_device")
+
+    def intersect_p_candidates_device(self, d_rays, d_occ, n, capacity, d_count, d_prim, d_instance, stream=0):
+        c = _lib.HostCandidates(int(capacity), d_count, None, d_prim, d_instance)
+        check(_lib.lib().nnbvh_intersect_any_candidates_device(self._h, d_rays, n, d_occ, ctypes.byref(c), stream),
+              "nnbvh_intersect_any_candidates_device")
+
+
+def candidates_dtype(capacity):
+    """Per-ray host candidates: count (0..K; -1 more than K; -2 alpha re-trace: void), before (closest hit:
+    candidates met before the device hit), prim[K] (nnbvh_prim.id), instance[K] (0 top level, k + 1 instance k)."""
+    return np.dtype([("count", "<i4"), ("before", "<i4"), ("prim", "<i4", capacity), ("instance", "<i4", capacity)])
+
+
+def _candidate_arrays(n, capacity):
+    if not 1 <= int(capacity) <= 16:
+        raise NNBVHError(f"host candidates: capacity must be 1..16, not {capacity}")
+    k = int(capacity)
+    return (np.zeros(n, np.int32), np.zeros(n, np.int32), np.full((n, k), -1, np.int32),
+            np.full((n, k), -1, np.int32))
+
+
+def _pack_candidates(cnt, before, prim, inst):
+    out = np.zeros(len(cnt), candidates_dtype(prim.shape[1]))
+    out["count"], out["before"], out["prim"], out["instance"] = cnt, before, prim, inst
+    return out
+
+
+def _test_candidates(rays, res, tmax, cands, host_intersect, lo, hi):
+    """Test candidate columns j with lo[i] <= j < hi[i] in order; a hit replaces the result and sets tMax.
+    Returns which rays accepted a candidate."""
+    took = np.zeros(len(rays), bool)
+    for j in range(cands["prim"].shape[1]):
+        idx = np.nonzero((lo <= j) & (j < hi))[0]
+        if len(idx) == 0:
+            continue
+        prim, inst = cands["prim"][idx, j], cands["instance"][idx, j]
+        hit, t, b0, b1, b2 = (np.asarray(x) for x in host_intersect(idx, prim, inst, tmax[idx].copy()))
+        w = idx[hit.astype(bool)]
+        h = hit.astype(bool)
+        res["prim"][w], res["instance"][w] = prim[h], inst[h]
+        res["t"][w], res["b0"][w], res["b1"][w], res["b2"][w] = t[h], b0[h], b1[h], b2[h]
+        tmax[w] = t[h]
+        took[w] = True
+    return took
+
+
+def resolve_host_candidates(rays, hits, cands, host_intersect, kind=None, device_intersect=None):
+    """Merge the device hit with the caller's tests of the host candidates (the rule of include/nnbvh.h):
+    candidates 0 .. before-1, then the device hit, then candidates before .. count-1, each accepted against the
+    running tMax and replacing the result.
+
+    host_intersect(ray_idx, prim, instance, tmax) -> (hit, t, b0, b1, b2): vectorised over one candidate column
+    (arrays of the same length); the ray is rays[ray_idx] in render space, transforming it into an instance's
+    space is the callback's job (as TransformedPrimitive's).
+    kind: array indexed by nnbvh_prim.id (the device primitives' kinds, NNBVH_PRIM_*); a device hit after an
+    accepted candidate stands iff t <= tMax (triangle kinds) or t < tMax (bilinear patch kinds).  None = every
+    device primitive is a triangle.
+    device_intersect: optional callback like host_intersect for the DEVICE primitives; when given, a device hit
+    after an accepted candidate is re-tested with it at the reduced tMax instead of being compared on t — the
+    reference's own test, exact also where t lies within an ulp of tMax.
+    Rays with count < 0 stay void (instance -1).  nodes_visited / prim_tests are the device walk's."""
+    rays = np.asarray(rays)
+    res = hits.copy()
+    cnt, before = cands["count"], cands["before"]
+    ok = cnt >= 0
+    tmax = rays["tmax"].astype(np.float32).copy()
+    first = np.where(ok, before, 0)
+    # the running result starts as a miss; the device hit is inserted between the two candidate runs
+    res["prim"][ok], res["t"][ok], res["instance"][ok] = -1, tmax[ok], 0
+    res["b0"][ok] = res["b1"][ok] = res["b2"][ok] = 0
+    took = _test_candidates(rays, res, tmax, cands, host_intersect, np.zeros_like(first), first)
+    dev = ok & (hits["prim"] >= 0)
+    accept = dev & ~took
+    ask = np.nonzero(dev & took)[0]
+    if len(ask):
+        t = hits["t"][ask]
+        if device_intersect is not None:
+            acc = np.asarray(device_intersect(ask, hits["prim"][ask], hits["instance"][ask], tmax[ask].copy())[0])
+            acc = acc.astype(bool)
+        else:
+            patch = np.zeros(len(ask), bool)
+            if kind is not None:
+                k = np.asarray(kind)[hits["prim"][ask]]
+                patch = (k == 1) | ((k >= 8) & (k <= 15))
+            acc = np.where(patch, t < tmax[ask], t <= tmax[ask])
+        accept[ask[acc]] = True
+    w = np.nonzero(accept)[0]
+    for f in ("prim", "t", "b0", "b1", "b2", "instance"):
+        res[f][w] = hits[f][w]
+    tmax[w] = hits["t"][w]
+    _test_candidates(rays, res, tmax, cands, host_intersect, first, np.where(ok, cnt, 0))
+    return res
+
+
+def resolve_host_candidates_any(rays, occluded, cands, host_intersect):
+    """Any hit: occluded = device occluded or some candidate hits with ray.tmax (host_intersect as in
+    resolve_host_candidates).  Rays with occluded 2 and count < 0 stay 2 (void)."""
+    rays = np.asarray(rays)
+    res = np.asarray(occluded).copy()
+    cnt = cands["count"]
+    todo = (res == 2) & (cnt > 0)
+    res[todo] = 0
+    for j in range(cands["prim"].shape[1]):
+        idx = np.nonzero(todo & (j < cnt) & (res == 0))[0]
+        if len(idx) == 0:
+            continue
+        hit = np.asarray(host_intersect(idx, cands["prim"][idx, j], cands["instance"][idx, j],
+                                        rays["tmax"][idx].astype(np.float32))[0]).astype(bool)
+        res[idx[hit]] = 1
+    return res

@@ -821,13 +821,14 @@ static int scene_prim_min(const nnbvh_scene *s) {
     return end < (1LL << 32) ? s->prim_min : 0;
 }
 
-static int grid_blocks(nnbvh_scene *s, int mode) {
+static int grid_blocks(nnbvh_scene *s, int mode, int candidates = 0) {
     int per_cu = s->blocks_per_cu;
     if (per_cu <= 0) {
         TraceParams dummy{};
         dummy.hasHostPrims = s->has_host_prims;  // selects between the lean and the general instances
         dummy.anim = s->d_anim;                  // ... and between the static- and the animated-instance ones
         dummy.fits32 = scene_fits32(s);
+        dummy.hcCap = candidates;                // ... and the candidate-mode twins
         int occ = 0;
         if (launch_trace(mode, dummy, s->window, s->instanced, patch_bits(s), 0, nullptr, &occ) != hipSuccess ||
             occ <= 0)
@@ -955,9 +956,12 @@ static Workspace *workspace_for(nnbvh_scene *s, hipStream_t stream) {
     return &(s->workspaces[stream] = w);
 }
 
+// hc (modes 0 / 2, nullable): candidate mode; its count (and before) arrays are zeroed here, and scenes with
+// host-only primitives run the HOSTC instances, which fill them in; other scenes run the plain instances
 static int launch(nnbvh_scene *s, int mode, const void *d_rays, int64_t n, void *d_hits,
                   void *d_occ, void *d_vis, void *d_tests, hipStream_t stream, Workspace *w,
-                  const int32_t *d_n = nullptr, const nnbvh_ray_soa *soa = nullptr) {
+                  const int32_t *d_n = nullptr, const nnbvh_ray_soa *soa = nullptr,
+                  const nnbvh_host_candidates *hc = nullptr) {
     TraceParams p{};
     if (soa) p.soa = *soa;  // d_rays == nullptr: the kernel reads the queue's SOA slices itself
     p.wide = s->d_wide;
@@ -987,10 +991,23 @@ static int launch(nnbvh_scene *s, int mode, const void *d_rays, int64_t n, void 
     p.anim = s->d_anim;
     p.nBatches = 0;
     p.anyMask = 0;
+    if (hc) {
+        if (!hip_ok(hipMemsetAsync(hc->count, 0, (size_t)n * sizeof(int32_t), stream), "hipMemsetAsync(count)") ||
+            (hc->before && !hip_ok(hipMemsetAsync(hc->before, 0, (size_t)n * sizeof(int32_t), stream),
+                                   "hipMemsetAsync(before)")))
+            return NNBVH_ERR_DEVICE;
+        if (s->has_host_prims) {
+            p.hcCap = hc->capacity;
+            p.hcCount = hc->count;
+            p.hcBefore = hc->before;
+            p.hcPrim = hc->prim;
+            p.hcInst = hc->instance;
+        }
+    }
     if (!hip_ok(launch_zero_queue(w->queue, kMaxQueues * kQueueStrideWords, stream), "queue reset launch"))
         return NNBVH_ERR_DEVICE;
     // never launch more threads than there are rays to start with (tiny batches)
-    int blocks = grid_blocks(s, mode);
+    int blocks = grid_blocks(s, mode, p.hcCap);
     const int64_t need = (n + kBlockThreads - 1) / kBlockThreads;
     if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
     if (!hip_ok(launch_trace(mode, p, s->window, s->instanced, patch_bits(s), blocks, stream, nullptr),
@@ -1054,6 +1071,104 @@ int nnbvh_intersect_any_device(nnbvh_scene *s, const void *d_rays, int64_t n, vo
     const int mode = (d_nodes_visited || d_prim_tests) ? 1 : 2;
     return launch(s, mode, d_rays, n, nullptr, d_occluded, d_nodes_visited, d_prim_tests,
                   (hipStream_t)stream, w);
+}
+
+// ---- host-only primitives as candidates (include/nnbvh.h) ----------------------------------------------------
+static bool candidates_ok(const char *fn, nnbvh_scene *s, int64_t n, const void *rays, const void *out,
+                          const nnbvh_host_candidates *c, bool closest) {
+    const char *why = nullptr;
+    if (!s || n < 0 || (n > 0 && (!rays || !out))) why = "bad argument";
+    else if (!c) why = "candidates is NULL";
+    else if (c->capacity < 1 || c->capacity > 16) why = "capacity must be 1..16";
+    else if (!c->count || !c->prim || !c->instance) why = "count, prim and instance are required";
+    else if (closest && !c->before) why = "before is required for closest hit";
+    else if (n >= 0x7fffffffLL) why = "at most 2^31-1 rays per call";
+    if (why) set_error(std::string(fn) + ": " + why);
+    return !why;
+}
+
+int nnbvh_intersect_closest_candidates_device(nnbvh_scene *s, const void *d_rays, int64_t n, void *d_hits,
+                                              const nnbvh_host_candidates *c, void *stream) {
+    if (!candidates_ok("intersect_closest_candidates_device", s, n, d_rays, d_hits, c, true)) return NNBVH_ERR_ARG;
+    if (n == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    Workspace *w = workspace_for(s, (hipStream_t)stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    return launch(s, 0, d_rays, n, d_hits, nullptr, nullptr, nullptr, (hipStream_t)stream, w, nullptr, nullptr, c);
+}
+
+int nnbvh_intersect_any_candidates_device(nnbvh_scene *s, const void *d_rays, int64_t n, void *d_occluded,
+                                          const nnbvh_host_candidates *c, void *stream) {
+    if (!candidates_ok("intersect_any_candidates_device", s, n, d_rays, d_occluded, c, false)) return NNBVH_ERR_ARG;
+    if (n == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    Workspace *w = workspace_for(s, (hipStream_t)stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    nnbvh_host_candidates any = *c;
+    any.before = nullptr;  // not an output of any hit
+    return launch(s, 2, d_rays, n, nullptr, d_occluded, nullptr, nullptr, (hipStream_t)stream, w, nullptr, nullptr,
+                  &any);
+}
+
+// host buffers: one staged copy in, one launch on the null stream, copies out (synchronous)
+static int candidates_host(nnbvh_scene *s, int mode, const nnbvh_ray *rays, int64_t n, void *out,
+                           const nnbvh_host_candidates *c) {
+    const size_t k = (size_t)c->capacity, out_elem = mode == 0 ? sizeof(nnbvh_hit) : 1;
+    void *d_rays = nullptr, *d_out = nullptr;
+    nnbvh_host_candidates d{};
+    d.capacity = c->capacity;
+    auto release = [&]() {
+        for (void *q : {d_rays, d_out, (void *)d.count, (void *)d.before, (void *)d.prim, (void *)d.instance})
+            if (q) (void)hipFree(q);
+    };
+    bool ok = hip_ok(hipMalloc(&d_rays, (size_t)n * sizeof(nnbvh_ray)), "hipMalloc(rays)") &&
+              hip_ok(hipMalloc(&d_out, (size_t)n * out_elem), "hipMalloc(results)") &&
+              hip_ok(hipMalloc((void **)&d.count, (size_t)n * 4), "hipMalloc(count)") &&
+              (mode != 0 || hip_ok(hipMalloc((void **)&d.before, (size_t)n * 4), "hipMalloc(before)")) &&
+              hip_ok(hipMalloc((void **)&d.prim, (size_t)n * k * 4), "hipMalloc(prim)") &&
+              hip_ok(hipMalloc((void **)&d.instance, (size_t)n * k * 4), "hipMalloc(instance)") &&
+              hip_ok(hipMemcpy(d_rays, rays, (size_t)n * sizeof(nnbvh_ray), hipMemcpyHostToDevice), "copy rays") &&
+              // the caller's entries beyond count stay as they were: start from them
+              hip_ok(hipMemcpy(d.prim, c->prim, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy prim") &&
+              hip_ok(hipMemcpy(d.instance, c->instance, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy instance");
+    Workspace *w = ok ? workspace_for(s, nullptr) : nullptr;
+    int rc = w ? NNBVH_OK : NNBVH_ERR_DEVICE;
+    if (rc == NNBVH_OK)
+        rc = mode == 0 ? launch(s, 0, d_rays, n, d_out, nullptr, nullptr, nullptr, nullptr, w, nullptr, nullptr, &d)
+                       : launch(s, 2, d_rays, n, nullptr, d_out, nullptr, nullptr, nullptr, w, nullptr, nullptr, &d);
+    if (rc == NNBVH_OK &&
+        !(hip_ok(hipMemcpy(out, d_out, (size_t)n * out_elem, hipMemcpyDeviceToHost), "copy results") &&
+          hip_ok(hipMemcpy(c->count, d.count, (size_t)n * 4, hipMemcpyDeviceToHost), "copy count") &&
+          (mode != 0 || hip_ok(hipMemcpy(c->before, d.before, (size_t)n * 4, hipMemcpyDeviceToHost), "copy before")) &&
+          hip_ok(hipMemcpy(c->prim, d.prim, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy prim") &&
+          hip_ok(hipMemcpy(c->instance, d.instance, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy instance")))
+        rc = NNBVH_ERR_DEVICE;
+    release();
+    return rc;
+}
+
+int nnbvh_intersect_closest_candidates(nnbvh_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits,
+                                       const nnbvh_host_candidates *c) {
+    if (!candidates_ok("intersect_closest_candidates", s, n, rays, hits, c, true)) return NNBVH_ERR_ARG;
+    if (n == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    return candidates_host(s, 0, rays, n, hits, c);
+}
+
+int nnbvh_intersect_any_candidates(nnbvh_scene *s, const nnbvh_ray *rays, int64_t n, uint8_t *occluded,
+                                   const nnbvh_host_candidates *c) {
+    if (!candidates_ok("intersect_any_candidates", s, n, rays, occluded, c, false)) return NNBVH_ERR_ARG;
+    if (n == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    return candidates_host(s, 2, rays, n, occluded, c);
 }
 
 // One mode-3 launch over up to kMaxFusedBatches closest-hit / occlusion-only batches (the caller has checked that

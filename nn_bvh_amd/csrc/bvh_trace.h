@@ -52,6 +52,13 @@ struct TraceParams {
     // (tmax == nullptr: Infinity, time == nullptr: 0) — no gather pass into nnbvh_ray records
     nnbvh_ray_soa soa;
     nnbvh_ray_soa bSoa[kMaxFusedBatches];
+    // candidate mode (hcCap > 0: the HOSTC instances of modes 0 / 2, scenes with host-only primitives): the host-only
+    // primitives a ray meets are listed instead of voiding its record (nnbvh_host_candidates, include/nnbvh.h)
+    int hcCap;              // K, list entries per ray; 0 = off
+    int32_t *hcCount;       // [n]: 0..K; -1 more than K; -2 an alpha re-trace voided the ray
+    int32_t *hcBefore;      // [n], mode 0: candidates met before the device hit that stands (zeroed before launch)
+    int32_t *hcPrim;        // [n * K]: nnbvh_prim.id of each candidate, traversal order
+    int32_t *hcInst;        // [n * K]: 0 = top level, k + 1 = inside instance k
 };
 
 // bvh_layout.cpp: re-orders the baked arrays in memory (speed only; see the modes there)

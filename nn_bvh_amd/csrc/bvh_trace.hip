@@ -124,11 +124,19 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // records and slots through 32-bit offsets from a scalar base, one primitive step per decision.
 // ALPHA = 1: the scene holds alpha-tested triangles (kPrimAlpha, cpu/primitive.cpp:57-70); compiled
 // separately so that other scenes pay nothing for the hash and the re-trace.
-template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0>
+// HOSTC = 1 (general instances of modes 0 and 2, window 8, scenes with host-only primitives): candidate mode.  A
+// host-only primitive no longer voids the ray: its id and the current instance are appended to the ray's list
+// (p.hcPrim / p.hcInst at ray * K, traversal order, the count in the kColdHost slot), and the walk goes on as
+// the walk that skips it, which is what the plain instances do already.  Closest hit: an accepted hit on a ray
+// with candidates stores how many came before it (p.hcBefore).  At retire the count goes to p.hcCount and the
+// record keeps its real instance unless the list overflowed (-1) or an alpha re-trace voided the ray (-2).
+// Instances of their own, so that the other instances' code is not touched.
+template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
 __global__ __launch_bounds__(kBlockThreads, (INST ? 1 : (ALPHA ? (ALPHA == 2 ? NNBVH_MINW_ALPHA_PATCH : NNBVH_MINW_ALPHA) : ((MODE == 0 || MODE == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (PATCH ? 0 : NNBVH_LEAN_EXTRA_WAVES))))
 void trace_kernel(TraceParams p) {
     static_assert(PATCH || !INST, "two-level scenes need the ray direction");
     static_assert(PATCH || !ALPHA, "the alpha test hashes the ray direction");
+    static_assert(!HOSTC || (PATCH && (MODE == 0 || MODE == 2) && !SOA), "candidate mode: general instances of modes 0 / 2");
     // the stack window: entry k of a lane = (child reference, entry distance), the two words 64 dwords
     // apart so that one ds_read2st64 / ds_write2st64 with one address moves both
     __shared__ float s_stack[kBlockThreads / 64][W][2][64];
@@ -304,7 +312,21 @@ void trace_kernel(TraceParams p) {
         } else if (!kLean && (flags & kPrimHost)) {
             // a primitive only the host can intersect (quadric, curve, alpha-tested
             // ...): this ray's result is void and the caller re-traces it on the CPU
-            cold[kColdHost][lane] = 1.0f;
+            if constexpr (HOSTC) {
+                // ... or, in candidate mode, the caller tests this primitive itself: list it (rare path: the
+                // entries go straight to global memory) and walk on as if it were absent
+                const int c = __float_as_int(cold[kColdHost][lane]);
+                if (c >= 0) {  // -1 (overflow) and -2 (alpha re-trace) stay
+                    if (c < p.hcCap) {
+                        const long at = (long)__float_as_int(cold[kColdRi][lane]) * p.hcCap + c;
+                        p.hcPrim[at] = __float_as_int(s0.w);
+                        p.hcInst[at] = INST ? __float_as_int(cold[kCurInst][lane]) : 0;
+                    }
+                    cold[kColdHost][lane] = __int_as_float(c < p.hcCap ? c + 1 : -1);
+                }
+            } else {
+                cold[kColdHost][lane] = 1.0f;
+            }
             cur = (flags & kPrimLast) ? pop_next() : ~(slot + 3);
         } else {
             tests += 1;
@@ -344,8 +366,8 @@ void trace_kernel(TraceParams p) {
                             if (triangle_test(rn, tMax - th, (flags & kPrimDegenerate) != 0,
                                               {s0.x, s0.y, s0.z}, {s1.x, s1.y, s1.z},
                                               {s2.x, s2.y, s2.z}, y0, y1, y2, tn))
-                                cold[kColdHost][lane] = 1.0f;  // never for a planar triangle; if
-                                                               // it happens the ray is the caller's
+                                cold[kColdHost][lane] = HOSTC ? __int_as_float(-2) : 1.0f;  // never for a planar
+                                                               // triangle; if it happens the ray is the caller's
                         }
                     }
                 }
@@ -373,7 +395,7 @@ void trace_kernel(TraceParams p) {
                         if (!(u > a)) break;  // accepted: (x0, x1, th) are this level's
                         if (k == kAlphaPatchDepth) {
                             hit = false;
-                            cold[kColdHost][lane] = 1.0f;
+                            cold[kColdHost][lane] = HOSTC ? __int_as_float(-2) : 1.0f;
                             break;
                         }
                         if (k == 0) t0 = th;
@@ -411,6 +433,10 @@ void trace_kernel(TraceParams p) {
                     if (INST) {
                         cold[kHitInst][lane] = cold[kCurInst][lane];
                         cold[kInnerHit][lane] = 1.0f;
+                    }
+                    if constexpr (HOSTC && MODE == 0) {  // the candidates met before this hit (the last store wins)
+                        const int c = __float_as_int(cold[kColdHost][lane]);
+                        if (c > 0) p.hcBefore[__float_as_int(cold[kColdRi][lane])] = c;
                     }
                 } else {
                     found = true;
@@ -587,12 +613,25 @@ void trace_kernel(TraceParams p) {
                     h1.y = __int_as_float(visited);
                     h1.z = __int_as_float(tests);
                     h1.w = INST ? cold[kHitInst][lane] : 0.0f;  // 0 / instance index + 1 (bit pattern)
-                    if (!kLean && p.hasHostPrims && cold[kColdHost][lane] != 0.0f) h1.w = __int_as_float(-1);
+                    if constexpr (HOSTC) {
+                        const int c = __float_as_int(cold[kColdHost][lane]);
+                        if (c < 0) h1.w = __int_as_float(-1);
+                        p.hcCount[ri] = c;
+                    } else if (!kLean && p.hasHostPrims && cold[kColdHost][lane] != 0.0f) {
+                        h1.w = __int_as_float(-1);
+                    }
                     float4 *out = reinterpret_cast<float4 *>(p.hits) + 2 * (long)ri;
                     out[0] = h0;
                     out[1] = h1;
                 } else {
-                    const bool needHost = !kLean && p.hasHostPrims && cold[kColdHost][lane] != 0.0f;
+                    bool needHost;
+                    if constexpr (HOSTC) {
+                        const int c = __float_as_int(cold[kColdHost][lane]);
+                        needHost = c != 0;
+                        p.hcCount[ri] = c;
+                    } else {
+                        needHost = !kLean && p.hasHostPrims && cold[kColdHost][lane] != 0.0f;
+                    }
                     p.occluded[ri] = found ? 1 : (needHost ? 2 : 0);
                     if (MODE == 1) {
                         if (p.visitedOut) p.visitedOut[ri] = visited;
@@ -680,7 +719,7 @@ void trace_kernel(TraceParams p) {
                     cold[kColdTime][lane] = r1.w;  // ray.time: read by animated instances
                     floor = -1;
                 }
-                if (!kLean && p.hasHostPrims) cold[kColdHost][lane] = 0.0f;
+                if (!kLean && (HOSTC || p.hasHostPrims)) cold[kColdHost][lane] = 0.0f;  // candidate mode: count 0
                 visited = 1;  // the root
                 tests = 0;
                 found = false;
@@ -790,15 +829,34 @@ void trace_kernel(TraceParams p) {
 }
 
 // ------------------------------------------------------------------------------------
-template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0>
+template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
 static hipError_t launch_one(const TraceParams &p, int blocks, hipStream_t stream, int *occupancy) {
     if (occupancy) {
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, trace_kernel<MODE, W, INST, PATCH, ALPHA, SOA>,
-                                                            kBlockThreads, 0);
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            occupancy, trace_kernel<MODE, W, INST, PATCH, ALPHA, SOA, HOSTC>, kBlockThreads, 0);
     }
-    hipLaunchKernelGGL((trace_kernel<MODE, W, INST, PATCH, ALPHA, SOA>), dim3((unsigned)blocks), dim3(kBlockThreads), 0,
-                       stream, p);
+    hipLaunchKernelGGL((trace_kernel<MODE, W, INST, PATCH, ALPHA, SOA, HOSTC>), dim3((unsigned)blocks),
+                       dim3(kBlockThreads), 0, stream, p);
     return hipGetLastError();
+}
+
+// candidate mode (p.hcCap > 0): the HOSTC twins of the general window-8 instances, modes 0 and 2 only
+template <int MODE>
+static hipError_t launch_candidates(const TraceParams &p, int instanced, int patches, int blocks, hipStream_t stream,
+                                    int *occupancy) {
+    if (patches & 4) {
+        if (!instanced) return launch_one<MODE, 8, 0, 1, 2, 0, 1>(p, blocks, stream, occupancy);
+        return p.anim ? launch_one<MODE, 8, 2, 1, 2, 0, 1>(p, blocks, stream, occupancy)
+                      : launch_one<MODE, 8, 1, 1, 2, 0, 1>(p, blocks, stream, occupancy);
+    }
+    if (patches & 2) {
+        if (!instanced) return launch_one<MODE, 8, 0, 1, 1, 0, 1>(p, blocks, stream, occupancy);
+        return p.anim ? launch_one<MODE, 8, 2, 1, 1, 0, 1>(p, blocks, stream, occupancy)
+                      : launch_one<MODE, 8, 1, 1, 1, 0, 1>(p, blocks, stream, occupancy);
+    }
+    if (!instanced) return launch_one<MODE, 8, 0, 1, 0, 0, 1>(p, blocks, stream, occupancy);
+    return p.anim ? launch_one<MODE, 8, 2, 1, 0, 0, 1>(p, blocks, stream, occupancy)
+                  : launch_one<MODE, 8, 1, 1, 0, 0, 1>(p, blocks, stream, occupancy);
 }
 
 // mode 3 exists for the window-8 instances without alpha-tested triangles
@@ -821,6 +879,9 @@ static hipError_t launch_mode(const TraceParams &p, int window, int instanced, i
     // scenes with alpha-tested triangles and two-level scenes: one instance of the kernel each (window 8)
     // INST: 0 single-level, 1 static instances, 2 instances with AnimatedPrimitives among them (the
     // interpolation of the transform costs 60 VGPRs: 160-177 against 98-116, 2 against 3 wavefronts per SIMD)
+    if constexpr (MODE == 0 || MODE == 2) {
+        if (p.hcCap > 0) return launch_candidates<MODE>(p, instanced, patches, blocks, stream, occupancy);
+    }
     if (patches & 4) {  // alpha-tested bilinear patches
         if (!instanced) return launch_one<MODE, 8, 0, 1, 2>(p, blocks, stream, occupancy);
         return p.anim ? launch_one<MODE, 8, 2, 1, 2>(p, blocks, stream, occupancy)
