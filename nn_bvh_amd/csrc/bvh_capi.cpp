@@ -103,7 +103,6 @@ struct nnbvh_scene {
     int fused_batches = 1;  // nnbvh_trace_batches_device: one mode-3 launch where the batches allow it
     int int_repeat = 3;
     int prim_repeat = 2;
-    int prim_min = 8;  // only read by builds with -DNNBVH_MERGED=1  // merged trips of the lean kernels (bvh_trace.hip); 0 = separate interior / primitive trips
     int max_grid_threads = 0;
     double build_ms[1] = {0};  // device build time of nnbvh_scene_create_gpu_build
     std::mutex mu;
@@ -275,26 +274,8 @@ static nnbvh_scene *scene_from_baked(const BakedScene &b, int depth, int device)
     s->d_prims = (float4 *)b.d_prims;
     s->device_bytes = (size_t)std::max(b.n_interior, 1) * sizeof(WideNode) +
                       std::max<size_t>((size_t)b.n_slots, 1) * 16;
-    if (const char *e = std::getenv("NNBVH_LAYOUT")) {  // memory order of records / leaves (bvh_layout.cpp)
-        const char *t = std::getenv("NNBVH_LAYOUT_TOP");
-        std::string err;
-        if (!relayout_scene(atoi(e), &s->d_wide, &s->d_prims, &s->n_interior, &s->n_slots, &s->root_ref,
-                            t ? atoi(t) : 12, &err)) {
-            set_error(err);
-            (void)hipFree(s->d_wide);
-            delete s;
-            return nullptr;
-        }
-        s->device_bytes = (size_t)std::max(s->n_interior, 1) * sizeof(WideNode) + (size_t)s->n_slots * 16;
-    }
     if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
-    if (const char *e = std::getenv("NNBVH_STACK_WINDOW")) nnbvh_scene_set_option(s, "stack_window", atoi(e));
-    if (const char *e = std::getenv("NNBVH_BLOCKS_PER_CU")) nnbvh_scene_set_option(s, "blocks_per_cu", atoi(e));
-    if (const char *e = std::getenv("NNBVH_XCD_QUEUES")) nnbvh_scene_set_option(s, "xcd_queues", atoi(e));
-    if (const char *e = std::getenv("NNBVH_REFILL_WEIGHT")) nnbvh_scene_set_option(s, "refill_weight", atoi(e));
-    if (const char *e = std::getenv("NNBVH_PRIM_WEIGHT")) nnbvh_scene_set_option(s, "prim_weight", atoi(e));
-    if (const char *e = std::getenv("NNBVH_PRIM_MIN")) nnbvh_scene_set_option(s, "prim_min", atoi(e));
     return s;
 }
 
@@ -594,12 +575,6 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
     }
     if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
-    if (const char *e = std::getenv("NNBVH_STACK_WINDOW")) nnbvh_scene_set_option(s, "stack_window", atoi(e));
-    if (const char *e = std::getenv("NNBVH_BLOCKS_PER_CU")) nnbvh_scene_set_option(s, "blocks_per_cu", atoi(e));
-    if (const char *e = std::getenv("NNBVH_XCD_QUEUES")) nnbvh_scene_set_option(s, "xcd_queues", atoi(e));
-    if (const char *e = std::getenv("NNBVH_REFILL_WEIGHT")) nnbvh_scene_set_option(s, "refill_weight", atoi(e));
-    if (const char *e = std::getenv("NNBVH_PRIM_WEIGHT")) nnbvh_scene_set_option(s, "prim_weight", atoi(e));
-    if (const char *e = std::getenv("NNBVH_PRIM_MIN")) nnbvh_scene_set_option(s, "prim_min", atoi(e));
     return s;
 }
 
@@ -815,11 +790,6 @@ int nnbvh_scene_bounds(const nnbvh_scene *s, float out[6]) {
 static int scene_fits32(const nnbvh_scene *s) {
     return (int64_t)s->n_interior < (1LL << 26) && s->n_slots < (1LL << 28) - 8;
 }
-// ... and the whole allocation (records, then the stream): a merged trip's one 32-bit offset reaches both
-static int scene_prim_min(const nnbvh_scene *s) {
-    const int64_t end = ((const char *)s->d_prims - (const char *)s->d_wide) + s->n_slots * 16 + 64;
-    return end < (1LL << 32) ? s->prim_min : 0;
-}
 
 static int grid_blocks(nnbvh_scene *s, int mode, int candidates = 0) {
     int per_cu = s->blocks_per_cu;
@@ -901,12 +871,6 @@ int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value) {
             return NNBVH_ERR_ARG;
         }
         s->host_chunk = value;
-    } else if (k == "prim_min") {
-        if (value < 0 || value > 64) {
-            set_error("set_option: prim_min must be 0..64");
-            return NNBVH_ERR_ARG;
-        }
-        s->prim_min = value;
     } else if (k == "prim_repeat") {
         if (value < 1 || value > 16) {
             set_error("set_option: prim_repeat must be 1..16");
@@ -984,8 +948,6 @@ static int launch(nnbvh_scene *s, int mode, const void *d_rays, int64_t n, void 
     p.intRepeat = s->int_repeat;
     p.primRepeat = s->prim_repeat;
     p.fits32 = scene_fits32(s);
-    p.primsOff = (unsigned)((const char *)s->d_prims - (const char *)s->d_wide);
-    p.primMin = scene_prim_min(s);
     p.hasHostPrims = s->has_host_prims;
     p.spill = w->spill;
     p.anim = s->d_anim;
@@ -1189,8 +1151,6 @@ static int launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream
     p.intRepeat = s->int_repeat;
     p.primRepeat = s->prim_repeat;
     p.fits32 = scene_fits32(s);
-    p.primsOff = (unsigned)((const char *)s->d_prims - (const char *)s->d_wide);
-    p.primMin = scene_prim_min(s);
     p.hasHostPrims = s->has_host_prims;
     p.spill = w->spill;
     p.anim = s->d_anim;

@@ -34,8 +34,6 @@ struct TraceParams {
     int intRepeat;          // interior steps per scheduling decision (>= 1)
     int primRepeat;         // primitive steps per scheduling decision (>= 1)
     int fits32;             // wide[] and prims[] are both below 4 GiB: the lean instances' 32-bit offsets reach them
-    unsigned primsOff;      // byte offset of prims[] from wide[] (one allocation; lean instances, merged trips)
-    int primMin;            // merged trips: lanes that must wait on a leaf before the primitive block runs; 0 = separate trips
     unsigned long long *stats;  // NNBVH_STATS builds: trips/lanes per step kind; else unused
     uint2 *spill;           // [kMaxStack][grid threads] overflow of the LDS stack window
     const float *anim;      // two-level scenes: kAnimStride floats per instance (anim_math.h), or null
@@ -61,15 +59,12 @@ struct TraceParams {
     int32_t *hcInst;        // [n * K]: 0 = top level, k + 1 = inside instance k
 };
 
-// bvh_layout.cpp: re-orders the baked arrays in memory (speed only; see the modes there)
-bool relayout_scene(int mode, float4 **d_wide, float4 **d_prims, int *n_interior, int64_t *n_slots, int *root_ref,
-                    int top_levels, std::string *error);
-
 hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream);
 
 // occupancy != nullptr: do not launch, report resident blocks per CU of that kernel instance
 // patches: bit 0 = the scene holds bilinear patches (0: kernel instances without the parked ray direction),
-// bit 1 = it holds alpha-tested triangles (the ALPHA kernel instances)
+// bit 1 = it holds alpha-tested triangles (the ALPHA = 1 kernel instances), bit 2 = alpha-tested bilinear patches
+// too (the ALPHA = 2 instances)
 hipError_t launch_trace(int mode, const TraceParams &p, int window, int instanced, int patches, int blocks,
                         hipStream_t stream, int *occupancy);
 

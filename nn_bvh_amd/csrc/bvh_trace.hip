@@ -38,6 +38,9 @@ constexpr int kDone = (int)0x80000000;    // never a leaf ref: ~slot with slot =
 constexpr int kReturn = (int)0x80000001;  // an instance's child traversal is exhausted (slot 0x7ffffffe)
 constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter an AnimatedPrimitive (slot 0x7ffffffd)
 
+// trace_kernel<MODE, W, INST, PATCH, ALPHA, SOA, HOSTC>: every ray of every entry point runs through one instance
+// of this template (the launcher at the end of the file picks it from the scene and the call).
+//
 // MODE 0: closest hit (counts always)
 // MODE 1: any hit with exact node-visit / prim-test counts (pushes every far child)
 // MODE 2: any hit, occlusion flag only
@@ -46,68 +49,18 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 //         (DESIGN.md §5.1).  A lane's ray tag carries its batch; what differs per lane is only what a
 //         hit does and what is written at retire.
 //
+// W: entries per lane of the LDS stack window (4, 8 or 16; every instance but the general single-level one has 8).
+//
 // Every lane is a small state machine over `cur`:
 //     cur >= 0            an interior record to process        (interior step)
 //     cur <  0, != kDone  ~cur = prim-stream slot to test next (primitive step)
-//     cur == kDone        no ray (retire the finished one, fetch the next)
+//     cur == kReturn      INST: the child tree is exhausted    (primitive step: back to the outer leaf)
+//     cur == kEnter       INST = 2: waits at an AnimatedPrimitive (enter step)
+//     cur == kDone        no ray (refill trip: retire the finished one, fetch the next)
 // Each trip of the scheduling loop the WAVE picks one kind of step (wave-uniform, from
 // ballots) and the lanes in that state execute it; the others idle for that trip.  A ray's
 // own sequence of steps is exactly the reference's, so results cannot depend on the policy.
-//
-// waves/SIMD the register allocator must leave room for (measured in steady state: closest
-// hit 5 -> 6 waves is +9 %; beyond that the spills cost more than the extra waves hide)
-#ifndef NNBVH_MINW_CLOSEST
-#define NNBVH_MINW_CLOSEST 6
-#endif
-#ifndef NNBVH_MINW_ANY
-#define NNBVH_MINW_ANY 6
-#endif
-// the ALPHA instances (hash + re-trace in the primitive step): at 6 waves they spill 8-18 registers, at 5 none —
-// a 1 M-triangle soup with 70 % alpha-tested triangles: closest 6.26 -> 4.95 ms, any 5.38 -> 4.52 ms
-#ifndef NNBVH_MINW_ALPHA
-#define NNBVH_MINW_ALPHA 5
-#endif
-// INST = 2: weight of a lane waiting to enter an AnimatedPrimitive in the step selection (interior = 16); 0 = enter
-// at once inside the primitive step (the round-2 form: 11 of 64 lanes active in the interpolation)
-// ALPHA = 2 (alpha-tested bilinear patches: the patch's interaction point and normal incl. the (s, t)
-// reparametrisation, the re-trace loop): 158-162 VGPRs = 3 waves without spills; 2 waves measured 30 % slower,
-// 4 waves (22-27 spilled registers) no faster
-#ifndef NNBVH_MINW_ALPHA_PATCH
-#define NNBVH_MINW_ALPHA_PATCH 3
-#endif
-#ifndef NNBVH_ANIM_ENTER_WEIGHT
-#define NNBVH_ANIM_ENTER_WEIGHT 8
-#endif
-#ifndef NNBVH_FUSED_PRIM_LOOP
-#define NNBVH_FUSED_PRIM_LOOP 0
-#endif
-// 1: the lean instances keep the ray-invariant select predicates (direction signs, kz) as wave-level masks
-// in SGPRs (trace_math.h RayMasks) instead of recomputing them per lane in every step
-#ifndef NNBVH_MASKS
-#define NNBVH_MASKS 1
-#endif
-#ifndef NNBVH_LEAN_PRIM_LOOP
-#define NNBVH_LEAN_PRIM_LOOP 1
-#endif
-#ifndef NNBVH_LEAN_EXTRA_WAVES
-#define NNBVH_LEAN_EXTRA_WAVES 2
-#endif
-// 1: the lean instances run MERGED trips (see the scheduling loop): every lane with a node OR a primitive
-// pending fetches in the same trip, through one load sequence, and the two kinds of arithmetic follow
-// each other — a lane waiting on a leaf no longer sits out the interior trips of its wavefront.
-#ifndef NNBVH_MERGED
-#define NNBVH_MERGED 0
-#endif
-#ifndef NNBVH_FAT
-#define NNBVH_FAT 0
-#endif
-// 1: a far child pushed and popped within the same step is taken from registers (experiment)
-#ifndef NNBVH_FWD_TOP
-#define NNBVH_FWD_TOP 0
-#endif
-// SOA = 1 (lean instances of modes 0, 2, 3 only): a batch without nnbvh_ray records (rays == nullptr) is read as the
-// SOA<Ray> slices of a wavefront queue — no gather pass.  Its own instances: the mere presence of the second fetch
-// path in the refill trip cost the one-launch step 1.3 % (9.31 -> 9.44 ms).
+// These four step kinds (refill, enter, primitive, interior) are all there are.
 //
 // INST = 1: the scene is two-level (TransformedPrimitive leaves, cpu/primitive.cpp:112-131).  An
 // instance primitive saves the lane's ray state in LDS, transforms the ray with the reference's
@@ -121,9 +74,16 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // PATCH = 0 ("lean"): the scene holds no bilinear patches, no instances and no host-only primitives, so
 // nothing ever reads the ray direction after the ray is fetched: no patch test, no direction / ray
 // index / host flag in LDS (20 KiB per block = 8 blocks per CU), <= 64 VGPRs = 8 wavefronts per SIMD,
-// records and slots through 32-bit offsets from a scalar base, one primitive step per decision.
+// records and slots through 32-bit offsets from a scalar base, and the ray-invariant select predicates
+// (direction signs, kz) kept as wave-level masks in SGPRs (trace_math.h RayMasks) instead of being
+// recomputed per lane in every step.
 // ALPHA = 1: the scene holds alpha-tested triangles (kPrimAlpha, cpu/primitive.cpp:57-70); compiled
 // separately so that other scenes pay nothing for the hash and the re-trace.
+// ALPHA = 2: ... and alpha-tested bilinear patches (the patch's interaction point and normal incl. the (s, t)
+// reparametrisation, the re-trace loop).
+// SOA = 1 (lean instances of modes 0, 2, 3 only): a batch without nnbvh_ray records (rays == nullptr) is read as the
+// SOA<Ray> slices of a wavefront queue — no gather pass.  Its own instances: the mere presence of the second fetch
+// path in the refill trip cost the one-launch step 1.3 % (9.31 -> 9.44 ms).
 // HOSTC = 1 (general instances of modes 0 and 2, window 8, scenes with host-only primitives): candidate mode.  A
 // host-only primitive no longer voids the ray: its id and the current instance are appended to the ray's list
 // (p.hcPrim / p.hcInst at ray * K, traversal order, the count in the kColdHost slot), and the walk goes on as
@@ -131,6 +91,35 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // with candidates stores how many came before it (p.hcBefore).  At retire the count goes to p.hcCount and the
 // record keeps its real instance unless the list overflowed (-1) or an alpha re-trace voided the ray (-2).
 // Instances of their own, so that the other instances' code is not touched.
+//
+// Tuning constants (each with its measurement; -D overrides are for A/B builds only).
+// waves/SIMD the register allocator must leave room for (measured in steady state: closest
+// hit 5 -> 6 waves is +9 %; beyond that the spills cost more than the extra waves hide)
+#ifndef NNBVH_MINW_CLOSEST
+#define NNBVH_MINW_CLOSEST 6
+#endif
+#ifndef NNBVH_MINW_ANY
+#define NNBVH_MINW_ANY 6
+#endif
+// ... and the waves/SIMD the lean instances (<= 64 VGPRs) run on top of that
+#ifndef NNBVH_LEAN_EXTRA_WAVES
+#define NNBVH_LEAN_EXTRA_WAVES 2
+#endif
+// the ALPHA instances (hash + re-trace in the primitive step): at 6 waves they spill 8-18 registers, at 5 none —
+// a 1 M-triangle soup with 70 % alpha-tested triangles: closest 6.26 -> 4.95 ms, any 5.38 -> 4.52 ms
+#ifndef NNBVH_MINW_ALPHA
+#define NNBVH_MINW_ALPHA 5
+#endif
+// ALPHA = 2: 158-162 VGPRs = 3 waves without spills; 2 waves measured 30 % slower, 4 waves (22-27 spilled
+// registers) no faster
+#ifndef NNBVH_MINW_ALPHA_PATCH
+#define NNBVH_MINW_ALPHA_PATCH 3
+#endif
+// INST = 2: weight of a lane waiting to enter an AnimatedPrimitive in the step selection (interior = 16); 0 = enter
+// at once inside the primitive step (the round-2 form: 11 of 64 lanes active in the interpolation)
+#ifndef NNBVH_ANIM_ENTER_WEIGHT
+#define NNBVH_ANIM_ENTER_WEIGHT 8
+#endif
 template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
 __global__ __launch_bounds__(kBlockThreads, (INST ? 1 : (ALPHA ? (ALPHA == 2 ? NNBVH_MINW_ALPHA_PATCH : NNBVH_MINW_ALPHA) : ((MODE == 0 || MODE == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (PATCH ? 0 : NNBVH_LEAN_EXTRA_WAVES))))
 void trace_kernel(TraceParams p) {
@@ -336,7 +325,7 @@ void trace_kernel(TraceParams p) {
             if (!PATCH || !(flags & kPrimPatch)) {
                 hit = triangle_test(r, tMax, (flags & kPrimDegenerate) != 0,
                                     {s0.x, s0.y, s0.z}, {s1.x, s1.y, s1.z},
-                                    {s2.x, s2.y, s2.z}, x0, x1, x2, th, (kLean && NNBVH_MASKS) ? &masks : nullptr);
+                                    {s2.x, s2.y, s2.z}, x0, x1, x2, th, kLean ? &masks : nullptr);
                 next = slot + ((ALPHA && (flags & kPrimSmooth)) ? 6 : 3);
                 if (ALPHA && hit && (flags & kPrimAlpha)) {
                     // GeometricPrimitive::Intersect, cpu/primitive.cpp:57-70 (IntersectP takes
@@ -457,10 +446,10 @@ void trace_kernel(TraceParams p) {
         const bool swap = ((r.kz >> axis) & 1) != 0;  // dirIsNeg[axis], packed by ray_shear
         // one float per child: its entry distance, +inf if the box is missed whatever tMax is
         // (slab_entry_key) — the verdicts are then two compares against tMax
-        const float k0 = (kLean && NNBVH_MASKS) ? slab_entry_key(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, r, masks)
-                                                : slab_entry_key(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, r);
-        const float k1 = (kLean && NNBVH_MASKS) ? slab_entry_key(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, r, masks)
-                                                : slab_entry_key(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, r);
+        const float k0 = kLean ? slab_entry_key(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, r, masks)
+                               : slab_entry_key(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, r);
+        const float k1 = kLean ? slab_entry_key(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, r, masks)
+                               : slab_entry_key(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, r);
         const int nearRef = swap ? ref1 : ref0, farRef = swap ? ref0 : ref1;
         const float nearT = swap ? k1 : k0, farT = swap ? k0 : k1;
         visited += 1;  // the near child is entered now
@@ -471,32 +460,18 @@ void trace_kernel(TraceParams p) {
         // it), and the reference tests the far child against that later value.  MODE 1 pushes every
         // far child (exact counts up to the first hit).
         const bool doPush = (MODE == 1) || (farT < __builtin_inff());
-#if NNBVH_FWD_TOP
-        // near child missed, far child hit: the entry about to be pushed is the one pop_next would hand straight back —
-        // take it from the registers (no LDS write + read, no spill of the oldest entry on its behalf)
-        const bool takeFar = doPush && !(nearT < tMax) && (farT < tMax);
-        if (!takeFar) {
-#else
-        constexpr bool takeFar = false;
-        {
-#endif
-            if (doPush && sp - base == W - 1) {
-                uint2 e;
-                e.x = __float_as_uint(stk[base & (W - 1)][0][lane]);
-                e.y = __float_as_uint(stk[base & (W - 1)][1][lane]);
-                p.spill[(long)base * spillStride + gtid] = e;
-                ++base;
-            }
-            stk[sp & (W - 1)][0][lane] = __int_as_float(farRef);
-            stk[sp & (W - 1)][1][lane] = farT;
-            sp += doPush ? 1 : 0;
+        if (doPush && sp - base == W - 1) {  // the window is full: its oldest entry goes to the HBM spill array
+            uint2 e;
+            e.x = __float_as_uint(stk[base & (W - 1)][0][lane]);
+            e.y = __float_as_uint(stk[base & (W - 1)][1][lane]);
+            p.spill[(long)base * spillStride + gtid] = e;
+            ++base;
         }
+        stk[sp & (W - 1)][0][lane] = __int_as_float(farRef);
+        stk[sp & (W - 1)][1][lane] = farT;
+        sp += doPush ? 1 : 0;
         if (MODE == 0 || MODE == 3) visited += doPush ? 0 : 1;
-        if (nearT < tMax) cur = nearRef;
-        else if (takeFar) {
-            if (MODE != 2) visited += 1;  // as pop_entry counts the popped entry
-            cur = farRef;
-        } else cur = pop_next();
+        cur = nearT < tMax ? nearRef : pop_next();
     };
     auto interior_step = [&]() {
 #ifdef NNBVH_STATS
@@ -504,41 +479,14 @@ void trace_kernel(TraceParams p) {
         st[15] += __popcll(__ballot(cur >= 0));
 #endif
         if (cur >= 0) {
-#ifdef NNBVH_PROBE_SALU  // sensitivity probes (tools only): extra scalar / vector instructions per interior step
-#pragma unroll
-            for (int k = 0; k < NNBVH_PROBE_SALU; ++k) asm volatile("s_add_u32 s95, s95, 1" ::: "s95", "scc");
-#endif
-#ifdef NNBVH_PROBE_VALU
-#pragma unroll
-            for (int k = 0; k < NNBVH_PROBE_VALU; ++k) asm volatile("v_add_u32 %0, %0, 1" : "+v"(tests));
-#endif
             // lean instances address records and slots with a 32-bit byte offset from a scalar base (one
             // 32-bit shift instead of a 64-bit shift and a 64-bit add per fetch); the launcher only picks
             // them when both arrays are below 4 GiB (p.fits32)
-            if constexpr (NNBVH_FAT && kLean) {
-            // experiment (bvh_layout.cpp mode 32): 192-B records = the node's own record + copies of both
-            // children's; the copy of the child this ray enters next arrives with the node's record, and the
-            // lanes that do enter it (and find it interior) take that step in the same trip
-            const unsigned at = ((unsigned)cur >> 2) * 192u;
-            const unsigned nearCopy = 64u + (((unsigned)r.kz >> (cur & 3)) & 1u) * 64u;
-            const float4 *rec = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(p.wide) + at);
-            const float4 *rec2 = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(p.wide) + at + nearCopy);
-            const float4 q3 = rec[3];
-            const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
-            const float4 n3 = rec2[3];
-            const float4 n0 = rec2[0], n1 = rec2[1], n2 = rec2[2];
-            const int nearChild = (((unsigned)r.kz >> (cur & 3)) & 1u) ? __float_as_int(q3.y) : __float_as_int(q3.x);
-            interior_math(q0, q1, q2, q3);
-            // the near child was entered iff the lane now stands on it; a popped entry with the same
-            // reference cannot exist (a node has one parent and is pushed at most once)
-            if (cur >= 0 && cur == nearChild) interior_math(n0, n1, n2, n3);
-            } else {
             const float4 *rec = kLean ? reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(p.wide) + ((unsigned)cur << 6))
                                       : p.wide + 4 * (long)cur;
             const float4 q3 = rec[3];
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
             interior_math(q0, q1, q2, q3);
-            }
         }
     };
 
@@ -731,7 +679,7 @@ void trace_kernel(TraceParams p) {
                     (tEntry < tMax);
                 cur = rootHit ? p.rootRef : kDone;
             }
-            if (kLean && NNBVH_MASKS) masks = ray_masks(r);  // some lanes carry new rays
+            if (kLean) masks = ray_masks(r);  // some lanes carry new rays
             continue;
         }
 
@@ -746,42 +694,13 @@ void trace_kernel(TraceParams p) {
             continue;
         }
 
-        if (kLean && NNBVH_MERGED && p.primMin > 0) {
-            // ---- merged trip (lean instances): every lane with a node pending, and — when at least
-            // p.primMin lanes wait on a leaf, or nobody has a node — every lane with a primitive pending,
-            // fetches 64 B through ONE load sequence (records and slots live in one allocation: a lane's
-            // 32-bit offset reaches either), then the two kinds of arithmetic follow each other.  A trip
-            // costs one round trip to memory whichever lanes take part; lanes waiting on a leaf no longer
-            // sit out their wavefront's interior trips.  (A primitive lane's fourth slot is not used.)
-            const bool primLane = !isInt && !isIdle && (nPrim >= p.primMin || nInt == 0);
-#ifdef NNBVH_STATS
-            st[0] += 1;
-            st[1] += nInt;
-            if (nPrim >= p.primMin || nInt == 0) {
-                st[2] += 1;
-                st[3] += nPrim;
-            }
-            stKind = 0;
-#endif
-            if (isInt || primLane) {
-                const unsigned off = isInt ? ((unsigned)cur << 6) : (p.primsOff + ((unsigned)~cur << 4));
-                const float4 *rec = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(p.wide) + off);
-                const float4 q3 = rec[3];
-                const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
-                if (isInt) interior_math(q0, q1, q2, q3);
-                else prim_math(~cur, q0, q1, q2);
-            }
-            for (int rep = 1; rep < p.intRepeat && __ballot(cur >= 0) != 0ull; ++rep) interior_step();
-            continue;
-        }
-
         if (sP > sI || nInt == 0) {
             // ---- primitive step: lanes with a pending leaf test ONE primitive -----------
             // (up to p.primRepeat of them per scheduling decision: lanes whose leaf is finished sit the
             // rest out, lanes still inside theirs go on without another round of ballots)
-            // (the one-launch kernel and the lean instances keep ONE: compiled in, the loop costs them 6
-            // registers — spills at 8 wavefronts per SIMD — and 2.6 % / 8 % of their rate)
-            const int nPrep = ((MODE == 3 && !NNBVH_FUSED_PRIM_LOOP) || (kLean && !NNBVH_LEAN_PRIM_LOOP)) ? 1 : p.primRepeat;
+            // (the one-launch kernel keeps ONE: compiled in, the loop costs it 6 registers — spills at 8
+            // wavefronts per SIMD — and 2.6 % of its rate)
+            const int nPrep = (MODE == 3) ? 1 : p.primRepeat;
             int prep = 0;
             do {
             if (cur < 0 && cur != kDone) {
@@ -840,23 +759,21 @@ static hipError_t launch_one(const TraceParams &p, int blocks, hipStream_t strea
     return hipGetLastError();
 }
 
-// candidate mode (p.hcCap > 0): the HOSTC twins of the general window-8 instances, modes 0 and 2 only
-template <int MODE>
-static hipError_t launch_candidates(const TraceParams &p, int instanced, int patches, int blocks, hipStream_t stream,
-                                    int *occupancy) {
-    if (patches & 4) {
-        if (!instanced) return launch_one<MODE, 8, 0, 1, 2, 0, 1>(p, blocks, stream, occupancy);
-        return p.anim ? launch_one<MODE, 8, 2, 1, 2, 0, 1>(p, blocks, stream, occupancy)
-                      : launch_one<MODE, 8, 1, 1, 2, 0, 1>(p, blocks, stream, occupancy);
-    }
-    if (patches & 2) {
-        if (!instanced) return launch_one<MODE, 8, 0, 1, 1, 0, 1>(p, blocks, stream, occupancy);
-        return p.anim ? launch_one<MODE, 8, 2, 1, 1, 0, 1>(p, blocks, stream, occupancy)
-                      : launch_one<MODE, 8, 1, 1, 1, 0, 1>(p, blocks, stream, occupancy);
-    }
-    if (!instanced) return launch_one<MODE, 8, 0, 1, 0, 0, 1>(p, blocks, stream, occupancy);
-    return p.anim ? launch_one<MODE, 8, 2, 1, 0, 0, 1>(p, blocks, stream, occupancy)
-                  : launch_one<MODE, 8, 1, 1, 0, 0, 1>(p, blocks, stream, occupancy);
+// The general (PATCH = 1) window-8 instances: INST x ALPHA, and their HOSTC twins for candidate mode.
+// INST: 0 single-level, 1 static instances, 2 instances with AnimatedPrimitives among them (the
+// interpolation of the transform costs 60 VGPRs: 160-177 against 98-116, 2 against 3 wavefronts per SIMD)
+template <int MODE, int ALPHA, int HOSTC>
+static hipError_t launch_inst(const TraceParams &p, int instanced, int blocks, hipStream_t stream, int *occupancy) {
+    if (!instanced) return launch_one<MODE, 8, 0, 1, ALPHA, 0, HOSTC>(p, blocks, stream, occupancy);
+    return p.anim ? launch_one<MODE, 8, 2, 1, ALPHA, 0, HOSTC>(p, blocks, stream, occupancy)
+                  : launch_one<MODE, 8, 1, 1, ALPHA, 0, HOSTC>(p, blocks, stream, occupancy);
+}
+template <int MODE, int HOSTC>
+static hipError_t launch_general(const TraceParams &p, int instanced, int patches, int blocks, hipStream_t stream,
+                                 int *occupancy) {
+    if (patches & 4) return launch_inst<MODE, 2, HOSTC>(p, instanced, blocks, stream, occupancy);  // alpha-tested patches
+    if (patches & 2) return launch_inst<MODE, 1, HOSTC>(p, instanced, blocks, stream, occupancy);  // alpha-tested triangles
+    return launch_inst<MODE, 0, HOSTC>(p, instanced, blocks, stream, occupancy);
 }
 
 // mode 3 exists for the window-8 instances without alpha-tested triangles
@@ -876,24 +793,12 @@ static hipError_t launch_fused(const TraceParams &p, int window, int instanced, 
 template <int MODE>
 static hipError_t launch_mode(const TraceParams &p, int window, int instanced, int patches, int blocks,
                               hipStream_t stream, int *occupancy) {
-    // scenes with alpha-tested triangles and two-level scenes: one instance of the kernel each (window 8)
-    // INST: 0 single-level, 1 static instances, 2 instances with AnimatedPrimitives among them (the
-    // interpolation of the transform costs 60 VGPRs: 160-177 against 98-116, 2 against 3 wavefronts per SIMD)
+    // candidate mode (p.hcCap > 0, modes 0 and 2 only): always a HOSTC instance, whatever the window
     if constexpr (MODE == 0 || MODE == 2) {
-        if (p.hcCap > 0) return launch_candidates<MODE>(p, instanced, patches, blocks, stream, occupancy);
+        if (p.hcCap > 0) return launch_general<MODE, 1>(p, instanced, patches, blocks, stream, occupancy);
     }
-    if (patches & 4) {  // alpha-tested bilinear patches
-        if (!instanced) return launch_one<MODE, 8, 0, 1, 2>(p, blocks, stream, occupancy);
-        return p.anim ? launch_one<MODE, 8, 2, 1, 2>(p, blocks, stream, occupancy)
-                      : launch_one<MODE, 8, 1, 1, 2>(p, blocks, stream, occupancy);
-    }
-    if (patches & 2) {
-        if (!instanced) return launch_one<MODE, 8, 0, 1, 1>(p, blocks, stream, occupancy);
-        return p.anim ? launch_one<MODE, 8, 2, 1, 1>(p, blocks, stream, occupancy)
-                      : launch_one<MODE, 8, 1, 1, 1>(p, blocks, stream, occupancy);
-    }
-    if (instanced) return p.anim ? launch_one<MODE, 8, 2, 1>(p, blocks, stream, occupancy)
-                                 : launch_one<MODE, 8, 1, 1>(p, blocks, stream, occupancy);
+    // scenes with alpha-tested primitives and two-level scenes: one instance of the kernel each (window 8)
+    if (instanced || (patches & 6)) return launch_general<MODE, 0>(p, instanced, patches, blocks, stream, occupancy);
     const bool soa = !p.rays && !occupancy;
     if (!patches && !p.hasHostPrims && p.fits32 && window == 8 && !instanced) {
         if (soa && MODE != 1) return launch_one<MODE == 1 ? 0 : MODE, 8, 0, 0, 0, 1>(p, blocks, stream, occupancy);

@@ -62,14 +62,7 @@ __global__ __launch_bounds__(256, FULL ? 1 : NNBVH_INTR_LEAN_WAVES) void k_trian
                     make_float4(__int_as_float(prim), __int_as_float(NNBVH_INTERACTION_HOST), 0.0f, 0.0f);
                 return;
             }
-#ifdef NNBVH_INTR_PROBE_NOWRITE  // tools only: what the 192-B record stores cost (the record is folded into 16 B)
-            const float *f = reinterpret_cast<const float *>(&r);
-            float4 acc = {0, 0, 0, 0};
-            for (int k = 0; k < 48; k += 4) acc = {acc.x + f[k], acc.y + f[k + 1], acc.z + f[k + 2], acc.w + f[k + 3]};
-            reinterpret_cast<float4 *>(out + i)[11] = acc;
-#else
             out[i] = r;
-#endif
         });
     }
 }

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""A/B of memory layouts (NNBVH_LAYOUT, bvh_layout.cpp) and scheduling knobs on the crown step, all variants
-interleaved round-robin in ONE process on one box: per ray class launched alone and the one-launch step.
+"""A/B of the scheduling knobs (int_repeat, prim_repeat, prim_weight, refill_weight, xcd_queues) on the crown step,
+all variants interleaved round-robin in ONE process on one box: per ray class launched alone and the one-launch step.
 Every variant's results are compared byte for byte with the first one's.
-Usage: python tools/variant_probe.py [--layouts 0,1,2,9,16,17] [--knobs prim_min=0:int_repeat=3,prim_min=8:int_repeat=1]"""
+Usage: python tools/variant_probe.py [--knobs int_repeat=3:prim_repeat=2,int_repeat=1:prim_repeat=1]"""
 import argparse
 import os
 import sys
@@ -15,8 +15,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--layouts", default="0,1,2,9,16,17")
-    ap.add_argument("--knobs", default="prim_min=0:int_repeat=3,prim_min=8:int_repeat=1")
+    ap.add_argument("--knobs", default="int_repeat=3:prim_repeat=2,int_repeat=1:prim_repeat=1")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--spp", type=int, default=8)
     ap.add_argument("--scene", default="crown")
@@ -34,13 +33,8 @@ def main():
         primary = np.stack(per, 1)[tiles].reshape(-1)
     else:
         primary = np.concatenate(per)
-    aggs = {}
-    for lay in [int(x) for x in args.layouts.split(",")]:
-        os.environ["NNBVH_LAYOUT"] = str(lay)
-        aggs[lay] = BVHAggregate.from_tree(tree.nodes, tree.ordered_prims, verts)
-    os.environ.pop("NNBVH_LAYOUT")
-    first = next(iter(aggs.values()))
-    hits = first.Intersect(primary)
+    agg = BVHAggregate.from_tree(tree.nodes, tree.ordered_prims, verts)
+    hits = agg.Intersect(primary)
     bounce = scene.bounce_rays(primary, hits, verts, tris, seed=2)
     if args.scene == "crown":
         shadow = scene.shadow_rays_to_quads(primary, hits, verts, tris, scene.CROWN_LIGHT_QUADS, seed=3)
@@ -57,7 +51,7 @@ def main():
     n = nP + nB + nS
     knobs = [dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in k.split(":")) for k in args.knobs.split(",")]
 
-    def run(agg, kind):
+    def run(kind):
         if kind == "fused":
             agg.trace_batches_device([("closest", dp.data_ptr(), nP, o1.data_ptr()), ("closest", db.data_ptr(), nB, o2.data_ptr()),
                                       ("any", ds.data_ptr(), nS, o3.data_ptr())], stream)
@@ -72,35 +66,33 @@ def main():
     times = {}
     ref = None
     for rnd in range(args.rounds + 1):
-        for lay, agg in aggs.items():
-            for ki, kn in enumerate(knobs):
-                for key, v in kn.items():
-                    agg.set_option(key, v)
-                for kind in kinds:
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    run(agg, kind)
-                    b.record()
-                    torch.cuda.synchronize()
-                    if rnd:
-                        times.setdefault((lay, ki, kind), []).append(a.elapsed_time(b))
-                if rnd == 0:  # results of the three separate launches (they ran last) against the first variant's
-                    cur = (o1.clone(), o2.clone(), o3.clone())
-                    if ref is None:
-                        ref = cur
-                    elif not all(torch.equal(x, y) for x, y in zip(ref, cur)):
-                        print(f"!! layout {lay} knobs {kn}: results DIFFER from the first variant", flush=True)
-                    run(agg, "fused")
-                    torch.cuda.synchronize()
-                    if not all(torch.equal(x, y) for x, y in zip(ref, (o1, o2, o3))):
-                        print(f"!! layout {lay} knobs {kn}: one-launch results DIFFER", flush=True)
-    print(f"# {source}; {n} rays per step ({nP} primary, {nB} bounce, {nS} shadow); order {args.order}; median of {args.rounds}")
-    print("layout knobs | step ms (Mray/s) | primary | bounce | shadow  Mray/s")
-    for lay in aggs:
         for ki, kn in enumerate(knobs):
-            t = {k: float(np.median(times[(lay, ki, k)])) for k in kinds}
-            print(f"{lay:3d} {kn} | {t['fused']:7.3f} ({n / t['fused'] / 1e3:7.1f}) | {nP / t['primary'] / 1e3:7.1f} | "
-                  f"{nB / t['bounce'] / 1e3:7.1f} | {nS / t['shadow'] / 1e3:7.1f}", flush=True)
+            for key, v in kn.items():
+                agg.set_option(key, v)
+            for kind in kinds:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                run(kind)
+                b.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    times.setdefault((ki, kind), []).append(a.elapsed_time(b))
+            if rnd == 0:  # results of the three separate launches (they ran last) against the first variant's
+                cur = (o1.clone(), o2.clone(), o3.clone())
+                if ref is None:
+                    ref = cur
+                elif not all(torch.equal(x, y) for x, y in zip(ref, cur)):
+                    print(f"!! knobs {kn}: results DIFFER from the first variant", flush=True)
+                run("fused")
+                torch.cuda.synchronize()
+                if not all(torch.equal(x, y) for x, y in zip(ref, (o1, o2, o3))):
+                    print(f"!! knobs {kn}: one-launch results DIFFER", flush=True)
+    print(f"# {source}; {n} rays per step ({nP} primary, {nB} bounce, {nS} shadow); order {args.order}; median of {args.rounds}")
+    print("knobs | step ms (Mray/s) | primary | bounce | shadow  Mray/s")
+    for ki, kn in enumerate(knobs):
+        t = {k: float(np.median(times[(ki, k)])) for k in kinds}
+        print(f"{kn} | {t['fused']:7.3f} ({n / t['fused'] / 1e3:7.1f}) | {nP / t['primary'] / 1e3:7.1f} | "
+              f"{nB / t['bounce'] / 1e3:7.1f} | {nS / t['shadow'] / 1e3:7.1f}", flush=True)
 
 
 if __name__ == "__main__":
