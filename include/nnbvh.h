@@ -336,12 +336,13 @@ int nnbvh_intersect_any_device(nnbvh_scene *s, const void *d_rays, int64_t n, vo
  * Any hit: occluded = device occluded || some candidate hits with ray.tmax.
  *
  * Scope: BVH scenes (flat, two-level static and animated, with or without alpha-tested kinds), closest hit and
- * occlusion-only any hit.  Follow-ups, not covered: shape math for spheres / disks / cylinders on the device,
- * nnbvh_trace_batches_device (mode-3 fused batches), the wavefront queue entry points (their needs_host queue
- * is unchanged), kd-tree scenes, exact node / test counts for rays with candidates.
+ * occlusion-only any hit: the single-batch calls below, several batches in one launch
+ * (nnbvh_trace_batches_candidates_device) and the wavefront queue entry points (nnbvh_wavefront_*_candidates, after
+ * the plain wavefront calls).  Follow-ups, not covered: shape math for spheres / disks / cylinders on the device,
+ * kd-tree scenes, exact node / test counts for rays with candidates.
  * NNBVH_ERR_ARG for capacity outside 1..16, a NULL count / prim / instance, or a NULL before on a closest call. */
 typedef struct nnbvh_host_candidates {
-    int32_t capacity;   /* K, 1..16 */
+    int32_t capacity;   /* K, 1..16 (0 = a plain batch, nnbvh_trace_batches_candidates_device only) */
     int32_t *count;     /* int32[n]: 0..K candidates; -1 more than K; -2 alpha re-trace: record void */
     int32_t *before;    /* int32[n], closest only (NULL for any-hit): candidates met before the device hit */
     int32_t *prim;      /* int32[n * K]: nnbvh_prim.id of each candidate, traversal order */
@@ -382,6 +383,15 @@ typedef struct nnbvh_batch {
 } nnbvh_batch;
 int nnbvh_trace_batches_device(nnbvh_scene *s, const nnbvh_batch *batches, int n_batches,
                                void *stream);
+/* ... with host candidates per batch: cands[b] (device pointers) belongs to batches[b] and is filled as by
+ * nnbvh_intersect_closest_candidates_device / nnbvh_intersect_any_candidates_device on the same rays; capacity == 0
+ * makes batch b a plain batch (its output is nnbvh_trace_batches_device's).  One launch where
+ * nnbvh_trace_batches_device uses one; scenes with alpha-tested primitives (and option "fused_batches" 0) run one
+ * candidate launch per batch, forked from and joined back into `stream`, with the same results.  NNBVH_ERR_ARG, and
+ * nothing launched, for a capacity outside 0..16, a NULL count / prim / instance, a NULL before on a closest batch,
+ * or an any-hit batch that asks for exact counts (d_nodes_visited / d_prim_tests) together with candidates. */
+int nnbvh_trace_batches_candidates_device(nnbvh_scene *s, const nnbvh_batch *batches, int n_batches,
+                                          const nnbvh_host_candidates *cands, void *stream);
 
 /* ---- wavefront queues: WavefrontAggregate::IntersectClosest / IntersectShadow ---------------
  * (wavefront/integrator.h:32-54; CPU implementation wavefront/aggregate.cpp:34-68).  The ray
@@ -656,6 +666,58 @@ int nnbvh_wavefront_intersect_closest_and_shadow_items(
     const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld, const float *d_r_u,
     const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_occluded,
     void *stream);
+
+/* ---- the wavefront calls with host candidates --------------------------------------------------------
+ * The plain wavefront calls above void a ray that reaches a host-only primitive and hand it to needs_host, so the
+ * embedder needs a CPU aggregate of the whole scene for those rays.  These forms return such a ray's candidate-mode
+ * record and its candidate list instead (nnbvh_host_candidates: device pointers, arrays of max_rays entries, rules
+ * as for nnbvh_intersect_closest_candidates_device).  The loop of one wavefront iteration:
+ *   1. nnbvh_wavefront_intersect_closest_[and_shadow_]items_candidates: rays with count[i] == 0 are routed exactly as
+ *      the plain call routes them (same queues, same item slices); a ray with count[i] != 0 goes to needs_host only,
+ *      and d_hits[i] (required) is its candidate-mode record: the closest device hit with its real instance, or void
+ *      (instance == -1) for count < 0;
+ *   2. the caller tests the candidates of the needs_host rays, merges them with d_hits[i] by the merge rule above and
+ *      writes the merged records back into d_hits (count < 0: the ray stays the caller's);
+ *   3. nnbvh_wavefront_enqueue_closest_items_indexed_device with the needs_host queue as the index list (and a fresh
+ *      needs_host queue) pushes those rays: nnbvh_wavefront_enqueue_closest_items_device applied to the rays
+ *      d_index[0 .. min(max_index, *d_index_size)) only (entries outside [0, max_rays) are skipped).  The pushes are
+ *      appended to the same queues: the size counters continue.  A merged hit on a host shape has no vertices in the
+ *      shading mesh and takes the NNBVH_INTERACTION_HOST route (needs_host);
+ *   4. shadow rays: nnbvh_wavefront_intersect_shadow_candidates writes d_occluded (required) 0 / 1 / 2; rays with 0
+ *      add to d_L as in the plain call, rays with 1 or 2 add nothing.  After testing the candidates of the 2s the
+ *      caller passes an array that is 1 everywhere but 0 on the resolved, unoccluded rays to
+ *      nnbvh_wavefront_record_shadow_device, which skips non-zero entries: no kernel of its own is needed for this.
+ * A scene without host-only primitives runs the plain calls' kernels and returns count == 0 everywhere.  All item
+ * slices may be NULL (index queues only).  NNBVH_ERR_ARG, and nothing launched, for a NULL d_hits / d_occluded and for
+ * the candidate-argument faults of nnbvh_intersect_*_candidates_device. */
+int nnbvh_wavefront_intersect_closest_items_candidates(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                       const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                                       const uint8_t *d_prim_class, int64_t n_prim_class,
+                                                       void *d_hits, const nnbvh_closest_queues *out,
+                                                       const nnbvh_closest_items *items,
+                                                       const nnbvh_host_candidates *c, void *stream);
+int nnbvh_wavefront_enqueue_closest_items_indexed_device(const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                         const nnbvh_ray_soa *ray_queue, const int32_t *d_index,
+                                                         const int32_t *d_index_size, int32_t max_index,
+                                                         const void *d_hits, const uint8_t *d_prim_class,
+                                                         int64_t n_prim_class, const nnbvh_closest_queues *out,
+                                                         const nnbvh_closest_items *items, void *stream);
+int nnbvh_wavefront_intersect_shadow_candidates(nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+                                                const int32_t *d_size, const float *d_Ld, const float *d_r_u,
+                                                const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                                int64_t n_pixels, uint8_t *d_occluded /* required */,
+                                                const nnbvh_host_candidates *c, void *stream);
+/* The closest and the shadow call above in ONE launch of the traversal kernel (its candidate-mode instances), with
+ * the fallback of nnbvh_wavefront_intersect_closest_and_shadow for the scenes the one-launch kernel does not cover
+ * (alpha-tested primitives) and for an empty side: the two calls one after the other.  c: the closest side's
+ * candidates, shadow_c: the shadow side's (its before is not read). */
+int nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, const nnbvh_host_candidates *c,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded /* required */, const nnbvh_host_candidates *shadow_c, void *stream);
 
 /* ---- KdTreeAggregate (cpu/aggregates.h:75-105; aggregates.cpp:746-1161) --------------------------
  * The reference's other accelerator ("kdtree" in CreateAccelerator, aggregates.cpp:1163-1178) and the

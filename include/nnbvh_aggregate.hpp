@@ -372,6 +372,66 @@ class HipBVHAggregate {
         if (nnbvh_trace_batches_device(scene_, batches, nBatches, stream) != NNBVH_OK)
             fatal("TraceBatchesDevice");
     }
+    // ... with host candidates per batch (cands[b].capacity == 0: a plain batch)
+    void TraceBatchesDevice(const nnbvh_batch *batches, int nBatches, const nnbvh_host_candidates *cands,
+                            void *stream) const {
+        if (nnbvh_trace_batches_candidates_device(scene_, batches, nBatches, cands, stream) != NNBVH_OK)
+            fatal("TraceBatchesDevice (candidates)");
+    }
+
+    // ---- the wavefront stages with host candidates (include/nnbvh.h "the wavefront calls with host candidates"):
+    //      rays that reached a host-only primitive come back in items.needs_host with their candidate-mode record in
+    //      dHits and their candidate list in `c` (device arrays); the embedder tests those shapes, writes the merged
+    //      records back and pushes the rays with EnqueueClosestItemsIndexed
+    void IntersectClosestItemsQueues(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &rayQueue,
+                                     const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass, void *dHits,
+                                     const nnbvh_closest_queues &out, const nnbvh_closest_items &items,
+                                     const nnbvh_host_candidates &c, void *stream) const {
+        if (nnbvh_wavefront_intersect_closest_items_candidates(scene_, mesh, maxRays, &rayQueue, dSize, dPrimClass,
+                                                               nPrimClass, dHits, &out, &items, &c, stream) != NNBVH_OK)
+            fatal("IntersectClosestItemsQueues (candidates)");
+    }
+    static void EnqueueClosestItemsIndexed(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &rayQueue,
+                                           const int32_t *dIndex, const int32_t *dIndexSize, int maxIndex,
+                                           const void *dHits, const uint8_t *dPrimClass, int64_t nPrimClass,
+                                           const nnbvh_closest_queues &out, const nnbvh_closest_items &items,
+                                           void *stream) {
+        if (nnbvh_wavefront_enqueue_closest_items_indexed_device(mesh, maxRays, &rayQueue, dIndex, dIndexSize, maxIndex,
+                                                                 dHits, dPrimClass, nPrimClass, &out, &items,
+                                                                 stream) != NNBVH_OK)
+            fatal("EnqueueClosestItemsIndexed");
+    }
+    // dOccluded (required): 0 recorded, 1 occluded, 2 = test the candidates, then RecordShadow with an array that is 1
+    // everywhere but on the rays resolved as unoccluded
+    void IntersectShadowQueue(int maxRays, const nnbvh_ray_soa &shadowQueue, const int32_t *dSize, const float *dLd,
+                              const float *dRu, const float *dRl, const int32_t *dPixelIndex, float *dL,
+                              int64_t nPixels, void *stream, uint8_t *dOccluded, const nnbvh_host_candidates &c) const {
+        if (nnbvh_wavefront_intersect_shadow_candidates(scene_, maxRays, &shadowQueue, dSize, dLd, dRu, dRl, dPixelIndex,
+                                                        dL, nPixels, dOccluded, &c, stream) != NNBVH_OK)
+            fatal("IntersectShadowQueue (candidates)");
+    }
+    static void RecordShadow(const uint8_t *dOccluded, int maxRays, const int32_t *dSize, const float *dLd,
+                             const float *dRu, const float *dRl, const int32_t *dPixelIndex, float *dL, int64_t nPixels,
+                             int device, void *stream) {
+        if (nnbvh_wavefront_record_shadow_device(dOccluded, maxRays, dSize, dLd, dRu, dRl, dPixelIndex, dL, nPixels,
+                                                 device, stream) != NNBVH_OK)
+            fatal("RecordShadow");
+    }
+    void IntersectClosestAndShadowItemsQueues(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &rayQueue,
+                                              const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass,
+                                              void *dHits, const nnbvh_closest_queues &out,
+                                              const nnbvh_closest_items &items, const nnbvh_host_candidates &c,
+                                              int maxShadowRays, const nnbvh_ray_soa &shadowQueue,
+                                              const int32_t *dShadowSize, const float *dLd, const float *dRu,
+                                              const float *dRl, const int32_t *dPixelIndex, float *dL, int64_t nPixels,
+                                              void *stream, uint8_t *dOccluded,
+                                              const nnbvh_host_candidates &shadowC) const {
+        if (nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
+                scene_, mesh, maxRays, &rayQueue, dSize, dPrimClass, nPrimClass, dHits, &out, &items, &c, maxShadowRays,
+                &shadowQueue, dShadowSize, dLd, dRu, dRl, dPixelIndex, dL, nPixels, dOccluded, &shadowC,
+                stream) != NNBVH_OK)
+            fatal("IntersectClosestAndShadowItemsQueues (candidates)");
+    }
     // == WavefrontAggregate::IntersectShadowTr (wavefront/integrator.h:48-49), scenes without media
     void IntersectShadowTrQueue(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &shadowQueue,
                                 const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass,

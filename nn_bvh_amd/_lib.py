@@ -82,6 +82,9 @@ EXPORTS = [
     "nnbvh_wavefront_intersect_closest_items", "nnbvh_wavefront_intersect_closest_and_shadow_items",
     "nnbvh_intersect_closest_candidates", "nnbvh_intersect_any_candidates",
     "nnbvh_intersect_closest_candidates_device", "nnbvh_intersect_any_candidates_device",
+    "nnbvh_trace_batches_candidates_device", "nnbvh_wavefront_intersect_closest_items_candidates",
+    "nnbvh_wavefront_enqueue_closest_items_indexed_device", "nnbvh_wavefront_intersect_shadow_candidates",
+    "nnbvh_wavefront_intersect_closest_and_shadow_items_candidates",
 ]
 
 
@@ -264,6 +267,17 @@ def lib():
     L.nnbvh_intersect_closest_candidates_device.argtypes = [vp, vp, i64, vp, hc, vp]
     L.nnbvh_intersect_any_candidates_device.restype = i32
     L.nnbvh_intersect_any_candidates_device.argtypes = [vp, vp, i64, vp, hc, vp]
+    L.nnbvh_trace_batches_candidates_device.restype = i32
+    L.nnbvh_trace_batches_candidates_device.argtypes = [vp, vp, i32, hc, vp]
+    L.nnbvh_wavefront_intersect_closest_items_candidates.restype = i32
+    L.nnbvh_wavefront_intersect_closest_items_candidates.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, hc, vp]
+    L.nnbvh_wavefront_enqueue_closest_items_indexed_device.restype = i32
+    L.nnbvh_wavefront_enqueue_closest_items_indexed_device.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp]
+    L.nnbvh_wavefront_intersect_shadow_candidates.restype = i32
+    L.nnbvh_wavefront_intersect_shadow_candidates.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, hc, vp]
+    L.nnbvh_wavefront_intersect_closest_and_shadow_items_candidates.restype = i32
+    L.nnbvh_wavefront_intersect_closest_and_shadow_items_candidates.argtypes = [
+        vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, hc, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, hc, vp]
     L.nnbvh_scene_sched_stats.restype = i32
     L.nnbvh_scene_sched_stats.argtypes = [vp, vp, i32]
     _lib = L

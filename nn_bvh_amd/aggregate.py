@@ -295,6 +295,24 @@ class BVHAggregate:
         check(_lib.lib().nnbvh_trace_batches_device(self._h, ptr(arr), len(arr), stream),
               "nnbvh_trace_batches_device")
 
+    def trace_batches_candidates_device(self, batches, candidates, stream=0):
+        """trace_batches_device with host candidates per batch (nnbvh_trace_batches_candidates_device).
+        candidates[b]: None for a plain batch, else (capacity, d_count, d_before, d_prim, d_instance) device
+        pointers (d_before None for an "any" batch), filled as by intersect[_p]_candidates_device."""
+        assert len(candidates) == len(batches)
+        arr = np.zeros(len(batches), _lib.BATCH_DTYPE)
+        for i, b in enumerate(batches):
+            arr[i]["kind"] = {"closest": 0, "any": 1}[b[0]]
+            arr[i]["d_rays"], arr[i]["n"], arr[i]["d_out"] = b[1], b[2], b[3]
+            if len(b) > 4:
+                arr[i]["d_nodes_visited"], arr[i]["d_prim_tests"] = b[4] or 0, b[5] or 0
+        cs = (_lib.HostCandidates * max(len(batches), 1))()
+        for i, c in enumerate(candidates):
+            if c is not None:
+                cs[i] = _lib.HostCandidates(int(c[0]), c[1], c[2], c[3], c[4])
+        check(_lib.lib().nnbvh_trace_batches_candidates_device(self._h, ptr(arr), len(arr), cs, stream),
+              "nnbvh_trace_batches_candidates_device")
+
     def intersect_p_device(self, d_rays, d_occ, n, d_visited=None, d_tests=None, stream=0):
         check(_lib.lib().nnbvh_intersect_any_device(self._h, d_rays, n, d_occ, d_visited, d_tests,
                                                     stream), "nnbvh_intersect_any_device")

@@ -920,12 +920,21 @@ static Workspace *workspace_for(nnbvh_scene *s, hipStream_t stream) {
     return &(s->workspaces[stream] = w);
 }
 
-// hc (modes 0 / 2, nullable): candidate mode; its count (and before) arrays are zeroed here, and scenes with
-// host-only primitives run the HOSTC instances, which fill them in; other scenes run the plain instances
+// the count (and, closest hit, before) arrays of a candidate call start at zero: a kernel node on `stream`
+static bool zero_candidates(const nnbvh_scene *s, const nnbvh_host_candidates *hc, int64_t n, bool closest,
+                            hipStream_t stream) {
+    return hip_ok(launch_zero_words(hc->count, (long)n, s->n_cus * 8, stream), "candidate count reset launch") &&
+           (!closest || !hc->before ||
+            hip_ok(launch_zero_words(hc->before, (long)n, s->n_cus * 8, stream), "candidate before reset launch"));
+}
+
+// hc (modes 0 / 2, nullable): candidate mode; its count (and before) arrays are zeroed here (hc_zeroed: the caller
+// has done it), and scenes with host-only primitives run the HOSTC instances, which fill them in; other scenes run
+// the plain instances
 static int launch(nnbvh_scene *s, int mode, const void *d_rays, int64_t n, void *d_hits,
                   void *d_occ, void *d_vis, void *d_tests, hipStream_t stream, Workspace *w,
                   const int32_t *d_n = nullptr, const nnbvh_ray_soa *soa = nullptr,
-                  const nnbvh_host_candidates *hc = nullptr) {
+                  const nnbvh_host_candidates *hc = nullptr, bool hc_zeroed = false) {
     TraceParams p{};
     if (soa) p.soa = *soa;  // d_rays == nullptr: the kernel reads the queue's SOA slices itself
     p.wide = s->d_wide;
@@ -954,9 +963,10 @@ static int launch(nnbvh_scene *s, int mode, const void *d_rays, int64_t n, void 
     p.nBatches = 0;
     p.anyMask = 0;
     if (hc) {
-        if (!hip_ok(hipMemsetAsync(hc->count, 0, (size_t)n * sizeof(int32_t), stream), "hipMemsetAsync(count)") ||
-            (hc->before && !hip_ok(hipMemsetAsync(hc->before, 0, (size_t)n * sizeof(int32_t), stream),
-                                   "hipMemsetAsync(before)")))
+        if (!hc_zeroed &&
+            (!hip_ok(hipMemsetAsync(hc->count, 0, (size_t)n * sizeof(int32_t), stream), "hipMemsetAsync(count)") ||
+             (hc->before && !hip_ok(hipMemsetAsync(hc->before, 0, (size_t)n * sizeof(int32_t), stream),
+                                    "hipMemsetAsync(before)"))))
             return NNBVH_ERR_DEVICE;
         if (s->has_host_prims) {
             p.hcCap = hc->capacity;
@@ -1135,8 +1145,11 @@ int nnbvh_intersect_any_candidates(nnbvh_scene *s, const nnbvh_ray *rays, int64_
 
 // One mode-3 launch over up to kMaxFusedBatches closest-hit / occlusion-only batches (the caller has checked that
 // the scene and the batches allow it).  d_n: nullable array of nullable device-resident batch sizes.
+// cands (nullable): cands[i] belongs to batches[i], capacity 0 = a plain batch.  Their count / before arrays are zeroed
+// by kernel nodes; scenes with host-only primitives then run the kernel's candidate-mode instances (ray records only).
 static int launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream, const nnbvh_batch *batches,
-                                int n_batches, const int32_t *const *d_n, const nnbvh_ray_soa *const *soas = nullptr) {
+                                int n_batches, const int32_t *const *d_n, const nnbvh_ray_soa *const *soas = nullptr,
+                                const nnbvh_host_candidates *cands = nullptr) {
     TraceParams p{};
     p.wide = s->d_wide;
     p.prims = s->d_prims;
@@ -1165,13 +1178,25 @@ static int launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream
         if (soas && soas[i]) p.bSoa[b] = *soas[i];  // with d_rays == nullptr: read as SOA slices
         if (batches[i].kind == NNBVH_BATCH_ANY) p.anyMask |= 1u << b;
         total += batches[i].n;
+        if (cands && cands[i].capacity > 0) {
+            const bool closest = batches[i].kind == NNBVH_BATCH_CLOSEST;
+            if (!zero_candidates(s, &cands[i], batches[i].n, closest, stream)) return NNBVH_ERR_DEVICE;
+            if (s->has_host_prims) {
+                p.hcCap = 1;  // selects the candidate-mode instances
+                p.bHcCap[b] = cands[i].capacity;
+                p.bHcCount[b] = cands[i].count;
+                p.bHcBefore[b] = closest ? cands[i].before : nullptr;
+                p.bHcPrim[b] = cands[i].prim;
+                p.bHcInst[b] = cands[i].instance;
+            }
+        }
     }
     if (p.nBatches == 0) return NNBVH_OK;
     p.n = (long)total;
     if (!hip_ok(launch_zero_queue(w->queue, kMaxFusedBatches * kMaxQueues * kQueueStrideWords, stream),
                 "queue reset launch"))
         return NNBVH_ERR_DEVICE;
-    int blocks = grid_blocks(s, 3);
+    int blocks = grid_blocks(s, 3, p.hcCap);
     const int64_t need = (total + kBlockThreads - 1) / kBlockThreads;
     if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
     if (!hip_ok(launch_trace(3, p, s->window, s->instanced, patch_bits(s), blocks, stream, nullptr),
@@ -1188,17 +1213,38 @@ static bool batches_fusable(const nnbvh_scene *s, const nnbvh_batch *batches, in
     return fusable;
 }
 
-int nnbvh_trace_batches_device(nnbvh_scene *s, const nnbvh_batch *batches, int n_batches,
-                               void *stream_) {
+// what is wrong with a candidates struct (closest: before is an output too), or nullptr; capacity 0 = "no candidates"
+// is the caller's to allow
+static const char *candidates_fault(const nnbvh_host_candidates *c, bool closest) {
+    if (!c) return "candidates is NULL";
+    if (c->capacity < 1 || c->capacity > 16) return "capacity must be 1..16";
+    if (!c->count || !c->prim || !c->instance) return "count, prim and instance are required";
+    if (closest && !c->before) return "before is required for closest hit";
+    return nullptr;
+}
+
+} // extern "C"
+
+// nnbvh_trace_batches_device and its candidates form (cands nullable; cands[i] belongs to batches[i])
+static int trace_batches(const char *fn, nnbvh_scene *s, const nnbvh_batch *batches, int n_batches,
+                         const nnbvh_host_candidates *cands, void *stream_) {
     if (!s || n_batches < 0 || (n_batches > 0 && !batches)) {
-        set_error("trace_batches_device: bad argument");
+        set_error(std::string(fn) + ": bad argument");
         return NNBVH_ERR_ARG;
     }
     for (int i = 0; i < n_batches; ++i) {
         const nnbvh_batch &b = batches[i];
         if ((b.kind != NNBVH_BATCH_CLOSEST && b.kind != NNBVH_BATCH_ANY) || b.n < 0 ||
             b.n >= 0x7fffffffLL || (b.n > 0 && (!b.d_rays || !b.d_out))) {
-            set_error("trace_batches_device: bad batch (kind, size or null buffer)");
+            set_error(std::string(fn) + ": bad batch (kind, size or null buffer)");
+            return NNBVH_ERR_ARG;
+        }
+        if (!cands || cands[i].capacity == 0) continue;
+        const char *why = candidates_fault(&cands[i], b.kind == NNBVH_BATCH_CLOSEST);
+        if (!why && b.kind == NNBVH_BATCH_ANY && (b.d_nodes_visited || b.d_prim_tests))
+            why = "an any-hit batch has exact counts or candidates, not both";
+        if (why) {
+            set_error(std::string(fn) + ": batch candidates: " + why);
             return NNBVH_ERR_ARG;
         }
     }
@@ -1213,7 +1259,7 @@ int nnbvh_trace_batches_device(nnbvh_scene *s, const nnbvh_batch *batches, int n
     if (fusable) {
         Workspace *w = workspace_for(s, stream);
         if (!w) return NNBVH_ERR_DEVICE;
-        return launch_fused_batches(s, w, stream, batches, n_batches, nullptr);
+        return launch_fused_batches(s, w, stream, batches, n_batches, nullptr, nullptr, cands);
     }
     if (!s->ev_fork) {
         bool ok = hip_ok(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming), "hipEventCreate");
@@ -1236,11 +1282,19 @@ int nnbvh_trace_batches_device(nnbvh_scene *s, const nnbvh_batch *batches, int n
         Workspace *w = workspace_for(s, s->side[k]);
         if (!w) return NNBVH_ERR_DEVICE;
         int rc;
+        nnbvh_host_candidates hc{};  // one candidate launch per batch (modes 0 / 2), forked and joined like the others
+        if (cands && cands[i].capacity > 0) {
+            hc = cands[i];
+            if (b.kind == NNBVH_BATCH_ANY) hc.before = nullptr;  // not an output of any hit
+            if (!zero_candidates(s, &hc, b.n, true, s->side[k])) return NNBVH_ERR_DEVICE;
+        }
+        const nnbvh_host_candidates *hcp = hc.capacity > 0 ? &hc : nullptr;
         if (b.kind == NNBVH_BATCH_CLOSEST)
-            rc = launch(s, 0, b.d_rays, b.n, b.d_out, nullptr, nullptr, nullptr, s->side[k], w);
+            rc = launch(s, 0, b.d_rays, b.n, b.d_out, nullptr, nullptr, nullptr, s->side[k], w, nullptr, nullptr, hcp,
+                        true);
         else
             rc = launch(s, (b.d_nodes_visited || b.d_prim_tests) ? 1 : 2, b.d_rays, b.n, nullptr,
-                        b.d_out, b.d_nodes_visited, b.d_prim_tests, s->side[k], w);
+                        b.d_out, b.d_nodes_visited, b.d_prim_tests, s->side[k], w, nullptr, nullptr, hcp, true);
         if (rc != NNBVH_OK) return rc;
     }
     for (int k = 0; k < nnbvh_scene::kSideStreams; ++k) {
@@ -1250,6 +1304,22 @@ int nnbvh_trace_batches_device(nnbvh_scene *s, const nnbvh_batch *batches, int n
             return NNBVH_ERR_DEVICE;
     }
     return NNBVH_OK;
+}
+
+extern "C" {
+
+int nnbvh_trace_batches_device(nnbvh_scene *s, const nnbvh_batch *batches, int n_batches,
+                               void *stream) {
+    return trace_batches("trace_batches_device", s, batches, n_batches, nullptr, stream);
+}
+
+int nnbvh_trace_batches_candidates_device(nnbvh_scene *s, const nnbvh_batch *batches, int n_batches,
+                                          const nnbvh_host_candidates *cands, void *stream) {
+    if (n_batches > 0 && !cands) {
+        set_error("trace_batches_candidates_device: candidates is NULL");
+        return NNBVH_ERR_ARG;
+    }
+    return trace_batches("trace_batches_candidates_device", s, batches, n_batches, cands, stream);
 }
 
 // ---- wavefront queues (wavefront/aggregate.cpp:34-68 on the device) ---------------------------
@@ -1808,6 +1878,230 @@ int nnbvh_wavefront_intersect_closest_and_shadow_items(
     rc = launch_items(m, max_rays, ray_queue, d_size, hits, d_prim_class, n_prim_class, out, items, stream);
     if (rc != NNBVH_OK) return rc;
     if (!hip_ok(launch_wf_record_shadow(occ, WavefrontCount{max_shadow_rays, d_shadow_size}, d_Ld, d_r_u, d_r_l,
+                                        d_pixel_index, d_L, (long)n_pixels, s->n_cus * 8, stream),
+                "shadow record kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+// ---- the wavefront calls with host candidates (include/nnbvh.h) -----------------------------------------------
+// Scenes without host-only primitives run the plain calls' kernels (lean and SOA-reading where they apply) over
+// zeroed count / before arrays; scenes with them gather the queue into ray records, as the plain calls do.
+static bool wf_candidates_ok(const char *fn, const nnbvh_host_candidates *c, bool closest) {
+    const char *why = candidates_fault(c, closest);
+    if (why) set_error(std::string(fn) + ": " + why);
+    return !why;
+}
+
+// the trace half of the closest call: d_hits = candidate-mode records, c filled in (the caller holds the lock)
+static int closest_trace_candidates(nnbvh_scene *s, Workspace *w, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                                    const int32_t *d_size, void *d_hits, const nnbvh_host_candidates *c,
+                                    hipStream_t stream) {
+    if (!zero_candidates(s, c, max_rays, true, stream)) return NNBVH_ERR_DEVICE;
+    if (!s->has_host_prims) return closest_trace(s, w, max_rays, ray_queue, d_size, d_hits, stream);
+    if (!grow(&w->d_in, &w->in_bytes, (size_t)max_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
+        return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_wf_gather(*ray_queue, WavefrontCount{max_rays, d_size}, w->d_in, s->n_cus * 8, stream),
+                "gather kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return launch(s, 0, w->d_in, max_rays, d_hits, nullptr, nullptr, nullptr, stream, w, d_size, nullptr, c, true);
+}
+
+// ... of the shadow call: occ = 0 / 1 / 2, c filled in (before is not an output of any hit)
+static int shadow_trace_candidates(nnbvh_scene *s, Workspace *w, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+                                   const int32_t *d_size, uint8_t *occ, const nnbvh_host_candidates *c,
+                                   hipStream_t stream) {
+    nnbvh_host_candidates any = *c;
+    any.before = nullptr;
+    if (!zero_candidates(s, &any, max_rays, false, stream)) return NNBVH_ERR_DEVICE;
+    if (scene_runs_lean(s))
+        return launch(s, 2, nullptr, max_rays, nullptr, occ, nullptr, nullptr, stream, w, d_size, shadow_queue);
+    if (!grow(&w->d_in, &w->in_bytes, (size_t)max_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
+        return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_wf_gather(*shadow_queue, WavefrontCount{max_rays, d_size}, w->d_in, s->n_cus * 8, stream),
+                "gather kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return launch(s, 2, w->d_in, max_rays, nullptr, occ, nullptr, nullptr, stream, w, d_size, nullptr, &any, true);
+}
+
+// the enqueue with the candidate counts: a ray with count != 0 is the caller's, whatever its record says
+static int launch_items_candidates(const nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                   const nnbvh_ray_soa *ray_queue, const int32_t *d_size, const void *d_hits,
+                                   const uint8_t *d_prim_class, int64_t n_prim_class, const nnbvh_closest_queues *out,
+                                   const nnbvh_closest_items *items, const nnbvh_host_candidates *c,
+                                   hipStream_t stream) {
+    if (!hip_ok(launch_wf_enqueue_closest_items(m->d, d_hits, WavefrontCount{max_rays, d_size}, *ray_queue,
+                                                d_prim_class, (long)n_prim_class, *out, *items, m->n_cus * 8, stream,
+                                                s->has_host_prims ? c->count : nullptr, nullptr, max_rays),
+                "work-item enqueue kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_wavefront_intersect_closest_items_candidates(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                       const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                                       const uint8_t *d_prim_class, int64_t n_prim_class,
+                                                       void *d_hits, const nnbvh_closest_queues *out,
+                                                       const nnbvh_closest_items *items,
+                                                       const nnbvh_host_candidates *c, void *stream_) {
+    const char *fn = "wavefront_intersect_closest_items_candidates";
+    if (!s || (max_rays > 0 && !d_hits)) {
+        set_error(std::string(fn) + ": bad argument (scene and d_hits are required)");
+        return NNBVH_ERR_ARG;
+    }
+    if (!items_args_ok(fn, m, max_rays, ray_queue, n_prim_class, out, items) || !wf_candidates_ok(fn, c, true))
+        return NNBVH_ERR_ARG;
+    if (s->device != m->device) {
+        set_error(std::string(fn) + ": scene and shading mesh live on different devices");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    hipStream_t stream = (hipStream_t)stream_;
+    Workspace *w = workspace_for(s, stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    const int rc = closest_trace_candidates(s, w, max_rays, ray_queue, d_size, d_hits, c, stream);
+    if (rc != NNBVH_OK) return rc;
+    return launch_items_candidates(s, m, max_rays, ray_queue, d_size, d_hits, d_prim_class, n_prim_class, out, items,
+                                   c, stream);
+}
+
+int nnbvh_wavefront_enqueue_closest_items_indexed_device(const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                         const nnbvh_ray_soa *ray_queue, const int32_t *d_index,
+                                                         const int32_t *d_index_size, int32_t max_index,
+                                                         const void *d_hits, const uint8_t *d_prim_class,
+                                                         int64_t n_prim_class, const nnbvh_closest_queues *out,
+                                                         const nnbvh_closest_items *items, void *stream) {
+    const char *fn = "wavefront_enqueue_closest_items_indexed_device";
+    if (!items_args_ok(fn, m, max_rays, ray_queue, n_prim_class, out, items)) return NNBVH_ERR_ARG;
+    if (max_index < 0 || (max_index > 0 && max_rays > 0 && (!d_index || !d_hits))) {
+        set_error(std::string(fn) + ": no index list or no hit records");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0 || max_index == 0) return NNBVH_OK;
+    DeviceGuard guard(m->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_wf_enqueue_closest_items(m->d, d_hits, WavefrontCount{max_index, d_index_size}, *ray_queue,
+                                                d_prim_class, (long)n_prim_class, *out, *items, m->n_cus * 8,
+                                                (hipStream_t)stream, nullptr, d_index, max_rays),
+                "work-item enqueue kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+static bool shadow_args_ok(const char *fn, int32_t max_rays, const nnbvh_ray_soa *shadow_queue, const float *d_Ld,
+                           const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, const float *d_L,
+                           int64_t n_pixels, const uint8_t *d_occluded) {
+    if (max_rays < 0 || n_pixels < 0 ||
+        (max_rays > 0 &&
+         (!soa_ok(shadow_queue) || !d_Ld || !d_r_u || !d_r_l || !d_pixel_index || !d_L || !d_occluded))) {
+        set_error(std::string(fn) + ": bad argument (d_occluded is required)");
+        return false;
+    }
+    return true;
+}
+
+int nnbvh_wavefront_intersect_shadow_candidates(nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+                                                const int32_t *d_size, const float *d_Ld, const float *d_r_u,
+                                                const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                                int64_t n_pixels, uint8_t *d_occluded,
+                                                const nnbvh_host_candidates *c, void *stream_) {
+    const char *fn = "wavefront_intersect_shadow_candidates";
+    if (!s) {
+        set_error(std::string(fn) + ": bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    if (!shadow_args_ok(fn, max_rays, shadow_queue, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, n_pixels, d_occluded) ||
+        !wf_candidates_ok(fn, c, false))
+        return NNBVH_ERR_ARG;
+    if (max_rays == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    hipStream_t stream = (hipStream_t)stream_;
+    Workspace *w = workspace_for(s, stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    const int rc = shadow_trace_candidates(s, w, max_rays, shadow_queue, d_size, d_occluded, c, stream);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_wf_record_shadow(d_occluded, WavefrontCount{max_rays, d_size}, d_Ld, d_r_u, d_r_l,
+                                        d_pixel_index, d_L, (long)n_pixels, s->n_cus * 8, stream),
+                "shadow record kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, const nnbvh_host_candidates *c,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded, const nnbvh_host_candidates *shadow_c, void *stream_) {
+    const char *fn = "wavefront_intersect_closest_and_shadow_items_candidates";
+    if (!s || (max_rays > 0 && !d_hits)) {
+        set_error(std::string(fn) + ": bad argument (scene and d_hits are required)");
+        return NNBVH_ERR_ARG;
+    }
+    // everything is checked before anything is launched, so that a bad argument leaves both sides untouched
+    if (!items_args_ok(fn, m, max_rays, ray_queue, n_prim_class, out, items) || !wf_candidates_ok(fn, c, true) ||
+        !shadow_args_ok(fn, max_shadow_rays, shadow_queue, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, n_pixels,
+                        d_occluded) ||
+        !wf_candidates_ok(fn, shadow_c, false))
+        return NNBVH_ERR_ARG;
+    if (s->device != m->device) {
+        set_error(std::string(fn) + ": scene and shading mesh live on different devices");
+        return NNBVH_ERR_ARG;
+    }
+    nnbvh_batch probe[2] = {{NNBVH_BATCH_CLOSEST, 0, nullptr, max_rays, nullptr, nullptr, nullptr},
+                            {NNBVH_BATCH_ANY, 0, nullptr, max_shadow_rays, nullptr, nullptr, nullptr}};
+    if (max_rays <= 0 || max_shadow_rays <= 0 || !batches_fusable(s, probe, 2)) {
+        // the scenes and sizes the one-launch form does not cover: the two calls one after the other
+        int rc = nnbvh_wavefront_intersect_shadow_candidates(s, max_shadow_rays, shadow_queue, d_shadow_size, d_Ld,
+                                                             d_r_u, d_r_l, d_pixel_index, d_L, n_pixels, d_occluded,
+                                                             shadow_c, stream_);
+        if (rc != NNBVH_OK) return rc;
+        return nnbvh_wavefront_intersect_closest_items_candidates(s, m, max_rays, ray_queue, d_size, d_prim_class,
+                                                                  n_prim_class, d_hits, out, items, c, stream_);
+    }
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    hipStream_t stream = (hipStream_t)stream_;
+    Workspace *w = workspace_for(s, stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    int rc;
+    if (!s->has_host_prims) {  // today's one-launch kernels; every count is zero
+        nnbvh_host_candidates any = *shadow_c;
+        any.before = nullptr;
+        if (!zero_candidates(s, c, max_rays, true, stream) || !zero_candidates(s, &any, max_shadow_rays, false, stream))
+            return NNBVH_ERR_DEVICE;
+        rc = closest_and_shadow_trace(s, w, max_rays, ray_queue, d_size, d_hits, max_shadow_rays, shadow_queue,
+                                      d_shadow_size, d_occluded, stream);
+    } else {
+        const size_t closest_bytes = (size_t)max_rays * sizeof(nnbvh_ray);
+        if (!grow(&w->d_in, &w->in_bytes, closest_bytes + (size_t)max_shadow_rays * sizeof(nnbvh_ray),
+                  "hipMalloc(wavefront rays)"))
+            return NNBVH_ERR_DEVICE;
+        void *closest_rays = w->d_in, *shadow_rays = (char *)w->d_in + closest_bytes;
+        if (!hip_ok(launch_wf_gather(*ray_queue, WavefrontCount{max_rays, d_size}, closest_rays, s->n_cus * 8, stream),
+                    "gather kernel launch") ||
+            !hip_ok(launch_wf_gather(*shadow_queue, WavefrontCount{max_shadow_rays, d_shadow_size}, shadow_rays,
+                                     s->n_cus * 8, stream),
+                    "gather kernel launch"))
+            return NNBVH_ERR_DEVICE;
+        const nnbvh_batch batches[2] = {{NNBVH_BATCH_CLOSEST, 0, closest_rays, max_rays, d_hits, nullptr, nullptr},
+                                        {NNBVH_BATCH_ANY, 0, shadow_rays, max_shadow_rays, d_occluded, nullptr, nullptr}};
+        const int32_t *sizes[2] = {d_size, d_shadow_size};
+        const nnbvh_host_candidates cands[2] = {*c, *shadow_c};
+        rc = launch_fused_batches(s, w, stream, batches, 2, sizes, nullptr, cands);
+    }
+    if (rc != NNBVH_OK) return rc;
+    rc = launch_items_candidates(s, m, max_rays, ray_queue, d_size, d_hits, d_prim_class, n_prim_class, out, items, c,
+                                 stream);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_wf_record_shadow(d_occluded, WavefrontCount{max_shadow_rays, d_shadow_size}, d_Ld, d_r_u, d_r_l,
                                         d_pixel_index, d_L, (long)n_pixels, s->n_cus * 8, stream),
                 "shadow record kernel launch"))
         return NNBVH_ERR_DEVICE;

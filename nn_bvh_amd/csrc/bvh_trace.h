@@ -57,9 +57,18 @@ struct TraceParams {
     int32_t *hcBefore;      // [n], mode 0: candidates met before the device hit that stands (zeroed before launch)
     int32_t *hcPrim;        // [n * K]: nnbvh_prim.id of each candidate, traversal order
     int32_t *hcInst;        // [n * K]: 0 = top level, k + 1 = inside instance k
+    // ... of mode 3 (its HOSTC instances; hcCap > 0 only selects them): the same five per batch, picked by the lane's
+    // batch tag.  bHcCap[b] == 0: batch b is a plain batch, a host-only primitive voids its ray as in the plain instances
+    int bHcCap[kMaxFusedBatches];
+    int32_t *bHcCount[kMaxFusedBatches];
+    int32_t *bHcBefore[kMaxFusedBatches];  // closest batches only
+    int32_t *bHcPrim[kMaxFusedBatches];
+    int32_t *bHcInst[kMaxFusedBatches];
 };
 
 hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream);
+// ... and the same for a per-ray int32 array (candidate counts, `before`): a kernel node, not a memset
+hipError_t launch_zero_words(int32_t *words, long n, int maxBlocks, hipStream_t stream);
 
 // occupancy != nullptr: do not launch, report resident blocks per CU of that kernel instance
 // patches: bit 0 = the scene holds bilinear patches (0: kernel instances without the parked ray direction),

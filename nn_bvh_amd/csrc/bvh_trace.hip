@@ -84,13 +84,16 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // SOA = 1 (lean instances of modes 0, 2, 3 only): a batch without nnbvh_ray records (rays == nullptr) is read as the
 // SOA<Ray> slices of a wavefront queue — no gather pass.  Its own instances: the mere presence of the second fetch
 // path in the refill trip cost the one-launch step 1.3 % (9.31 -> 9.44 ms).
-// HOSTC = 1 (general instances of modes 0 and 2, window 8, scenes with host-only primitives): candidate mode.  A
+// HOSTC = 1 (general instances of modes 0, 2 and 3, window 8, scenes with host-only primitives): candidate mode.  A
 // host-only primitive no longer voids the ray: its id and the current instance are appended to the ray's list
 // (p.hcPrim / p.hcInst at ray * K, traversal order, the count in the kColdHost slot), and the walk goes on as
 // the walk that skips it, which is what the plain instances do already.  Closest hit: an accepted hit on a ray
 // with candidates stores how many came before it (p.hcBefore).  At retire the count goes to p.hcCount and the
 // record keeps its real instance unless the list overflowed (-1) or an alpha re-trace voided the ray (-2).
 // Instances of their own, so that the other instances' code is not touched.
+// MODE 3 (no ALPHA instances): every batch has its own five arrays (p.bHc*), picked by the lane's batch tag at the same
+// three sites; a batch with bHcCap[b] == 0 is a plain batch (its first host-only primitive "overflows" a list of
+// zero entries, so the record is void as in the plain instances, and nothing is written to candidate arrays).
 //
 // Tuning constants (each with its measurement; -D overrides are for A/B builds only).
 // waves/SIMD the register allocator must leave room for (measured in steady state: closest
@@ -120,12 +123,20 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 #ifndef NNBVH_ANIM_ENTER_WEIGHT
 #define NNBVH_ANIM_ENTER_WEIGHT 8
 #endif
+// entry b of a per-batch table of the kernel arguments (scalar loads and selects: no indexed access into the argument)
+template <typename T>
+__device__ __forceinline__ T pick_batch(const T (&a)[kMaxFusedBatches], int b) {
+    static_assert(kMaxFusedBatches == 4, "written out for four batches");
+    return b == 0 ? a[0] : (b == 1 ? a[1] : (b == 2 ? a[2] : a[3]));
+}
+
 template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
 __global__ __launch_bounds__(kBlockThreads, (INST ? 1 : (ALPHA ? (ALPHA == 2 ? NNBVH_MINW_ALPHA_PATCH : NNBVH_MINW_ALPHA) : ((MODE == 0 || MODE == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (PATCH ? 0 : NNBVH_LEAN_EXTRA_WAVES))))
 void trace_kernel(TraceParams p) {
     static_assert(PATCH || !INST, "two-level scenes need the ray direction");
     static_assert(PATCH || !ALPHA, "the alpha test hashes the ray direction");
-    static_assert(!HOSTC || (PATCH && (MODE == 0 || MODE == 2) && !SOA), "candidate mode: general instances of modes 0 / 2");
+    static_assert(!HOSTC || (PATCH && (MODE == 0 || MODE == 2 || (MODE == 3 && !ALPHA && W == 8)) && !SOA),
+                  "candidate mode: general instances of modes 0 / 2 / 3");
     // the stack window: entry k of a lane = (child reference, entry distance), the two words 64 dwords
     // apart so that one ds_read2st64 / ds_write2st64 with one address moves both
     __shared__ float s_stack[kBlockThreads / 64][W][2][64];
@@ -306,12 +317,22 @@ void trace_kernel(TraceParams p) {
                 // entries go straight to global memory) and walk on as if it were absent
                 const int c = __float_as_int(cold[kColdHost][lane]);
                 if (c >= 0) {  // -1 (overflow) and -2 (alpha re-trace) stay
-                    if (c < p.hcCap) {
-                        const long at = (long)__float_as_int(cold[kColdRi][lane]) * p.hcCap + c;
-                        p.hcPrim[at] = __float_as_int(s0.w);
-                        p.hcInst[at] = INST ? __float_as_int(cold[kCurInst][lane]) : 0;
+                    long ray = __float_as_int(cold[kColdRi][lane]);
+                    int cap = p.hcCap;
+                    int32_t *hcPrim = p.hcPrim, *hcInst = p.hcInst;
+                    if constexpr (MODE == 3) {  // the lane's batch has its own arrays
+                        const int b = (int)(ray >> kFusedIndexBits);
+                        ray &= (1 << kFusedIndexBits) - 1;
+                        cap = pick_batch(p.bHcCap, b);
+                        hcPrim = pick_batch(p.bHcPrim, b);
+                        hcInst = pick_batch(p.bHcInst, b);
                     }
-                    cold[kColdHost][lane] = __int_as_float(c < p.hcCap ? c + 1 : -1);
+                    if (c < cap) {
+                        const long at = ray * cap + c;
+                        hcPrim[at] = __float_as_int(s0.w);
+                        hcInst[at] = INST ? __float_as_int(cold[kCurInst][lane]) : 0;
+                    }
+                    cold[kColdHost][lane] = __int_as_float(c < cap ? c + 1 : -1);
                 }
             } else {
                 cold[kColdHost][lane] = 1.0f;
@@ -427,6 +448,13 @@ void trace_kernel(TraceParams p) {
                         const int c = __float_as_int(cold[kColdHost][lane]);
                         if (c > 0) p.hcBefore[__float_as_int(cold[kColdRi][lane])] = c;
                     }
+                    if constexpr (HOSTC && MODE == 3) {  // c > 0 only in a batch with candidate arrays
+                        const int c = __float_as_int(cold[kColdHost][lane]);
+                        if (c > 0) {
+                            const int tag = __float_as_int(cold[kColdRi][lane]);
+                            pick_batch(p.bHcBefore, tag >> kFusedIndexBits)[tag & ((1 << kFusedIndexBits) - 1)] = c;
+                        }
+                    }
                 } else {
                     found = true;
                 }
@@ -528,7 +556,35 @@ void trace_kernel(TraceParams p) {
         if (nIdle == 64 || (sR > sI && sR > sP)) {
             // ---- retire finished rays, refill idle lanes -------------------------------
             const int ri = isIdle ? (kLean ? riReg : __float_as_int(cold[kColdRi][lane])) : -1;
-            if (MODE == 3 && ri >= 0) {
+            if constexpr (MODE == 3 && HOSTC) {
+                // candidate mode of the one-launch kernel, a block of its own so that the plain instances' retire
+                // below stays as it is: the count goes to the batch's array; an any-hit ray is the caller's (2) when
+                // it met a host-only primitive, a closest-hit record is void only for count < 0
+                if (ri >= 0) {
+                    const int b = ri >> kFusedIndexBits;
+                    const long idx = ri & ((1 << kFusedIndexBits) - 1);
+                    void *outp = pick_batch(p.bOut, b);
+                    const int c = __float_as_int(cold[kColdHost][lane]);
+                    if (pick_batch(p.bHcCap, b) > 0) pick_batch(p.bHcCount, b)[idx] = c;
+                    if ((p.anyMask >> b) & 1u) {
+                        reinterpret_cast<uint8_t *>(outp)[idx] = found ? 1 : (c != 0 ? 2 : 0);
+                    } else {
+                        float4 h0, h1;
+                        h0.x = cold[kColdHit][lane];
+                        h0.y = tMax;
+                        h0.z = cold[kColdHit + 1][lane];
+                        h0.w = cold[kColdHit + 2][lane];
+                        h1.x = cold[kColdHit + 3][lane];
+                        h1.y = __int_as_float(visited);
+                        h1.z = __int_as_float(tests);
+                        h1.w = INST ? cold[kHitInst][lane] : 0.0f;
+                        if (c < 0) h1.w = __int_as_float(-1);
+                        float4 *out = reinterpret_cast<float4 *>(outp) + 2 * idx;
+                        out[0] = h0;
+                        out[1] = h1;
+                    }
+                }
+            } else if (MODE == 3 && ri >= 0) {
                 const int b = ri >> kFusedIndexBits;
                 const long idx = ri & ((1 << kFusedIndexBits) - 1);
                 void *outp = b == 0 ? p.bOut[0] : (b == 1 ? p.bOut[1] : (b == 2 ? p.bOut[2] : p.bOut[3]));
@@ -780,6 +836,11 @@ static hipError_t launch_general(const TraceParams &p, int instanced, int patche
 static hipError_t launch_fused(const TraceParams &p, int window, int instanced, int patches, int blocks,
                                hipStream_t stream, int *occupancy) {
     if (window != 8 || (patches & 2)) return hipErrorInvalidValue;
+    if (p.hcCap > 0) {  // candidate mode (some batch has candidate arrays; the batches come as ray records)
+        if (instanced) return p.anim ? launch_one<3, 8, 2, 1, 0, 0, 1>(p, blocks, stream, occupancy)
+                                     : launch_one<3, 8, 1, 1, 0, 0, 1>(p, blocks, stream, occupancy);
+        return launch_one<3, 8, 0, 1, 0, 0, 1>(p, blocks, stream, occupancy);
+    }
     if (instanced) return p.anim ? launch_one<3, 8, 2, 1>(p, blocks, stream, occupancy)
                                  : launch_one<3, 8, 1, 1>(p, blocks, stream, occupancy);
     bool soa = false;
@@ -820,6 +881,16 @@ __global__ void zero_queue_kernel(unsigned *queue, int words) {
 }
 hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream) {
     hipLaunchKernelGGL(zero_queue_kernel, dim3(1), dim3(256), 0, stream, queue, words);
+    return hipGetLastError();
+}
+
+__global__ void zero_words_kernel(int32_t *words, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) words[i] = 0;
+}
+hipError_t launch_zero_words(int32_t *words, long n, int maxBlocks, hipStream_t stream) {
+    long blocks = (n + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks < maxBlocks ? blocks : maxBlocks);
+    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, words, n);
     return hipGetLastError();
 }
 

@@ -37,6 +37,10 @@ struct ItemsParams {
     long nPrimClass;
     nnbvh_closest_queues out;
     nnbvh_closest_items items;
+    // the EXT instances only (at the end: the other instances read nothing behind `items`)
+    const int32_t *hcCount;  // nullable, per ray: != 0 = the ray has host candidates (or is void): needs_host only
+    const int32_t *index;    // nullable: the items are rays index[0 .. n) instead of 0 .. n (cnt counts the list)
+    int maxRays;             // rays the hit records / the ray queue hold: list entries outside [0, maxRays) are skipped
 };
 
 // intersect.h:19-29 (miss) and :56-128 (hit), plus the two cases the device cannot finish: a voided
@@ -121,7 +125,10 @@ __device__ __forceinline__ void store_item(SliceTable table, int at, int prim, b
 #ifndef NNBVH_ITEMS_LEAN_WAVES
 #define NNBVH_ITEMS_LEAN_WAVES 4
 #endif
-template <bool FULL>
+// EXT = 1: the forms that go with host candidates (include/nnbvh.h): a per-ray candidate count that sends a ray to
+// needs_host whatever its record says, and / or an index list of the rays to enqueue (the second pass over the
+// rays the caller has resolved).  Instances of their own: the plain ones stay as they are.
+template <bool FULL, bool EXT = false>
 __global__ __launch_bounds__(kItBlock, FULL ? 1 : NNBVH_ITEMS_LEAN_WAVES) void wf_enqueue_closest_items(
     ItemsParams p) {
     __shared__ float4 hitLds[kItItems][2][kItBlock];  // the chunk's hit records, 32 KB
@@ -137,9 +144,14 @@ __global__ __launch_bounds__(kItBlock, FULL ? 1 : NNBVH_ITEMS_LEAN_WAVES) void w
         int count[kItQueues] = {0, 0, 0, 0, 0, 0, 0};  // wave-uniform
 #pragma unroll
         for (int k = 0; k < kItItems; ++k) {
-            const long i = chunk + k * kItBlock + threadIdx.x;
+            long i = chunk + k * kItBlock + threadIdx.x;
             unsigned d = 0;
-            if (i < n) {
+            bool live = i < n;
+            if (EXT && live && p.index) {
+                i = p.index[i];
+                live = i >= 0 && i < p.maxRays;
+            }
+            if (live) {
                 const float4 h0 = p.hits[2 * i], h1 = p.hits[2 * i + 1];
                 hitLds[k][0][threadIdx.x] = h0;
                 hitLds[k][1][threadIdx.x] = h1;
@@ -148,6 +160,7 @@ __global__ __launch_bounds__(kItBlock, FULL ? 1 : NNBVH_ITEMS_LEAN_WAVES) void w
                 unsigned cls = NNBVH_CLASS_BASIC;
                 if (prim >= 0 && p.primClass && (long)prim < p.nPrimClass) cls = p.primClass[prim];
                 d = item_destinations<FULL>(p.m, prim, __float_as_int(h1.w), medium, cls);
+                if (EXT && p.hcCount && p.hcCount[i] != 0) d = kIHost;
             }
             dest |= d << (kItBits * k);
 #pragma unroll
@@ -175,8 +188,9 @@ __global__ __launch_bounds__(kItBlock, FULL ? 1 : NNBVH_ITEMS_LEAN_WAVES) void w
         for (int q = 0; q < kItQueues; ++q) run[q] = __builtin_amdgcn_readfirstlane(waveBase[wave][q]);  // SGPRs
 #pragma unroll 1
         for (int k = 0; k < kItItems; ++k) {
-            const int i = (int)(chunk + k * kItBlock + threadIdx.x);
+            int i = (int)(chunk + k * kItBlock + threadIdx.x);
             const unsigned d = (dest >> (kItBits * k)) & ((1u << kItBits) - 1);
+            if (EXT && d != 0 && p.index) i = p.index[i];  // d != 0: the slot is inside the list and its ray in range
             // an item is pushed to one queue, or to hit_area_light + one material queue: two slots
             int atLight = 0, at = 0;
 #pragma unroll
@@ -238,8 +252,12 @@ __global__ __launch_bounds__(kItBlock, FULL ? 1 : NNBVH_ITEMS_LEAN_WAVES) void w
 hipError_t launch_wf_enqueue_closest_items(const ShadingMeshDevice &m, const void *hits, WavefrontCount cnt,
                                            const nnbvh_ray_soa &soa, const uint8_t *primClass, long nPrimClass,
                                            const nnbvh_closest_queues &out, const nnbvh_closest_items &items,
-                                           int maxBlocks, hipStream_t stream) {
+                                           int maxBlocks, hipStream_t stream, const int32_t *hcCount,
+                                           const int32_t *index, int maxRays) {
     ItemsParams p;
+    p.hcCount = hcCount;
+    p.index = index;
+    p.maxRays = maxRays;
     p.m = MeshView{m.verts, m.triVerts, m.patchVerts, m.normals, m.uvs, m.tangents, m.faceIndices, m.triFlags,
                    m.nTris, m.defaultFlags, m.instances, m.nInstances, m.anim, m.animFwd};
     p.hits = (const float4 *)hits;
@@ -251,7 +269,12 @@ hipError_t launch_wf_enqueue_closest_items(const ShadingMeshDevice &m, const voi
     p.items = items;
     int blocks = (cnt.n + kItChunk - 1) / kItChunk;
     blocks = blocks < 1 ? 1 : (blocks < maxBlocks ? blocks : maxBlocks);
-    if (items_kernel_full(m))
+    if (hcCount || index) {
+        if (items_kernel_full(m))
+            hipLaunchKernelGGL((wf_enqueue_closest_items<true, true>), dim3(blocks), dim3(kItBlock), 0, stream, p);
+        else
+            hipLaunchKernelGGL((wf_enqueue_closest_items<false, true>), dim3(blocks), dim3(kItBlock), 0, stream, p);
+    } else if (items_kernel_full(m))
         hipLaunchKernelGGL(wf_enqueue_closest_items<true>, dim3(blocks), dim3(kItBlock), 0, stream, p);
     else
         hipLaunchKernelGGL(wf_enqueue_closest_items<false>, dim3(blocks), dim3(kItBlock), 0, stream, p);

@@ -7,6 +7,8 @@ the reference's SOA<Ray> (workitems.soa:40-50): six float arrays plus the queue'
 size; the output queues hold indices into the input queue, pushed by the device with the
 reference's rules (wavefront/intersect.h:16-156).  IntersectShadowTr / IntersectOneRandom come in
 their media-free form (see include/nnbvh.h)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -113,20 +115,63 @@ def _queues_record(queues):
     return qrec
 
 
+class HostCandidateArrays:
+    """Device arrays of nnbvh_host_candidates for a queue of `n` rays: count / before int32 [n], prim / instance
+    int32 [n, capacity] (entries beyond count keep their -1)."""
+
+    def __init__(self, n, capacity, device):
+        self.capacity = int(capacity)
+        n = max(int(n), 1)
+        self.count = torch.zeros(n, dtype=torch.int32, device=device)
+        self.before = torch.zeros(n, dtype=torch.int32, device=device)
+        self.prim = torch.full((n, self.capacity), -1, dtype=torch.int32, device=device)
+        self.instance = torch.full((n, self.capacity), -1, dtype=torch.int32, device=device)
+
+    def _wire(self):
+        return _lib.HostCandidates(self.capacity, self.count.data_ptr(), self.before.data_ptr(),
+                                   self.prim.data_ptr(), self.instance.data_ptr())
+
+    def numpy(self):
+        """Host copy as a candidates_dtype(capacity) array (synchronises)."""
+        from .aggregate import _pack_candidates
+        return _pack_candidates(self.count.cpu().numpy(), self.before.cpu().numpy(), self.prim.cpu().numpy(),
+                                self.instance.cpu().numpy())
+
+
 def enqueue_closest_items(shading_mesh, max_rays, ray_queue, hits, prim_class=None, items=None, needs_host=None,
-                          **queues):
+                          index=None, **queues):
     """nnbvh_wavefront_enqueue_closest_items_device: IntersectClosest's enqueue with the work items for hit
     records from any source (hits: device tensor of HIT_DTYPE rows).  queues: WorkQueues by
-    _lib.CLOSEST_QUEUES name; items: ItemSlices by _lib.ITEM_QUEUES name; needs_host: WorkQueue or None."""
+    _lib.CLOSEST_QUEUES name; items: ItemSlices by _lib.ITEM_QUEUES name; needs_host: WorkQueue or None.
+    index: a WorkQueue of ray indices: only those rays are enqueued, appended to the queues
+    (nnbvh_wavefront_enqueue_closest_items_indexed_device; the second pass of the host-candidates loop)."""
     dev = ray_queue.o.device
     pc = prim_class
     # the records must outlive the call: ptr() does not keep its array alive
     soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
+    if index is not None:
+        check(_lib.lib().nnbvh_wavefront_enqueue_closest_items_indexed_device(
+            shading_mesh._h, int(max_rays), ptr(soa), index.items.data_ptr(), index.size.data_ptr(),
+            int(index.capacity), hits.data_ptr(), pc.data_ptr() if pc is not None else None,
+            0 if pc is None else pc.numel(), ptr(qrec), ptr(irec), torch.cuda.current_stream(dev).cuda_stream),
+            "nnbvh_wavefront_enqueue_closest_items_indexed_device")
+        return
     check(_lib.lib().nnbvh_wavefront_enqueue_closest_items_device(
         shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), hits.data_ptr(),
         pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), ptr(qrec), ptr(irec),
         torch.cuda.current_stream(dev).cuda_stream),
         "nnbvh_wavefront_enqueue_closest_items_device")
+
+
+def record_shadow(max_rays, shadow_queue, occluded, Ld, r_u, r_l, pixel_index, L):
+    """nnbvh_wavefront_record_shadow_device: RecordShadowRayResult for a per-ray uint8 `occluded` array (entries
+    that are not 0 add nothing).  In the host-candidates loop: 1 everywhere but 0 on the rays the caller resolved
+    as unoccluded."""
+    dev = L.device
+    check(_lib.lib().nnbvh_wavefront_record_shadow_device(
+        occluded.data_ptr(), int(max_rays), shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(),
+        r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0], dev.index or 0,
+        torch.cuda.current_stream(dev).cuda_stream), "nnbvh_wavefront_record_shadow_device")
 
 
 class WavefrontAggregate:
@@ -251,6 +296,62 @@ class WavefrontAggregate:
             shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(),
             L.data_ptr(), L.shape[0], occluded.data_ptr() if occluded is not None else None,
             torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_closest_and_shadow_items")
+        return hits
+
+    def IntersectClosestItemsWithCandidates(self, max_rays, ray_queue, shading_mesh, candidates, hits, items=None,
+                                            needs_host=None, **queues):
+        """IntersectClosestItems that lists the host-only primitives a ray reached instead of voiding it
+        (nnbvh_wavefront_intersect_closest_items_candidates).  candidates: HostCandidateArrays of the queue's
+        capacity; hits (required): device tensor of HIT_DTYPE rows.  Rays with count 0 are routed as
+        IntersectClosestItems routes them; the others go to needs_host only, their candidate-mode record in hits:
+        resolve them (resolve_host_candidates), write the merged records back and enqueue them with
+        enqueue_closest_items(index=needs_host)."""
+        pc = self.prim_class
+        soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
+        c = candidates._wire()
+        check(_lib.lib().nnbvh_wavefront_intersect_closest_items_candidates(
+            self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
+            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), hits.data_ptr(), ptr(qrec),
+            ptr(irec), ctypes.byref(c), torch.cuda.current_stream(self.device).cuda_stream),
+            "nnbvh_wavefront_intersect_closest_items_candidates")
+        return hits
+
+    def IntersectShadowWithCandidates(self, max_rays, shadow_queue, Ld, r_u, r_l, pixel_index, L, occluded,
+                                      candidates):
+        """IntersectShadow with host candidates (nnbvh_wavefront_intersect_shadow_candidates): occluded (required,
+        uint8 [capacity]) gets 0 / 1 / 2; rays with 0 add to L, rays with 2 and count > 0 are the caller's to test
+        (resolve_host_candidates_any) and to record with record_shadow."""
+        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
+        for t in (Ld, r_u, r_l, L):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
+        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        soa, c = shadow_queue._wire(), candidates._wire()
+        check(_lib.lib().nnbvh_wavefront_intersect_shadow_candidates(
+            self.aggregate._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(),
+            r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0], occluded.data_ptr(), ctypes.byref(c),
+            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_shadow_candidates")
+
+    def IntersectClosestAndShadowItemsWithCandidates(self, max_rays, ray_queue, shading_mesh, candidates, hits,
+                                                     max_shadow_rays, shadow_queue, Ld, r_u, r_l, pixel_index, L,
+                                                     occluded, shadow_candidates, items=None, needs_host=None,
+                                                     **queues):
+        """IntersectClosestItemsWithCandidates and IntersectShadowWithCandidates in ONE launch of the traversal
+        kernel (nnbvh_wavefront_intersect_closest_and_shadow_items_candidates); same results as the two calls."""
+        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
+        for t in (Ld, r_u, r_l, L):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
+        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        pc = self.prim_class
+        soa, ssoa = ray_queue._wire(), shadow_queue._wire()
+        qrec, irec = _queues_record(queues), _items_record(items, needs_host)
+        c, sc = candidates._wire(), shadow_candidates._wire()
+        check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
+            self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
+            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), hits.data_ptr(), ptr(qrec),
+            ptr(irec), ctypes.byref(c), int(max_shadow_rays), ptr(ssoa), shadow_queue.size.data_ptr(), Ld.data_ptr(),
+            r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0], occluded.data_ptr(),
+            ctypes.byref(sc), torch.cuda.current_stream(self.device).cuda_stream),
+            "nnbvh_wavefront_intersect_closest_and_shadow_items_candidates")
         return hits
 
     def IntersectShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None):
