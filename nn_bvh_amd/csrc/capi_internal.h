@@ -1,0 +1,194 @@
+// capi_internal.h — what the host files of the C ABI share (bvh_capi.cpp, capi_trace.cpp, capi_wavefront.cpp,
+// capi_shading.cpp): the scene object, per-stream workspaces, the call prologue and the trace-job launcher.
+// Included by .cpp files only, never by device code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <mutex>
+#include <string>
+
+#include "bvh_trace.h"
+#include "interaction.h"
+
+namespace nnbvh {
+
+inline bool hip_ok(hipError_t e, const char *what) {
+    if (e == hipSuccess) return true;
+    set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return false;
+}
+
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hip_ok(hipSetDevice(dev), "hipSetDevice");
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+struct Workspace {
+    unsigned *queue = nullptr;  // kMaxQueues heads
+    uint2 *spill = nullptr;
+    // grow-only staging for the host-buffer entry points
+    void *d_in = nullptr, *d_out = nullptr, *d_aux0 = nullptr, *d_aux1 = nullptr;
+    size_t in_bytes = 0, out_bytes = 0, aux_bytes = 0;
+    void *d_hits = nullptr;  // hit records of the *_items calls made without d_hits
+    size_t hits_bytes = 0;
+    // grow-only scratch of the multi-pass entry points (IntersectShadowTr / IntersectOneRandom): ping-pong ray and
+    // hit buffers, per-item state, counters.  Per stream like the queue heads: the calls are asynchronous on their
+    // stream, so two streams must not share them
+    static constexpr int kScratch = 12;
+    void *scratch[kScratch] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[kScratch] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// one slot of the host-buffer pipeline (nnbvh_intersect_closest / _any): device chunk buffers, events and — for
+// callers with pageable memory — pinned staging buffers
+struct HostSlot {
+    hipEvent_t ev_in = nullptr, ev_traced = nullptr, ev_out = nullptr;  // rays uploaded / chunk traced / results down
+    void *d_in = nullptr, *h_in = nullptr;
+    size_t d_in_bytes = 0, h_in_bytes = 0;
+    void *d_out[3] = {nullptr, nullptr, nullptr}, *h_out[3] = {nullptr, nullptr, nullptr};
+    size_t d_out_bytes[3] = {0, 0, 0}, h_out_bytes[3] = {0, 0, 0};
+};
+
+}  // namespace nnbvh
+
+struct nnbvh_scene {
+    int device = 0;
+    int n_cus = 0;
+    int n_interior = 0;
+    int64_t n_slots = 0;
+    int depth = 0;
+    float bounds[6];
+    int root_ref = 0;
+    float4 *d_wide = nullptr;
+    float4 *d_prims = nullptr;
+    float *d_anim = nullptr;  // AnimatedPrimitive table (kAnimStride floats per instance), or null
+    size_t device_bytes = 0;
+    // tuning (speed only)
+    int window = 8;
+    int blocks_per_cu = 0;  // 0 = from the occupancy query
+    int xcd_queues = 1;
+    int prim_weight = 32;
+    int refill_weight = 8;
+    unsigned long long *d_stats = nullptr;  // diagnostics (NNBVH_STATS builds)
+    int instanced = 0;      // two-level scene: use the INST kernels
+    int has_host_prims = 0;
+    int has_patches = 1;    // 0: no bilinear patches, the lean kernels (no ray direction parked in LDS) run
+    int has_alpha = 0;      // 1: alpha-tested triangles present (the ALPHA kernels run), 2: alpha-tested patches too
+    int fused_batches = 1;  // nnbvh_trace_batches_device: one mode-3 launch where the batches allow it
+    int int_repeat = 3;
+    int prim_repeat = 2;
+    int max_grid_threads = 0;
+    double build_ms[1] = {0};  // device build time of nnbvh_scene_create_gpu_build
+    std::mutex mu;
+    std::map<hipStream_t, nnbvh::Workspace> workspaces;
+    static constexpr int kHostSlots = 3, kHostChunks = 6;
+    nnbvh::HostSlot host_slots[kHostSlots];
+    hipStream_t host_up = nullptr, host_trace = nullptr, host_down = nullptr;
+    int64_t host_chunk = 1 << 20;  // least rays per chunk of the host-buffer pipeline (at most kHostChunks chunks)
+    // fork/join machinery of nnbvh_trace_batches_device
+    static constexpr int kSideStreams = 4;
+    hipStream_t side[kSideStreams] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_fork = nullptr;
+    hipEvent_t ev_join[kSideStreams] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+struct nnbvh_shading_mesh {
+    int device = 0;
+    int n_cus = 0;
+    nnbvh::ShadingMeshDevice d;
+};
+
+namespace nnbvh {
+
+// One workspace per stream: launches on one stream are ordered, so they may share the
+// queue heads and the spill array; launches on different streams get their own.  (bvh_capi.cpp)
+Workspace *workspace_for(nnbvh_scene *s, hipStream_t stream);
+
+// one entry of the device's animation table (layout: anim_math.h; bvh_capi.cpp)
+void fill_anim_entry(const nnbvh_animated_transform &a, float *t);
+
+// The prologue of a call on a scene: the scene's device made current and its lock held for the call, and with a
+// stream that stream's workspace.
+struct SceneCall {
+    DeviceGuard guard;
+    std::unique_lock<std::mutex> lock;
+    Workspace *w = nullptr;
+    bool good;
+    explicit SceneCall(nnbvh_scene *s) : guard(s->device), good(guard.ok) {
+        if (good) lock = std::unique_lock<std::mutex>(s->mu);
+    }
+    SceneCall(nnbvh_scene *s, hipStream_t stream) : SceneCall(s) {
+        if (good) good = (w = workspace_for(s, stream)) != nullptr;
+    }
+    bool ok() const { return good; }  // false: NNBVH_ERR_DEVICE, the error text is set
+};
+
+inline bool grow(void **ptr, size_t *have, size_t need, const char *what) {
+    if (*have >= need) return true;
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *have = 0;
+    if (!hip_ok(hipMalloc(ptr, need), what)) return false;
+    *have = need;
+    return true;
+}
+
+// launch_trace's `patches`: bit 0 patches (or alpha: the parked ray direction), bit 1 alpha-tested triangles,
+// bit 2 alpha-tested patches
+inline int patch_bits(const nnbvh_scene *s) { return s->has_patches + 2 * (s->has_alpha != 0) + 4 * (s->has_alpha == 2); }
+
+// both device arrays below 4 GiB (64 B per interior record, 16 B per primitive slot): the lean
+// kernel instances reach them with 32-bit byte offsets
+inline int scene_fits32(const nnbvh_scene *s) {
+    return (int64_t)s->n_interior < (1LL << 26) && s->n_slots < (1LL << 28) - 8;
+}
+
+// the lean kernel instances (bvh_trace.hip) have forms that read a wavefront queue's SOA slices themselves
+inline bool scene_runs_lean(const nnbvh_scene *s) {
+    return !s->instanced && patch_bits(s) == 0 && !s->has_host_prims && scene_fits32(s) && s->window == 8;
+}
+
+// ---- the launchers (capi_trace.cpp) ---------------------------------------------------------------------------
+int grid_blocks(nnbvh_scene *s, int mode, int candidates = 0);
+
+// One launch of the trace kernel over one batch of rays.
+struct TraceJob {
+    int mode = 0;                        // 0 closest hit, 1 any hit with exact counts, 2 any hit
+    const void *rays = nullptr;          // nnbvh_ray records, or with rays == nullptr ...
+    const nnbvh_ray_soa *soa = nullptr;  // ... a wavefront queue whose SOA slices the lean kernels read themselves
+    int64_t n = 0;
+    const int32_t *d_n = nullptr;        // nullable: device-resident batch size, clamped to [0, n]
+    void *hits = nullptr;                // mode 0
+    void *occluded = nullptr;            // modes 1 / 2
+    void *visited = nullptr, *tests = nullptr;  // mode 1
+    // modes 0 / 2, nullable: candidate mode.  The count (and, closest hit, before) arrays start at zero: the launcher
+    // clears them with memset nodes unless hc_zeroed says the caller has done it.  Scenes with host-only primitives
+    // then run the HOSTC instances, which fill them in; other scenes run the plain instances
+    const nnbvh_host_candidates *hc = nullptr;
+    bool hc_zeroed = false;
+};
+int launch(nnbvh_scene *s, Workspace *w, hipStream_t stream, const TraceJob &job);
+
+// ... over up to kMaxFusedBatches closest-hit / occlusion-only batches in one mode-3 launch, where batches_fusable
+int launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream, const nnbvh_batch *batches, int n_batches,
+                         const int32_t *const *d_n, const nnbvh_ray_soa *const *soas = nullptr,
+                         const nnbvh_host_candidates *cands = nullptr);
+bool batches_fusable(const nnbvh_scene *s, const nnbvh_batch *batches, int n_batches);
+
+// what is wrong with a candidates struct (closest: before is an output too), or nullptr; ..._ok reports it as fn's
+const char *candidates_fault(const nnbvh_host_candidates *c, bool closest);
+bool candidates_ok(const char *fn, const nnbvh_host_candidates *c, bool closest);
+// the count (and, closest hit, before) arrays of a candidate call start at zero: kernel nodes on `stream`
+bool zero_candidates(const nnbvh_scene *s, const nnbvh_host_candidates *hc, int64_t n, bool closest, hipStream_t stream);
+
+}  // namespace nnbvh

@@ -1,0 +1,623 @@
+// capi_wavefront.cpp — the C ABI of include/nnbvh.h, wavefront queues (wavefront/aggregate.cpp:34-116 on the
+// device): IntersectClosest, IntersectShadow and the two in one launch, each with or without the work items and
+// the host candidates, and the multi-pass IntersectShadowTr / IntersectOneRandom.  Host code only.
+#include <algorithm>
+#include <cstring>
+
+#include "capi_internal.h"
+#include "wavefront.h"
+#include "wavefront2.h"
+#include "wavefront_items.h"
+
+using namespace nnbvh;
+
+static bool fail(const char *fn, const char *why) {
+    set_error(std::string(fn) + ": " + why);
+    return false;
+}
+
+static bool soa_ok(const nnbvh_ray_soa *q) {
+    return q && q->ox && q->oy && q->oz && q->dx && q->dy && q->dz;
+}
+
+static bool queues_ok(const nnbvh_closest_queues *out) {
+    const nnbvh_work_queue *qs[6] = {&out->escaped, &out->hit_area_light, &out->basic_eval_material,
+                                     &out->universal_eval_material, &out->medium_sample, &out->next_ray};
+    for (const nnbvh_work_queue *q : qs)
+        if (q->size && (q->capacity < 0 || (q->capacity > 0 && !q->items))) return false;
+    return true;
+}
+
+// ---- IntersectClosest with the work items (wavefront/intersect.h:16-156) --------------------------------
+static_assert(sizeof(nnbvh_item_slices) == 48 * sizeof(void *), "nnbvh_item_slices: 48 pointers");
+
+// every non-null slice must be one its queue's Push stores (include/nnbvh.h), and a wanted needs_host
+// queue needs storage like the others
+static bool items_ok(const nnbvh_closest_items *items, const char **why) {
+    enum { kPrim = 1, kPi = 2, kP = 4, kN = 8, kGeo = 16, kWo = 32, kUv = 64, kFace = 128, kTime = 256, kTMax = 512, kRay = 1024 };
+    struct Field {
+        size_t offset, count;
+        unsigned kind;
+    };
+#define F(name, kind) {offsetof(nnbvh_item_slices, name), sizeof(((nnbvh_item_slices *)0)->name) / sizeof(void *), kind}
+    static const Field fields[] = {F(prim, kPrim), F(pi, kPi), F(p, kP), F(n, kN), F(ns, kGeo), F(dpdu, kGeo),
+                                   F(dpdv, kGeo), F(dpdus, kGeo), F(dpdvs, kGeo), F(dndus, kGeo), F(dndvs, kGeo),
+                                   F(wo, kWo), F(uv, kUv), F(face_index, kFace), F(time, kTime), F(t_max, kTMax),
+                                   F(ray_o, kRay), F(ray_d, kRay)};
+#undef F
+    const unsigned material = kPrim | kPi | kN | kGeo | kWo | kUv | kFace | kTime;
+    const struct {
+        const nnbvh_item_slices *s;
+        unsigned allowed;
+        const char *name;
+    } queues[5] = {{&items->hit_area_light, kPrim | kP | kN | kWo | kUv, "hit_area_light"},
+                   {&items->basic_eval_material, material, "basic_eval_material"},
+                   {&items->universal_eval_material, material, "universal_eval_material"},
+                   {&items->medium_sample, material | kTMax, "medium_sample"},
+                   {&items->next_ray, kPrim | kRay | kTime, "next_ray"}};
+    for (const auto &q : queues) {
+        const char *base = (const char *)q.s;
+        for (const Field &f : fields) {
+            if (q.allowed & f.kind) continue;
+            for (size_t k = 0; k < f.count; ++k)
+                if (((void *const *)(base + f.offset))[k]) {
+                    *why = q.name;
+                    return false;
+                }
+        }
+    }
+    const nnbvh_work_queue &h = items->needs_host;
+    if (h.size && (h.capacity < 0 || (h.capacity > 0 && !h.items))) {
+        *why = "needs_host";
+        return false;
+    }
+    return true;
+}
+
+// The closest side of a call (IntersectClosest) in its three forms: plain; with_items: the work items come with
+// the index queues, computed from a shading mesh (d_hits may be NULL: the records then stay in a workspace);
+// with_candidates, an _items form: host-only primitives are listed in hc instead of voiding the ray (d_hits required).
+struct ClosestSide {
+    int32_t max_rays;
+    const nnbvh_ray_soa *queue;
+    const int32_t *d_size;
+    const uint8_t *d_prim_class;
+    int64_t n_prim_class;
+    void *d_hits;
+    const nnbvh_closest_queues *out;
+    bool with_items = false;
+    const nnbvh_shading_mesh *mesh = nullptr;
+    const nnbvh_closest_items *items = nullptr;
+    bool with_candidates = false;
+    const nnbvh_host_candidates *hc = nullptr;
+};
+
+// The shadow side (IntersectShadow), plain (d_occluded may be NULL: a workspace then holds the flags) or
+// with_candidates (d_occluded required: 0 / 1 / 2 per ray).
+struct ShadowSide {
+    int32_t max_rays;
+    const nnbvh_ray_soa *queue;
+    const int32_t *d_size;
+    const float *d_Ld, *d_r_u, *d_r_l;
+    const int32_t *d_pixel_index;
+    float *d_L;
+    int64_t n_pixels;
+    uint8_t *d_occluded;
+    bool with_candidates = false;
+    const nnbvh_host_candidates *hc = nullptr;
+};
+
+// the entry point a side, or the pair, was called through: error texts carry its name
+static const char *closest_fn(const ClosestSide &a) {
+    return a.with_candidates ? "wavefront_intersect_closest_items_candidates"
+                             : a.with_items ? "wavefront_intersect_closest_items" : "wavefront_intersect_closest";
+}
+static const char *shadow_fn(const ShadowSide &a) {
+    return a.with_candidates ? "wavefront_intersect_shadow_candidates" : "wavefront_intersect_shadow";
+}
+static const char *pair_fn(const ClosestSide &a) {
+    return a.with_candidates ? "wavefront_intersect_closest_and_shadow_items_candidates"
+                             : a.with_items ? "wavefront_intersect_closest_and_shadow_items"
+                                            : "wavefront_intersect_closest_and_shadow";
+}
+
+// the closest side without the scene and the hit records (the enqueue-only calls have neither rule)
+static bool queue_args_ok(const char *fn, const ClosestSide &a) {
+    if (a.max_rays < 0 || !a.out || a.n_prim_class < 0 || (a.max_rays > 0 && !soa_ok(a.queue)) ||
+        (a.with_items && (!a.mesh || !a.items)))
+        return fail(fn, "bad argument");
+    if (!queues_ok(a.out)) return fail(fn, "queue with a size counter but no item storage");
+    const char *why = nullptr;
+    if (a.with_items && !items_ok(a.items, &why)) {
+        set_error(std::string(fn) + ": slice not carried by queue " + why + ", or needs_host without storage");
+        return false;
+    }
+    return true;
+}
+
+static bool closest_args_ok(const char *fn, const nnbvh_scene *s, const ClosestSide &a) {
+    const bool no_hits = a.max_rays > 0 && !a.d_hits;
+    if (a.with_candidates && (!s || no_hits)) return fail(fn, "bad argument (scene and d_hits are required)");
+    if (!s || (!a.with_items && no_hits)) return fail(fn, "bad argument");
+    if (!queue_args_ok(fn, a) || (a.with_candidates && !candidates_ok(fn, a.hc, true))) return false;
+    if (a.with_items && s->device != a.mesh->device) return fail(fn, "scene and shading mesh live on different devices");
+    return true;
+}
+
+static bool shadow_args_ok(const char *fn, const nnbvh_scene *s, const ShadowSide &a) {
+    if (!s) return fail(fn, "bad argument");
+    if (a.max_rays < 0 || a.n_pixels < 0 ||
+        (a.max_rays > 0 && (!soa_ok(a.queue) || !a.d_Ld || !a.d_r_u || !a.d_r_l || !a.d_pixel_index || !a.d_L ||
+                            (a.with_candidates && !a.d_occluded))))
+        return fail(fn, a.with_candidates ? "bad argument (d_occluded is required)" : "bad argument");
+    return !a.with_candidates || candidates_ok(fn, a.hc, false);
+}
+
+// d_hits == NULL: the records go to a per-stream workspace of the scene's; d_occluded == NULL: likewise
+static void *hits_storage(Workspace *w, void *d_hits, int32_t max_rays) {
+    if (d_hits) return d_hits;
+    if (!grow(&w->d_hits, &w->hits_bytes, (size_t)max_rays * sizeof(nnbvh_hit), "hipMalloc(wavefront hits)"))
+        return nullptr;
+    return w->d_hits;
+}
+static uint8_t *occluded_storage(Workspace *w, uint8_t *d_occluded, int32_t max_rays) {
+    if (d_occluded) return d_occluded;
+    if (!grow(&w->d_out, &w->out_bytes, (size_t)max_rays, "hipMalloc(wavefront occluded)")) return nullptr;
+    return (uint8_t *)w->d_out;
+}
+
+// One queue (job.soa) through the trace kernel.  The lean kernels read the queue's SOA slices themselves (no gather
+// pass into nnbvh_ray records); for the others it is gathered into the workspace.  Candidates start from zero; scenes
+// without host-only primitives run the plain kernels over them.  The caller holds the scene's lock.
+static int trace_queue(nnbvh_scene *s, Workspace *w, hipStream_t stream, TraceJob job) {
+    if (job.hc && !zero_candidates(s, job.hc, job.n, job.mode == 0, stream)) return NNBVH_ERR_DEVICE;
+    job.hc_zeroed = true;
+    if (!scene_runs_lean(s)) {
+        if (!grow(&w->d_in, &w->in_bytes, (size_t)job.n * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
+            return NNBVH_ERR_DEVICE;
+        if (!hip_ok(launch_wf_gather(*job.soa, WavefrontCount{(int)job.n, job.d_n}, w->d_in, s->n_cus * 8, stream),
+                    "gather kernel launch"))
+            return NNBVH_ERR_DEVICE;
+        job.rays = w->d_in;
+        job.soa = nullptr;
+    }
+    return launch(s, w, stream, job);
+}
+
+// IntersectShadow of one depth and IntersectClosest of the next (wavefront/integrator.cpp: TraceShadowRays(depth),
+// then the next iteration's IntersectClosest): both queues are filled by the shading of the same depth and neither
+// reads what the other writes, so they can share ONE launch (mode 3: one ramp-up and one drain instead of two).
+// The trace half of that form (the caller has checked that the scene allows it and holds its lock).  cands: null, or
+// the candidates of the closest and of the shadow side.
+static int trace_two_queues(nnbvh_scene *s, Workspace *w, hipStream_t stream, const ClosestSide &c, void *hits,
+                            const ShadowSide &sh, uint8_t *occ, const nnbvh_host_candidates *cands) {
+    if (cands && !s->has_host_prims) {  // the plain kernels over zeroed arrays; every count stays zero
+        if (!zero_candidates(s, &cands[0], c.max_rays, true, stream) ||
+            !zero_candidates(s, &cands[1], sh.max_rays, false, stream))
+            return NNBVH_ERR_DEVICE;
+        cands = nullptr;
+    }
+    // the (longer) closest-hit batch first: the shadow rays fill the lanes its tail leaves idle
+    nnbvh_batch batches[2] = {{NNBVH_BATCH_CLOSEST, 0, nullptr, c.max_rays, hits, nullptr, nullptr},
+                              {NNBVH_BATCH_ANY, 0, nullptr, sh.max_rays, occ, nullptr, nullptr}};
+    const int32_t *sizes[2] = {c.d_size, sh.d_size};
+    const nnbvh_ray_soa *soas[2] = {c.queue, sh.queue};
+    if (scene_runs_lean(s))  // both queues are read as the SOA slices they are
+        return launch_fused_batches(s, w, stream, batches, 2, sizes, soas);
+    const size_t closest_bytes = (size_t)c.max_rays * sizeof(nnbvh_ray);
+    if (!grow(&w->d_in, &w->in_bytes, closest_bytes + (size_t)sh.max_rays * sizeof(nnbvh_ray),
+              "hipMalloc(wavefront rays)"))
+        return NNBVH_ERR_DEVICE;
+    void *closest_rays = w->d_in, *shadow_rays = (char *)w->d_in + closest_bytes;
+    if (!hip_ok(launch_wf_gather(*c.queue, WavefrontCount{c.max_rays, c.d_size}, closest_rays, s->n_cus * 8, stream),
+                "gather kernel launch") ||
+        !hip_ok(launch_wf_gather(*sh.queue, WavefrontCount{sh.max_rays, sh.d_size}, shadow_rays, s->n_cus * 8, stream),
+                "gather kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    batches[0].d_rays = closest_rays;
+    batches[1].d_rays = shadow_rays;
+    return launch_fused_batches(s, w, stream, batches, 2, sizes, nullptr, cands);
+}
+
+// IntersectClosest's enqueue with the work items (wavefront/intersect.h:16-156).  hc_count (nullable): a ray with
+// count != 0 is the caller's, whatever its record says
+static int launch_items(const ClosestSide &a, const void *hits, const int32_t *hc_count, hipStream_t stream) {
+    if (!hip_ok(launch_wf_enqueue_closest_items(a.mesh->d, hits, WavefrontCount{a.max_rays, a.d_size}, *a.queue,
+                                                a.d_prim_class, (long)a.n_prim_class, *a.out, *a.items,
+                                                a.mesh->n_cus * 8, stream, hc_count, nullptr, a.max_rays),
+                "work-item enqueue kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+// the second half of each side: hit records -> index queues (and work items), occlusion flags -> L
+static int enqueue_closest(const nnbvh_scene *s, const ClosestSide &a, const void *hits, hipStream_t stream) {
+    if (a.with_items)
+        return launch_items(a, hits, a.with_candidates && s->has_host_prims ? a.hc->count : nullptr, stream);
+    if (!hip_ok(launch_wf_enqueue_closest(hits, WavefrontCount{a.max_rays, a.d_size}, a.queue->has_medium,
+                                          a.d_prim_class, (long)a.n_prim_class, *a.out, s->n_cus * 8, stream),
+                "enqueue kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+static int record_shadow(const nnbvh_scene *s, const ShadowSide &a, const uint8_t *occ, hipStream_t stream) {
+    if (!hip_ok(launch_wf_record_shadow(occ, WavefrontCount{a.max_rays, a.d_size}, a.d_Ld, a.d_r_u, a.d_r_l,
+                                        a.d_pixel_index, a.d_L, (long)a.n_pixels, s->n_cus * 8, stream),
+                "shadow record kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+static int intersect_closest(nnbvh_scene *s, const ClosestSide &a, hipStream_t stream) {
+    if (!closest_args_ok(closest_fn(a), s, a)) return NNBVH_ERR_ARG;
+    if (a.max_rays == 0) return NNBVH_OK;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    void *hits = hits_storage(call.w, a.d_hits, a.max_rays);
+    if (!hits) return NNBVH_ERR_DEVICE;
+    const int rc = trace_queue(s, call.w, stream,
+                               {.mode = 0, .soa = a.queue, .n = a.max_rays, .d_n = a.d_size, .hits = hits, .hc = a.hc});
+    return rc != NNBVH_OK ? rc : enqueue_closest(s, a, hits, stream);
+}
+
+static int intersect_shadow(nnbvh_scene *s, const ShadowSide &a, hipStream_t stream) {
+    if (!shadow_args_ok(shadow_fn(a), s, a)) return NNBVH_ERR_ARG;
+    if (a.max_rays == 0) return NNBVH_OK;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    uint8_t *occ = occluded_storage(call.w, a.d_occluded, a.max_rays);
+    if (!occ) return NNBVH_ERR_DEVICE;
+    const int rc = trace_queue(s, call.w, stream,
+                               {.mode = 2, .soa = a.queue, .n = a.max_rays, .d_n = a.d_size, .occluded = occ, .hc = a.hc});
+    return rc != NNBVH_OK ? rc : record_shadow(s, a, occ, stream);
+}
+
+// Both sides in one launch where the scene and the sizes allow it; both sides have candidates, or neither.
+static int intersect_closest_and_shadow(nnbvh_scene *s, const ClosestSide &c, const ShadowSide &sh,
+                                        hipStream_t stream) {
+    const char *fn = pair_fn(c);
+    const nnbvh_batch probe[2] = {{NNBVH_BATCH_CLOSEST, 0, nullptr, c.max_rays, nullptr, nullptr, nullptr},
+                                  {NNBVH_BATCH_ANY, 0, nullptr, sh.max_rays, nullptr, nullptr, nullptr}};
+    const bool one_launch = s && c.max_rays > 0 && sh.max_rays > 0 && batches_fusable(s, probe, 2);
+    // Under the pair's own name: the closest side of the _items forms, and with candidates everything, checked before
+    // anything is launched, so that a bad argument leaves both sides untouched.  The rest is the one launch's to check:
+    // the two calls check their own.
+    if ((c.with_items || one_launch) && !closest_args_ok(fn, s, c)) return NNBVH_ERR_ARG;
+    if ((sh.with_candidates || one_launch) && !shadow_args_ok(fn, s, sh)) return NNBVH_ERR_ARG;
+    if (!one_launch) {
+        // a scene or sizes the one-launch form does not cover, or one side empty: the two calls one after the other
+        const int rc = intersect_shadow(s, sh, stream);
+        return rc != NNBVH_OK ? rc : intersect_closest(s, c, stream);
+    }
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    uint8_t *occ = occluded_storage(call.w, sh.d_occluded, sh.max_rays);
+    void *hits = occ ? hits_storage(call.w, c.d_hits, c.max_rays) : nullptr;
+    if (!hits) return NNBVH_ERR_DEVICE;
+    const nnbvh_host_candidates cands[2] = {c.with_candidates ? *c.hc : nnbvh_host_candidates{},
+                                            sh.with_candidates ? *sh.hc : nnbvh_host_candidates{}};
+    int rc = trace_two_queues(s, call.w, stream, c, hits, sh, occ, c.with_candidates ? cands : nullptr);
+    if (rc == NNBVH_OK) rc = enqueue_closest(s, c, hits, stream);
+    if (rc == NNBVH_OK) rc = record_shadow(s, sh, occ, stream);
+    return rc;
+}
+
+extern "C" {
+
+int nnbvh_wavefront_intersect_closest(nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                                      const int32_t *d_size, const uint8_t *d_prim_class,
+                                      int64_t n_prim_class, void *d_hits,
+                                      const nnbvh_closest_queues *out, void *stream) {
+    return intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                 .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out},
+                             (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_intersect_closest_items(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                            const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                            const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+                                            const nnbvh_closest_queues *out, const nnbvh_closest_items *items,
+                                            void *stream) {
+    return intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                 .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out,
+                                 .with_items = true, .mesh = m, .items = items},
+                             (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_intersect_closest_items_candidates(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                       const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                                       const uint8_t *d_prim_class, int64_t n_prim_class,
+                                                       void *d_hits, const nnbvh_closest_queues *out,
+                                                       const nnbvh_closest_items *items,
+                                                       const nnbvh_host_candidates *c, void *stream) {
+    return intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                 .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out,
+                                 .with_items = true, .mesh = m, .items = items, .with_candidates = true, .hc = c},
+                             (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_intersect_shadow(nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+                                     const int32_t *d_size, const float *d_Ld, const float *d_r_u,
+                                     const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                     int64_t n_pixels, uint8_t *d_occluded, void *stream) {
+    return intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
+                                .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
+                                .n_pixels = n_pixels, .d_occluded = d_occluded},
+                            (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_intersect_shadow_candidates(nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+                                                const int32_t *d_size, const float *d_Ld, const float *d_r_u,
+                                                const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                                int64_t n_pixels, uint8_t *d_occluded,
+                                                const nnbvh_host_candidates *c, void *stream) {
+    return intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
+                                .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
+                                .n_pixels = n_pixels, .d_occluded = d_occluded, .with_candidates = true, .hc = c},
+                            (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_intersect_closest_and_shadow(
+    nnbvh_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+    const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits, const nnbvh_closest_queues *out,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded, void *stream) {
+    return intersect_closest_and_shadow(
+        s,
+        {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size, .d_prim_class = d_prim_class,
+         .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out},
+        {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
+         .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded},
+        (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_intersect_closest_and_shadow_items(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, int32_t max_shadow_rays,
+    const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld, const float *d_r_u,
+    const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_occluded,
+    void *stream) {
+    return intersect_closest_and_shadow(
+        s,
+        {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size, .d_prim_class = d_prim_class,
+         .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out, .with_items = true, .mesh = m, .items = items},
+        {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
+         .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded},
+        (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, const nnbvh_host_candidates *c,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded, const nnbvh_host_candidates *shadow_c, void *stream) {
+    return intersect_closest_and_shadow(
+        s,
+        {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size, .d_prim_class = d_prim_class,
+         .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out, .with_items = true, .mesh = m, .items = items,
+         .with_candidates = true, .hc = c},
+        {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
+         .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded,
+         .with_candidates = true, .hc = shadow_c},
+        (hipStream_t)stream);
+}
+
+// ---- the halves of the calls above for records and flags from any source ------------------------------------
+int nnbvh_wavefront_enqueue_closest_items_device(const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                 const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                                 const void *d_hits, const uint8_t *d_prim_class,
+                                                 int64_t n_prim_class, const nnbvh_closest_queues *out,
+                                                 const nnbvh_closest_items *items, void *stream) {
+    const char *fn = "wavefront_enqueue_closest_items_device";
+    const ClosestSide a{.max_rays = max_rays, .queue = ray_queue, .d_size = d_size, .d_prim_class = d_prim_class,
+                        .n_prim_class = n_prim_class, .out = out, .with_items = true, .mesh = m, .items = items};
+    if (!queue_args_ok(fn, a)) return NNBVH_ERR_ARG;
+    if (max_rays > 0 && !d_hits) {
+        fail(fn, "no hit records");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0) return NNBVH_OK;
+    DeviceGuard guard(m->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    return launch_items(a, d_hits, nullptr, (hipStream_t)stream);
+}
+
+int nnbvh_wavefront_enqueue_closest_items_indexed_device(const nnbvh_shading_mesh *m, int32_t max_rays,
+                                                         const nnbvh_ray_soa *ray_queue, const int32_t *d_index,
+                                                         const int32_t *d_index_size, int32_t max_index,
+                                                         const void *d_hits, const uint8_t *d_prim_class,
+                                                         int64_t n_prim_class, const nnbvh_closest_queues *out,
+                                                         const nnbvh_closest_items *items, void *stream) {
+    const char *fn = "wavefront_enqueue_closest_items_indexed_device";
+    const ClosestSide a{.max_rays = max_rays, .queue = ray_queue, .n_prim_class = n_prim_class, .out = out,
+                        .with_items = true, .mesh = m, .items = items};
+    if (!queue_args_ok(fn, a)) return NNBVH_ERR_ARG;
+    if (max_index < 0 || (max_index > 0 && max_rays > 0 && (!d_index || !d_hits))) {
+        fail(fn, "no index list or no hit records");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0 || max_index == 0) return NNBVH_OK;
+    DeviceGuard guard(m->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_wf_enqueue_closest_items(m->d, d_hits, WavefrontCount{max_index, d_index_size}, *ray_queue,
+                                                d_prim_class, (long)n_prim_class, *out, *items, m->n_cus * 8,
+                                                (hipStream_t)stream, nullptr, d_index, max_rays),
+                "work-item enqueue kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_wavefront_record_shadow_device(const uint8_t *d_occluded, int32_t max_rays, const int32_t *d_size,
+                                         const float *d_Ld, const float *d_r_u, const float *d_r_l,
+                                         const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+                                         int device, void *stream_) {
+    if (max_rays < 0 || n_pixels < 0 ||
+        (max_rays > 0 && (!d_occluded || !d_Ld || !d_r_u || !d_r_l || !d_pixel_index || !d_L))) {
+        set_error("wavefront_record_shadow_device: bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0) return NNBVH_OK;
+    DeviceGuard guard(device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    const WavefrontCount cnt{max_rays, d_size};
+    if (!hip_ok(launch_wf_record_shadow(d_occluded, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L,
+                                        (long)n_pixels, 256 * 8, (hipStream_t)stream_),
+                "shadow record kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+// ---- IntersectShadowTr / IntersectOneRandom (wavefront/aggregate.cpp:70-116), media-free -------------
+// Host-driven loops of device passes; the only host round trip per pass is the 4-byte count of
+// items that go on (interface surfaces are rare: the usual shadow batch ends after its first pass).
+static bool scratch(Workspace *w, int slot, size_t bytes, void **out) {
+    if (!grow(&w->scratch[slot], &w->scratch_bytes[slot], std::max<size_t>(bytes, 16), "hipMalloc(wavefront scratch)"))
+        return false;
+    *out = w->scratch[slot];
+    return true;
+}
+
+static bool read_count(const int32_t *d_counter, hipStream_t stream, int *out) {
+    int32_t v = 0;
+    if (!hip_ok(hipMemcpyAsync(&v, d_counter, 4, hipMemcpyDeviceToHost, stream), "read pass count") ||
+        !hip_ok(hipStreamSynchronize(stream), "wavefront pass"))
+        return false;
+    *out = v;
+    return true;
+}
+
+int nnbvh_wavefront_intersect_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                        const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                        const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
+                                        const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index,
+                                        float *d_L, int64_t n_pixels, uint8_t *d_state, void *stream_) {
+    if (!s || !m || max_rays < 0 || n_pixels < 0 || n_prim_class < 0 ||
+        (max_rays > 0 && (!soa_ok(shadow_queue) || !d_Ld || !d_r_u || !d_r_l || !d_pixel_index || !d_L))) {
+        set_error("wavefront_intersect_shadow_tr: bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    if (m->device != s->device) {
+        set_error("wavefront_intersect_shadow_tr: scene and shading mesh live on different devices");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_rays == 0) return NNBVH_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    Workspace *w = call.w;
+    const size_t n = (size_t)max_rays;
+    void *raysA, *raysB, *hitsA, *hitsB, *origA, *origB, *pLight, *state, *counters, *intr;
+    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hitsA) ||
+        !scratch(w, 3, n * 32, &hitsB) || !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) ||
+        !scratch(w, 6, n * 16, &pLight) || !scratch(w, 7, n, &state) || !scratch(w, 8, 64, &counters))
+        return NNBVH_ERR_DEVICE;
+    int32_t *nCur = (int32_t *)counters, *nNext = nCur + 1;
+    const WavefrontCount cnt{max_rays, d_size};
+    const int max_blocks = s->n_cus * 8;
+    if (!hip_ok(launch_str_init(*shadow_queue, cnt, raysA, (int32_t *)origA, (float4 *)pLight, (uint8_t *)state,
+                                max_blocks, stream), "shadow-tr init launch"))
+        return NNBVH_ERR_DEVICE;
+    // the first pass covers the whole queue: its size is max_rays clamped by *d_size
+    if (d_size) {
+        if (!hip_ok(hipMemcpyAsync(nCur, d_size, 4, hipMemcpyDeviceToDevice, stream), "copy queue size"))
+            return NNBVH_ERR_DEVICE;
+    } else if (!hip_ok(hipMemcpyAsync(nCur, &max_rays, 4, hipMemcpyHostToDevice, stream), "copy queue size")) {
+        return NNBVH_ERR_DEVICE;
+    }
+    int active = max_rays;
+    for (int pass = 0; active > 0; ++pass) {
+        if (pass > 4096) {
+            set_error("wavefront_intersect_shadow_tr: more than 4096 interface surfaces on one shadow ray");
+            return NNBVH_ERR_ARG;
+        }
+        int rc = launch(s, w, stream, {.mode = 0, .rays = raysA, .n = active, .d_n = nCur, .hits = hitsA});
+        if (rc != NNBVH_OK) return rc;
+        if (!hip_ok(hipMemsetAsync(nNext, 0, 4, stream), "reset pass count") ||
+            !hip_ok(launch_str_classify(raysA, hitsA, (const int32_t *)origA, nCur, d_prim_class, (long)n_prim_class,
+                                        (uint8_t *)state, raysB, hitsB, (int32_t *)origB, nNext, active, max_blocks,
+                                        stream), "shadow-tr classify launch"))
+            return NNBVH_ERR_DEVICE;
+        int n_iface = 0;
+        if (!read_count(nNext, stream, &n_iface)) return NNBVH_ERR_DEVICE;
+        if (n_iface <= 0) break;
+        if (!scratch(w, 9, (size_t)n_iface * sizeof(nnbvh_interaction), &intr)) return NNBVH_ERR_DEVICE;
+        if (!hip_ok(launch_triangle_interactions(m->d, raysB, nullptr, hitsB, n_iface, nNext, intr, m->n_cus * 8, stream),
+                    "interaction kernel launch") ||
+            !hip_ok(hipMemsetAsync(nCur, 0, 4, stream), "reset pass count") ||
+            !hip_ok(launch_str_spawn(raysB, intr, (const int32_t *)origB, nNext, (const float4 *)pLight, (uint8_t *)state,
+                                     raysA, (int32_t *)origA, nCur, n_iface, max_blocks, stream), "shadow-tr spawn launch"))
+            return NNBVH_ERR_DEVICE;
+        if (!read_count(nCur, stream, &active)) return NNBVH_ERR_DEVICE;
+    }
+    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
+                                  d_state, max_blocks, stream), "shadow-tr record launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_wavefront_intersect_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
+                                         const float *d_p0, const float *d_p1, const int32_t *d_material,
+                                         const int32_t *d_size, const int32_t *d_prim_material,
+                                         int64_t n_prim_material, void *d_sel_hits, void *d_sel_rays,
+                                         float *d_reservoir_pdf, float *d_weight_sum, void *stream_) {
+    if (!s || !m || max_items < 0 || n_prim_material < 0 ||
+        (max_items > 0 && (!d_p0 || !d_p1 || !d_material || !d_sel_hits || !d_sel_rays || !d_reservoir_pdf))) {
+        set_error("wavefront_intersect_one_random: bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    if (m->device != s->device) {
+        set_error("wavefront_intersect_one_random: scene and shading mesh live on different devices");
+        return NNBVH_ERR_ARG;
+    }
+    if (max_items == 0) return NNBVH_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    Workspace *w = call.w;
+    const size_t n = (size_t)max_items;
+    void *raysA, *raysB, *hits, *origA, *origB, *pi, *rng, *weights, *counters, *intr;
+    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hits) ||
+        !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) || !scratch(w, 6, n * 36, &pi) ||
+        !scratch(w, 10, n * 16, &rng) || !scratch(w, 11, n * 8, &weights) || !scratch(w, 8, 64, &counters))
+        return NNBVH_ERR_DEVICE;
+    int32_t *nCur = (int32_t *)counters, *nNext = nCur + 1;
+    OneRandomState st{(float *)pi, (uint64_t *)rng, (float *)weights};
+    const WavefrontCount cnt{max_items, d_size};
+    const int max_blocks = s->n_cus * 8;
+    if (!hip_ok(hipMemsetAsync(nCur, 0, 4, stream), "reset pass count") ||
+        !hip_ok(launch_or_init(d_p0, d_p1, cnt, st, raysA, (int32_t *)origA, nCur, d_sel_hits, d_sel_rays, max_blocks,
+                               stream), "one-random init launch"))
+        return NNBVH_ERR_DEVICE;
+    int active = 0;
+    if (!read_count(nCur, stream, &active)) return NNBVH_ERR_DEVICE;
+    void *cur = raysA, *next = raysB, *ocur = origA, *onext = origB;
+    for (int pass = 0; active > 0; ++pass) {
+        if (pass > 65536) {
+            set_error("wavefront_intersect_one_random: more than 65536 surfaces on one segment");
+            return NNBVH_ERR_ARG;
+        }
+        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = active, .d_n = nCur, .hits = hits});
+        if (rc != NNBVH_OK) return rc;
+        if (!scratch(w, 9, (size_t)active * sizeof(nnbvh_interaction), &intr)) return NNBVH_ERR_DEVICE;
+        if (!hip_ok(launch_triangle_interactions(m->d, cur, nullptr, hits, active, nCur, intr, m->n_cus * 8, stream),
+                    "interaction kernel launch") ||
+            !hip_ok(hipMemsetAsync(nNext, 0, 4, stream), "reset pass count") ||
+            !hip_ok(launch_or_step(cur, hits, intr, (const int32_t *)ocur, nCur, d_p1, d_material, d_prim_material,
+                                   (long)n_prim_material, st, next, (int32_t *)onext, nNext, d_sel_hits, d_sel_rays,
+                                   active, max_blocks, stream), "one-random step launch"))
+            return NNBVH_ERR_DEVICE;
+        if (!read_count(nNext, stream, &active)) return NNBVH_ERR_DEVICE;
+        std::swap(cur, next);
+        std::swap(ocur, onext);
+        std::swap(nCur, nNext);
+    }
+    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+}  // extern "C"

@@ -106,6 +106,18 @@ def _items_record(items, needs_host):
     return rec
 
 
+def _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L):
+    assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
+    for t in (Ld, r_u, r_l, L):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
+    assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+
+
+def _ptr_count(t):
+    """The (pointer, element count) argument pair of an optional per-primitive device tensor."""
+    return (None, 0) if t is None else (t.data_ptr(), t.numel())
+
+
 def _queues_record(queues):
     qrec = np.zeros(1, _lib.CLOSEST_QUEUES_DTYPE)
     for name, q in queues.items():
@@ -152,14 +164,13 @@ def enqueue_closest_items(shading_mesh, max_rays, ray_queue, hits, prim_class=No
     if index is not None:
         check(_lib.lib().nnbvh_wavefront_enqueue_closest_items_indexed_device(
             shading_mesh._h, int(max_rays), ptr(soa), index.items.data_ptr(), index.size.data_ptr(),
-            int(index.capacity), hits.data_ptr(), pc.data_ptr() if pc is not None else None,
-            0 if pc is None else pc.numel(), ptr(qrec), ptr(irec), torch.cuda.current_stream(dev).cuda_stream),
+            int(index.capacity), hits.data_ptr(), *_ptr_count(pc), ptr(qrec), ptr(irec),
+            torch.cuda.current_stream(dev).cuda_stream),
             "nnbvh_wavefront_enqueue_closest_items_indexed_device")
         return
     check(_lib.lib().nnbvh_wavefront_enqueue_closest_items_device(
-        shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), hits.data_ptr(),
-        pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), ptr(qrec), ptr(irec),
-        torch.cuda.current_stream(dev).cuda_stream),
+        shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), hits.data_ptr(), *_ptr_count(pc),
+        ptr(qrec), ptr(irec), torch.cuda.current_stream(dev).cuda_stream),
         "nnbvh_wavefront_enqueue_closest_items_device")
 
 
@@ -198,17 +209,12 @@ class WavefrontAggregate:
         (HIT_DTYPE rows as a uint8 tensor [max_rays, 32]); asynchronous on the current stream."""
         if hits is None:
             hits = torch.empty((max(int(max_rays), 1), 32), dtype=torch.uint8, device=self.device)
-        qrec = np.zeros(1, _lib.CLOSEST_QUEUES_DTYPE)
-        given = dict(zip(CLOSEST_QUEUES, (escaped, hit_area_light, basic_eval_material,
-                                          universal_eval_material, medium_sample, next_ray)))
-        for name, q in given.items():
-            if q is not None:
-                q._wire(qrec[name][0:1])
+        qrec = _queues_record(dict(zip(CLOSEST_QUEUES, (escaped, hit_area_light, basic_eval_material,
+                                                        universal_eval_material, medium_sample, next_ray))))
         soa = ray_queue._wire()
         pc = self.prim_class
         check(_lib.lib().nnbvh_wavefront_intersect_closest(
-            self.aggregate._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
-            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(),
+            self.aggregate._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), *_ptr_count(pc),
             hits.data_ptr(), ptr(qrec), torch.cuda.current_stream(self.device).cuda_stream),
             "nnbvh_wavefront_intersect_closest")
         return hits
@@ -217,10 +223,7 @@ class WavefrontAggregate:
         """Traces the shadow queue and adds Ld / (r_u + r_l).Average() to L[pixel_index] for the
         unoccluded rays (RecordShadowRayResult, wavefront/intersect.h:32-47).  Ld, r_u, r_l:
         float32 [capacity, 4]; L: float32 [n_pixels, 4]; all device tensors."""
-        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
-        for t in (Ld, r_u, r_l, L):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
-        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa = shadow_queue._wire()
         check(_lib.lib().nnbvh_wavefront_intersect_shadow(
             self.aggregate._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(), Ld.data_ptr(),
@@ -237,24 +240,16 @@ class WavefrontAggregate:
         ...) of the next in ONE launch of the traversal kernel (both queues come out of the same shading pass and
         neither reads what the other writes: wavefront/integrator.cpp's render loop).  Same results as the two calls.
         Returns the hit records."""
-        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
-        for t in (Ld, r_u, r_l, L):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
-        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         if hits is None:
             hits = torch.empty((max(int(max_rays), 1), 32), dtype=torch.uint8, device=self.device)
-        qrec = np.zeros(1, _lib.CLOSEST_QUEUES_DTYPE)
-        given = dict(zip(CLOSEST_QUEUES, (escaped, hit_area_light, basic_eval_material,
-                                          universal_eval_material, medium_sample, next_ray)))
-        for name, q in given.items():
-            if q is not None:
-                q._wire(qrec[name][0:1])
+        qrec = _queues_record(dict(zip(CLOSEST_QUEUES, (escaped, hit_area_light, basic_eval_material,
+                                                        universal_eval_material, medium_sample, next_ray))))
         soa, ssoa = ray_queue._wire(), shadow_queue._wire()
         pc = self.prim_class
         check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow(
-            self.aggregate._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
-            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), hits.data_ptr(), ptr(qrec),
-            int(max_shadow_rays), ptr(ssoa), shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(),
+            self.aggregate._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), *_ptr_count(pc), hits.data_ptr(),
+            ptr(qrec), int(max_shadow_rays), ptr(ssoa), shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(),
             r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0],
             occluded.data_ptr() if occluded is not None else None,
             torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_closest_and_shadow")
@@ -272,8 +267,7 @@ class WavefrontAggregate:
         soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
         check(_lib.lib().nnbvh_wavefront_intersect_closest_items(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
-            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(),
-            hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec),
+            *_ptr_count(pc), hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec),
             torch.cuda.current_stream(self.device).cuda_stream),
             "nnbvh_wavefront_intersect_closest_items")
         return hits
@@ -282,17 +276,14 @@ class WavefrontAggregate:
                                        r_u, r_l, pixel_index, L, items=None, needs_host=None, hits=None,
                                        occluded=None, **queues):
         """IntersectClosestAndShadow with the closest side's work items (see IntersectClosestItems)."""
-        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
-        for t in (Ld, r_u, r_l, L):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
-        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         pc = self.prim_class
         soa, ssoa = ray_queue._wire(), shadow_queue._wire()
         qrec, irec = _queues_record(queues), _items_record(items, needs_host)
         check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow_items(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
-            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(),
-            hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec), int(max_shadow_rays), ptr(ssoa),
+            *_ptr_count(pc), hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec),
+            int(max_shadow_rays), ptr(ssoa),
             shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(),
             L.data_ptr(), L.shape[0], occluded.data_ptr() if occluded is not None else None,
             torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_closest_and_shadow_items")
@@ -311,7 +302,7 @@ class WavefrontAggregate:
         c = candidates._wire()
         check(_lib.lib().nnbvh_wavefront_intersect_closest_items_candidates(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
-            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), hits.data_ptr(), ptr(qrec),
+            *_ptr_count(pc), hits.data_ptr(), ptr(qrec),
             ptr(irec), ctypes.byref(c), torch.cuda.current_stream(self.device).cuda_stream),
             "nnbvh_wavefront_intersect_closest_items_candidates")
         return hits
@@ -321,10 +312,7 @@ class WavefrontAggregate:
         """IntersectShadow with host candidates (nnbvh_wavefront_intersect_shadow_candidates): occluded (required,
         uint8 [capacity]) gets 0 / 1 / 2; rays with 0 add to L, rays with 2 and count > 0 are the caller's to test
         (resolve_host_candidates_any) and to record with record_shadow."""
-        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
-        for t in (Ld, r_u, r_l, L):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
-        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa, c = shadow_queue._wire(), candidates._wire()
         check(_lib.lib().nnbvh_wavefront_intersect_shadow_candidates(
             self.aggregate._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(),
@@ -337,17 +325,14 @@ class WavefrontAggregate:
                                                      **queues):
         """IntersectClosestItemsWithCandidates and IntersectShadowWithCandidates in ONE launch of the traversal
         kernel (nnbvh_wavefront_intersect_closest_and_shadow_items_candidates); same results as the two calls."""
-        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
-        for t in (Ld, r_u, r_l, L):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
-        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         pc = self.prim_class
         soa, ssoa = ray_queue._wire(), shadow_queue._wire()
         qrec, irec = _queues_record(queues), _items_record(items, needs_host)
         c, sc = candidates._wire(), shadow_candidates._wire()
         check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
-            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), hits.data_ptr(), ptr(qrec),
+            *_ptr_count(pc), hits.data_ptr(), ptr(qrec),
             ptr(irec), ctypes.byref(c), int(max_shadow_rays), ptr(ssoa), shadow_queue.size.data_ptr(), Ld.data_ptr(),
             r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0], occluded.data_ptr(),
             ctypes.byref(sc), torch.cuda.current_stream(self.device).cuda_stream),
@@ -359,17 +344,13 @@ class WavefrontAggregate:
         164-274) without media: shadow rays pass through interface surfaces (CLASS_INTERFACE) and are
         blocked by the first surface with a material; arriving rays add Ld * (1 / (r_u + r_l).Average())
         to L[pixel_index].  state: optional uint8 [capacity] out (0 arrived, 1 blocked, 2 host)."""
-        assert shadow_queue.tmax is not None, "a shadow queue carries tMax per item"
-        for t in (Ld, r_u, r_l, L):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4
-        assert pixel_index.dtype == torch.int32 and pixel_index.is_contiguous()
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa = shadow_queue._wire()
         pc = self.prim_class
         check(_lib.lib().nnbvh_wavefront_intersect_shadow_tr(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(),
-            pc.data_ptr() if pc is not None else None, 0 if pc is None else pc.numel(), Ld.data_ptr(),
-            r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0],
-            state.data_ptr() if state is not None else None,
+            *_ptr_count(pc), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(),
+            L.shape[0], state.data_ptr() if state is not None else None,
             torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_shadow_tr")
 
     def IntersectOneRandom(self, max_items, p0, p1, material, shading_mesh, prim_material=None, size=None):
@@ -387,8 +368,8 @@ class WavefrontAggregate:
         pm = prim_material
         check(_lib.lib().nnbvh_wavefront_intersect_one_random(
             self.aggregate._h, shading_mesh._h, n, p0.data_ptr(), p1.data_ptr(), material.data_ptr(),
-            size.data_ptr() if size is not None else None, pm.data_ptr() if pm is not None else None,
-            0 if pm is None else pm.numel(), sel_hits.data_ptr(), sel_rays.data_ptr(), pdf.data_ptr(),
+            size.data_ptr() if size is not None else None, *_ptr_count(pm), sel_hits.data_ptr(), sel_rays.data_ptr(),
+            pdf.data_ptr(),
             wsum.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
             "nnbvh_wavefront_intersect_one_random")
         return sel_hits, sel_rays, pdf, wsum
