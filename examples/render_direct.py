@@ -45,6 +45,8 @@ def main():
     ap.add_argument("--spp", type=int, default=16)
     ap.add_argument("--scale", type=int, default=2, help="render every k-th pixel per axis")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "render_direct.png"))
+    ap.add_argument("--tree", default="bvh", choices=["bvh", "kd"],
+                    help="kd: the same image through a KdTreeAggregate built on the device (the same queue calls)")
     args = ap.parse_args()
     import torch
     from nn_bvh_amd import BVHAggregate, build_tree, make_prims, scene
@@ -54,7 +56,11 @@ def main():
     dev = torch.device("cuda", 0)
     verts, tris, source = scene.load_scene(args.scene)
     t0 = time.perf_counter()
-    agg = BVHAggregate.build_on_device(make_prims(tris), verts)  # SAH tree built and baked on the GPU
+    if args.tree == "kd":  # kd tree built on the GPU; WavefrontAggregate dispatches on the handle type
+        from nn_bvh_amd.kdtree import KdTreeAggregate
+        agg = KdTreeAggregate.build(make_prims(tris), verts, where="gpu")
+    else:
+        agg = BVHAggregate.build_on_device(make_prims(tris), verts)  # SAH tree built and baked on the GPU
     t_build = time.perf_counter() - t0
     wf = WavefrontAggregate(agg)
     cam = args.scene if args.scene in scene.CAMERAS else "crown"
@@ -121,7 +127,7 @@ def main():
     img = (img / (1 + img)).clamp(0, 1) ** (1 / 2.2)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     write_png(args.out, (img.cpu().numpy() * 255 + 0.5).astype(np.uint8))
-    print(f"scene built and baked on the device in {t_build * 1e3:.0f} ms")
+    print(f"scene built and baked on the device in {t_build * 1e3:.0f} ms" + (" (kd tree)" if args.tree == "kd" else ""))
     print(f"{source}: {xres}x{yres}, {args.spp} spp, {n_traced} rays in {t_trace * 1e3:.1f} ms of trace stages "
           f"({n_traced / t_trace / 1e6:.0f} Mray/s incl. queue kernels) -> {args.out}")
 

@@ -793,6 +793,49 @@ int nnbvh_kd_intersect_closest_device(nnbvh_kd_scene *s, const void *d_rays, int
 int nnbvh_kd_intersect_any_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_occluded,
                                   void *d_nodes_visited, void *d_prim_tests, void *stream);
 
+/* ---- kd-tree scenes: one-launch batches and wavefront queues ----------------------------------------------
+ * nnbvh_kd_trace_batches_device: 1..4 independent batches (nnbvh_batch, each fewer than 2^28 rays, closest-hit or
+ * any-hit, any-hit with exact counts where the batch supplies the arrays) traced by ONE kernel launch on `stream`;
+ * every kd scene is covered (patches, alpha-tested kinds, host-only primitives: a ray that meets one is voided as by
+ * nnbvh_kd_intersect_*).  Results are those of nnbvh_kd_intersect_closest_device / _any_device on the same rays.
+ * nnbvh_kd_wavefront_*: the argument lists and meanings of the nnbvh_wavefront_* calls of the same name, on a kd
+ * scene: n = min(max_rays, max(*d_size, 0)), NULL queue sizes mean "not wanted", pushes beyond a capacity are counted
+ * and not stored, each call is one asynchronous operation on `stream` without a host read-back, and the
+ * closest_and_shadow forms trace both queues in one launch where option "pair_one_launch" is set (below).  A bad argument (NULL scene, negative or >= 2^28
+ * max_rays, ...) returns NNBVH_ERR_ARG before any device call.  IntersectShadowTr / IntersectOneRandom, host
+ * candidates and two-level scenes are not offered for kd scenes. */
+int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches, void *stream);
+/* tuning knobs (speed only, never results), as nnbvh_scene_set_option: "read_soa" (lean scenes: the kernel reads a
+ * queue's SOA slices itself; 0, the default: gathered into records first), "pair_one_launch" (closest_and_shadow traces
+ * both queues in one launch; 0, the default: the two calls one after the other).  The defaults follow the measurement
+ * rule of DESIGN.md §5.7: a new form becomes the default once a recorded run shows it ahead by more than the spread. */
+int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value);
+int nnbvh_kd_wavefront_intersect_closest(nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                                         const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class,
+                                         void *d_hits, const nnbvh_closest_queues *out, void *stream);
+int nnbvh_kd_wavefront_intersect_shadow(nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+                                        const int32_t *d_size, const float *d_Ld, const float *d_r_u,
+                                        const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                        int64_t n_pixels, uint8_t *d_occluded, void *stream);
+int nnbvh_kd_wavefront_intersect_closest_and_shadow(
+    nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+    const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits, const nnbvh_closest_queues *out,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded, void *stream);
+int nnbvh_kd_wavefront_intersect_closest_items(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                               const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                               const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+                                               const nnbvh_closest_queues *out, const nnbvh_closest_items *items,
+                                               void *stream);
+int nnbvh_kd_wavefront_intersect_closest_and_shadow_items(
+    nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, int32_t max_shadow_rays,
+    const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld, const float *d_r_u,
+    const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_occluded,
+    void *stream);
+
 /* tuning knobs (speed only, never results): "stack_window" (LDS entries per lane: 4, 8, 16),
  * "blocks_per_cu" (0 = auto), "xcd_queues" (0/1), "prim_weight" / "refill_weight" (1..64: how much a
  * lane waiting on a primitive test / an idle lane counts against a lane waiting on an interior node,

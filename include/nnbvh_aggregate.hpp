@@ -598,6 +598,66 @@ class HipKdTreeAggregate {
             HipBVHAggregate::fatal("kd IntersectShadowDevice");
     }
 
+    // ---- one-launch batches and whole wavefront stages on a kd scene: HipBVHAggregate's signatures and meanings
+    //      (nnbvh_kd_trace_batches_device, nnbvh_kd_wavefront_*; no candidates, include/nnbvh.h) ------------------
+    void TraceBatchesDevice(const nnbvh_batch *batches, int nBatches, void *stream) const {
+        if (nnbvh_kd_trace_batches_device(scene_, batches, nBatches, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd TraceBatchesDevice");
+    }
+    void IntersectClosestQueues(int maxRays, const nnbvh_ray_soa &rayQueue, const int32_t *dSize,
+                                const uint8_t *dPrimClass, int64_t nPrimClass, void *dHits,
+                                const nnbvh_closest_queues &out, void *stream) const {
+        if (nnbvh_kd_wavefront_intersect_closest(scene_, maxRays, &rayQueue, dSize, dPrimClass, nPrimClass, dHits, &out,
+                                                 stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd IntersectClosestQueues");
+    }
+    void IntersectShadowQueues(int maxRays, const nnbvh_ray_soa &shadowQueue, const int32_t *dSize, const float *dLd,
+                               const float *dRu, const float *dRl, const int32_t *dPixelIndex, float *dL,
+                               int64_t nPixels, void *stream, uint8_t *dOccluded = nullptr) const {
+        if (nnbvh_kd_wavefront_intersect_shadow(scene_, maxRays, &shadowQueue, dSize, dLd, dRu, dRl, dPixelIndex, dL,
+                                                nPixels, dOccluded, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd IntersectShadowQueues");
+    }
+    void IntersectShadowQueue(int maxRays, const nnbvh_ray_soa &shadowQueue, const int32_t *dSize, const float *dLd,
+                              const float *dRu, const float *dRl, const int32_t *dPixelIndex, float *dL,
+                              int64_t nPixels, void *stream, uint8_t *dOccluded = nullptr) const {  // HipBVHAggregate's name
+        IntersectShadowQueues(maxRays, shadowQueue, dSize, dLd, dRu, dRl, dPixelIndex, dL, nPixels, stream, dOccluded);
+    }
+    void IntersectClosestAndShadowQueues(int maxRays, const nnbvh_ray_soa &rayQueue, const int32_t *dSize,
+                                         const uint8_t *dPrimClass, int64_t nPrimClass, void *dHits,
+                                         const nnbvh_closest_queues &out, int maxShadowRays,
+                                         const nnbvh_ray_soa &shadowQueue, const int32_t *dShadowSize, const float *dLd,
+                                         const float *dRu, const float *dRl, const int32_t *dPixelIndex, float *dL,
+                                         int64_t nPixels, void *stream, uint8_t *dOccluded = nullptr) const {
+        if (nnbvh_kd_wavefront_intersect_closest_and_shadow(scene_, maxRays, &rayQueue, dSize, dPrimClass, nPrimClass,
+                                                            dHits, &out, maxShadowRays, &shadowQueue, dShadowSize, dLd,
+                                                            dRu, dRl, dPixelIndex, dL, nPixels, dOccluded,
+                                                            stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd IntersectClosestAndShadowQueues");
+    }
+    void IntersectClosestItemsQueues(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &rayQueue,
+                                     const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass, void *dHits,
+                                     const nnbvh_closest_queues &out, const nnbvh_closest_items &items,
+                                     void *stream) const {
+        if (nnbvh_kd_wavefront_intersect_closest_items(scene_, mesh, maxRays, &rayQueue, dSize, dPrimClass, nPrimClass,
+                                                       dHits, &out, &items, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd IntersectClosestItemsQueues");
+    }
+    void IntersectClosestAndShadowItemsQueues(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &rayQueue,
+                                              const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass,
+                                              void *dHits, const nnbvh_closest_queues &out,
+                                              const nnbvh_closest_items &items, int maxShadowRays,
+                                              const nnbvh_ray_soa &shadowQueue, const int32_t *dShadowSize,
+                                              const float *dLd, const float *dRu, const float *dRl,
+                                              const int32_t *dPixelIndex, float *dL, int64_t nPixels, void *stream,
+                                              uint8_t *dOccluded = nullptr) const {
+        if (nnbvh_kd_wavefront_intersect_closest_and_shadow_items(scene_, mesh, maxRays, &rayQueue, dSize, dPrimClass,
+                                                                  nPrimClass, dHits, &out, &items, maxShadowRays,
+                                                                  &shadowQueue, dShadowSize, dLd, dRu, dRl, dPixelIndex,
+                                                                  dL, nPixels, dOccluded, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd IntersectClosestAndShadowItemsQueues");
+    }
+
   private:
     nnbvh_kd_scene *scene_ = nullptr;
     float bounds_[6] = {0, 0, 0, 0, 0, 0};

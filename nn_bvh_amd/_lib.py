@@ -85,6 +85,9 @@ EXPORTS = [
     "nnbvh_trace_batches_candidates_device", "nnbvh_wavefront_intersect_closest_items_candidates",
     "nnbvh_wavefront_enqueue_closest_items_indexed_device", "nnbvh_wavefront_intersect_shadow_candidates",
     "nnbvh_wavefront_intersect_closest_and_shadow_items_candidates",
+    "nnbvh_kd_trace_batches_device", "nnbvh_kd_wavefront_intersect_closest", "nnbvh_kd_wavefront_intersect_shadow",
+    "nnbvh_kd_wavefront_intersect_closest_and_shadow", "nnbvh_kd_wavefront_intersect_closest_items",
+    "nnbvh_kd_wavefront_intersect_closest_and_shadow_items", "nnbvh_kd_scene_set_option",
 ]
 
 
@@ -205,6 +208,16 @@ def lib():
     L.nnbvh_wavefront_intersect_closest_and_shadow_items.restype = i32
     L.nnbvh_wavefront_intersect_closest_and_shadow_items.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, vp,
                                                                      vp, vp, vp, vp, vp, vp, i64, vp, vp]
+    # kd-tree scenes: the BVH calls' argument lists behind a nnbvh_kd_scene *
+    L.nnbvh_kd_scene_set_option.restype = i32
+    L.nnbvh_kd_scene_set_option.argtypes = [vp, ctypes.c_char_p, i32]
+    L.nnbvh_kd_trace_batches_device.restype = i32
+    L.nnbvh_kd_trace_batches_device.argtypes = L.nnbvh_trace_batches_device.argtypes
+    for name in ("intersect_closest", "intersect_shadow", "intersect_closest_and_shadow", "intersect_closest_items",
+                 "intersect_closest_and_shadow_items"):
+        kd = getattr(L, "nnbvh_kd_wavefront_" + name)
+        kd.restype = i32
+        kd.argtypes = getattr(L, "nnbvh_wavefront_" + name).argtypes
     L.nnbvh_wavefront_record_shadow_device.restype = i32
     L.nnbvh_wavefront_record_shadow_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, i32, vp]
     L.nnbvh_film_create.restype = vp

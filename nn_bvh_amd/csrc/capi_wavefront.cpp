@@ -1,10 +1,12 @@
 // capi_wavefront.cpp — the C ABI of include/nnbvh.h, wavefront queues (wavefront/aggregate.cpp:34-116 on the
 // device): IntersectClosest, IntersectShadow and the two in one launch, each with or without the work items and
-// the host candidates, and the multi-pass IntersectShadowTr / IntersectOneRandom.  Host code only.
+// the host candidates, and the multi-pass IntersectShadowTr / IntersectOneRandom; the first three also for kd-tree
+// scenes (kd_trace.h), over the same argument packs, checks and queue kernels.  Host code only.
 #include <algorithm>
 #include <cstring>
 
 #include "capi_internal.h"
+#include "kd_trace.h"
 #include "wavefront.h"
 #include "wavefront2.h"
 #include "wavefront_items.h"
@@ -90,6 +92,7 @@ struct ClosestSide {
     const nnbvh_closest_items *items = nullptr;
     bool with_candidates = false;
     const nnbvh_host_candidates *hc = nullptr;
+    bool kd = false;  // called through a nnbvh_kd_wavefront_* entry point
 };
 
 // The shadow side (IntersectShadow), plain (d_occluded may be NULL: a workspace then holds the flags) or
@@ -105,17 +108,21 @@ struct ShadowSide {
     uint8_t *d_occluded;
     bool with_candidates = false;
     const nnbvh_host_candidates *hc = nullptr;
+    bool kd = false;
 };
 
 // the entry point a side, or the pair, was called through: error texts carry its name
 static const char *closest_fn(const ClosestSide &a) {
+    if (a.kd) return a.with_items ? "kd_wavefront_intersect_closest_items" : "kd_wavefront_intersect_closest";
     return a.with_candidates ? "wavefront_intersect_closest_items_candidates"
                              : a.with_items ? "wavefront_intersect_closest_items" : "wavefront_intersect_closest";
 }
 static const char *shadow_fn(const ShadowSide &a) {
+    if (a.kd) return "kd_wavefront_intersect_shadow";
     return a.with_candidates ? "wavefront_intersect_shadow_candidates" : "wavefront_intersect_shadow";
 }
 static const char *pair_fn(const ClosestSide &a) {
+    if (a.kd) return a.with_items ? "kd_wavefront_intersect_closest_and_shadow_items" : "kd_wavefront_intersect_closest_and_shadow";
     return a.with_candidates ? "wavefront_intersect_closest_and_shadow_items_candidates"
                              : a.with_items ? "wavefront_intersect_closest_and_shadow_items"
                                             : "wavefront_intersect_closest_and_shadow";
@@ -135,32 +142,42 @@ static bool queue_args_ok(const char *fn, const ClosestSide &a) {
     return true;
 }
 
-static bool closest_args_ok(const char *fn, const nnbvh_scene *s, const ClosestSide &a) {
+// (the scene, of either type, as "is there one" and its device)
+static bool closest_side_ok(const char *fn, bool scene, int device, const ClosestSide &a) {
     const bool no_hits = a.max_rays > 0 && !a.d_hits;
-    if (a.with_candidates && (!s || no_hits)) return fail(fn, "bad argument (scene and d_hits are required)");
-    if (!s || (!a.with_items && no_hits)) return fail(fn, "bad argument");
+    if (a.with_candidates && (!scene || no_hits)) return fail(fn, "bad argument (scene and d_hits are required)");
+    if (!scene || (!a.with_items && no_hits)) return fail(fn, "bad argument");
     if (!queue_args_ok(fn, a) || (a.with_candidates && !candidates_ok(fn, a.hc, true))) return false;
-    if (a.with_items && s->device != a.mesh->device) return fail(fn, "scene and shading mesh live on different devices");
+    if (a.with_items && device != a.mesh->device) return fail(fn, "scene and shading mesh live on different devices");
     return true;
 }
+static bool closest_args_ok(const char *fn, const nnbvh_scene *s, const ClosestSide &a) {
+    return closest_side_ok(fn, s != nullptr, s ? s->device : 0, a);
+}
 
-static bool shadow_args_ok(const char *fn, const nnbvh_scene *s, const ShadowSide &a) {
-    if (!s) return fail(fn, "bad argument");
+static bool shadow_side_ok(const char *fn, bool scene, const ShadowSide &a) {
+    if (!scene) return fail(fn, "bad argument");
     if (a.max_rays < 0 || a.n_pixels < 0 ||
         (a.max_rays > 0 && (!soa_ok(a.queue) || !a.d_Ld || !a.d_r_u || !a.d_r_l || !a.d_pixel_index || !a.d_L ||
                             (a.with_candidates && !a.d_occluded))))
         return fail(fn, a.with_candidates ? "bad argument (d_occluded is required)" : "bad argument");
     return !a.with_candidates || candidates_ok(fn, a.hc, false);
 }
+static bool shadow_args_ok(const char *fn, const nnbvh_scene *s, const ShadowSide &a) {
+    return shadow_side_ok(fn, s != nullptr, a);
+}
 
 // d_hits == NULL: the records go to a per-stream workspace of the scene's; d_occluded == NULL: likewise
-static void *hits_storage(Workspace *w, void *d_hits, int32_t max_rays) {
+// (W: the BVH scenes' Workspace or the kd scenes' KdWorkspace)
+template <class W>
+static void *hits_storage(W *w, void *d_hits, int32_t max_rays) {
     if (d_hits) return d_hits;
     if (!grow(&w->d_hits, &w->hits_bytes, (size_t)max_rays * sizeof(nnbvh_hit), "hipMalloc(wavefront hits)"))
         return nullptr;
     return w->d_hits;
 }
-static uint8_t *occluded_storage(Workspace *w, uint8_t *d_occluded, int32_t max_rays) {
+template <class W>
+static uint8_t *occluded_storage(W *w, uint8_t *d_occluded, int32_t max_rays) {
     if (d_occluded) return d_occluded;
     if (!grow(&w->d_out, &w->out_bytes, (size_t)max_rays, "hipMalloc(wavefront occluded)")) return nullptr;
     return (uint8_t *)w->d_out;
@@ -231,21 +248,27 @@ static int launch_items(const ClosestSide &a, const void *hits, const int32_t *h
 }
 
 // the second half of each side: hit records -> index queues (and work items), occlusion flags -> L
-static int enqueue_closest(const nnbvh_scene *s, const ClosestSide &a, const void *hits, hipStream_t stream) {
+static int enqueue_closest(int n_cus, bool has_host_prims, const ClosestSide &a, const void *hits, hipStream_t stream) {
     if (a.with_items)
-        return launch_items(a, hits, a.with_candidates && s->has_host_prims ? a.hc->count : nullptr, stream);
+        return launch_items(a, hits, a.with_candidates && has_host_prims ? a.hc->count : nullptr, stream);
     if (!hip_ok(launch_wf_enqueue_closest(hits, WavefrontCount{a.max_rays, a.d_size}, a.queue->has_medium,
-                                          a.d_prim_class, (long)a.n_prim_class, *a.out, s->n_cus * 8, stream),
+                                          a.d_prim_class, (long)a.n_prim_class, *a.out, n_cus * 8, stream),
                 "enqueue kernel launch"))
         return NNBVH_ERR_DEVICE;
     return NNBVH_OK;
 }
-static int record_shadow(const nnbvh_scene *s, const ShadowSide &a, const uint8_t *occ, hipStream_t stream) {
+static int enqueue_closest(const nnbvh_scene *s, const ClosestSide &a, const void *hits, hipStream_t stream) {
+    return enqueue_closest(s->n_cus, s->has_host_prims != 0, a, hits, stream);
+}
+static int record_shadow(int n_cus, const ShadowSide &a, const uint8_t *occ, hipStream_t stream) {
     if (!hip_ok(launch_wf_record_shadow(occ, WavefrontCount{a.max_rays, a.d_size}, a.d_Ld, a.d_r_u, a.d_r_l,
-                                        a.d_pixel_index, a.d_L, (long)a.n_pixels, s->n_cus * 8, stream),
+                                        a.d_pixel_index, a.d_L, (long)a.n_pixels, n_cus * 8, stream),
                 "shadow record kernel launch"))
         return NNBVH_ERR_DEVICE;
     return NNBVH_OK;
+}
+static int record_shadow(const nnbvh_scene *s, const ShadowSide &a, const uint8_t *occ, hipStream_t stream) {
+    return record_shadow(s->n_cus, a, occ, stream);
 }
 
 static int intersect_closest(nnbvh_scene *s, const ClosestSide &a, hipStream_t stream) {
@@ -299,6 +322,85 @@ static int intersect_closest_and_shadow(nnbvh_scene *s, const ClosestSide &c, co
     int rc = trace_two_queues(s, call.w, stream, c, hits, sh, occ, c.with_candidates ? cands : nullptr);
     if (rc == NNBVH_OK) rc = enqueue_closest(s, c, hits, stream);
     if (rc == NNBVH_OK) rc = record_shadow(s, sh, occ, stream);
+    return rc;
+}
+
+// ---- the same three calls on a kd-tree scene -----------------------------------------------------------------
+// The trace half is kd_trace.hip's batch-mode launch (one for a single queue, ONE for the pair); the argument packs,
+// their checks and the queue kernels behind the launch are the ones above.  No candidates: a host-only primitive
+// voids the ray, and the enqueue sends it to needs_host (or nowhere) as for a BVH scene without them.
+struct KdSceneCall {
+    DeviceGuard guard;
+    std::unique_lock<std::mutex> lock;
+    KdWorkspace *w = nullptr;
+    bool good;
+    KdSceneCall(nnbvh_kd_scene *s, hipStream_t stream) : guard(s->device), good(guard.ok) {
+        if (good) lock = std::unique_lock<std::mutex>(s->mu);
+        if (good) good = (w = kd_workspace_for(s, stream)) != nullptr;
+    }
+    bool ok() const { return good; }
+};
+
+// a batch-mode launch tags a ray with batch << kKdIndexBits | index.  Checked first, before the scene is looked at
+static bool kd_size_ok(const char *fn, int32_t max_rays) {
+    if (max_rays < 0) return fail(fn, "bad argument");
+    return max_rays < (1 << kKdIndexBits) || fail(fn, "a queue of 2^28 rays or more");
+}
+
+static int kd_intersect_closest(nnbvh_kd_scene *s, const ClosestSide &a, hipStream_t stream) {
+    const char *fn = closest_fn(a);
+    if (!kd_size_ok(fn, a.max_rays) || !closest_side_ok(fn, s != nullptr, s ? s->device : 0, a)) return NNBVH_ERR_ARG;
+    if (a.max_rays == 0) return NNBVH_OK;
+    KdSceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    void *hits = hits_storage(call.w, a.d_hits, a.max_rays);
+    if (!hits) return NNBVH_ERR_DEVICE;
+    KdBatch batch;
+    batch.soa = a.queue, batch.n = a.max_rays, batch.d_n = a.d_size, batch.out = hits;
+    const int rc = kd_launch_batches(s, call.w, stream, &batch, 1);
+    return rc != NNBVH_OK ? rc : enqueue_closest(s->n_cus, false, a, hits, stream);
+}
+
+static int kd_intersect_shadow(nnbvh_kd_scene *s, const ShadowSide &a, hipStream_t stream) {
+    const char *fn = shadow_fn(a);
+    if (!kd_size_ok(fn, a.max_rays) || !shadow_side_ok(fn, s != nullptr, a)) return NNBVH_ERR_ARG;
+    if (a.max_rays == 0) return NNBVH_OK;
+    KdSceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    uint8_t *occ = occluded_storage(call.w, a.d_occluded, a.max_rays);
+    if (!occ) return NNBVH_ERR_DEVICE;
+    KdBatch batch;
+    batch.any = 1, batch.soa = a.queue, batch.n = a.max_rays, batch.d_n = a.d_size, batch.out = occ;
+    const int rc = kd_launch_batches(s, call.w, stream, &batch, 1);
+    return rc != NNBVH_OK ? rc : record_shadow(s->n_cus, a, occ, stream);
+}
+
+// Both sides checked under the pair's name before anything is launched; one side empty (or the scene set to two
+// launches, "pair_one_launch" 0): the two calls one after the other.
+static int kd_intersect_closest_and_shadow(nnbvh_kd_scene *s, const ClosestSide &c, const ShadowSide &sh,
+                                           hipStream_t stream) {
+    const char *fn = pair_fn(c);
+    if (!kd_size_ok(fn, c.max_rays) || !kd_size_ok(fn, sh.max_rays) ||
+        !closest_side_ok(fn, s != nullptr, s ? s->device : 0, c) || !shadow_side_ok(fn, s != nullptr, sh))
+        return NNBVH_ERR_ARG;
+    if (c.max_rays == 0 || sh.max_rays == 0 || !s->pair_one_launch) {
+        const int rc = kd_intersect_shadow(s, sh, stream);
+        return rc != NNBVH_OK ? rc : kd_intersect_closest(s, c, stream);
+    }
+    KdSceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    uint8_t *occ = occluded_storage(call.w, sh.d_occluded, sh.max_rays);
+    void *hits = occ ? hits_storage(call.w, c.d_hits, c.max_rays) : nullptr;
+    if (!hits) return NNBVH_ERR_DEVICE;
+    // closest-hit batch first, the order of the BVH pair call (tools/kd_wavefront_probe.py times both orders of the
+    // flat batches)
+    KdBatch batches[2];
+    batches[0].soa = c.queue, batches[0].n = c.max_rays, batches[0].d_n = c.d_size, batches[0].out = hits;
+    batches[1].any = 1, batches[1].soa = sh.queue, batches[1].n = sh.max_rays, batches[1].d_n = sh.d_size,
+    batches[1].out = occ;
+    int rc = kd_launch_batches(s, call.w, stream, batches, 2);
+    if (rc == NNBVH_OK) rc = enqueue_closest(s->n_cus, false, c, hits, stream);
+    if (rc == NNBVH_OK) rc = record_shadow(s->n_cus, sh, occ, stream);
     return rc;
 }
 
@@ -403,6 +505,71 @@ int nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
         {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
          .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded,
          .with_candidates = true, .hc = shadow_c},
+        (hipStream_t)stream);
+}
+
+// ---- kd-tree scenes: the argument lists of the calls of the same name above ---------------------------------------
+int nnbvh_kd_wavefront_intersect_closest(nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                                         const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class,
+                                         void *d_hits, const nnbvh_closest_queues *out, void *stream) {
+    return kd_intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                    .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
+                                    .out = out, .kd = true},
+                                (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_intersect_closest_items(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                               const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+                                               const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+                                               const nnbvh_closest_queues *out, const nnbvh_closest_items *items,
+                                               void *stream) {
+    return kd_intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                    .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
+                                    .out = out, .with_items = true, .mesh = m, .items = items, .kd = true},
+                                (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_intersect_shadow(nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+                                        const int32_t *d_size, const float *d_Ld, const float *d_r_u,
+                                        const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                        int64_t n_pixels, uint8_t *d_occluded, void *stream) {
+    return kd_intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
+                                   .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
+                                   .n_pixels = n_pixels, .d_occluded = d_occluded, .kd = true},
+                               (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_intersect_closest_and_shadow(
+    nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue, const int32_t *d_size,
+    const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits, const nnbvh_closest_queues *out,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded, void *stream) {
+    return kd_intersect_closest_and_shadow(
+        s,
+        {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size, .d_prim_class = d_prim_class,
+         .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out, .kd = true},
+        {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
+         .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded,
+         .kd = true},
+        (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_intersect_closest_and_shadow_items(
+    nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, int32_t max_shadow_rays,
+    const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld, const float *d_r_u,
+    const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_occluded,
+    void *stream) {
+    return kd_intersect_closest_and_shadow(
+        s,
+        {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size, .d_prim_class = d_prim_class,
+         .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out, .with_items = true, .mesh = m, .items = items,
+         .kd = true},
+        {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
+         .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded,
+         .kd = true},
         (hipStream_t)stream);
 }
 

@@ -28,6 +28,8 @@
 #include "nnbvh_internal.h"
 #include "trace_math.h"
 #include "spawn_math.h"
+#include "kd_trace.h"
+#include "wavefront.h"
 
 namespace nnbvh {
 
@@ -58,6 +60,18 @@ struct KdParams {
     float4 *spill;                // [kMaxStack][grid threads] overflow of the LDS window
     const float4 *extras;         // ATTR instances: 6 slots per primitive {n0} {n1} {n2} {n3} {uv00, uv10} {uv01, uv11}
                                   // (per-vertex normals / uvs of the alpha-tested kinds that read them), else null
+    // batch mode (MODE 2 / 3: one launch over several batches, closest-hit and any-hit mixed).  Appended, so that the
+    // fields above keep their kernel-argument offsets.  Batch b's queue heads sit at
+    // queue[(b * nQueues + q) * kKdQueueStride]; bit b of anyMask = batch b is any-hit (bOut = uint8 occluded[]),
+    // else closest (bOut = nnbvh_hit[])
+    int nBatches;
+    unsigned anyMask;
+    const nnbvh_ray *bRays[kKdMaxBatches];   // MODE 2
+    nnbvh_ray_soa bSoa[kKdMaxBatches];       // MODE 3: SOA<Ray> slices (tmax == nullptr: Infinity, time == nullptr: 0)
+    void *bOut[kKdMaxBatches];
+    int32_t *bVisited[kKdMaxBatches], *bTests[kKdMaxBatches];  // any-hit batches, nullable
+    long bN[kKdMaxBatches];
+    const int32_t *bNDev[kKdMaxBatches];     // nullable: device-resident size of batch b, clamped to [0, bN[b]]
 };
 
 // util/vecmath.h:1547-1571 with invRayDir = 1 / d[i] taken from the ray's precomputed reciprocals
@@ -86,6 +100,13 @@ DEV bool kd_root_interval(const float bmin[3], const float bmax[3], V3 o, V3 inv
 }
 
 // MODE 0: closest hit; MODE 1: any hit (counts written when asked for).
+// MODE 2 / 3: batch mode.  One launch drains up to kKdMaxBatches independent batches in list order, each closest-hit
+// or any-hit, each with its own eight queue heads and a size that may live on the device (the kernel reads it).  The
+// lane's ray tag (cold ray index) carries its batch in the bits above kKdIndexBits; whether the lane's ray is an
+// any-hit ray rides as bit 7 of r.kz, and the three places where the two walks differ (the rayTMax < tMin exit, an
+// accepted hit, what is retired) are chosen per lane from it.  MODE 2 reads nnbvh_ray records; MODE 3 (lean form
+// only) reads every batch as the SOA<Ray> slices of a wavefront queue, its own instance so that the record form does
+// not carry the second fetch path.
 // PATCH = 0: the scene holds no bilinear patches — nothing reads the ray direction after the ray is
 // fetched except `ray.d[axis] <= 0` at interior nodes, which rides as three bits beside the shear's
 // kz; the patch test, the largest register consumer, is not compiled in.
@@ -104,7 +125,10 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
     // KdNodeToVisit {node, tMin, tMax}: the three words of an entry 64 dwords apart
     __shared__ float s_stack[kKdBlock / 64][W][3][64];
     // cold per-ray state ([field][lane]): ray index, best hit (closest), reached-a-host-primitive flag
-    constexpr int kColdRi = 0, kColdHit = 1, kColdHost = (MODE == 0) ? 5 : 1, kColdFields = kColdHost + 1;
+    constexpr bool BATCH = MODE >= 2, SOA = MODE == 3;
+    static_assert(MODE >= 0 && MODE <= 3 && (!SOA || (!PATCH && !ATTR)), "SOA instances: the lean form only");
+    constexpr int kAnyLane = 128;  // BATCH: bit 7 of r.kz
+    constexpr int kColdRi = 0, kColdHit = 1, kColdHost = (MODE != 1) ? 5 : 1, kColdFields = kColdHost + 1;
     __shared__ float s_cold[kKdBlock / 64][kColdFields][64];
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -122,6 +146,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
     }
     int queuesTried = 0;
     const long nRays = p.n;
+    int curBatch = 0;  // BATCH: the batch this wave draws from
 
     RayState r;          // o, 1/d, shear; r.kz also carries bit 4 + k = (d[k] <= 0), see the refill
     V3 d = {0, 0, 0};    // PATCH only: the patch test reads the direction
@@ -171,7 +196,31 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
             const int ri = isIdle ? __float_as_int(cold[kColdRi][lane]) : -1;
             if (ri >= 0) {
                 const bool needHost = p.hasHostPrims && cold[kColdHost][lane] != 0.0f;
-                if (MODE == 0) {
+                if constexpr (BATCH) {  // the lane's batch has its own arrays
+                    const int b = ri >> kKdIndexBits;
+                    const long idx = ri & ((1 << kKdIndexBits) - 1);
+                    void *outp = b == 0 ? p.bOut[0] : (b == 1 ? p.bOut[1] : (b == 2 ? p.bOut[2] : p.bOut[3]));
+                    if (r.kz & kAnyLane) {
+                        int32_t *vis = b == 0 ? p.bVisited[0] : (b == 1 ? p.bVisited[1] : (b == 2 ? p.bVisited[2] : p.bVisited[3]));
+                        int32_t *tst = b == 0 ? p.bTests[0] : (b == 1 ? p.bTests[1] : (b == 2 ? p.bTests[2] : p.bTests[3]));
+                        reinterpret_cast<uint8_t *>(outp)[idx] = found ? 1 : (needHost ? 2 : 0);
+                        if (vis) vis[idx] = visited;
+                        if (tst) tst[idx] = tests;
+                    } else {
+                        float4 h0, h1;
+                        h0.x = cold[kColdHit][lane];
+                        h0.y = rayTMax;
+                        h0.z = cold[kColdHit + 1][lane];
+                        h0.w = cold[kColdHit + 2][lane];
+                        h1.x = cold[kColdHit + 3][lane];
+                        h1.y = __int_as_float(visited);
+                        h1.z = __int_as_float(tests);
+                        h1.w = needHost ? __int_as_float(-1) : 0.0f;
+                        float4 *out = reinterpret_cast<float4 *>(outp) + 2 * idx;
+                        out[0] = h0;
+                        out[1] = h1;
+                    }
+                } else if (MODE == 0) {
                     float4 h0, h1;
                     h0.x = cold[kColdHit][lane];
                     h0.y = rayTMax;
@@ -195,9 +244,17 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
             for (;;) {
                 static_assert(kKdQueues == 8, "queue ranges are computed with a shift by 3");
                 const int qShift = p.nQueues > 1 ? 3 : 0;  // nQueues is 1 or 8: a shift, not a 64-bit division
-                const long qBegin = (nRays * q) >> qShift, qEnd = (nRays * (q + 1)) >> qShift;
+                long nQ = nRays;
+                if constexpr (BATCH) {
+                    nQ = p.bN[curBatch];
+                    if (const int32_t *nd = p.bNDev[curBatch]) {  // wavefront queues: the size lives on the device
+                        const long v = *nd;
+                        nQ = v < 0 ? 0 : (v < nQ ? v : nQ);
+                    }
+                }
+                const long qBegin = (nQ * q) >> qShift, qEnd = (nQ * (q + 1)) >> qShift;
                 unsigned got = 0;
-                if (lane == 0) got = atomicAdd(&p.queue[q * kKdQueueStride], (unsigned)nIdle);
+                if (lane == 0) got = atomicAdd(&p.queue[((BATCH ? curBatch * p.nQueues : 0) + q) * kKdQueueStride], (unsigned)nIdle);
                 got = __builtin_amdgcn_readfirstlane(got);
                 const long start = qBegin + (long)got;
                 if (start < qEnd) {
@@ -207,15 +264,30 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                     break;
                 }
                 if (++queuesTried >= p.nQueues) {
+                    if constexpr (BATCH) {
+                        if (curBatch + 1 < p.nBatches) {  // this batch is handed out (or empty): on to the next
+                            ++curBatch;
+                            queuesTried = 0;
+                            continue;
+                        }
+                    }
                     exhausted = true;
                     break;
                 }
                 q = (q + 1 == p.nQueues) ? 0 : q + 1;
             }
-            if (isIdle) cold[kColdRi][lane] = __int_as_float(newRi);
+            if (isIdle) cold[kColdRi][lane] = __int_as_float((BATCH && newRi >= 0) ? (newRi | (curBatch << kKdIndexBits)) : newRi);
             if (newRi >= 0) {
-                const float4 *in = reinterpret_cast<const float4 *>(p.rays) + 2 * (long)newRi;
-                const float4 r0 = in[0], r1 = in[1];
+                float4 r0, r1;
+                if constexpr (SOA) {  // a wavefront queue: SOA<Ray> slices (wavefront/workitems.soa:40-50)
+                    const nnbvh_ray_soa &s = p.bSoa[curBatch];
+                    r0 = {s.ox[newRi], s.oy[newRi], s.oz[newRi], s.tmax ? s.tmax[newRi] : __builtin_inff()};
+                    r1 = {s.dx[newRi], s.dy[newRi], s.dz[newRi], s.time ? s.time[newRi] : 0.0f};
+                } else {
+                    const float4 *in = reinterpret_cast<const float4 *>(BATCH ? p.bRays[curBatch] : p.rays) + 2 * (long)newRi;
+                    r0 = in[0];
+                    r1 = in[1];
+                }
                 r.o = {r0.x, r0.y, r0.z};
                 rayTMax = r0.w;
                 const V3 dir = {r1.x, r1.y, r1.z};
@@ -224,7 +296,8 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                 ray_shear(r, dir);
                 // `ray.d[axis] <= 0` of aggregates.cpp:1002-1003, once per ray
                 r.kz |= (dir.x <= 0.0f ? 16 : 0) | (dir.y <= 0.0f ? 32 : 0) | (dir.z <= 0.0f ? 64 : 0);
-                if (MODE == 0) {
+                if constexpr (BATCH) r.kz |= ((p.anyMask >> curBatch) & 1u) ? kAnyLane : 0;
+                if (MODE != 1) {
                     cold[kColdHit][lane] = __int_as_float(-1);
                     cold[kColdHit + 1][lane] = 0.0f;
                     cold[kColdHit + 2][lane] = 0.0f;
@@ -334,7 +407,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                         }
                     }
                     if (hit) {
-                        if (MODE == 0) {
+                        if (MODE == 0 || (BATCH && !(r.kz & kAnyLane))) {
                             cold[kColdHit][lane] = s0.w;
                             cold[kColdHit + 1][lane] = x0;
                             cold[kColdHit + 2][lane] = x1;
@@ -348,7 +421,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                 leafLeft -= 1;
                 leafIdx = nextIdx;
                 leafPos += 1;
-                if (MODE == 1 && found) cur = kKdDone;  // :1091-1094, :1101-1104
+                if ((MODE == 1 || BATCH) && found) cur = kKdDone;  // :1091-1094, :1101-1104 (only any-hit lanes set it)
                 else if (leafLeft == 0) pop_or_done();
             }
         } else {
@@ -356,7 +429,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
             int rep = 0;
             do {
                 if (cur >= 0) {
-                    if (MODE == 0 && rayTMax < tMin) {  // :989-991 a hit closer than this node: finished
+                    if ((MODE == 0 || (BATCH && !(r.kz & kAnyLane))) && rayTMax < tMin) {  // :989-991 a hit closer than this node: finished
                         cur = kKdDone;
                     } else {
                         visited += 1;
@@ -438,13 +511,6 @@ struct KdDeviceGuard {
     }
 };
 
-struct KdWorkspace {
-    unsigned *queue = nullptr;
-    float4 *spill = nullptr;
-    void *d_in = nullptr, *d_out = nullptr, *d_aux0 = nullptr, *d_aux1 = nullptr;
-    size_t in_bytes = 0, out_bytes = 0, aux_bytes = 0;
-};
-
 static bool kd_grow(void **ptr, size_t *have, size_t need, const char *what) {
     if (*have >= need) return true;
     if (*ptr) (void)hipFree(*ptr);
@@ -475,24 +541,7 @@ static bool kd_triangle_is_degenerate(const float *p0, const float *p1, const fl
 
 using namespace nnbvh;
 
-struct nnbvh_kd_scene {
-    int device = 0;
-    int n_cus = 0;
-    int depth = 0;
-    int has_host_prims = 0;
-    int has_patches = 0;
-    int fits32 = 0;  // nodes (8 B), primitive records (64 B) and indices (4 B) each below 4 GiB
-    float bounds[6];
-    uint2 *d_nodes = nullptr;
-    int32_t *d_indices = nullptr;
-    float4 *d_prims = nullptr;
-    float4 *d_extras = nullptr;  // 6 slots per primitive, scenes with attribute-reading alpha kinds only
-    int blocks_per_cu[2] = {0, 0};
-    std::mutex mu;
-    std::map<hipStream_t, KdWorkspace> workspaces;
-};
-
-static KdWorkspace *kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream) {
+KdWorkspace *nnbvh::kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream) {
     auto it = s->workspaces.find(stream);
     if (it != s->workspaces.end()) return &it->second;
     KdWorkspace w;
@@ -500,7 +549,7 @@ static KdWorkspace *kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream) {
     // smallest window any instance runs with
     const size_t spill_levels = (size_t)std::max(s->depth + 1 - std::min(kKdW, kKdWLean), 1);
     const size_t spill_bytes = spill_levels * (size_t)s->n_cus * 8 * kKdBlock * sizeof(float4);
-    if (!kd_hip_ok(hipMalloc((void **)&w.queue, kKdQueues * kKdQueueStride * sizeof(unsigned)), "hipMalloc(queue)"))
+    if (!kd_hip_ok(hipMalloc((void **)&w.queue, kKdMaxBatches * kKdQueues * kKdQueueStride * sizeof(unsigned)), "hipMalloc(queue)"))
         return nullptr;
     if (!kd_hip_ok(hipMalloc((void **)&w.spill, spill_bytes), "hipMalloc(spill)")) {
         (void)hipFree(w.queue);
@@ -509,20 +558,12 @@ static KdWorkspace *kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream) {
     return &(s->workspaces[stream] = w);
 }
 
-static int kd_launch(nnbvh_kd_scene *s, int mode, const void *d_rays, int64_t n, void *d_hits, void *d_occ,
-                     void *d_vis, void *d_tests, hipStream_t stream, KdWorkspace *w) {
-    KdParams p;
+static void kd_fill_scene(const nnbvh_kd_scene *s, const KdWorkspace *w, KdParams &p) {
     p.nodes = s->d_nodes;
     p.primIndices = s->d_indices;
     p.prims = s->d_prims;
     std::memcpy(p.bmin, s->bounds, 12);
     std::memcpy(p.bmax, s->bounds + 3, 12);
-    p.rays = (const nnbvh_ray *)d_rays;
-    p.hits = (nnbvh_hit *)d_hits;
-    p.occluded = (uint8_t *)d_occ;
-    p.visitedOut = (int32_t *)d_vis;
-    p.testsOut = (int32_t *)d_tests;
-    p.n = (long)n;
     p.queue = w->queue;
     p.nQueues = kKdQueues;
     p.primWeight = 12;  // swept on bathroom: 12 / 8 / 4 is the best of 4 x 2 x 3 (+1.5 % over 24 / 8 / 4)
@@ -530,6 +571,22 @@ static int kd_launch(nnbvh_kd_scene *s, int mode, const void *d_rays, int64_t n,
     p.nodeRepeat = 4;
     p.hasHostPrims = s->has_host_prims;
     p.spill = w->spill;
+    p.extras = s->d_extras;
+}
+
+// lean scenes (no patches, no attributes): their batch-mode instance has a form that reads SOA slices itself
+static bool kd_scene_reads_soa(const nnbvh_kd_scene *s) { return s->read_soa && !s->has_patches && !s->d_extras; }
+
+static int kd_launch(nnbvh_kd_scene *s, int mode, const void *d_rays, int64_t n, void *d_hits, void *d_occ,
+                     void *d_vis, void *d_tests, hipStream_t stream, KdWorkspace *w) {
+    KdParams p{};
+    kd_fill_scene(s, w, p);
+    p.rays = (const nnbvh_ray *)d_rays;
+    p.hits = (nnbvh_hit *)d_hits;
+    p.occluded = (uint8_t *)d_occ;
+    p.visitedOut = (int32_t *)d_vis;
+    p.testsOut = (int32_t *)d_tests;
+    p.n = (long)n;
     // the four instances: closest / any hit x scenes with / without bilinear patches
     void (*const kernels[8])(KdParams) = {
         kd_trace_kernel<0, 0, kKdWLean, 0>, kd_trace_kernel<1, 0, kKdWLean, 0>, kd_trace_kernel<0, 1, kKdW, 0>,
@@ -538,7 +595,6 @@ static int kd_launch(nnbvh_kd_scene *s, int mode, const void *d_rays, int64_t n,
     // ... and the attribute-reading forms of the PATCH instances
     void (*const attr_kernels[4])(KdParams) = {kd_trace_kernel<0, 1, kKdW, 0, 1>, kd_trace_kernel<1, 1, kKdW, 0, 1>,
                                                kd_trace_kernel<0, 1, kKdW, 1, 1>, kd_trace_kernel<1, 1, kKdW, 1, 1>};
-    p.extras = s->d_extras;
     void (*const kernel)(KdParams) = s->d_extras ? attr_kernels[mode + 2 * s->fits32]
                                                  : kernels[mode + 2 * s->has_patches + 4 * s->fits32];
     if (s->blocks_per_cu[mode] == 0) {
@@ -552,6 +608,65 @@ static int kd_launch(nnbvh_kd_scene *s, int mode, const void *d_rays, int64_t n,
     hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, w->queue, kKdQueues * kKdQueueStride);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
     return kd_hip_ok(hipGetLastError(), "kd trace kernel launch") ? NNBVH_OK : NNBVH_ERR_DEVICE;
+}
+
+int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdBatch *batches, int n_batches) {
+    KdParams p{};
+    kd_fill_scene(s, w, p);
+    bool all_soa = true;
+    int64_t total = 0, soa_rays = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        all_soa = all_soa && !batches[b].rays;
+        if (!batches[b].rays) soa_rays += batches[b].n;
+        total += batches[b].n;
+    }
+    const bool read_soa = all_soa && kd_scene_reads_soa(s);
+    if (!read_soa && soa_rays > 0 &&
+        !kd_grow(&w->d_in, &w->in_bytes, (size_t)soa_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
+        return NNBVH_ERR_DEVICE;
+    char *gathered = (char *)w->d_in;
+    p.nBatches = n_batches;
+    p.anyMask = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        const KdBatch &k = batches[b];
+        p.anyMask |= k.any ? 1u << b : 0u;
+        p.bOut[b] = k.out;
+        p.bVisited[b] = k.any ? (int32_t *)k.visited : nullptr;
+        p.bTests[b] = k.any ? (int32_t *)k.tests : nullptr;
+        p.bN[b] = (long)k.n;
+        p.bNDev[b] = k.d_n;
+        if (read_soa) {
+            if (k.soa) p.bSoa[b] = *k.soa;  // (an empty batch may come without slices)
+        } else if (!k.rays && k.n > 0) {
+            if (!kd_hip_ok(launch_wf_gather(*k.soa, WavefrontCount{(int)k.n, k.d_n}, gathered, s->n_cus * 8, stream),
+                           "gather kernel launch"))
+                return NNBVH_ERR_DEVICE;
+            p.bRays[b] = (const nnbvh_ray *)gathered;
+            gathered += (size_t)k.n * sizeof(nnbvh_ray);
+        } else {
+            p.bRays[b] = (const nnbvh_ray *)k.rays;
+        }
+    }
+    // record form: lean / patches / attributes, each with and without 32-bit offsets; SOA form: lean only
+    void (*const kernels[8])(KdParams) = {
+        kd_trace_kernel<2, 0, kKdWLean, 0>, kd_trace_kernel<2, 1, kKdW, 0>, kd_trace_kernel<2, 1, kKdW, 0, 1>,
+        kd_trace_kernel<3, 0, kKdWLean, 0>, kd_trace_kernel<2, 0, kKdWLean, 1>, kd_trace_kernel<2, 1, kKdW, 1>,
+        kd_trace_kernel<2, 1, kKdW, 1, 1>,  kd_trace_kernel<3, 0, kKdWLean, 1>};
+    const int form = read_soa ? 3 : (s->d_extras ? 2 : (s->has_patches ? 1 : 0));
+    void (*const kernel)(KdParams) = kernels[form + 4 * s->fits32];
+    const int slot = read_soa ? 3 : 2;
+    if (s->blocks_per_cu[slot] == 0) {
+        int occ = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kKdBlock, 0);
+        s->blocks_per_cu[slot] = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
+    }
+    int blocks = s->n_cus * s->blocks_per_cu[slot];
+    const int64_t need = (total + kKdBlock - 1) / kKdBlock;
+    if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
+    hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, w->queue,
+                       n_batches * kKdQueues * kKdQueueStride);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
+    return kd_hip_ok(hipGetLastError(), "kd batch trace kernel launch") ? NNBVH_OK : NNBVH_ERR_DEVICE;
 }
 
 extern "C" {
@@ -744,7 +859,7 @@ void nnbvh_kd_scene_destroy(nnbvh_kd_scene *s) {
     KdDeviceGuard guard(s->device);
     for (auto &kv : s->workspaces) {
         KdWorkspace &w = kv.second;
-        for (void *ptr : {(void *)w.queue, (void *)w.spill, w.d_in, w.d_out, w.d_aux0, w.d_aux1})
+        for (void *ptr : {(void *)w.queue, (void *)w.spill, w.d_in, w.d_out, w.d_aux0, w.d_aux1, w.d_hits})
             if (ptr) (void)hipFree(ptr);
     }
     if (s->d_nodes) (void)hipFree(s->d_nodes);
@@ -782,6 +897,53 @@ int nnbvh_kd_intersect_any_device(nnbvh_kd_scene *s, const void *d_rays, int64_t
     KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
     if (!w) return NNBVH_ERR_DEVICE;
     return kd_launch(s, 1, d_rays, n, nullptr, d_occluded, d_nodes_visited, d_prim_tests, (hipStream_t)stream, w);
+}
+
+int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value) {
+    if (!s || !key) {
+        set_error("kd_scene_set_option: null argument");
+        return NNBVH_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lock(s->mu);
+    const std::string k(key);
+    if (k == "read_soa") s->read_soa = value != 0;
+    else if (k == "pair_one_launch") s->pair_one_launch = value != 0;
+    else {
+        set_error("kd_scene_set_option: unknown key " + k);
+        return NNBVH_ERR_ARG;
+    }
+    return NNBVH_OK;
+}
+
+int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches, void *stream) {
+    if (!s || !batches || n_batches < 1 || n_batches > kKdMaxBatches) {
+        set_error("kd_trace_batches_device: bad argument (a scene and 1..4 batches)");
+        return NNBVH_ERR_ARG;
+    }
+    KdBatch jobs[kKdMaxBatches];
+    int64_t total = 0;
+    for (int b = 0; b < n_batches; ++b) {
+        const nnbvh_batch &k = batches[b];
+        if ((k.kind != NNBVH_BATCH_CLOSEST && k.kind != NNBVH_BATCH_ANY) || k.n < 0 || k.n >= (1LL << kKdIndexBits) ||
+            (k.n > 0 && (!k.d_rays || !k.d_out))) {
+            set_error("kd_trace_batches_device: bad batch (kind, 0 <= n < 2^28, rays and output)");
+            return NNBVH_ERR_ARG;
+        }
+        jobs[b].any = k.kind == NNBVH_BATCH_ANY;
+        jobs[b].rays = k.d_rays;
+        jobs[b].n = k.n;
+        jobs[b].out = k.d_out;
+        jobs[b].visited = k.d_nodes_visited;
+        jobs[b].tests = k.d_prim_tests;
+        total += k.n;
+    }
+    if (total == 0) return NNBVH_OK;
+    KdDeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    return kd_launch_batches(s, w, (hipStream_t)stream, jobs, n_batches);
 }
 
 int nnbvh_kd_intersect_closest(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits) {

@@ -51,9 +51,10 @@ def build_kd_tree(prims, verts, prim_bounds=None, isect_cost=5, traversal_cost=1
 class KdTreeAggregate:
     """KdTreeAggregate (cpu/aggregates.h:75-105) resident on the device."""
 
-    def __init__(self, handle, bounds):
+    def __init__(self, handle, bounds, device=0):
         self._h = handle
         self.bounds = bounds
+        self.device = device
 
     @classmethod
     def from_tree(cls, nodes, prim_indices, prims, verts, bounds, device=0, normals=None, uvs=None, prim_alpha=None):
@@ -73,7 +74,7 @@ class KdTreeAggregate:
             len(verts), ptr(bounds), opt(nrm), opt(uv), opt(pa), device)
         if not h:
             raise _lib.NNBVHError(f"nnbvh_kd_scene_create failed: {_lib.last_error()}")
-        return cls(h, bounds)
+        return cls(h, bounds, device)
 
     @classmethod
     def build(cls, prims, verts, device=0, normals=None, uvs=None, prim_alpha=None, **kw):
@@ -122,6 +123,26 @@ class KdTreeAggregate:
                                                        ctypes.c_void_p(d_tests) if d_tests else None,
                                                        ctypes.c_void_p(stream)),
               "nnbvh_kd_intersect_any_device")
+
+    def set_option(self, key, value):
+        """nnbvh_kd_scene_set_option: "read_soa", "pair_one_launch" (speed only, never results)."""
+        check(_lib.lib().nnbvh_kd_scene_set_option(self._h, key.encode(), int(value)), f"kd set_option({key})")
+
+    def trace_batches_device(self, batches, stream=0):
+        """nnbvh_kd_trace_batches_device: 1..4 independent batches, closest-hit and any-hit mixed, in ONE kernel launch
+        on `stream`.  batches: iterable of (kind, d_rays, n, d_out[, d_visited, d_tests]) with kind "closest"
+        (d_out: HIT_DTYPE records) or "any" (d_out: uint8 flags; the optional int32 arrays get the exact counts);
+        device pointers."""
+        rec = np.zeros(len(batches), _lib.BATCH_DTYPE)
+        for k, b in enumerate(batches):
+            kind, d_rays, n, d_out = b[:4]
+            rec[k]["kind"] = {"closest": 0, "any": 1}[kind]
+            rec[k]["d_rays"], rec[k]["n"], rec[k]["d_out"] = d_rays or 0, n, d_out or 0
+            rec[k]["d_nodes_visited"] = (b[4] or 0) if len(b) > 4 else 0
+            rec[k]["d_prim_tests"] = (b[5] or 0) if len(b) > 5 else 0
+        check(_lib.lib().nnbvh_kd_trace_batches_device(self._h, ptr(rec) if len(rec) else None, len(rec),
+                                                       ctypes.c_void_p(stream)),
+              "nnbvh_kd_trace_batches_device")
 
 
 # ---- nss learned kd-trees ---------------------------------------------------------------------

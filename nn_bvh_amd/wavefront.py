@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import CLOSEST_QUEUES, check, ptr
+from .kdtree import KdTreeAggregate
 
 
 class WorkQueue:
@@ -186,13 +187,17 @@ def record_shadow(max_rays, shadow_queue, occluded, Ld, r_u, r_l, pixel_index, L
 
 
 class WavefrontAggregate:
-    """IntersectClosest / IntersectShadow of wavefront/integrator.h:32-54 on one BVHAggregate.
+    """IntersectClosest / IntersectShadow of wavefront/integrator.h:32-54 on one BVHAggregate or KdTreeAggregate
+    (a kd scene offers the five queue calls without candidates; IntersectShadowTr, IntersectOneRandom and the
+    *WithCandidates methods raise NNBVHError for it).
 
     prim_class: optional uint8 per primitive id (nn_bvh_amd._lib.CLASS_*), what the reference
     reads off the hit's SurfaceInteraction when it decides the destination queues."""
 
     def __init__(self, aggregate, prim_class=None):
         self.aggregate = aggregate
+        # a KdTreeAggregate binds the nnbvh_kd_wavefront_* entry points: the same argument lists on a kd scene
+        self._prefix = "nnbvh_kd_wavefront_" if isinstance(aggregate, KdTreeAggregate) else "nnbvh_wavefront_"
         self.device = torch.device("cuda", aggregate.device)
         self.prim_class = None
         if prim_class is not None:
@@ -200,6 +205,17 @@ class WavefrontAggregate:
 
     def Bounds(self):
         return self.aggregate.Bounds()
+
+    def _name(self, call):
+        return self._prefix + call
+
+    def _entry(self, call):
+        return getattr(_lib.lib(), self._prefix + call)
+
+    def _bvh_only(self, method):
+        if self._prefix != "nnbvh_wavefront_":
+            raise _lib.NNBVHError(f"WavefrontAggregate.{method} is not offered for kd-tree scenes (DESIGN.md §8): "
+                                  "bind a BVH aggregate for it")
 
     def IntersectClosest(self, max_rays, ray_queue, escaped=None, hit_area_light=None,
                          basic_eval_material=None, universal_eval_material=None, medium_sample=None,
@@ -213,10 +229,10 @@ class WavefrontAggregate:
                                                         universal_eval_material, medium_sample, next_ray))))
         soa = ray_queue._wire()
         pc = self.prim_class
-        check(_lib.lib().nnbvh_wavefront_intersect_closest(
+        check(self._entry("intersect_closest")(
             self.aggregate._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), *_ptr_count(pc),
             hits.data_ptr(), ptr(qrec), torch.cuda.current_stream(self.device).cuda_stream),
-            "nnbvh_wavefront_intersect_closest")
+            self._name("intersect_closest"))
         return hits
 
     def IntersectShadow(self, max_rays, shadow_queue, Ld, r_u, r_l, pixel_index, L, occluded=None):
@@ -225,12 +241,12 @@ class WavefrontAggregate:
         float32 [capacity, 4]; L: float32 [n_pixels, 4]; all device tensors."""
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa = shadow_queue._wire()
-        check(_lib.lib().nnbvh_wavefront_intersect_shadow(
+        check(self._entry("intersect_shadow")(
             self.aggregate._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(), Ld.data_ptr(),
             r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0],
             occluded.data_ptr() if occluded is not None else None,
             torch.cuda.current_stream(self.device).cuda_stream),
-            "nnbvh_wavefront_intersect_shadow")
+            self._name("intersect_shadow"))
 
     def IntersectClosestAndShadow(self, max_rays, ray_queue, max_shadow_rays, shadow_queue, Ld, r_u, r_l, pixel_index,
                                   L, escaped=None, hit_area_light=None, basic_eval_material=None,
@@ -247,12 +263,12 @@ class WavefrontAggregate:
                                                         universal_eval_material, medium_sample, next_ray))))
         soa, ssoa = ray_queue._wire(), shadow_queue._wire()
         pc = self.prim_class
-        check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow(
+        check(self._entry("intersect_closest_and_shadow")(
             self.aggregate._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(), *_ptr_count(pc), hits.data_ptr(),
             ptr(qrec), int(max_shadow_rays), ptr(ssoa), shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(),
             r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0],
             occluded.data_ptr() if occluded is not None else None,
-            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_closest_and_shadow")
+            torch.cuda.current_stream(self.device).cuda_stream), self._name("intersect_closest_and_shadow"))
         return hits
 
     def IntersectClosestItems(self, max_rays, ray_queue, shading_mesh, items=None, needs_host=None, hits=None,
@@ -265,11 +281,11 @@ class WavefrontAggregate:
         Returns hits."""
         pc = self.prim_class
         soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
-        check(_lib.lib().nnbvh_wavefront_intersect_closest_items(
+        check(self._entry("intersect_closest_items")(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
             *_ptr_count(pc), hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec),
             torch.cuda.current_stream(self.device).cuda_stream),
-            "nnbvh_wavefront_intersect_closest_items")
+            self._name("intersect_closest_items"))
         return hits
 
     def IntersectClosestAndShadowItems(self, max_rays, ray_queue, shading_mesh, max_shadow_rays, shadow_queue, Ld,
@@ -280,13 +296,13 @@ class WavefrontAggregate:
         pc = self.prim_class
         soa, ssoa = ray_queue._wire(), shadow_queue._wire()
         qrec, irec = _queues_record(queues), _items_record(items, needs_host)
-        check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow_items(
+        check(self._entry("intersect_closest_and_shadow_items")(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
             *_ptr_count(pc), hits.data_ptr() if hits is not None else None, ptr(qrec), ptr(irec),
             int(max_shadow_rays), ptr(ssoa),
             shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(),
             L.data_ptr(), L.shape[0], occluded.data_ptr() if occluded is not None else None,
-            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_closest_and_shadow_items")
+            torch.cuda.current_stream(self.device).cuda_stream), self._name("intersect_closest_and_shadow_items"))
         return hits
 
     def IntersectClosestItemsWithCandidates(self, max_rays, ray_queue, shading_mesh, candidates, hits, items=None,
@@ -297,6 +313,7 @@ class WavefrontAggregate:
         IntersectClosestItems routes them; the others go to needs_host only, their candidate-mode record in hits:
         resolve them (resolve_host_candidates), write the merged records back and enqueue them with
         enqueue_closest_items(index=needs_host)."""
+        self._bvh_only("IntersectClosestItemsWithCandidates")
         pc = self.prim_class
         soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
         c = candidates._wire()
@@ -312,6 +329,7 @@ class WavefrontAggregate:
         """IntersectShadow with host candidates (nnbvh_wavefront_intersect_shadow_candidates): occluded (required,
         uint8 [capacity]) gets 0 / 1 / 2; rays with 0 add to L, rays with 2 and count > 0 are the caller's to test
         (resolve_host_candidates_any) and to record with record_shadow."""
+        self._bvh_only("IntersectShadowWithCandidates")
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa, c = shadow_queue._wire(), candidates._wire()
         check(_lib.lib().nnbvh_wavefront_intersect_shadow_candidates(
@@ -325,6 +343,7 @@ class WavefrontAggregate:
                                                      **queues):
         """IntersectClosestItemsWithCandidates and IntersectShadowWithCandidates in ONE launch of the traversal
         kernel (nnbvh_wavefront_intersect_closest_and_shadow_items_candidates); same results as the two calls."""
+        self._bvh_only("IntersectClosestAndShadowItemsWithCandidates")
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         pc = self.prim_class
         soa, ssoa = ray_queue._wire(), shadow_queue._wire()
@@ -344,6 +363,7 @@ class WavefrontAggregate:
         164-274) without media: shadow rays pass through interface surfaces (CLASS_INTERFACE) and are
         blocked by the first surface with a material; arriving rays add Ld * (1 / (r_u + r_l).Average())
         to L[pixel_index].  state: optional uint8 [capacity] out (0 arrived, 1 blocked, 2 host)."""
+        self._bvh_only("IntersectShadowTr")
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa = shadow_queue._wire()
         pc = self.prim_class
@@ -357,6 +377,7 @@ class WavefrontAggregate:
         """IntersectOneRandom (wavefront/aggregate.cpp:90-116): p0, p1 float32 [n, 3], material int32 [n]
         device tensors; prim_material int32 per primitive id.  Returns (selected hit records uint8
         [n, 32], their segment rays uint8 [n, 32], reservoir pdf float32 [n], weight sum float32 [n])."""
+        self._bvh_only("IntersectOneRandom")
         for t in (p0, p1):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 3
         assert material.dtype == torch.int32 and material.is_contiguous()
