@@ -747,6 +747,40 @@ static int alpha_intersect(const orc_prim *p, const float *verts, const float o[
     return 1;
 }
 
+/* ---- pending-list depth (the optional per-ray output of orc_set_pending_depth_out) ------------- */
+/* How many entries of nodesToVisit[64] were in use at once: g_pend_base = the entries the walks
+ * that called into this one hold at the moment (a TransformedPrimitive's child aggregate runs with
+ * the outer walk's entries still pending), g_pend_max = the ray's maximum of base + toVisitOffset.
+ * g_tree_max = the maximum toVisitOffset of the tree walk that returned last; g_pend_outer /
+ * g_pend_child = the outer entries pending at an instance's entry and that child walk's own maximum,
+ * of the instance visit with the largest min(outer, child).  Counters only: no result depends on them. */
+static int32_t *g_pending_out = NULL;
+void orc_set_pending_depth_out(int32_t *out3) { g_pending_out = out3; }
+static __thread int g_pend_base = 0, g_pend_max = 0, g_tree_max = 0, g_pend_outer = 0, g_pend_child = 0;
+static inline void pend_reset(void) { g_pend_base = g_pend_max = g_tree_max = g_pend_outer = g_pend_child = 0; }
+static inline void pend_push(int to_visit, int *tree_max) {
+    if (to_visit > *tree_max) *tree_max = to_visit;
+    if (g_pend_base + to_visit > g_pend_max) g_pend_max = g_pend_base + to_visit;
+}
+static inline int pend_enter(int to_visit) { /* returns the base to restore */
+    const int saved = g_pend_base;
+    g_pend_base = saved + to_visit;
+    return saved;
+}
+static inline void pend_leave(int saved) {
+    const int outer = g_pend_base, child = g_tree_max;
+    const int m = outer < child ? outer : child;
+    const int best = g_pend_outer < g_pend_child ? g_pend_outer : g_pend_child;
+    if (m > best || (g_pend_outer == 0 && g_pend_child == 0)) g_pend_outer = outer, g_pend_child = child;
+    g_pend_base = saved;
+}
+static inline void pend_store(int64_t i) {
+    if (!g_pending_out) return;
+    g_pending_out[3 * i] = g_pend_max;
+    g_pending_out[3 * i + 1] = g_pend_outer;
+    g_pending_out[3 * i + 2] = g_pend_child;
+}
+
 /* ---- BVHAggregate::Intersect, aggregates.cpp:529-579 -------------------------------- */
 /* One BVHAggregate::Intersect over the tree rooted at `root`; hit/tmax/counters are carried
  * by the caller so that a TransformedPrimitive's child aggregate (cpu/primitive.cpp:112-126)
@@ -758,7 +792,7 @@ static void closest_tree(const orc_node *nodes, const orc_prim *prims, const flo
     float tmax = *tmax_io;
     float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
     int neg[3] = {inv[0] < 0, inv[1] < 0, inv[2] < 0};
-    int to_visit = 0, cur = root, visited = *visited_io, tests = *tests_io;
+    int to_visit = 0, cur = root, visited = *visited_io, tests = *tests_io, tree_max = 0;
     int stack[64];
     for (;;) {
         ++visited;
@@ -780,8 +814,10 @@ static void closest_tree(const orc_node *nodes, const orc_prim *prims, const flo
                         float inner_tmax = x[6];
                         orc_hit inner = *hit;
                         inner.prim = -1;
+                        const int pend_saved = pend_enter(to_visit);
                         closest_tree(nodes, prims, verts, instances, in->root, x, x + 3,
                                      &inner_tmax, &inner, &visited, &tests, p->v[0] + 1, host_io);
+                        pend_leave(pend_saved);
                         if (inner.prim >= 0) { /* si = primSi; tMax = si->tHit */
                             *hit = inner;
                             tmax = inner.t;
@@ -815,6 +851,7 @@ static void closest_tree(const orc_node *nodes, const orc_prim *prims, const flo
                     stack[to_visit++] = nd->offset;
                     cur = cur + 1;
                 }
+                pend_push(to_visit, &tree_max);
             }
         } else {
             if (to_visit == 0) break;
@@ -824,6 +861,7 @@ static void closest_tree(const orc_node *nodes, const orc_prim *prims, const flo
     *tmax_io = tmax;
     *visited_io = visited;
     *tests_io = tests;
+    g_tree_max = tree_max;
 }
 
 static void closest_one(const orc_node *nodes, const orc_prim *prims, const float *verts,
@@ -849,7 +887,7 @@ static int any_tree(const orc_node *nodes, const orc_prim *prims, const float *v
                     float tmax, int *visited_io, int *tests_io, int *host_io) {
     float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
     int neg[3] = {inv[0] < 0, inv[1] < 0, inv[2] < 0};
-    int to_visit = 0, cur = root, visited = *visited_io, tests = *tests_io, found = 0;
+    int to_visit = 0, cur = root, visited = *visited_io, tests = *tests_io, found = 0, tree_max = 0;
     int stack[64];
     for (;;) {
         ++visited;
@@ -868,8 +906,11 @@ static int any_tree(const orc_node *nodes, const orc_prim *prims, const float *v
                         float x[7], mi12[12];
                         instance_minv(in, p->v[0], mi12);
                         orc_apply_inverse_ray(mi12, o, d, tmax, x);
-                        if (any_tree(nodes, prims, verts, instances, in->root, x, x + 3, x[6],
-                                     &visited, &tests, host_io)) {
+                        const int pend_saved = pend_enter(to_visit);
+                        const int inner_found = any_tree(nodes, prims, verts, instances, in->root, x, x + 3, x[6],
+                                                         &visited, &tests, host_io);
+                        pend_leave(pend_saved);
+                        if (inner_found) {
                             found = 1;
                             goto done;
                         }
@@ -897,6 +938,7 @@ static int any_tree(const orc_node *nodes, const orc_prim *prims, const float *v
                     stack[to_visit++] = nd->offset;
                     cur = cur + 1;
                 }
+                pend_push(to_visit, &tree_max);
             }
         } else {
             if (to_visit == 0) break;
@@ -906,6 +948,7 @@ static int any_tree(const orc_node *nodes, const orc_prim *prims, const float *v
 done:
     *visited_io = visited;
     *tests_io = tests;
+    g_tree_max = tree_max;
     return found;
 }
 
@@ -941,6 +984,7 @@ static void *orc_worker(void *arg) {
     g_anims = j->anims;
     for (int64_t i = j->begin; i < j->end; ++i) {
         g_ray_time = j->rays[i].time;
+        pend_reset();
         if (j->any) {
             int v, t;
             int f = any_one(j->nodes, j->prims, j->verts, j->instances, &j->rays[i], &v, &t);
@@ -950,6 +994,7 @@ static void *orc_worker(void *arg) {
         } else {
             closest_one(j->nodes, j->prims, j->verts, j->instances, &j->rays[i], &j->hits[i]);
         }
+        pend_store(i);
     }
     return NULL;
 }
@@ -1769,6 +1814,7 @@ static void kd_one(const orc_kd_node *nodes, const int32_t *prim_indices, const 
                     toVisit[toVisitIndex].tMin = tSplit;
                     toVisit[toVisitIndex].tMax = tMax;
                     ++toVisitIndex;
+                    if (toVisitIndex > g_pend_max) g_pend_max = toVisitIndex; /* todoPos */
                     node = firstChild;
                     tMax = tSplit;
                 }
@@ -1841,12 +1887,14 @@ typedef struct {
 static void *kd_worker(void *arg) {
     kd_job *j = (kd_job *)arg;
     for (int64_t i = j->begin; i < j->end; ++i) {
+        pend_reset();
         if (j->hits)
             kd_one(j->nodes, j->prim_indices, j->prims, j->verts, j->bounds, &j->rays[i], 1, &j->hits[i], NULL,
                    NULL, NULL);
         else
             kd_one(j->nodes, j->prim_indices, j->prims, j->verts, j->bounds, &j->rays[i], 0, NULL, &j->occ[i],
                    j->visited ? &j->visited[i] : NULL, j->tests ? &j->tests[i] : NULL);
+        pend_store(i);
     }
     return NULL;
 }

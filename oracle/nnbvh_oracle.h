@@ -88,6 +88,16 @@ void orc_intersect_any(const orc_node *nodes, int n_nodes, const orc_prim *prims
                        uint8_t *occluded, int32_t *nodes_visited, int32_t *prim_tests,
                        int nthreads);
 
+/* Optional per-ray output of every traversal entry point in this file (plain, _inst, _anim, kd_; closest and
+ * any): how many entries of nodesToVisit[64] (toVisitOffset; for kd: todoPos of todo[64]) were pending at once.
+ * out3 = 3 int32 per ray, written by the calls that follow until it is set back to NULL:
+ *   [0] the maximum pending count; inside a TransformedPrimitive / AnimatedPrimitive it is the outer walk's
+ *       entries pending at that moment plus the child walk's,
+ *   [1] the outer entries pending when an instance was entered and [2] that child walk's own maximum, of the
+ *       instance visit with the largest min([1], [2]) (0, 0 = no instance was entered).
+ * Nothing the walks return depends on it. */
+void orc_set_pending_depth_out(int32_t *out3);
+
 /* Transform::ApplyInverse(const Ray&, Float *tMax) (util/transform.h:416-429) for an affine
  * transform given by the 3x4 inverse matrix: out = o'[3], d'[3], tmax'. */
 void orc_apply_inverse_ray(const float m_inv[12], const float o[3], const float d[3], float tmax,

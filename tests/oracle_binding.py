@@ -355,3 +355,22 @@ def set_vertex_normals(normals):
     global _normals_keepalive
     _normals_keepalive = None if normals is None else np.ascontiguousarray(normals, np.float32)
     lib().orc_set_vertex_normals(None if normals is None else _p(_normals_keepalive))
+
+
+class pending_depth:
+    """Context manager: the traversal calls made inside it (closest / any_hit, their _inst / _anim / kd_ forms)
+    also record, per ray, how many stack entries were pending at once.  `.depth` is int32 [n, 3]: the maximum
+    (outer + child inside an instance), and the outer count at entry / the child walk's own maximum of the
+    instance visit with the largest min of the two (see orc_set_pending_depth_out).  One traversal call per
+    context: a second call overwrites the first n rows."""
+
+    def __init__(self, n_rays):
+        self.depth = np.zeros((n_rays, 3), np.int32)
+
+    def __enter__(self):
+        lib().orc_set_pending_depth_out(_p(self.depth))
+        return self
+
+    def __exit__(self, *exc):
+        lib().orc_set_pending_depth_out(None)
+        return False

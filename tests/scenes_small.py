@@ -1,4 +1,5 @@
 """Small seeded scenes shared by the parity tests (inputs only)."""
+import collections
 import os
 
 import numpy as np
@@ -113,3 +114,297 @@ def edge_case_rays(verts, prims, seed=0, n=2048):
     d[1::2, 2] = 1e-42
     parts.append(make_rays(o2, d))
     return np.concatenate(parts)
+
+
+# ---- skewed chains: scenes whose rays provably keep up to 64 nodes pending -------------------------------------
+# (tests/test_stack_limits.py; the CPU tests there prove the depths with the oracle's pending-depth output)
+Chain = collections.namedtuple("Chain", "verts prims nodes normals uvs prim_alpha leaf_lo leaf_hi")
+TwoLevelChain = collections.namedtuple("TwoLevelChain", "verts prims nodes instances n_top a b outer_lo outer_hi "
+                                                        "child_lo child_hi")
+KdChain = collections.namedtuple("KdChain", "verts prims nodes prim_indices bounds normals uvs prim_alpha splits")
+
+TRI_KINDS = (0, 4, 5, 6, 7)
+PATCH_KINDS = (1, 8, 9, 10, 11, 12, 13, 14, 15)
+ALPHAS = np.array([0.0, 0.25, 0.5, 0.9, 1.0, 1.5], np.float32)
+LEAF_MIXES = {  # kind of leaf k = mix[k % len(mix)]
+    "tri": (0,),
+    "patch": (0, 1, 1),
+    "alpha_tri": (4, 0, 5, 4, 6, 7),
+    "alpha_patch": (8, 0, 9, 1, 10, 11, 4, 12, 13, 14, 15),
+    "host": (0, 0, 3, 0, 1, 0, 0),
+    "host_tri": (0, 0, 3, 0, 0),  # kind 3 leaves that keep their triangle (the same scene as triangles: the oracle's)
+}
+
+
+def chain_nodes(lo, hi, node_base=0, prim_base=0):
+    """LinearBVHNode array of a maximally skewed tree over leaves with the boxes lo[k] / hi[k], one primitive each:
+    node 2k = interior k (first child: leaf k at 2k + 1, second child: interior k + 1 at 2k + 2), the last node =
+    the last leaf; every interior splits along x.  node_base / prim_base: where the tree sits in shared arrays."""
+    from nn_bvh_amd import NODE_DTYPE
+    n_leaves = len(lo)
+    nodes = np.zeros(2 * n_leaves - 1, NODE_DTYPE)
+    for k in range(n_leaves - 1):
+        nodes[2 * k]["pmin"], nodes[2 * k]["pmax"] = lo[k:].min(0), hi[k:].max(0)
+        nodes[2 * k]["offset"], nodes[2 * k]["nprims"], nodes[2 * k]["axis"] = node_base + 2 * k + 2, 0, 0
+        nodes[2 * k + 1]["pmin"], nodes[2 * k + 1]["pmax"] = lo[k], hi[k]
+        nodes[2 * k + 1]["offset"], nodes[2 * k + 1]["nprims"] = prim_base + k, 1
+    nodes[-1]["pmin"], nodes[-1]["pmax"] = lo[-1], hi[-1]
+    nodes[-1]["offset"], nodes[-1]["nprims"] = prim_base + n_leaves - 1, 1
+    return nodes
+
+
+def _tube_leaf(rng, x, n_verts):
+    """Vertices of a triangle (3) or bilinear patch (4) at x inside the tube [-1, 1]^2 around the x axis.  Two kinds
+    of leaf, drawn per leaf: with probability 0.85 a WALL primitive: its vertices are random points of the square's
+    perimeter squeezed into the strip of width 0.5 along one wall (|y| or |z| in [0.5, 1]), which a ray within 0.45 of
+    the axis cannot meet; else (0.15) an AXIS primitive: its vertices are random points of [-0.7, 0.7]^2 around the
+    axis, which some of those rays meet and others miss.  A chain ray therefore misses most leaves' primitives and
+    has a fair chance to hit each of the few axis ones: over 65 leaves most rays hit something, at a depth that
+    varies from ray to ray.  The x coordinates are jittered by up to 0.3 (a patch is twisted: the ray spawned off its
+    surface after a rejected alpha hit can meet it again)."""
+    out = []
+    side, off = rng.integers(0, 4), rng.random() < 0.85
+    for _ in range(n_verts):
+        s, t = rng.integers(0, 4), rng.uniform(-1.0, 1.0)
+        y, z = ((t, -1.0), (t, 1.0), (-1.0, t), (1.0, t))[s]
+        if off:  # squeezed into the half-width strip along wall `side`
+            y, z = ((y, 0.25 * z - 0.75), (y, 0.25 * z + 0.75), (0.25 * y - 0.75, z), (0.25 * y + 0.75, z))[side]
+        else:  # a small shape somewhere around the axis: some of the rays meet it
+            y, z = rng.uniform(-0.7, 0.7, 2)
+        out.append((x + rng.uniform(-0.3, 0.3), y, z))
+    return out
+
+
+def chain_tree(depth, rng, tube=False, leaves="tri", extras=False, x0=0.0):
+    """A maximally skewed tree: every interior node has one leaf child (first) and one interior child (second),
+    `depth` edges deep, built by hand in the LinearBVHNode layout; leaf k sits at x = x0 + 2 k.  A ray with d.x < 0
+    enters the interior child first and keeps one leaf pending per level: `depth` entries at the deepest leaf.
+
+    tube: every leaf's box is the cross-section [-1, 1]^2 around the x axis times the primitive's x extent, and the
+    primitive lies inside it with its vertices on the tube's walls (see _tube_leaf; the boxes are conservative, as a
+    caller's may be), so that a ray that stays within 0.45 of the axis crosses EVERY leaf box by a margin, whatever
+    its tMax, and still misses most primitives.
+    leaves: a key of LEAF_MIXES or a sequence of primitive kinds, cycled over the leaves: 0 triangle, 1 bilinear patch,
+    3 host-only (its bounds are the caller's: the tube's cross-section around its x; in the "host_tri" mix it keeps a
+    triangle's vertices in v, which the device never reads, so the same arrays with kind 0 are the oracle's scene), 4 .. 7 alpha-tested triangles
+    (the alpha in v[3]; 6 / 7 read the normals), 8 .. 15 alpha-tested patches (prim_alpha; normals, uvs).
+    extras: return a Chain (normals / uvs / prim_alpha per vertex / vertex / primitive, the leaf boxes) instead of
+    (verts, prims, nodes)."""
+    from nn_bvh_amd import PRIM_DTYPE, make_prims
+    n_leaves = depth + 1
+    x = x0 + np.arange(n_leaves, dtype=np.float32) * 2.0
+    if not tube and leaves == "tri":  # the form test_gpu_parity's depth tests have always used
+        c = np.stack([x, np.zeros_like(x), np.zeros_like(x)], 1)[:, None, :]
+        verts = (c + rng.uniform(-0.7, 0.7, size=(n_leaves, 3, 3))).reshape(-1, 3).astype(np.float32)
+        prims = make_prims(np.arange(3 * n_leaves, dtype=np.int32).reshape(n_leaves, 3))
+        lo = verts.reshape(n_leaves, 3, 3).min(1)
+        hi = verts.reshape(n_leaves, 3, 3).max(1)
+        nodes = chain_nodes(lo, hi)
+        if extras:
+            return Chain(verts, prims, nodes, None, None, None, lo, hi)
+        return verts, prims, nodes
+    assert tube, "leaf kinds other than triangles come in the tube form"
+    mix = LEAF_MIXES[leaves] if isinstance(leaves, str) else tuple(leaves)
+    verts, lo, hi = [], np.zeros((n_leaves, 3), np.float32), np.zeros((n_leaves, 3), np.float32)
+    prims = np.zeros(n_leaves, PRIM_DTYPE)
+    prims["id"] = np.arange(n_leaves)
+    alpha = np.ones(n_leaves, np.float32)
+    for k in range(n_leaves):
+        kind = mix[k % len(mix)]
+        prims[k]["kind"] = kind
+        if kind == 3 and leaves != "host_tri":
+            lo[k], hi[k] = (x[k] - 0.3, -1, -1), (x[k] + 0.3, 1, 1)
+            continue
+        nv = 3 if kind in TRI_KINDS or kind == 3 else 4
+        v = np.array(_tube_leaf(rng, float(x[k]), nv), np.float32)
+        prims[k]["v"][:nv] = len(verts) + np.arange(nv)
+        verts.extend(v)
+        lo[k], hi[k] = (v[:, 0].min(), -1, -1), (v[:, 0].max(), 1, 1)
+        if kind >= 4:
+            alpha[k] = ALPHAS[rng.integers(0, len(ALPHAS))]
+            if kind <= 7:
+                prims[k]["v"][3] = alpha[k:k + 1].view(np.int32)[0]
+    verts = np.array(verts, np.float32).reshape(-1, 3)
+    nodes = chain_nodes(lo, hi)
+    if not extras:
+        return verts, prims, nodes
+    normals = rng.normal(size=(len(verts), 3)).astype(np.float32)
+    normals /= np.linalg.norm(normals, axis=1, keepdims=True)
+    uvs = rng.random((len(verts), 2)).astype(np.float32)
+    return Chain(verts, prims, nodes, normals, uvs, alpha, lo, hi)
+
+
+def chain_rays(x_far, n, seed, tmax_share=0.25):
+    """n rays down a tube chain from beyond its far end (x_far = the largest x of the scene): origins within 0.3 of
+    the axis, slopes up to 1e-3, so over a chain up to 150 long they stay within 0.45 of the axis.  d.x < 0: the
+    interior child is the near one at every level.  A share has a finite tMax that ends inside the chain."""
+    from nn_bvh_amd import make_rays
+    rng = np.random.default_rng(seed)
+    o = np.stack([np.full(n, x_far + 12.0), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.3, 0.3, n)], 1)
+    d = np.stack([-np.ones(n), rng.uniform(-1e-3, 1e-3, n), rng.uniform(-1e-3, 1e-3, n)], 1)
+    rays = make_rays(o, d)
+    short = rng.random(n) < tmax_share
+    rays["tmax"][short] = rng.uniform(20.0, x_far, short.sum()).astype(np.float32)
+    return rays
+
+
+def line_box_margin(rays, lo, hi, m_inv=None):
+    """float64: the smallest distance by which the LINES of `rays` stay inside the y / z extent of the boxes lo / hi
+    while they cross the boxes' x extent (negative: a line leaves a box sideways), per ray.  m_inv (3x4): the rays are
+    taken into that space first."""
+    o, d = rays["o"].astype(np.float64), rays["d"].astype(np.float64)
+    if m_inv is not None:
+        m = np.asarray(m_inv, np.float64).reshape(3, 4)
+        o, d = o @ m[:, :3].T + m[:, 3], d @ m[:, :3].T
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    margin = np.full(len(rays), np.inf)
+    for xs in (lo[:, 0], hi[:, 0]):
+        t = (xs[None, :] - o[:, :1]) / d[:, :1]
+        for ax in (1, 2):
+            p = o[:, ax:ax + 1] + t * d[:, ax:ax + 1]
+            margin = np.minimum(margin, np.minimum(p - lo[None, :, ax], hi[None, :, ax] - p).min(1))
+    return margin
+
+
+def rot_x(theta, tx):
+    """Rigid transform: rotation by theta about the x axis, then translation by tx along it -> (m, m_inv) 3x4."""
+    c, s = np.cos(theta), np.sin(theta)
+    r = np.array([[1, 0, 0], [0, c, -s], [0, s, c]], np.float64)
+    m = np.concatenate([r, [[tx], [0], [0]]], 1)
+    mi = np.concatenate([r.T, -r.T @ [[tx], [0], [0]]], 1)
+    return m.astype(np.float32).reshape(12), mi.astype(np.float32).reshape(12)
+
+
+def two_level_chain(a, b, seed, instance_levels=None, moving=False):
+    """Outer tube chain of depth a whose leaves at `instance_levels` (default: 3, a // 2 and the deepest, a) hold
+    instance primitives of ONE child: a tube chain of depth b.  Placements rotate about the chain axis and shift along
+    it, so a ray near the axis stays near the child's axis too, with d.x < 0 in both spaces: `a` outer entries are
+    pending when the deepest instance is entered and b more inside it.  The library bounds a + (b + 1) by 64.
+    moving: the instance boxes cover the motion of animated_two_level_chain (every second placement turns on about the
+    axis and slides along it): the x extent of both end placements, and [-1.5, 1.5]^2 across (the child's
+    cross-section [-1, 1]^2 at any angle lies within radius sqrt(2))."""
+    from nn_bvh_amd import PRIM_DTYPE, instancing
+    from nn_bvh_amd._lib import INSTANCE_DTYPE
+    rng = np.random.default_rng(seed)
+    levels = sorted(set(instance_levels if instance_levels is not None else (3, a // 2, a)))
+    child = chain_tree(b, rng, tube=True, leaves="patch", extras=True)
+    outer = chain_tree(a, rng, tube=True, leaves="tri", extras=True)
+    n_top_nodes, n_top_prims = len(outer.nodes), len(outer.prims)
+    verts = np.concatenate([outer.verts, child.verts])
+    cprims = child.prims.copy()
+    for k in range(len(cprims)):
+        nv = 3 if cprims[k]["kind"] in TRI_KINDS else 4
+        cprims[k]["v"][:nv] += len(outer.verts)
+    cprims["id"] += n_top_prims
+    oprims, lo, hi = outer.prims.copy(), outer.leaf_lo.copy(), outer.leaf_hi.copy()
+    instances = np.zeros(len(levels), INSTANCE_DTYPE)
+    croot = np.concatenate([child.nodes[0]["pmin"], child.nodes[0]["pmax"]])
+    for j, k in enumerate(levels):
+        m, mi = rot_x(0.4 + 0.9 * j, 2.0 * k)
+        instances[j]["render_from_prim"], instances[j]["prim_from_render"] = m, mi
+        instances[j]["root"], instances[j]["n_nodes"] = n_top_nodes, len(child.nodes)
+        oprims[k] = np.zeros(1, PRIM_DTYPE)[0]
+        oprims[k]["kind"], oprims[k]["id"], oprims[k]["v"][0] = 2, k, j
+        box = instancing.transform_bounds(m, croot)
+        lo[k], hi[k] = box[:3], box[3:]
+        if moving:
+            end = instancing.transform_bounds(rot_x(*end_placement(j, k))[0], croot)
+            lo[k] = (min(box[0], end[0]) - 0.05, -1.5, -1.5)
+            hi[k] = (max(box[3], end[3]) + 0.05, 1.5, 1.5)
+    nodes = np.concatenate([chain_nodes(lo, hi), chain_nodes(child.leaf_lo, child.leaf_hi, n_top_nodes, n_top_prims)])
+    return TwoLevelChain(verts, np.concatenate([oprims, cprims]), nodes, instances, n_top_nodes, a, b, lo, hi,
+                         child.leaf_lo, child.leaf_hi)
+
+
+def end_placement(j, k):
+    """(angle, shift) of instance j (at outer leaf k) at the end of its motion; its start: (0.4 + 0.9 j, 2 k)."""
+    return 0.4 + 0.9 * j + 0.7, 2.0 * k + 1.5
+
+
+def animated_two_level_chain(a, b, seed):
+    """two_level_chain with AnimatedTransforms: -> (TwoLevelChain, device records, oracle records).  Every second
+    instance, the deepest one included, is actually animated over the time range [0, 1]: it turns by 0.7 rad about the
+    chain axis and slides 1.5 along it, so that at EVERY ray time a ray near the axis stays near the child's axis and
+    the depth argument of two_level_chain holds.  That is why the transforms are written here and not drawn from
+    tests/golden/anim_interpolate.npz as tests/test_animated.py does: those are arbitrary affine maps, which take the
+    ray off the child's axis.  The records are what the reference's AnimatedTransform holds for such a motion: T = the
+    shifts, R = the unit quaternions (sin(angle / 2), 0, 0, cos(angle / 2)), S = identity, and the start / end
+    matrices are Interpolate's own products Translate(T) * Rotate(R) * S, taken from the oracle so that they are
+    bit-equal to what it gives an instant inside the range.  Instance boxes cover the motion (moving=True)."""
+    import oracle_binding as ob
+    from nn_bvh_amd import _lib
+    t = two_level_chain(a, b, seed, moving=True)
+    n = len(t.instances)
+    levels = sorted({3, a // 2, a})
+    oa = np.zeros(n, ob.ANIM_DTYPE)
+    oa["start_time"], oa["end_time"] = 0.0, 1.0
+    oa["S"] = np.eye(4, dtype=np.float32).reshape(16)
+    ends = np.zeros((n, 2, 2))
+    for j, k in enumerate(levels):
+        ends[j] = (0.4 + 0.9 * j, 2.0 * k), end_placement(j, k)
+        oa["actually_animated"][j] = int((n - 1 - j) % 2 == 0)
+    for e, (fm, fi) in enumerate((("start_m", "start_minv"), ("end_m", "end_minv"))):
+        oa["T"][:, e, 0] = ends[:, e, 1]
+        oa["R"][:, e, 0], oa["R"][:, e, 3] = np.sin(ends[:, e, 0] / 2), np.cos(ends[:, e, 0] / 2)
+    for e, (fm, fi) in enumerate((("start_m", "start_minv"), ("end_m", "end_minv"))):
+        still = oa.copy()  # a motion that rests at this end: Interpolate inside the range composes its matrices
+        still["T"][:, 1 - e], still["R"][:, 1 - e] = still["T"][:, e], still["R"][:, e]
+        still["actually_animated"] = 1
+        mm = ob.anim_interpolate(still, np.full(n, 0.5, np.float32))
+        oa[fm], oa[fi] = mm[:, :16], mm[:, 16:]
+    anims = np.zeros(n, _lib.ANIMATED_DTYPE)
+    for f_o, f_p in (("start_m", "start_from"), ("start_minv", "start_inv"), ("end_m", "end_from"), ("end_minv", "end_inv")):
+        anims[f_p] = oa[f_o]
+    for f in ("T", "R", "S", "start_time", "end_time", "actually_animated"):
+        anims[f] = oa[f]
+    inst = t.instances.copy()  # the static placement = the start transform, as the oracle's walk and the device use it
+    inst["render_from_prim"], inst["prim_from_render"] = oa["start_m"][:, :12], oa["start_minv"][:, :12]
+    return t._replace(instances=inst), anims, oa
+
+
+def kd_chain(depth, seed, form="lean"):
+    """A maximally skewed kd-tree in KdTreeNode layout (8 B: interior {split, axis | above << 2}, leaf {index,
+    3 | n << 2}; the below child follows its parent): interior k (node k) splits x at 2 (depth - k); its below child is
+    interior k + 1, its above child the leaf of the slab [2 (depth - k), 2 (depth - k + 1)].  A ray along +x from
+    x < 0 has o < split at every level and crosses every split plane inside the tree's bounds: one entry pushed per
+    level, `depth` pending at the deepest leaf.  Leaves hold one tube primitive each (every fifth also its
+    neighbour's, through primitiveIndices).  form: "lean" triangles, "patch" with bilinear patches, "attr" with the
+    attribute-reading alpha kinds (6 .. 15)."""
+    from nn_bvh_amd._lib import KD_NODE_DTYPE
+    rng = np.random.default_rng(seed)
+    mix = {"lean": "tri", "patch": "patch", "attr": "alpha_patch"}[form]
+    # leaf slab j (j = 0 .. depth) covers x in [2 j, 2 j + 2]: its primitive at x = 2 j + 1
+    ch = chain_tree(depth, rng, tube=True, leaves=mix, extras=True, x0=1.0)
+    n_leaves = depth + 1
+    nodes = np.zeros(2 * depth + 1, KD_NODE_DTYPE)
+    splits = np.zeros(depth, np.float32)
+    idx = []
+
+    def leaf(node, j):
+        if j % 5 == 2:
+            nodes[node]["split_or_index"], nodes[node]["flags"] = len(idx), 3 | (2 << 2)
+            idx.extend([j, (j + 1) % n_leaves])
+        else:
+            nodes[node]["split_or_index"], nodes[node]["flags"] = j, 3 | (1 << 2)
+
+    for k in range(depth):
+        splits[k] = 2.0 * (depth - k)
+        above = 2 * depth - k  # node index of the above leaf: the leaves follow the interiors, deepest first
+        nodes[k]["split_or_index"] = splits[k:k + 1].view(np.uint32)[0]
+        nodes[k]["flags"] = 0 | (above << 2)
+        leaf(above, depth - k)
+    leaf(depth, 0)
+    bounds = np.array([0.5, -1, -1, 2 * depth + 1.5, 1, 1], np.float32)
+    return KdChain(ch.verts, ch.prims, nodes, np.array(idx, np.int32), bounds, ch.normals, ch.uvs, ch.prim_alpha, splits)
+
+
+def kd_chain_rays(n, seed, tmax_share=0.25):
+    """Rays up a kd chain from x = -5 (see chain_rays: within 0.45 of the axis throughout)."""
+    from nn_bvh_amd import make_rays
+    rng = np.random.default_rng(seed)
+    o = np.stack([np.full(n, -5.0), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.3, 0.3, n)], 1)
+    d = np.stack([np.ones(n), rng.uniform(-1e-3, 1e-3, n), rng.uniform(-1e-3, 1e-3, n)], 1)
+    rays = make_rays(o, d)
+    short = rng.random(n) < tmax_share
+    rays["tmax"][short] = rng.uniform(20.0, 120.0, short.sum()).astype(np.float32)
+    return rays

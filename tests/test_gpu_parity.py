@@ -375,27 +375,7 @@ def test_concurrent_host_threads_and_streams():
     agg.close()
 
 
-def chain_tree(depth, rng):
-    """A maximally skewed tree: every interior node has one leaf child (first) and one interior
-    child (second), `depth` edges deep — built by hand in the LinearBVHNode layout."""
-    from nn_bvh_amd import NODE_DTYPE, make_prims
-    n_leaves = depth + 1
-    x = np.arange(n_leaves, dtype=np.float32) * 2.0
-    c = np.stack([x, np.zeros_like(x), np.zeros_like(x)], 1)[:, None, :]
-    verts = (c + rng.uniform(-0.7, 0.7, size=(n_leaves, 3, 3))).reshape(-1, 3).astype(np.float32)
-    prims = make_prims(np.arange(3 * n_leaves, dtype=np.int32).reshape(n_leaves, 3))
-    nodes = np.zeros(2 * n_leaves - 1, NODE_DTYPE)
-    lo = verts.reshape(n_leaves, 3, 3).min(1)
-    hi = verts.reshape(n_leaves, 3, 3).max(1)
-    # node 2k = interior k (children: leaf 2k+1, interior/leaf 2k+2); last node = last leaf
-    for k in range(n_leaves - 1):
-        nodes[2 * k]["pmin"], nodes[2 * k]["pmax"] = lo[k:].min(0), hi[k:].max(0)
-        nodes[2 * k]["offset"], nodes[2 * k]["nprims"], nodes[2 * k]["axis"] = 2 * k + 2, 0, 0
-        nodes[2 * k + 1]["pmin"], nodes[2 * k + 1]["pmax"] = lo[k], hi[k]
-        nodes[2 * k + 1]["offset"], nodes[2 * k + 1]["nprims"] = k, 1
-    nodes[-1]["pmin"], nodes[-1]["pmax"] = lo[-1], hi[-1]
-    nodes[-1]["offset"], nodes[-1]["nprims"] = n_leaves - 1, 1
-    return verts, prims, nodes
+from scenes_small import chain_tree  # noqa: E402  (the builder lives with the other scenes now)
 
 
 def test_maximum_depth_and_maximum_leaf_size():

@@ -231,7 +231,7 @@ def _check_batches(agg, tree, prims, verts, spec, oracle=True):
 def _soup_rays(verts, prims, seeds, n=40000):
     return np.concatenate([scene.random_rays(n, verts.min(0) - 2, verts.max(0) + 2, seeds[0]),
                            scene.random_rays(n // 4, verts.min(0), verts.max(0), seeds[1], tmax=0.5),
-                           ss.edge_case_rays(verts, prims, seeds[2])])  # NaN / inf components among them
+                           ss.edge_case_rays(verts, prims, seeds[2])])  # zero, -0 and denormal components among them (no NaN / inf)
 
 
 def _four(rays, shadow_rays):

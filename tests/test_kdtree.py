@@ -351,3 +351,83 @@ def test_device_kd_traversal_on_scene_blobs_sampled_per_ray_class(name):
     assert np.array_equal(agg.IntersectP(shadow), occ)  # counting == non-counting, whole batch
     assert (hits["prim"] >= 0).mean() > (0.9 if name == "bathroom" else 0.7) and hits["nodes_visited"].mean() > 30
     agg.close()
+
+
+# ---- rays on split planes with zero / infinite / NaN components (tSplit = 0 * inf, aggregates.cpp:1000-1023) --------
+def snapped_grid(n=10, seed=5):
+    """grid_mesh with every coordinate a multiple of 1/4: the builder's split planes (primitive bounds' edges) then
+    coincide with vertex coordinates, and so with the origins split_plane_rays takes from the vertices."""
+    verts, prims = ss.grid_mesh(n, seed)
+    return (np.round(verts * 4) / 4).astype(np.float32), prims
+
+
+def split_plane_rays(verts, seed, n=6000):
+    """Origins on vertices (about 30 % moved off the plane, per axis), direction components from {0, -0, +-1, 0.5,
+    +-inf, +-1e-30}, tMax from {inf, 1, 3, 0, 1e-30}; 1 % of the rays get NaN / Inf specials anywhere."""
+    from nn_bvh_amd import make_rays
+    rng = np.random.default_rng(seed)
+    o = verts[rng.integers(0, len(verts), n)].copy()
+    off = rng.random((n, 3)) < 0.3
+    o = np.where(off, o + rng.choice(np.array([-1.5, -0.25, 0.25, 2.0], np.float32), (n, 3)), o).astype(np.float32)
+    d = rng.choice(np.array([0.0, -0.0, 1.0, -1.0, 0.5, np.inf, -np.inf, 1e-30, -1e-30], np.float32), (n, 3))
+    rays = make_rays(o, d.astype(np.float32))
+    rays["tmax"] = rng.choice(np.array([np.inf, 1.0, 3.0, 0.0, 1e-30], np.float32), n)
+    special = np.array([0.0, -0.0, 1.0, -1.0, 0.5, np.inf, -np.inf, 1e-30, -1e-30, np.nan], np.float32)
+    bad = rng.random(n) < 0.01
+    for f in ("o", "d"):
+        v = rays[f].copy()
+        m = bad[:, None] & (rng.random(v.shape) < 0.4)
+        v[m] = rng.choice(special, int(m.sum()))
+        rays[f] = v
+    return rays
+
+
+def _equal_but_nan_t(got, exp):
+    """records equal bit for bit, except that a NaN t equals a NaN t (the default NaN's sign differs between hosts)"""
+    for f in ("prim", "nodes_visited", "prim_tests", "instance"):
+        assert np.array_equal(got[f], exp[f]), f
+    for f in ("t", "b0", "b1", "b2"):
+        differ = (got[f].view(np.uint32) != exp[f].view(np.uint32)) & ~(np.isnan(got[f]) & np.isnan(exp[f]))
+        assert not differ.any(), f"{f} differs on rays {np.nonzero(differ)[0][:5]}"
+
+
+@pytest.mark.parametrize("max_prims", [1, 4])
+def test_oracle_kd_rays_on_split_planes_terminate_with_hits_and_misses(max_prims):
+    """The ray set really sits on the tree's split planes, holds NaN / Inf rays, and the restated walk ends on every
+    one of them with a hit share strictly between 2 % and 98 %; threads do not change a record."""
+    verts, prims = snapped_grid()
+    tree = build_kd_tree(prims, verts, max_prims=max_prims)
+    rays = split_plane_rays(verts, 3)
+    interior = (tree.nodes["flags"] & 3) != 3
+    splits = [np.unique(tree.nodes["split_or_index"][interior & ((tree.nodes["flags"] & 3) == ax)].view(np.float32))
+              for ax in range(3)]
+    on_plane = np.stack([np.isin(rays["o"][:, ax], splits[ax]) for ax in range(3)], 1)
+    assert on_plane.any(1).mean() > 0.5, "most origins lie exactly on a split plane of the tree"
+    assert np.isnan(rays["d"]).any() and np.isinf(rays["d"]).any() and (rays["d"] == 0).any()
+    exp = ob.kd_closest(tree.nodes, tree.prim_indices, prims, verts, tree.bounds, rays, 1)
+    assert 0.02 < (exp["prim"] >= 0).mean() < 0.98
+    _equal_but_nan_t(ob.kd_closest(tree.nodes, tree.prim_indices, prims, verts, tree.bounds, rays, 4), exp)
+    occ, vis, tst = ob.kd_any_hit(tree.nodes, tree.prim_indices, prims, verts, tree.bounds, rays, 1)
+    occ4, vis4, tst4 = ob.kd_any_hit(tree.nodes, tree.prim_indices, prims, verts, tree.bounds, rays, 4)
+    assert np.array_equal(occ, occ4) and np.array_equal(vis, vis4) and np.array_equal(tst, tst4)
+    assert 0.02 < (occ == 1).mean() < 0.98
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_prims", [1, 4])
+def test_device_kd_rays_on_split_planes_with_zero_infinite_and_nan_components(max_prims):
+    """The kd counterpart of test_rays_on_box_planes_with_zero_and_infinite_components: origins exactly ON split planes
+    with zero, negative-zero, infinite and NaN direction components make tSplit = 0 * inf = NaN in every combination;
+    records, both counters and the occlusion flags must still be the oracle's."""
+    verts, prims = snapped_grid()
+    tree = build_kd_tree(prims, verts, max_prims=max_prims)
+    rays = split_plane_rays(verts, 3)
+    exp = ob.kd_closest(tree.nodes, tree.prim_indices, prims, verts, tree.bounds, rays, 4)
+    assert 0.02 < (exp["prim"] >= 0).mean() < 0.98
+    eo, ev, et = ob.kd_any_hit(tree.nodes, tree.prim_indices, prims, verts, tree.bounds, rays, 4)
+    agg = KdTreeAggregate.from_tree(tree.nodes, tree.prim_indices, prims, verts, tree.bounds)
+    _equal_but_nan_t(agg.Intersect(rays), exp)
+    occ, vis, tst = agg.IntersectP(rays, counts=True)
+    assert np.array_equal(occ, eo) and np.array_equal(vis, ev) and np.array_equal(tst, et)
+    assert np.array_equal(agg.IntersectP(rays), eo)
+    agg.close()
