@@ -556,7 +556,8 @@ nnbvh_shading_mesh *nnbvh_shading_mesh_create(const float *verts, int n_verts,
  * Hits inside instance k are then finished on the device as TransformedPrimitive::Intersect does
  * (cpu/primitive.cpp:112-125): interaction in the instance's space (wo = -ApplyInverse(ray.d)), then
  * Transform::operator()(const SurfaceInteraction &) with renderFromPrimitive (util/transform.cpp:
- * 229-261).  Without it such hits get NNBVH_INTERACTION_HOST. */
+ * 229-261).  Without it such hits get NNBVH_INTERACTION_HOST.  Each call replaces the whole table of an
+ * earlier call, animation tables included (all instances static); n_instances = 0 removes it. */
 int nnbvh_shading_mesh_set_instances(nnbvh_shading_mesh *m, const nnbvh_instance *instances, int n_instances);
 /* ... with AnimatedPrimitives among the instances (the tables given to nnbvh_scene_create_instanced_animated):
  * a hit inside an instance whose `animated[k].actually_animated` is set is finished as

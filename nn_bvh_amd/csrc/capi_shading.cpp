@@ -84,6 +84,12 @@ int nnbvh_shading_mesh_set_instances(nnbvh_shading_mesh *m, const nnbvh_instance
     if (m->d.instances) (void)hipFree(m->d.instances);
     m->d.instances = nullptr;
     m->d.nInstances = 0;
+    // the animation tables describe the table they came with: a new instance table starts without them
+    // (surface_interaction indexes m.anim by the instance of the NEW table)
+    for (float **p : {&m->d.anim, &m->d.animFwd}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
     if (n_instances == 0) return NNBVH_OK;
     if (!upload(&m->d.instances, instances, (size_t)n_instances, "shading mesh: instances")) return NNBVH_ERR_DEVICE;
     m->d.nInstances = n_instances;

@@ -6,7 +6,8 @@ flags: 1 = mesh has uv, 2 = has normals, 4 = has tangents, 8 = reverseOrientatio
 import numpy as np
 
 
-def cases(n, seed):
+def cases(n, seed, return_kind=False):
+    """return_kind: also return the kind drawn per record (the comments below name the kinds)."""
     rng = np.random.default_rng(seed)
     rec = np.zeros((n, 45), np.float32)
     scale = (10.0 ** rng.uniform(-3, 3, size=(n, 1))).astype(np.float32)
@@ -63,7 +64,7 @@ def cases(n, seed):
     rec[k, 0:9] = (rng.uniform(-1, 1, size=(int(k.sum()), 9)) * 1e-4).astype(np.float32)
     rec[k, 20:26] = (rng.uniform(-1, 1, size=(int(k.sum()), 6)) * 1e8).astype(np.float32)
     rec[k, 19] = (rec[k, 19].astype(np.int32) | 1).astype(np.float32)
-    return rec
+    return (rec, kind) if return_kind else rec
 
 
 def patch_cases(n, seed):

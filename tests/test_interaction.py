@@ -131,37 +131,46 @@ def test_oracle_interaction_transform_equals_reference_live():
     assert np.array_equal(ob.transform_interaction_batch(rec).view(np.uint32), ref)
 
 
-def check_instance_interactions(got, rows, kind, rays, hits, verts, normals, tri_vertices, patch_vertices, m, mi):
-    """Device records `got[rows]` of hits inside instances against the oracle composed of pinned pieces: the
-    shape's InteractionFromIntersection in the instance's space (wo = -ApplyInverse(ray.d)), then
-    Transform::operator()(SurfaceInteraction) with the per-row matrices m / mi ([n, 3, 4])."""
-    d = rays["d"][rows]
-    d_in = np.stack([(mi[:, i, 0] * d[:, 0] + mi[:, i, 1] * d[:, 1]) + mi[:, i, 2] * d[:, 2] for i in range(3)], 1)
+# fields of Transform::operator()(SurfaceInteraction)'s 40-float oracle / reference record
+XF_FIELDS = {"pi_lo": slice(0, 3), "pi_hi": slice(3, 6), "n": slice(6, 9), "wo": slice(9, 12), "dpdu": slice(12, 15),
+             "dpdv": slice(15, 18), "dndu": slice(18, 21), "dndv": slice(21, 24), "ns": slice(24, 27),
+             "dpdus": slice(27, 30), "dpdvs": slice(30, 33), "dndus": slice(33, 36), "dndvs": slice(36, 39)}
+
+
+def instance_oracle(kind, rec, m, mi, d, time, face_index=None):
+    """The oracle for "a hit inside an instance", composed of pinned pieces as cpu/primitive.cpp:112-125 and
+    :143-153 compose them.  rec: golden-style input records of the struck shapes in the INSTANCE's space (kind 0:
+    the 45-column triangle layout, kind 1: the 40-column patch layout of golden/interaction_cases.py), their own
+    flags column honoured; m / mi: the per-row renderFromPrimitive and its inverse ([n, 3, 4]); d, time: the
+    render-space ray directions and times (they replace the records' wo and time columns).
+      1. wo = -ApplyInverse(ray.d)                       (TransformedPrimitive::Intersect's ray)
+      2. the shape's InteractionFromIntersection          (ob.triangle_ / patch_interaction_batch)
+      3. Transform::operator()(SurfaceInteraction)        (ob.transform_interaction_batch)
+    m = None stops after step 2 with wo = -ray.d: a hit at top level.  Returns {field: array} for every field of
+    the 192-byte record but prim / status; uv, time and face_index are the shape's own (the transform must not
+    touch them), face_index the given array or the oracle's 7 + record number."""
+    rec = np.array(rec, np.float32)
+    n = len(rec)
+    d = np.ascontiguousarray(d, np.float32)
+    d_in = d if m is None else np.stack(
+        [(mi[:, i, 0] * d[:, 0] + mi[:, i, 1] * d[:, 1]) + mi[:, i, 2] * d[:, 2] for i in range(3)], 1)
     if kind == 0:
-        rec = np.zeros((len(rows), 45), np.float32)
-        tv = tri_vertices[hits["prim"][rows]]
-        rec[:, 0:9] = verts[tv].reshape(-1, 9)
-        rec[:, 9], rec[:, 10], rec[:, 11] = hits["b0"][rows], hits["b1"][rows], hits["b2"][rows]
-        rec[:, 12:15] = -d_in
-        rec[:, 18] = rays["time"][rows]
-        rec[:, 19] = 2
-        rec[:, 26:35] = normals[tv].reshape(-1, 9)
+        rec[:, 12:15], rec[:, 18] = -d_in, time
         local = ob.triangle_interaction_batch(rec)
-        gdn = np.zeros((len(rows), 6), np.float32)
+        gdn = np.zeros((n, 6), np.float32)               # Triangle passes Normal3f() twice
     else:
-        rec = np.zeros((len(rows), 40), np.float32)
-        pv = patch_vertices[hits["prim"][rows]]
-        rec[:, 0:12] = verts[pv].reshape(-1, 12)
-        rec[:, 12], rec[:, 13] = hits["b0"][rows], hits["b1"][rows]
-        rec[:, 14:17] = -d_in
-        rec[:, 17] = rays["time"][rows]
-        rec[:, 18] = 2
-        rec[:, 27:39] = normals[pv].reshape(-1, 12)
+        rec[:, 14:17], rec[:, 17] = -d_in, time
         local = ob.patch_interaction_batch(rec)
         gdn = local[:, 44:50]
-    xf = np.zeros((len(rows), 72), np.float32)
+    out = {"uv": local[:, 6:8], "time": local[:, 35],
+           "face_index": local[:, 36].astype(np.int32) if face_index is None else np.asarray(face_index, np.int32)}
+    if m is None:
+        out.update({name: local[:, sl] for name, sl in FIELDS.items() if name != "uv"})
+        out["dndu"], out["dndv"] = gdn[:, 0:3], gdn[:, 3:6]
+        return out
+    xf = np.zeros((n, 72), np.float32)
     for half, mat in ((0, m), (16, mi)):
-        m44 = np.zeros((len(rows), 4, 4), np.float32)
+        m44 = np.zeros((n, 4, 4), np.float32)
         m44[:, :3, :] = mat
         m44[:, 3, 3] = 1
         xf[:, half:half + 16] = m44.reshape(-1, 16)
@@ -171,17 +180,82 @@ def check_instance_interactions(got, rows, kind, rays, hits, verts, normals, tri
     xf[:, 50:56] = gdn                                   # geometric dndu dndv
     xf[:, 56:71] = local[:, 20:35]                       # shading n dpdu dpdv dndu dndv
     exp = ob.transform_interaction_batch(xf)
-    g = got[rows]
-    for name, sl in (("pi_lo", slice(0, 3)), ("pi_hi", slice(3, 6)), ("n", slice(6, 9)), ("wo", slice(9, 12)),
-                     ("dpdu", slice(12, 15)), ("dpdv", slice(15, 18)), ("dndu", slice(18, 21)),
-                     ("dndv", slice(21, 24)), ("ns", slice(24, 27)), ("dpdus", slice(27, 30)),
-                     ("dpdvs", slice(30, 33)), ("dndus", slice(33, 36)), ("dndvs", slice(36, 39))):
-        a = np.ascontiguousarray(g[name]).view(np.uint32)
-        b = np.ascontiguousarray(exp[:, sl]).view(np.uint32)
+    out.update({name: exp[:, sl] for name, sl in XF_FIELDS.items()})
+    return out
+
+
+def assert_interaction_fields(got, exp, what, flags=None, xf_kind=None):
+    """Device records `got` against instance_oracle's fields, every word as uint32; the message names the field
+    and, of the first differing record, the flag value and the kind of transform."""
+    for name, e in exp.items():
+        a = np.ascontiguousarray(got[name]).view(np.uint32).reshape(len(got), -1)
+        b = np.ascontiguousarray(e).view(np.uint32).reshape(len(got), -1)
         bad = np.nonzero((a != b).any(1))[0]
-        assert len(bad) == 0, f"kind {kind}: {name} differs on {len(bad)} of {len(rows)} records"
-    # the (u, v) of the hit are not touched by the transform
-    assert np.array_equal(g["uv"].view(np.uint32), np.ascontiguousarray(local[:, 6:8]).view(np.uint32))
+        if len(bad):
+            k = bad[0]
+            where = "" if flags is None else f", flags {int(np.asarray(flags)[k])}"
+            where += "" if xf_kind is None else f", transform {np.asarray(xf_kind)[k]}"
+            raise AssertionError(f"{what}: {name} differs on {len(bad)} of {len(got)} records, first {bad[:5]}"
+                                 f"{where}: device {np.ascontiguousarray(got[name])[k]} oracle {e[k]}")
+
+
+def records_from_hits(kind, hits, verts, prim_vertices, flags, normals=None, uvs=None, tangents=None):
+    """Golden-style input records (45 columns for kind 0, 40 for kind 1) of the primitives `hits` struck in a
+    mesh with shared vertex arrays; flags: the golden flag value per hit (1 uv, 2 n, 4 s, 8 reverseOrientation)."""
+    n, nv = len(hits), 3 if kind == 0 else 4
+    pv = prim_vertices[hits["prim"]]
+    flags = np.broadcast_to(np.asarray(flags, np.int32), (n,))
+    rec = np.zeros((n, 45 if kind == 0 else 40), np.float32)
+    rec[:, 0:3 * nv] = verts[pv].reshape(n, -1)
+    if kind == 0:
+        rec[:, 9], rec[:, 10], rec[:, 11] = hits["b0"], hits["b1"], hits["b2"]
+        c_flags, c_uv, c_n = 19, 20, 26
+        if tangents is not None:
+            rec[:, 36:45] = tangents[pv].reshape(n, -1)
+    else:
+        rec[:, 12], rec[:, 13] = hits["b0"], hits["b1"]
+        c_flags, c_uv, c_n = 18, 19, 27
+    rec[:, c_flags] = flags
+    if uvs is not None:
+        rec[:, c_uv:c_uv + 2 * nv] = uvs[pv].reshape(n, -1)
+    if normals is not None:  # the mesh stores them flipped under reverseOrientation (util/mesh.cpp:52-58)
+        rec[:, c_n:c_n + 3 * nv] = normals[pv].reshape(n, -1) * np.where(flags & 8, -1, 1).astype(np.float32)[:, None]
+    return rec
+
+
+def check_hits_against_oracle(got, rows, rays, hits, verts, tri_vertices, patch_vertices, prim_flags, m, mi,
+                              normals=None, uvs=None, what="hits"):
+    """Device records got[rows] (hits at top level and inside instances, on triangles and patches of a mesh
+    without a faceIndices array) against instance_oracle; prim_flags: golden flag value per primitive id;
+    m / mi: [len(rows), 3, 4], read for the rows inside instances only.  Returns the rows per (kind, inside)."""
+    counts = {}
+    prim = hits["prim"][rows]
+    is_patch = tri_vertices[prim, 0] < 0
+    inside = hits["instance"][rows] > 0
+    for kind in (0, 1):
+        for ins in (False, True):
+            sel = np.nonzero((is_patch == bool(kind)) & (inside == ins))[0]
+            counts[kind, ins] = len(sel)
+            if len(sel) == 0:
+                continue
+            r = rows[sel]
+            flags = np.asarray(prim_flags, np.int32)[prim[sel]]
+            rec = records_from_hits(kind, hits[r], verts, tri_vertices if kind == 0 else patch_vertices, flags,
+                                    normals, uvs)
+            exp = instance_oracle(kind, rec, m[sel] if ins else None, mi[sel] if ins else None, rays["d"][r],
+                                  rays["time"][r], face_index=np.zeros(len(r), np.int32))
+            assert (got["status"][r] == (1, 3)[kind]).all(), what
+            assert_interaction_fields(got[r], exp, f"{what}: kind {kind}, {'inside instances' if ins else 'top level'}",
+                                      flags=flags)
+    return counts
+
+
+def check_instance_interactions(got, rows, kind, rays, hits, verts, normals, tri_vertices, patch_vertices, m, mi):
+    """Device records `got[rows]` of hits inside instances on a normals-only mesh against instance_oracle."""
+    rec = records_from_hits(kind, hits[rows], verts, tri_vertices if kind == 0 else patch_vertices, 2, normals)
+    exp = instance_oracle(kind, rec, m, mi, rays["d"][rows], rays["time"][rows],
+                          face_index=np.zeros(len(rows), np.int32))
+    assert_interaction_fields(got[rows], exp, f"kind {kind}", flags=np.full(len(rows), 2))
 
 
 @pytest.mark.gpu

@@ -17,6 +17,7 @@ import pytest
 import oracle_binding as ob
 import scenes_small as ss
 from nn_bvh_amd import HIT_DTYPE, _lib, build_tree, scene
+from test_interaction import check_hits_against_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QUEUES = _lib.CLOSEST_QUEUES
@@ -304,11 +305,27 @@ def test_gpu_items_full_path_patches_uvs_instances():
     intr = reference_records(mesh, hits_t, rq, n, dev)
     exp = dict(zip(QUEUES, ob.wavefront_enqueue_closest(hits, has_medium, prim_class)))
     inside = patches = 0
+    held = []
     for k in _lib.ITEM_QUEUES:
         rows = check_slices(k, queues[k], items[k], intr, hits, np.ascontiguousarray(rays["d"]), exp[k])
         inside += (hits["instance"][rows] > 0).sum()
         patches += (intr["status"][rows] == 3).sum()
+        held.append(rows[hits["prim"][rows] >= 0])
     assert inside > 500 and patches > 20
+    # ... and the post-pass records the slices equal are themselves the composed oracle's, on the same hits
+    held = np.unique(np.concatenate(held))
+    inst = instances[np.maximum(hits["instance"][held] - 1, 0)]
+    golden_flags = 2 + (np.arange(len(prims)) % 2 == 0)  # normals everywhere, uv on the even ids
+    counts = check_hits_against_oracle(intr, held, rays, hits, verts, tri_vertices, patch_vertices, golden_flags,
+                                       inst["render_from_prim"].reshape(-1, 3, 4),
+                                       inst["prim_from_render"].reshape(-1, 3, 4), normals=normals, uvs=uvs,
+                                       what="records of the item queues")
+    assert counts[0, True] + counts[1, True] == (hits["instance"][held] > 0).sum() > 500
+    assert counts[1, False] + counts[1, True] == (intr["status"][held] == 3).sum() > 20
+    for kind in (0, 1):  # triangles and patches inside instances, each with and without uv
+        sel = held[(hits["instance"][held] > 0) & (intr["status"][held] == (1, 3)[kind])]
+        for uv in (0, 1):
+            assert ((golden_flags[hits["prim"][sel]] & 1) == uv).any(), (kind, uv)
     agg.close()
     mesh.close()
 
@@ -343,6 +360,20 @@ def test_gpu_items_animated_instances():
     rows = check_slices("basic_eval_material", queues["basic_eval_material"], items["basic_eval_material"], intr,
                         hits, np.ascontiguousarray(rays["d"]), np.nonzero(hits["prim"] >= 0)[0])
     assert (hits["instance"][rows] > 0).sum() > 1000
+    # ... and the post-pass records the slices equal are themselves the composed oracle's (Interpolate with the
+    # device's sine, the path's documented exception)
+    k = np.maximum(hits["instance"][rows] - 1, 0)
+    try:
+        ob.set_sin_mode(1)
+        mm = ob.anim_interpolate(oa[k], rays["time"][rows])
+    finally:
+        ob.set_sin_mode(0)
+    counts = check_hits_against_oracle(intr, rows, rays, hits, verts, tri_vertices, None,
+                                       np.zeros(len(tri_vertices), np.int32), mm[:, :16].reshape(-1, 4, 4)[:, :3, :],
+                                       mm[:, 16:].reshape(-1, 4, 4)[:, :3, :], what="records of the item queue")
+    assert counts[0, True] == (hits["instance"][rows] > 0).sum()
+    moving = (anims["actually_animated"][k] != 0) & (rays["time"][rows] > 0) & (rays["time"][rows] < 1)
+    assert moving.sum() > 500
     agg.close()
     mesh.close()
 
