@@ -408,3 +408,156 @@ def kd_chain_rays(n, seed, tmax_share=0.25):
     short = rng.random(n) < tmax_share
     rays["tmax"][short] = rng.uniform(20.0, 120.0, short.sum()).astype(np.float32)
     return rays
+
+
+# ---- kd-tree builder scenes: one per decision path of buildTree (tests/test_kd_build_gpu.py) -------------------
+# Every generator returns (verts, prims) or, for host-only primitives, (verts, prims, prim_bounds).  The CPU tests
+# there prove with a census of the host-built tree that each scene reaches the path it is named for.
+def box_tris(lo, hi):
+    """One triangle per box [lo, hi] whose Bounds() is exactly that box: (lo.x lo.y lo.z), (hi.x hi.y lo.z),
+    (lo.x hi.y hi.z).  The coordinates are copied, never computed: signed zeros survive."""
+    lo, hi = np.asarray(lo, np.float32).reshape(-1, 3), np.asarray(hi, np.float32).reshape(-1, 3)
+    v = np.stack([lo, np.stack([hi[:, 0], hi[:, 1], lo[:, 2]], 1), np.stack([lo[:, 0], hi[:, 1], hi[:, 2]], 1)], 1)
+    return v.reshape(-1, 3).copy(), make_prims(np.arange(3 * len(lo), dtype=np.int32).reshape(-1, 3))
+
+
+def merge(*parts):
+    """Concatenate (verts, prims) scenes of triangles / patches: vertex indices and ids shifted."""
+    verts, prims, nv, n = [], [], 0, 0
+    for v, p in parts:
+        p = p.copy()
+        p["v"] = np.where(np.arange(4)[None, :] < np.where(p["kind"] == 1, 4, 3)[:, None], p["v"] + nv, p["v"])
+        p["id"] = n + np.arange(len(p))
+        verts.append(np.asarray(v, np.float32))
+        prims.append(p)
+        nv, n = nv + len(v), n + len(p)
+    return np.concatenate(verts), np.concatenate(prims)
+
+
+def host_boxes(lo, hi):
+    """Host-only primitives (kind 3) with the caller's bounds: (verts, prims, prim_bounds)."""
+    from nn_bvh_amd import PRIM_DTYPE
+    pb = np.concatenate([np.asarray(lo, np.float32).reshape(-1, 3), np.asarray(hi, np.float32).reshape(-1, 3)], 1)
+    prims = np.zeros(len(pb), PRIM_DTYPE)
+    prims["kind"], prims["id"] = 3, np.arange(len(pb))
+    return np.zeros((1, 3), np.float32), prims, np.ascontiguousarray(pb)
+
+
+def kd_sticks(seed=0, n_bundles=9, n_soup=500):
+    """Retries on the other axes.  A bundle = 6 .. 14 disjoint slabs that all span the bundle's whole extent on its
+    longest axis a: no edge lies strictly inside a node that holds only the bundle, so attempt 0 fails.  Family 1
+    differs on both other axes (attempt 1, axis a + 1, splits it); family 2 ("plates") also spans axis a + 1 and is
+    stacked along a + 2 (attempt 2).  Bundles sit on a ring far outside an ordinary soup and far from each other, so
+    that empty-space cuts isolate them at various depths while soup nodes of the same levels split on attempt 0."""
+    rng = np.random.default_rng(seed)
+    los, his = [], []
+    for b in range(2 * n_bundles):
+        a = b % 3
+        u, w = (a + 1) % 3, (a + 2) % 3
+        ang = 2 * np.pi * b / (2 * n_bundles)
+        c = np.array([40 * np.cos(ang), 40 * np.sin(ang), 12.0 * (b % 5) - 24], np.float32)
+        m = int(rng.integers(6, 15))
+        lo, hi = np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32)
+        lo[:, a], hi[:, a] = c[a] - 4, c[a] + 4                       # every slab: the whole long extent
+        if b < n_bundles:                                             # family 1: a grid of rods across u and w
+            ku, kw = np.arange(m) % 3, np.arange(m) // 3
+            lo[:, u], hi[:, u] = c[u] + 0.5 * ku, c[u] + 0.5 * ku + 0.25
+            lo[:, w], hi[:, w] = c[w] + 0.5 * kw, c[w] + 0.5 * kw + 0.25
+        else:                                                         # family 2: plates spanning a and u, stacked on w
+            lo[:, u], hi[:, u] = c[u] - 1.5, c[u] + 1.5
+            lo[:, w], hi[:, w] = c[w] + 0.25 * np.arange(m), c[w] + 0.25 * np.arange(m) + 0.125
+        los.append(lo)
+        his.append(hi)
+    return merge(box_tris(np.concatenate(los), np.concatenate(his)), random_soup(n_soup, 0, seed + 1, extent=8.0))
+
+
+def kd_signed_zeros(seed=0, n=600, n_soup=600):
+    """Many bound edges at exactly 0 on every axis, -0 and +0 mixed per primitive and axis in list order, inside a
+    soup that straddles the origin.  Per axis k a primitive lies on the negative side (its box ENDS at +-0) or on the
+    positive side (its box STARTS at +-0, or a little inside: a clean cut at the run of End edges), so the plane 0 is
+    a cheap split and the chosen edge's own sign goes into the node."""
+    rng = np.random.default_rng(seed)
+    z = np.where(rng.random((n, 3)) < 0.5, 0.0, -0.0).astype(np.float32)
+    side = rng.random((n, 3)) < 0.5
+    size = rng.uniform(0.2, 3.0, (n, 3)).astype(np.float32)
+    gap = np.where(rng.random((n, 3)) < 0.5, z, np.float32(0.03125)).astype(np.float32)   # start AT zero or past it
+    lo = np.where(side, -size, gap).astype(np.float32)
+    hi = np.where(side, z, size).astype(np.float32)
+    return merge(box_tris(lo, hi), random_soup(n_soup, 0, seed + 1, extent=3.0, size=0.3))
+
+
+def kd_lattice(nx=256, ny=3, nz=2):
+    """Equal costs: a regular lattice of identical disjoint boxes (host-only primitives, the caller's bounds), pitch 1
+    and size 0.5, all coordinates small dyadic numbers: symmetric edges cost the same and the FIRST must win.  A run
+    of nx >= 200 boxes per x row: one segment's edges span several wavefronts."""
+    g = np.stack(np.meshgrid(np.arange(nx), np.arange(ny), np.arange(nz), indexing="ij"), -1).reshape(-1, 3)
+    lo = g.astype(np.float32)
+    return host_boxes(lo, lo + np.float32(0.5))
+
+
+def kd_cluster_lattice(seed=0, n_clusters=150):
+    """Equal costs in SMALL segments: clusters of 3 .. 20 identical boxes in a row, the clusters on a coarse regular
+    grid far apart: after a few levels many segments of a handful of edges share each wavefront."""
+    rng = np.random.default_rng(seed)
+    los = []
+    for c in range(n_clusters):
+        k = int(rng.integers(3, 21))
+        base = np.array([64.0 * (c % 6), 64.0 * ((c // 6) % 5), 64.0 * (c // 30)], np.float32)
+        row = np.zeros((k, 3), np.float32)
+        row[:, c % 3] = np.arange(k)
+        los.append(base + row)
+    lo = np.concatenate(los)
+    return host_boxes(lo, lo + np.float32(0.5))
+
+
+def kd_overlap_clusters(seed=0, n_clusters=6, n_per=24, spacing=30.0):
+    """Refusals: clusters of boxes that all contain a common core [-1, 1]^3 and reach 0 .. 1 beyond it on every side:
+    every split leaves nearly all primitives on both sides, cost > leafCost three times along a path (bad == 3)."""
+    rng = np.random.default_rng(seed)
+    c = (np.arange(n_clusters)[:, None] * np.array([spacing, 0.37 * spacing, -0.21 * spacing])).astype(np.float32)
+    c = np.repeat(c, n_per, 0)
+    lo = c - 1 - rng.random((len(c), 3)).astype(np.float32)
+    hi = c + 1 + rng.random((len(c), 3)).astype(np.float32)
+    return box_tris(lo, hi)
+
+
+def kd_identical_boxes(seed=0, n_stacks=5, n_per=12, n_soup=400):
+    """No valid edge: stacks of IDENTICAL boxes next to a soup: a node that holds only one stack is cut down to the
+    stack's box, and then no edge lies strictly inside it on any axis."""
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(-20, 20, (n_stacks, 3)).astype(np.float32)
+    h = rng.uniform(0.5, 1.5, (n_stacks, 3)).astype(np.float32)
+    lo, hi = np.repeat(c - h, n_per, 0), np.repeat(c + h, n_per, 0)
+    return merge(box_tris(lo, hi), random_soup(n_soup, 0, seed + 1, extent=6.0))
+
+
+def kd_flat(n=800, seed=0):
+    """All triangles in the plane z = 0 (written as +0 and -0): one zero extent, costs stay finite."""
+    rng = np.random.default_rng(seed)
+    verts, prims = random_soup(n, 0, seed, extent=6.0)
+    verts = verts.copy()
+    verts[:, 2] = np.where(rng.random(len(verts)) < 0.5, 0.0, -0.0)
+    return verts, prims
+
+
+def kd_line(n=60, seed=0, point=False):
+    """Degenerate triangles with every vertex on one line (the x axis shifted to y = 1, z = 2) or, point=True, at one
+    point: the root's box has no surface area, 1 / 0 = inf, 0 * inf = NaN: no cost ever wins."""
+    rng = np.random.default_rng(seed)
+    verts = np.zeros((3 * n, 3), np.float32)
+    verts[:, 0] = 0.5 if point else rng.uniform(-5, 5, 3 * n)
+    verts[:, 1], verts[:, 2] = 1.0, 2.0
+    return verts, make_prims(np.arange(3 * n, dtype=np.int32).reshape(n, 3))
+
+
+def kd_flat_mix(seed=0):
+    """A plane, a line and a point of degenerate geometry inside an ordinary soup."""
+    return merge(kd_flat(300, seed), kd_line(40, seed + 1), kd_line(20, seed + 2, point=True),
+                 random_soup(500, 0, seed + 3, extent=6.0))
+
+
+def kd_two_clusters(seed=0, n=400):
+    """Empty space: two dense clusters far apart (and off each other's axes): cutting empty space away pays."""
+    v1, p1 = random_soup(n, 0, seed, extent=1.0, size=0.2)
+    v2, p2 = random_soup(n, 0, seed + 1, extent=1.5, size=0.2)
+    return merge((v1, p1), (v2 + np.array([60, 25, -40], np.float32), p2))
