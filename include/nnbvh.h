@@ -338,8 +338,10 @@ int nnbvh_intersect_any_device(nnbvh_scene *s, const void *d_rays, int64_t n, vo
  * Scope: BVH scenes (flat, two-level static and animated, with or without alpha-tested kinds), closest hit and
  * occlusion-only any hit: the single-batch calls below, several batches in one launch
  * (nnbvh_trace_batches_candidates_device) and the wavefront queue entry points (nnbvh_wavefront_*_candidates, after
- * the plain wavefront calls).  Follow-ups, not covered: shape math for spheres / disks / cylinders on the device,
- * kd-tree scenes, exact node / test counts for rays with candidates.
+ * the plain wavefront calls); and kd-tree scenes through the nnbvh_kd_*_candidates calls of the kd section, with one
+ * rule of their own: a kd-tree holds a primitive in every leaf its box overlaps, and a host-only primitive is listed
+ * once, at the first position in traversal order at which the ray reached it.  Follow-ups, not covered: shape math
+ * for spheres / disks / cylinders on the device, exact node / test counts for rays with candidates.
  * NNBVH_ERR_ARG for capacity outside 1..16, a NULL count / prim / instance, or a NULL before on a closest call. */
 typedef struct nnbvh_host_candidates {
     int32_t capacity;   /* K, 1..16 (0 = a plain batch, nnbvh_trace_batches_candidates_device only) */
@@ -803,8 +805,8 @@ int nnbvh_kd_intersect_any_device(nnbvh_kd_scene *s, const void *d_rays, int64_t
  * scene: n = min(max_rays, max(*d_size, 0)), NULL queue sizes mean "not wanted", pushes beyond a capacity are counted
  * and not stored, each call is one asynchronous operation on `stream` without a host read-back, and the
  * closest_and_shadow forms trace both queues in one launch where option "pair_one_launch" is set (below).  A bad argument (NULL scene, negative or >= 2^28
- * max_rays, ...) returns NNBVH_ERR_ARG before any device call.  IntersectShadowTr / IntersectOneRandom, host
- * candidates and two-level scenes are not offered for kd scenes. */
+ * max_rays, ...) returns NNBVH_ERR_ARG before any device call.  IntersectShadowTr / IntersectOneRandom and two-level
+ * scenes are not offered for kd scenes; host candidates are (below). */
 int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches, void *stream);
 /* tuning knobs (speed only, never results), as nnbvh_scene_set_option: "read_soa" (lean scenes: the kernel reads a
  * queue's SOA slices itself; 0, the default: gathered into records first), "pair_one_launch" (closest_and_shadow traces
@@ -836,6 +838,60 @@ int nnbvh_kd_wavefront_intersect_closest_and_shadow_items(
     const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld, const float *d_r_u,
     const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_occluded,
     void *stream);
+
+/* ---- kd-tree scenes: host-only primitives as candidates ------------------------------------------------------
+ * The nnbvh_host_candidates interface above on a kd scene: the same struct, the same meaning of every field, the same
+ * merge rule and the same argument faults as the calls of the same name without `kd_`.  instance[] is required and
+ * written as 0 (kd scenes have one level), so one resolver serves both scene types.  The argument of the BVH case
+ * carries over to KdTreeAggregate::Intersect / IntersectP (aggregates.cpp:973-1150): a host-only primitive never
+ * lowers the device's tMax, both walks visit nodes in the same order, and the walk's only tMax-dependent decision is
+ * the `rayTMax < tMin` exit, so the device reaches a superset of the reference's leaves.
+ * The repeat rule: the reference tests a primitive in every leaf the ray reaches (no mailboxing); the device lists a
+ * host-only primitive once, at its first position in traversal order.  A shape's test accepts iff its t passes the
+ * comparison with the current tMax, and tMax only falls, so a later test of the same shape can only repeat the
+ * acceptance it already had, or miss (residual case: t within an ulp or two of the running tMax, as in step 3 of the
+ * merge rule).
+ * Every candidate call is traced by the record-reading one-launch kernel: a single-batch call is a launch of one
+ * batch (so n < 2^28), a queue is gathered into records first (option "read_soa" has no effect), and the pair call
+ * is one launch under option "pair_one_launch", else two.  A scene without host-only primitives runs the plain
+ * kernels over zeroed counts.  count / before are cleared by kernel nodes: the device calls can be captured.
+ * nnbvh_kd_trace_batches_candidates_device: cands[b] belongs to batches[b], capacity 0 = a plain batch (its rays are
+ * voided as by nnbvh_kd_trace_batches_device).  NNBVH_ERR_ARG, before the scene is looked at and with nothing
+ * launched, for a capacity outside 0..16, a NULL count / prim / instance, a NULL before on a closest batch, an any-hit
+ * batch that asks for exact counts together with candidates, and a batch of 2^28 rays or more.
+ * nnbvh_kd_wavefront_*_candidates: the loop of "the wavefront calls with host candidates" above, steps 3 and 4 with the
+ * scene-free nnbvh_wavefront_enqueue_closest_items_indexed_device / nnbvh_wavefront_record_shadow_device. */
+int nnbvh_kd_intersect_closest_candidates_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_hits,
+                                                 const nnbvh_host_candidates *c, void *stream);
+int nnbvh_kd_intersect_any_candidates_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_occluded,
+                                             const nnbvh_host_candidates *c, void *stream);
+/* host buffers (the pointers in `c` are host pointers): a plain synchronous staged copy */
+int nnbvh_kd_intersect_closest_candidates(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits,
+                                          const nnbvh_host_candidates *c);
+int nnbvh_kd_intersect_any_candidates(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, uint8_t *occluded,
+                                      const nnbvh_host_candidates *c);
+int nnbvh_kd_trace_batches_candidates_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches,
+                                             const nnbvh_host_candidates *cands, void *stream);
+int nnbvh_kd_wavefront_intersect_closest_items_candidates(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m,
+                                                          int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                                                          const int32_t *d_size, const uint8_t *d_prim_class,
+                                                          int64_t n_prim_class, void *d_hits,
+                                                          const nnbvh_closest_queues *out,
+                                                          const nnbvh_closest_items *items,
+                                                          const nnbvh_host_candidates *c, void *stream);
+int nnbvh_kd_wavefront_intersect_shadow_candidates(nnbvh_kd_scene *s, int32_t max_rays,
+                                                   const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                                   const float *d_Ld, const float *d_r_u, const float *d_r_l,
+                                                   const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+                                                   uint8_t *d_occluded /* required */,
+                                                   const nnbvh_host_candidates *c, void *stream);
+int nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates(
+    nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, const nnbvh_host_candidates *c,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded /* required */, const nnbvh_host_candidates *shadow_c, void *stream);
 
 /* tuning knobs (speed only, never results): "stack_window" (LDS entries per lane: 4, 8, 16),
  * "blocks_per_cu" (0 = auto), "xcd_queues" (0/1), "prim_weight" / "refill_weight" (1..64: how much a

@@ -85,6 +85,80 @@ struct ResolvedHit {
     bool host = false;  // true: a host candidate (the embedder's shape) won
 };
 
+// The candidate overloads of HipBVHAggregate and HipKdTreeAggregate: one trace call that fills nnbvh_host_candidates
+// (trace(rays, n, out, &c) -> NNBVH_* status: the scene type's entry point), then the merge rule of include/nnbvh.h.
+// fail(message) is the class's fatal().
+namespace detail {
+// the ids of the bilinear patches, sorted: the merge rule's comparison for a device hit depends on its kind
+inline void note_patch_ids(std::vector<int32_t> &ids, const nnbvh_prim *prims, int n) {
+    for (int i = 0; i < n; ++i)
+        if (prims[i].kind == NNBVH_PRIM_BILINEAR_PATCH || (prims[i].kind >= NNBVH_PRIM_ALPHA_PATCH && prims[i].kind <= NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH_FLIPPED))
+            ids.push_back(prims[i].id);
+    std::sort(ids.begin(), ids.end());
+}
+// count < 0: the candidates cannot settle the ray (more than the capacity, or an alpha re-trace)
+template <typename Fail>
+bool candidates_settle(int32_t count, uint8_t *needsHost, const char *what, Fail &&fail) {
+    if (needsHost) *needsHost = count < 0;
+    if (count < 0 && !needsHost)
+        fail(std::string(what) + ": the ray's host candidates cannot settle it (pass needsHost and re-trace it on the CPU)");
+    return count >= 0;
+}
+inline Ray ray_of(const nnbvh_ray &r) { return Ray{{r.o[0], r.o[1], r.o[2]}, {r.d[0], r.d[1], r.d[2]}, r.time}; }
+
+template <typename Trace, typename F, typename Fail>
+void resolve_closest(Trace &&trace, const std::vector<int32_t> &patchIds, const nnbvh_ray *rays, int64_t n,
+                     std::optional<ResolvedHit> *hits, F &&hostIntersect, uint8_t *needsHost, int capacity,
+                     const char *what, Fail &&fail) {
+    std::vector<nnbvh_hit> rec((size_t)n);
+    std::vector<int32_t> count((size_t)n), before((size_t)n), prim((size_t)n * capacity), inst((size_t)n * capacity);
+    nnbvh_host_candidates c{capacity, count.data(), before.data(), prim.data(), inst.data()};
+    if (trace(rays, n, rec.data(), &c) != NNBVH_OK) fail(what);
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t at = (size_t)i * capacity;
+        hits[i].reset();
+        if (!candidates_settle(count[i], needsHost ? needsHost + i : nullptr, what, fail)) continue;
+        const Ray ray = ray_of(rays[i]);
+        float tMax = rays[i].tmax;
+        auto test = [&](int j) {  // a hit replaces the result and sets tMax (aggregates.cpp:529-579, :1033-1049)
+            if (std::optional<HostHit> hh = hostIntersect(prim[at + j], inst[at + j], ray, tMax)) {
+                hits[i] = ResolvedHit{HitRecord{prim[at + j], hh->tHit, hh->b0, hh->b1, hh->b2, inst[at + j]}, true};
+                tMax = hh->tHit;
+            }
+        };
+        for (int j = 0; j < before[i]; ++j) test(j);
+        const nnbvh_hit &h = rec[(size_t)i];
+        if (h.prim >= 0) {
+            // after a candidate's hit: accepted iff t <= tMax (triangle) / t < tMax (patch), include/nnbvh.h
+            const bool patch = std::binary_search(patchIds.begin(), patchIds.end(), h.prim);
+            if (!hits[i] || (patch ? h.t < tMax : h.t <= tMax)) {
+                hits[i] = ResolvedHit{HitRecord{h.prim, h.t, h.b0, h.b1, h.b2, h.instance}, false};
+                tMax = h.t;
+            }
+        }
+        for (int j = before[i]; j < count[i]; ++j) test(j);
+    }
+}
+
+template <typename Trace, typename F, typename Fail>
+void resolve_shadow(Trace &&trace, const nnbvh_ray *rays, int64_t n, uint8_t *occluded, F &&hostIntersect,
+                    uint8_t *needsHost, int capacity, const char *what, Fail &&fail) {
+    std::vector<int32_t> count((size_t)n), prim((size_t)n * capacity), inst((size_t)n * capacity);
+    nnbvh_host_candidates c{capacity, count.data(), nullptr, prim.data(), inst.data()};
+    if (trace(rays, n, occluded, &c) != NNBVH_OK) fail(what);
+    for (int64_t i = 0; i < n; ++i) {
+        if (needsHost) needsHost[i] = 0;
+        if (occluded[i] != 2) continue;
+        occluded[i] = 0;
+        if (!candidates_settle(count[i], needsHost ? needsHost + i : nullptr, what, fail)) continue;
+        const Ray ray = ray_of(rays[i]);
+        for (int j = 0; j < count[i] && !occluded[i]; ++j)
+            occluded[i] = hostIntersect(prim[(size_t)i * capacity + j], inst[(size_t)i * capacity + j], ray,
+                                        rays[i].tmax).has_value();
+    }
+}
+}  // namespace detail
+
 class HipBVHAggregate {
   public:
     using FatalHandler = void (*)(const char *);
@@ -237,52 +311,21 @@ class HipBVHAggregate {
                                                                            int32_t, const Ray &, float>>>
     void IntersectClosest(const nnbvh_ray *rays, int64_t n, std::optional<ResolvedHit> *hits, F &&hostIntersect,
                           uint8_t *needsHost = nullptr, int capacity = 8) const {
-        std::vector<nnbvh_hit> rec((size_t)n);
-        std::vector<int32_t> count((size_t)n), before((size_t)n), prim((size_t)n * capacity), inst((size_t)n * capacity);
-        nnbvh_host_candidates c{capacity, count.data(), before.data(), prim.data(), inst.data()};
-        if (nnbvh_intersect_closest_candidates(scene_, rays, n, rec.data(), &c) != NNBVH_OK) fatal("IntersectClosest");
-        for (int64_t i = 0; i < n; ++i) {
-            const size_t at = (size_t)i * capacity;
-            hits[i].reset();
-            if (!settled(count[i], needsHost ? needsHost + i : nullptr, "IntersectClosest")) continue;
-            const Ray ray = unwire(rays[i]);
-            float tMax = rays[i].tmax;
-            auto test = [&](int j) {  // a hit replaces the result and sets tMax (aggregates.cpp:529-579)
-                if (std::optional<HostHit> hh = hostIntersect(prim[at + j], inst[at + j], ray, tMax)) {
-                    hits[i] = ResolvedHit{HitRecord{prim[at + j], hh->tHit, hh->b0, hh->b1, hh->b2, inst[at + j]}, true};
-                    tMax = hh->tHit;
-                }
-            };
-            for (int j = 0; j < before[i]; ++j) test(j);
-            const nnbvh_hit &h = rec[(size_t)i];
-            if (h.prim >= 0) {
-                // after a candidate's hit: accepted iff t <= tMax (triangle) / t < tMax (patch), include/nnbvh.h
-                const bool patch = std::binary_search(patchIds_.begin(), patchIds_.end(), h.prim);
-                if (!hits[i] || (patch ? h.t < tMax : h.t <= tMax)) {
-                    hits[i] = ResolvedHit{HitRecord{h.prim, h.t, h.b0, h.b1, h.b2, h.instance}, false};
-                    tMax = h.t;
-                }
-            }
-            for (int j = before[i]; j < count[i]; ++j) test(j);
-        }
+        detail::resolve_closest(
+            [this](const nnbvh_ray *r, int64_t k, nnbvh_hit *h, const nnbvh_host_candidates *c) {
+                return nnbvh_intersect_closest_candidates(scene_, r, k, h, c);
+            },
+            patchIds_, rays, n, hits, hostIntersect, needsHost, capacity, "IntersectClosest", [](const std::string &m) { fatal(m); });
     }
     template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
                                                                            int32_t, const Ray &, float>>>
     void IntersectShadow(const nnbvh_ray *rays, int64_t n, uint8_t *occluded, F &&hostIntersect,
                          uint8_t *needsHost = nullptr, int capacity = 8) const {
-        std::vector<int32_t> count((size_t)n), prim((size_t)n * capacity), inst((size_t)n * capacity);
-        nnbvh_host_candidates c{capacity, count.data(), nullptr, prim.data(), inst.data()};
-        if (nnbvh_intersect_any_candidates(scene_, rays, n, occluded, &c) != NNBVH_OK) fatal("IntersectShadow");
-        for (int64_t i = 0; i < n; ++i) {
-            if (needsHost) needsHost[i] = 0;
-            if (occluded[i] != 2) continue;
-            occluded[i] = 0;
-            if (!settled(count[i], needsHost ? needsHost + i : nullptr, "IntersectShadow")) continue;
-            const Ray ray = unwire(rays[i]);
-            for (int j = 0; j < count[i] && !occluded[i]; ++j)
-                occluded[i] = hostIntersect(prim[(size_t)i * capacity + j], inst[(size_t)i * capacity + j], ray,
-                                            rays[i].tmax).has_value();
-        }
+        detail::resolve_shadow(
+            [this](const nnbvh_ray *r, int64_t k, uint8_t *occ, const nnbvh_host_candidates *c) {
+                return nnbvh_intersect_any_candidates(scene_, r, k, occ, c);
+            },
+            rays, n, occluded, hostIntersect, needsHost, capacity, "IntersectShadow", [](const std::string &m) { fatal(m); });
     }
 
     // ---- WavefrontAggregate-shaped batches (host buffers; synchronous) -------------------
@@ -461,21 +504,7 @@ class HipBVHAggregate {
     static nnbvh_ray wire(const Ray &ray, float tMax) {
         return nnbvh_ray{{ray.o.x, ray.o.y, ray.o.z}, tMax, {ray.d.x, ray.d.y, ray.d.z}, ray.time};
     }
-    static Ray unwire(const nnbvh_ray &r) { return Ray{{r.o[0], r.o[1], r.o[2]}, {r.d[0], r.d[1], r.d[2]}, r.time}; }
-    // count < 0: the candidates cannot settle the ray (more than the capacity, or an alpha re-trace)
-    static bool settled(int32_t count, uint8_t *needsHost, const char *what) {
-        if (needsHost) *needsHost = count < 0;
-        if (count < 0 && !needsHost)
-            fatal(std::string(what) + ": the ray's host candidates cannot settle it (pass needsHost and re-trace it on the CPU)");
-        return count >= 0;
-    }
-    // the ids of the bilinear patches: the merge rule's comparison for a device hit depends on its kind
-    void note_patches(const nnbvh_prim *prims, int n) {
-        for (int i = 0; i < n; ++i)
-            if (prims[i].kind == NNBVH_PRIM_BILINEAR_PATCH || (prims[i].kind >= NNBVH_PRIM_ALPHA_PATCH && prims[i].kind <= NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH_FLIPPED))
-                patchIds_.push_back(prims[i].id);
-        std::sort(patchIds_.begin(), patchIds_.end());
-    }
+    void note_patches(const nnbvh_prim *prims, int n) { detail::note_patch_ids(patchIds_, prims, n); }
     nnbvh_scene *scene_ = nullptr;
     std::vector<int32_t> patchIds_;
 };
@@ -542,6 +571,7 @@ class HipKdTreeAggregate {
                                                        primAlpha ? primAlpha->data() : nullptr, device);
         nnbvh_kd_build_destroy(b);
         if (!scene_) HipBVHAggregate::fatal("HipKdTreeAggregate: scene_create");
+        note_patches(prims.data(), (int)prims.size());
     }
     // from a tree pbrt itself built: KdTreeAggregate::nodes, primitiveIndices, primitives, bounds
     HipKdTreeAggregate(const nnbvh_kd_node *nodes, int nNodes, const int32_t *primIndices, int nIndices,
@@ -552,6 +582,7 @@ class HipKdTreeAggregate {
         scene_ = nnbvh_kd_scene_create_with_attributes(nodes, nNodes, primIndices, nIndices, prims, nPrims, verts, nVerts,
                                                        boundsMinMax, normals, uvs, primAlpha, device);
         if (!scene_) HipBVHAggregate::fatal("HipKdTreeAggregate: scene_create");
+        note_patches(prims, nPrims);
     }
     HipKdTreeAggregate(const HipKdTreeAggregate &) = delete;
     HipKdTreeAggregate &operator=(const HipKdTreeAggregate &) = delete;
@@ -588,6 +619,65 @@ class HipKdTreeAggregate {
         if (nnbvh_kd_intersect_any(scene_, rays, n, occluded, nodesVisited, primTests) != NNBVH_OK)
             HipBVHAggregate::fatal("kd IntersectShadow");
     }
+    // ---- ... with host-only primitives as candidates: HipBVHAggregate's overloads, types and merge rule
+    //      (nnbvh_kd_*_candidates; `instance` is 0 in every call of hostIntersect, a shape is asked about once per ray
+    //      however many leaves hold it) ---------------------------------------------------------------------------
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    std::optional<ResolvedHit> Intersect(const Ray &ray, float tMax, F &&hostIntersect, bool *needsHost = nullptr,
+                                         int capacity = 8) const {
+        std::optional<ResolvedHit> out;
+        uint8_t voided = 0;
+        nnbvh_ray r{{ray.o.x, ray.o.y, ray.o.z}, tMax, {ray.d.x, ray.d.y, ray.d.z}, ray.time};
+        IntersectClosest(&r, 1, &out, hostIntersect, needsHost ? &voided : nullptr, capacity);
+        if (needsHost) *needsHost = voided != 0;
+        return out;
+    }
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    bool IntersectP(const Ray &ray, float tMax, F &&hostIntersect, bool *needsHost = nullptr, int capacity = 8) const {
+        uint8_t occ = 0, voided = 0;
+        nnbvh_ray r{{ray.o.x, ray.o.y, ray.o.z}, tMax, {ray.d.x, ray.d.y, ray.d.z}, ray.time};
+        IntersectShadow(&r, 1, &occ, hostIntersect, needsHost ? &voided : nullptr, capacity);
+        if (needsHost) *needsHost = voided != 0;
+        return occ != 0;
+    }
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    void IntersectClosest(const nnbvh_ray *rays, int64_t n, std::optional<ResolvedHit> *hits, F &&hostIntersect,
+                          uint8_t *needsHost = nullptr, int capacity = 8) const {
+        detail::resolve_closest(
+            [this](const nnbvh_ray *r, int64_t k, nnbvh_hit *h, const nnbvh_host_candidates *c) {
+                return nnbvh_kd_intersect_closest_candidates(scene_, r, k, h, c);
+            },
+            patchIds_, rays, n, hits, hostIntersect, needsHost, capacity, "kd IntersectClosest", [](const std::string &m) { HipBVHAggregate::fatal(m); });
+    }
+    template <typename F, typename = std::enable_if_t<std::is_invocable_r_v<std::optional<HostHit>, F &, int32_t,
+                                                                           int32_t, const Ray &, float>>>
+    void IntersectShadow(const nnbvh_ray *rays, int64_t n, uint8_t *occluded, F &&hostIntersect,
+                         uint8_t *needsHost = nullptr, int capacity = 8) const {
+        detail::resolve_shadow(
+            [this](const nnbvh_ray *r, int64_t k, uint8_t *occ, const nnbvh_host_candidates *c) {
+                return nnbvh_kd_intersect_any_candidates(scene_, r, k, occ, c);
+            },
+            rays, n, occluded, hostIntersect, needsHost, capacity, "kd IntersectShadow", [](const std::string &m) { HipBVHAggregate::fatal(m); });
+    }
+    void IntersectClosestCandidatesDevice(const void *dRays, int64_t n, void *dHits, const nnbvh_host_candidates &c,
+                                          void *stream) const {
+        if (nnbvh_kd_intersect_closest_candidates_device(scene_, dRays, n, dHits, &c, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd IntersectClosestCandidatesDevice");
+    }
+    void IntersectShadowCandidatesDevice(const void *dRays, int64_t n, void *dOccluded, const nnbvh_host_candidates &c,
+                                         void *stream) const {
+        if (nnbvh_kd_intersect_any_candidates_device(scene_, dRays, n, dOccluded, &c, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd IntersectShadowCandidatesDevice");
+    }
+    void TraceBatchesCandidatesDevice(const nnbvh_batch *batches, int nBatches, const nnbvh_host_candidates *cands,
+                                      void *stream) const {
+        if (nnbvh_kd_trace_batches_candidates_device(scene_, batches, nBatches, cands, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd TraceBatchesCandidatesDevice");
+    }
+
     void IntersectClosestDevice(const void *dRays, int64_t n, void *dHits, void *stream) const {
         if (nnbvh_kd_intersect_closest_device(scene_, dRays, n, dHits, stream) != NNBVH_OK)
             HipBVHAggregate::fatal("kd IntersectClosestDevice");
@@ -599,7 +689,7 @@ class HipKdTreeAggregate {
     }
 
     // ---- one-launch batches and whole wavefront stages on a kd scene: HipBVHAggregate's signatures and meanings
-    //      (nnbvh_kd_trace_batches_device, nnbvh_kd_wavefront_*; no candidates, include/nnbvh.h) ------------------
+    //      (nnbvh_kd_trace_batches_device, nnbvh_kd_wavefront_*, include/nnbvh.h) --------------------------------
     void TraceBatchesDevice(const nnbvh_batch *batches, int nBatches, void *stream) const {
         if (nnbvh_kd_trace_batches_device(scene_, batches, nBatches, stream) != NNBVH_OK)
             HipBVHAggregate::fatal("kd TraceBatchesDevice");
@@ -659,7 +749,9 @@ class HipKdTreeAggregate {
     }
 
   private:
+    void note_patches(const nnbvh_prim *prims, int n) { detail::note_patch_ids(patchIds_, prims, n); }
     nnbvh_kd_scene *scene_ = nullptr;
+    std::vector<int32_t> patchIds_;
     float bounds_[6] = {0, 0, 0, 0, 0, 0};
 };
 

@@ -88,6 +88,11 @@ EXPORTS = [
     "nnbvh_kd_trace_batches_device", "nnbvh_kd_wavefront_intersect_closest", "nnbvh_kd_wavefront_intersect_shadow",
     "nnbvh_kd_wavefront_intersect_closest_and_shadow", "nnbvh_kd_wavefront_intersect_closest_items",
     "nnbvh_kd_wavefront_intersect_closest_and_shadow_items", "nnbvh_kd_scene_set_option",
+    "nnbvh_kd_intersect_closest_candidates", "nnbvh_kd_intersect_any_candidates",
+    "nnbvh_kd_intersect_closest_candidates_device", "nnbvh_kd_intersect_any_candidates_device",
+    "nnbvh_kd_trace_batches_candidates_device", "nnbvh_kd_wavefront_intersect_closest_items_candidates",
+    "nnbvh_kd_wavefront_intersect_shadow_candidates",
+    "nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates",
 ]
 
 
@@ -291,6 +296,14 @@ def lib():
     L.nnbvh_wavefront_intersect_closest_and_shadow_items_candidates.restype = i32
     L.nnbvh_wavefront_intersect_closest_and_shadow_items_candidates.argtypes = [
         vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, hc, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, hc, vp]
+    # ... and their kd forms
+    for name in ("intersect_closest_candidates", "intersect_any_candidates", "intersect_closest_candidates_device",
+                 "intersect_any_candidates_device", "trace_batches_candidates_device",
+                 "wavefront_intersect_closest_items_candidates", "wavefront_intersect_shadow_candidates",
+                 "wavefront_intersect_closest_and_shadow_items_candidates"):
+        kd = getattr(L, "nnbvh_kd_" + name)
+        kd.restype = i32
+        kd.argtypes = getattr(L, "nnbvh_" + name).argtypes
     L.nnbvh_scene_sched_stats.restype = i32
     L.nnbvh_scene_sched_stats.argtypes = [vp, vp, i32]
     _lib = L

@@ -185,8 +185,7 @@ int launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream, const
                          const nnbvh_host_candidates *cands = nullptr);
 bool batches_fusable(const nnbvh_scene *s, const nnbvh_batch *batches, int n_batches);
 
-// what is wrong with a candidates struct (closest: before is an output too), or nullptr; ..._ok reports it as fn's
-const char *candidates_fault(const nnbvh_host_candidates *c, bool closest);
+// candidates_fault (nnbvh_internal.h) reported as fn's
 bool candidates_ok(const char *fn, const nnbvh_host_candidates *c, bool closest);
 // the count (and, closest hit, before) arrays of a candidate call start at zero: kernel nodes on `stream`
 bool zero_candidates(const nnbvh_scene *s, const nnbvh_host_candidates *hc, int64_t n, bool closest, hipStream_t stream);

@@ -1,7 +1,8 @@
 // capi_wavefront.cpp — the C ABI of include/nnbvh.h, wavefront queues (wavefront/aggregate.cpp:34-116 on the
 // device): IntersectClosest, IntersectShadow and the two in one launch, each with or without the work items and
 // the host candidates, and the multi-pass IntersectShadowTr / IntersectOneRandom; the first three also for kd-tree
-// scenes (kd_trace.h), over the same argument packs, checks and queue kernels.  Host code only.
+// scenes (kd_trace.h), host candidates included, over the same argument packs, checks and queue kernels.  Host code
+// only.
 #include <algorithm>
 #include <cstring>
 
@@ -113,16 +114,21 @@ struct ShadowSide {
 
 // the entry point a side, or the pair, was called through: error texts carry its name
 static const char *closest_fn(const ClosestSide &a) {
-    if (a.kd) return a.with_items ? "kd_wavefront_intersect_closest_items" : "kd_wavefront_intersect_closest";
+    if (a.kd)
+        return a.with_candidates ? "kd_wavefront_intersect_closest_items_candidates"
+                                 : a.with_items ? "kd_wavefront_intersect_closest_items" : "kd_wavefront_intersect_closest";
     return a.with_candidates ? "wavefront_intersect_closest_items_candidates"
                              : a.with_items ? "wavefront_intersect_closest_items" : "wavefront_intersect_closest";
 }
 static const char *shadow_fn(const ShadowSide &a) {
-    if (a.kd) return "kd_wavefront_intersect_shadow";
+    if (a.kd) return a.with_candidates ? "kd_wavefront_intersect_shadow_candidates" : "kd_wavefront_intersect_shadow";
     return a.with_candidates ? "wavefront_intersect_shadow_candidates" : "wavefront_intersect_shadow";
 }
 static const char *pair_fn(const ClosestSide &a) {
-    if (a.kd) return a.with_items ? "kd_wavefront_intersect_closest_and_shadow_items" : "kd_wavefront_intersect_closest_and_shadow";
+    if (a.kd)
+        return a.with_candidates ? "kd_wavefront_intersect_closest_and_shadow_items_candidates"
+                                 : a.with_items ? "kd_wavefront_intersect_closest_and_shadow_items"
+                                                : "kd_wavefront_intersect_closest_and_shadow";
     return a.with_candidates ? "wavefront_intersect_closest_and_shadow_items_candidates"
                              : a.with_items ? "wavefront_intersect_closest_and_shadow_items"
                                             : "wavefront_intersect_closest_and_shadow";
@@ -327,8 +333,10 @@ static int intersect_closest_and_shadow(nnbvh_scene *s, const ClosestSide &c, co
 
 // ---- the same three calls on a kd-tree scene -----------------------------------------------------------------
 // The trace half is kd_trace.hip's batch-mode launch (one for a single queue, ONE for the pair); the argument packs,
-// their checks and the queue kernels behind the launch are the ones above.  No candidates: a host-only primitive
-// voids the ray, and the enqueue sends it to needs_host (or nowhere) as for a BVH scene without them.
+// their checks and the queue kernels behind the launch are the ones above.  Without candidates a host-only primitive
+// voids the ray, and the enqueue sends it to needs_host (or nowhere) as for a BVH scene without them; with them
+// (the *_candidates calls) the launch runs the kernel's candidate-mode instances over the gathered queue, the enqueue
+// routes by the per-ray count and the shadow record skips the non-zero flags, as for a BVH scene.
 struct KdSceneCall {
     DeviceGuard guard;
     std::unique_lock<std::mutex> lock;
@@ -347,9 +355,15 @@ static bool kd_size_ok(const char *fn, int32_t max_rays) {
     return max_rays < (1 << kKdIndexBits) || fail(fn, "a queue of 2^28 rays or more");
 }
 
+// ... and so are a candidate call's nnbvh_host_candidates (the side checks below read the scene's device)
+static bool kd_candidates_ok(const char *fn, bool scene, bool with_candidates, const nnbvh_host_candidates *hc, bool closest) {
+    if (!with_candidates) return true;
+    return scene ? candidates_ok(fn, hc, closest) : fail(fn, "bad argument (a scene is required)");
+}
+
 static int kd_intersect_closest(nnbvh_kd_scene *s, const ClosestSide &a, hipStream_t stream) {
     const char *fn = closest_fn(a);
-    if (!kd_size_ok(fn, a.max_rays) || !closest_side_ok(fn, s != nullptr, s ? s->device : 0, a)) return NNBVH_ERR_ARG;
+    if (!kd_size_ok(fn, a.max_rays) || !kd_candidates_ok(fn, s != nullptr, a.with_candidates, a.hc, true) || !closest_side_ok(fn, s != nullptr, s ? s->device : 0, a)) return NNBVH_ERR_ARG;
     if (a.max_rays == 0) return NNBVH_OK;
     KdSceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
@@ -357,13 +371,14 @@ static int kd_intersect_closest(nnbvh_kd_scene *s, const ClosestSide &a, hipStre
     if (!hits) return NNBVH_ERR_DEVICE;
     KdBatch batch;
     batch.soa = a.queue, batch.n = a.max_rays, batch.d_n = a.d_size, batch.out = hits;
+    batch.hc = a.with_candidates ? a.hc : nullptr;
     const int rc = kd_launch_batches(s, call.w, stream, &batch, 1);
-    return rc != NNBVH_OK ? rc : enqueue_closest(s->n_cus, false, a, hits, stream);
+    return rc != NNBVH_OK ? rc : enqueue_closest(s->n_cus, s->has_host_prims != 0, a, hits, stream);
 }
 
 static int kd_intersect_shadow(nnbvh_kd_scene *s, const ShadowSide &a, hipStream_t stream) {
     const char *fn = shadow_fn(a);
-    if (!kd_size_ok(fn, a.max_rays) || !shadow_side_ok(fn, s != nullptr, a)) return NNBVH_ERR_ARG;
+    if (!kd_size_ok(fn, a.max_rays) || !kd_candidates_ok(fn, s != nullptr, a.with_candidates, a.hc, false) || !shadow_side_ok(fn, s != nullptr, a)) return NNBVH_ERR_ARG;
     if (a.max_rays == 0) return NNBVH_OK;
     KdSceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
@@ -371,6 +386,7 @@ static int kd_intersect_shadow(nnbvh_kd_scene *s, const ShadowSide &a, hipStream
     if (!occ) return NNBVH_ERR_DEVICE;
     KdBatch batch;
     batch.any = 1, batch.soa = a.queue, batch.n = a.max_rays, batch.d_n = a.d_size, batch.out = occ;
+    batch.hc = a.with_candidates ? a.hc : nullptr;
     const int rc = kd_launch_batches(s, call.w, stream, &batch, 1);
     return rc != NNBVH_OK ? rc : record_shadow(s->n_cus, a, occ, stream);
 }
@@ -381,6 +397,8 @@ static int kd_intersect_closest_and_shadow(nnbvh_kd_scene *s, const ClosestSide 
                                            hipStream_t stream) {
     const char *fn = pair_fn(c);
     if (!kd_size_ok(fn, c.max_rays) || !kd_size_ok(fn, sh.max_rays) ||
+        !kd_candidates_ok(fn, s != nullptr, c.with_candidates, c.hc, true) ||
+        !kd_candidates_ok(fn, s != nullptr, sh.with_candidates, sh.hc, false) ||
         !closest_side_ok(fn, s != nullptr, s ? s->device : 0, c) || !shadow_side_ok(fn, s != nullptr, sh))
         return NNBVH_ERR_ARG;
     if (c.max_rays == 0 || sh.max_rays == 0 || !s->pair_one_launch) {
@@ -398,8 +416,10 @@ static int kd_intersect_closest_and_shadow(nnbvh_kd_scene *s, const ClosestSide 
     batches[0].soa = c.queue, batches[0].n = c.max_rays, batches[0].d_n = c.d_size, batches[0].out = hits;
     batches[1].any = 1, batches[1].soa = sh.queue, batches[1].n = sh.max_rays, batches[1].d_n = sh.d_size,
     batches[1].out = occ;
+    batches[0].hc = c.with_candidates ? c.hc : nullptr;
+    batches[1].hc = sh.with_candidates ? sh.hc : nullptr;
     int rc = kd_launch_batches(s, call.w, stream, batches, 2);
-    if (rc == NNBVH_OK) rc = enqueue_closest(s->n_cus, false, c, hits, stream);
+    if (rc == NNBVH_OK) rc = enqueue_closest(s->n_cus, s->has_host_prims != 0, c, hits, stream);
     if (rc == NNBVH_OK) rc = record_shadow(s->n_cus, sh, occ, stream);
     return rc;
 }
@@ -570,6 +590,50 @@ int nnbvh_kd_wavefront_intersect_closest_and_shadow_items(
         {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
          .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded,
          .kd = true},
+        (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_intersect_closest_items_candidates(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m,
+                                                          int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+                                                          const int32_t *d_size, const uint8_t *d_prim_class,
+                                                          int64_t n_prim_class, void *d_hits,
+                                                          const nnbvh_closest_queues *out,
+                                                          const nnbvh_closest_items *items,
+                                                          const nnbvh_host_candidates *c, void *stream) {
+    return kd_intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                    .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
+                                    .out = out, .with_items = true, .mesh = m, .items = items, .with_candidates = true,
+                                    .hc = c, .kd = true},
+                                (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_intersect_shadow_candidates(nnbvh_kd_scene *s, int32_t max_rays,
+                                                   const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                                   const float *d_Ld, const float *d_r_u, const float *d_r_l,
+                                                   const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+                                                   uint8_t *d_occluded, const nnbvh_host_candidates *c, void *stream) {
+    return kd_intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
+                                   .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
+                                   .n_pixels = n_pixels, .d_occluded = d_occluded, .with_candidates = true, .hc = c,
+                                   .kd = true},
+                               (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates(
+    nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
+    const nnbvh_closest_queues *out, const nnbvh_closest_items *items, const nnbvh_host_candidates *c,
+    int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
+    const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
+    uint8_t *d_occluded, const nnbvh_host_candidates *shadow_c, void *stream) {
+    return kd_intersect_closest_and_shadow(
+        s,
+        {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size, .d_prim_class = d_prim_class,
+         .n_prim_class = n_prim_class, .d_hits = d_hits, .out = out, .with_items = true, .mesh = m, .items = items,
+         .with_candidates = true, .hc = c, .kd = true},
+        {.max_rays = max_shadow_rays, .queue = shadow_queue, .d_size = d_shadow_size, .d_Ld = d_Ld, .d_r_u = d_r_u,
+         .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L, .n_pixels = n_pixels, .d_occluded = d_occluded,
+         .with_candidates = true, .hc = shadow_c, .kd = true},
         (hipStream_t)stream);
 }
 

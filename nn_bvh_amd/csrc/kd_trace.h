@@ -33,6 +33,9 @@ struct KdBatch {
     const int32_t *d_n = nullptr;
     void *out = nullptr;
     void *visited = nullptr, *tests = nullptr;  // any hit, nullable: exact counts
+    // nullable; capacity > 0: the batch's host candidates (device pointers, arrays of n entries; the caller has checked
+    // them).  count / before are zeroed by kernel nodes ahead of the launch
+    const nnbvh_host_candidates *hc = nullptr;
 };
 
 }  // namespace nnbvh
@@ -49,7 +52,8 @@ struct nnbvh_kd_scene {
     int32_t *d_indices = nullptr;
     float4 *d_prims = nullptr;
     float4 *d_extras = nullptr;  // 6 slots per primitive, scenes with attribute-reading alpha kinds only
-    int blocks_per_cu[4] = {0, 0, 0, 0};  // closest, any, batches of records, batches of SOA slices
+    int blocks_per_cu[5] = {0, 0, 0, 0, 0};  // closest, any, batches of records, batches of SOA slices, batches with
+                                             // host candidates
     // tuning (speed only, never results; nnbvh_kd_scene_set_option "read_soa" / "pair_one_launch"; DESIGN.md §5.7
     // holds the measurement behind the defaults)
     // both 0 until a recorded probe run shows the new form ahead by more than the spread of either form
@@ -66,8 +70,10 @@ KdWorkspace *kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream);
 
 // ONE batch-mode launch (behind the one queue-reset node) over 1..kKdMaxBatches batches.  Batches given as SOA
 // slices are read by the kernel itself where the scene's instance has a SOA form (lean scenes, every batch of the
-// launch SOA); else they are gathered into workspace records first.  The caller has checked the arguments, made
-// the scene's device current and holds s->mu.
+// launch SOA); else they are gathered into workspace records first.  Where a batch has host candidates the launch
+// runs the kernel's candidate-mode instances (record form only) if the scene holds host-only primitives, else the
+// plain ones over the zeroed counts.  The caller has checked the arguments, made the scene's device current and holds
+// s->mu.
 int kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdBatch *batches, int n_batches);
 
 }  // namespace nnbvh

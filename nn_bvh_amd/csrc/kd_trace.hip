@@ -28,6 +28,7 @@
 #include "nnbvh_internal.h"
 #include "trace_math.h"
 #include "spawn_math.h"
+#include "bvh_trace.h"
 #include "kd_trace.h"
 #include "wavefront.h"
 
@@ -72,6 +73,14 @@ struct KdParams {
     int32_t *bVisited[kKdMaxBatches], *bTests[kKdMaxBatches];  // any-hit batches, nullable
     long bN[kKdMaxBatches];
     const int32_t *bNDev[kKdMaxBatches];     // nullable: device-resident size of batch b, clamped to [0, bN[b]]
+    // candidate mode (the HOSTC instances of MODE 2, scenes with host-only primitives), appended
+    // again: per batch the arrays of its nnbvh_host_candidates.  bHcCap[b] == 0: batch b is a plain batch, a
+    // host-only primitive voids its ray as in the plain instances
+    int bHcCap[kKdMaxBatches];
+    int32_t *bHcCount[kKdMaxBatches];
+    int32_t *bHcBefore[kKdMaxBatches];       // closest batches only
+    int32_t *bHcPrim[kKdMaxBatches];
+    int32_t *bHcInst[kKdMaxBatches];
 };
 
 // util/vecmath.h:1547-1571 with invRayDir = 1 / d[i] taken from the ray's precomputed reciprocals
@@ -115,8 +124,19 @@ DEV bool kd_root_interval(const float bmin[3], const float bmax[3], V3 o, V3 inv
 // byte offsets from a scalar base (no 64-bit shift / add per fetch).
 // ATTR = 1 (with PATCH = 1): the scene holds alpha-tested triangles of smooth meshes or alpha-tested bilinear patches,
 // whose re-trace reads per-vertex attributes from p.extras (bvh_trace.hip's ALPHA = 1 smooth / ALPHA = 2 code)
-template <int MODE, int PATCH, int W, int O32, int ATTR = 0>
+// HOSTC = 1 (MODE 2 only, scenes with host-only primitives): candidate mode.  A host-only primitive does not void the
+// ray: its id goes to the ray's list (p.bHcPrim / p.bHcInst of the lane's batch at ray * K, traversal order, the count
+// in the kColdHost slot) unless it stands there already — a kd-tree holds a primitive in every leaf its box overlaps
+// — and the walk goes on as if the primitive were absent.  An accepted closest hit on a lane with candidates stores
+// how many came before it (p.bHcBefore).  At retire the count goes to p.bHcCount: 0..K, -1 = more than K (record
+// void), -2 = an alpha re-trace voided the ray.  A batch with bHcCap[b] == 0 is a plain batch: its first host-only
+// primitive "overflows" a list of none.
+template <int MODE, int PATCH, int W, int O32, int ATTR = 0, int HOSTC = 0>
 __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdParams p) {
+    static_assert(!HOSTC || MODE == 2, "candidate mode: the record-reading batch instances only");
+    auto pick_batch = [](const auto &arr, int b) {  // arr[b] of a kernel-argument array
+        return b == 0 ? arr[0] : (b == 1 ? arr[1] : (b == 2 ? arr[2] : arr[3]));
+    };
     auto at = [](const auto *base, int index) {  // &base[index]
         using T = decltype(base);
         return O32 ? reinterpret_cast<T>(reinterpret_cast<const char *>(base) + (unsigned)index * (unsigned)sizeof(*base))
@@ -196,7 +216,35 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
             const int ri = isIdle ? __float_as_int(cold[kColdRi][lane]) : -1;
             if (ri >= 0) {
                 const bool needHost = p.hasHostPrims && cold[kColdHost][lane] != 0.0f;
-                if constexpr (BATCH) {  // the lane's batch has its own arrays
+                if constexpr (HOSTC) {
+                    // candidate mode, a block of its own so that the plain instances' retire below stays as it is:
+                    // the count goes to the batch's array; an any-hit ray is the caller's (2) when it met a host-only
+                    // primitive, a closest-hit record is void only for count < 0
+                    const int b = ri >> kKdIndexBits;
+                    const long idx = ri & ((1 << kKdIndexBits) - 1);
+                    void *outp = pick_batch(p.bOut, b);
+                    const int c = __float_as_int(cold[kColdHost][lane]);
+                    if (pick_batch(p.bHcCap, b) > 0) pick_batch(p.bHcCount, b)[idx] = c;
+                    if (r.kz & kAnyLane) {
+                        int32_t *vis = pick_batch(p.bVisited, b), *tst = pick_batch(p.bTests, b);
+                        reinterpret_cast<uint8_t *>(outp)[idx] = found ? 1 : (c != 0 ? 2 : 0);
+                        if (vis) vis[idx] = visited;
+                        if (tst) tst[idx] = tests;
+                    } else {
+                        float4 h0, h1;
+                        h0.x = cold[kColdHit][lane];
+                        h0.y = rayTMax;
+                        h0.z = cold[kColdHit + 1][lane];
+                        h0.w = cold[kColdHit + 2][lane];
+                        h1.x = cold[kColdHit + 3][lane];
+                        h1.y = __int_as_float(visited);
+                        h1.z = __int_as_float(tests);
+                        h1.w = c < 0 ? __int_as_float(-1) : 0.0f;
+                        float4 *out = reinterpret_cast<float4 *>(outp) + 2 * idx;
+                        out[0] = h0;
+                        out[1] = h1;
+                    }
+                } else if constexpr (BATCH) {  // the lane's batch has its own arrays
                     const int b = ri >> kKdIndexBits;
                     const long idx = ri & ((1 << kKdIndexBits) - 1);
                     void *outp = b == 0 ? p.bOut[0] : (b == 1 ? p.bOut[1] : (b == 2 ? p.bOut[2] : p.bOut[3]));
@@ -303,7 +351,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                     cold[kColdHit + 2][lane] = 0.0f;
                     cold[kColdHit + 3][lane] = 0.0f;
                 }
-                if (p.hasHostPrims) cold[kColdHost][lane] = 0.0f;
+                if (HOSTC || p.hasHostPrims) cold[kColdHost][lane] = 0.0f;  // candidate mode: count 0
                 visited = 0;
                 tests = 0;
                 found = false;
@@ -327,7 +375,32 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                                   "+v"(s1.z), "+v"(s1.w), "+v"(s2.x), "+v"(s2.y), "+v"(s2.z), "+v"(s2.w), "+v"(nextIdx));
                 const unsigned flags = __float_as_uint(s1.w);
                 if (flags & kPrimHost) {
-                    cold[kColdHost][lane] = 1.0f;
+                    if constexpr (HOSTC) {
+                        // the caller tests this primitive itself: list it (rare path: the entries go straight to
+                        // global memory) and walk on as if it were absent
+                        const int c = __float_as_int(cold[kColdHost][lane]);
+                        if (c >= 0) {  // -1 (overflow) and -2 (alpha re-trace) stay
+                            const int tag = __float_as_int(cold[kColdRi][lane]);
+                            const int b = tag >> kKdIndexBits;
+                            const int cap = pick_batch(p.bHcCap, b);
+                            const long first = (long)(tag & ((1 << kKdIndexBits) - 1)) * cap;
+                            int32_t *hcPrim = pick_batch(p.bHcPrim, b);
+                            const int id = __float_as_int(s0.w);
+                            // the repeat rule: the primitive sits in every leaf its box overlaps; only its first
+                            // position in traversal order is listed (c <= cap entries of this lane's own)
+                            bool listed = false;
+                            for (int j = 0; j < c; ++j) listed = listed || hcPrim[first + j] == id;
+                            if (!listed) {
+                                if (c < cap) {
+                                    hcPrim[first + c] = id;
+                                    pick_batch(p.bHcInst, b)[first + c] = 0;  // kd scenes have one level
+                                }
+                                cold[kColdHost][lane] = __int_as_float(c < cap ? c + 1 : -1);
+                            }
+                        }
+                    } else {
+                        cold[kColdHost][lane] = 1.0f;
+                    }
                 } else {
                     tests += 1;
                     bool hit;
@@ -359,7 +432,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                                     float y0, y1, y2, tn;
                                     if (triangle_test(rn, rayTMax - th, (flags & kPrimDegenerate) != 0, {s0.x, s0.y, s0.z},
                                                       {s1.x, s1.y, s1.z}, {s2.x, s2.y, s2.z}, y0, y1, y2, tn))
-                                        cold[kColdHost][lane] = 1.0f;  // the ray is the caller's (see bvh_trace.hip)
+                                        cold[kColdHost][lane] = HOSTC ? __int_as_float(-2) : 1.0f;  // the ray is the caller's (see bvh_trace.hip)
                                 }
                             }
                         }
@@ -382,7 +455,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                                 if (!(u > a)) break;
                                 if (k == kAlphaPatchDepth) {
                                     hit = false;
-                                    cold[kColdHost][lane] = 1.0f;
+                                    cold[kColdHost][lane] = HOSTC ? __int_as_float(-2) : 1.0f;
                                     break;
                                 }
                                 if (k == 0) t0 = th;
@@ -413,6 +486,14 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                             cold[kColdHit + 2][lane] = x1;
                             cold[kColdHit + 3][lane] = x2;
                             rayTMax = th;  // :1035-1036, :1046-1047
+                            if constexpr (HOSTC) {  // the candidates met before this hit (the last store wins);
+                                                    // c > 0 only in a batch with candidate arrays
+                                const int c = __float_as_int(cold[kColdHost][lane]);
+                                if (c > 0) {
+                                    const int tag = __float_as_int(cold[kColdRi][lane]);
+                                    pick_batch(p.bHcBefore, tag >> kKdIndexBits)[tag & ((1 << kKdIndexBits) - 1)] = c;
+                                }
+                            }
                         } else {
                             found = true;
                         }
@@ -613,14 +694,17 @@ static int kd_launch(nnbvh_kd_scene *s, int mode, const void *d_rays, int64_t n,
 int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdBatch *batches, int n_batches) {
     KdParams p{};
     kd_fill_scene(s, w, p);
-    bool all_soa = true;
+    bool all_soa = true, candidates = false;
     int64_t total = 0, soa_rays = 0;
     for (int b = 0; b < n_batches; ++b) {
         all_soa = all_soa && !batches[b].rays;
         if (!batches[b].rays) soa_rays += batches[b].n;
         total += batches[b].n;
+        candidates = candidates || (batches[b].hc && batches[b].hc->capacity > 0);
     }
-    const bool read_soa = all_soa && kd_scene_reads_soa(s);
+    // a candidate call always goes through the record form ("read_soa" has no effect on it)
+    const bool read_soa = !candidates && all_soa && kd_scene_reads_soa(s);
+    const bool hostc = candidates && s->has_host_prims;  // else: the plain instances over zeroed counts
     if (!read_soa && soa_rays > 0 &&
         !kd_grow(&w->d_in, &w->in_bytes, (size_t)soa_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
         return NNBVH_ERR_DEVICE;
@@ -635,6 +719,20 @@ int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stre
         p.bTests[b] = k.any ? (int32_t *)k.tests : nullptr;
         p.bN[b] = (long)k.n;
         p.bNDev[b] = k.d_n;
+        if (k.hc && k.hc->capacity > 0 && k.n > 0) {
+            const int zero_blocks = s->n_cus * 8;
+            if (!kd_hip_ok(launch_zero_words(k.hc->count, (long)k.n, zero_blocks, stream), "candidate count reset launch") ||
+                (!k.any && !kd_hip_ok(launch_zero_words(k.hc->before, (long)k.n, zero_blocks, stream),
+                                      "candidate before reset launch")))
+                return NNBVH_ERR_DEVICE;
+            if (hostc) {
+                p.bHcCap[b] = k.hc->capacity;
+                p.bHcCount[b] = k.hc->count;
+                p.bHcBefore[b] = k.any ? nullptr : k.hc->before;
+                p.bHcPrim[b] = k.hc->prim;
+                p.bHcInst[b] = k.hc->instance;
+            }
+        }
         if (read_soa) {
             if (k.soa) p.bSoa[b] = *k.soa;  // (an empty batch may come without slices)
         } else if (!k.rays && k.n > 0) {
@@ -652,9 +750,13 @@ int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stre
         kd_trace_kernel<2, 0, kKdWLean, 0>, kd_trace_kernel<2, 1, kKdW, 0>, kd_trace_kernel<2, 1, kKdW, 0, 1>,
         kd_trace_kernel<3, 0, kKdWLean, 0>, kd_trace_kernel<2, 0, kKdWLean, 1>, kd_trace_kernel<2, 1, kKdW, 1>,
         kd_trace_kernel<2, 1, kKdW, 1, 1>,  kd_trace_kernel<3, 0, kKdWLean, 1>};
+    // ... and the candidate-mode twins of the record form
+    void (*const hostc_kernels[6])(KdParams) = {
+        kd_trace_kernel<2, 0, kKdWLean, 0, 0, 1>, kd_trace_kernel<2, 1, kKdW, 0, 0, 1>, kd_trace_kernel<2, 1, kKdW, 0, 1, 1>,
+        kd_trace_kernel<2, 0, kKdWLean, 1, 0, 1>, kd_trace_kernel<2, 1, kKdW, 1, 0, 1>, kd_trace_kernel<2, 1, kKdW, 1, 1, 1>};
     const int form = read_soa ? 3 : (s->d_extras ? 2 : (s->has_patches ? 1 : 0));
-    void (*const kernel)(KdParams) = kernels[form + 4 * s->fits32];
-    const int slot = read_soa ? 3 : 2;
+    void (*const kernel)(KdParams) = hostc ? hostc_kernels[form + 3 * s->fits32] : kernels[form + 4 * s->fits32];
+    const int slot = hostc ? 4 : (read_soa ? 3 : 2);
     if (s->blocks_per_cu[slot] == 0) {
         int occ = 0;
         const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kKdBlock, 0);
@@ -915,9 +1017,15 @@ int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value) {
     return NNBVH_OK;
 }
 
-int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches, void *stream) {
-    if (!s || !batches || n_batches < 1 || n_batches > kKdMaxBatches) {
-        set_error("kd_trace_batches_device: bad argument (a scene and 1..4 batches)");
+}  // extern "C"
+
+// nnbvh_kd_trace_batches_device and its candidates form (cands nullable; cands[b] belongs to batches[b], capacity 0 =
+// a plain batch).  Everything is checked before the scene is looked at.
+static int kd_trace_batches(const char *fn, nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches,
+                            const nnbvh_host_candidates *cands, bool with_candidates, void *stream) {
+    if (!s || !batches || n_batches < 1 || n_batches > kKdMaxBatches || (with_candidates && !cands)) {
+        set_error(std::string(fn) + (with_candidates ? ": bad argument (a scene, 1..4 batches and their candidates)"
+                                                     : ": bad argument (a scene and 1..4 batches)"));
         return NNBVH_ERR_ARG;
     }
     KdBatch jobs[kKdMaxBatches];
@@ -926,8 +1034,18 @@ int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches,
         const nnbvh_batch &k = batches[b];
         if ((k.kind != NNBVH_BATCH_CLOSEST && k.kind != NNBVH_BATCH_ANY) || k.n < 0 || k.n >= (1LL << kKdIndexBits) ||
             (k.n > 0 && (!k.d_rays || !k.d_out))) {
-            set_error("kd_trace_batches_device: bad batch (kind, 0 <= n < 2^28, rays and output)");
+            set_error(std::string(fn) + ": bad batch (kind, 0 <= n < 2^28, rays and output)");
             return NNBVH_ERR_ARG;
+        }
+        if (cands && cands[b].capacity != 0) {
+            const char *why = candidates_fault(&cands[b], k.kind == NNBVH_BATCH_CLOSEST);
+            if (!why && k.kind == NNBVH_BATCH_ANY && (k.d_nodes_visited || k.d_prim_tests))
+                why = "an any-hit batch has exact counts or candidates, not both";
+            if (why) {
+                set_error(std::string(fn) + ": batch candidates: " + why);
+                return NNBVH_ERR_ARG;
+            }
+            jobs[b].hc = &cands[b];
         }
         jobs[b].any = k.kind == NNBVH_BATCH_ANY;
         jobs[b].rays = k.d_rays;
@@ -944,6 +1062,104 @@ int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches,
     KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
     if (!w) return NNBVH_ERR_DEVICE;
     return kd_launch_batches(s, w, (hipStream_t)stream, jobs, n_batches);
+}
+
+// the arguments of a single-batch candidate call (a one-batch launch: fewer than 2^28 rays)
+static bool kd_candidate_args_ok(const char *fn, const nnbvh_kd_scene *s, int64_t n, const void *rays, const void *out,
+                                 const nnbvh_host_candidates *c, bool closest) {
+    const char *why = nullptr;
+    if (!s || n < 0 || (n > 0 && (!rays || !out))) why = "bad argument";
+    else if ((why = candidates_fault(c, closest)) != nullptr) {}
+    else if (n >= (1LL << kKdIndexBits)) why = "a batch of 2^28 rays or more";
+    if (why) set_error(std::string(fn) + ": " + why);
+    return !why;
+}
+
+static int kd_candidates_device(const char *fn, nnbvh_kd_scene *s, bool any, const void *d_rays, int64_t n, void *d_out,
+                                const nnbvh_host_candidates *c, void *stream) {
+    if (!kd_candidate_args_ok(fn, s, n, d_rays, d_out, c, !any)) return NNBVH_ERR_ARG;
+    if (n == 0) return NNBVH_OK;
+    KdDeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
+    if (!w) return NNBVH_ERR_DEVICE;
+    KdBatch batch;
+    batch.any = any, batch.rays = d_rays, batch.n = n, batch.out = d_out, batch.hc = c;
+    return kd_launch_batches(s, w, (hipStream_t)stream, &batch, 1);
+}
+
+// host buffers: one staged copy in, one launch on the null stream, copies out (synchronous)
+static int kd_candidates_host(const char *fn, nnbvh_kd_scene *s, bool any, const nnbvh_ray *rays, int64_t n, void *out,
+                              const nnbvh_host_candidates *c) {
+    if (!kd_candidate_args_ok(fn, s, n, rays, out, c, !any)) return NNBVH_ERR_ARG;
+    if (n == 0) return NNBVH_OK;
+    KdDeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::lock_guard<std::mutex> lock(s->mu);
+    const size_t k = (size_t)c->capacity, out_elem = any ? 1 : sizeof(nnbvh_hit);
+    void *d_rays = nullptr, *d_out = nullptr;
+    nnbvh_host_candidates d{};
+    d.capacity = c->capacity;
+    bool ok = kd_hip_ok(hipMalloc(&d_rays, (size_t)n * sizeof(nnbvh_ray)), "hipMalloc(rays)") &&
+              kd_hip_ok(hipMalloc(&d_out, (size_t)n * out_elem), "hipMalloc(results)") &&
+              kd_hip_ok(hipMalloc((void **)&d.count, (size_t)n * 4), "hipMalloc(count)") &&
+              (any || kd_hip_ok(hipMalloc((void **)&d.before, (size_t)n * 4), "hipMalloc(before)")) &&
+              kd_hip_ok(hipMalloc((void **)&d.prim, (size_t)n * k * 4), "hipMalloc(prim)") &&
+              kd_hip_ok(hipMalloc((void **)&d.instance, (size_t)n * k * 4), "hipMalloc(instance)") &&
+              kd_hip_ok(hipMemcpy(d_rays, rays, (size_t)n * sizeof(nnbvh_ray), hipMemcpyHostToDevice), "copy rays") &&
+              // the caller's entries beyond count stay as they were: start from them
+              kd_hip_ok(hipMemcpy(d.prim, c->prim, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy prim") &&
+              kd_hip_ok(hipMemcpy(d.instance, c->instance, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy instance");
+    KdWorkspace *w = ok ? kd_workspace_for(s, nullptr) : nullptr;
+    int rc = w ? NNBVH_OK : NNBVH_ERR_DEVICE;
+    if (rc == NNBVH_OK) {
+        KdBatch batch;
+        batch.any = any, batch.rays = d_rays, batch.n = n, batch.out = d_out, batch.hc = &d;
+        rc = kd_launch_batches(s, w, nullptr, &batch, 1);
+    }
+    if (rc == NNBVH_OK &&
+        !(kd_hip_ok(hipStreamSynchronize(nullptr), "kd trace") &&
+          kd_hip_ok(hipMemcpy(out, d_out, (size_t)n * out_elem, hipMemcpyDeviceToHost), "copy results") &&
+          kd_hip_ok(hipMemcpy(c->count, d.count, (size_t)n * 4, hipMemcpyDeviceToHost), "copy count") &&
+          (any || kd_hip_ok(hipMemcpy(c->before, d.before, (size_t)n * 4, hipMemcpyDeviceToHost), "copy before")) &&
+          kd_hip_ok(hipMemcpy(c->prim, d.prim, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy prim") &&
+          kd_hip_ok(hipMemcpy(c->instance, d.instance, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy instance")))
+        rc = NNBVH_ERR_DEVICE;
+    for (void *q : {d_rays, d_out, (void *)d.count, (void *)d.before, (void *)d.prim, (void *)d.instance})
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
+extern "C" {
+
+int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches, void *stream) {
+    return kd_trace_batches("kd_trace_batches_device", s, batches, n_batches, nullptr, false, stream);
+}
+
+int nnbvh_kd_trace_batches_candidates_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches,
+                                             const nnbvh_host_candidates *cands, void *stream) {
+    return kd_trace_batches("kd_trace_batches_candidates_device", s, batches, n_batches, cands, true, stream);
+}
+
+int nnbvh_kd_intersect_closest_candidates_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_hits,
+                                                 const nnbvh_host_candidates *c, void *stream) {
+    return kd_candidates_device("kd_intersect_closest_candidates_device", s, false, d_rays, n, d_hits, c, stream);
+}
+
+int nnbvh_kd_intersect_any_candidates_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_occluded,
+                                             const nnbvh_host_candidates *c, void *stream) {
+    return kd_candidates_device("kd_intersect_any_candidates_device", s, true, d_rays, n, d_occluded, c, stream);
+}
+
+int nnbvh_kd_intersect_closest_candidates(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits,
+                                          const nnbvh_host_candidates *c) {
+    return kd_candidates_host("kd_intersect_closest_candidates", s, false, rays, n, hits, c);
+}
+
+int nnbvh_kd_intersect_any_candidates(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, uint8_t *occluded,
+                                      const nnbvh_host_candidates *c) {
+    return kd_candidates_host("kd_intersect_any_candidates", s, true, rays, n, occluded, c);
 }
 
 int nnbvh_kd_intersect_closest(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits) {

@@ -8,6 +8,9 @@
 namespace nnbvh {
 
 void set_error(const std::string &msg);
+// what is wrong with a call's nnbvh_host_candidates (closest: before is an output too), or nullptr (capi_trace.cpp;
+// shared by the BVH and the kd-tree entry points)
+const char *candidates_fault(const nnbvh_host_candidates *c, bool closest);
 
 // ---- device data layout -----------------------------------
 // One 64-byte record per INTERIOR node, holding both children's boxes, so that one

@@ -144,6 +144,67 @@ class KdTreeAggregate:
                                                        ctypes.c_void_p(stream)),
               "nnbvh_kd_trace_batches_device")
 
+    # -- host-only primitives as candidates (include/nnbvh.h nnbvh_host_candidates; the BVHAggregate methods of the
+    # same names, with instance 0 in every entry and a primitive listed once however many leaves hold it) ----------
+    def intersect_with_host_candidates(self, rays, capacity=8):
+        """Closest hit that lists the host-only primitives each ray reached instead of voiding it.  Returns
+        (hits, cands) as BVHAggregate.intersect_with_host_candidates; merge with resolve_host_candidates."""
+        from .aggregate import _candidate_arrays, _pack_candidates
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        cnt, before, prim, inst = _candidate_arrays(len(rays), capacity)
+        c = _lib.HostCandidates(int(capacity), cnt.ctypes.data, before.ctypes.data, prim.ctypes.data, inst.ctypes.data)
+        check(_lib.lib().nnbvh_kd_intersect_closest_candidates(self._h, ptr(rays), len(rays), ptr(hits),
+                                                               ctypes.byref(c)),
+              "nnbvh_kd_intersect_closest_candidates")
+        return hits, _pack_candidates(cnt, before, prim, inst)
+
+    def intersect_p_with_host_candidates(self, rays, capacity=8):
+        """Any hit with candidates -> (occluded uint8, cands); cands["before"] is 0.  occluded 2 with count > 0: test
+        the candidates (resolve_host_candidates_any)."""
+        from .aggregate import _candidate_arrays, _pack_candidates
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        occ = np.zeros(len(rays), np.uint8)
+        cnt, before, prim, inst = _candidate_arrays(len(rays), capacity)
+        c = _lib.HostCandidates(int(capacity), cnt.ctypes.data, None, prim.ctypes.data, inst.ctypes.data)
+        check(_lib.lib().nnbvh_kd_intersect_any_candidates(self._h, ptr(rays), len(rays), ptr(occ), ctypes.byref(c)),
+              "nnbvh_kd_intersect_any_candidates")
+        return occ, _pack_candidates(cnt, before, prim, inst)
+
+    def intersect_candidates_device(self, d_rays, d_hits, n, capacity, d_count, d_before, d_prim, d_instance,
+                                    stream=0):
+        """intersect_device with candidates: device pointers int32[n] count / before, int32[n * capacity] prim /
+        instance (nnbvh_kd_intersect_closest_candidates_device)."""
+        c = _lib.HostCandidates(int(capacity), d_count, d_before, d_prim, d_instance)
+        check(_lib.lib().nnbvh_kd_intersect_closest_candidates_device(self._h, d_rays, n, d_hits, ctypes.byref(c),
+                                                                      stream),
+              "nnbvh_kd_intersect_closest_candidates_device")
+
+    def intersect_p_candidates_device(self, d_rays, d_occ, n, capacity, d_count, d_prim, d_instance, stream=0):
+        c = _lib.HostCandidates(int(capacity), d_count, None, d_prim, d_instance)
+        check(_lib.lib().nnbvh_kd_intersect_any_candidates_device(self._h, d_rays, n, d_occ, ctypes.byref(c), stream),
+              "nnbvh_kd_intersect_any_candidates_device")
+
+    def trace_batches_candidates_device(self, batches, candidates, stream=0):
+        """trace_batches_device with host candidates per batch (nnbvh_kd_trace_batches_candidates_device), ONE launch.
+        candidates[b]: None for a plain batch, else (capacity, d_count, d_before, d_prim, d_instance) device pointers
+        (d_before None for an "any" batch), filled as by intersect[_p]_candidates_device."""
+        assert len(candidates) == len(batches)
+        rec = np.zeros(len(batches), _lib.BATCH_DTYPE)
+        for k, b in enumerate(batches):
+            kind, d_rays, n, d_out = b[:4]
+            rec[k]["kind"] = {"closest": 0, "any": 1}[kind]
+            rec[k]["d_rays"], rec[k]["n"], rec[k]["d_out"] = d_rays or 0, n, d_out or 0
+            rec[k]["d_nodes_visited"] = (b[4] or 0) if len(b) > 4 else 0
+            rec[k]["d_prim_tests"] = (b[5] or 0) if len(b) > 5 else 0
+        cs = (_lib.HostCandidates * max(len(batches), 1))()
+        for k, c in enumerate(candidates):
+            if c is not None:
+                cs[k] = _lib.HostCandidates(int(c[0]), c[1], c[2], c[3], c[4])
+        check(_lib.lib().nnbvh_kd_trace_batches_candidates_device(self._h, ptr(rec) if len(rec) else None, len(rec),
+                                                                  cs, ctypes.c_void_p(stream)),
+              "nnbvh_kd_trace_batches_candidates_device")
+
 
 # ---- nss learned kd-trees ---------------------------------------------------------------------
 def prim_bounds_of(prims, verts):

@@ -188,8 +188,8 @@ def record_shadow(max_rays, shadow_queue, occluded, Ld, r_u, r_l, pixel_index, L
 
 class WavefrontAggregate:
     """IntersectClosest / IntersectShadow of wavefront/integrator.h:32-54 on one BVHAggregate or KdTreeAggregate
-    (a kd scene offers the five queue calls without candidates; IntersectShadowTr, IntersectOneRandom and the
-    *WithCandidates methods raise NNBVHError for it).
+    (a kd scene offers the five queue calls and the three *WithCandidates ones; IntersectShadowTr and
+    IntersectOneRandom raise NNBVHError for it).
 
     prim_class: optional uint8 per primitive id (nn_bvh_amd._lib.CLASS_*), what the reference
     reads off the hit's SurfaceInteraction when it decides the destination queues."""
@@ -313,15 +313,14 @@ class WavefrontAggregate:
         IntersectClosestItems routes them; the others go to needs_host only, their candidate-mode record in hits:
         resolve them (resolve_host_candidates), write the merged records back and enqueue them with
         enqueue_closest_items(index=needs_host)."""
-        self._bvh_only("IntersectClosestItemsWithCandidates")
         pc = self.prim_class
         soa, qrec, irec = ray_queue._wire(), _queues_record(queues), _items_record(items, needs_host)
         c = candidates._wire()
-        check(_lib.lib().nnbvh_wavefront_intersect_closest_items_candidates(
+        check(self._entry("intersect_closest_items_candidates")(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
             *_ptr_count(pc), hits.data_ptr(), ptr(qrec),
             ptr(irec), ctypes.byref(c), torch.cuda.current_stream(self.device).cuda_stream),
-            "nnbvh_wavefront_intersect_closest_items_candidates")
+            self._name("intersect_closest_items_candidates"))
         return hits
 
     def IntersectShadowWithCandidates(self, max_rays, shadow_queue, Ld, r_u, r_l, pixel_index, L, occluded,
@@ -329,13 +328,12 @@ class WavefrontAggregate:
         """IntersectShadow with host candidates (nnbvh_wavefront_intersect_shadow_candidates): occluded (required,
         uint8 [capacity]) gets 0 / 1 / 2; rays with 0 add to L, rays with 2 and count > 0 are the caller's to test
         (resolve_host_candidates_any) and to record with record_shadow."""
-        self._bvh_only("IntersectShadowWithCandidates")
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa, c = shadow_queue._wire(), candidates._wire()
-        check(_lib.lib().nnbvh_wavefront_intersect_shadow_candidates(
+        check(self._entry("intersect_shadow_candidates")(
             self.aggregate._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(), Ld.data_ptr(), r_u.data_ptr(),
             r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0], occluded.data_ptr(), ctypes.byref(c),
-            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_shadow_candidates")
+            torch.cuda.current_stream(self.device).cuda_stream), self._name("intersect_shadow_candidates"))
 
     def IntersectClosestAndShadowItemsWithCandidates(self, max_rays, ray_queue, shading_mesh, candidates, hits,
                                                      max_shadow_rays, shadow_queue, Ld, r_u, r_l, pixel_index, L,
@@ -343,19 +341,18 @@ class WavefrontAggregate:
                                                      **queues):
         """IntersectClosestItemsWithCandidates and IntersectShadowWithCandidates in ONE launch of the traversal
         kernel (nnbvh_wavefront_intersect_closest_and_shadow_items_candidates); same results as the two calls."""
-        self._bvh_only("IntersectClosestAndShadowItemsWithCandidates")
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         pc = self.prim_class
         soa, ssoa = ray_queue._wire(), shadow_queue._wire()
         qrec, irec = _queues_record(queues), _items_record(items, needs_host)
         c, sc = candidates._wire(), shadow_candidates._wire()
-        check(_lib.lib().nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
+        check(self._entry("intersect_closest_and_shadow_items_candidates")(
             self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), ray_queue.size.data_ptr(),
             *_ptr_count(pc), hits.data_ptr(), ptr(qrec),
             ptr(irec), ctypes.byref(c), int(max_shadow_rays), ptr(ssoa), shadow_queue.size.data_ptr(), Ld.data_ptr(),
             r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0], occluded.data_ptr(),
             ctypes.byref(sc), torch.cuda.current_stream(self.device).cuda_stream),
-            "nnbvh_wavefront_intersect_closest_and_shadow_items_candidates")
+            self._name("intersect_closest_and_shadow_items_candidates"))
         return hits
 
     def IntersectShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None):
