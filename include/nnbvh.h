@@ -785,6 +785,35 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes
                                                       const nnbvh_prim *prims, int n_prims, const float *verts,
                                                       int n_verts, const float bounds_min_max[6], const float *normals,
                                                       const float *uvs, const float *prim_alpha, int device);
+/* Primitives in, traceable kd scene out, and the tree never visits the host: primitive bounds, their union, the device
+ * builder of nnbvh_kd_build_create_gpu and the primitive records all run on `device` (kd_bake.hip).  The scene is the
+ * one nnbvh_kd_build_create_stable + nnbvh_kd_scene_create_with_attributes make from the same arguments: the four
+ * device arrays byte for byte (the sign of a +-0 split plane included), bounds, depth and every later result.  LEAF
+ * ORDER: as with nnbvh_kd_build_create_gpu, the primitives inside a multi-primitive leaf stand in std::stable_sort
+ * order, not in the libstdc++ std::sort order nnbvh_kd_build_create leaves (the order that reproduces a libstdc++
+ * build of the reference byte for byte); where coincident primitives tie at equal t the two scenes may name
+ * different ones, and an any-hit walk may stop after a different number of tests.  The primitive list is checked on the device before anything is read through it and fails
+ * with nnbvh_kd_build_create's messages; NULL / empty arrays, max_depth > 64 and the device number are refused before
+ * any device work.  prim_bounds: read (and uploaded) only where the list holds NNBVH_PRIM_HOST entries.  No CPU
+ * fallback: without a HIP device the call fails. */
+nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build(const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts,
+                                                const float *prim_bounds, int isect_cost, int traversal_cost,
+                                                float empty_bonus, int max_prims, int max_depth, int device);
+/* ... with the attribute arrays of nnbvh_kd_scene_create_with_attributes (each nullable; a kind whose arrays are
+ * missing stays the host's) */
+nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_attributes(const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                                int n_verts, const float *prim_bounds,
+                                                                const float *normals, const float *uvs,
+                                                                const float *prim_alpha, int isect_cost,
+                                                                int traversal_cost, float empty_bonus, int max_prims,
+                                                                int max_depth, int device);
+/* What a kd scene holds, whichever call created it.  info: n_nodes, n_indices, n_prims, depth, device bytes,
+ * has_host_prims, has_patches, has_attribute_slots.  read: `what` 0 = nodes (8 B each), 1 = primitiveIndices, 2 =
+ * primitive records (64 B each), 3 = attribute slots (96 B each, scenes that have them); synchronous; NNBVH_ERR_ARG
+ * when `bytes` is not the array's exact size. */
+int nnbvh_kd_scene_bounds(const nnbvh_kd_scene *s, float out_min_max[6]);
+int nnbvh_kd_scene_info(const nnbvh_kd_scene *s, int64_t out[8]);
+int nnbvh_kd_scene_read(const nnbvh_kd_scene *s, int what, void *out, size_t bytes);
 void nnbvh_kd_scene_destroy(nnbvh_kd_scene *s);
 /* host buffers (synchronous) */
 int nnbvh_kd_intersect_closest(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits);

@@ -548,6 +548,9 @@ class HipShadingMesh {
 // Primitive-shaped methods; batches as for HipBVHAggregate.
 class HipKdTreeAggregate {
   public:
+    // Builds on the HOST (nnbvh_kd_build_create): primitives inside multi-primitive leaves in libstdc++'s std::sort
+    // order — the constructor that reproduces the tree of a libstdc++ build of the reference exactly.  BuildOnDevice
+    // below is the fast route (crown: seconds here, a fraction of a second there).
     HipKdTreeAggregate(const std::vector<nnbvh_prim> &prims, const std::vector<float> &verts,
                        int isectCost = 5, int traversalCost = 1, float emptyBonus = 0.5f, int maxPrims = 1,
                        int maxDepth = -1, int device = 0, const std::vector<float> *primBounds = nullptr,
@@ -584,9 +587,31 @@ class HipKdTreeAggregate {
         if (!scene_) HipBVHAggregate::fatal("HipKdTreeAggregate: scene_create");
         note_patches(prims, nPrims);
     }
+    // Bounds, tree and primitive records made on the device (nnbvh_kd_scene_create_gpu_build_with_attributes): the
+    // same nodes as the building constructor's, with the primitives inside multi-primitive leaves in std::stable_sort
+    // order (the scene of nnbvh_kd_build_create_stable + the from-tree constructor, byte for byte).
+    static std::unique_ptr<HipKdTreeAggregate> BuildOnDevice(
+        const std::vector<nnbvh_prim> &prims, const std::vector<float> &verts, int isectCost = 5, int traversalCost = 1,
+        float emptyBonus = 0.5f, int maxPrims = 1, int maxDepth = -1, int device = 0,
+        const std::vector<float> *primBounds = nullptr, const std::vector<float> *normals = nullptr,
+        const std::vector<float> *uvs = nullptr, const std::vector<float> *primAlpha = nullptr) {
+        nnbvh_kd_scene *scene = nnbvh_kd_scene_create_gpu_build_with_attributes(
+            prims.data(), (int)prims.size(), verts.data(), (int)(verts.size() / 3),
+            primBounds ? primBounds->data() : nullptr, normals ? normals->data() : nullptr, uvs ? uvs->data() : nullptr,
+            primAlpha ? primAlpha->data() : nullptr, isectCost, traversalCost, emptyBonus, maxPrims, maxDepth, device);
+        if (!scene) {
+            HipBVHAggregate::fatal("HipKdTreeAggregate::BuildOnDevice");
+            return nullptr;
+        }
+        std::unique_ptr<HipKdTreeAggregate> agg(new HipKdTreeAggregate(scene));
+        agg->note_patches(prims.data(), (int)prims.size());
+        return agg;
+    }
     HipKdTreeAggregate(const HipKdTreeAggregate &) = delete;
     HipKdTreeAggregate &operator=(const HipKdTreeAggregate &) = delete;
     ~HipKdTreeAggregate() { nnbvh_kd_scene_destroy(scene_); }
+
+    nnbvh_kd_scene *handle() const { return scene_; }
 
     Bounds3f Bounds() const { return {{bounds_[0], bounds_[1], bounds_[2]}, {bounds_[3], bounds_[4], bounds_[5]}}; }
     std::optional<HitRecord> Intersect(const Ray &ray, float tMax = std::numeric_limits<float>::infinity(),
@@ -749,6 +774,7 @@ class HipKdTreeAggregate {
     }
 
   private:
+    explicit HipKdTreeAggregate(nnbvh_kd_scene *scene) : scene_(scene) { nnbvh_kd_scene_bounds(scene_, bounds_); }
     void note_patches(const nnbvh_prim *prims, int n) { detail::note_patch_ids(patchIds_, prims, n); }
     nnbvh_kd_scene *scene_ = nullptr;
     std::vector<int32_t> patchIds_;

@@ -93,6 +93,8 @@ EXPORTS = [
     "nnbvh_kd_trace_batches_candidates_device", "nnbvh_kd_wavefront_intersect_closest_items_candidates",
     "nnbvh_kd_wavefront_intersect_shadow_candidates",
     "nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates",
+    "nnbvh_kd_scene_create_gpu_build", "nnbvh_kd_scene_create_gpu_build_with_attributes", "nnbvh_kd_scene_bounds",
+    "nnbvh_kd_scene_info", "nnbvh_kd_scene_read",
 ]
 
 
@@ -262,6 +264,17 @@ def lib():
     L.nnbvh_kd_scene_create.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
     L.nnbvh_kd_scene_create_with_attributes.restype = vp
     L.nnbvh_kd_scene_create_with_attributes.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32]
+    L.nnbvh_kd_scene_create_gpu_build.restype = vp
+    L.nnbvh_kd_scene_create_gpu_build.argtypes = [vp, i32, vp, i32, vp, i32, i32, ctypes.c_float, i32, i32, i32]
+    L.nnbvh_kd_scene_create_gpu_build_with_attributes.restype = vp
+    L.nnbvh_kd_scene_create_gpu_build_with_attributes.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32,
+                                                                  ctypes.c_float, i32, i32, i32]
+    L.nnbvh_kd_scene_bounds.restype = i32
+    L.nnbvh_kd_scene_bounds.argtypes = [vp, vp]
+    L.nnbvh_kd_scene_info.restype = i32
+    L.nnbvh_kd_scene_info.argtypes = [vp, vp]
+    L.nnbvh_kd_scene_read.restype = i32
+    L.nnbvh_kd_scene_read.argtypes = [vp, i32, vp, ctypes.c_size_t]
     L.nnbvh_kd_scene_destroy.restype = None
     L.nnbvh_kd_scene_destroy.argtypes = [vp]
     L.nnbvh_kd_intersect_closest.restype = i32

@@ -187,6 +187,27 @@ struct nnbvh_kd_build {
     double build_ms[2] = {0, 0};  // device builder: on the device / incl. the download
 };
 
+// what can be wrong with one primitive, in the order kd_prepare checks it; nnbvh_kd_scene_create_gpu_build finds the
+// same faults on the device (kd_bake.hip) and reports them in these words
+static const char *const kPrimFaultText[] = {
+    nullptr,
+    "nnbvh_kd_build_create: host primitives need prim_bounds",
+    "nnbvh_kd_build_create: unsupported primitive kind (triangles, alpha-tested triangles, patches, host primitives)",
+    "nnbvh_kd_build_create: vertex index out of range",
+    "nnbvh_kd_build_create: non-finite vertex or primitive bounds",
+};
+static const char *const kDepthFaultText = "nnbvh_kd_build_create: max_depth above the traversal stack (64, aggregates.cpp:982)";
+
+// the depth limit of :808-809, or the caller's; false when the traversal stack cannot hold it
+static bool kd_resolve_max_depth(int n_prims, int *max_depth) {
+    if (*max_depth <= 0) *max_depth = (int)std::round(8 + 1.3f * log2_int((uint64_t)n_prims));  // :808-809
+    if (*max_depth > nnbvh::kMaxStack) {
+        nnbvh::set_error(kDepthFaultText);
+        return false;
+    }
+    return true;
+}
+
 // primitive bounds (Triangle::Bounds / BilinearPatch::Bounds / the caller's for host primitives), their union
 // and the depth limit of :808-809 — shared by the three builders
 static bool kd_prepare(const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts, const float *prim_bounds,
@@ -202,19 +223,19 @@ static bool kd_prepare(const nnbvh_prim *prims, int n_prims, const float *verts,
         KBox b;
         if (p.kind == NNBVH_PRIM_HOST) {
             if (!prim_bounds) {
-                nnbvh::set_error("nnbvh_kd_build_create: host primitives need prim_bounds");
+                nnbvh::set_error(kPrimFaultText[nnbvh::kKdHostNeedsBounds]);
                 return false;
             }
             std::memcpy(b.mn, prim_bounds + 6 * (size_t)i, 12);
             std::memcpy(b.mx, prim_bounds + 6 * (size_t)i + 3, 12);
         } else if (!nv) {
-            nnbvh::set_error("nnbvh_kd_build_create: unsupported primitive kind (triangles, alpha-tested triangles, patches, host primitives)");
+            nnbvh::set_error(kPrimFaultText[nnbvh::kKdBadKind]);
             return false;
         } else {
             const float *v[4] = {nullptr, nullptr, nullptr, nullptr};
             for (int k = 0; k < nv; ++k) {
                 if (p.v[k] < 0 || p.v[k] >= n_verts) {
-                    nnbvh::set_error("nnbvh_kd_build_create: vertex index out of range");
+                    nnbvh::set_error(kPrimFaultText[nnbvh::kKdBadVertexIndex]);
                     return false;
                 }
                 v[k] = verts + 3 * (size_t)p.v[k];
@@ -225,18 +246,13 @@ static bool kd_prepare(const nnbvh_prim *prims, int n_prims, const float *verts,
         }
         for (int k = 0; k < 3; ++k)
             if (!std::isfinite(b.mn[k]) || !std::isfinite(b.mx[k])) {
-                nnbvh::set_error("nnbvh_kd_build_create: non-finite vertex or primitive bounds");
+                nnbvh::set_error(kPrimFaultText[nnbvh::kKdNonFinite]);
                 return false;
             }
         *bounds = box_union(*bounds, b);
         (*primBounds)[(size_t)i] = b;
     }
-    if (*max_depth <= 0) *max_depth = (int)std::round(8 + 1.3f * log2_int((uint64_t)n_prims));  // :808-809
-    if (*max_depth > nnbvh::kMaxStack) {
-        nnbvh::set_error("nnbvh_kd_build_create: max_depth above the traversal stack (64, aggregates.cpp:982)");
-        return false;
-    }
-    return true;
+    return kd_resolve_max_depth(n_prims, max_depth);
 }
 
 static nnbvh_kd_build *kd_build_host(const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts,
@@ -310,6 +326,40 @@ nnbvh_kd_build *nnbvh_kd_build_create_gpu(const nnbvh_prim *prims, int n_prims, 
     out->build_ms[0] = r.device_ms;
     out->build_ms[1] = r.total_ms;
     return out;
+}
+
+nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_attributes(const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                                int n_verts, const float *prim_bounds,
+                                                                const float *normals, const float *uvs,
+                                                                const float *prim_alpha, int isect_cost,
+                                                                int traversal_cost, float empty_bonus, int max_prims,
+                                                                int max_depth, int device) {
+    // everything the host can judge, before any device call; the primitive list itself is judged on the device
+    if (!prims || !verts || n_prims <= 0 || n_verts <= 0) {
+        nnbvh::set_error("nnbvh_kd_scene_create_gpu_build: empty primitive or vertex array");
+        return nullptr;
+    }
+    if (!kd_resolve_max_depth(n_prims, &max_depth)) return nullptr;
+    int n_dev = 0;
+    if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
+        nnbvh::set_error("nnbvh_kd_scene_create_gpu_build: no usable HIP device (the device route has no CPU fallback)");
+        return nullptr;
+    }
+    const nnbvh::KdSceneInputs in{prims,      n_prims,        verts,     n_verts,   prim_bounds, normals, uvs,   prim_alpha,
+                                  isect_cost, traversal_cost, max_prims, max_depth, empty_bonus, device};
+    nnbvh::KdPrimFault fault = nnbvh::kKdPrimOk;
+    std::string err;
+    nnbvh_kd_scene *s = nnbvh::kd_scene_create_on_device(in, &fault, &err);
+    if (!s) nnbvh::set_error(fault != nnbvh::kKdPrimOk ? std::string(kPrimFaultText[fault]) : err);
+    return s;
+}
+
+nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build(const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts,
+                                                const float *prim_bounds, int isect_cost, int traversal_cost,
+                                                float empty_bonus, int max_prims, int max_depth, int device) {
+    return nnbvh_kd_scene_create_gpu_build_with_attributes(prims, n_prims, verts, n_verts, prim_bounds, nullptr, nullptr,
+                                                           nullptr, isect_cost, traversal_cost, empty_bonus, max_prims,
+                                                           max_depth, device);
 }
 
 int nnbvh_kd_build_timing(const nnbvh_kd_build *b, double out_ms[2]) {

@@ -41,6 +41,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "kd_build_gpu.h"
+#include "kd_device_util.h"
 
 namespace nnbvh {
 namespace {
@@ -73,12 +74,6 @@ struct DBuf {
         if (p) (void)hipFree(p);
     }
 };
-
-__device__ __forceinline__ unsigned ordered_bits(float f) {  // monotone float -> unsigned; -0 and +0 compare equal
-    unsigned u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct KdParamsBuild {
     int isectCost, traversalCost, maxPrims;
@@ -130,8 +125,8 @@ __global__ __launch_bounds__(kB) void k_make_edges(const Seg *segs, const int *l
     const float *b = pb + 6 * (long)list[r];
     const unsigned long long hi = (unsigned long long)s << 33;
     const long e = (long)g.edgeStart + 2 * j;
-    keys[e] = hi | ((unsigned long long)ordered_bits(b[g.axis]) << 1);           // Start
-    keys[e + 1] = hi | ((unsigned long long)ordered_bits(b[3 + g.axis]) << 1) | 1ull;  // End
+    keys[e] = hi | ((unsigned long long)kd_ordered_bits(b[g.axis]) << 1);           // Start
+    keys[e + 1] = hi | ((unsigned long long)kd_ordered_bits(b[3 + g.axis]) << 1) | 1ull;  // End
     vals[e] = 2u * (unsigned)r;
     vals[e + 1] = 2u * (unsigned)r + 1u;
     if (j == 0) best[s] = ~0ull;
@@ -140,15 +135,6 @@ __global__ __launch_bounds__(kB) void k_make_edges(const Seg *segs, const int *l
 __global__ __launch_bounds__(kB) void k_start_flags(const unsigned *vals, long n, int *flags) {
     const long i = (long)blockIdx.x * kB + threadIdx.x;
     if (i <= n) flags[i] = (i < n && !(vals[i] & 1u)) ? 1 : 0;
-}
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, off), hi = __shfl_xor((unsigned)(v >> 32), off);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
 }
 
 // the sweep of aggregates.cpp:905-935 for every edge at once
@@ -180,13 +166,13 @@ __global__ __launch_bounds__(kB) void k_costs(const Seg *segs, const unsigned lo
             const float eb = (nAbove == 0 || nBelow == 0) ? P.emptyBonus : 0;
             const float cost = P.traversalCost + P.isectCost * (1 - eb) * (pBelow * nBelow + pAbove * nAbove);
             if (cost < __builtin_inff())  // `cost < bestCost` with bestCost = inf at first; a NaN never wins
-                packed = ((unsigned long long)ordered_bits(cost) << 32) | (unsigned)local;
+                packed = ((unsigned long long)kd_ordered_bits(cost) << 32) | (unsigned)local;
         }
     }
     // one atomic per wavefront where the whole wavefront sweeps one segment
     const int s0 = __shfl(s, 0), s63 = __shfl(s, 63);
     if (s0 == s63 && s0 >= 0) {
-        const unsigned long long m = wave_min_u64(packed);
+        const unsigned long long m = kd_wave_min_u64(packed);
         if ((threadIdx.x & 63) == 0 && m != ~0ull) atomicMin(&best[s0], m);
     } else if (packed != ~0ull) {
         atomicMin(&best[s], packed);
@@ -421,27 +407,23 @@ inline int grid(long n) { return (int)((n + kB - 1) / kB); }
         }                                                             \
     } while (0)
 
-bool gpu_kd_build(const float *prim_bounds, int n_prims, const float bounds[6], int isect_cost, int traversal_cost,
-                  float empty_bonus, int max_prims, int max_depth, int device, KdGpuResult *out, std::string *error) {
-    const auto t0 = std::chrono::steady_clock::now();
+bool gpu_kd_build_device(const float *d_prim_bounds, int n_prims, const float bounds[6], int isect_cost,
+                         int traversal_cost, float empty_bonus, int max_prims, int max_depth, hipStream_t stream,
+                         KdGpuTree *out, std::string *error) {
     constexpr long kMaxRefs = 1L << 29;
     if (n_prims > kMaxRefs) {
         *error = "device kd build: more than 2^29 primitives";
         return false;
     }
-    KG_CHECK(hipSetDevice(device), "hipSetDevice");
-    hipStream_t stream = nullptr;
     const KdParamsBuild P{isect_cost, traversal_cost, max_prims, empty_bonus};
+    const float *const dPB = d_prim_bounds;
 
-    DBuf<float> dPB;
     DBuf<int> listA, listB, refSegA, refSegB, scanA, scanB, scanC, flagA, flagB, flagC, pool, poolNode;
     DBuf<Seg> segA, segB;
     DBuf<unsigned long long> keys, keysS, best;
     DBuf<unsigned> vals, valsS;
     DBuf<NodeRec> nodes;
     DBuf<char> tmp;
-    KG_ALLOC(dPB, (size_t)6 * n_prims, false);
-    KG_CHECK(hipMemcpyAsync(dPB.p, prim_bounds, (size_t)24 * n_prims, hipMemcpyHostToDevice, stream), "upload bounds");
     KG_ALLOC(listA, n_prims, false);
     KG_ALLOC(refSegA, n_prims, false);
     hipLaunchKernelGGL(k_iota, dim3(grid(n_prims)), dim3(kB), 0, stream, listA.p, n_prims);
@@ -500,7 +482,7 @@ bool gpu_kd_build(const float *prim_bounds, int n_prims, const float bounds[6], 
             KG_ALLOC(vals, nEdges, false);
             KG_ALLOC(valsS, nEdges, false);
             hipLaunchKernelGGL(k_make_edges, dim3(grid(nRefs)), dim3(kB), 0, stream, segs->p, list->p, refSeg->p, nRefs,
-                               dPB.p, keys.p, vals.p, best.p);
+                               dPB, keys.p, vals.p, best.p);
             int segBits = 1;
             while ((1ll << segBits) < nSeg) ++segBits;
             size_t sortBytes = 0;
@@ -518,9 +500,9 @@ bool gpu_kd_build(const float *prim_bounds, int n_prims, const float bounds[6], 
                 return false;
             }
             hipLaunchKernelGGL(k_costs, dim3(grid(nEdges)), dim3(kB), 0, stream, segs->p, keysS.p, valsS.p, scanB.p, nEdges,
-                               list->p, dPB.p, P, best.p);
+                               list->p, dPB, P, best.p);
             hipLaunchKernelGGL(k_decide, dim3(grid(nSeg + 1)), dim3(kB), 0, stream, segs->p, nSeg, best.p, valsS.p, list->p,
-                               dPB.p, attempt, P, flagA.p);
+                               dPB, attempt, P, flagA.p);
             if (!scan(flagA.p, scanA.p, (size_t)nSeg + 1)) {
                 *error = "device kd build: scan failed";
                 return false;
@@ -627,15 +609,50 @@ bool gpu_kd_build(const float *prim_bounds, int n_prims, const float bounds[6], 
                            dIdx.p);
     KG_CHECK(hipGetLastError(), "layout kernels");
     KG_CHECK(hipStreamSynchronize(stream), "sync");
-    out->device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    out->nodes.resize((size_t)nNodes);
-    out->prim_indices.resize((size_t)nIndices);
-    KG_CHECK(hipMemcpy(out->nodes.data(), dOut.p, (size_t)nNodes * sizeof(nnbvh_kd_node), hipMemcpyDeviceToHost), "download nodes");
-    if (nIndices > 0)
-        KG_CHECK(hipMemcpy(out->prim_indices.data(), dIdx.p, (size_t)nIndices * sizeof(int), hipMemcpyDeviceToHost),
-                 "download indices");
+    out->d_nodes = dOut.p;
+    out->d_indices = dIdx.p;
+    dOut.p = nullptr;  // now the caller's
+    dIdx.p = nullptr;
+    out->n_nodes = nNodes;
+    out->n_indices = nIndices;
     out->depth = (int)levelBase.size() - 1;
     out->levels = (int)levelBase.size();
+    return true;
+}
+
+bool gpu_kd_build(const float *prim_bounds, int n_prims, const float bounds[6], int isect_cost, int traversal_cost,
+                  float empty_bonus, int max_prims, int max_depth, int device, KdGpuResult *out, std::string *error) {
+    const auto t0 = std::chrono::steady_clock::now();
+    ScopedDevice guard(device);  // the caller's current device comes back on every return below
+    KG_CHECK(guard.status, "hipSetDevice");
+    struct Stream {  // a stream of the build's own: nothing here orders itself against the caller's NULL-stream work
+        hipStream_t s = nullptr;
+        ~Stream() {
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } own;
+    KG_CHECK(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+    hipStream_t stream = own.s;
+    KdGpuTree tree;
+    {
+        DBuf<float> dPB;  // freed before the download
+        KG_ALLOC(dPB, (size_t)6 * n_prims, false);
+        KG_CHECK(hipMemcpyAsync(dPB.p, prim_bounds, (size_t)24 * n_prims, hipMemcpyHostToDevice, stream), "upload bounds");
+        if (!gpu_kd_build_device(dPB.p, n_prims, bounds, isect_cost, traversal_cost, empty_bonus, max_prims, max_depth, stream,
+                                 &tree, error))
+            return false;
+    }
+    out->device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    out->nodes.resize((size_t)tree.n_nodes);
+    out->prim_indices.resize((size_t)tree.n_indices);
+    KG_CHECK(hipMemcpyAsync(out->nodes.data(), tree.d_nodes, (size_t)tree.n_nodes * sizeof(nnbvh_kd_node), hipMemcpyDeviceToHost,
+                            stream), "download nodes");
+    if (tree.n_indices > 0)
+        KG_CHECK(hipMemcpyAsync(out->prim_indices.data(), tree.d_indices, (size_t)tree.n_indices * sizeof(int),
+                                hipMemcpyDeviceToHost, stream), "download indices");
+    KG_CHECK(hipStreamSynchronize(stream), "download");
+    out->depth = tree.depth;
+    out->levels = tree.levels;
     out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return true;
 }

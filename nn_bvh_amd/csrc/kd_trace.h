@@ -47,6 +47,7 @@ struct nnbvh_kd_scene {
     int has_host_prims = 0;
     int has_patches = 0;
     int fits32 = 0;  // nodes (8 B), primitive records (64 B) and indices (4 B) each below 4 GiB
+    int n_nodes = 0, n_indices = 0, n_prims = 0;  // what nnbvh_kd_scene_info / _read report (d_indices holds max(n_indices, 1))
     float bounds[6];
     uint2 *d_nodes = nullptr;
     int32_t *d_indices = nullptr;

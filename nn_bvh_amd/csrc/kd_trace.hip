@@ -602,22 +602,6 @@ static bool kd_grow(void **ptr, size_t *have, size_t need, const char *what) {
     return true;
 }
 
-// shapes.cpp:176-177 with the reference's float32 operations (see bvh_capi.cpp)
-static float kd_dop_host(float a, float b, float c, float d) {
-    float cd = c * d;
-    float diff = std::fma(a, b, -cd);
-    float err = std::fma(-c, d, cd);
-    return diff + err;
-}
-static bool kd_triangle_is_degenerate(const float *p0, const float *p1, const float *p2) {
-    float v[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-    float w[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-    float cx = kd_dop_host(v[1], w[2], v[2], w[1]);
-    float cy = kd_dop_host(v[2], w[0], v[0], w[2]);
-    float cz = kd_dop_host(v[0], w[1], v[1], w[0]);
-    return cx * cx + cy * cy + cz * cz == 0.0f;
-}
-
 }  // namespace nnbvh
 
 using namespace nnbvh;
@@ -935,6 +919,9 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes
     s->depth = max_depth;
     s->has_host_prims = has_host ? 1 : 0;
     s->has_patches = has_patch ? 1 : 0;
+    s->n_nodes = n_nodes;
+    s->n_indices = n_indices;
+    s->n_prims = n_prims;
     s->fits32 = (n_nodes < (1 << 29) && n_prims < (1 << 26) - 1 && n_indices < (1 << 30)) ? 1 : 0;
     std::memcpy(s->bounds, bounds_min_max, 24);
     const size_t ni = (size_t)std::max(n_indices, 1);

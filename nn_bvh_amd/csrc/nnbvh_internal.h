@@ -63,11 +63,11 @@ constexpr uint32_t kPrimAnimated = 128u;
 constexpr uint32_t kPrimSmooth = 256u;
 constexpr uint32_t kPrimUV = 512u;  // alpha-tested patch of a mesh with (u, v) coordinates
 constexpr int kAnimStride = 76;  // floats per entry of the animation table (layout: anim_math.h)
-inline bool is_triangle_kind(int kind) {
+constexpr bool is_triangle_kind(int kind) {
     return kind == NNBVH_PRIM_TRIANGLE || kind == NNBVH_PRIM_ALPHA_TRIANGLE || kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED ||
            kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH || kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED;
 }
-inline bool is_smooth_alpha_kind(int kind) {
+constexpr bool is_smooth_alpha_kind(int kind) {
     return kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH || kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED;
 }
 // alpha-tested bilinear patches: kind = 8 + flipped + 2 * smooth + 4 * uv
@@ -76,10 +76,34 @@ constexpr bool is_smooth_alpha_patch_kind(int kind) { return is_alpha_patch_kind
 constexpr bool is_flipped_alpha_patch_kind(int kind) { return is_alpha_patch_kind(kind) && ((kind - NNBVH_PRIM_ALPHA_PATCH) & 1); }
 constexpr bool is_uv_alpha_patch_kind(int kind) { return is_alpha_patch_kind(kind) && ((kind - NNBVH_PRIM_ALPHA_PATCH) & 4); }
 constexpr int alpha_patch_slots(int kind) { return 4 + (is_smooth_alpha_patch_kind(kind) ? 4 : 0) + (is_uv_alpha_patch_kind(kind) ? 2 : 0); }
-inline bool is_flat_alpha_kind(int kind) {
+constexpr bool is_flat_alpha_kind(int kind) {
     return kind == NNBVH_PRIM_ALPHA_TRIANGLE || kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED;
 }
 
 constexpr int kMaxStack = 64;  // the reference's nodesToVisit[64], aggregates.cpp:538
+
+// The degenerate-triangle test of shapes.cpp:176-177, LengthSquared(Cross(p2 - p0, p1 - p0)) == 0 with
+// DifferenceOfProducts (util/math.h:569-575), in the reference's float32 operations: ONE function for the host bake
+// (kd_trace.hip) and the device bake (kd_bake.hip) of the kd primitive records, so that both set kPrimDegenerate from
+// the same bits.  The fused multiply-adds are explicit; the build's -ffp-contract=off forms no others.
+#if defined(__HIPCC__)
+#define NNBVH_HD __host__ __device__
+#else
+#define NNBVH_HD
+#endif
+NNBVH_HD inline float kd_difference_of_products(float a, float b, float c, float d) {
+    const float cd = c * d;
+    const float diff = __builtin_fmaf(a, b, -cd);
+    const float err = __builtin_fmaf(-c, d, cd);
+    return diff + err;
+}
+NNBVH_HD inline bool kd_triangle_is_degenerate(const float *p0, const float *p1, const float *p2) {
+    const float v[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+    const float w[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+    const float cx = kd_difference_of_products(v[1], w[2], v[2], w[1]);
+    const float cy = kd_difference_of_products(v[2], w[0], v[0], w[2]);
+    const float cz = kd_difference_of_products(v[0], w[1], v[1], w[0]);
+    return cx * cx + cy * cy + cz * cz == 0.0f;
+}
 
 }  // namespace nnbvh

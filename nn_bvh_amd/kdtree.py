@@ -81,6 +81,54 @@ class KdTreeAggregate:
         t = build_kd_tree(prims, verts, **kw)
         return cls.from_tree(t.nodes, t.prim_indices, prims, verts, t.bounds, device, normals, uvs, prim_alpha)
 
+    @classmethod
+    def build_on_device(cls, prims, verts, device=0, normals=None, uvs=None, prim_alpha=None, prim_bounds=None,
+                        isect_cost=5, traversal_cost=1, empty_bonus=0.5, max_prims=1, max_depth=-1):
+        """nnbvh_kd_scene_create_gpu_build_with_attributes: primitive bounds, the tree and the primitive records are
+        made on the device and stay there.  The scene of build_kd_tree(where="host_stable") + from_tree, byte for byte:
+        inside multi-primitive leaves the primitives stand in std::stable_sort order, not in the libstdc++ std::sort
+        order of build() (the leaf-order note of build_kd_tree).  prim_bounds: read for host-only primitives only."""
+        prims = np.ascontiguousarray(prims, PRIM_DTYPE)
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(len(verts), 3)
+        uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(len(verts), 2)
+        pa = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(len(prims))
+        pb = None if prim_bounds is None else np.ascontiguousarray(prim_bounds, np.float32).reshape(len(prims), 6)
+        opt = lambda a: ptr(a) if a is not None and a.size else None  # noqa: E731
+        L = _lib.lib()
+        h = L.nnbvh_kd_scene_create_gpu_build_with_attributes(
+            opt(prims), len(prims), opt(verts), len(verts), opt(pb), opt(nrm), opt(uv), opt(pa), isect_cost,
+            traversal_cost, ctypes.c_float(empty_bonus), max_prims, max_depth, device)
+        if not h:
+            raise _lib.NNBVHError(f"nnbvh_kd_scene_create_gpu_build failed: {_lib.last_error()}")
+        bounds = np.zeros(6, np.float32)
+        agg = cls(h, bounds, device)
+        check(L.nnbvh_kd_scene_bounds(h, ptr(bounds)), "nnbvh_kd_scene_bounds")
+        return agg
+
+    INFO_KEYS = ("n_nodes", "n_indices", "n_prims", "depth", "device_bytes", "has_host_prims", "has_patches",
+                 "has_attribute_slots")
+
+    def info(self):
+        """nnbvh_kd_scene_info as a dict (INFO_KEYS)."""
+        out = np.zeros(8, np.int64)
+        check(_lib.lib().nnbvh_kd_scene_info(self._h, ptr(out)), "nnbvh_kd_scene_info")
+        return dict(zip(self.INFO_KEYS, (int(v) for v in out)))
+
+    def read(self, what):
+        """nnbvh_kd_scene_read: the scene's device arrays as numpy arrays.  what: 0 / "nodes" (KD_NODE_DTYPE), 1 /
+        "prim_indices" (int32), 2 / "prims" (float32 [n, 16]: the 64-B records), 3 / "attributes" (float32 [n, 24]:
+        the 96-B slots; empty in scenes without them)."""
+        what = {"nodes": 0, "prim_indices": 1, "prims": 2, "attributes": 3}.get(what, what)
+        i = self.info()
+        rows, dtype, width = [(i["n_nodes"], KD_NODE_DTYPE, 1), (i["n_indices"], np.int32, 1),
+                              (i["n_prims"], np.float32, 16),
+                              (i["n_prims"] if i["has_attribute_slots"] else 0, np.float32, 24)][what]
+        out = np.zeros(rows * width, dtype)
+        check(_lib.lib().nnbvh_kd_scene_read(self._h, what, ptr(out) if out.size else None, out.nbytes),
+              "nnbvh_kd_scene_read")
+        return out if width == 1 else out.reshape(-1, width)
+
     def close(self):
         if self._h:
             _lib.lib().nnbvh_kd_scene_destroy(self._h)

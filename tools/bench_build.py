@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Build-time comparison on the GPU box: host SAH (threaded), host HLBVH and GPU HLBVH
 (nnbvh_build_create_gpu) per scene blob; the GPU tree is checked byte-for-byte against the host
-HLBVH.  Prints one JSON object.  usage: tools/bench_build.py [scene ...]"""
+HLBVH.  Prints one JSON object.  usage: tools/bench_build.py [scene ...]
+
+kd section (--kd: both sections, --kd-only: this one alone; scenes default to bathroom and crown; --kd-out=PATH
+writes the table, default profiles/kd_device_scene.txt): creating a kd-tree scene, in one process alternated
+A B A B ..., medians with min..max:
+  A  build_kd_tree(where="gpu") + KdTreeAggregate.from_tree   the tree downloaded, validated and baked on the host
+  B  KdTreeAggregate.build_on_device                          bounds, tree and records made and kept on the device
+  C  build_kd_tree(where="host") + from_tree, once, for the record
+and the peak of the device memory in use during one B (sampled from a second thread) beside what the scene keeps."""
 import json
 import os
 import sys
@@ -13,9 +21,100 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 from nn_bvh_amd import BVHAggregate, build_tree, build_tree_gpu, make_prims, scene  # noqa: E402
 
-names = sys.argv[1:] or ["killeroos", "coffee_maker", "bathroom", "crown"]
+
+
+def kd_section(names, out_path, rounds=5):
+    import threading
+
+    import torch
+
+    from nn_bvh_amd.kdtree import KdTreeAggregate, build_kd_tree
+    lines, result = [], {}
+
+    def stats(ms):
+        return f"{np.median(ms):9.1f} ms  ({min(ms):.1f} .. {max(ms):.1f})"
+
+    for name in names:
+        verts, tris, source = scene.load_scene(name)
+        prims = make_prims(tris)
+
+        def route_a():
+            t = build_kd_tree(prims, verts, where="gpu")
+            return KdTreeAggregate.from_tree(t.nodes, t.prim_indices, prims, verts, t.bounds), t.build_ms
+
+        def route_b():
+            return KdTreeAggregate.build_on_device(prims, verts), None
+
+        for fn in (route_a, route_b):  # first-call costs (module load, allocator) outside the timing
+            fn()[0].close()
+        a_ms, b_ms, a_dev = [], [], []
+        for _ in range(rounds):
+            for fn, ms in ((route_a, a_ms), (route_b, b_ms)):
+                t0 = time.perf_counter()
+                agg, build_ms = fn()
+                ms.append((time.perf_counter() - t0) * 1e3)
+                if build_ms:
+                    a_dev.append(build_ms)
+                info = agg.info()
+                agg.close()
+        # peak device memory of one B: bytes in use on the device, sampled while the call runs
+        torch.cuda.synchronize()
+        base = torch.cuda.mem_get_info()[0]
+        low, stop = [base], threading.Event()
+
+        def sample():
+            while not stop.is_set():
+                low[0] = min(low[0], torch.cuda.mem_get_info()[0])
+                time.sleep(0.0005)
+
+        th = threading.Thread(target=sample)
+        th.start()
+        agg, _ = route_b()
+        stop.set()
+        th.join()
+        kept = base - torch.cuda.mem_get_info()[0]
+        agg.close()
+        t0 = time.perf_counter()
+        t = build_kd_tree(prims, verts, where="host")
+        c_build = (time.perf_counter() - t0) * 1e3
+        KdTreeAggregate.from_tree(t.nodes, t.prim_indices, prims, verts, t.bounds).close()
+        c_ms = (time.perf_counter() - t0) * 1e3
+        gain = np.median(a_ms) - np.median(b_ms)
+        spread = max(max(a_ms) - min(a_ms), max(b_ms) - min(b_ms))
+        verdict = ("B ahead of A by more than either spread" if gain > spread else
+                   "B behind A by more than either spread" if -gain > spread else "B and A within the spread")
+        lines += [f"{name}: {source}",
+                  f"  {len(tris)} triangles, {info['n_nodes']} nodes, {info['n_indices']} indices, depth {info['depth']}",
+                  f"  A  device build + download + host bake   {stats(a_ms)}",
+                  f"     of which the builder itself           {stats([m[0] for m in a_dev])} on the device, "
+                  f"{np.median([m[1] for m in a_dev]):.1f} ms with the download",
+                  f"  B  build_on_device                       {stats(b_ms)}",
+                  f"  C  host build + host bake (once)         {c_ms:9.1f} ms  (build {c_build:.1f})",
+                  f"  median A - median B = {gain:.1f} ms, larger spread {spread:.1f} ms: {verdict}",
+                  f"  B device memory: peak {(base - low[0]) / 2**20:.0f} MiB in use during the call (sampled), "
+                  f"{kept / 2**20:.0f} MiB kept (scene arrays {info['device_bytes'] / 2**20:.0f} MiB)", ""]
+        result[name] = {"a_ms": a_ms, "b_ms": b_ms, "c_ms": c_ms, "peak_bytes": int(base - low[0]),
+                        "scene_bytes": info["device_bytes"], "verdict": verdict}
+    text = "\n".join([f"kd scene creation, {rounds} alternated rounds per scene, one process; {torch.cuda.get_device_name(0)}",
+                      ""] + lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(text)
+    return result
+
+
+flags = [a for a in sys.argv[1:] if a.startswith("--")]
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+kd_out = os.path.join(ROOT, "profiles", "kd_device_scene.txt")
+for f in flags:
+    if f.startswith("--kd-out="):
+        kd_out = f.split("=", 1)[1]
+names = args or ["killeroos", "coffee_maker", "bathroom", "crown"]
 out = {}
-for name in names:
+if "--kd" in flags or "--kd-only" in flags:
+    out["kd_scene_create"] = kd_section(args or ["bathroom", "crown"], kd_out)
+for name in ([] if "--kd-only" in flags else names):
     if not os.path.exists(os.path.join(ROOT, "data", name + ".npz")):
         continue
     verts, tris = scene.load_blob(name)
