@@ -144,6 +144,15 @@ typedef struct nnbvh_instance {
     int32_t n_nodes;
 } nnbvh_instance;
 
+/* A placement of an object definition, for scenes whose trees are built on the device
+ * (nnbvh_scene_create_instanced_gpu_build): the matrices as in nnbvh_instance, and which object it places. */
+typedef struct nnbvh_placement {
+    float render_from_prim[12];
+    float prim_from_render[12];
+    int32_t object; /* index of the object definition */
+    int32_t pad;
+} nnbvh_placement;
+
 typedef struct nnbvh_scene nnbvh_scene;
 typedef struct nnbvh_build nnbvh_build;
 
@@ -244,7 +253,8 @@ void nnbvh_transform_bounds(const float render_from_prim[12], const float in_min
  * (nnbvh_build_create_gpu's builders), baked there into the traversal layout, and never visits the
  * host.  Same tree and same traversal results as nnbvh_build_create_with_bounds(...,
  * split_method) + nnbvh_scene_create.  split_method NNBVH_SPLIT_SAH or NNBVH_SPLIT_HLBVH;
- * triangles, bilinear patches and host-only primitives (instances: nnbvh_scene_create_instanced). */
+ * triangles, bilinear patches and host-only primitives (instances: nnbvh_scene_create_instanced_gpu_build below,
+ * or nnbvh_scene_create_instanced with host-built trees). */
 nnbvh_scene *nnbvh_scene_create_gpu_build(const nnbvh_prim *prims, int n_prims, const float *verts,
                                           int n_verts, const float *prim_bounds,
                                           int max_prims_in_node, int split_method, int device);
@@ -254,6 +264,39 @@ nnbvh_scene *nnbvh_scene_create_gpu_build_with_attributes(const nnbvh_prim *prim
                                                           int n_verts, const float *prim_bounds, const float *normals,
                                                           const float *uvs, const float *prim_alpha,
                                                           int max_prims_in_node, int split_method, int device);
+/* A two-level scene (object instances, scene.cpp:1521-1577: one BVHAggregate per object definition, one
+ * TransformedPrimitive / AnimatedPrimitive per placement) entirely on the device: every object's tree, then the
+ * top-level tree, are built there, put into one numbering and baked; no tree visits the host.  The device arrays are
+ * byte for byte those of nnbvh_scene_create_instanced_with_attributes on host-built trees of the same split_method
+ * (nodes [top, object 0, object 1, ...], primitives [top in leaf order, object 0 in leaf order, ...]).
+ *   prims[n_prims]            the caller's order: [0, n_top_prims) is the top-level list (triangles, patches, the
+ *                             alpha kinds, NNBVH_PRIM_HOST and NNBVH_PRIM_INSTANCE entries; for an instance entry
+ *                             v[0] is the placement index and id the caller's), then the object definitions one
+ *                             after another (no instance entries: nested instances are not supported)
+ *   object_first[n_objects+1] object k is prims[object_first[k], object_first[k+1]); object_first[0] == n_top_prims,
+ *                             the last entry == n_prims, no object is empty.  Every object is built and baked, named
+ *                             by a placement or not
+ *   normals, uvs, prim_alpha  nullable, as nnbvh_scene_create_gpu_build_with_attributes (prim_alpha per entry of
+ *                             prims in the CALLER's order)
+ *   prim_bounds               nullable, 6 floats per entry of prims: read for NNBVH_PRIM_HOST entries and for instance
+ *                             entries whose placement is actually_animated (AnimatedTransform::MotionBounds stays the
+ *                             caller's).  A static instance's bounds (Transform::operator()(Bounds3f) of the child's
+ *                             root box, nnbvh_transform_bounds bit for bit) are computed on the device and the
+ *                             caller's values are ignored
+ *   placements[n_placements]  at least one; animated[n_placements] nullable
+ *   split_method              NNBVH_SPLIT_SAH or NNBVH_SPLIT_HLBVH
+ * NULL + nnbvh_last_error() for every argument fault (null or empty arrays, a malformed object_first, a placement's
+ * object or an instance entry's v[0] out of range, an instance entry inside an object, vertex indices, a missing
+ * prim_bounds or attribute array, an animated placement with an empty time range, a bad split method: all checked
+ * on the host before a device is looked at), for no usable device, for non-finite vertices, and for a scene deeper
+ * (top depth + deepest child + 1) than the 64-entry traversal stack. */
+nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(const nnbvh_prim *prims, int n_prims, int n_top_prims,
+                                                    const int32_t *object_first, int n_objects, const float *verts,
+                                                    int n_verts, const float *normals, const float *uvs,
+                                                    const float *prim_alpha, const float *prim_bounds,
+                                                    const nnbvh_placement *placements, int n_placements,
+                                                    const nnbvh_animated_transform *animated, int max_prims_in_node,
+                                                    int split_method, int device);
 /* nnbvh_scene_create with the meshes' per-vertex shading normals (3 floats per vertex, indexed like `verts`;
  * TriangleMesh::n, util/mesh.h:48): read for NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH[_FLIPPED] primitives only, whose
  * three normals are baked into the primitive stream.  normals = NULL is nnbvh_scene_create. */
@@ -272,6 +315,11 @@ int nnbvh_scene_bounds(const nnbvh_scene *s, float out_min_max[6]);
 /* what the baked device layout looks like: [0]=interior records, [1]=prim-stream slots,
  * [2]=tree depth, [3]=device bytes, [4]=persistent grid blocks, [5]=LDS stack window */
 int nnbvh_scene_info(const nnbvh_scene *s, int64_t out[6]);
+/* the baked device arrays of any scene, however it was created, copied to the host (tests, tools): what 0 = interior
+ * records (info[0] * 64 bytes), 1 = primitive stream (info[1] * 16 bytes), 2 = animation table (304 bytes per instance;
+ * scenes created with one).  Synchronous.  NNBVH_ERR_ARG for a NULL scene or buffer, an unknown `what`, or a `bytes`
+ * that is not the array's size. */
+int nnbvh_scene_read(const nnbvh_scene *s, int what, void *out, size_t bytes);
 
 /* ---- traversal, host buffers (synchronous; copies in and out) ----------------------
  * What Integrator::Intersect / IntersectP callers (cpu/integrators.cpp:296-313) hand over.  The batch is

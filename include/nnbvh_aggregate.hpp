@@ -247,6 +247,44 @@ class HipBVHAggregate {
         note_patches(orderedPrims, nPrims);
     }
 
+    // A two-level scene (one BVHAggregate per object definition, one TransformedPrimitive / AnimatedPrimitive per
+    // placement, scene.cpp:1521-1577) with every tree built AND baked on the device
+    // (nnbvh_scene_create_instanced_gpu_build): the scene of host-built trees, byte for byte.  topPrims: what lives
+    // directly in the top-level tree (may be empty); one instance entry per placement is generated behind them (kind
+    // NNBVH_PRIM_INSTANCE, v[0] = j, id = topPrims.size() + j).  primBounds / primAlpha: per entry of the list
+    // [topPrims, the generated instance entries, objects[0], objects[1], ...]; primBounds is read for host-only
+    // entries and the instances of animated placements only.  splitMethod "sah" or "hlbvh".
+    static std::unique_ptr<HipBVHAggregate> BuildTwoLevelOnDevice(
+        const std::vector<nnbvh_prim> &topPrims, const std::vector<float> &verts,
+        const std::vector<std::vector<nnbvh_prim>> &objects, const std::vector<nnbvh_placement> &placements,
+        int maxPrimsInNode = 4, const std::string &splitMethod = "sah", int device = 0,
+        const std::vector<nnbvh_animated_transform> *animated = nullptr, const std::vector<float> *primBounds = nullptr,
+        const std::vector<float> *normals = nullptr, const std::vector<float> *primAlpha = nullptr,
+        const std::vector<float> *uvs = nullptr) {
+        std::vector<nnbvh_prim> prims(topPrims);
+        for (size_t j = 0; j < placements.size(); ++j)
+            prims.push_back(nnbvh_prim{NNBVH_PRIM_INSTANCE, (int32_t)(topPrims.size() + j), {(int32_t)j, 0, 0, 0}});
+        const int nTop = (int)prims.size();
+        std::vector<int32_t> first{nTop};
+        for (const std::vector<nnbvh_prim> &o : objects) {
+            prims.insert(prims.end(), o.begin(), o.end());
+            first.push_back((int32_t)prims.size());
+        }
+        const int method = splitMethod == "sah" ? NNBVH_SPLIT_SAH : splitMethod == "hlbvh" ? NNBVH_SPLIT_HLBVH : -1;
+        nnbvh_scene *scene = nnbvh_scene_create_instanced_gpu_build(
+            prims.data(), (int)prims.size(), nTop, first.data(), (int)objects.size(), verts.data(),
+            (int)(verts.size() / 3), normals ? normals->data() : nullptr, uvs ? uvs->data() : nullptr,
+            primAlpha ? primAlpha->data() : nullptr, primBounds ? primBounds->data() : nullptr, placements.data(),
+            (int)placements.size(), animated ? animated->data() : nullptr, maxPrimsInNode, method, device);
+        if (!scene) {
+            fatal("HipBVHAggregate::BuildTwoLevelOnDevice");
+            return nullptr;
+        }
+        std::unique_ptr<HipBVHAggregate> agg(new HipBVHAggregate(scene));
+        agg->note_patches(prims.data(), (int)prims.size());
+        return agg;
+    }
+
     HipBVHAggregate(const HipBVHAggregate &) = delete;
     HipBVHAggregate &operator=(const HipBVHAggregate &) = delete;
     ~HipBVHAggregate() { nnbvh_scene_destroy(scene_); }
@@ -501,6 +539,7 @@ class HipBVHAggregate {
     nnbvh_scene *handle() const { return scene_; }
 
   private:
+    explicit HipBVHAggregate(nnbvh_scene *scene) : scene_(scene) {}
     static nnbvh_ray wire(const Ray &ray, float tMax) {
         return nnbvh_ray{{ray.o.x, ray.o.y, ray.o.z}, tMax, {ray.d.x, ray.d.y, ray.d.z}, ray.time};
     }

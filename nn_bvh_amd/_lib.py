@@ -16,6 +16,8 @@ PRIM_DTYPE = np.dtype([("kind", "<i4"), ("id", "<i4"), ("v", "<i4", 4)])
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmax", "<f4"), ("d", "<f4", 3), ("time", "<f4")])
 INSTANCE_DTYPE = np.dtype([("render_from_prim", "<f4", 12), ("prim_from_render", "<f4", 12),
                            ("root", "<i4"), ("n_nodes", "<i4")])
+PLACEMENT_DTYPE = np.dtype([("render_from_prim", "<f4", 12), ("prim_from_render", "<f4", 12),
+                            ("object", "<i4"), ("pad", "<i4")])
 ANIMATED_DTYPE = np.dtype([("start_from", "<f4", 16), ("start_inv", "<f4", 16), ("end_from", "<f4", 16),
                            ("end_inv", "<f4", 16), ("T", "<f4", (2, 3)), ("R", "<f4", (2, 4)), ("S", "<f4", (2, 16)),
                            ("start_time", "<f4"), ("end_time", "<f4"), ("actually_animated", "<i4"), ("pad", "<i4")])
@@ -94,7 +96,7 @@ EXPORTS = [
     "nnbvh_kd_wavefront_intersect_shadow_candidates",
     "nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates",
     "nnbvh_kd_scene_create_gpu_build", "nnbvh_kd_scene_create_gpu_build_with_attributes", "nnbvh_kd_scene_bounds",
-    "nnbvh_kd_scene_info", "nnbvh_kd_scene_read",
+    "nnbvh_kd_scene_info", "nnbvh_kd_scene_read", "nnbvh_scene_create_instanced_gpu_build", "nnbvh_scene_read",
 ]
 
 
@@ -273,6 +275,11 @@ def lib():
     L.nnbvh_kd_scene_bounds.argtypes = [vp, vp]
     L.nnbvh_kd_scene_info.restype = i32
     L.nnbvh_kd_scene_info.argtypes = [vp, vp]
+    L.nnbvh_scene_create_instanced_gpu_build.restype = vp
+    L.nnbvh_scene_create_instanced_gpu_build.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp,
+                                                         i32, i32, i32]
+    L.nnbvh_scene_read.restype = i32
+    L.nnbvh_scene_read.argtypes = [vp, i32, vp, ctypes.c_size_t]
     L.nnbvh_kd_scene_read.restype = i32
     L.nnbvh_kd_scene_read.argtypes = [vp, i32, vp, ctypes.c_size_t]
     L.nnbvh_kd_scene_destroy.restype = None

@@ -160,6 +160,86 @@ class BVHAggregate:
         self._read_info()
         return self
 
+    @staticmethod
+    def two_level_entries(top_prims, objects, placements):
+        """The primitive list nnbvh_scene_create_instanced_gpu_build takes, made of assemble_two_level's inputs:
+        the top-level primitives, the instance entries assemble_two_level generates (kind 2, v[0] = j,
+        id = n_top + j), then the objects one after another.  Returns (prims, n_top_prims, object_first)."""
+        top_prims = np.asarray(top_prims, PRIM_DTYPE).reshape(-1)
+        n_top = len(top_prims)
+        inst_prims = np.zeros(len(placements), PRIM_DTYPE)
+        inst_prims["kind"] = 2
+        inst_prims["v"][:, 0] = np.arange(len(placements))
+        inst_prims["id"] = n_top + np.arange(len(placements))
+        objects = [np.asarray(o, PRIM_DTYPE).reshape(-1) for o in objects]
+        prims = np.ascontiguousarray(np.concatenate([top_prims, inst_prims] + objects), PRIM_DTYPE)
+        first = n_top + len(placements) + np.concatenate([[0], np.cumsum([len(o) for o in objects])])
+        return prims, n_top + len(placements), np.ascontiguousarray(first, np.int32)
+
+    @classmethod
+    def build_two_level_on_device(cls, top_prims, verts, objects, placements, max_prims_in_node=4, split_method="sah",
+                                  animated=None, prim_bounds=None, normals=None, prim_alpha=None, uvs=None, device=0):
+        """A two-level scene (instancing.assemble_two_level's inputs: top-level primitives, object definitions,
+        placements (object index, render_from_prim 3x4, prim_from_render 3x4)) with every tree built AND baked on
+        the GPU (nnbvh_scene_create_instanced_gpu_build); byte-identical device arrays and the same results as
+        assemble_two_level + from_tree.  prim_bounds / prim_alpha: per entry of two_level_entries(...)[0] (the top
+        list, the generated instance entries, then the objects); prim_bounds is read for host-only primitives and
+        the instances of animated placements only.  animated: ANIMATED_DTYPE, one per placement.  `nodes` /
+        `ordered_prims` are not available on this object; `instances` is the placement table in the form
+        ShadingMesh.set_instances takes (root / n_nodes zero: the trees live on the device)."""
+        if split_method not in ("sah", "hlbvh"):
+            raise NNBVHError(f'GPU build supports "sah" and "hlbvh", not "{split_method}"')
+        self = cls.__new__(cls)
+        L = _lib.lib()
+        prims, n_top, first = cls.two_level_entries(top_prims, objects, placements)
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+        table = np.zeros(len(placements), _lib.PLACEMENT_DTYPE)
+        self.instances = np.zeros(len(placements), _lib.INSTANCE_DTYPE)
+        for j, (k, m, mi) in enumerate(placements):
+            table[j]["render_from_prim"] = np.asarray(m, np.float32).reshape(12)
+            table[j]["prim_from_render"] = np.asarray(mi, np.float32).reshape(12)
+            table[j]["object"] = int(k)
+        self.instances["render_from_prim"] = table["render_from_prim"]
+        self.instances["prim_from_render"] = table["prim_from_render"]
+        self.nodes = self.ordered_prims = None
+        self.verts = verts
+        self.device = int(device)
+        self.animated = None if animated is None else np.ascontiguousarray(animated, _lib.ANIMATED_DTYPE)
+        if self.animated is not None and len(self.animated) != len(placements):
+            raise NNBVHError(f"animated has {len(self.animated)} entries for {len(placements)} placements")
+        pb = None if prim_bounds is None else np.ascontiguousarray(prim_bounds, np.float32).reshape(len(prims), 6)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(len(verts), 3)
+        pa = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(len(prims))
+        uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(len(verts), 2)
+        opt = lambda a: ptr(a) if a is not None and len(a) else None  # noqa: E731
+        self._h = L.nnbvh_scene_create_instanced_gpu_build(
+            opt(prims), len(prims), n_top, ptr(first), len(objects), opt(verts), len(verts), opt(nrm), opt(uv), opt(pa),
+            opt(pb), opt(table), len(table), opt(self.animated), int(max_prims_in_node), SPLIT_METHODS[split_method],
+            self.device)
+        if not self._h:
+            raise NNBVHError("nnbvh_scene_create_instanced_gpu_build: " + _lib.last_error())
+        self._read_info()
+        return self
+
+    def read(self, what):
+        """The baked device arrays (nnbvh_scene_read) as bytes-exact numpy arrays: 0 = interior records
+        (uint32 [n, 16]), 1 = primitive stream (uint32 [slots, 4]), 2 = animation table (float32 [instances, 76];
+        None for scenes without one)."""
+        if what not in (0, 1, 2):
+            raise NNBVHError(f"read: unknown array {what!r} (0 interior records, 1 primitive stream, 2 animation table)")
+        if what == 2:
+            n = 0 if getattr(self, "animated", None) is None else len(self.animated)
+            if n == 0:
+                return None
+            out = np.zeros((n, 76), np.float32)
+        elif what == 0:
+            out = np.zeros((self.info["interior_records"], 16), np.uint32)
+        else:
+            out = np.zeros((self.info["prim_slots"], 4), np.uint32)
+        if out.nbytes:
+            check(_lib.lib().nnbvh_scene_read(self._h, int(what), ptr(out), out.nbytes), "nnbvh_scene_read")
+        return out
+
     def _read_info(self):
         info = np.zeros(6, np.int64)
         check(_lib.lib().nnbvh_scene_info(self._h, ptr(info)), "nnbvh_scene_info")

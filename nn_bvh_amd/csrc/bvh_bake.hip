@@ -2,7 +2,9 @@
 // a device-resident LinearBVHNode array + leaf-ordered primitive table: the counterpart of the
 // host baking in bvh_capi.cpp (create_scene), bit for bit, for scenes of triangles, bilinear
 // patches and host-only primitives.  With the device builders (bvh_build_gpu.hip) a scene goes
-// from triangles to traceable without its tree ever visiting the host.
+// from triangles to traceable without its tree ever visiting the host.  Two-level scenes
+// (capi_two_level.cpp) add the bounds an instance presents to the top-level builder, the child trees'
+// move into the scene's numbering, and the instance-aware form of the bake (InstanceBake).
 //
 // Four streaming passes over 24-32-B records plus three prefix sums; HBM-bound.
 #include <hip/hip_runtime.h>
@@ -21,8 +23,10 @@ namespace {
 
 constexpr int kBk = 256;
 
+// instances != 0 is the instance-aware form (two-level scenes, bake_instanced_on_device): an instance entry takes 6
+// slots; otherwise it is refused (flag 2)
 __global__ __launch_bounds__(kBk) void k_bake_slot_counts(const nnbvh_prim *__restrict__ prims, int n,
-                                                         int *__restrict__ slots, int *flags) {
+                                                         int *__restrict__ slots, int *flags, int instances) {
     const int i = blockIdx.x * kBk + threadIdx.x;
     if (i >= n) return;
     const int kind = prims[i].kind;
@@ -40,18 +44,21 @@ __global__ __launch_bounds__(kBk) void k_bake_slot_counts(const nnbvh_prim *__re
         c = alpha_patch_slots(kind);  // four slots of vertex normals and / or two of (u, v) follow the patch's
         atomicOr(flags, 4 | 8 | 32 | (is_smooth_alpha_patch_kind(kind) ? 16 : 0) | (is_uv_alpha_patch_kind(kind) ? 64 : 0));
     }
+    else if (kind == NNBVH_PRIM_INSTANCE && instances) c = 6;
     else if (kind != NNBVH_PRIM_TRIANGLE) atomicOr(flags, 2);  // instances are not baked here
     slots[i] = c;
 }
 
 __global__ __launch_bounds__(kBk) void k_bake_node_flags(const nnbvh_linear_node *__restrict__ nodes, int n,
                                                         int *__restrict__ interior,
-                                                        unsigned char *__restrict__ leafLast) {
+                                                        unsigned char *__restrict__ leafLast,
+                                                        const unsigned char *__restrict__ unnamed) {
     const int i = blockIdx.x * kBk + threadIdx.x;
     if (i >= n) return;
     const nnbvh_linear_node nd = nodes[i];
     interior[i] = nd.nprims == 0 ? 1 : 0;
-    if (nd.nprims != 0) leafLast[nd.offset + nd.nprims - 1] = 1;
+    // (two-level scenes: create_scene walks, and marks, only the trees a placement names)
+    if (nd.nprims != 0 && !(unnamed && unnamed[i])) leafLast[nd.offset + nd.nprims - 1] = 1;
 }
 
 // DifferenceOfProducts (util/math.h:569-575) and the degenerate-triangle test of shapes.cpp:176-177
@@ -62,6 +69,10 @@ __device__ __forceinline__ float bake_dop(float a, float b, float c, float d) {
     return diff + err;
 }
 
+__device__ __forceinline__ int bake_ref(const nnbvh_linear_node &nd, int index, const int *ord, const int *slotOf) {
+    return nd.nprims == 0 ? ord[index] : ~slotOf[nd.offset];
+}
+
 __global__ __launch_bounds__(kBk) void k_bake_stream(const nnbvh_prim *__restrict__ prims, int n,
                                                     const float *__restrict__ verts,
                                                     const float *__restrict__ normals,
@@ -69,12 +80,32 @@ __global__ __launch_bounds__(kBk) void k_bake_stream(const nnbvh_prim *__restric
                                                     const float *__restrict__ primAlpha,
                                                     const int *__restrict__ slotOf,
                                                     const unsigned char *__restrict__ leafLast,
-                                                    float4 *__restrict__ stream) {
+                                                    float4 *__restrict__ stream,
+                                                    const nnbvh_linear_node *__restrict__ nodes,
+                                                    const int *__restrict__ ord, InstanceBake inst) {
     const int i = blockIdx.x * kBk + threadIdx.x;
     if (i >= n) return;
     const nnbvh_prim p = prims[i];
     float4 *s = stream + slotOf[i];
     unsigned flags = leafLast[i] ? kPrimLast : 0u;
+    if (p.kind == NNBVH_PRIM_INSTANCE) {
+        // the 6-slot record of create_scene (bvh_capi.cpp): the child root's box, the placement index, the flags,
+        // prim_from_render and the child root's ref.  Reached in the instance-aware form only (k_bake_slot_counts),
+        // with p.v[0] and the placement's object range-checked by the caller
+        const nnbvh_placement *pl = inst.d_placements + p.v[0];
+        const int r = inst.d_object_root[pl->object];
+        const nnbvh_linear_node root = nodes[r];
+        flags |= kPrimInstance;
+        if (inst.d_animated && inst.d_animated[p.v[0]]) flags |= kPrimAnimated;
+        const float *m = pl->prim_from_render;
+        s[0] = make_float4(root.pmin[0], root.pmin[1], root.pmin[2], __int_as_float(p.v[0]));
+        s[1] = make_float4(root.pmax[0], root.pmax[1], root.pmax[2], __uint_as_float(flags));
+        s[2] = make_float4(m[0], m[1], m[2], m[3]);
+        s[3] = make_float4(m[4], m[5], m[6], m[7]);
+        s[4] = make_float4(m[8], m[9], m[10], m[11]);
+        s[5] = make_float4(__int_as_float(bake_ref(root, r, ord, slotOf)), 0, 0, 0);
+        return;
+    }
     if (p.kind == NNBVH_PRIM_HOST) {
         flags |= kPrimHost;
         s[0] = make_float4(0, 0, 0, __int_as_float(p.id));
@@ -126,10 +157,6 @@ __global__ __launch_bounds__(kBk) void k_bake_stream(const nnbvh_prim *__restric
     if (nv == 4) s[3] = make_float4(v[3][0], v[3][1], v[3][2], 0);
 }
 
-__device__ __forceinline__ int bake_ref(const nnbvh_linear_node &nd, int index, const int *ord, const int *slotOf) {
-    return nd.nprims == 0 ? ord[index] : ~slotOf[nd.offset];
-}
-
 __global__ __launch_bounds__(kBk) void k_bake_wide(const nnbvh_linear_node *__restrict__ nodes, int n,
                                                   const int *__restrict__ ord, const int *__restrict__ slotOf,
                                                   float4 *__restrict__ wide) {
@@ -146,8 +173,57 @@ __global__ __launch_bounds__(kBk) void k_bake_wide(const nnbvh_linear_node *__re
                        __int_as_float((int)nd.axis), __int_as_float(0));
 }
 
+// ---- two-level scenes -------------------------------------------------------------------------------------------
+// TransformedPrimitive::Bounds (cpu/primitive.h:94): one lane per top-level entry; an instance entry of a static
+// placement gets render_from_prim applied to its child's root box (transform_bounds, nnbvh_internal.h: the host's
+// nnbvh_transform_bounds bit for bit).  Other entries keep what the caller's prim_bounds said.
+__global__ __launch_bounds__(kBk) void k_instance_bounds(const nnbvh_prim *__restrict__ topPrims, int nTop,
+                                                        const nnbvh_placement *__restrict__ placements,
+                                                        const unsigned char *__restrict__ animated,
+                                                        const nnbvh_linear_node *__restrict__ childNodes,
+                                                        const int *__restrict__ childBase,
+                                                        float *__restrict__ bounds) {
+    const int i = blockIdx.x * kBk + threadIdx.x;
+    if (i >= nTop) return;
+    const nnbvh_prim p = topPrims[i];
+    if (p.kind != NNBVH_PRIM_INSTANCE) return;
+    if (animated && animated[p.v[0]]) return;  // MotionBounds: the caller's
+    const nnbvh_placement *pl = placements + p.v[0];
+    const nnbvh_linear_node root = childNodes[childBase[pl->object]];
+    const float in[6] = {root.pmin[0], root.pmin[1], root.pmin[2], root.pmax[0], root.pmax[1], root.pmax[2]};
+    float m[12], out[6];
+    for (int k = 0; k < 12; ++k) m[k] = pl->render_from_prim[k];
+    transform_bounds(m, in, out);
+    for (int k = 0; k < 6; ++k) bounds[6 * (long)i + k] = out[k];
+}
+
+// The child trees, built one after another into childNodes (tree k at childBase[k], offsets relative to itself), put
+// behind the top tree in the scene's numbering: an interior node's second child moves by the tree's place in the node
+// array, a leaf's first primitive by the object's place in the primitive array.
+__global__ __launch_bounds__(kBk) void k_rebase_children(const nnbvh_linear_node *__restrict__ childNodes, int nChild,
+                                                        const int *__restrict__ childBase,
+                                                        const int *__restrict__ objectFirst, int nObjects,
+                                                        int nTopNodes, nnbvh_linear_node *__restrict__ out,
+                                                        int *__restrict__ objectRoot,
+                                                        const unsigned char *__restrict__ objectNamed,
+                                                        unsigned char *__restrict__ nodeUnnamed) {
+    const int i = blockIdx.x * kBk + threadIdx.x;
+    if (i < nObjects) objectRoot[i] = nTopNodes + childBase[i];
+    if (i >= nChild) return;
+    int lo = 0, hi = nObjects - 1;  // the last tree with childBase <= i
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (childBase[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    nnbvh_linear_node nd = childNodes[i];
+    nd.offset += nd.nprims == 0 ? nTopNodes + childBase[lo] : objectFirst[lo];
+    out[nTopNodes + i] = nd;
+    nodeUnnamed[nTopNodes + i] = objectNamed[lo] ? 0 : 1;
+}
+
 struct Scratch {
-    void *ptrs[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void *ptrs[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // (bake_on_device asks for 7)
     int n = 0;
     void *get(size_t bytes) {
         void *p = nullptr;
@@ -184,14 +260,38 @@ __global__ __launch_bounds__(kBk) void k_gather_alpha_restore_ids(nnbvh_prim *__
         }                                                                               \
     } while (0)
 
+bool instance_bounds_on_device(const void *d_top_prims, int n_top, const nnbvh_placement *d_placements,
+                               const unsigned char *d_animated, const void *d_child_nodes, const int *d_child_base,
+                               float *d_bounds, void *stream, std::string *error) {
+    hipLaunchKernelGGL(k_instance_bounds, dim3((n_top + kBk - 1) / kBk), dim3(kBk), 0, (hipStream_t)stream,
+                       (const nnbvh_prim *)d_top_prims, n_top, d_placements, d_animated,
+                       (const nnbvh_linear_node *)d_child_nodes, d_child_base, d_bounds);
+    BK_CHECK(hipGetLastError(), "instance bounds");
+    return true;
+}
+
+bool rebase_children_on_device(const void *d_child_nodes, int n_child_nodes, const int *d_child_base,
+                               const int *d_object_first, int n_objects, int n_top_nodes, void *d_nodes_out,
+                               int *d_object_root, const unsigned char *d_object_named, unsigned char *d_node_unnamed,
+                               void *stream, std::string *error) {
+    BK_CHECK(hipMemsetAsync(d_node_unnamed, 0, (size_t)n_top_nodes, (hipStream_t)stream), "memset");
+    const int n = std::max(n_child_nodes, n_objects);
+    hipLaunchKernelGGL(k_rebase_children, dim3((n + kBk - 1) / kBk), dim3(kBk), 0, (hipStream_t)stream,
+                       (const nnbvh_linear_node *)d_child_nodes, n_child_nodes, d_child_base, d_object_first, n_objects,
+                       n_top_nodes, (nnbvh_linear_node *)d_nodes_out, d_object_root, d_object_named, d_node_unnamed);
+    BK_CHECK(hipGetLastError(), "rebase child trees");
+    return true;
+}
+
 bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int n_prims, const void *d_verts_,
                     int device, BakedScene *out, std::string *error, const void *d_normals_, const void *d_prim_alpha_,
-                    const void *d_uvs_) {
+                    const void *d_uvs_, const InstanceBake *instances, void *stream_) {
     const auto *dNodes = (const nnbvh_linear_node *)d_nodes_;
     const auto *dPrims = (const nnbvh_prim *)d_prims_;
     const auto *dVerts = (const float *)d_verts_;
     BK_CHECK(hipSetDevice(device), "hipSetDevice");
-    hipStream_t stream = nullptr;
+    hipStream_t stream = (hipStream_t)stream_;
+    const InstanceBake inst = instances ? *instances : InstanceBake();
     Scratch sc;
     int *dSlots = (int *)sc.get(((size_t)n_prims + 1) * sizeof(int));
     int *dSlotOf = (int *)sc.get(((size_t)n_prims + 1) * sizeof(int));
@@ -213,8 +313,8 @@ bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int
     BK_CHECK(hipMemsetAsync(dLeafLast, 0, (size_t)n_prims, stream), "memset");
     BK_CHECK(hipMemsetAsync(dFlags, 0, sizeof(int), stream), "memset");
     const int gp = (n_prims + kBk - 1) / kBk, gn = (n_nodes + kBk - 1) / kBk;
-    hipLaunchKernelGGL(k_bake_slot_counts, dim3(gp), dim3(kBk), 0, stream, dPrims, n_prims, dSlots, dFlags);
-    hipLaunchKernelGGL(k_bake_node_flags, dim3(gn), dim3(kBk), 0, stream, dNodes, n_nodes, dInterior, dLeafLast);
+    hipLaunchKernelGGL(k_bake_slot_counts, dim3(gp), dim3(kBk), 0, stream, dPrims, n_prims, dSlots, dFlags, instances ? 1 : 0);
+    hipLaunchKernelGGL(k_bake_node_flags, dim3(gn), dim3(kBk), 0, stream, dNodes, n_nodes, dInterior, dLeafLast, inst.d_node_unnamed);
     BK_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dSlots, dSlotOf, 0, (size_t)n_prims + 1, rocprim::plus<int>(), stream),
              "scan slots");
     BK_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dInterior, dOrd, 0, (size_t)n_nodes + 1, rocprim::plus<int>(), stream),
@@ -258,7 +358,7 @@ bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int
     dStream = (char *)dWide + wideBytes;
     BK_CHECK(hipMemsetAsync((char *)dStream + (size_t)nSlots * 16, 0, 64, stream), "memset");
     hipLaunchKernelGGL(k_bake_stream, dim3(gp), dim3(kBk), 0, stream, dPrims, n_prims, dVerts, (const float *)d_normals_, (const float *)d_uvs_, (const float *)d_prim_alpha_, dSlotOf, dLeafLast,
-                       (float4 *)dStream);
+                       (float4 *)dStream, dNodes, dOrd, inst);
     hipLaunchKernelGGL(k_bake_wide, dim3(gn), dim3(kBk), 0, stream, dNodes, n_nodes, dOrd, dSlotOf, (float4 *)dWide);
     int rootSlot = 0;
     if (root.nprims != 0)

@@ -49,9 +49,43 @@ bool gpu_hlbvh(const nnbvh_prim *prims, int n_prims, const float *verts, int n_v
 bool gpu_sah(const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts, const float *prim_bounds,
              int max_prims_in_node, int device, GpuBuildResult *out, std::string *error);
 
+// Device memory handed from one build to the next: a block a build gives back serves the next request it is
+// large enough for (the smallest such block), so a sequence of builds on ONE stream allocates for its largest
+// member only.  clear() frees everything.
+struct ScratchPool {
+    struct Block {
+        void *p;
+        size_t bytes;
+        bool used;
+    };
+    std::vector<Block> blocks;
+    void *take(size_t bytes);  // null: hipMalloc failed
+    void give(void *p);
+    void clear();
+    ~ScratchPool() { clear(); }
+};
+
+// The builders' cores: input that is already on the device (the current one), output left there.  gpu_hlbvh /
+// gpu_sah are an upload (and, without keep_on_device, a download) around them.  out: d_nodes, d_ordered,
+// total_nodes, depth, ms[1..3] and the counts.
+struct DeviceBuildInput {
+    const nnbvh_prim *d_prims = nullptr;
+    int n_prims = 0;
+    const float *d_verts = nullptr;
+    int n_verts = 0;
+    const float *d_prim_bounds = nullptr;  // 6 floats per primitive, or null (as prim_bounds above)
+    int max_prims_in_node = 4;
+    void *stream = nullptr;  // hipStream_t (this header is also read by host-only builds)
+    ScratchPool *pool = nullptr;               // nullable: scratch comes from and goes back to it
+    nnbvh_linear_node *d_nodes_out = nullptr;  // nullable: room for 2 * n_prims - 1 nodes; else hipMalloc'ed, the caller's
+    nnbvh_prim *d_ordered_out = nullptr;       // nullable: room for n_prims primitives; else likewise
+};
+bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error);
+bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error);
+
 // Device-side counterpart of nnbvh_scene_create's baking (bvh_capi.cpp): the 64-B "both children"
 // records and the 16-B-slot primitive stream, straight from device-resident build output.  Triangles,
-// bilinear patches and host-only primitives (no instances).
+// bilinear patches and host-only primitives; instance entries with an InstanceBake (two-level scenes).
 struct BakedScene {
     void *d_wide = nullptr, *d_prims = nullptr;  // float4 arrays, owned by the caller afterwards
     int n_interior = 0;
@@ -64,9 +98,33 @@ struct BakedScene {
 };
 // d_normals: per-vertex shading normals (3 floats, indexed like the vertices) or null; read for
 // NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH primitives only
+// instances: null refuses NNBVH_PRIM_INSTANCE entries (flat scenes); else the instance-aware form for two-level
+// scenes, d_nodes = [top tree, child trees] in one numbering.  stream: a hipStream_t, null = the default stream.
+struct InstanceBake {
+    const nnbvh_placement *d_placements = nullptr;  // v[0] of an instance entry indexes this (the caller has checked it)
+    const int *d_object_root = nullptr;             // [n_objects] node index of each object's root (placement.object indexes it)
+    const unsigned char *d_animated = nullptr;      // nullable, [n_placements]: 1 = kPrimAnimated
+    // [n_nodes]: 1 = a node of an object no placement names.  The host route (create_scene) walks only the trees that
+    // placements name, so only their leaves mark a last primitive; such an object is baked, and never reached
+    const unsigned char *d_node_unnamed = nullptr;
+};
 bool bake_on_device(const void *d_nodes, int n_nodes, const void *d_ordered_prims, int n_prims, const void *d_verts,
                     int device, BakedScene *out, std::string *error, const void *d_normals = nullptr,
-                    const void *d_prim_alpha = nullptr, const void *d_uvs = nullptr);
+                    const void *d_prim_alpha = nullptr, const void *d_uvs = nullptr,
+                    const InstanceBake *instances = nullptr, void *stream = nullptr);
+
+// Two-level scenes on the device (bvh_bake.hip).  instance_bounds: d_bounds[6 i .. 6 i + 5] of every top-level entry i
+// that is an instance of a static placement becomes Transform::operator()(Bounds3f) of its child's root box
+// (d_child_nodes[d_child_base[object]]).  rebase_children: the child trees copied behind the n_top_nodes nodes of
+// d_nodes_out with their offsets moved into the scene's numbering; d_object_root[k] = n_top_nodes + d_child_base[k];
+// d_node_unnamed[i] (one per node of d_nodes_out) = 1 for the nodes of objects with d_object_named[k] == 0.
+bool instance_bounds_on_device(const void *d_top_prims, int n_top, const nnbvh_placement *d_placements,
+                               const unsigned char *d_animated, const void *d_child_nodes, const int *d_child_base,
+                               float *d_bounds, void *stream, std::string *error);
+bool rebase_children_on_device(const void *d_child_nodes, int n_child_nodes, const int *d_child_base,
+                               const int *d_object_first, int n_objects, int n_top_nodes, void *d_nodes_out,
+                               int *d_object_root, const unsigned char *d_object_named, unsigned char *d_node_unnamed,
+                               void *stream, std::string *error);
 
 // d_ordered: leaf-ordered nnbvh_prim[n_prims] of a build that ran with ids = positions in the caller's array;
 // gathers prim_alpha into that order (*d_alpha_out, hipMalloc'ed, the caller's to free) and restores caller_ids

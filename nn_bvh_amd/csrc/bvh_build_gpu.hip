@@ -458,15 +458,19 @@ __global__ __launch_bounds__(kB) void k_scatter_nodes(const int *__restrict__ in
 }
 
 // ---------------------------------------------------------------------------------------------------------
-struct DevMem {  // frees everything it handed out
+struct DevMem {  // frees everything it handed out (with a pool: hands it back for the next build)
     std::vector<void *> ptrs;
     std::string *error;
     bool ok = true;
+    ScratchPool *pool = nullptr;
     template <typename T>
     T *get(size_t count) {
         void *p = nullptr;
         if (!ok) return nullptr;
-        if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        if (pool) p = pool->take(bytes);
+        else if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr;
+        if (!p) {
             ok = false;
             *error = "gpu build: hipMalloc failed";
             return nullptr;
@@ -479,8 +483,11 @@ struct DevMem {  // frees everything it handed out
             if (q == p) q = nullptr;
     }
     ~DevMem() {
-        for (void *p : ptrs)
-            if (p) (void)hipFree(p);
+        for (void *p : ptrs) {
+            if (!p) continue;
+            if (pool) pool->give(p);
+            else (void)hipFree(p);
+        }
     }
 };
 
@@ -505,25 +512,115 @@ int grid_all(long n) { return (int)std::max<long>(1, (n + kB - 1) / kB); }
         }                                                            \
     } while (0)
 
+void *ScratchPool::take(size_t bytes) {
+    Block *best = nullptr;
+    for (Block &b : blocks)
+        if (!b.used && b.bytes >= bytes && (!best || b.bytes < best->bytes)) best = &b;
+    if (best) {
+        best->used = true;
+        return best->p;
+    }
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    blocks.push_back(Block{p, bytes, true});
+    return p;
+}
+
+void ScratchPool::give(void *p) {
+    for (Block &b : blocks)
+        if (b.p == p) b.used = false;
+}
+
+void ScratchPool::clear() {
+    for (Block &b : blocks) (void)hipFree(b.p);
+    blocks.clear();
+}
+
+namespace {
+
+// upload of a wrapper's host arrays (the device-resident cores below take it from there)
+struct Uploaded {
+    nnbvh_prim *prims = nullptr;
+    float *verts = nullptr, *bounds = nullptr;
+};
+bool upload_build_input(DevMem &mem, const nnbvh_prim *prims, int n, const float *verts, int n_verts,
+                        const float *prim_bounds, Uploaded *up, std::string *error) {
+    up->prims = mem.get<nnbvh_prim>(n);
+    up->verts = mem.get<float>(3 * (size_t)n_verts);
+    up->bounds = prim_bounds ? mem.get<float>(6 * (size_t)n) : nullptr;
+    if (!mem.ok) return false;
+    GB_CHECK(hipMemcpyAsync(up->prims, prims, (size_t)n * sizeof(nnbvh_prim), hipMemcpyHostToDevice, nullptr), "copy prims");
+    GB_CHECK(hipMemcpyAsync(up->verts, verts, 3 * (size_t)n_verts * sizeof(float), hipMemcpyHostToDevice, nullptr), "copy verts");
+    if (up->bounds)
+        GB_CHECK(hipMemcpyAsync(up->bounds, prim_bounds, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, nullptr), "copy bounds");
+    GB_CHECK(hipStreamSynchronize(nullptr), "sync after upload");
+    return true;
+}
+
+// what the wrappers do with a core's device-resident result: hand it over, or download and free it
+bool finish_build(DevMem &mem, const Uploaded &up, int n, GpuBuildResult *out, std::string *error) {
+    if (out->keep_on_device) {
+        out->d_verts = up.verts;
+        mem.release(up.verts);
+        return true;
+    }
+    out->nodes.resize((size_t)out->total_nodes);
+    out->ordered.resize((size_t)n);
+    hipError_t e = hipMemcpy(out->nodes.data(), out->d_nodes, out->nodes.size() * sizeof(nnbvh_linear_node), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        e = hipMemcpy(out->ordered.data(), out->d_ordered, out->ordered.size() * sizeof(nnbvh_prim), hipMemcpyDeviceToHost);
+    (void)hipFree(out->d_nodes);
+    (void)hipFree(out->d_ordered);
+    out->d_nodes = out->d_ordered = nullptr;
+    GB_CHECK(e, "read nodes / ordered prims");
+    return true;
+}
+
+struct RestoreDevice {
+    int d;
+    ~RestoreDevice() { (void)hipSetDevice(d); }
+};
+
+}  // namespace
+
 bool gpu_hlbvh(const nnbvh_prim *prims, int n, const float *verts, int n_verts,
                const float *prim_bounds, int max_prims_in_node, int device, GpuBuildResult *out,
                std::string *error) {
     int prev = 0;
     GB_CHECK(hipGetDevice(&prev), "hipGetDevice");
     GB_CHECK(hipSetDevice(device), "hipSetDevice");
-    struct Restore {
-        int d;
-        ~Restore() { (void)hipSetDevice(d); }
-    } restore{prev};
-    const int maxPrims = std::min(255, max_prims_in_node);  // aggregates.cpp:142
-    hipStream_t stream = nullptr;
+    RestoreDevice restore{prev};
     DevMem mem;
     mem.error = error;
+    auto t0 = std::chrono::steady_clock::now();
+    Uploaded up;
+    if (!upload_build_input(mem, prims, n, verts, n_verts, prim_bounds, &up, error)) return false;
+    out->ms[0] = ms_since(t0);
+    DeviceBuildInput in;
+    in.d_prims = up.prims;
+    in.n_prims = n;
+    in.d_verts = up.verts;
+    in.n_verts = n_verts;
+    in.d_prim_bounds = up.bounds;
+    in.max_prims_in_node = max_prims_in_node;
+    if (!gpu_hlbvh_device(in, out, error)) return false;
+    t0 = std::chrono::steady_clock::now();
+    const bool ok = finish_build(mem, up, n, out, error);
+    out->ms[4] = ms_since(t0);
+    return ok;
+}
+
+bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error) {
+    const int n = in.n_prims, n_verts = in.n_verts;
+    const nnbvh_prim *dPrims = in.d_prims;
+    const float *dVerts = in.d_verts, *dCaller = in.d_prim_bounds;
+    const int maxPrims = std::min(255, in.max_prims_in_node);  // aggregates.cpp:142
+    hipStream_t stream = (hipStream_t)in.stream;
+    DevMem mem, outMem;  // outMem: the result arrays this call allocates itself
+    mem.error = outMem.error = error;
+    mem.pool = in.pool;
 
     auto t0 = std::chrono::steady_clock::now();
-    nnbvh_prim *dPrims = mem.get<nnbvh_prim>(n);
-    float *dVerts = mem.get<float>(3 * (size_t)n_verts);
-    float *dCaller = prim_bounds ? mem.get<float>(6 * (size_t)n) : nullptr;
     Box6 *dPb = mem.get<Box6>(n);
     unsigned *dCodes = mem.get<unsigned>(n), *dCodesS = mem.get<unsigned>(n);
     int *dIdx = mem.get<int>(n), *dIdxS = mem.get<int>(n);
@@ -532,16 +629,8 @@ bool gpu_hlbvh(const nnbvh_prim *prims, int n, const float *verts, int n_verts,
     unsigned *dUcode = mem.get<unsigned>(n);
     int *dScalars = mem.get<int>(16);  // [0..5] centroid-bound keys, 6 err, 7 m, 8 maxDepth
     if (!mem.ok) return false;
-    GB_CHECK(hipMemcpyAsync(dPrims, prims, (size_t)n * sizeof(nnbvh_prim), hipMemcpyHostToDevice, stream), "copy prims");
-    GB_CHECK(hipMemcpyAsync(dVerts, verts, 3 * (size_t)n_verts * sizeof(float), hipMemcpyHostToDevice, stream), "copy verts");
-    if (dCaller)
-        GB_CHECK(hipMemcpyAsync(dCaller, prim_bounds, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream), "copy bounds");
     const int init[16] = {-1, -1, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // min keys all-ones, max keys 0
     GB_CHECK(hipMemcpyAsync(dScalars, init, sizeof init, hipMemcpyHostToDevice, stream), "init scalars");
-    GB_CHECK(hipStreamSynchronize(stream), "sync after upload");
-    out->ms[0] = ms_since(t0);
-
-    t0 = std::chrono::steady_clock::now();
     unsigned *dCb = (unsigned *)dScalars;
     int *dErr = dScalars + 6, *dM = dScalars + 7, *dMaxDepth = dScalars + 8;
     hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(n, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts,
@@ -645,51 +734,34 @@ bool gpu_hlbvh(const nnbvh_prim *prims, int n, const float *verts, int n_verts,
     out->ms[2] = ms_since(t0);
 
     t0 = std::chrono::steady_clock::now();
-    nnbvh_linear_node *dNodes = mem.get<nnbvh_linear_node>(up.total_nodes);
-    nnbvh_prim *dOrdered = mem.get<nnbvh_prim>(n);
-    if (!mem.ok) return false;
+    nnbvh_linear_node *dNodes = in.d_nodes_out ? in.d_nodes_out : outMem.get<nnbvh_linear_node>(up.total_nodes);
+    nnbvh_prim *dOrdered = in.d_ordered_out ? in.d_ordered_out : outMem.get<nnbvh_prim>(n);
+    if (!outMem.ok) return false;
     GB_CHECK(hipMemcpyAsync(dTbase, up.base.data(), nTreelets * sizeof(int), hipMemcpyHostToDevice, stream), "copy bases");
     GB_CHECK(hipMemcpyAsync(dTdepth, up.depth.data(), nTreelets * sizeof(int), hipMemcpyHostToDevice, stream), "copy depths");
     hipLaunchKernelGGL(k_emit, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dBit, dPstart, dFirst, dLast, dLeft,
                        dParent, dLeafOrd, dTreeOrd, dTbase, dTdepth, dNodeBox, dNodes, dMaxDepth);
     hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kB), 0, stream, dPrims, dIdxS, n, dOrdered);
+    // the upper nodes join the device array
+    if (!up.upper_index.empty()) {
+        int *dUi = mem.get<int>(up.upper_index.size());
+        nnbvh_linear_node *dUn = mem.get<nnbvh_linear_node>(up.upper_nodes.size());
+        if (!mem.ok) return false;
+        GB_CHECK(hipMemcpyAsync(dUi, up.upper_index.data(), up.upper_index.size() * sizeof(int), hipMemcpyHostToDevice, stream), "copy upper");
+        GB_CHECK(hipMemcpyAsync(dUn, up.upper_nodes.data(), up.upper_nodes.size() * sizeof(nnbvh_linear_node), hipMemcpyHostToDevice, stream), "copy upper");
+        hipLaunchKernelGGL(k_scatter_nodes, dim3(grid_all((long)up.upper_index.size())), dim3(kB), 0, stream, dUi, dUn,
+                           (int)up.upper_index.size(), dNodes);
+    }
+    out->depth = 0;
+    GB_CHECK(hipMemcpyAsync(&out->depth, dMaxDepth, sizeof(int), hipMemcpyDeviceToHost, stream), "read depth");
     GB_CHECK(hipGetLastError(), "kernel launch");
     GB_CHECK(hipStreamSynchronize(stream), "sync after emit");
     out->ms[3] = ms_since(t0);
-
-    t0 = std::chrono::steady_clock::now();
-    out->depth = 0;
-    GB_CHECK(hipMemcpy(&out->depth, dMaxDepth, sizeof(int), hipMemcpyDeviceToHost), "read depth");
     out->total_nodes = up.total_nodes;
-    if (out->keep_on_device) {
-        // upper nodes join the device array; nothing else leaves the device
-        if (!up.upper_index.empty()) {
-            int *dUi = mem.get<int>(up.upper_index.size());
-            nnbvh_linear_node *dUn = mem.get<nnbvh_linear_node>(up.upper_nodes.size());
-            if (!mem.ok) return false;
-            GB_CHECK(hipMemcpy(dUi, up.upper_index.data(), up.upper_index.size() * sizeof(int), hipMemcpyHostToDevice), "copy upper");
-            GB_CHECK(hipMemcpy(dUn, up.upper_nodes.data(), up.upper_nodes.size() * sizeof(nnbvh_linear_node), hipMemcpyHostToDevice), "copy upper");
-            hipLaunchKernelGGL(k_scatter_nodes, dim3(grid_all((long)up.upper_index.size())), dim3(kB), 0, stream, dUi, dUn,
-                               (int)up.upper_index.size(), dNodes);
-            GB_CHECK(hipStreamSynchronize(stream), "sync (upper nodes)");
-        }
-        out->d_nodes = dNodes;
-        out->d_ordered = dOrdered;
-        out->d_verts = dVerts;
-        mem.release(dNodes);
-        mem.release(dOrdered);
-        mem.release(dVerts);
-        out->ms[4] = ms_since(t0);
-        return true;
-    }
-    out->nodes.resize((size_t)up.total_nodes);
-    out->ordered.resize((size_t)n);
-    GB_CHECK(hipMemcpy(out->nodes.data(), dNodes, out->nodes.size() * sizeof(nnbvh_linear_node), hipMemcpyDeviceToHost),
-             "read nodes");
-    GB_CHECK(hipMemcpy(out->ordered.data(), dOrdered, out->ordered.size() * sizeof(nnbvh_prim), hipMemcpyDeviceToHost),
-             "read ordered prims");
-    for (size_t k = 0; k < up.upper_index.size(); ++k) out->nodes[(size_t)up.upper_index[k]] = up.upper_nodes[k];
-    out->ms[4] = ms_since(t0);
+    out->d_nodes = dNodes;
+    out->d_ordered = dOrdered;
+    outMem.release(dNodes);
+    outMem.release(dOrdered);
     return true;
 }
 
@@ -1372,21 +1444,40 @@ bool gpu_sah(const nnbvh_prim *prims, int n, const float *verts, int n_verts, co
     int prev = 0;
     GB_CHECK(hipGetDevice(&prev), "hipGetDevice");
     GB_CHECK(hipSetDevice(device), "hipSetDevice");
-    struct Restore {
-        int d;
-        ~Restore() { (void)hipSetDevice(d); }
-    } restore{prev};
-    const int maxPrims = std::min(255, max_prims_in_node);
-    int kSmallSegment = kSmallSegmentDefault;  // speed only: where breadth-first hands over to wavefronts
-    if (const char *e = std::getenv("NNBVH_SAH_SMALL")) kSmallSegment = std::max(2, std::atoi(e));
-    hipStream_t stream = nullptr;
+    RestoreDevice restore{prev};
     DevMem mem;
     mem.error = error;
+    auto t0 = std::chrono::steady_clock::now();
+    Uploaded up;
+    if (!upload_build_input(mem, prims, n, verts, n_verts, prim_bounds, &up, error)) return false;
+    out->ms[0] = ms_since(t0);
+    DeviceBuildInput in;
+    in.d_prims = up.prims;
+    in.n_prims = n;
+    in.d_verts = up.verts;
+    in.n_verts = n_verts;
+    in.d_prim_bounds = up.bounds;
+    in.max_prims_in_node = max_prims_in_node;
+    if (!gpu_sah_device(in, out, error)) return false;
+    t0 = std::chrono::steady_clock::now();
+    const bool ok = finish_build(mem, up, n, out, error);
+    out->ms[4] = ms_since(t0);
+    return ok;
+}
+
+bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error) {
+    const int n = in.n_prims, n_verts = in.n_verts;
+    const nnbvh_prim *dPrims = in.d_prims;
+    const float *dVerts = in.d_verts, *dCaller = in.d_prim_bounds;
+    const int maxPrims = std::min(255, in.max_prims_in_node);
+    int kSmallSegment = kSmallSegmentDefault;  // speed only: where breadth-first hands over to wavefronts
+    if (const char *e = std::getenv("NNBVH_SAH_SMALL")) kSmallSegment = std::max(2, std::atoi(e));
+    hipStream_t stream = (hipStream_t)in.stream;
+    DevMem mem, outMem;  // outMem: the result arrays this call allocates itself
+    mem.error = outMem.error = error;
+    mem.pool = in.pool;
 
     auto t0 = std::chrono::steady_clock::now();
-    nnbvh_prim *dPrims = mem.get<nnbvh_prim>(n);
-    float *dVerts = mem.get<float>(3 * (size_t)n_verts);
-    float *dCaller = prim_bounds ? mem.get<float>(6 * (size_t)n) : nullptr;
     Box6 *dPb = mem.get<Box6>(n);
     int *dPerm = mem.get<int>(n);
     int *dLfFlag = mem.get<int>((size_t)n + 1), *dRtFlag = mem.get<int>((size_t)n + 1);
@@ -1395,16 +1486,8 @@ bool gpu_sah(const nnbvh_prim *prims, int n, const float *verts, int n_verts, co
     unsigned *dCodesUnused = mem.get<unsigned>(n);
     int *dScalars = mem.get<int>(16);
     if (!mem.ok) return false;
-    GB_CHECK(hipMemcpyAsync(dPrims, prims, (size_t)n * sizeof(nnbvh_prim), hipMemcpyHostToDevice, stream), "copy prims");
-    GB_CHECK(hipMemcpyAsync(dVerts, verts, 3 * (size_t)n_verts * sizeof(float), hipMemcpyHostToDevice, stream), "copy verts");
-    if (dCaller)
-        GB_CHECK(hipMemcpyAsync(dCaller, prim_bounds, 6 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream), "copy bounds");
     const int init[16] = {-1, -1, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     GB_CHECK(hipMemcpyAsync(dScalars, init, sizeof init, hipMemcpyHostToDevice, stream), "init scalars");
-    GB_CHECK(hipStreamSynchronize(stream), "sync after upload");
-    out->ms[0] = ms_since(t0);
-
-    t0 = std::chrono::steady_clock::now();
     int *dErr = dScalars + 6;
     hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(n, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts, dCaller, n,
                        dPb, (unsigned *)dScalars, dErr);
@@ -1595,12 +1678,12 @@ bool gpu_sah(const nnbvh_prim *prims, int n, const float *verts, int n_verts, co
         *error = "gpu build: tree deeper than 255 levels";
         return false;
     }
-    nnbvh_linear_node *dNodes = mem.get<nnbvh_linear_node>((size_t)totalNodes);
+    nnbvh_linear_node *dNodes = in.d_nodes_out ? in.d_nodes_out : outMem.get<nnbvh_linear_node>((size_t)totalNodes);
     unsigned char *dDepthOf = mem.get<unsigned char>((size_t)totalNodes);
     int *dSegBase = mem.get<int>(nSmall), *dSegBaseDepth = mem.get<int>(nSmall);
     UpperNode *dUpper = mem.get<UpperNode>(upper.size());
-    nnbvh_prim *dOrdered = mem.get<nnbvh_prim>(n);
-    if (!mem.ok) return false;
+    nnbvh_prim *dOrdered = in.d_ordered_out ? in.d_ordered_out : outMem.get<nnbvh_prim>(n);
+    if (!mem.ok || !outMem.ok) return false;
     GB_CHECK(hipMemcpyAsync(dSegBase, segBase.data(), (size_t)nSmall * sizeof(int), hipMemcpyHostToDevice, stream), "copy bases");
     GB_CHECK(hipMemcpyAsync(dSegBaseDepth, segBaseDepth.data(), (size_t)nSmall * sizeof(int), hipMemcpyHostToDevice, stream), "copy depths");
     if (!upper.empty())
@@ -1617,25 +1700,14 @@ bool gpu_sah(const nnbvh_prim *prims, int n, const float *verts, int n_verts, co
     GB_CHECK(hipStreamSynchronize(stream), "sync after emit");
     out->ms[3] = ms_since(t0);
 
-    t0 = std::chrono::steady_clock::now();
     out->total_nodes = totalNodes;
-    if (out->keep_on_device) {
-        out->d_nodes = dNodes;
-        out->d_ordered = dOrdered;
-        out->d_verts = dVerts;
-        mem.release(dNodes);
-        mem.release(dOrdered);
-        mem.release(dVerts);
-    } else {
-        out->nodes.resize((size_t)totalNodes);
-        out->ordered.resize((size_t)n);
-        GB_CHECK(hipMemcpy(out->nodes.data(), dNodes, out->nodes.size() * sizeof(nnbvh_linear_node), hipMemcpyDeviceToHost), "read nodes");
-        GB_CHECK(hipMemcpy(out->ordered.data(), dOrdered, out->ordered.size() * sizeof(nnbvh_prim), hipMemcpyDeviceToHost), "read ordered prims");
-    }
+    out->d_nodes = dNodes;
+    out->d_ordered = dOrdered;
+    outMem.release(dNodes);
+    outMem.release(dOrdered);
     out->depth = maxDepth;
     out->n_treelets = nSmall;
     out->n_unique_codes = (int)upper.size();
-    out->ms[4] = ms_since(t0);
     return true;
 }
 

@@ -472,6 +472,7 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
             nnbvh_scene_destroy(s);
             return nullptr;
         }
+        s->n_anim = n_instances;
     }
     if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
@@ -620,24 +621,7 @@ nnbvh_scene *nnbvh_scene_create_instanced_with_attributes(const nnbvh_linear_nod
 }
 
 void nnbvh_transform_bounds(const float m[12], const float in[6], float out[6]) {
-    // Transform::operator()(const Bounds3f&), util/transform.cpp:134-139: union of the 8
-    // transformed corners (Bounds3::Corner, vecmath.h:1284-1289; point transform
-    // util/transform.h:310-319 with w == 1)
-    float mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) {
-        mn[k] = std::numeric_limits<float>::max();
-        mx[k] = std::numeric_limits<float>::lowest();
-    }
-    for (int c = 0; c < 8; ++c) {
-        const float p[3] = {in[(c & 1) ? 3 : 0], in[(c & 2) ? 4 : 1], in[(c & 4) ? 5 : 2]};
-        for (int k = 0; k < 3; ++k) {
-            const float v = m[4 * k] * p[0] + m[4 * k + 1] * p[1] + m[4 * k + 2] * p[2] + m[4 * k + 3];
-            mn[k] = std::min(mn[k], v);
-            mx[k] = std::max(mx[k], v);
-        }
-    }
-    std::memcpy(out, mn, 12);
-    std::memcpy(out + 3, mx, 12);
+    transform_bounds(m, in, out);  // nnbvh_internal.h: shared with the device's instance bounds
 }
 
 void nnbvh_scene_destroy(nnbvh_scene *s) {
@@ -693,6 +677,35 @@ int nnbvh_scene_info(const nnbvh_scene *s, int64_t out[6]) {
     out[3] = (int64_t)s->device_bytes;
     out[4] = grid_blocks(const_cast<nnbvh_scene *>(s), 0);
     out[5] = s->window;
+    return NNBVH_OK;
+}
+
+int nnbvh_scene_read(const nnbvh_scene *s, int what, void *out, size_t bytes) {
+    if (!s || !out) {
+        set_error("scene_read: null argument");
+        return NNBVH_ERR_ARG;
+    }
+    if (what < 0 || what > 2) {
+        set_error("scene_read: unknown array (0 interior records, 1 primitive stream, 2 animation table)");
+        return NNBVH_ERR_ARG;
+    }
+    if (what == 2 && !s->d_anim) {
+        set_error("scene_read: the scene has no animation table");
+        return NNBVH_ERR_ARG;
+    }
+    const void *src = what == 0 ? (const void *)s->d_wide : what == 1 ? (const void *)s->d_prims : (const void *)s->d_anim;
+    const size_t have = what == 0   ? (size_t)s->n_interior * sizeof(WideNode)
+                        : what == 1 ? (size_t)s->n_slots * 16
+                                    : (size_t)s->n_anim * kAnimStride * sizeof(float);
+    if (bytes != have) {
+        set_error("scene_read: " + std::to_string(bytes) + " bytes asked for, the array has " + std::to_string(have));
+        return NNBVH_ERR_ARG;
+    }
+    if (bytes == 0) return NNBVH_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    if (!hip_ok(hipDeviceSynchronize(), "scene_read") || !hip_ok(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost), "scene_read"))
+        return NNBVH_ERR_DEVICE;
     return NNBVH_OK;
 }
 

@@ -72,6 +72,7 @@ struct nnbvh_scene {
     float4 *d_wide = nullptr;
     float4 *d_prims = nullptr;
     float *d_anim = nullptr;  // AnimatedPrimitive table (kAnimStride floats per instance), or null
+    int n_anim = 0;           // its entries
     size_t device_bytes = 0;
     // tuning (speed only)
     int window = 8;
@@ -88,7 +89,7 @@ struct nnbvh_scene {
     int int_repeat = 3;
     int prim_repeat = 2;
     int max_grid_threads = 0;
-    double build_ms[1] = {0};  // device build time of nnbvh_scene_create_gpu_build
+    double build_ms[1] = {0};  // device build time of nnbvh_scene_create_gpu_build / _instanced_gpu_build
     std::mutex mu;
     std::map<hipStream_t, nnbvh::Workspace> workspaces;
     static constexpr int kHostSlots = 3, kHostChunks = 6;

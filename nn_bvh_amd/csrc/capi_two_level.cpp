@@ -1,0 +1,321 @@
+// capi_two_level.cpp — nnbvh_scene_create_instanced_gpu_build: a two-level scene (object instances as pbrt builds
+// them, scene.cpp:1521-1577) from the caller's primitive lists to traceable without a tree visiting the host.  Every
+// object definition's tree, then the top-level tree over the instances' transformed bounds, come from the device
+// builders' cores (bvh_build_gpu.hip); the trees are put into one numbering and baked by bvh_bake.hip.  The device
+// arrays are byte for byte those of nn_bvh_amd.instancing.assemble_two_level + nnbvh_scene_create_instanced_with_attributes.
+// Host code only.
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <vector>
+
+#include "bvh_build_gpu.h"
+#include "capi_internal.h"
+
+using namespace nnbvh;
+
+namespace {
+
+const char *kFn = "scene_create_instanced_gpu_build: ";
+
+bool fault(const std::string &msg) {
+    set_error(msg);
+    return false;
+}
+
+// Everything a kernel indexes with, checked on the host arrays before a device is looked at.
+bool check_arguments(const nnbvh_prim *prims, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects,
+                     const float *verts, int n_verts, const float *normals, const float *uvs, const float *prim_alpha,
+                     const float *prim_bounds, const nnbvh_placement *placements, int n_placements,
+                     const nnbvh_animated_transform *animated, int split_method) {
+    if (!prims || !verts || !object_first || !placements || n_prims <= 0 || n_verts <= 0 || n_top_prims <= 0 ||
+        n_objects <= 0 || n_placements <= 0)
+        return fault(std::string(kFn) + "null or empty input array");
+    if (object_first[0] != n_top_prims || object_first[n_objects] != n_prims)
+        return fault(std::string(kFn) + "malformed object_first (it starts at n_top_prims and ends at n_prims)");
+    for (int k = 0; k < n_objects; ++k)
+        if (object_first[k + 1] <= object_first[k])
+            return fault(std::string(kFn) + "malformed object_first (an object is empty or the entries decrease)");
+    if (split_method != NNBVH_SPLIT_SAH && split_method != NNBVH_SPLIT_HLBVH)
+        return fault(std::string(kFn) + "only the sah and hlbvh split methods are built on the device");
+    for (int j = 0; j < n_placements; ++j) {
+        if (placements[j].object < 0 || placements[j].object >= n_objects)
+            return fault(std::string(kFn) + "placement object out of range");
+        if (animated && animated[j].actually_animated && !(animated[j].end_time > animated[j].start_time))
+            return fault("scene_create: animated instance with an empty time range");
+    }
+    for (int i = 0; i < n_prims; ++i) {
+        const nnbvh_prim &p = prims[i];
+        int nv = 0;
+        if (p.kind == NNBVH_PRIM_INSTANCE) {
+            if (i >= n_top_prims) return fault("scene_create: nested instances are not supported");
+            if (p.v[0] < 0 || p.v[0] >= n_placements) return fault("scene_create: instance index out of range");
+            if (animated && animated[p.v[0]].actually_animated && !prim_bounds)
+                return fault("nnbvh_build_create: instance / host primitives need prim_bounds");
+        } else if (p.kind == NNBVH_PRIM_HOST) {
+            if (!prim_bounds) return fault("nnbvh_build_create: instance / host primitives need prim_bounds");
+        } else if (is_smooth_alpha_kind(p.kind)) {
+            nv = 3;
+            if (!normals)
+                return fault("scene_create: NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH primitives need the vertex normals "
+                             "(nnbvh_scene_create_with_normals)");
+        } else if (is_alpha_patch_kind(p.kind)) {
+            nv = 4;
+            if (!prim_alpha || (is_smooth_alpha_patch_kind(p.kind) && !normals) || (is_uv_alpha_patch_kind(p.kind) && !uvs))
+                return fault("scene_create: NNBVH_PRIM_ALPHA_PATCH primitives need the per-primitive alpha array, the "
+                             "smooth ones the vertex normals, the _UV ones the vertex uvs too "
+                             "(nnbvh_scene_create_with_attributes)");
+        } else if (is_triangle_kind(p.kind)) nv = 3;
+        else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = 4;
+        else return fault("scene_create: unknown primitive kind");
+        for (int j = 0; j < nv; ++j)
+            if (p.v[j] < 0 || p.v[j] >= n_verts) return fault("nnbvh_build_create: vertex index out of range");
+    }
+    return true;
+}
+
+// the call's device memory and stream: freed on every way out
+struct Held {
+    std::vector<void *> ptrs;
+    hipStream_t stream = nullptr;
+    ScratchPool pool;
+    template <typename T>
+    T *get(size_t count, const char *what) {
+        void *p = nullptr;
+        if (!hip_ok(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)), what)) return nullptr;
+        ptrs.push_back(p);
+        return (T *)p;
+    }
+    void drop(const void *p) {
+        for (void *&q : ptrs)
+            if (q && q == p) {
+                (void)hipFree(q);
+                q = nullptr;
+            }
+    }
+    ~Held() {
+        pool.clear();
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+template <typename T>
+bool put(T *dst, const T *src, size_t count, hipStream_t stream, const char *what) {
+    return hip_ok(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, stream), what);
+}
+
+}  // namespace
+
+extern "C" nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(
+    const nnbvh_prim *prims_in, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects,
+    const float *verts, int n_verts, const float *normals, const float *uvs, const float *prim_alpha,
+    const float *prim_bounds, const nnbvh_placement *placements, int n_placements,
+    const nnbvh_animated_transform *animated, int max_prims_in_node, int split_method, int device) {
+    if (!check_arguments(prims_in, n_prims, n_top_prims, object_first, n_objects, verts, n_verts, normals, uvs,
+                         prim_alpha, prim_bounds, placements, n_placements, animated, split_method))
+        return nullptr;
+    const int n_dev = nnbvh_device_count();
+    if (n_dev <= 0 || device < 0 || device >= n_dev) {
+        set_error(std::string(kFn) + "no usable HIP device (this library has no CPU fallback)");
+        return nullptr;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return nullptr;
+    hipDeviceProp_t prop;
+    if (!hip_ok(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties")) return nullptr;
+    const auto t_start = std::chrono::steady_clock::now();
+
+    // with a per-primitive array to carry along, the builds run with ids = positions in the caller's array; the
+    // gather pass puts the caller's ids back (bvh_bake.hip), as nnbvh_scene_create_gpu_build_with_attributes does
+    const nnbvh_prim *prims = prims_in;
+    std::vector<nnbvh_prim> tagged;
+    std::vector<int32_t> caller_ids;
+    if (prim_alpha) {
+        tagged.assign(prims_in, prims_in + n_prims);
+        caller_ids.resize((size_t)n_prims);
+        for (int i = 0; i < n_prims; ++i) {
+            caller_ids[(size_t)i] = tagged[(size_t)i].id;
+            tagged[(size_t)i].id = i;
+        }
+        prims = tagged.data();
+    }
+    std::vector<unsigned char> anim_flag;
+    if (animated) {
+        anim_flag.resize((size_t)n_placements);
+        for (int j = 0; j < n_placements; ++j) anim_flag[(size_t)j] = animated[j].actually_animated ? 1 : 0;
+    }
+
+    std::vector<unsigned char> named((size_t)n_objects, 0);
+    for (int j = 0; j < n_placements; ++j) named[(size_t)placements[j].object] = 1;
+
+    Held h;
+    if (!hip_ok(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking), "hipStreamCreate")) return nullptr;
+    hipStream_t stream = h.stream;
+    const int n_obj_prims = n_prims - n_top_prims;
+    const size_t child_cap = 2 * (size_t)n_obj_prims - (size_t)n_objects;  // sum of 2 n - 1
+    const size_t top_cap = 2 * (size_t)n_top_prims - 1;
+    // the vertices, the primitives and the caller's bounds go up once; every build reads its part of them
+    nnbvh_prim *d_prims = h.get<nnbvh_prim>((size_t)n_prims, "hipMalloc(primitives)");
+    float *d_verts = h.get<float>(3 * (size_t)n_verts, "hipMalloc(vertices)");
+    float *d_bounds = h.get<float>(6 * (size_t)(prim_bounds ? n_prims : n_top_prims), "hipMalloc(bounds)");
+    nnbvh_placement *d_placements = h.get<nnbvh_placement>((size_t)n_placements, "hipMalloc(placements)");
+    unsigned char *d_anim_flag = animated ? h.get<unsigned char>((size_t)n_placements, "hipMalloc(placements)") : nullptr;
+    int *d_object_first = h.get<int>((size_t)n_objects, "hipMalloc(objects)");
+    int *d_child_base = h.get<int>((size_t)n_objects, "hipMalloc(objects)");
+    int *d_object_root = h.get<int>((size_t)n_objects, "hipMalloc(objects)");
+    unsigned char *d_named = h.get<unsigned char>((size_t)n_objects, "hipMalloc(objects)");
+    nnbvh_prim *d_ordered = h.get<nnbvh_prim>((size_t)n_prims, "hipMalloc(ordered primitives)");
+    nnbvh_linear_node *d_child_nodes = h.get<nnbvh_linear_node>(child_cap, "hipMalloc(child trees)");
+    if (!d_prims || !d_verts || !d_bounds || !d_placements || (animated && !d_anim_flag) || !d_object_first ||
+        !d_child_base || !d_object_root || !d_named || !d_ordered || !d_child_nodes)
+        return nullptr;
+    bool ok = put(d_prims, prims, (size_t)n_prims, stream, "hipMemcpy(primitives)") &&
+              put(d_verts, verts, 3 * (size_t)n_verts, stream, "hipMemcpy(vertices)") &&
+              put(d_placements, placements, (size_t)n_placements, stream, "hipMemcpy(placements)") &&
+              put(d_object_first, (const int *)object_first, (size_t)n_objects, stream, "hipMemcpy(objects)") &&
+              put(d_named, named.data(), (size_t)n_objects, stream, "hipMemcpy(objects)");
+    if (ok && prim_bounds) ok = put(d_bounds, prim_bounds, 6 * (size_t)n_prims, stream, "hipMemcpy(bounds)");
+    if (ok && !prim_bounds) ok = hip_ok(hipMemsetAsync(d_bounds, 0, 24 * (size_t)n_top_prims, stream), "hipMemset(bounds)");
+    if (ok && animated) ok = put(d_anim_flag, anim_flag.data(), (size_t)n_placements, stream, "hipMemcpy(placements)");
+    if (!ok || !hip_ok(hipStreamSynchronize(stream), "upload")) return nullptr;
+
+    // the children first: tree k into d_child_nodes at child_base[k], its leaf order into the scene's primitive array
+    // at the object's own place (the scene's order is [top, object 0, object 1, ...], as the caller's list is)
+    std::string err;
+    std::vector<int> child_base((size_t)n_objects);
+    int child_total = 0, child_depth = 0;
+    auto build = [&](DeviceBuildInput &in, GpuBuildResult *r) {
+        in.d_verts = d_verts;
+        in.n_verts = n_verts;
+        in.max_prims_in_node = max_prims_in_node;
+        in.stream = stream;
+        in.pool = &h.pool;
+        const bool built = split_method == NNBVH_SPLIT_SAH ? gpu_sah_device(in, r, &err) : gpu_hlbvh_device(in, r, &err);
+        if (!built) set_error(err);
+        return built;
+    };
+    for (int k = 0; k < n_objects; ++k) {
+        const int first = object_first[k], count = object_first[k + 1] - first;
+        DeviceBuildInput in;
+        in.d_prims = d_prims + first;
+        in.n_prims = count;
+        in.d_prim_bounds = prim_bounds ? d_bounds + 6 * (size_t)first : nullptr;
+        in.d_nodes_out = d_child_nodes + child_total;
+        in.d_ordered_out = d_ordered + first;
+        GpuBuildResult r;
+        if (!build(in, &r)) return nullptr;
+        child_base[(size_t)k] = child_total;
+        child_total += r.total_nodes;
+        // (create_scene walks only the trees a placement names: an object nobody places adds nothing to the depth)
+        if (named[(size_t)k]) child_depth = std::max(child_depth, r.depth + 1);
+    }
+    // the top tree over the instances' bounds, straight into the front of the scene's node array
+    nnbvh_linear_node *d_nodes = h.get<nnbvh_linear_node>(top_cap + (size_t)child_total, "hipMalloc(tree)");
+    unsigned char *d_node_unnamed = h.get<unsigned char>(top_cap + (size_t)child_total, "hipMalloc(tree)");
+    if (!d_nodes || !d_node_unnamed) return nullptr;
+    if (!put(d_child_base, child_base.data(), (size_t)n_objects, stream, "hipMemcpy(objects)")) return nullptr;
+    if (!instance_bounds_on_device(d_prims, n_top_prims, d_placements, d_anim_flag, d_child_nodes, d_child_base, d_bounds,
+                                   stream, &err)) {
+        set_error(err);
+        return nullptr;
+    }
+    GpuBuildResult top;
+    {
+        DeviceBuildInput in;
+        in.d_prims = d_prims;
+        in.n_prims = n_top_prims;
+        in.d_prim_bounds = d_bounds;
+        in.d_nodes_out = d_nodes;
+        in.d_ordered_out = d_ordered;
+        if (!build(in, &top)) return nullptr;
+    }
+    const int depth = top.depth + child_depth;  // pending entries of the outer walk + those of the child walk
+    if (depth > kMaxStack) {
+        set_error("scene_create: tree deeper than the 64-entry traversal stack");
+        return nullptr;
+    }
+    const int n_nodes = top.total_nodes + child_total;
+    if (!rebase_children_on_device(d_child_nodes, child_total, d_child_base, d_object_first, n_objects, top.total_nodes,
+                                   d_nodes, d_object_root, d_named, d_node_unnamed, stream, &err)) {
+        set_error(err);
+        return nullptr;
+    }
+    if (!hip_ok(hipStreamSynchronize(stream), "two-level build")) return nullptr;
+    // all builder scratch goes before the bake allocates
+    h.pool.clear();
+    h.drop(d_prims);
+    h.drop(d_bounds);
+    h.drop(d_child_nodes);
+    h.drop(d_child_base);
+    h.drop(d_object_first);
+    h.drop(d_named);
+
+    float *d_alpha = nullptr, *d_normals = nullptr, *d_uvs = nullptr;
+    if (prim_alpha) {
+        // the gather works on the DEFAULT stream with blocking copies and ends with hipDeviceSynchronize: it sees the
+        // builds' output only because the private stream was synchronised above, and the bake below (private stream
+        // again) sees its output only because of that device-wide wait.  Keep both
+        void *p = nullptr;
+        if (!gather_prim_alpha_on_device(d_ordered, n_prims, prim_alpha, caller_ids.data(), &p, &err)) {
+            set_error(err);
+            return nullptr;
+        }
+        h.ptrs.push_back(p);
+        d_alpha = (float *)p;
+    }
+    if (normals) {
+        d_normals = h.get<float>(3 * (size_t)n_verts, "hipMalloc(normals)");
+        if (!d_normals || !put(d_normals, normals, 3 * (size_t)n_verts, stream, "hipMemcpy(normals)")) return nullptr;
+    }
+    if (uvs) {
+        d_uvs = h.get<float>(2 * (size_t)n_verts, "hipMalloc(uvs)");
+        if (!d_uvs || !put(d_uvs, uvs, 2 * (size_t)n_verts, stream, "hipMemcpy(uvs)")) return nullptr;
+    }
+    InstanceBake inst;
+    inst.d_placements = d_placements;
+    inst.d_object_root = d_object_root;
+    inst.d_animated = d_anim_flag;
+    inst.d_node_unnamed = d_node_unnamed;
+    BakedScene b;
+    if (!bake_on_device(d_nodes, n_nodes, d_ordered, n_prims, d_verts, device, &b, &err, d_normals, d_alpha, d_uvs, &inst,
+                        stream)) {
+        set_error(err);
+        return nullptr;
+    }
+
+    // the scene object, filled as create_scene (bvh_capi.cpp) fills it for a two-level scene
+    auto *s = new nnbvh_scene;
+    s->device = device;
+    s->n_cus = prop.multiProcessorCount;
+    s->n_interior = b.n_interior;
+    s->n_slots = b.n_slots;
+    s->depth = depth;
+    std::memcpy(s->bounds, b.bounds, sizeof b.bounds);
+    s->root_ref = b.root_ref;
+    s->instanced = 1;
+    s->has_host_prims = (b.has_host_prims || b.has_alpha) ? 1 : 0;
+    s->has_alpha = b.has_alpha;
+    s->has_patches = 1;  // two-level scenes always run the general kernels
+    s->max_grid_threads = s->n_cus * 8 * kBlockThreads;
+    s->d_wide = (float4 *)b.d_wide;
+    s->d_prims = (float4 *)b.d_prims;
+    s->device_bytes = ((((size_t)std::max(b.n_interior, 1) * sizeof(WideNode)) + 255) & ~(size_t)255) +
+                      std::max<size_t>((size_t)b.n_slots, 1) * 16 + 64;
+    if (animated) {
+        std::vector<float> table((size_t)n_placements * kAnimStride, 0.0f);
+        for (int k = 0; k < n_placements; ++k) fill_anim_entry(animated[k], &table[(size_t)k * kAnimStride]);
+        if (!hip_ok(hipMalloc((void **)&s->d_anim, table.size() * 4), "hipMalloc(animation table)") ||
+            !hip_ok(hipMemcpy(s->d_anim, table.data(), table.size() * 4, hipMemcpyHostToDevice),
+                    "hipMemcpy(animation table)")) {
+            nnbvh_scene_destroy(s);
+            return nullptr;
+        }
+        s->n_anim = n_placements;
+    }
+    if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
+    s->build_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    return s;
+}

@@ -106,4 +106,29 @@ NNBVH_HD inline bool kd_triangle_is_degenerate(const float *p0, const float *p1,
     return cx * cx + cy * cy + cz * cz == 0.0f;
 }
 
+// Transform::operator()(const Bounds3f&), util/transform.cpp:134-139: the union of the 8 transformed corners
+// (Bounds3::Corner, vecmath.h:1284-1289; point transform util/transform.h:310-319 with w == 1), corner after corner
+// with std::min / std::max's choice among equals (the first is kept), so the sign of a zero extreme is the
+// sequential one.  ONE function for nnbvh_transform_bounds (bvh_capi.cpp) and the device's instance bounds
+// (bvh_bake.hip): no contraction (-ffp-contract=off), the sums in the written order.
+NNBVH_HD inline void transform_bounds(const float m[12], const float in[6], float out[6]) {
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) {
+        mn[k] = 3.402823466e+38f;   // numeric_limits<float>::max()
+        mx[k] = -3.402823466e+38f;  // ... ::lowest()
+    }
+    for (int c = 0; c < 8; ++c) {
+        const float p[3] = {in[(c & 1) ? 3 : 0], in[(c & 2) ? 4 : 1], in[(c & 4) ? 5 : 2]};
+        for (int k = 0; k < 3; ++k) {
+            const float v = m[4 * k] * p[0] + m[4 * k + 1] * p[1] + m[4 * k + 2] * p[2] + m[4 * k + 3];
+            mn[k] = v < mn[k] ? v : mn[k];
+            mx[k] = mx[k] < v ? v : mx[k];
+        }
+    }
+    for (int k = 0; k < 3; ++k) {
+        out[k] = mn[k];
+        out[3 + k] = mx[k];
+    }
+}
+
 }  // namespace nnbvh

@@ -9,7 +9,15 @@ A B A B ..., medians with min..max:
   A  build_kd_tree(where="gpu") + KdTreeAggregate.from_tree   the tree downloaded, validated and baked on the host
   B  KdTreeAggregate.build_on_device                          bounds, tree and records made and kept on the device
   C  build_kd_tree(where="host") + from_tree, once, for the record
-and the peak of the device memory in use during one B (sampled from a second thread) beside what the scene keeps."""
+and the peak of the device memory in use during one B (sampled from a second thread) beside what the scene keeps.
+
+two-level section (--two-level: with the other sections, --two-level-only: alone; --two-level-out=PATH, default
+profiles/two_level_device_scene.txt): creating a two-level (instanced) scene, the same way:
+  A0 instancing.assemble_two_level + BVHAggregate.from_tree   every tree from the host builder, host bake
+  A  the same with the child and top trees from build_tree_gpu (built on the device, downloaded, host bake)
+  B  BVHAggregate.build_two_level_on_device                    every tree built, numbered and baked on the device
+on (i) the 400 placements of the 33 K-triangle killeroo of tools/bench_instances.py and (ii) 2 000 objects of 64
+triangles with 20 000 placements, where the per-object cost of building one tree after another shows."""
 import json
 import os
 import sys
@@ -104,17 +112,181 @@ def kd_section(names, out_path, rounds=5):
     return result
 
 
+def two_level_scenes():
+    """name -> (top_prims, verts, objects, placements)"""
+    out = {}
+    rng = np.random.default_rng(1)
+
+    def place(k, M):
+        return (k, M[:3].astype(np.float32).reshape(12), np.linalg.inv(M)[:3].astype(np.float32).reshape(12))
+
+    if os.path.exists(os.path.join(ROOT, "data", "killeroos.npz")):  # tools/bench_instances.py's scene
+        side = 20
+        verts, tris = scene.load_blob("killeroos")
+        used, inv = np.unique(tris[4:4 + 33264], return_inverse=True)
+        kv = verts[used]
+        ext = kv.max(0) - kv.min(0)
+        ground = (np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float32) * side * ext.max()
+                  + [0, 0, kv[:, 2].min()])
+        top = make_prims(np.array([[0, 1, 2], [2, 3, 0]], np.int32) + len(kv))
+        top["id"] += 10_000_000
+        placements = []
+        for i in range(side):
+            for j in range(side):
+                a, s = rng.uniform(0, 2 * np.pi), rng.uniform(0.6, 1.2)
+                M = np.eye(4)
+                M[:3, :3] = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]) * s
+                M[:3, 3] = [(i - side / 2) * ext[0] * 1.3, (j - side / 2) * ext[1] * 1.3, 0]
+                placements.append(place(0, M))
+        out["400 placements of one 33 264-triangle killeroo + a ground quad"] = (
+            top, np.concatenate([kv, ground]).astype(np.float32), [make_prims(inv.reshape(-1, 3).astype(np.int32))],
+            placements)
+    n_obj, n_tri, n_place = 2000, 64, 20000
+    c = rng.uniform(-1, 1, (n_obj * n_tri, 1, 3))
+    verts = (c + rng.uniform(-0.2, 0.2, (n_obj * n_tri, 3, 3))).reshape(-1, 3).astype(np.float32)
+    prims = make_prims(np.arange(3 * n_obj * n_tri, dtype=np.int32).reshape(-1, 3))
+    placements = []
+    for j in range(n_place):
+        M = np.eye(4)
+        M[:3, :3] *= rng.uniform(0.5, 2.0)
+        M[:3, 3] = rng.uniform(-200, 200, 3)
+        placements.append(place(j % n_obj, M))
+    out[f"{n_obj} objects of {n_tri} triangles, {n_place} placements"] = (
+        prims[:0], verts, [prims[k * n_tri:(k + 1) * n_tri] for k in range(n_obj)], placements)
+    return out
+
+
+def assemble_with(builder, top_prims, verts, objects, placements):
+    """instancing.assemble_two_level with the trees from `builder`"""
+    from nn_bvh_amd import instancing
+    from nn_bvh_amd._lib import INSTANCE_DTYPE, PRIM_DTYPE
+    children = [builder(o, verts) for o in objects]
+    entries, n_top, _ = BVHAggregate.two_level_entries(top_prims, objects, placements)
+    bounds = np.zeros((n_top, 6), np.float32)
+    for j, (k, m, _) in enumerate(placements):
+        root = children[k].nodes[0]
+        bounds[len(top_prims) + j] = instancing.transform_bounds(m, np.concatenate([root["pmin"], root["pmax"]]))
+    top = builder(entries[:n_top], verts, prim_bounds=bounds)
+    nodes, prims, node_base = [top.nodes], [top.ordered_prims], []
+    nb, pb = len(top.nodes), len(top.ordered_prims)
+    for c in children:
+        node_base.append(nb)
+        cn = c.nodes.copy()
+        interior = cn["nprims"] == 0
+        cn["offset"][interior] += nb
+        cn["offset"][~interior] += pb
+        nodes.append(cn)
+        prims.append(c.ordered_prims)
+        nb += len(cn)
+        pb += len(c.ordered_prims)
+    instances = np.zeros(len(placements), INSTANCE_DTYPE)
+    instances["render_from_prim"] = [p[1] for p in placements]
+    instances["prim_from_render"] = [p[2] for p in placements]
+    instances["root"] = [node_base[p[0]] for p in placements]
+    instances["n_nodes"] = [len(children[p[0]].nodes) for p in placements]
+    return np.concatenate(nodes), np.concatenate(prims).astype(PRIM_DTYPE), instances, len(top.nodes)
+
+
+def two_level_section(out_path, rounds=5):
+    import threading
+
+    import torch
+
+    from nn_bvh_amd import instancing
+    lines, result = [], {}
+
+    def stats(ms):
+        return f"{np.median(ms):9.1f} ms  ({min(ms):.1f} .. {max(ms):.1f})"
+
+    for name, (top, verts, objects, placements) in two_level_scenes().items():
+        def from_arrays(nodes, prims, instances, n_top):
+            return BVHAggregate.from_tree(nodes, prims, verts, instances=instances, n_top_nodes=n_top)
+
+        def route_a0():
+            return from_arrays(*instancing.assemble_two_level(top, verts, objects, placements))
+
+        def route_a():
+            gpu = lambda p, v, prim_bounds=None: build_tree_gpu(p, v, 4, prim_bounds, split_method="sah")  # noqa: E731
+            return from_arrays(*assemble_with(gpu, top, verts, objects, placements))
+
+        def route_b():
+            return BVHAggregate.build_two_level_on_device(top, verts, objects, placements)
+
+        routes = (route_a0, route_a, route_b)
+        ref = None
+        for fn in routes:  # first-call costs outside the timing; and the three scenes are one scene
+            agg = fn()
+            arrays = (agg.read(0).tobytes(), agg.read(1).tobytes(), agg.info)
+            assert ref is None or arrays == ref, f"{fn.__name__} bakes other arrays"
+            ref = arrays
+            info = agg.info
+            agg.close()
+        ms = {fn.__name__: [] for fn in routes}
+        for _ in range(rounds):
+            for fn in routes:
+                t0 = time.perf_counter()
+                agg = fn()
+                ms[fn.__name__].append((time.perf_counter() - t0) * 1e3)
+                agg.close()
+        torch.cuda.synchronize()
+        base = torch.cuda.mem_get_info()[0]
+        low, stop = [base], threading.Event()
+
+        def sample():
+            while not stop.is_set():
+                low[0] = min(low[0], torch.cuda.mem_get_info()[0])
+                time.sleep(0.0005)
+
+        th = threading.Thread(target=sample)
+        th.start()
+        agg = route_b()
+        stop.set()
+        th.join()
+        kept = base - torch.cuda.mem_get_info()[0]
+        agg.close()
+        a_ms, b_ms = ms["route_a"], ms["route_b"]
+        gain = np.median(a_ms) - np.median(b_ms)
+        spread = max(max(a_ms) - min(a_ms), max(b_ms) - min(b_ms))
+        verdict = ("B ahead of A by more than either spread" if gain > spread else
+                   "B behind A by more than either spread" if -gain > spread else "B and A within the spread")
+        lines += [f"{name}",
+                  f"  {sum(len(o) for o in objects)} object + {len(top)} top-level primitives, {len(objects)} objects, "
+                  f"{len(placements)} placements; {info['interior_records']} interior records, "
+                  f"{info['prim_slots']} slots, depth {info['depth']}",
+                  f"  A0 host trees + host bake                 {stats(ms['route_a0'])}",
+                  f"  A  device trees, downloaded + host bake   {stats(a_ms)}",
+                  f"  B  build_two_level_on_device              {stats(b_ms)}",
+                  f"  median A - median B = {gain:.1f} ms, larger spread {spread:.1f} ms: {verdict}",
+                  f"  B device memory: peak {(base - low[0]) / 2**20:.0f} MiB in use during the call (sampled), "
+                  f"{kept / 2**20:.0f} MiB kept (scene arrays {info['device_bytes'] / 2**20:.0f} MiB)", ""]
+        result[name] = {"a0_ms": ms["route_a0"], "a_ms": a_ms, "b_ms": b_ms, "peak_bytes": int(base - low[0]),
+                        "scene_bytes": info["device_bytes"], "verdict": verdict}
+    text = "\n".join([f"two-level scene creation, {rounds} alternated rounds per scene, one process; "
+                      f"{torch.cuda.get_device_name(0)}", ""] + lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(text)
+    return result
+
+
 flags = [a for a in sys.argv[1:] if a.startswith("--")]
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 kd_out = os.path.join(ROOT, "profiles", "kd_device_scene.txt")
 for f in flags:
     if f.startswith("--kd-out="):
         kd_out = f.split("=", 1)[1]
+two_level_out = os.path.join(ROOT, "profiles", "two_level_device_scene.txt")
+for f in flags:
+    if f.startswith("--two-level-out="):
+        two_level_out = f.split("=", 1)[1]
 names = args or ["killeroos", "coffee_maker", "bathroom", "crown"]
 out = {}
+if "--two-level" in flags or "--two-level-only" in flags:
+    out["two_level_scene_create"] = two_level_section(two_level_out)
 if "--kd" in flags or "--kd-only" in flags:
     out["kd_scene_create"] = kd_section(args or ["bathroom", "crown"], kd_out)
-for name in ([] if "--kd-only" in flags else names):
+for name in ([] if "--kd-only" in flags or "--two-level-only" in flags else names):
     if not os.path.exists(os.path.join(ROOT, "data", name + ".npz")):
         continue
     verts, tris = scene.load_blob(name)
