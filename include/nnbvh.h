@@ -516,7 +516,8 @@ int nnbvh_wavefront_intersect_closest_and_shadow(
  * T_ray, r_u, r_l stay 1, so an arriving ray adds Ld * (1 / (r_u + r_l).Average()) to its pixel sample
  * (intersect.h:258-273).  Needs the scene's shading mesh for the hit points (pi, n).  Runs as passes
  * over the still-active rays; between passes the host reads one 4-byte count (not hipGraph-
- * capturable).  d_state: optional uint8[max_rays]: 0 = arrived, 1 = blocked, 2 = a host-only
+ * capturable: nnbvh_wavefront_intersect_shadow_tr_bounded below is).  d_state: optional
+ * uint8[max_rays]: 0 = arrived, 1 = blocked, 2 = a host-only
  * primitive lies on the way (nothing added: the caller's to finish).  Media themselves (ray.medium,
  * SampleT_maj) are outside this path's scope. */
 typedef struct nnbvh_shading_mesh nnbvh_shading_mesh;
@@ -539,6 +540,30 @@ int nnbvh_wavefront_intersect_one_random(nnbvh_scene *s, const nnbvh_shading_mes
                                          const int32_t *d_size, const int32_t *d_prim_material,
                                          int64_t n_prim_material, void *d_sel_hits, void *d_sel_rays,
                                          float *d_reservoir_pdf, float *d_weight_sum, void *stream);
+
+/* The two walks above with a caller-given bound on passes and NO host round trip: the call enqueues exactly
+ * max_passes passes (1..64) — a trace and one fused step kernel each, sized for max_rays / max_items and taking
+ * their live count from a device counter — then a marking kernel and the final record / finish kernel.  Inside the
+ * call there are kernel launches only: no copy, no memset, no synchronisation and, once the stream's workspace has
+ * its size, no allocation, so after ONE warm-up call with the same max_rays / max_items on the stream the call can
+ * be captured in a hipGraph and replayed (a later call on that stream with a larger size regrows the workspace
+ * and invalidates such a graph).  An item is FINISHED iff the reference loop (intersect.h:183-256,
+ * aggregate.cpp:100-108) makes at most max_passes calls of Intersect for it; finished items get exactly what the
+ * unbounded calls give them, bit for bit.  An unfinished shadow ray gets state 2 and adds nothing to L; an
+ * unfinished one-random item gets instance = -1 in its selected hit record (pdf, weight sum and segment ray are
+ * then unspecified): both are the existing "the caller's to finish" marks.  d_unfinished: nullable, receives the
+ * number of unfinished items.  A pass over an empty list costs launches whose waves exit at once; walks longer
+ * than 64 surfaces need the unbounded calls. */
+int nnbvh_wavefront_intersect_shadow_tr_bounded(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld, const float *d_r_u,
+    const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_state,
+    int32_t max_passes, int32_t *d_unfinished, void *stream);
+int nnbvh_wavefront_intersect_one_random_bounded(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items, const float *d_p0, const float *d_p1,
+    const int32_t *d_material, const int32_t *d_size, const int32_t *d_prim_material, int64_t n_prim_material,
+    void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum, int32_t max_passes,
+    int32_t *d_unfinished, void *stream);
 
 /* RecordShadowRayResult (wavefront/intersect.h:32-47) for a shadow batch that was traced with
  * nnbvh_intersect_any_device: the bookkeeping half of nnbvh_wavefront_intersect_shadow on its own. */

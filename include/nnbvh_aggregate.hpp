@@ -535,6 +535,29 @@ class HipBVHAggregate {
                                                  dReservoirPdf, dWeightSum, stream) != NNBVH_OK)
             fatal("IntersectOneRandomQueue");
     }
+    // ... with at most maxPasses passes and no host round trip (hipGraph-capturable after one warm-up call):
+    // rays whose walk needs more get state 2, items instance = -1; dUnfinished (nullable) receives their number
+    void IntersectShadowTrBounded(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &shadowQueue,
+                                  const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass,
+                                  const float *dLd, const float *dRu, const float *dRl,
+                                  const int32_t *dPixelIndex, float *dL, int64_t nPixels, int maxPasses,
+                                  void *stream, uint8_t *dState = nullptr, int32_t *dUnfinished = nullptr) const {
+        if (nnbvh_wavefront_intersect_shadow_tr_bounded(scene_, mesh, maxRays, &shadowQueue, dSize, dPrimClass,
+                                                        nPrimClass, dLd, dRu, dRl, dPixelIndex, dL, nPixels, dState,
+                                                        maxPasses, dUnfinished, stream) != NNBVH_OK)
+            fatal("IntersectShadowTrBounded");
+    }
+    void IntersectOneRandomBounded(const nnbvh_shading_mesh *mesh, int maxItems, const float *dP0,
+                                   const float *dP1, const int32_t *dMaterial, const int32_t *dSize,
+                                   const int32_t *dPrimMaterial, int64_t nPrimMaterial, void *dSelHits,
+                                   void *dSelRays, float *dReservoirPdf, int maxPasses, void *stream,
+                                   float *dWeightSum = nullptr, int32_t *dUnfinished = nullptr) const {
+        if (nnbvh_wavefront_intersect_one_random_bounded(scene_, mesh, maxItems, dP0, dP1, dMaterial, dSize,
+                                                         dPrimMaterial, nPrimMaterial, dSelHits, dSelRays,
+                                                         dReservoirPdf, dWeightSum, maxPasses, dUnfinished,
+                                                         stream) != NNBVH_OK)
+            fatal("IntersectOneRandomBounded");
+    }
 
     nnbvh_scene *handle() const { return scene_; }
 

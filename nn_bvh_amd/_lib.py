@@ -80,6 +80,7 @@ EXPORTS = [
     "nnbvh_kd_scene_create", "nnbvh_kd_scene_create_with_attributes", "nnbvh_kd_scene_destroy", "nnbvh_kd_intersect_closest", "nnbvh_kd_intersect_any",
     "nnbvh_kd_intersect_closest_device", "nnbvh_kd_intersect_any_device",
     "nnbvh_wavefront_intersect_shadow_tr", "nnbvh_wavefront_intersect_one_random",
+    "nnbvh_wavefront_intersect_shadow_tr_bounded", "nnbvh_wavefront_intersect_one_random_bounded",
     "nnbvh_scene_create_instanced_animated", "nnbvh_wavefront_enqueue_closest_items_device",
     "nnbvh_wavefront_intersect_closest_items", "nnbvh_wavefront_intersect_closest_and_shadow_items",
     "nnbvh_intersect_closest_candidates", "nnbvh_intersect_any_candidates",
@@ -296,6 +297,12 @@ def lib():
     L.nnbvh_wavefront_intersect_shadow_tr.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp]
     L.nnbvh_wavefront_intersect_one_random.restype = i32
     L.nnbvh_wavefront_intersect_one_random.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.nnbvh_wavefront_intersect_shadow_tr_bounded.restype = i32
+    L.nnbvh_wavefront_intersect_shadow_tr_bounded.argtypes = [vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp,
+                                                              i32, vp, vp]
+    L.nnbvh_wavefront_intersect_one_random_bounded.restype = i32
+    L.nnbvh_wavefront_intersect_one_random_bounded.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp,
+                                                               i32, vp, vp]
     hc = ctypes.POINTER(HostCandidates)
     L.nnbvh_intersect_closest_candidates.restype = i32
     L.nnbvh_intersect_closest_candidates.argtypes = [vp, vp, i64, vp, hc]

@@ -851,4 +851,125 @@ int nnbvh_wavefront_intersect_one_random(nnbvh_scene *s, const nnbvh_shading_mes
     return NNBVH_OK;
 }
 
+// ---- the bounded forms: max_passes passes enqueued up front, kernel launches only ------------------------------
+// Nothing inside these calls waits for the device or copies from host memory, so they can be captured in a hipGraph
+// once the stream's workspace has its size (a warm-up call with the same max_rays): every pass is sized for
+// max_rays and takes its live count from counters[k], which the step of pass k - 1 has counted up.  The counters
+// are cleared by a kernel node.  A pass over an empty list is a trace and a step whose waves exit at once.
+static constexpr int kMaxBoundedPasses = 64;
+
+static bool bounded_args_ok(const char *fn, const nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
+                            int64_t n_prim, int32_t max_passes, bool arrays) {
+    const char *what = nullptr;
+    if (!s) what = "no scene";
+    else if (!m) what = "no shading mesh";
+    else if (max_passes < 1 || max_passes > kMaxBoundedPasses) what = "max_passes outside 1..64";
+    else if (max_items < 0 || n_prim < 0) what = "negative size";
+    else if (max_items > 0 && !arrays) what = "null array";
+    else if (m->device != s->device) what = "scene and shading mesh live on different devices";
+    if (what) set_error(std::string(fn) + ": " + what);
+    return !what;
+}
+
+int nnbvh_wavefront_intersect_shadow_tr_bounded(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
+    const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld, const float *d_r_u,
+    const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_state,
+    int32_t max_passes, int32_t *d_unfinished, void *stream_) {
+    const char *fn = "wavefront_intersect_shadow_tr_bounded";
+    if (!bounded_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), max_passes,
+                         soa_ok(shadow_queue) && d_Ld && d_r_u && d_r_l && d_pixel_index && d_L))
+        return NNBVH_ERR_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_rays == 0) return NNBVH_OK;
+    Workspace *w = call.w;
+    const size_t n = (size_t)max_rays;
+    void *raysA, *raysB, *hits, *origA, *origB, *pLight, *state, *counters;
+    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hits) ||
+        !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) || !scratch(w, 6, n * 16, &pLight) ||
+        !scratch(w, 7, n, &state) || !scratch(w, 8, (kMaxBoundedPasses + 1) * 4, &counters))
+        return NNBVH_ERR_DEVICE;
+    int32_t *count = (int32_t *)counters;  // count[k]: the size of pass k's list, k >= 1 (pass 0 runs the queue)
+    const WavefrontCount cnt{max_rays, d_size};
+    if (!hip_ok(launch_zero_words(count, max_passes + 1, max_blocks, stream), "pass count reset launch") ||
+        !hip_ok(launch_str_init(*shadow_queue, cnt, raysA, (int32_t *)origA, (float4 *)pLight, (uint8_t *)state,
+                                max_blocks, stream), "shadow-tr init launch"))
+        return NNBVH_ERR_DEVICE;
+    void *cur = raysA, *next = raysB, *ocur = origA, *onext = origB;
+    for (int pass = 0; pass < max_passes; ++pass) {
+        const int32_t *d_n = pass == 0 ? d_size : count + pass;
+        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = max_rays, .d_n = d_n, .hits = hits});
+        if (rc != NNBVH_OK) return rc;
+        if (!hip_ok(launch_str_step(m->d, cur, hits, (const int32_t *)ocur, WavefrontCount{max_rays, d_n}, d_prim_class,
+                                    (long)n_prim_class, (const float4 *)pLight, (uint8_t *)state, next,
+                                    (int32_t *)onext, count + pass + 1, max_blocks, stream), "shadow-tr step launch"))
+            return NNBVH_ERR_DEVICE;
+        std::swap(cur, next);
+        std::swap(ocur, onext);
+    }
+    if (!hip_ok(launch_w2_mark_unfinished(cur, (const int32_t *)ocur, WavefrontCount{max_rays, count + max_passes},
+                                          (uint8_t *)state, nullptr, d_unfinished, max_blocks, stream),
+                "shadow-tr marking launch") ||
+        !hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
+                                  d_state, max_blocks, stream), "shadow-tr record launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_wavefront_intersect_one_random_bounded(
+    nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items, const float *d_p0, const float *d_p1,
+    const int32_t *d_material, const int32_t *d_size, const int32_t *d_prim_material, int64_t n_prim_material,
+    void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum, int32_t max_passes,
+    int32_t *d_unfinished, void *stream_) {
+    const char *fn = "wavefront_intersect_one_random_bounded";
+    if (!bounded_args_ok(fn, s, m, max_items, n_prim_material, max_passes,
+                         d_p0 && d_p1 && d_material && d_sel_hits && d_sel_rays && d_reservoir_pdf))
+        return NNBVH_ERR_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_items == 0) return NNBVH_OK;
+    Workspace *w = call.w;
+    const size_t n = (size_t)max_items;
+    void *raysA, *raysB, *hits, *origA, *origB, *pi, *rng, *weights, *counters;
+    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hits) ||
+        !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) || !scratch(w, 6, n * 36, &pi) ||
+        !scratch(w, 10, n * 16, &rng) || !scratch(w, 11, n * 8, &weights) ||
+        !scratch(w, 8, (kMaxBoundedPasses + 1) * 4, &counters))
+        return NNBVH_ERR_DEVICE;
+    int32_t *count = (int32_t *)counters;  // count[k]: the size of pass k's list
+    OneRandomState st{(float *)pi, (uint64_t *)rng, (float *)weights};
+    const WavefrontCount cnt{max_items, d_size};
+    if (!hip_ok(launch_zero_words(count, max_passes + 1, max_blocks, stream), "pass count reset launch") ||
+        !hip_ok(launch_or_init(d_p0, d_p1, cnt, st, raysA, (int32_t *)origA, count, d_sel_hits, d_sel_rays, max_blocks,
+                               stream), "one-random init launch"))
+        return NNBVH_ERR_DEVICE;
+    void *cur = raysA, *next = raysB, *ocur = origA, *onext = origB;
+    for (int pass = 0; pass < max_passes; ++pass) {
+        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = max_items, .d_n = count + pass, .hits = hits});
+        if (rc != NNBVH_OK) return rc;
+        if (!hip_ok(launch_or_step_fused(m->d, cur, hits, (const int32_t *)ocur, WavefrontCount{max_items, count + pass},
+                                         d_p1, d_material, d_prim_material, (long)n_prim_material, st, next,
+                                         (int32_t *)onext, count + pass + 1, d_sel_hits, d_sel_rays, max_blocks, stream),
+                    "one-random step launch"))
+            return NNBVH_ERR_DEVICE;
+        std::swap(cur, next);
+        std::swap(ocur, onext);
+    }
+    if (!hip_ok(launch_w2_mark_unfinished(cur, (const int32_t *)ocur, WavefrontCount{max_items, count + max_passes},
+                                          nullptr, d_sel_hits, d_unfinished, max_blocks, stream),
+                "one-random marking launch") ||
+        !hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/nnbvh.h"
+#include "interaction.h"
 #include "wavefront.h"
 
 namespace nnbvh {
@@ -42,5 +43,26 @@ hipError_t launch_or_step(const void *raysCur, const void *hitsCur, const void *
                           int maxBlocks, hipStream_t stream);
 hipError_t launch_or_finish(WavefrontCount cnt, OneRandomState st, float *pdf, float *weightSum, int maxBlocks,
                             hipStream_t stream);
+
+// ---- the bounded forms: one fused step per pass, no host round trip ---------------------------------
+// One pass of the shadow walk after its trace: hit -> verdict (str_classify's rules), and for an interface hit the
+// interaction in registers and the next segment's ray towards pLight, appended to the next list.  cur: the list's
+// size (the queue's own for the first pass, a counter of the call's for the others).
+hipError_t launch_str_step(const ShadingMeshDevice &m, const void *raysCur, const void *hitsCur,
+                           const int32_t *origCur, WavefrontCount cur, const uint8_t *primClass, long nPrimClass,
+                           const float4 *pLight, uint8_t *state, void *raysNext, int32_t *origNext, int32_t *counter,
+                           int maxBlocks, hipStream_t stream);
+// ... of the one-random walk: or_step with the interaction in registers
+hipError_t launch_or_step_fused(const ShadingMeshDevice &m, const void *raysCur, const void *hitsCur,
+                                const int32_t *origCur, WavefrontCount cur, const float *p1, const int32_t *material,
+                                const int32_t *primMaterial, long nPrimMaterial, OneRandomState st, void *raysNext,
+                                int32_t *origNext, int32_t *counter, void *selHits, void *selRays, int maxBlocks,
+                                hipStream_t stream);
+// What the last pass left on its list is the caller's to finish: state 2 (shadow rays; a zero direction has ended
+// its walk and is skipped) or instance = -1 in the selected hit record (one-random items, state == nullptr).
+// *unfinished (nullable, zero before the launch) receives their number.
+hipError_t launch_w2_mark_unfinished(const void *raysLeft, const int32_t *origLeft, WavefrontCount left,
+                                     uint8_t *state, void *selHits, int32_t *unfinished, int maxBlocks,
+                                     hipStream_t stream);
 
 }  // namespace nnbvh

@@ -16,6 +16,7 @@
 // wavefront).  Every kernel is a streaming pass, HBM-bound.
 #include <hip/hip_runtime.h>
 
+#include "interaction_math.h"
 #include "spawn_math.h"
 #include "wavefront2.h"
 
@@ -319,6 +320,167 @@ __global__ __launch_bounds__(kW2Block) void or_finish(WavefrontCount cnt, OneRan
     }
 }
 
+// ---- the bounded forms: one fused step per pass ---------------------------------------------------
+// nnbvh_wavefront_intersect_shadow_tr_bounded / _one_random_bounded run a caller-given number of passes with no
+// host round trip, so a pass is two kernels: the trace and one of the steps below.  A step does what the
+// interaction post-pass and str_classify + str_spawn (or or_step) do between them, but computes the hit's
+// interaction in registers: only pi and n are used, so the other fields' arithmetic is dead code and no
+// 192-byte record is written or read back.  The arithmetic is interaction_math.h's, as in the post-pass.
+
+// pi low / high and n of the SurfaceInteraction of hit {h0, h1} of the ray whose second half is r1;
+// false: a hit the device cannot finish (the post-pass's status is neither TRIANGLE nor PATCH)
+template <bool FULL>
+__device__ __forceinline__ bool w2_hit_pi_n(const MeshView &m, float4 h0, float4 h1, float4 r1, V3 &lo, V3 &hi,
+                                            V3 &n) {
+    const int prim = __float_as_int(h0.x);
+    const int status = imath::interaction_status<FULL>(m, prim, __float_as_int(h1.w));
+    if (status != NNBVH_INTERACTION_TRIANGLE && status != NNBVH_INTERACTION_PATCH) return false;
+    nnbvh_interaction r;
+    __builtin_memset(&r, 0, sizeof r);
+    bool ok = false;
+    imath::surface_interaction<FULL>(m, status, prim, h0, h1, imath::F3{-r1.x, -r1.y, -r1.z}, r1.w, r,
+                                     [&](int final_status) { ok = final_status != NNBVH_INTERACTION_HOST; });
+    lo = {r.pi_lo[0], r.pi_lo[1], r.pi_lo[2]};
+    hi = {r.pi_hi[0], r.pi_hi[1], r.pi_hi[2]};
+    n = {r.n[0], r.n[1], r.n[2]};
+    return ok;
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(kW2Block) void str_step(MeshView m, const float4 *raysCur, const float4 *hitsCur,
+                                                     const int32_t *origCur, WavefrontCount cur,
+                                                     const uint8_t *primClass, long nPrimClass, const float4 *pLight,
+                                                     uint8_t *state, float4 *raysNext, int32_t *origNext,
+                                                     int32_t *counter) {
+    const int n = w2_count(cur);
+    const int nPad = (n + 63) & ~63;  // whole wavefronts take part in the ballots
+    for (int j = blockIdx.x * kW2Block + threadIdx.x; j < nPad; j += gridDim.x * kW2Block) {
+        bool goOn = false;
+        float4 a, b;
+        int item = 0;
+        if (j < n) {
+            const float4 r0 = raysCur[2 * (long)j], r1 = raysCur[2 * (long)j + 1];
+            const float4 h0 = hitsCur[2 * (long)j], h1 = hitsCur[2 * (long)j + 1];
+            item = origCur[j];
+            // the verdicts of str_classify, in its order
+            const bool zeroDir = r1.x == 0.0f && r1.y == 0.0f && r1.z == 0.0f;
+            const int prim = __float_as_int(h0.x);
+            if (zeroDir) {
+            } else if (__float_as_int(h1.w) == -1) {
+                state[item] = 2;
+            } else if (prim >= 0) {
+                unsigned cls = NNBVH_CLASS_BASIC;
+                if (primClass && (long)prim < nPrimClass) cls = primClass[prim];
+                if (!(cls & NNBVH_CLASS_INTERFACE)) {
+                    state[item] = 1;
+                } else {  // str_spawn
+                    V3 lo, hi, nn;
+                    if (!w2_hit_pi_n<FULL>(m, h0, h1, r1, lo, hi, nn)) {
+                        state[item] = 2;
+                    } else {
+                        const float4 pl = pLight[item];
+                        V3 o, d;
+                        spawn_ray_to(lo, hi, nn, {pl.x, pl.y, pl.z}, o, d);
+                        a = make_float4(o.x, o.y, o.z, r0.w);
+                        b = make_float4(d.x, d.y, d.z, r1.w);
+                        goOn = true;  // a zero direction is caught by the next step, or by the final marking
+                    }
+                }
+            }
+        }
+        const int at = w2_append(goOn, counter);
+        if (at >= 0) {
+            raysNext[2 * (long)at] = a;
+            raysNext[2 * (long)at + 1] = b;
+            origNext[at] = item;
+        }
+    }
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(kW2Block) void or_step_fused(MeshView m, const float4 *raysCur, const float4 *hitsCur,
+                                                          const int32_t *origCur, WavefrontCount cur, const float *p1,
+                                                          const int32_t *material, const int32_t *primMaterial,
+                                                          long nPrimMaterial, OneRandomState st, float4 *raysNext,
+                                                          int32_t *origNext, int32_t *counter, float4 *selHits,
+                                                          float4 *selRays) {
+    const int n = w2_count(cur);
+    const int nPad = (n + 63) & ~63;
+    for (int j = blockIdx.x * kW2Block + threadIdx.x; j < nPad; j += gridDim.x * kW2Block) {
+        bool goOn = false;
+        float4 a, b;
+        int item = 0;
+        if (j < n) {
+            item = origCur[j];
+            const float4 r0 = raysCur[2 * (long)j], r1 = raysCur[2 * (long)j + 1];
+            const float4 h0 = hitsCur[2 * (long)j], h1 = hitsCur[2 * (long)j + 1];
+            const int prim = __float_as_int(h0.x);
+            V3 lo, hi, nn;
+            if (prim < 0 && __float_as_int(h1.w) != -1) {
+                // no further surface on the segment: the walk ends
+            } else if (__float_as_int(h1.w) == -1 || !w2_hit_pi_n<FULL>(m, h0, h1, r1, lo, hi, nn)) {
+                selHits[2 * (long)item + 1].w = __int_as_float(-1);  // the item is the caller's
+            } else {  // or_step from here on
+                const int mat = (primMaterial && (long)prim < nPrimMaterial) ? primMaterial[prim] : 0;
+                if (mat == material[item]) {
+                    Pcg32 g = {st.rng[2 * (long)item], st.rng[2 * (long)item + 1]};
+                    float weightSum = st.weights[2 * (long)item];
+                    const float weight = 1.0f;
+                    weightSum += weight;
+                    const float p = weight / weightSum;
+                    if (pcg32_float(g) < p) {
+                        selHits[2 * (long)item] = h0;
+                        selHits[2 * (long)item + 1] = h1;
+                        selRays[2 * (long)item] = r0;
+                        selRays[2 * (long)item + 1] = r1;
+                        st.weights[2 * (long)item + 1] = weight;
+                    }
+                    st.weights[2 * (long)item] = weightSum;
+                    st.rng[2 * (long)item] = g.state;
+                }
+                const V3 a1 = {p1[3 * (long)item], p1[3 * (long)item + 1], p1[3 * (long)item + 2]};
+                V3 o, d;
+                spawn_ray_to(lo, hi, nn, a1, o, d);
+                if (!(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f)) {
+                    goOn = true;
+                    a = make_float4(o.x, o.y, o.z, 1.0f);
+                    b = make_float4(d.x, d.y, d.z, 0.0f);
+                }
+            }
+        }
+        const int at = w2_append(goOn, counter);
+        if (at >= 0) {
+            raysNext[2 * (long)at] = a;
+            raysNext[2 * (long)at + 1] = b;
+            origNext[at] = item;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kW2Block) void w2_mark_unfinished(const float4 *raysLeft, const int32_t *origLeft,
+                                                               WavefrontCount left, uint8_t *state, float4 *selHits,
+                                                               int32_t *unfinished) {
+    const int n = w2_count(left);
+    const int nPad = (n + 63) & ~63;
+    for (int j = blockIdx.x * kW2Block + threadIdx.x; j < nPad; j += gridDim.x * kW2Block) {
+        bool mark = false;
+        if (j < n) {
+            const int item = origLeft[j];
+            if (state) {  // while (ray.d != Vector3f(0, 0, 0)): a zero direction has ended the walk, the ray arrives
+                const float4 r1 = raysLeft[2 * (long)j + 1];
+                mark = !(r1.x == 0.0f && r1.y == 0.0f && r1.z == 0.0f);
+                if (mark) state[item] = 2;
+            } else {
+                mark = true;
+                selHits[2 * (long)item + 1].w = __int_as_float(-1);
+            }
+        }
+        const unsigned long long mask = __ballot(mark);
+        if (unfinished && mask != 0ull && (threadIdx.x & 63) == __ffsll((long long)mask) - 1)
+            atomicAdd(unfinished, __popcll(mask));
+    }
+}
+
 // ---- launchers ----------------------------------------------------------------------------------
 hipError_t launch_str_init(const nnbvh_ray_soa &q, WavefrontCount cnt, void *rays, int32_t *orig, float4 *pLight,
                            uint8_t *state, int maxBlocks, hipStream_t stream) {
@@ -373,6 +535,50 @@ hipError_t launch_or_finish(WavefrontCount cnt, OneRandomState st, float *pdf, f
                             hipStream_t stream) {
     hipLaunchKernelGGL(or_finish, dim3(w2_grid(cnt.n, maxBlocks)), dim3(kW2Block), 0, stream, cnt, st, pdf,
                        weightSum);
+    return hipGetLastError();
+}
+
+static MeshView w2_mesh_view(const ShadingMeshDevice &m) {
+    return {m.verts, m.triVerts, m.patchVerts, m.normals, m.uvs, m.tangents, m.faceIndices, m.triFlags, m.nTris,
+            m.defaultFlags, m.instances, m.nInstances, m.anim, m.animFwd};
+}
+// FULL as launch_triangle_interactions chooses it: the mesh has patches or an instance table
+hipError_t launch_str_step(const ShadingMeshDevice &m, const void *raysCur, const void *hitsCur,
+                           const int32_t *origCur, WavefrontCount cur, const uint8_t *primClass, long nPrimClass,
+                           const float4 *pLight, uint8_t *state, void *raysNext, int32_t *origNext, int32_t *counter,
+                           int maxBlocks, hipStream_t stream) {
+    const dim3 grid(w2_grid(cur.n, maxBlocks)), block(kW2Block);
+    if (m.patchVerts || m.instances)
+        hipLaunchKernelGGL(str_step<true>, grid, block, 0, stream, w2_mesh_view(m), (const float4 *)raysCur,
+                           (const float4 *)hitsCur, origCur, cur, primClass, nPrimClass, pLight, state,
+                           (float4 *)raysNext, origNext, counter);
+    else
+        hipLaunchKernelGGL(str_step<false>, grid, block, 0, stream, w2_mesh_view(m), (const float4 *)raysCur,
+                           (const float4 *)hitsCur, origCur, cur, primClass, nPrimClass, pLight, state,
+                           (float4 *)raysNext, origNext, counter);
+    return hipGetLastError();
+}
+hipError_t launch_or_step_fused(const ShadingMeshDevice &m, const void *raysCur, const void *hitsCur,
+                                const int32_t *origCur, WavefrontCount cur, const float *p1, const int32_t *material,
+                                const int32_t *primMaterial, long nPrimMaterial, OneRandomState st, void *raysNext,
+                                int32_t *origNext, int32_t *counter, void *selHits, void *selRays, int maxBlocks,
+                                hipStream_t stream) {
+    const dim3 grid(w2_grid(cur.n, maxBlocks)), block(kW2Block);
+    if (m.patchVerts || m.instances)
+        hipLaunchKernelGGL(or_step_fused<true>, grid, block, 0, stream, w2_mesh_view(m), (const float4 *)raysCur,
+                           (const float4 *)hitsCur, origCur, cur, p1, material, primMaterial, nPrimMaterial, st,
+                           (float4 *)raysNext, origNext, counter, (float4 *)selHits, (float4 *)selRays);
+    else
+        hipLaunchKernelGGL(or_step_fused<false>, grid, block, 0, stream, w2_mesh_view(m), (const float4 *)raysCur,
+                           (const float4 *)hitsCur, origCur, cur, p1, material, primMaterial, nPrimMaterial, st,
+                           (float4 *)raysNext, origNext, counter, (float4 *)selHits, (float4 *)selRays);
+    return hipGetLastError();
+}
+hipError_t launch_w2_mark_unfinished(const void *raysLeft, const int32_t *origLeft, WavefrontCount left,
+                                     uint8_t *state, void *selHits, int32_t *unfinished, int maxBlocks,
+                                     hipStream_t stream) {
+    hipLaunchKernelGGL(w2_mark_unfinished, dim3(w2_grid(left.n, maxBlocks)), dim3(kW2Block), 0, stream,
+                       (const float4 *)raysLeft, origLeft, left, state, (float4 *)selHits, unfinished);
     return hipGetLastError();
 }
 

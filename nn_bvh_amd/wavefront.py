@@ -119,6 +119,13 @@ def _ptr_count(t):
     return (None, 0) if t is None else (t.data_ptr(), t.numel())
 
 
+def _unfinished_ptr(t):
+    if t is None:
+        return None
+    assert t.dtype == torch.int32 and t.numel() >= 1 and t.is_contiguous()
+    return t.data_ptr()
+
+
 def _queues_record(queues):
     qrec = np.zeros(1, _lib.CLOSEST_QUEUES_DTYPE)
     for name, q in queues.items():
@@ -355,25 +362,43 @@ class WavefrontAggregate:
             self._name("intersect_closest_and_shadow_items_candidates"))
         return hits
 
-    def IntersectShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None):
+    def IntersectShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None,
+                          max_passes=None, unfinished=None):
         """IntersectShadowTr (wavefront/aggregate.cpp:70-88, TraceTransmittance of wavefront/intersect.h:
         164-274) without media: shadow rays pass through interface surfaces (CLASS_INTERFACE) and are
         blocked by the first surface with a material; arriving rays add Ld * (1 / (r_u + r_l).Average())
-        to L[pixel_index].  state: optional uint8 [capacity] out (0 arrived, 1 blocked, 2 host)."""
+        to L[pixel_index].  state: optional uint8 [capacity] out (0 arrived, 1 blocked, 2 host).
+
+        max_passes None: the host-driven loop (reads a count per pass; not graph-capturable).  max_passes 1..64:
+        nnbvh_wavefront_intersect_shadow_tr_bounded — exactly that many passes, kernel launches only (capturable
+        after one warm-up call); a ray whose walk needs more Intersect calls gets state 2 and adds nothing.
+        unfinished: optional int32 [1] device tensor, receives the number of such rays."""
         self._bvh_only("IntersectShadowTr")
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa = shadow_queue._wire()
         pc = self.prim_class
-        check(_lib.lib().nnbvh_wavefront_intersect_shadow_tr(
-            self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(),
-            *_ptr_count(pc), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(),
-            L.shape[0], state.data_ptr() if state is not None else None,
-            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_wavefront_intersect_shadow_tr")
+        args = (self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(),
+                *_ptr_count(pc), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(),
+                L.shape[0], state.data_ptr() if state is not None else None)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if max_passes is None:
+            assert unfinished is None, "unfinished belongs to the bounded form: pass max_passes"
+            check(_lib.lib().nnbvh_wavefront_intersect_shadow_tr(*args, stream), "nnbvh_wavefront_intersect_shadow_tr")
+        else:
+            check(_lib.lib().nnbvh_wavefront_intersect_shadow_tr_bounded(
+                *args, int(max_passes), _unfinished_ptr(unfinished), stream),
+                "nnbvh_wavefront_intersect_shadow_tr_bounded")
 
-    def IntersectOneRandom(self, max_items, p0, p1, material, shading_mesh, prim_material=None, size=None):
+    def IntersectOneRandom(self, max_items, p0, p1, material, shading_mesh, prim_material=None, size=None,
+                           max_passes=None, unfinished=None):
         """IntersectOneRandom (wavefront/aggregate.cpp:90-116): p0, p1 float32 [n, 3], material int32 [n]
         device tensors; prim_material int32 per primitive id.  Returns (selected hit records uint8
-        [n, 32], their segment rays uint8 [n, 32], reservoir pdf float32 [n], weight sum float32 [n])."""
+        [n, 32], their segment rays uint8 [n, 32], reservoir pdf float32 [n], weight sum float32 [n]).
+
+        max_passes None: the host-driven loop.  max_passes 1..64: nnbvh_wavefront_intersect_one_random_bounded —
+        exactly that many passes, kernel launches only; an item whose segment needs more Intersect calls gets
+        instance = -1 in its selected hit record (its pdf, weight sum and ray are then unspecified).
+        unfinished: optional int32 [1] device tensor, receives the number of such items."""
         self._bvh_only("IntersectOneRandom")
         for t in (p0, p1):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 3
@@ -384,10 +409,15 @@ class WavefrontAggregate:
         pdf = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
         wsum = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
         pm = prim_material
-        check(_lib.lib().nnbvh_wavefront_intersect_one_random(
-            self.aggregate._h, shading_mesh._h, n, p0.data_ptr(), p1.data_ptr(), material.data_ptr(),
-            size.data_ptr() if size is not None else None, *_ptr_count(pm), sel_hits.data_ptr(), sel_rays.data_ptr(),
-            pdf.data_ptr(),
-            wsum.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
-            "nnbvh_wavefront_intersect_one_random")
+        args = (self.aggregate._h, shading_mesh._h, n, p0.data_ptr(), p1.data_ptr(), material.data_ptr(),
+                size.data_ptr() if size is not None else None, *_ptr_count(pm), sel_hits.data_ptr(),
+                sel_rays.data_ptr(), pdf.data_ptr(), wsum.data_ptr())
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if max_passes is None:
+            assert unfinished is None, "unfinished belongs to the bounded form: pass max_passes"
+            check(_lib.lib().nnbvh_wavefront_intersect_one_random(*args, stream), "nnbvh_wavefront_intersect_one_random")
+        else:
+            check(_lib.lib().nnbvh_wavefront_intersect_one_random_bounded(
+                *args, int(max_passes), _unfinished_ptr(unfinished), stream),
+                "nnbvh_wavefront_intersect_one_random_bounded")
         return sel_hits, sel_rays, pdf, wsum
