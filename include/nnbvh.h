@@ -907,8 +907,8 @@ int nnbvh_kd_intersect_any_device(nnbvh_kd_scene *s, const void *d_rays, int64_t
  * scene: n = min(max_rays, max(*d_size, 0)), NULL queue sizes mean "not wanted", pushes beyond a capacity are counted
  * and not stored, each call is one asynchronous operation on `stream` without a host read-back, and the
  * closest_and_shadow forms trace both queues in one launch where option "pair_one_launch" is set (below).  A bad argument (NULL scene, negative or >= 2^28
- * max_rays, ...) returns NNBVH_ERR_ARG before any device call.  IntersectShadowTr / IntersectOneRandom and two-level
- * scenes are not offered for kd scenes; host candidates are (below). */
+ * max_rays, ...) returns NNBVH_ERR_ARG before any device call.  Two-level scenes are not offered for kd scenes; host
+ * candidates are (below), and IntersectShadowTr / IntersectOneRandom come as the walk calls (further below). */
 int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches, void *stream);
 /* tuning knobs (speed only, never results), as nnbvh_scene_set_option: "read_soa" (lean scenes: the kernel reads a
  * queue's SOA slices itself; 0, the default: gathered into records first), "pair_one_launch" (closest_and_shadow traces
@@ -994,6 +994,36 @@ int nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates(
     int32_t max_shadow_rays, const nnbvh_ray_soa *shadow_queue, const int32_t *d_shadow_size, const float *d_Ld,
     const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
     uint8_t *d_occluded /* required */, const nnbvh_host_candidates *shadow_c, void *stream);
+
+/* ---- kd-tree scenes: IntersectShadowTr / IntersectOneRandom walked inside ONE trace launch ----------------------
+ * The argument lists and outputs of nnbvh_wavefront_intersect_shadow_tr_bounded / _one_random_bounded on a kd scene,
+ * with max_surfaces (1..65536) in the place of max_passes.  The trace kernel's walk instances run the per-item loop
+ * inside the lane: a lane that has finished its closest hit on a surface the walk passes through computes pi / n,
+ * spawns the next ray and re-enters the tree with the same item.  A call is five kernel launches whatever
+ * max_surfaces is — queue-head reset, *d_unfinished reset, init, ONE walk launch, record / finish — with no copy, no
+ * memset, no synchronisation and, once the stream's workspace has its size, no allocation: after one warm-up call
+ * with the same max_rays / max_items the call can be captured in a hipGraph.
+ * An item is FINISHED iff the reference loop (intersect.h:183-256, aggregate.cpp:100-108) makes at most max_surfaces
+ * calls of Intersect for it; finished items get what the BVH calls give them for the same closest hits, bit for bit.
+ * An item that would start call max_surfaces + 1 gets the "caller's to finish" mark (state 2 and nothing added to L /
+ * instance = -1) and is counted in *d_unfinished (nullable); so are, uncounted, rays that reach a host-only
+ * primitive or a hit the mesh cannot finish.  max_rays == 0 zeroes *d_unfinished and returns NNBVH_OK.
+ * NNBVH_ERR_ARG with nothing launched: a NULL scene or mesh, max_surfaces outside 1..65536, a negative size, 2^28
+ * items or more, a NULL array with a non-zero size, a mesh on another device, a mesh with an instance table (kd
+ * scenes have one level), and a scene created with the attribute arrays its alpha-tested smooth triangles or
+ * alpha-tested patches read (the ATTR kernels have no walk instances; create the scene without those arrays and such
+ * primitives become host-only, state 2 / instance = -1). */
+int nnbvh_kd_wavefront_walk_shadow_tr(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                      const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                      const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
+                                      const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                      int64_t n_pixels, uint8_t *d_state, int32_t max_surfaces, int32_t *d_unfinished,
+                                      void *stream);
+int nnbvh_kd_wavefront_walk_one_random(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
+                                       const float *d_p0, const float *d_p1, const int32_t *d_material,
+                                       const int32_t *d_size, const int32_t *d_prim_material, int64_t n_prim_material,
+                                       void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum,
+                                       int32_t max_surfaces, int32_t *d_unfinished, void *stream);
 
 /* tuning knobs (speed only, never results): "stack_window" (LDS entries per lane: 4, 8, 16),
  * "blocks_per_cu" (0 = auto), "xcd_queues" (0/1), "prim_weight" / "refill_weight" (1..64: how much a

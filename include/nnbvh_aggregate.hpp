@@ -834,6 +834,27 @@ class HipKdTreeAggregate {
                                                                   dL, nPixels, dOccluded, stream) != NNBVH_OK)
             HipBVHAggregate::fatal("kd IntersectClosestAndShadowItemsQueues");
     }
+    // IntersectShadowTr / IntersectOneRandom walked inside ONE trace launch (nnbvh_kd_wavefront_walk_*): the
+    // arguments and outputs of HipBVHAggregate::IntersectShadowTrBounded / IntersectOneRandomBounded with
+    // maxSurfaces (1..65536) for maxPasses; hipGraph-capturable after one warm-up call
+    void WalkShadowTr(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &shadowQueue,
+                      const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass, const float *dLd,
+                      const float *dRu, const float *dRl, const int32_t *dPixelIndex, float *dL, int64_t nPixels,
+                      int maxSurfaces, void *stream, uint8_t *dState = nullptr, int32_t *dUnfinished = nullptr) const {
+        if (nnbvh_kd_wavefront_walk_shadow_tr(scene_, mesh, maxRays, &shadowQueue, dSize, dPrimClass, nPrimClass, dLd,
+                                              dRu, dRl, dPixelIndex, dL, nPixels, dState, maxSurfaces, dUnfinished,
+                                              stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd WalkShadowTr");
+    }
+    void WalkOneRandom(const nnbvh_shading_mesh *mesh, int maxItems, const float *dP0, const float *dP1,
+                       const int32_t *dMaterial, const int32_t *dSize, const int32_t *dPrimMaterial,
+                       int64_t nPrimMaterial, void *dSelHits, void *dSelRays, float *dReservoirPdf, int maxSurfaces,
+                       void *stream, float *dWeightSum = nullptr, int32_t *dUnfinished = nullptr) const {
+        if (nnbvh_kd_wavefront_walk_one_random(scene_, mesh, maxItems, dP0, dP1, dMaterial, dSize, dPrimMaterial,
+                                               nPrimMaterial, dSelHits, dSelRays, dReservoirPdf, dWeightSum,
+                                               maxSurfaces, dUnfinished, stream) != NNBVH_OK)
+            HipBVHAggregate::fatal("kd WalkOneRandom");
+    }
 
   private:
     explicit HipKdTreeAggregate(nnbvh_kd_scene *scene) : scene_(scene) { nnbvh_kd_scene_bounds(scene_, bounds_); }

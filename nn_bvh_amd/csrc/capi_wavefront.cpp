@@ -972,4 +972,107 @@ int nnbvh_wavefront_intersect_one_random_bounded(
     return NNBVH_OK;
 }
 
+// ---- the walk calls of a kd-tree scene: IntersectShadowTr / IntersectOneRandom inside ONE trace launch ---------------
+// The walk instances of the kd trace kernel (kd_trace.hip) run the per-item loop inside the lane, so
+// a call is five kernel nodes whatever max_surfaces is: queue-head reset, unfinished-count reset, init, walk, record /
+// finish.  Nothing waits for the device or copies from host memory; once the stream's workspace has its size (a
+// warm-up call with the same max_rays) nothing is allocated and the call can be captured in a hipGraph.
+static constexpr int kMaxWalkSurfaces = 65536;
+
+static bool kd_walk_args_ok(const char *fn, const nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
+                            int64_t n_prim, int32_t max_surfaces, bool arrays) {
+    const char *what = nullptr;
+    if (!s) what = "no scene";
+    else if (!m) what = "no shading mesh";
+    else if (max_surfaces < 1 || max_surfaces > kMaxWalkSurfaces) what = "max_surfaces outside 1..65536";
+    else if (max_items < 0 || n_prim < 0) what = "negative size";
+    else if (max_items >= (1 << kKdIndexBits)) what = "a queue of 2^28 items or more";
+    else if (max_items > 0 && !arrays) what = "null array";
+    else if (m->device != s->device) what = "scene and shading mesh live on different devices";
+    else if (m->d.instances) what = "the shading mesh carries an instance table (kd-tree scenes have one level)";
+    else if (s->d_extras)
+        what = "the scene holds alpha-tested smooth triangles or alpha-tested patches on the device (the ATTR kernels), "
+               "which have no walk instances";
+    if (what) set_error(std::string(fn) + ": " + what);
+    return !what;
+}
+
+int nnbvh_kd_wavefront_walk_shadow_tr(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                      const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                      const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
+                                      const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                      int64_t n_pixels, uint8_t *d_state, int32_t max_surfaces, int32_t *d_unfinished,
+                                      void *stream_) {
+    const char *fn = "kd_wavefront_walk_shadow_tr";
+    if (!kd_walk_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), max_surfaces,
+                         soa_ok(shadow_queue) && d_Ld && d_r_u && d_r_l && d_pixel_index && d_L))
+        return NNBVH_ERR_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    KdSceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_rays == 0) return NNBVH_OK;
+    const size_t n = (size_t)max_rays;
+    void *rays, *orig, *pLight, *state;
+    if (!kd_walk_scratch(call.w, 0, n * 32, &rays) || !kd_walk_scratch(call.w, 1, n * 4, &orig) ||
+        !kd_walk_scratch(call.w, 2, n * 16, &pLight) || !kd_walk_scratch(call.w, 3, n, &state))
+        return NNBVH_ERR_DEVICE;
+    const WavefrontCount cnt{max_rays, d_size};
+    // str_init: every ray's record, light point and state 0 (its item list is the identity and is not read)
+    if (!hip_ok(launch_str_init(*shadow_queue, cnt, rays, (int32_t *)orig, (float4 *)pLight, (uint8_t *)state, max_blocks,
+                                stream), "shadow-tr init launch"))
+        return NNBVH_ERR_DEVICE;
+    KdWalk walk;
+    walk.kind = 1, walk.mesh = &m->d, walk.rays = rays, walk.n = max_rays, walk.d_n = d_size;
+    walk.maxSurfaces = max_surfaces, walk.unfinished = d_unfinished;
+    walk.primClass = d_prim_class, walk.nPrimClass = (long)n_prim_class;
+    walk.pLight = (const float4 *)pLight, walk.state = (uint8_t *)state;
+    const int rc = kd_launch_walk(s, call.w, stream, walk);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
+                                  d_state, max_blocks, stream), "shadow-tr record launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_kd_wavefront_walk_one_random(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
+                                       const float *d_p0, const float *d_p1, const int32_t *d_material,
+                                       const int32_t *d_size, const int32_t *d_prim_material, int64_t n_prim_material,
+                                       void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum,
+                                       int32_t max_surfaces, int32_t *d_unfinished, void *stream_) {
+    const char *fn = "kd_wavefront_walk_one_random";
+    if (!kd_walk_args_ok(fn, s, m, max_items, n_prim_material, max_surfaces,
+                         d_p0 && d_p1 && d_material && d_sel_hits && d_sel_rays && d_reservoir_pdf))
+        return NNBVH_ERR_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    KdSceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_items == 0) return NNBVH_OK;
+    const size_t n = (size_t)max_items;
+    void *rays, *rng, *weights;
+    if (!kd_walk_scratch(call.w, 0, n * 32, &rays) || !kd_walk_scratch(call.w, 4, n * 16, &rng) ||
+        !kd_walk_scratch(call.w, 5, n * 8, &weights))
+        return NNBVH_ERR_DEVICE;
+    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};  // (the base interaction stays in registers)
+    const WavefrontCount cnt{max_items, d_size};
+    if (!hip_ok(launch_kd_or_init_all(d_p0, d_p1, cnt, st, rays, d_sel_hits, d_sel_rays, max_blocks, stream),
+                "one-random init launch"))
+        return NNBVH_ERR_DEVICE;
+    KdWalk walk;
+    walk.kind = 2, walk.mesh = &m->d, walk.rays = rays, walk.n = max_items, walk.d_n = d_size;
+    walk.maxSurfaces = max_surfaces, walk.unfinished = d_unfinished;
+    walk.p1 = d_p1, walk.material = d_material, walk.primMaterial = d_prim_material;
+    walk.nPrimMaterial = (long)n_prim_material, walk.st = st, walk.selHits = d_sel_hits, walk.selRays = d_sel_rays;
+    const int rc = kd_launch_walk(s, call.w, stream, walk);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
 }  // extern "C"

@@ -31,6 +31,7 @@
 #include "bvh_trace.h"
 #include "kd_trace.h"
 #include "wavefront.h"
+#include "walk_math.h"
 
 namespace nnbvh {
 
@@ -81,6 +82,21 @@ struct KdParams {
     int32_t *bHcBefore[kKdMaxBatches];       // closest batches only
     int32_t *bHcPrim[kKdMaxBatches];
     int32_t *bHcInst[kKdMaxBatches];
+    // walk mode (the WALK instances), appended again: the shading mesh the hit's pi / n come from and
+    // the per-item arrays of the walk.  One batch; a lane's ray tag is its work item
+    MeshView wMesh;
+    const uint8_t *wPrimClass;       // WALK 1: class per primitive id, nullable
+    long wNPrimClass;
+    const float4 *wPLight;           // WALK 1: the light point of each item
+    uint8_t *wState;                 // WALK 1: 0 at launch; 1 blocked, 2 the caller's to finish
+    const float *wP1;                // WALK 2: the segment's end point of each item
+    const int32_t *wMaterial;        // WALK 2: the material each item looks for
+    const int32_t *wPrimMaterial;    // WALK 2: material per primitive id, nullable
+    long wNPrimMaterial;
+    OneRandomState wSt;              // WALK 2: PCG32 state and reservoir weights per item
+    float4 *wSelHits, *wSelRays;     // WALK 2: selected hit record and its segment ray per item
+    int wMaxSurfaces;                // Intersect calls an item may make
+    int32_t *wUnfinished;            // nullable: counts the items that would start one more
 };
 
 // util/vecmath.h:1547-1571 with invRayDir = 1 / d[i] taken from the ray's precomputed reciprocals
@@ -108,6 +124,42 @@ DEV bool kd_root_interval(const float bmin[3], const float bmax[3], V3 o, V3 inv
     return true;
 }
 
+// A lane takes up the ray {R0, R1} = {o, tMax} {d, time}: the reciprocals (aggregates.cpp:980), the shear, the
+// `ray.d[axis] <= 0` bits of aggregates.cpp:1002-1003, cold hit slots, zeroed counts and the root interval (:975-977:
+// rays that miss the tree's bounds return before anything is counted).  Used at a refill and, in the walk instances,
+// when an item's walk goes on with its spawned ray.  A macro and not a lambda or a function: the refill path of the
+// existing instances then compiles to the code it compiled to before the walk instances shared it.
+#define KD_BEGIN_RAY(R0, R1)                                                                                          \
+    do {                                                                                                              \
+        r.o = {(R0).x, (R0).y, (R0).z};                                                                               \
+        rayTMax = (R0).w;                                                                                             \
+        const V3 dir = {(R1).x, (R1).y, (R1).z};                                                                      \
+        if (PATCH) d = dir;                                                                                           \
+        r.inv = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z};                                                           \
+        ray_shear(r, dir);                                                                                            \
+        r.kz |= (dir.x <= 0.0f ? 16 : 0) | (dir.y <= 0.0f ? 32 : 0) | (dir.z <= 0.0f ? 64 : 0);                       \
+        if constexpr (BATCH) r.kz |= ((p.anyMask >> curBatch) & 1u) ? kAnyLane : 0;                                   \
+        if (MODE != 1) {                                                                                              \
+            cold[kColdHit][lane] = __int_as_float(-1);                                                                \
+            cold[kColdHit + 1][lane] = 0.0f;                                                                          \
+            cold[kColdHit + 2][lane] = 0.0f;                                                                          \
+            cold[kColdHit + 3][lane] = 0.0f;                                                                          \
+        }                                                                                                             \
+        if (HOSTC || p.hasHostPrims) cold[kColdHost][lane] = 0.0f;                                                    \
+        if constexpr (WALK != 0) {                                                                                    \
+            cold[kColdDir][lane] = (R1).x;                                                                            \
+            cold[kColdDir + 1][lane] = (R1).y;                                                                        \
+            cold[kColdDir + 2][lane] = (R1).z;                                                                        \
+            cold[kColdTime][lane] = (R1).w;                                                                           \
+            cold[kColdTMax][lane] = (R0).w;                                                                           \
+        }                                                                                                             \
+        visited = 0;                                                                                                  \
+        tests = 0;                                                                                                    \
+        found = false;                                                                                                \
+        sp = base = 0;                                                                                                \
+        cur = kd_root_interval(p.bmin, p.bmax, r.o, r.inv, rayTMax, tMin, tMax) ? 0 : kKdDone;                        \
+    } while (0)
+
 // MODE 0: closest hit; MODE 1: any hit (counts written when asked for).
 // MODE 2 / 3: batch mode.  One launch drains up to kKdMaxBatches independent batches in list order, each closest-hit
 // or any-hit, each with its own eight queue heads and a size that may live on the device (the kernel reads it).  The
@@ -131,9 +183,18 @@ DEV bool kd_root_interval(const float bmin[3], const float bmax[3], V3 o, V3 inv
 // how many came before it (p.bHcBefore).  At retire the count goes to p.bHcCount: 0..K, -1 = more than K (record
 // void), -2 = an alpha re-trace voided the ray.  A batch with bHcCap[b] == 0 is a plain batch: its first host-only
 // primitive "overflows" a list of none.
+// MODE 4 / 5 = MODE 2 with WALK = 1 / 2 (one closest-hit batch, no ATTR, no HOSTC): the walk instances.  A lane does not retire
+// its ray when the closest-hit walk is finished: it runs one step of IntersectShadowTr (1) or IntersectOneRandom (2)
+// for its work item (walk_math.h: the verdicts and arithmetic of the fused pass steps of wavefront2.hip) and, where
+// the item's walk goes on, re-enters the tree with the spawned ray.  Nothing is written to bOut.  PATCH = 1 instances
+// compute the interaction with the patch-capable code (FULL), the lean ones with the triangle-only code.
+// (WALK rides in MODE — MODE 4 = MODE 2 with WALK 1, MODE 5 = MODE 2 with WALK 2 — and not as a seventh template
+// parameter: that would rename every existing instance.)
 template <int MODE, int PATCH, int W, int O32, int ATTR = 0, int HOSTC = 0>
 __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdParams p) {
+    constexpr int WALK = MODE >= 4 ? MODE - 3 : 0;
     static_assert(!HOSTC || MODE == 2, "candidate mode: the record-reading batch instances only");
+    static_assert(!WALK || (!ATTR && !HOSTC), "walk instances: the plain record-reading batch form only");
     auto pick_batch = [](const auto &arr, int b) {  // arr[b] of a kernel-argument array
         return b == 0 ? arr[0] : (b == 1 ? arr[1] : (b == 2 ? arr[2] : arr[3]));
     };
@@ -146,9 +207,13 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
     __shared__ float s_stack[kKdBlock / 64][W][3][64];
     // cold per-ray state ([field][lane]): ray index, best hit (closest), reached-a-host-primitive flag
     constexpr bool BATCH = MODE >= 2, SOA = MODE == 3;
-    static_assert(MODE >= 0 && MODE <= 3 && (!SOA || (!PATCH && !ATTR)), "SOA instances: the lean form only");
+    static_assert(MODE >= 0 && MODE <= 5 && (!SOA || (!PATCH && !ATTR)), "SOA instances: the lean form only");
     constexpr int kAnyLane = 128;  // BATCH: bit 7 of r.kz
-    constexpr int kColdRi = 0, kColdHit = 1, kColdHost = (MODE != 1) ? 5 : 1, kColdFields = kColdHost + 1;
+    // WALK: six more slots — the direction, time and tMax of the item's current ray (the step needs them for wo, the
+    // selected segment ray and the next ray) and the number of Intersect calls made for the item
+    constexpr int kColdRi = 0, kColdHit = 1, kColdHost = (MODE != 1) ? 5 : 1, kColdWalk = kColdHost + 1;
+    constexpr int kColdDir = kColdWalk, kColdTime = kColdWalk + 3, kColdTMax = kColdWalk + 4, kColdCalls = kColdWalk + 5;
+    constexpr int kColdFields = kColdWalk + (WALK ? 6 : 0);
     __shared__ float s_cold[kKdBlock / 64][kColdFields][64];
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -214,9 +279,44 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
         if (nIdle == 64 || (sR > sI && sR > sP)) {
             // ---- retire finished rays, refill idle lanes ------------------------------------
             const int ri = isIdle ? __float_as_int(cold[kColdRi][lane]) : -1;
+            // WALK: the lane's item walks on from nextO in direction nextD / would start call wMaxSurfaces + 1
+            [[maybe_unused]] bool goOn = false, capped = false;
+            [[maybe_unused]] V3 nextO = {0.0f, 0.0f, 0.0f}, nextD = {0.0f, 0.0f, 0.0f};
+            [[maybe_unused]] float nextTMax = 1.0f, nextTime = 0.0f;  // aggregate.Intersect(r, 1), time 0: WALK 2
             if (ri >= 0) {
                 const bool needHost = p.hasHostPrims && cold[kColdHost][lane] != 0.0f;
-                if constexpr (HOSTC) {
+                if constexpr (WALK != 0) {
+                    // one step of the walk for item ri (the tag of the one batch is the index), on the hit record a
+                    // MODE 2 closest lane would retire
+                    const float4 r0 = {r.o.x, r.o.y, r.o.z, cold[kColdTMax][lane]};
+                    const float4 r1 = {cold[kColdDir][lane], cold[kColdDir + 1][lane], cold[kColdDir + 2][lane],
+                                       cold[kColdTime][lane]};
+                    const float4 h0 = {cold[kColdHit][lane], rayTMax, cold[kColdHit + 1][lane], cold[kColdHit + 2][lane]};
+                    const float4 h1 = {cold[kColdHit + 3][lane], __int_as_float(visited), __int_as_float(tests),
+                                       needHost ? __int_as_float(-1) : 0.0f};
+                    if constexpr (WALK == 1) {
+                        goOn = w2_str_item<PATCH != 0>(p.wMesh, r0, r1, h0, h1, ri, p.wPrimClass, p.wNPrimClass,
+                                                       p.wPLight, p.wState, nextO, nextD);
+                        nextTMax = r0.w;  // tMax is the work item's, unchanged (intersect.h:175, :187)
+                        nextTime = r1.w;
+                        // the spawned ray has a zero direction: the walk ends, the ray arrives (state stays 0)
+                        if (goOn && nextD.x == 0.0f && nextD.y == 0.0f && nextD.z == 0.0f) goOn = false;
+                    } else {
+                        goOn = w2_or_item<PATCH != 0>(p.wMesh, r0, r1, h0, h1, ri, p.wP1, p.wMaterial, p.wPrimMaterial,
+                                                      p.wNPrimMaterial, p.wSt, p.wSelHits, p.wSelRays, nextO, nextD);
+                    }
+                    if (goOn) {
+                        const int calls = __float_as_int(cold[kColdCalls][lane]);
+                        if (calls >= p.wMaxSurfaces) {  // the caller's to finish, as w2_mark_unfinished marks it
+                            goOn = false;
+                            capped = true;
+                            if constexpr (WALK == 1) p.wState[ri] = 2;
+                            else p.wSelHits[2 * (long)ri + 1].w = __int_as_float(-1);
+                        } else {
+                            cold[kColdCalls][lane] = __int_as_float(calls + 1);
+                        }
+                    }
+                } else if constexpr (HOSTC) {
                     // candidate mode, a block of its own so that the plain instances' retire below stays as it is:
                     // the count goes to the batch's array; an any-hit ray is the caller's (2) when it met a host-only
                     // primitive, a closest-hit record is void only for count < 0
@@ -288,8 +388,32 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                 }
             }
             int newRi = -1;
-            if (exhausted) break;  // only reached with every lane idle
+            // the lanes that take a new ray, their number and mask: the idle ones, less (WALK) those that walk on
+            bool takes = isIdle;
+            unsigned long long takeMask = idleMask;
+            int nTake = nIdle;
+            if constexpr (WALK != 0) {
+                const unsigned long long cm = __ballot(capped);
+                if (p.wUnfinished && cm != 0ull && lane == __ffsll((long long)cm) - 1) atomicAdd(p.wUnfinished, __popcll(cm));
+                if (goOn) {  // same item, same lane: cold[kColdRi] stays
+                    const float4 a = {nextO.x, nextO.y, nextO.z, nextTMax}, b = {nextD.x, nextD.y, nextD.z, nextTime};
+                    KD_BEGIN_RAY(a, b);
+                }
+                takes = isIdle && !goOn;
+                takeMask = __ballot(takes);
+                nTake = __popcll(takeMask);
+                if (exhausted) {  // every lane was idle: the wave ends when none of them walks on
+                    if (nTake == 64) break;
+                    if (takes) cold[kColdRi][lane] = __int_as_float(-1);  // retired: the step must not run on it again
+                    continue;
+                }
+            } else {
+                if (exhausted) break;  // only reached with every lane idle
+            }
             for (;;) {
+                if constexpr (WALK != 0) {
+                    if (nTake == 0) break;
+                }
                 static_assert(kKdQueues == 8, "queue ranges are computed with a shift by 3");
                 const int qShift = p.nQueues > 1 ? 3 : 0;  // nQueues is 1 or 8: a shift, not a 64-bit division
                 long nQ = nRays;
@@ -302,13 +426,13 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                 }
                 const long qBegin = (nQ * q) >> qShift, qEnd = (nQ * (q + 1)) >> qShift;
                 unsigned got = 0;
-                if (lane == 0) got = atomicAdd(&p.queue[((BATCH ? curBatch * p.nQueues : 0) + q) * kKdQueueStride], (unsigned)nIdle);
+                if (lane == 0) got = atomicAdd(&p.queue[((BATCH ? curBatch * p.nQueues : 0) + q) * kKdQueueStride], (unsigned)nTake);
                 got = __builtin_amdgcn_readfirstlane(got);
                 const long start = qBegin + (long)got;
                 if (start < qEnd) {
-                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idleMask >> 32),
-                                                               __builtin_amdgcn_mbcnt_lo((unsigned)idleMask, 0u));
-                    if (isIdle && start + rank < qEnd) newRi = (int)(start + rank);
+                    const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(takeMask >> 32),
+                                                               __builtin_amdgcn_mbcnt_lo((unsigned)takeMask, 0u));
+                    if (takes && start + rank < qEnd) newRi = (int)(start + rank);
                     break;
                 }
                 if (++queuesTried >= p.nQueues) {
@@ -324,7 +448,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                 }
                 q = (q + 1 == p.nQueues) ? 0 : q + 1;
             }
-            if (isIdle) cold[kColdRi][lane] = __int_as_float((BATCH && newRi >= 0) ? (newRi | (curBatch << kKdIndexBits)) : newRi);
+            if (takes) cold[kColdRi][lane] = __int_as_float((BATCH && newRi >= 0) ? (newRi | (curBatch << kKdIndexBits)) : newRi);
             if (newRi >= 0) {
                 float4 r0, r1;
                 if constexpr (SOA) {  // a wavefront queue: SOA<Ray> slices (wavefront/workitems.soa:40-50)
@@ -336,28 +460,18 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                     r0 = in[0];
                     r1 = in[1];
                 }
-                r.o = {r0.x, r0.y, r0.z};
-                rayTMax = r0.w;
-                const V3 dir = {r1.x, r1.y, r1.z};
-                if (PATCH) d = dir;
-                r.inv = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z};  // aggregates.cpp:980
-                ray_shear(r, dir);
-                // `ray.d[axis] <= 0` of aggregates.cpp:1002-1003, once per ray
-                r.kz |= (dir.x <= 0.0f ? 16 : 0) | (dir.y <= 0.0f ? 32 : 0) | (dir.z <= 0.0f ? 64 : 0);
-                if constexpr (BATCH) r.kz |= ((p.anyMask >> curBatch) & 1u) ? kAnyLane : 0;
-                if (MODE != 1) {
-                    cold[kColdHit][lane] = __int_as_float(-1);
-                    cold[kColdHit + 1][lane] = 0.0f;
-                    cold[kColdHit + 2][lane] = 0.0f;
-                    cold[kColdHit + 3][lane] = 0.0f;
+                if constexpr (WALK != 0) {
+                    // `while (ray.d != Vector3f(0, 0, 0))`, intersect.h:183 / aggregate.cpp:100: a zero direction makes
+                    // no Intersect call — the item is finished as the init kernel left it, the lane stays idle
+                    if (r1.x == 0.0f && r1.y == 0.0f && r1.z == 0.0f) {
+                        cold[kColdRi][lane] = __int_as_float(-1);
+                    } else {
+                        cold[kColdCalls][lane] = __int_as_float(1);
+                        KD_BEGIN_RAY(r0, r1);
+                    }
+                } else {
+                    KD_BEGIN_RAY(r0, r1);
                 }
-                if (HOSTC || p.hasHostPrims) cold[kColdHost][lane] = 0.0f;  // candidate mode: count 0
-                visited = 0;
-                tests = 0;
-                found = false;
-                sp = base = 0;
-                // :975-977: rays that miss the tree's bounds return before anything is counted
-                cur = kd_root_interval(p.bmin, p.bmax, r.o, r.inv, rayTMax, tMin, tMax) ? 0 : kKdDone;
             }
             continue;
         }
@@ -569,6 +683,8 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
         }
     }
 }
+
+#undef KD_BEGIN_RAY
 
 __global__ void kd_zero_queue_kernel(unsigned *queue, int words) {
     for (int i = threadIdx.x; i < words; i += blockDim.x) queue[i] = 0u;
@@ -950,6 +1066,8 @@ void nnbvh_kd_scene_destroy(nnbvh_kd_scene *s) {
         KdWorkspace &w = kv.second;
         for (void *ptr : {(void *)w.queue, (void *)w.spill, w.d_in, w.d_out, w.d_aux0, w.d_aux1, w.d_hits})
             if (ptr) (void)hipFree(ptr);
+        for (void *ptr : w.walk)
+            if (ptr) (void)hipFree(ptr);
     }
     if (s->d_nodes) (void)hipFree(s->d_nodes);
     if (s->d_indices) (void)hipFree(s->d_indices);
@@ -1206,3 +1324,104 @@ int nnbvh_kd_intersect_any(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, 
 }
 
 }  // extern "C"
+
+// ---- the walk calls' launchers (capi_wavefront.cpp: nnbvh_kd_wavefront_walk_*).  They stand last in the file so that
+// the kernels above keep their places in the compiler's output ----------------------------------------------------
+namespace nnbvh {
+
+// or_init (wavefront2.hip) for the walk instances: EVERY item's first segment ray goes to rays[i], a zero direction
+// included (the walk kernel ends such an item at its fetch), so there is no list to compact and nothing to count.
+// The per-item base interaction is not kept: the walk step has pi / n in registers.  (A template, so that it is emitted
+// with the walk instances behind the existing kernels.)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void kd_or_init_all(const float *p0, const float *p1, WavefrontCount cnt,
+                                                      OneRandomState st, float4 *rays, float4 *selHits,
+                                                      float4 *selRays) {
+    int n = cnt.n;
+    if (cnt.nDev) {
+        const int nd = *cnt.nDev;
+        n = nd < 0 ? 0 : (nd < n ? nd : n);
+    }
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const V3 a0 = {p0[3 * (long)i], p0[3 * (long)i + 1], p0[3 * (long)i + 2]};
+        const V3 a1 = {p1[3 * (long)i], p1[3 * (long)i + 1], p1[3 * (long)i + 2]};
+        Pcg32 g;  // WeightedReservoirSampler wrs(Hash(w.p0, w.p1)), aggregate.cpp:94-96
+        pcg32_set_sequence(g, hash_6f(a0, a1));
+        st.rng[2 * (long)i] = g.state;
+        st.rng[2 * (long)i + 1] = g.inc;
+        st.weights[2 * (long)i] = 0.0f;
+        st.weights[2 * (long)i + 1] = 0.0f;
+        selHits[2 * (long)i] = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
+        selHits[2 * (long)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        selRays[2 * (long)i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        selRays[2 * (long)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        V3 o, d;
+        spawn_ray_to(a0, a0, {0.0f, 0.0f, 0.0f}, a1, o, d);  // r = Interaction(w.p0).SpawnRayTo(w.p1), :97-99
+        rays[2 * (long)i] = make_float4(o.x, o.y, o.z, 1.0f);  // aggregate.Intersect(r, 1), :102
+        rays[2 * (long)i + 1] = make_float4(d.x, d.y, d.z, 0.0f);
+    }
+}
+
+}  // namespace nnbvh
+
+hipError_t nnbvh::launch_kd_or_init_all(const float *p0, const float *p1, WavefrontCount cnt, OneRandomState st,
+                                        void *rays, void *selHits, void *selRays, int maxBlocks, hipStream_t stream) {
+    int blocks = (cnt.n + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks < maxBlocks ? blocks : maxBlocks);
+    hipLaunchKernelGGL(kd_or_init_all<256>, dim3(blocks), dim3(256), 0, stream, p0, p1, cnt, st, (float4 *)rays,
+                       (float4 *)selHits, (float4 *)selRays);
+    return hipGetLastError();
+}
+
+bool nnbvh::kd_walk_scratch(KdWorkspace *w, int slot, size_t bytes, void **out) {
+    if (!kd_grow(&w->walk[slot], &w->walk_bytes[slot], std::max<size_t>(bytes, 16), "hipMalloc(walk workspace)"))
+        return false;
+    *out = w->walk[slot];
+    return true;
+}
+
+int nnbvh::kd_launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdWalk &k) {
+    KdParams p{};
+    kd_fill_scene(s, w, p);
+    p.nBatches = 1;
+    p.anyMask = 0;
+    p.bRays[0] = (const nnbvh_ray *)k.rays;
+    p.bN[0] = (long)k.n;
+    p.bNDev[0] = k.d_n;
+    const ShadingMeshDevice &m = *k.mesh;
+    p.wMesh = {m.verts, m.triVerts, m.patchVerts, m.normals, m.uvs, m.tangents, m.faceIndices, m.triFlags, m.nTris,
+               m.defaultFlags, nullptr, 0, nullptr, nullptr};  // kd scenes have one level
+    p.wPrimClass = k.primClass;
+    p.wNPrimClass = k.nPrimClass;
+    p.wPLight = k.pLight;
+    p.wState = k.state;
+    p.wP1 = k.p1;
+    p.wMaterial = k.material;
+    p.wPrimMaterial = k.primMaterial;
+    p.wNPrimMaterial = k.nPrimMaterial;
+    p.wSt = k.st;
+    p.wSelHits = (float4 *)k.selHits;
+    p.wSelRays = (float4 *)k.selRays;
+    p.wMaxSurfaces = k.maxSurfaces;
+    p.wUnfinished = k.unfinished;
+    // the lean instance with the triangle-only interaction where neither the scene nor the mesh holds patches, else the
+    // PATCH = 1 instance with the patch-capable one (launch_str_step's choice of FULL); each with both offset widths
+    void (*const kernels[8])(KdParams) = {
+        kd_trace_kernel<4, 0, kKdWLean, 0>, kd_trace_kernel<4, 1, kKdW, 0>, kd_trace_kernel<4, 0, kKdWLean, 1>,
+        kd_trace_kernel<4, 1, kKdW, 1>,     kd_trace_kernel<5, 0, kKdWLean, 0>, kd_trace_kernel<5, 1, kKdW, 0>,
+        kd_trace_kernel<5, 0, kKdWLean, 1>, kd_trace_kernel<5, 1, kKdW, 1>};
+    const int full = (s->has_patches || m.patchVerts) ? 1 : 0;
+    void (*const kernel)(KdParams) = kernels[4 * (k.kind - 1) + 2 * s->fits32 + full];
+    const int slot = 5 + 2 * (k.kind - 1) + full;
+    if (s->blocks_per_cu[slot] == 0) {
+        int occ = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kKdBlock, 0);
+        s->blocks_per_cu[slot] = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
+    }
+    int blocks = s->n_cus * s->blocks_per_cu[slot];
+    const int64_t need = (k.n + kKdBlock - 1) / kKdBlock;
+    if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
+    hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, w->queue, kKdQueues * kKdQueueStride);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
+    return kd_hip_ok(hipGetLastError(), "kd walk kernel launch") ? NNBVH_OK : NNBVH_ERR_DEVICE;
+}

@@ -18,6 +18,7 @@
 
 #include "interaction_math.h"
 #include "spawn_math.h"
+#include "walk_math.h"
 #include "wavefront2.h"
 
 namespace nnbvh {
@@ -327,24 +328,7 @@ __global__ __launch_bounds__(kW2Block) void or_finish(WavefrontCount cnt, OneRan
 // interaction in registers: only pi and n are used, so the other fields' arithmetic is dead code and no
 // 192-byte record is written or read back.  The arithmetic is interaction_math.h's, as in the post-pass.
 
-// pi low / high and n of the SurfaceInteraction of hit {h0, h1} of the ray whose second half is r1;
-// false: a hit the device cannot finish (the post-pass's status is neither TRIANGLE nor PATCH)
-template <bool FULL>
-__device__ __forceinline__ bool w2_hit_pi_n(const MeshView &m, float4 h0, float4 h1, float4 r1, V3 &lo, V3 &hi,
-                                            V3 &n) {
-    const int prim = __float_as_int(h0.x);
-    const int status = imath::interaction_status<FULL>(m, prim, __float_as_int(h1.w));
-    if (status != NNBVH_INTERACTION_TRIANGLE && status != NNBVH_INTERACTION_PATCH) return false;
-    nnbvh_interaction r;
-    __builtin_memset(&r, 0, sizeof r);
-    bool ok = false;
-    imath::surface_interaction<FULL>(m, status, prim, h0, h1, imath::F3{-r1.x, -r1.y, -r1.z}, r1.w, r,
-                                     [&](int final_status) { ok = final_status != NNBVH_INTERACTION_HOST; });
-    lo = {r.pi_lo[0], r.pi_lo[1], r.pi_lo[2]};
-    hi = {r.pi_hi[0], r.pi_hi[1], r.pi_hi[2]};
-    n = {r.n[0], r.n[1], r.n[2]};
-    return ok;
-}
+// (w2_hit_pi_n: walk_math.h, shared with the walk instances of the kd-tree trace kernel)
 
 template <bool FULL>
 __global__ __launch_bounds__(kW2Block) void str_step(MeshView m, const float4 *raysCur, const float4 *hitsCur,

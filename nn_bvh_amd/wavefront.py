@@ -195,8 +195,8 @@ def record_shadow(max_rays, shadow_queue, occluded, Ld, r_u, r_l, pixel_index, L
 
 class WavefrontAggregate:
     """IntersectClosest / IntersectShadow of wavefront/integrator.h:32-54 on one BVHAggregate or KdTreeAggregate
-    (a kd scene offers the five queue calls and the three *WithCandidates ones; IntersectShadowTr and
-    IntersectOneRandom raise NNBVHError for it).
+    (a kd scene offers the five queue calls, the three *WithCandidates ones and WalkShadowTr / WalkOneRandom;
+    IntersectShadowTr and IntersectOneRandom raise NNBVHError for it, WalkShadowTr / WalkOneRandom for a BVH scene).
 
     prim_class: optional uint8 per primitive id (nn_bvh_amd._lib.CLASS_*), what the reference
     reads off the hit's SurfaceInteraction when it decides the destination queues."""
@@ -222,7 +222,13 @@ class WavefrontAggregate:
     def _bvh_only(self, method):
         if self._prefix != "nnbvh_wavefront_":
             raise _lib.NNBVHError(f"WavefrontAggregate.{method} is not offered for kd-tree scenes (DESIGN.md §8): "
-                                  "bind a BVH aggregate for it")
+                                  f"call Walk{method[len('Intersect'):]} (the walk inside one trace launch), or bind "
+                                  "a BVH aggregate")
+
+    def _kd_only(self, method):
+        if self._prefix != "nnbvh_kd_wavefront_":
+            raise _lib.NNBVHError(f"WavefrontAggregate.{method} is not offered for BVH scenes (DESIGN.md §8): call "
+                                  f"Intersect{method[len('Walk'):]} with max_passes")
 
     def IntersectClosest(self, max_rays, ray_queue, escaped=None, hit_area_light=None,
                          basic_eval_material=None, universal_eval_material=None, medium_sample=None,
@@ -420,4 +426,44 @@ class WavefrontAggregate:
             check(_lib.lib().nnbvh_wavefront_intersect_one_random_bounded(
                 *args, int(max_passes), _unfinished_ptr(unfinished), stream),
                 "nnbvh_wavefront_intersect_one_random_bounded")
+        return sel_hits, sel_rays, pdf, wsum
+
+    def WalkShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None,
+                     max_surfaces=65536, unfinished=None):
+        """IntersectShadowTr on a KdTreeAggregate, walked inside ONE trace launch (nnbvh_kd_wavefront_walk_shadow_tr):
+        the arguments and results of IntersectShadowTr(max_passes=...), with max_surfaces (1..65536) Intersect calls
+        per ray in the place of the passes.  A ray whose walk would start one more call gets state 2, adds nothing
+        and is counted in unfinished (optional int32 [1] device tensor).  Kernel launches only: capturable after one
+        warm-up call with the same max_rays."""
+        self._kd_only("WalkShadowTr")
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
+        soa = shadow_queue._wire()
+        pc = self.prim_class
+        check(_lib.lib().nnbvh_kd_wavefront_walk_shadow_tr(
+            self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(), *_ptr_count(pc),
+            Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0],
+            state.data_ptr() if state is not None else None, int(max_surfaces), _unfinished_ptr(unfinished),
+            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_kd_wavefront_walk_shadow_tr")
+
+    def WalkOneRandom(self, max_items, p0, p1, material, shading_mesh, prim_material=None, size=None,
+                      max_surfaces=65536, unfinished=None):
+        """IntersectOneRandom on a KdTreeAggregate, walked inside ONE trace launch
+        (nnbvh_kd_wavefront_walk_one_random): the arguments and the four returned tensors of
+        IntersectOneRandom(max_passes=...), with max_surfaces (1..65536) Intersect calls per item in the place of the
+        passes.  An item whose segment would start one more call gets instance = -1 in its selected hit record and
+        is counted in unfinished."""
+        self._kd_only("WalkOneRandom")
+        for t in (p0, p1):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 3
+        assert material.dtype == torch.int32 and material.is_contiguous()
+        n = int(max_items)
+        sel_hits = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
+        sel_rays = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
+        pdf = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
+        wsum = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
+        check(_lib.lib().nnbvh_kd_wavefront_walk_one_random(
+            self.aggregate._h, shading_mesh._h, n, p0.data_ptr(), p1.data_ptr(), material.data_ptr(),
+            size.data_ptr() if size is not None else None, *_ptr_count(prim_material), sel_hits.data_ptr(),
+            sel_rays.data_ptr(), pdf.data_ptr(), wsum.data_ptr(), int(max_surfaces), _unfinished_ptr(unfinished),
+            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_kd_wavefront_walk_one_random")
         return sel_hits, sel_rays, pdf, wsum
