@@ -20,6 +20,7 @@
 // the reference produces because the same libstdc++ std::partition / std::nth_element are
 // driven by the same predicates on the same float32 values.
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -116,6 +117,7 @@ struct Builder {
     Arena main_arena;
     std::mutex mu;
     std::vector<std::unique_ptr<Arena>> thread_arenas;
+    std::atomic<bool> sah_costs_not_finite{false};  // a node without a minimum-cost split: see kSahCostsErrorText
     static constexpr size_t kParallelAbove = 128 * 1024;  // aggregates.cpp:359
 
     BuildNode *alloc() {  // HLBVH path
@@ -207,6 +209,12 @@ struct Builder {
                         min_cost = costs[i];
                         best = i;
                     }
+                if (best == -1) {
+                    // every cost is +inf or NaN: partition(bucket <= -1) would put nothing on the left and
+                    // build(bp, 0) below would recurse for ever, as the reference does.  The build is refused.
+                    sah_costs_not_finite = true;
+                    return leaf(node, bp, n, bounds);
+                }
                 float leaf_cost = (float)n;
                 min_cost = 1.f / 2.f + min_cost / bounds.surface_area();
                 if ((int)n > max_prims || min_cost < leaf_cost) {
@@ -576,6 +584,10 @@ nnbvh_build *nnbvh_build_create_with_bounds(const nnbvh_prim *prims, int n_prims
     } else {
         b.bp_base = bp.data();
         root = b.build(bp.data(), bp.size());
+        if (b.sah_costs_not_finite) {
+            nnbvh::set_error(nnbvh::kSahCostsErrorText);
+            return nullptr;
+        }
     }
     auto t2 = now();
     auto *out = new nnbvh_build;

@@ -43,6 +43,14 @@ bool gpu_hlbvh(const nnbvh_prim *prims, int n_prims, const float *verts, int n_v
                const float *prim_bounds, int max_prims_in_node, int device, GpuBuildResult *out,
                std::string *error);
 
+// A SAH node none of whose 11 split costs is below +inf (count * surface area overflows for every split): the
+// reference's minCostSplitBucket stays -1 there (aggregates.cpp:343-353), its std::partition puts nothing on the
+// left and buildRecursive recurses on the same range for ever.  The host and the device builder evaluate the same
+// floats, refuse the same nodes and say so in the same words.
+constexpr const char *kSahCostsErrorText =
+    "nnbvh_build_create: coordinates too large for the SAH costs (count * surface area is not finite for any "
+    "split; the reference does not terminate on this input)";
+
 // SAH (buildRecursive's default branch) on the device; same tree and leaf order as the host builder.
 // ms: upload, big nodes breadth-first, subtrees (one wavefront each), layout + bounds, download;
 // n_treelets = subtrees built by wavefronts, n_unique_codes = nodes built breadth-first.

@@ -1089,7 +1089,12 @@ __global__ __launch_bounds__(kB) void k_seg_choose(int nSeg, int maxPrims, const
 struct SmallSeg {
     int start, n, pool;
 };
+// Pending second children: the first kSubtreeStack of a subtree's in LDS.  A left spine longer than that (only
+// primitives whose centroids grow geometrically make one) keeps the rest in the tree itself: the interior node that
+// waits for its second child holds the child's range in pmin[0..1] and the node below it on the stack in pmin[2],
+// fields phase C overwrites with the bounds.
 constexpr int kSubtreeStack = 64;
+constexpr int kSahCostsFlag = 3;  // err[3] (the builder's scalar block): a node without a finite split cost was met
 
 // sah_choose for a wavefront: lane i < 11 prices split i (the same additions in the same order as
 // the sequential loops: buckets 0..i ascending for the part below, 11..i+1 descending for the part
@@ -1153,6 +1158,7 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
     const SmallSeg sg = segs[s];
     nnbvh_linear_node *nodes = pool + sg.pool;
     int sp = 0, idx = 0, maxDepth = 0;
+    int top = -1;  // the node holding stack entry sp - 1, while sp > kSubtreeStack
     int start = sg.start, n = sg.n, depth = 0;
     for (;;) {
         const int me = idx++;
@@ -1212,6 +1218,7 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
         }
         bool leaf = hb_area(bounds) == 0 || n == 1;  // :221
         int dim = 0, mid = 0, best = 0;
+        bool refused = false;
         if (!leaf) {
             dim = hb_maxdim(cb);
             if (cb.mx[dim] == cb.mn[dim]) leaf = true;  // :243
@@ -1248,7 +1255,11 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
                 __syncthreads();
                 const SahChoice ch = sah_choose_wave(lane, bcount, bkeys, bounds, n, maxPrims);
                 __syncthreads();  // everyone has read the buckets before the next node clears them
-                if (!ch.split) {
+                if (ch.best < 0) {  // no split costs less than +inf: refused, as by the host builder
+                    if (lane == 0) err[kSahCostsFlag] = 1;  // a word of its own: no other block's error hides it
+                    refused = true;
+                    leaf = true;
+                } else if (!ch.split) {
                     leaf = true;
                 } else if (small) {
                     best = ch.best;
@@ -1310,20 +1321,24 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
             }
         }
         if (!leaf) {
+            const bool inLds = sp < kSubtreeStack;
             if (lane == 0) {
                 nnbvh_linear_node nd;
                 for (int k = 0; k < 3; ++k) nd.pmin[k] = nd.pmax[k] = 0;
+                if (!inLds) {
+                    nd.pmin[0] = __int_as_float(start + mid);
+                    nd.pmin[1] = __int_as_float(n - mid);
+                    nd.pmin[2] = __int_as_float(top);
+                }
                 nd.offset = 0;  // second child: set when it is created
                 nd.nprims = 0;
                 nd.axis = (uint8_t)dim;
                 nd.pad = (uint8_t)depth;  // carried to phase C, cleared there
                 nodes[me] = nd;
             }
-            if (sp >= kSubtreeStack) {
-                if (lane == 0) *err = 102;
-                break;
-            }
-            if (lane == 0) {
+            if (!inLds) {
+                top = me;
+            } else if (lane == 0) {
                 stStart[sp] = start + mid;
                 stN[sp] = n - mid;
                 stParent[sp] = me;
@@ -1365,17 +1380,30 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
                 nd.axis = 0;
                 nd.pad = (uint8_t)depth;
                 nodes[me] = nd;
-                if (n > 65535) *err = kErrLeafSize;
+                if (n > 65535 && !refused) *err = kErrLeafSize;
             }
             if (depth > maxDepth) maxDepth = depth;
         }
         if (sp == 0) break;
         --sp;
         __syncthreads();
-        start = stStart[sp];
-        n = stN[sp];
-        depth = stDepth[sp];
-        if (lane == 0) nodes[stParent[sp]].offset = idx;  // the node about to be created
+        if (sp >= kSubtreeStack) {  // the entry lives in the waiting node (written by lane 0 before a barrier)
+            const int parent = top;
+            start = __float_as_int(nodes[parent].pmin[0]);
+            n = __float_as_int(nodes[parent].pmin[1]);
+            top = __float_as_int(nodes[parent].pmin[2]);
+            depth = (int)nodes[parent].pad + 1;
+            __syncthreads();  // every lane has read the entry before lane 0 clears it
+            if (lane == 0) {
+                nodes[parent].pmin[0] = nodes[parent].pmin[1] = nodes[parent].pmin[2] = 0;
+                nodes[parent].offset = idx;
+            }
+        } else {
+            start = stStart[sp];
+            n = stN[sp];
+            depth = stDepth[sp];
+            if (lane == 0) nodes[stParent[sp]].offset = idx;  // the node about to be created
+        }
         __syncthreads();
     }
     if (lane == 0) {
@@ -1631,8 +1659,14 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
     std::vector<int> segCount((size_t)nSmall), segDepth((size_t)nSmall);
     GB_CHECK(hipMemcpyAsync(segCount.data(), dSegCount, (size_t)nSmall * sizeof(int), hipMemcpyDeviceToHost, stream), "read counts");
     GB_CHECK(hipMemcpyAsync(segDepth.data(), dSegDepth, (size_t)nSmall * sizeof(int), hipMemcpyDeviceToHost, stream), "read depths");
-    GB_CHECK(hipMemcpyAsync(&errNow, dErr, sizeof(int), hipMemcpyDeviceToHost, stream), "read error flag");
+    int errWords[kSahCostsFlag + 1] = {0, 0, 0, 0};
+    GB_CHECK(hipMemcpyAsync(errWords, dErr, sizeof errWords, hipMemcpyDeviceToHost, stream), "read error flag");
     GB_CHECK(hipStreamSynchronize(stream), "sync (subtrees)");
+    errNow = errWords[0];
+    if (errWords[kSahCostsFlag] != 0) {  // first, as on the host, whatever else another subtree reported
+        *error = kSahCostsErrorText;
+        return false;
+    }
     if (errNow != 0) {
         *error = errNow == kErrLeafSize ? "nnbvh_build_create: a leaf would hold more than 65535 primitives"
                                         : "gpu build: internal error " + std::to_string(errNow);

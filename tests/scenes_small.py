@@ -561,3 +561,115 @@ def kd_two_clusters(seed=0, n=400):
     v1, p1 = random_soup(n, 0, seed, extent=1.0, size=0.2)
     v2, p2 = random_soup(n, 0, seed + 1, extent=1.5, size=0.2)
     return merge((v1, p1), (v2 + np.array([60, 25, -40], np.float32), p2))
+
+
+# ---- BVH builder scenes: one per decision path of the SAH / HLBVH builders (tests/test_bvh_build_paths.py) --------
+# Every generator returns (verts, prims) with ids = positions.  The CPU tests there prove with a census of the
+# host-built tree that each scene reaches the path it is named for.
+def shifted(scene_, by):
+    """A (verts, prims) scene translated by a vector of small integers (exact for the dyadic coordinates used here)."""
+    v, p = scene_
+    return (np.asarray(v, np.float32) + np.asarray(by, np.float32)).astype(np.float32), p
+
+
+def bvh_overlapping(n, centre, seed, jitter=0.02):
+    """n triangles whose boxes all nearly fill the cube centre +- 1 (each face moved out by up to `jitter`): distinct
+    centroids, but no split separates anything, so every SAH split costs about n + 1/2 against a leaf's n."""
+    rng = np.random.default_rng(seed)
+    c = np.asarray(centre, np.float32)
+    lo = c - 1 - jitter * rng.random((n, 3)).astype(np.float32)
+    hi = c + 1 + jitter * rng.random((n, 3)).astype(np.float32)
+    return box_tris(lo, hi)
+
+
+def bvh_signed_zero_cluster(n=700, seed=12, x0=0.0):
+    """n triangles with the box [+-0, 1]^3 (one centroid): their minimum corner mixes +0 and -0 per axis.  x0 != 0
+    moves the cluster along x: its box starts at x0 there and keeps the mixed zeros on y and z."""
+    rng = np.random.default_rng(seed)
+    z = np.where(rng.random((n, 3)) < 0.5, 0.0, -0.0).astype(np.float32)
+    v = np.zeros((n, 3, 3), np.float32)
+    v[:, 0] = z
+    v[:, 1] = [1, 1, 0]
+    v[:, 2] = [1, 0, 1]
+    v[:, 1, 2] = z[:, 2]
+    v[:, 2, 1] = z[:, 1]
+    if x0:
+        v[:, :, 0] += np.float32(x0)
+    return v.reshape(-1, 3), make_prims(np.arange(3 * n, dtype=np.int32).reshape(n, 3))
+
+
+def bvh_signed_zero_row(n=96, seed=0, x0=14.0, pitch=1.5):
+    """A row of unit boxes along x whose y and z start at +-0, signs mixed: every interior node above them joins two
+    children that both supply the zero, often with different signs."""
+    rng = np.random.default_rng(seed)
+    lo = np.where(rng.random((n, 3)) < 0.5, 0.0, -0.0).astype(np.float32)
+    lo[:, 0] = x0 + pitch * np.arange(n)
+    hi = np.ones((n, 3), np.float32)
+    hi[:, 0] = lo[:, 0] + 1
+    return box_tris(lo, hi)
+
+
+def bvh_leaf_rules(seed=0):
+    """A 3 000-triangle soup around the origin with, placed around and inside it: overlapping cubes (the cost rule),
+    coincident centroids, degenerate triangles on an x-parallel segment (no surface area) and signed zeros (clusters
+    of 700 inside the soup, of 40 and 150 beside it, and a row of boxes)."""
+    return merge(
+        random_soup(3000, 0, seed, extent=10.0),
+        bvh_overlapping(40, (40, 5, -7), seed + 1), bvh_overlapping(200, (-35, 20, 9), seed + 2),
+        shifted(coincident_centroids(40, seed + 3), (10, -40, 5)), shifted(coincident_centroids(200, seed + 4), (-20, -30, -15)),
+        shifted(coincident_centroids(700, seed + 5), (25, 35, 20)),
+        shifted(kd_line(30, seed + 6), (-40, -10, 20)), shifted(kd_line(150, seed + 7), (30, -25, -30)),
+        shifted(kd_line(600, seed + 8), (-15, 40, -25)),
+        bvh_signed_zero_cluster(700, seed + 9), bvh_signed_zero_row(96, seed + 10),
+        bvh_signed_zero_cluster(40, seed + 11, x0=-14.0), bvh_signed_zero_cluster(150, seed + 12, x0=-18.0))
+
+
+def bvh_lattice(n=16):
+    """n^3 identical boxes on a regular lattice: equal centroid spacings and equal extents on the three axes."""
+    g = np.stack(np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij"), -1).reshape(-1, 3)
+    lo = g.astype(np.float32)
+    return box_tris(lo, lo + np.float32(0.5))
+
+
+def bvh_spine(n, ratio=12.1, k0=-32, pairs=False):
+    """n tiny triangles in planes x = ratio^(k0 + k), 2^-10 wide in y and z: with 12 SAH buckets the largest centroid
+    is alone in the last bucket and every other one falls into the first, at every level: a left spine of n - 1.
+    pairs: a second triangle at x (1 + 2^-10) beside each, so that what comes off per level is a pair, i.e. an
+    interior node (the nth_element of two) as the second child."""
+    x = (np.float64(ratio) ** (k0 + np.arange(n))).astype(np.float32)
+    if pairs:
+        x = np.stack([x, x * np.float32(1 + 2.0 ** -10)], 1).reshape(-1).astype(np.float32)
+        n = 2 * n
+    lo = np.zeros((n, 3), np.float32)
+    lo[:, 0] = x
+    hi = np.full((n, 3), 2.0 ** -10, np.float32)
+    hi[:, 0] = x
+    return box_tris(lo, hi)
+
+
+def bvh_cluster_and_outlier(seed=0, n=1500, far=40.0):
+    """A unit-extent soup and one triangle far away on the diagonal: the soup falls into ONE cell of the 16^3 treelet
+    grid, the outlier into the opposite one."""
+    v, p = random_soup(1, 0, seed + 1, extent=0.0, size=0.5)
+    return merge(random_soup(n, 0, seed, extent=1.0, size=0.2), (v + np.float32(far), p))
+
+
+def bvh_all_cells(seed=0, n_soup=2000):
+    """A 16^3 lattice of small triangles (one per cell of the treelet grid) inside a soup of the same extent."""
+    return merge(bvh_lattice(16), shifted(random_soup(n_soup, 0, seed, extent=7.0, size=0.3), (7.5, 7.5, 7.5)))
+
+
+def bvh_code_runs(seed=0):
+    """Runs of identical Morton codes of 64, 65 and 700 primitives (coincident centroids), each with a few dozen
+    small triangles close by, inside a soup."""
+    parts = [random_soup(3000, 0, seed, extent=10.0)]
+    for k, (n, at) in enumerate(((64, (4, -6, 2)), (65, (-7, 3, -5)), (700, (1, 8, 6)))):
+        parts.append(shifted(coincident_centroids(n, seed + 1 + k), at))
+        parts.append(shifted(random_soup(40, 0, seed + 5 + k, extent=0.25, size=0.05), np.array(at) + [1, 2, 3]))
+    return merge(*parts)
+
+
+def bvh_dense_cell(seed=0):
+    """3 000 triangles spread over about one cell of the treelet grid of a sparse 2 000-triangle soup: the cell's
+    treelet splits on every one of the 18 bits."""
+    return merge(random_soup(3000, 0, seed, extent=3.0, size=0.1), random_soup(2000, 0, seed + 1, extent=50.0))

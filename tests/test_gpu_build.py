@@ -14,12 +14,19 @@ from nn_bvh_amd import NNBVHError, build_tree, build_tree_gpu, make_prims, scene
 pytestmark = pytest.mark.gpu
 
 
-def same_tree(prims, verts, max_prims=4, prim_bounds=None, what="", method="hlbvh"):
-    host = build_tree(prims, verts, max_prims, method, prim_bounds=prim_bounds)
+def same_tree(prims, verts, max_prims=4, prim_bounds=None, what="", method="hlbvh", host=None):
+    """A fresh device build against the host builder's tree, byte for byte (nodes, ordered primitives) and in depth.
+    host: a tree built before (the host builder's, or an earlier device build to repeat) instead of a new host build.
+    Returns (host tree, device tree) when host was given, else the host tree."""
+    given = host is not None
+    if not given:
+        host = build_tree(prims, verts, max_prims, method, prim_bounds=prim_bounds)
     dev = build_tree_gpu(prims, verts, max_prims, prim_bounds=prim_bounds, split_method=method)
     what = f"{what} [{method}]"
     assert len(dev.nodes) == len(host.nodes), f"{what}: {len(dev.nodes)} vs {len(host.nodes)} nodes"
-    assert dev.ordered_prims.tobytes() == host.ordered_prims.tobytes(), f"{what}: ordered prims differ"
+    if dev.ordered_prims.tobytes() != host.ordered_prims.tobytes():
+        raise AssertionError(f"{what}: ordered prims differ, first at "
+                             f"{int(np.nonzero(dev.ordered_prims != host.ordered_prims)[0][0])}")
     if dev.nodes.tobytes() != host.nodes.tobytes():
         a = dev.nodes.view(np.uint8).reshape(-1, 32)
         b = host.nodes.view(np.uint8).reshape(-1, 32)
@@ -27,7 +34,7 @@ def same_tree(prims, verts, max_prims=4, prim_bounds=None, what="", method="hlbv
         raise AssertionError(f"{what}: {len(bad)} nodes differ, first {bad[:5]}: "
                              f"{dev.nodes[bad[:3]]} vs {host.nodes[bad[:3]]}")
     assert dev.depth == host.depth, f"{what}: depth {dev.depth} vs {host.depth}"
-    return host
+    return (host, dev) if given else host
 
 
 @pytest.mark.parametrize("max_prims", [1, 2, 4, 16, 255])
@@ -153,6 +160,9 @@ def test_scene_blobs(name):
 # ---- SAH on the device: same tree, same leaf order as the host builder (= the reference's) -------------
 @pytest.mark.parametrize("max_prims", [1, 4, 255])
 def test_sah_soup_with_patches(max_prims):
+    """Triangles AND bilinear patches through the device SAH build.  max_prims changes nothing here: the host-built
+    tree of this soup has 14 999 nodes and 7 500 one-primitive leaves at 1, 4 and 255 alike (every split is cheaper
+    than its leaf).  Multi-primitive leaves under each leaf rule are test_bvh_build_paths.py's sah_leaf_rules."""
     verts, prims = ss.random_soup(6000, 1500, 3)
     same_tree(prims, verts, max_prims, what=f"soup maxprims {max_prims}", method="sah")
 
