@@ -99,31 +99,6 @@ struct KdParams {
     int32_t *wUnfinished;            // nullable: counts the items that would start one more
 };
 
-// util/vecmath.h:1547-1571 with invRayDir = 1 / d[i] taken from the ray's precomputed reciprocals
-// (the same division)
-DEV bool kd_root_interval(const float bmin[3], const float bmax[3], V3 o, V3 inv, float tMaxRay, float &t0Out,
-                          float &t1Out) {
-    float t0 = 0.0f, t1 = tMaxRay;
-    const float oo[3] = {o.x, o.y, o.z}, ii[3] = {inv.x, inv.y, inv.z};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float tNear = (bmin[i] - oo[i]) * ii[i];
-        float tFar = (bmax[i] - oo[i]) * ii[i];
-        if (tNear > tFar) {
-            const float s = tNear;
-            tNear = tFar;
-            tFar = s;
-        }
-        tFar *= 1.0f + 2.0f * gamma_f(3);
-        t0 = tNear > t0 ? tNear : t0;
-        t1 = tFar < t1 ? tFar : t1;
-        if (t0 > t1) return false;
-    }
-    t0Out = t0;
-    t1Out = t1;
-    return true;
-}
-
 // A lane takes up the ray {R0, R1} = {o, tMax} {d, time}: the reciprocals (aggregates.cpp:980), the shear, the
 // `ray.d[axis] <= 0` bits of aggregates.cpp:1002-1003, cold hit slots, zeroed counts and the root interval (:975-977:
 // rays that miss the tree's bounds return before anything is counted).  Used at a refill and, in the walk instances,

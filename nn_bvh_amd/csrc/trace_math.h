@@ -174,6 +174,32 @@ DEV float slab_entry_key(float mnx, float mny, float mnz, float mxx, float mxy, 
     return ok ? a : __builtin_inff();
 }
 
+// KdTreeAggregate's root interval (kd_trace.hip)
+// util/vecmath.h:1547-1571 with invRayDir = 1 / d[i] taken from the ray's precomputed reciprocals
+// (the same division)
+DEV bool kd_root_interval(const float bmin[3], const float bmax[3], V3 o, V3 inv, float tMaxRay, float &t0Out,
+                          float &t1Out) {
+    float t0 = 0.0f, t1 = tMaxRay;
+    const float oo[3] = {o.x, o.y, o.z}, ii[3] = {inv.x, inv.y, inv.z};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        float tNear = (bmin[i] - oo[i]) * ii[i];
+        float tFar = (bmax[i] - oo[i]) * ii[i];
+        if (tNear > tFar) {
+            const float s = tNear;
+            tNear = tFar;
+            tFar = s;
+        }
+        tFar *= 1.0f + 2.0f * gamma_f(3);
+        t0 = tNear > t0 ? tNear : t0;
+        t1 = tFar < t1 ? tFar : t1;
+        if (t0 > t1) return false;
+    }
+    t0Out = t0;
+    t1Out = t1;
+    return true;
+}
+
 // shapes.cpp:172-273.  `degenerate` is the reference's first test
 // (LengthSquared(Cross(p2 - p0, p1 - p0)) == 0, :176-177): it depends on the triangle only and
 // is evaluated once, with the same float32 operations, when the scene is baked (kPrimDegenerate).

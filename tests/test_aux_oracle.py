@@ -59,31 +59,21 @@ def test_weighted_reservoir_sampler_golden():
 @pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/ref_leaf not built")
 @pytest.mark.parametrize("seed", [1, 2])
 def test_live_against_the_reference_binary(seed):
-    from test_oracle_vs_reference_live import specials
-    rng = np.random.default_rng(seed)
+    from awkward_cases import cases_hash, cases_offset, cases_slab2, cases_wrs
+    rng = np.random.default_rng(seed)  # one stream through the four families, in this order
     n = 20000
-    x = specials(rng, (n, 6))
+    x = cases_hash(rng, n)
     first, bits = run_ref_raw("hash", x, 2)
     lo, hi, hf = ob.hash_batch(x)
     assert np.array_equal(lo, first) and np.array_equal(hi, bits[:, 1]) and np.array_equal(hf.view(np.uint32), bits[:, 0])
-    p = specials(rng, (n, 3))
-    err = np.abs(specials(rng, (n, 3))) * np.float32(1e-6)
-    nn = rng.normal(size=(n, 3)).astype(np.float32)
-    nn[rng.random(n) < 0.1] = 0
-    lo = (p - err).astype(np.float32)
-    y = np.concatenate([lo, np.where(err == 0, lo, p + err), nn, specials(rng, (n, 3))], 1).astype(np.float32)
-    y = y[np.isfinite(y).all(1)]
+    y = cases_offset(rng, n)
     _, bits = run_ref_raw("offset", y, 9)
     assert np.array_equal(ob.offset_batch(y).view(np.uint32), bits)
-    z = np.concatenate([specials(rng, (n, 6)), rng.integers(0, 30, (n, 1))], 1).astype(np.float32)
+    z = cases_wrs(rng, n)
     first, bits = run_ref_raw("wrs", z, 2)
     sel, out = ob.wrs_batch(z)
     assert np.array_equal(sel, first.view(np.int32)) and np.array_equal(out.view(np.uint32), bits)
-    b = np.sort(rng.uniform(-5, 5, (n, 2, 3)), axis=1).reshape(n, 6)
-    o = rng.uniform(-8, 8, (n, 3))
-    d = (b[:, :3] + rng.uniform(-2, 6, (n, 3)) - o)
-    d[::7, 1] = 0
-    w = np.concatenate([o, d, np.where(rng.random(n) < 0.5, np.inf, rng.uniform(0, 4, n))[:, None], b], 1).astype(np.float32)
+    w = cases_slab2(rng, n)
     first, bits = run_ref_raw("slab2", w, 2)
     hit, tt = ob.bounds_t0t1(w[:, 7:13], w[:, 0:3], w[:, 3:6], w[:, 6])
     assert np.array_equal(hit, first.astype(np.uint8))
