@@ -194,6 +194,37 @@ const nnbvh_prim *nnbvh_build_ordered_prims(const nnbvh_build *b, int *n_prims);
 int nnbvh_build_depth(const nnbvh_build *b); /* edges root -> deepest leaf */
 void nnbvh_build_destroy(nnbvh_build *b);
 
+/* The SAH trees of many objects in ONE pass on the GPU: what nnbvh_build_create_gpu(..., NNBVH_SPLIT_SAH, ...) makes
+ * of each object alone, tree k byte for byte (its second-child offsets count from its own root, its leaves' first
+ * primitives from the object's first primitive), without the per-build launches, read-backs and synchronisations
+ * that dominate when the objects are small and many.
+ *   prims[n_prims]             the objects' primitives one after another (triangles, bilinear patches, the alpha
+ *                              kinds, NNBVH_PRIM_HOST; no NNBVH_PRIM_INSTANCE entries), over ONE vertex array
+ *   object_first[n_objects+1]  object k is prims[object_first[k], object_first[k+1]); object_first[0] == 0, the last
+ *                              entry == n_prims, no object is empty
+ *   prim_bounds                nullable, 6 floats per entry of prims, read for NNBVH_PRIM_HOST entries
+ *   split_method               NNBVH_SPLIT_SAH (anything else is refused: the forest build is SAH only)
+ * NULL + nnbvh_last_error() for every argument fault (null or empty arrays, a malformed object_first, vertex indices,
+ * unknown kinds, instance entries, host-only primitives without prim_bounds, the split method: all checked on the
+ * host before a device is looked at), for no usable device, and for malformed geometry, where the message is the one
+ * a loop of single builds over the objects would have stopped at: the lowest-numbered failing object's.
+ * Accessors: the node array [tree 0, tree 1, ...]; node_first[n_objects + 1] (tree k is nodes[node_first[k],
+ * node_first[k + 1])); depths[n_objects]; the leaf-ordered primitives, object k's at object_first[k]; timing = the
+ * phases of nnbvh_build_gpu_timing's SAH; n_levels = breadth-first passes run (each covers every object's nodes above
+ * 256 primitives of one level; 0 when no object is that large); n_subtrees = subtrees built by one wavefront each. */
+typedef struct nnbvh_forest nnbvh_forest;
+nnbvh_forest *nnbvh_build_forest_create_gpu(const nnbvh_prim *prims, int n_prims, const int32_t *object_first,
+                                            int n_objects, const float *verts, int n_verts, const float *prim_bounds,
+                                            int max_prims_in_node, int split_method, int device);
+const nnbvh_linear_node *nnbvh_forest_nodes(const nnbvh_forest *f, int *n_nodes);
+const int32_t *nnbvh_forest_node_first(const nnbvh_forest *f, int *n_objects);
+const int32_t *nnbvh_forest_depths(const nnbvh_forest *f, int *n_objects);
+const nnbvh_prim *nnbvh_forest_ordered_prims(const nnbvh_forest *f, int *n_prims);
+int nnbvh_forest_gpu_timing(const nnbvh_forest *f, double out_ms[5]);
+int nnbvh_forest_n_levels(const nnbvh_forest *f);
+int nnbvh_forest_n_subtrees(const nnbvh_forest *f);
+void nnbvh_forest_destroy(nnbvh_forest *f);
+
 /* ---- device scene ------------------------------------------------------------------ */
 /* Uploads and bakes a flattened tree (the reference's LinearBVHNode[] in its DFS layout, first child
  * at index + 1) with its leaf-ordered primitives.  Everything the kernels index with is validated
@@ -268,7 +299,9 @@ nnbvh_scene *nnbvh_scene_create_gpu_build_with_attributes(const nnbvh_prim *prim
  * TransformedPrimitive / AnimatedPrimitive per placement) entirely on the device: every object's tree, then the
  * top-level tree, are built there, put into one numbering and baked; no tree visits the host.  The device arrays are
  * byte for byte those of nnbvh_scene_create_instanced_with_attributes on host-built trees of the same split_method
- * (nodes [top, object 0, object 1, ...], primitives [top in leaf order, object 0 in leaf order, ...]).
+ * (nodes [top, object 0, object 1, ...], primitives [top in leaf order, object 0 in leaf order, ...]).  With
+ * NNBVH_SPLIT_SAH all object trees come from one forest pass (nnbvh_build_forest_create_gpu's builder), so a scene of
+ * thousands of small objects pays the builder's launches and read-backs once; NNBVH_SPLIT_HLBVH builds them one by one.
  *   prims[n_prims]            the caller's order: [0, n_top_prims) is the top-level list (triangles, patches, the
  *                             alpha kinds, NNBVH_PRIM_HOST and NNBVH_PRIM_INSTANCE entries; for an instance entry
  *                             v[0] is the placement index and id the caller's), then the object definitions one

@@ -99,6 +99,9 @@ EXPORTS = [
     "nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates",
     "nnbvh_kd_scene_create_gpu_build", "nnbvh_kd_scene_create_gpu_build_with_attributes", "nnbvh_kd_scene_bounds",
     "nnbvh_kd_scene_info", "nnbvh_kd_scene_read", "nnbvh_scene_create_instanced_gpu_build", "nnbvh_scene_read",
+    "nnbvh_build_forest_create_gpu", "nnbvh_forest_nodes", "nnbvh_forest_node_first", "nnbvh_forest_depths",
+    "nnbvh_forest_ordered_prims", "nnbvh_forest_gpu_timing", "nnbvh_forest_n_levels", "nnbvh_forest_n_subtrees",
+    "nnbvh_forest_destroy",
 ]
 
 
@@ -282,6 +285,19 @@ def lib():
                                                          i32, i32, i32]
     L.nnbvh_scene_read.restype = i32
     L.nnbvh_scene_read.argtypes = [vp, i32, vp, ctypes.c_size_t]
+    L.nnbvh_build_forest_create_gpu.restype = vp
+    L.nnbvh_build_forest_create_gpu.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]
+    for name in ("nodes", "node_first", "depths", "ordered_prims"):
+        getattr(L, "nnbvh_forest_" + name).restype = vp
+        getattr(L, "nnbvh_forest_" + name).argtypes = [vp, vp]
+    L.nnbvh_forest_gpu_timing.restype = i32
+    L.nnbvh_forest_gpu_timing.argtypes = [vp, vp]
+    L.nnbvh_forest_n_levels.restype = i32
+    L.nnbvh_forest_n_levels.argtypes = [vp]
+    L.nnbvh_forest_n_subtrees.restype = i32
+    L.nnbvh_forest_n_subtrees.argtypes = [vp]
+    L.nnbvh_forest_destroy.restype = None
+    L.nnbvh_forest_destroy.argtypes = [vp]
     L.nnbvh_kd_scene_read.restype = i32
     L.nnbvh_kd_scene_read.argtypes = [vp, i32, vp, ctypes.c_size_t]
     L.nnbvh_kd_scene_destroy.restype = None

@@ -106,6 +106,55 @@ def build_tree_gpu(prims, verts, max_prims_in_node=4, prim_bounds=None, device=0
     return _take_build(L, h, "nnbvh_build_create_gpu")
 
 
+class BuiltForest(list):
+    """build_forest_gpu's result: a list of BuiltTree, one per object, with the pass's own figures as attributes:
+    gpu_ms (the five phases of nnbvh_forest_gpu_timing), n_levels (breadth-first passes run), n_subtrees (subtrees
+    built by one wavefront each) and node_first (where each tree starts in the forest's node array)."""
+
+
+def build_forest_gpu(objects, verts, max_prims_in_node=4, prim_bounds=None, device=0):
+    """The SAH trees of `objects` (a list of PRIM_DTYPE arrays over ONE vertex array) built in one pass on the GPU
+    (nnbvh_build_forest_create_gpu): tree k is byte for byte build_tree(objects[k], verts, max_prims_in_node, "sah").
+    prim_bounds ([total primitives, 6] float32, the objects' rows one after another) is read for host-only primitives.
+    Returns a BuiltForest."""
+    L = _lib.lib()
+    objects = [np.ascontiguousarray(o, PRIM_DTYPE) for o in objects]
+    prims = np.ascontiguousarray(np.concatenate(objects), PRIM_DTYPE) if objects else np.zeros(0, PRIM_DTYPE)
+    first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(o) for o in objects])]), np.int32)
+    verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    pb = None
+    if prim_bounds is not None:
+        pb = np.ascontiguousarray(prim_bounds, np.float32).reshape(len(prims), 6)
+    h = L.nnbvh_build_forest_create_gpu(ptr(prims), len(prims), ptr(first), len(objects), ptr(verts), len(verts),
+                                        ptr(pb) if pb is not None else None, int(max_prims_in_node),
+                                        SPLIT_METHODS["sah"], int(device))
+    if not h:
+        raise NNBVHError("nnbvh_build_forest_create_gpu: " + _lib.last_error())
+    try:
+        def array(fn, dtype, extra=0):  # a copy of what an accessor points at: its count + extra elements
+            n = ctypes.c_int(0)
+            p = fn(h, ctypes.byref(n))
+            nbytes = (n.value + extra) * np.dtype(dtype).itemsize
+            return np.frombuffer((ctypes.c_char * nbytes).from_address(p), dtype).copy()
+
+        nodes = array(L.nnbvh_forest_nodes, NODE_DTYPE)
+        ordered = array(L.nnbvh_forest_ordered_prims, PRIM_DTYPE)
+        node_first = array(L.nnbvh_forest_node_first, np.int32, 1)
+        depths = array(L.nnbvh_forest_depths, np.int32)
+        forest = BuiltForest(BuiltTree(nodes[node_first[k]:node_first[k + 1]].copy(),
+                                       ordered[first[k]:first[k + 1]].copy(), int(depths[k]))
+                             for k in range(len(objects)))
+        ms = np.zeros(5, np.float64)
+        L.nnbvh_forest_gpu_timing(h, ptr(ms))
+        forest.gpu_ms = [float(x) for x in ms]
+        forest.n_levels = L.nnbvh_forest_n_levels(h)
+        forest.n_subtrees = L.nnbvh_forest_n_subtrees(h)
+        forest.node_first = node_first
+    finally:
+        L.nnbvh_forest_destroy(h)
+    return forest
+
+
 class BVHAggregate:
     """GPU-resident aggregate.  Construct from primitives (builds the tree on the host like
     BVHAggregate::Create, aggregates.cpp:725-744: splitmethod "sah", maxnodeprims 4) or from

@@ -91,6 +91,25 @@ struct DeviceBuildInput {
 bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error);
 bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error);
 
+// SAH trees of many objects in ONE pass (gpu_sah_device is its one-object case).  in.d_prims holds the objects'
+// primitives one after another, object k at [object_first[k], object_first[k + 1]) (host array, object_first[0] = 0,
+// strictly increasing, object_first[n_objects] = in.n_prims); in.d_prim_bounds is indexed like in.d_prims.  Every tree is
+// byte for byte gpu_sah_device's of that object alone: its second-child offsets count from its own root, its leaves'
+// first primitives from the object's first primitive.  in.d_nodes_out, when given, has room for
+// 2 * n_prims - n_objects nodes.  A malformed input fails with the message a loop of gpu_sah_device calls over the
+// objects would have stopped at: the lowest-numbered failing object's.
+struct ForestBuildResult {
+    void *d_nodes = nullptr, *d_ordered = nullptr;  // [tree 0, tree 1, ...]; object k's primitives at object_first[k]
+    int total_nodes = 0;
+    std::vector<int> node_first;  // [n_objects + 1] tree k is d_nodes[node_first[k] .. node_first[k + 1])
+    std::vector<int> depth;       // [n_objects]
+    double ms[5] = {0, 0, 0, 0, 0};  // as gpu_sah's ([0] and [4] are the wrappers')
+    int n_levels = 0;                // breadth-first passes run (each works on every object's big nodes of one level)
+    int n_subtrees = 0, n_upper = 0;  // subtrees built by wavefronts, nodes built breadth-first
+};
+bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,
+                           std::string *error);
+
 // Device-side counterpart of nnbvh_scene_create's baking (bvh_capi.cpp): the 64-B "both children"
 // records and the 16-B-slot primitive stream, straight from device-resident build output.  Triangles,
 // bilinear patches and host-only primitives; instance entries with an InstanceBake (two-level scenes).

@@ -46,7 +46,12 @@ namespace {
 constexpr int kB = 256;
 constexpr int kTreeletBit = 18;  // bits >= 18 separate treelets (mask 0x3ffc0000, aggregates.cpp:423)
 
-enum : int { kErrVertex = 1, kErrNeedBounds = 2, kErrKind = 3, kErrLeafSize = 4, kErrNonFinite = 5 };
+enum : int { kErrVertex = 1, kErrNeedBounds = 2, kErrKind = 3, kErrLeafSize = 4, kErrNonFinite = 5, kErrSahCosts = 6 };
+// The SAH builders' error words, one per kind above: errObj[kind] = the lowest-numbered object that raised it
+// (atomicMin; kNoObject = nobody), so a forest reports what a loop over its objects would have stopped at.
+// errObj[0] is a plain word for the "cannot happen" codes.
+constexpr int kErrWords = 8;
+constexpr int kNoObject = 0x7fffffff;
 enum : unsigned char { kRealInterior = 1, kRealLeaf = 2, kTreeletRoot = 4 };
 
 struct Box6 {
@@ -90,8 +95,23 @@ __global__ __launch_bounds__(kB) void k_prim_bounds(const nnbvh_prim *__restrict
                                                     const float *__restrict__ verts, int nVerts,
                                                     const float *__restrict__ callerBounds, int n,
                                                     Box6 *__restrict__ pb, unsigned *cbKeys,
-                                                    int *err) {
+                                                    int *err, const int *__restrict__ objectFirst,
+                                                    int nObjects, int *errObj) {
     __shared__ float red[6][kB / 64];
+    // err (HLBVH): one word, the last writer's kind.  errObj (SAH, with objectFirst[nObjects + 1]): see kErrWords
+    auto report = [&](int kind, int i) {
+        if (!errObj) {
+            *err = kind;
+            return;
+        }
+        int lo = 0, hi = nObjects - 1;  // the object of primitive i: the last k with objectFirst[k] <= i
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (objectFirst[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        atomicMin(&errObj[kind], lo);
+    };
     float cmin[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f};
     float cmax[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) {
@@ -101,18 +121,18 @@ __global__ __launch_bounds__(kB) void k_prim_bounds(const nnbvh_prim *__restrict
         const int nv = (p.kind == NNBVH_PRIM_TRIANGLE || (p.kind >= NNBVH_PRIM_ALPHA_TRIANGLE && p.kind <= NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED)) ? 3 : ((p.kind == NNBVH_PRIM_BILINEAR_PATCH || (p.kind >= NNBVH_PRIM_ALPHA_PATCH && p.kind <= NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH_FLIPPED)) ? 4 : 0);
         if (p.kind == NNBVH_PRIM_INSTANCE || p.kind == NNBVH_PRIM_HOST) {
             if (!callerBounds) {
-                *err = kErrNeedBounds;
+                report(kErrNeedBounds, i);
             } else {
                 box_add(b, callerBounds + 6 * (long)i);
                 box_add(b, callerBounds + 6 * (long)i + 3);
             }
         } else if (nv == 0) {
-            *err = kErrKind;
+            report(kErrKind, i);
         }
         for (int k = 0; k < nv; ++k) {
             const int vi = p.v[k];
             if (vi < 0 || vi >= nVerts) {
-                *err = kErrVertex;
+                report(kErrVertex, i);
                 continue;
             }
             box_add(b, verts + 3 * (long)vi);
@@ -123,12 +143,12 @@ __global__ __launch_bounds__(kB) void k_prim_bounds(const nnbvh_prim *__restrict
             const int vi = p.v[k];
             if (vi < 0 || vi >= nVerts) continue;
             const float *v = verts + 3 * (long)vi;
-            if (!(__builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]))) *err = kErrNonFinite;
+            if (!(__builtin_isfinite(v[0]) && __builtin_isfinite(v[1]) && __builtin_isfinite(v[2]))) report(kErrNonFinite, i);
         }
         if ((p.kind == NNBVH_PRIM_INSTANCE || p.kind == NNBVH_PRIM_HOST) && callerBounds) {
             const float *c = callerBounds + 6 * (long)i;
             for (int k = 0; k < 6; ++k)
-                if (!__builtin_isfinite(c[k])) *err = kErrNonFinite;
+                if (!__builtin_isfinite(c[k])) report(kErrNonFinite, i);
         }
         pb[i] = b;
         for (int k = 0; k < 3; ++k) {
@@ -450,6 +470,10 @@ __global__ __launch_bounds__(kB) void k_gather_prims(const nnbvh_prim *__restric
         ordered[i] = prims[idxSorted[i]];
 }
 
+__global__ __launch_bounds__(kB) void k_iota(int n, int *__restrict__ perm) {
+    for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) perm[i] = i;
+}
+
 __global__ __launch_bounds__(kB) void k_scatter_nodes(const int *__restrict__ index,
                                                       const nnbvh_linear_node *__restrict__ src, int n,
                                                       nnbvh_linear_node *__restrict__ nodes) {
@@ -634,7 +658,7 @@ bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::stri
     unsigned *dCb = (unsigned *)dScalars;
     int *dErr = dScalars + 6, *dM = dScalars + 7, *dMaxDepth = dScalars + 8;
     hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(n, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts,
-                       dCaller, n, dPb, dCb, dErr);
+                       dCaller, n, dPb, dCb, dErr, (const int *)nullptr, 0, (int *)nullptr);
     hipLaunchKernelGGL(k_morton, dim3(grid_for(n)), dim3(kB), 0, stream, dPb, dCb, n, dCodes, dIdx);
     size_t tmpBytes = 0, scanBytes = 0;
     GB_CHECK(rocprim::radix_sort_pairs(nullptr, tmpBytes, dCodes, dCodesS, dIdx, dIdxS, (size_t)n, 0u, 30u, stream),
@@ -787,6 +811,11 @@ bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::stri
 // Phase B: every remaining subtree is built depth-first by ONE wavefront (explicit stack in LDS,
 //          nodes written in DFS order into the subtree's pool slice).
 // Phase C: DFS layout of the phase-A nodes + subtree slices, copy, bounds, download.
+// A FOREST (gpu_sah_forest_device; one tree is its one-object case): the objects' primitives share one permutation
+// array, phase A starts with one root segment per object and works on every object's big nodes of a level at once,
+// phase B is one launch over all objects' subtrees, phase C lays out tree after tree.  No segment's arithmetic looks
+// outside its own range, so each tree is the one the object alone gets; only the two kinds of offset need care:
+// a leaf's first primitive counts from its object's first primitive, a second child from its own tree's root.
 namespace {
 
 constexpr int kSahBuckets = 12;
@@ -1087,14 +1116,14 @@ __global__ __launch_bounds__(kB) void k_seg_choose(int nSeg, int maxPrims, const
 
 // ---- phase B: one wavefront builds one subtree ----------------------------------------------------------
 struct SmallSeg {
-    int start, n, pool;
+    int start, n, pool;  // start: position in the forest's permutation array
+    int object, first;   // the object it belongs to and that object's first primitive (leaf offsets count from there)
 };
 // Pending second children: the first kSubtreeStack of a subtree's in LDS.  A left spine longer than that (only
 // primitives whose centroids grow geometrically make one) keeps the rest in the tree itself: the interior node that
 // waits for its second child holds the child's range in pmin[0..1] and the node below it on the stack in pmin[2],
 // fields phase C overwrites with the bounds.
 constexpr int kSubtreeStack = 64;
-constexpr int kSahCostsFlag = 3;  // err[3] (the builder's scalar block): a node without a finite split cost was met
 
 // sah_choose for a wavefront: lane i < 11 prices split i (the same additions in the same order as
 // the sequential loops: buckets 0..i ascending for the part below, 11..i+1 descending for the part
@@ -1147,7 +1176,7 @@ __device__ __forceinline__ SahChoice sah_choose_wave(int lane, const int *count,
 __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict__ segs, int nSegs, int maxPrims,
                                                      const Box6 *__restrict__ pb, int *perm, int *lfPos, int *rtPos,
                                                      nnbvh_linear_node *pool, int *segCount, int *segDepth,
-                                                     int *err) {
+                                                     int *errObj) {
     __shared__ int stStart[kSubtreeStack], stN[kSubtreeStack], stParent[kSubtreeStack], stDepth[kSubtreeStack];
     __shared__ unsigned bkeys[kSahBuckets * 6];
     __shared__ int bcount[kSahBuckets];
@@ -1256,7 +1285,7 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
                 const SahChoice ch = sah_choose_wave(lane, bcount, bkeys, bounds, n, maxPrims);
                 __syncthreads();  // everyone has read the buckets before the next node clears them
                 if (ch.best < 0) {  // no split costs less than +inf: refused, as by the host builder
-                    if (lane == 0) err[kSahCostsFlag] = 1;  // a word of its own: no other block's error hides it
+                    if (lane == 0) atomicMin(&errObj[kErrSahCosts], sg.object);  // a word of its own: no other error hides it
                     refused = true;
                     leaf = true;
                 } else if (!ch.split) {
@@ -1276,7 +1305,7 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
                     __syncthreads();
                     if (leftOff) perm[start + rpos[kL]] = myIdx;
                     if (rightOff) perm[start + lpos[kR]] = myIdx;
-                    if (__popcll(mL) != __popcll(mR) && lane == 0) *err = 100;  // cannot happen
+                    if (__popcll(mL) != __popcll(mR) && lane == 0) errObj[0] = 100;  // cannot happen
                     __syncthreads();
                     __threadfence_block();
                 } else {
@@ -1302,7 +1331,7 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
                         if (f) rtPos[start + nr + __popcll(mask & ((1ull << lane) - 1ull))] = start + j;
                         nr += __popcll(mask);
                     }
-                    if (nl != nr && lane == 0) *err = 100;  // cannot happen: both equal the number of swaps
+                    if (nl != nr && lane == 0) errObj[0] = 100;  // cannot happen: both equal the number of swaps
                     __threadfence_block();
                     for (int k = lane; k < nl; k += 64) {
                         const int a = lfPos[start + k], b = rtPos[start + k];
@@ -1316,7 +1345,7 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
         }
         if (!leaf) {
             if (mid <= 0 || mid >= n) {  // cannot happen (buckets 0 and 11 are never empty): no endless loop
-                if (lane == 0) *err = 101;
+                if (lane == 0) errObj[0] = 101;
                 leaf = true;
             }
         }
@@ -1375,12 +1404,12 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
                     nd.pmin[k] = b.mn[k];
                     nd.pmax[k] = b.mx[k];
                 }
-                nd.offset = start;
+                nd.offset = start - sg.first;  // object-local, as the tree of the object alone has it
                 nd.nprims = (uint16_t)n;
                 nd.axis = 0;
                 nd.pad = (uint8_t)depth;
                 nodes[me] = nd;
-                if (n > 65535 && !refused) *err = kErrLeafSize;
+                if (n > 65535 && !refused) atomicMin(&errObj[kErrLeafSize], sg.object);
             }
             if (depth > maxDepth) maxDepth = depth;
         }
@@ -1414,26 +1443,35 @@ __global__ __launch_bounds__(64) void k_sah_subtrees(const SmallSeg *__restrict_
 
 // ---- phase C ----------------------------------------------------------------------------------------------
 // subtree slices -> final DFS positions
+// where a subtree's slice goes: `at` in the forest's node array, `local` = the same place counted from its tree's
+// root (what second-child offsets are relative to; the tree's root stands at at - local), `depth` of the slice's root
+struct SegPlace {
+    int at, local, depth;
+};
 __global__ __launch_bounds__(kB) void k_sah_emit(const SmallSeg *__restrict__ segs, const int *__restrict__ segCount,
-                                                 const int *__restrict__ segBase, const int *__restrict__ segBaseDepth,
+                                                 const SegPlace *__restrict__ place,
                                                  const nnbvh_linear_node *__restrict__ pool,
-                                                 nnbvh_linear_node *__restrict__ nodes, unsigned char *__restrict__ depthOf) {
+                                                 nnbvh_linear_node *__restrict__ nodes, unsigned char *__restrict__ depthOf,
+                                                 int *__restrict__ rootOf) {
     const int s = blockIdx.x;
-    const int cnt = segCount[s], base = segBase[s], bd = segBaseDepth[s];
+    const int cnt = segCount[s];
+    const SegPlace pl = place[s];
     const nnbvh_linear_node *src = pool + segs[s].pool;
     for (int i = threadIdx.x; i < cnt; i += kB) {
         nnbvh_linear_node nd = src[i];
-        depthOf[base + i] = (unsigned char)(bd + nd.pad);
+        depthOf[pl.at + i] = (unsigned char)(pl.depth + nd.pad);
+        rootOf[pl.at + i] = pl.at - pl.local;
         nd.pad = 0;
-        if (nd.nprims == 0) nd.offset += base;
-        nodes[base + i] = nd;
+        if (nd.nprims == 0) nd.offset += pl.local;
+        nodes[pl.at + i] = nd;
     }
 }
 struct UpperNode {
-    int index, second, axis, depth;
+    int index, second, axis, depth, root;  // index, root: in the forest's node array; second: from the tree's root
 };
 __global__ __launch_bounds__(kB) void k_sah_upper(const UpperNode *__restrict__ up, int nUp,
-                                                  nnbvh_linear_node *__restrict__ nodes, unsigned char *__restrict__ depthOf) {
+                                                  nnbvh_linear_node *__restrict__ nodes, unsigned char *__restrict__ depthOf,
+                                                  int *__restrict__ rootOf) {
     const int i = blockIdx.x * kB + threadIdx.x;
     if (i >= nUp) return;
     nnbvh_linear_node nd;
@@ -1444,13 +1482,14 @@ __global__ __launch_bounds__(kB) void k_sah_upper(const UpperNode *__restrict__ 
     nd.pad = 0;
     nodes[up[i].index] = nd;
     depthOf[up[i].index] = (unsigned char)up[i].depth;
+    rootOf[up[i].index] = up[i].root;
 }
 // interior bounds = Union(child 0, child 1) (:371-373), one tree level per launch, deepest first
 __global__ __launch_bounds__(kB) void k_sah_level_bounds(int nNodes, int level, const unsigned char *__restrict__ depthOf,
-                                                         nnbvh_linear_node *nodes) {
+                                                         const int *__restrict__ rootOf, nnbvh_linear_node *nodes) {
     const int i = blockIdx.x * kB + threadIdx.x;
     if (i >= nNodes || depthOf[i] != level || nodes[i].nprims != 0) return;
-    const nnbvh_linear_node c0 = nodes[i + 1], c1 = nodes[nodes[i].offset];
+    const nnbvh_linear_node c0 = nodes[i + 1], c1 = nodes[rootOf[i] + nodes[i].offset];
     Box6 b, o;
     box_init(b);
     for (int k = 0; k < 3; ++k) o.mn[k] = c0.pmin[k], o.mx[k] = c0.pmax[k];
@@ -1493,8 +1532,33 @@ bool gpu_sah(const nnbvh_prim *prims, int n, const float *verts, int n_verts, co
     return ok;
 }
 
+// one tree = a forest of one object
 bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error) {
-    const int n = in.n_prims, n_verts = in.n_verts;
+    const int object_first[2] = {0, in.n_prims};
+    ForestBuildResult f;
+    if (!gpu_sah_forest_device(in, object_first, 1, &f, error)) return false;
+    out->d_nodes = f.d_nodes;
+    out->d_ordered = f.d_ordered;
+    out->total_nodes = f.total_nodes;
+    out->depth = f.depth[0];
+    for (int k = 1; k <= 3; ++k) out->ms[k] = f.ms[k];
+    out->n_treelets = f.n_subtrees;
+    out->n_unique_codes = f.n_upper;
+    return true;
+}
+
+bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *objectFirst, int nObjects, ForestBuildResult *out,
+                           std::string *error) {
+    const int nAll = in.n_prims, n_verts = in.n_verts;
+    if (!objectFirst || nObjects < 1 || objectFirst[0] != 0 || objectFirst[nObjects] != nAll) {
+        *error = "gpu build: malformed object_first (it starts at 0 and ends at n_prims)";
+        return false;
+    }
+    for (int k = 0; k < nObjects; ++k)
+        if (objectFirst[k + 1] <= objectFirst[k]) {
+            *error = "gpu build: malformed object_first (an object is empty or the entries decrease)";
+            return false;
+        }
     const nnbvh_prim *dPrims = in.d_prims;
     const float *dVerts = in.d_verts, *dCaller = in.d_prim_bounds;
     const int maxPrims = std::min(255, in.max_prims_in_node);
@@ -1505,56 +1569,74 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
     mem.error = outMem.error = error;
     mem.pool = in.pool;
 
+    // What a loop of one-object builds would have reported: the failure of the lowest-numbered object, and within
+    // one object the first in the order of the phases.  refuse() is called in that order, so a tie keeps the earlier.
+    int refusedObject = kNoObject;
+    std::string refusal;
+    auto refuse = [&](int object, const std::string &text) {
+        if (object < refusedObject) {
+            refusedObject = object;
+            refusal = text;
+        }
+    };
+
     auto t0 = std::chrono::steady_clock::now();
-    Box6 *dPb = mem.get<Box6>(n);
-    int *dPerm = mem.get<int>(n);
-    int *dLfFlag = mem.get<int>((size_t)n + 1), *dRtFlag = mem.get<int>((size_t)n + 1);
-    int *dLfScan = mem.get<int>((size_t)n + 1), *dRtScan = mem.get<int>((size_t)n + 1);
-    int *dLfPos = mem.get<int>(n), *dRtPos = mem.get<int>(n);
-    unsigned *dCodesUnused = mem.get<unsigned>(n);
-    int *dScalars = mem.get<int>(16);
+    Box6 *dPb = mem.get<Box6>(nAll);
+    int *dPerm = mem.get<int>(nAll);
+    int *dLfFlag = mem.get<int>((size_t)nAll + 1), *dRtFlag = mem.get<int>((size_t)nAll + 1);
+    int *dLfScan = mem.get<int>((size_t)nAll + 1), *dRtScan = mem.get<int>((size_t)nAll + 1);
+    int *dLfPos = mem.get<int>(nAll), *dRtPos = mem.get<int>(nAll);
+    int *dObjectFirst = mem.get<int>((size_t)nObjects + 1);
+    int *dScalars = mem.get<int>(8 + kErrWords);  // [0..5] centroid-bound keys (k_prim_bounds' by-product), [8..] errObj
     if (!mem.ok) return false;
-    const int init[16] = {-1, -1, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int init[8 + kErrWords] = {-1, -1, -1, 0, 0, 0, 0, 0};  // min keys all-ones, max keys 0, errObj[0] = 0
+    for (int k = 1; k < kErrWords; ++k) init[8 + k] = kNoObject;
     GB_CHECK(hipMemcpyAsync(dScalars, init, sizeof init, hipMemcpyHostToDevice, stream), "init scalars");
-    int *dErr = dScalars + 6;
-    hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(n, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts, dCaller, n,
-                       dPb, (unsigned *)dScalars, dErr);
-    hipLaunchKernelGGL(k_morton, dim3(grid_for(n)), dim3(kB), 0, stream, dPb, (unsigned *)dScalars, n, dCodesUnused,
-                       dPerm);  // only for perm[i] = i
+    GB_CHECK(hipMemcpyAsync(dObjectFirst, objectFirst, ((size_t)nObjects + 1) * sizeof(int), hipMemcpyHostToDevice, stream),
+             "copy object_first");
+    int *dErrObj = dScalars + 8;
+    hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(nAll, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts, dCaller, nAll,
+                       dPb, (unsigned *)dScalars, (int *)nullptr, (const int *)dObjectFirst, nObjects, dErrObj);
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(nAll)), dim3(kB), 0, stream, nAll, dPerm);
     size_t scanBytes = 0;
-    GB_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, dLfFlag, dLfScan, 0, (size_t)n + 1, rocprim::plus<int>(), stream),
+    GB_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, dLfFlag, dLfScan, 0, (size_t)nAll + 1, rocprim::plus<int>(), stream),
              "scan (size query)");
     void *dTmp = mem.get<char>(scanBytes);
     if (!mem.ok) return false;
-    int errNow = 0;
-    GB_CHECK(hipMemcpyAsync(&errNow, dErr, sizeof(int), hipMemcpyDeviceToHost, stream), "read error flag");
+    int errWords[kErrWords];
+    GB_CHECK(hipMemcpyAsync(errWords, dErrObj, sizeof errWords, hipMemcpyDeviceToHost, stream), "read error words");
     GB_CHECK(hipStreamSynchronize(stream), "sync after bounds");
-    if (errNow != 0) {
-        *error = errNow == kErrVertex       ? "nnbvh_build_create: vertex index out of range"
-                 : errNow == kErrNeedBounds ? "nnbvh_build_create: instance / host primitives need prim_bounds"
-                 : errNow == kErrNonFinite  ? "nnbvh_build_create: non-finite vertex or primitive bounds"
-                                            : "nnbvh_build_create: unknown primitive kind";
+    refuse(errWords[kErrVertex], "nnbvh_build_create: vertex index out of range");
+    refuse(errWords[kErrNeedBounds], "nnbvh_build_create: instance / host primitives need prim_bounds");
+    refuse(errWords[kErrNonFinite], "nnbvh_build_create: non-finite vertex or primitive bounds");
+    refuse(errWords[kErrKind], "nnbvh_build_create: unknown primitive kind");
+    // Objects from the first malformed one on are not built: only a lower-numbered object can still change the
+    // message, and no malformed primitive reaches the phases below.
+    const int nBuild = std::min(nObjects, refusedObject);
+    if (nBuild == 0) {
+        *error = refusal;
         return false;
     }
+    const int n = objectFirst[nBuild];
 
-    // ---- phase A: big nodes, breadth-first -------------------------------------------------------------
+    // ---- phase A: big nodes, breadth-first, every object's at once -------------------------------------------
     struct Big {
-        int start, n, host;  // host = HostNode index
+        int start, n, host, object;  // host = HostNode index
     };
     std::vector<HostNode> hostNodes;
     std::vector<SmallSeg> smallSegs;
     std::vector<Big> level;
-    int rootRef;  // >= 0 host node, < 0 ~small segment
-    auto make_child = [&](int start, int cnt, std::vector<Big> &next) -> int {
+    std::vector<int> rootRef((size_t)nBuild);  // >= 0 host node, < 0 ~small segment
+    auto make_child = [&](int start, int cnt, int object, std::vector<Big> &next) -> int {
         if (cnt > kSmallSegment) {
             hostNodes.push_back(HostNode{{0, 0}, 0});
-            next.push_back(Big{start, cnt, (int)hostNodes.size() - 1});
+            next.push_back(Big{start, cnt, (int)hostNodes.size() - 1, object});
             return (int)hostNodes.size() - 1;
         }
-        smallSegs.push_back(SmallSeg{start, cnt, 0});
+        smallSegs.push_back(SmallSeg{start, cnt, 0, object, objectFirst[object]});
         return ~((int)smallSegs.size() - 1);
     };
-    rootRef = make_child(0, n, level);
+    for (int k = 0; k < nBuild; ++k) rootRef[(size_t)k] = make_child(objectFirst[k], objectFirst[k + 1] - objectFirst[k], k, level);
     std::vector<Tile> tiles;
     Tile *dTiles = nullptr;
     SegInfo *dInfo = nullptr;
@@ -1566,7 +1648,9 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
     SegStart *dSegStart = nullptr;
     HBox *dSegBounds = nullptr;
     int2 *dVerdict = nullptr;
+    int nLevels = 0;
     while (!level.empty()) {
+        ++nLevels;
         const int nSeg = (int)level.size();
         tiles.clear();
         segStarts.resize((size_t)nSeg);
@@ -1615,18 +1699,18 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
         std::vector<Big> next;
         for (int s = 0; s < nSeg; ++s) {
             const int dim = verdicts[(size_t)s].x, mid = verdicts[(size_t)s].y;
-            const int host = level[s].host;
+            const int host = level[s].host, object = level[s].object;
             if (mid <= 0) {
                 // a big node that does not split (coincident centroids / flat bounds): it becomes a
                 // subtree for the wavefront builder, which reaches the same verdict and makes the leaf
-                smallSegs.push_back(SmallSeg{level[s].start, level[s].n, 0});
+                smallSegs.push_back(SmallSeg{level[s].start, level[s].n, 0, object, objectFirst[object]});
                 hostNodes[(size_t)host].axis = -1;
                 hostNodes[(size_t)host].child[0] = ~((int)smallSegs.size() - 1);
                 hostNodes[(size_t)host].child[1] = 0;
                 continue;
             }
-            const int c0 = make_child(level[s].start, mid, next);
-            const int c1 = make_child(level[s].start + mid, level[s].n - mid, next);
+            const int c0 = make_child(level[s].start, mid, object, next);
+            const int c1 = make_child(level[s].start + mid, level[s].n - mid, object, next);
             hostNodes[(size_t)host].axis = dim;  // (index again: make_child may have grown the vector)
             hostNodes[(size_t)host].child[0] = c0;
             hostNodes[(size_t)host].child[1] = c1;
@@ -1637,7 +1721,7 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
     // every one of them is "right part, predicate false" -> stays in place.
     out->ms[1] = ms_since(t0);
 
-    // ---- phase B ------------------------------------------------------------------------------------------
+    // ---- phase B: every object's subtrees in one launch ---------------------------------------------------------
     t0 = std::chrono::steady_clock::now();
     const int nSmall = (int)smallSegs.size();
     long poolTotal = 0;
@@ -1655,80 +1739,91 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
     if (!mem.ok) return false;
     GB_CHECK(hipMemcpyAsync(dSegs, smallSegs.data(), (size_t)nSmall * sizeof(SmallSeg), hipMemcpyHostToDevice, stream), "copy subtrees");
     hipLaunchKernelGGL(k_sah_subtrees, dim3(nSmall), dim3(64), 0, stream, dSegs, nSmall, maxPrims, dPb, dPerm, dLfPos,
-                       dRtPos, dPool, dSegCount, dSegDepth, dErr);
+                       dRtPos, dPool, dSegCount, dSegDepth, dErrObj);
     std::vector<int> segCount((size_t)nSmall), segDepth((size_t)nSmall);
     GB_CHECK(hipMemcpyAsync(segCount.data(), dSegCount, (size_t)nSmall * sizeof(int), hipMemcpyDeviceToHost, stream), "read counts");
     GB_CHECK(hipMemcpyAsync(segDepth.data(), dSegDepth, (size_t)nSmall * sizeof(int), hipMemcpyDeviceToHost, stream), "read depths");
-    int errWords[kSahCostsFlag + 1] = {0, 0, 0, 0};
-    GB_CHECK(hipMemcpyAsync(errWords, dErr, sizeof errWords, hipMemcpyDeviceToHost, stream), "read error flag");
+    GB_CHECK(hipMemcpyAsync(errWords, dErrObj, sizeof errWords, hipMemcpyDeviceToHost, stream), "read error words");
     GB_CHECK(hipStreamSynchronize(stream), "sync (subtrees)");
-    errNow = errWords[0];
-    if (errWords[kSahCostsFlag] != 0) {  // first, as on the host, whatever else another subtree reported
-        *error = kSahCostsErrorText;
+    if (errWords[0] != 0) {
+        *error = "gpu build: internal error " + std::to_string(errWords[0]);
         return false;
     }
-    if (errNow != 0) {
-        *error = errNow == kErrLeafSize ? "nnbvh_build_create: a leaf would hold more than 65535 primitives"
-                                        : "gpu build: internal error " + std::to_string(errNow);
-        return false;
-    }
+    refuse(errWords[kErrSahCosts], kSahCostsErrorText);  // first, as on the host, whatever else the object's subtrees reported
+    refuse(errWords[kErrLeafSize], "nnbvh_build_create: a leaf would hold more than 65535 primitives");
     out->ms[2] = ms_since(t0);
 
-    // ---- phase C: DFS layout (flattenBVH, :505-522) ----------------------------------------------------------
+    // ---- phase C: DFS layout (flattenBVH, :505-522), tree after tree ------------------------------------------
     t0 = std::chrono::steady_clock::now();
-    std::vector<int> segBase((size_t)nSmall), segBaseDepth((size_t)nSmall);
+    std::vector<SegPlace> place((size_t)nSmall);
     std::vector<UpperNode> upper;
-    int offset = 0, maxDepth = 0;
+    out->node_first.assign((size_t)nBuild + 1, 0);
+    out->depth.assign((size_t)nBuild, 0);
+    int maxDepthAll = 0;
     // iterative DFS over the phase-A tree
     struct Frame {
         int ref, depth, parentUpper, which;
     };
     std::vector<Frame> stack;
-    stack.push_back(Frame{rootRef, 0, -1, 0});
-    while (!stack.empty()) {
-        Frame f = stack.back();
-        stack.pop_back();
-        int ref = f.ref;
-        // a delegated big node stands for its subtree
-        if (ref >= 0 && hostNodes[(size_t)ref].axis < 0) ref = hostNodes[(size_t)ref].child[0];
-        if (f.which == 1) upper[(size_t)f.parentUpper].second = offset;
-        if (ref < 0) {
-            const int sidx = ~ref;
-            segBase[(size_t)sidx] = offset;
-            segBaseDepth[(size_t)sidx] = f.depth;
-            offset += segCount[(size_t)sidx];
-            maxDepth = std::max(maxDepth, f.depth + segDepth[(size_t)sidx]);
-            continue;
+    for (int k = 0; k < nBuild; ++k) {
+        const int root = out->node_first[(size_t)k];
+        int offset = 0, maxDepth = 0;  // offset: from the tree's own root
+        stack.push_back(Frame{rootRef[(size_t)k], 0, -1, 0});
+        while (!stack.empty()) {
+            Frame f = stack.back();
+            stack.pop_back();
+            int ref = f.ref;
+            // a delegated big node stands for its subtree
+            if (ref >= 0 && hostNodes[(size_t)ref].axis < 0) ref = hostNodes[(size_t)ref].child[0];
+            if (f.which == 1) upper[(size_t)f.parentUpper].second = offset;
+            if (ref < 0) {
+                const int sidx = ~ref;
+                place[(size_t)sidx] = SegPlace{root + offset, offset, f.depth};
+                offset += segCount[(size_t)sidx];
+                maxDepth = std::max(maxDepth, f.depth + segDepth[(size_t)sidx]);
+                continue;
+            }
+            const HostNode &hn = hostNodes[(size_t)ref];
+            upper.push_back(UpperNode{root + offset, 0, hn.axis, f.depth, root});
+            const int me = (int)upper.size() - 1;
+            ++offset;
+            stack.push_back(Frame{hn.child[1], f.depth + 1, me, 1});  // popped after the whole left subtree
+            stack.push_back(Frame{hn.child[0], f.depth + 1, me, 0});
         }
-        const HostNode &hn = hostNodes[(size_t)ref];
-        upper.push_back(UpperNode{offset, 0, hn.axis, f.depth});
-        const int me = (int)upper.size() - 1;
-        ++offset;
-        stack.push_back(Frame{hn.child[1], f.depth + 1, me, 1});  // popped after the whole left subtree
-        stack.push_back(Frame{hn.child[0], f.depth + 1, me, 0});
+        if ((long)root + offset >= 0x7fffffffL) {
+            *error = "gpu build: too many nodes";
+            return false;
+        }
+        out->node_first[(size_t)k + 1] = root + offset;
+        out->depth[(size_t)k] = maxDepth;
+        maxDepthAll = std::max(maxDepthAll, maxDepth);
+        if (maxDepth > 255) {
+            refuse(k, "gpu build: tree deeper than 255 levels");
+            break;  // (no later object changes the message)
+        }
     }
-    const int totalNodes = offset;
-    if (maxDepth > 255) {
-        *error = "gpu build: tree deeper than 255 levels";
+    if (refusedObject != kNoObject) {
+        *error = refusal;
         return false;
     }
+    const int totalNodes = out->node_first[(size_t)nBuild];
     nnbvh_linear_node *dNodes = in.d_nodes_out ? in.d_nodes_out : outMem.get<nnbvh_linear_node>((size_t)totalNodes);
     unsigned char *dDepthOf = mem.get<unsigned char>((size_t)totalNodes);
-    int *dSegBase = mem.get<int>(nSmall), *dSegBaseDepth = mem.get<int>(nSmall);
+    int *dRootOf = mem.get<int>((size_t)totalNodes);
+    SegPlace *dPlace = mem.get<SegPlace>(nSmall);
     UpperNode *dUpper = mem.get<UpperNode>(upper.size());
     nnbvh_prim *dOrdered = in.d_ordered_out ? in.d_ordered_out : outMem.get<nnbvh_prim>(n);
     if (!mem.ok || !outMem.ok) return false;
-    GB_CHECK(hipMemcpyAsync(dSegBase, segBase.data(), (size_t)nSmall * sizeof(int), hipMemcpyHostToDevice, stream), "copy bases");
-    GB_CHECK(hipMemcpyAsync(dSegBaseDepth, segBaseDepth.data(), (size_t)nSmall * sizeof(int), hipMemcpyHostToDevice, stream), "copy depths");
+    GB_CHECK(hipMemcpyAsync(dPlace, place.data(), (size_t)nSmall * sizeof(SegPlace), hipMemcpyHostToDevice, stream), "copy bases");
     if (!upper.empty())
         GB_CHECK(hipMemcpyAsync(dUpper, upper.data(), upper.size() * sizeof(UpperNode), hipMemcpyHostToDevice, stream), "copy upper nodes");
-    hipLaunchKernelGGL(k_sah_emit, dim3(nSmall), dim3(kB), 0, stream, dSegs, dSegCount, dSegBase, dSegBaseDepth, dPool, dNodes,
-                       dDepthOf);
+    hipLaunchKernelGGL(k_sah_emit, dim3(nSmall), dim3(kB), 0, stream, dSegs, dSegCount, dPlace, dPool, dNodes, dDepthOf, dRootOf);
     if (!upper.empty())
         hipLaunchKernelGGL(k_sah_upper, dim3(grid_all((long)upper.size())), dim3(kB), 0, stream, dUpper, (int)upper.size(),
-                           dNodes, dDepthOf);
-    for (int lvl = maxDepth - 1; lvl >= 0; --lvl)
-        hipLaunchKernelGGL(k_sah_level_bounds, dim3(grid_all(totalNodes)), dim3(kB), 0, stream, totalNodes, lvl, dDepthOf, dNodes);
+                           dNodes, dDepthOf, dRootOf);
+    for (int lvl = maxDepthAll - 1; lvl >= 0; --lvl)
+        hipLaunchKernelGGL(k_sah_level_bounds, dim3(grid_all(totalNodes)), dim3(kB), 0, stream, totalNodes, lvl, dDepthOf, dRootOf,
+                           dNodes);
     hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kB), 0, stream, dPrims, dPerm, n, dOrdered);
     GB_CHECK(hipGetLastError(), "kernel launch");
     GB_CHECK(hipStreamSynchronize(stream), "sync after emit");
@@ -1739,10 +1834,11 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
     out->d_ordered = dOrdered;
     outMem.release(dNodes);
     outMem.release(dOrdered);
-    out->depth = maxDepth;
-    out->n_treelets = nSmall;
-    out->n_unique_codes = (int)upper.size();
+    out->n_levels = nLevels;
+    out->n_subtrees = nSmall;
+    out->n_upper = (int)upper.size();
     return true;
 }
 
 }  // namespace nnbvh
+

@@ -1,12 +1,15 @@
 // capi_two_level.cpp — nnbvh_scene_create_instanced_gpu_build: a two-level scene (object instances as pbrt builds
 // them, scene.cpp:1521-1577) from the caller's primitive lists to traceable without a tree visiting the host.  Every
-// object definition's tree, then the top-level tree over the instances' transformed bounds, come from the device
-// builders' cores (bvh_build_gpu.hip); the trees are put into one numbering and baked by bvh_bake.hip.  The device
+// object definition's tree (SAH: all of them in one forest pass; HLBVH: one after another), then the top-level tree
+// over the instances' transformed bounds, come from the device builders' cores (bvh_build_gpu.hip); the trees are put
+// into one numbering and baked by bvh_bake.hip.  nnbvh_build_forest_create_gpu, at the end, is that forest pass alone.  The device
 // arrays are byte for byte those of nn_bvh_amd.instancing.assemble_two_level + nnbvh_scene_create_instanced_with_attributes.
 // Host code only.
 #include <algorithm>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "bvh_build_gpu.h"
@@ -21,6 +24,48 @@ const char *kFn = "scene_create_instanced_gpu_build: ";
 bool fault(const std::string &msg) {
     set_error(msg);
     return false;
+}
+
+// The per-primitive part of the checks below, for the scene call and the forest call alike: kinds, vertex indices,
+// the arrays a kind needs.  A scene's list is [n_top_prims top-level entries, the objects' primitives]; a forest's
+// has objects only (n_top_prims = 0, no placements) and builds trees, which read no vertex attributes.
+struct PrimListCheck {
+    int n_top_prims = 0, n_placements = 0;
+    const nnbvh_animated_transform *animated = nullptr;
+    const float *prim_bounds = nullptr, *normals = nullptr, *uvs = nullptr, *prim_alpha = nullptr;
+    bool scene = true;  // false: a forest of trees: attributes are not asked for, instance entries have no place
+};
+bool check_prims(const nnbvh_prim *prims, int n_prims, int n_verts, const PrimListCheck &c) {
+    for (int i = 0; i < n_prims; ++i) {
+        const nnbvh_prim &p = prims[i];
+        int nv = 0;
+        if (p.kind == NNBVH_PRIM_INSTANCE) {
+            if (!c.scene) return fault("nnbvh_build_forest_create_gpu: instance entries are not built in a forest");
+            if (i >= c.n_top_prims) return fault("scene_create: nested instances are not supported");
+            if (p.v[0] < 0 || p.v[0] >= c.n_placements) return fault("scene_create: instance index out of range");
+            if (c.animated && c.animated[p.v[0]].actually_animated && !c.prim_bounds)
+                return fault("nnbvh_build_create: instance / host primitives need prim_bounds");
+        } else if (p.kind == NNBVH_PRIM_HOST) {
+            if (!c.prim_bounds) return fault("nnbvh_build_create: instance / host primitives need prim_bounds");
+        } else if (is_smooth_alpha_kind(p.kind)) {
+            nv = 3;
+            if (c.scene && !c.normals)
+                return fault("scene_create: NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH primitives need the vertex normals "
+                             "(nnbvh_scene_create_with_normals)");
+        } else if (is_alpha_patch_kind(p.kind)) {
+            nv = 4;
+            if (c.scene && (!c.prim_alpha || (is_smooth_alpha_patch_kind(p.kind) && !c.normals) ||
+                            (is_uv_alpha_patch_kind(p.kind) && !c.uvs)))
+                return fault("scene_create: NNBVH_PRIM_ALPHA_PATCH primitives need the per-primitive alpha array, the "
+                             "smooth ones the vertex normals, the _UV ones the vertex uvs too "
+                             "(nnbvh_scene_create_with_attributes)");
+        } else if (is_triangle_kind(p.kind)) nv = 3;
+        else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = 4;
+        else return fault("scene_create: unknown primitive kind");
+        for (int j = 0; j < nv; ++j)
+            if (p.v[j] < 0 || p.v[j] >= n_verts) return fault("nnbvh_build_create: vertex index out of range");
+    }
+    return true;
 }
 
 // Everything a kernel indexes with, checked on the host arrays before a device is looked at.
@@ -44,34 +89,34 @@ bool check_arguments(const nnbvh_prim *prims, int n_prims, int n_top_prims, cons
         if (animated && animated[j].actually_animated && !(animated[j].end_time > animated[j].start_time))
             return fault("scene_create: animated instance with an empty time range");
     }
-    for (int i = 0; i < n_prims; ++i) {
-        const nnbvh_prim &p = prims[i];
-        int nv = 0;
-        if (p.kind == NNBVH_PRIM_INSTANCE) {
-            if (i >= n_top_prims) return fault("scene_create: nested instances are not supported");
-            if (p.v[0] < 0 || p.v[0] >= n_placements) return fault("scene_create: instance index out of range");
-            if (animated && animated[p.v[0]].actually_animated && !prim_bounds)
-                return fault("nnbvh_build_create: instance / host primitives need prim_bounds");
-        } else if (p.kind == NNBVH_PRIM_HOST) {
-            if (!prim_bounds) return fault("nnbvh_build_create: instance / host primitives need prim_bounds");
-        } else if (is_smooth_alpha_kind(p.kind)) {
-            nv = 3;
-            if (!normals)
-                return fault("scene_create: NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH primitives need the vertex normals "
-                             "(nnbvh_scene_create_with_normals)");
-        } else if (is_alpha_patch_kind(p.kind)) {
-            nv = 4;
-            if (!prim_alpha || (is_smooth_alpha_patch_kind(p.kind) && !normals) || (is_uv_alpha_patch_kind(p.kind) && !uvs))
-                return fault("scene_create: NNBVH_PRIM_ALPHA_PATCH primitives need the per-primitive alpha array, the "
-                             "smooth ones the vertex normals, the _UV ones the vertex uvs too "
-                             "(nnbvh_scene_create_with_attributes)");
-        } else if (is_triangle_kind(p.kind)) nv = 3;
-        else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = 4;
-        else return fault("scene_create: unknown primitive kind");
-        for (int j = 0; j < nv; ++j)
-            if (p.v[j] < 0 || p.v[j] >= n_verts) return fault("nnbvh_build_create: vertex index out of range");
-    }
-    return true;
+    PrimListCheck c;
+    c.n_top_prims = n_top_prims;
+    c.n_placements = n_placements;
+    c.animated = animated;
+    c.prim_bounds = prim_bounds;
+    c.normals = normals;
+    c.uvs = uvs;
+    c.prim_alpha = prim_alpha;
+    return check_prims(prims, n_prims, n_verts, c);
+}
+
+// The forest call's: the same faults in the same words where the two calls share them.
+bool check_forest_arguments(const nnbvh_prim *prims, int n_prims, const int32_t *object_first, int n_objects,
+                            const float *verts, int n_verts, const float *prim_bounds, int split_method) {
+    const char *fn = "nnbvh_build_forest_create_gpu: ";
+    if (!prims || !verts || !object_first || n_prims <= 0 || n_verts <= 0 || n_objects <= 0)
+        return fault(std::string(fn) + "null or empty input array");
+    if (object_first[0] != 0 || object_first[n_objects] != n_prims)
+        return fault(std::string(fn) + "malformed object_first (it starts at 0 and ends at n_prims)");
+    for (int k = 0; k < n_objects; ++k)
+        if (object_first[k + 1] <= object_first[k])
+            return fault(std::string(fn) + "malformed object_first (an object is empty or the entries decrease)");
+    if (split_method != NNBVH_SPLIT_SAH)
+        return fault(std::string(fn) + "the forest build is SAH only (split_method NNBVH_SPLIT_SAH)");
+    PrimListCheck c;
+    c.prim_bounds = prim_bounds;
+    c.scene = false;
+    return check_prims(prims, n_prims, n_verts, c);
 }
 
 // the call's device memory and stream: freed on every way out
@@ -196,7 +241,36 @@ extern "C" nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(
         if (!built) set_error(err);
         return built;
     };
-    for (int k = 0; k < n_objects; ++k) {
+    // SAH: all objects in one forest pass.  NNBVH_TWO_LEVEL_LOOP=1 keeps the object-by-object loop for them too (speed
+    // only, like NNBVH_SAH_SMALL: the same bytes either way); HLBVH has no forest form and always loops
+    const char *loop_env = std::getenv("NNBVH_TWO_LEVEL_LOOP");
+    const bool forest = split_method == NNBVH_SPLIT_SAH && !(loop_env && std::atoi(loop_env) != 0);
+    if (forest) {
+        std::vector<int> local_first((size_t)n_objects + 1);
+        for (int k = 0; k <= n_objects; ++k) local_first[(size_t)k] = object_first[k] - n_top_prims;
+        DeviceBuildInput in;
+        in.d_prims = d_prims + n_top_prims;
+        in.n_prims = n_obj_prims;
+        in.d_prim_bounds = prim_bounds ? d_bounds + 6 * (size_t)n_top_prims : nullptr;
+        in.d_nodes_out = d_child_nodes;
+        in.d_ordered_out = d_ordered + n_top_prims;
+        in.d_verts = d_verts;
+        in.n_verts = n_verts;
+        in.max_prims_in_node = max_prims_in_node;
+        in.stream = stream;
+        in.pool = &h.pool;
+        ForestBuildResult f;
+        if (!gpu_sah_forest_device(in, local_first.data(), n_objects, &f, &err)) {
+            set_error(err);
+            return nullptr;
+        }
+        child_total = f.total_nodes;
+        for (int k = 0; k < n_objects; ++k) {
+            child_base[(size_t)k] = f.node_first[(size_t)k];
+            if (named[(size_t)k]) child_depth = std::max(child_depth, f.depth[(size_t)k] + 1);
+        }
+    }
+    for (int k = 0; k < n_objects && !forest; ++k) {
         const int first = object_first[k], count = object_first[k + 1] - first;
         DeviceBuildInput in;
         in.d_prims = d_prims + first;
@@ -319,3 +393,108 @@ extern "C" nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(
     s->build_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return s;
 }
+
+// ---- nnbvh_build_forest_create_gpu: the object trees alone, downloaded ------------------------------------------------
+// (here and not beside nnbvh_build_create_gpu: bvh_build.cpp is also built on its own, without the device code, and
+// this call shares its argument checks with the scene call above)
+struct nnbvh_forest {
+    std::vector<nnbvh_linear_node> nodes;
+    std::vector<nnbvh_prim> ordered;
+    std::vector<int32_t> node_first, depths;
+    double ms[5] = {0, 0, 0, 0, 0};
+    int n_levels = 0, n_subtrees = 0;
+};
+
+extern "C" nnbvh_forest *nnbvh_build_forest_create_gpu(const nnbvh_prim *prims, int n_prims, const int32_t *object_first,
+                                                       int n_objects, const float *verts, int n_verts,
+                                                       const float *prim_bounds, int max_prims_in_node, int split_method,
+                                                       int device) {
+    if (!check_forest_arguments(prims, n_prims, object_first, n_objects, verts, n_verts, prim_bounds, split_method))
+        return nullptr;
+    const int n_dev = nnbvh_device_count();
+    if (n_dev <= 0 || device < 0 || device >= n_dev) {
+        set_error("nnbvh_build_forest_create_gpu: no usable HIP device (this library has no CPU fallback)");
+        return nullptr;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) return nullptr;
+    auto since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    Held h;
+    if (!hip_ok(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking), "hipStreamCreate")) return nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    nnbvh_prim *d_prims = h.get<nnbvh_prim>((size_t)n_prims, "hipMalloc(primitives)");
+    float *d_verts = h.get<float>(3 * (size_t)n_verts, "hipMalloc(vertices)");
+    float *d_bounds = prim_bounds ? h.get<float>(6 * (size_t)n_prims, "hipMalloc(bounds)") : nullptr;
+    if (!d_prims || !d_verts || (prim_bounds && !d_bounds)) return nullptr;
+    bool ok = put(d_prims, prims, (size_t)n_prims, h.stream, "hipMemcpy(primitives)") &&
+              put(d_verts, verts, 3 * (size_t)n_verts, h.stream, "hipMemcpy(vertices)");
+    if (ok && prim_bounds) ok = put(d_bounds, prim_bounds, 6 * (size_t)n_prims, h.stream, "hipMemcpy(bounds)");
+    if (!ok || !hip_ok(hipStreamSynchronize(h.stream), "upload")) return nullptr;
+    auto out = std::make_unique<nnbvh_forest>();
+    out->ms[0] = since(t0);
+
+    DeviceBuildInput in;
+    in.d_prims = d_prims;
+    in.n_prims = n_prims;
+    in.d_verts = d_verts;
+    in.n_verts = n_verts;
+    in.d_prim_bounds = d_bounds;
+    in.max_prims_in_node = max_prims_in_node;
+    in.stream = h.stream;
+    in.pool = &h.pool;
+    ForestBuildResult f;
+    std::string err;
+    if (!gpu_sah_forest_device(in, (const int *)object_first, n_objects, &f, &err)) {
+        set_error(err);
+        return nullptr;
+    }
+    h.ptrs.push_back(f.d_nodes);
+    h.ptrs.push_back(f.d_ordered);
+    t0 = std::chrono::steady_clock::now();
+    out->nodes.resize((size_t)f.total_nodes);
+    out->ordered.resize((size_t)n_prims);
+    if (!hip_ok(hipMemcpyAsync(out->nodes.data(), f.d_nodes, out->nodes.size() * sizeof(nnbvh_linear_node),
+                               hipMemcpyDeviceToHost, h.stream), "hipMemcpy(nodes)") ||
+        !hip_ok(hipMemcpyAsync(out->ordered.data(), f.d_ordered, out->ordered.size() * sizeof(nnbvh_prim),
+                               hipMemcpyDeviceToHost, h.stream), "hipMemcpy(ordered primitives)") ||
+        !hip_ok(hipStreamSynchronize(h.stream), "download"))
+        return nullptr;
+    out->ms[4] = since(t0);
+    for (int k = 1; k <= 3; ++k) out->ms[k] = f.ms[k];
+    out->node_first.assign(f.node_first.begin(), f.node_first.end());
+    out->depths.assign(f.depth.begin(), f.depth.end());
+    out->n_levels = f.n_levels;
+    out->n_subtrees = f.n_subtrees;
+    return out.release();
+}
+
+extern "C" const nnbvh_linear_node *nnbvh_forest_nodes(const nnbvh_forest *f, int *n_nodes) {
+    if (!f) return nullptr;
+    if (n_nodes) *n_nodes = (int)f->nodes.size();
+    return f->nodes.data();
+}
+extern "C" const int32_t *nnbvh_forest_node_first(const nnbvh_forest *f, int *n_objects) {
+    if (!f) return nullptr;
+    if (n_objects) *n_objects = (int)f->depths.size();
+    return f->node_first.data();
+}
+extern "C" const int32_t *nnbvh_forest_depths(const nnbvh_forest *f, int *n_objects) {
+    if (!f) return nullptr;
+    if (n_objects) *n_objects = (int)f->depths.size();
+    return f->depths.data();
+}
+extern "C" const nnbvh_prim *nnbvh_forest_ordered_prims(const nnbvh_forest *f, int *n_prims) {
+    if (!f) return nullptr;
+    if (n_prims) *n_prims = (int)f->ordered.size();
+    return f->ordered.data();
+}
+extern "C" int nnbvh_forest_gpu_timing(const nnbvh_forest *f, double out_ms[5]) {
+    if (!f || !out_ms) return NNBVH_ERR_ARG;
+    std::memcpy(out_ms, f->ms, sizeof f->ms);
+    return NNBVH_OK;
+}
+extern "C" int nnbvh_forest_n_levels(const nnbvh_forest *f) { return f ? f->n_levels : -1; }
+extern "C" int nnbvh_forest_n_subtrees(const nnbvh_forest *f) { return f ? f->n_subtrees : -1; }
+extern "C" void nnbvh_forest_destroy(nnbvh_forest *f) { delete f; }

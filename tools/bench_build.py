@@ -15,9 +15,13 @@ two-level section (--two-level: with the other sections, --two-level-only: alone
 profiles/two_level_device_scene.txt): creating a two-level (instanced) scene, the same way:
   A0 instancing.assemble_two_level + BVHAggregate.from_tree   every tree from the host builder, host bake
   A  the same with the child and top trees from build_tree_gpu (built on the device, downloaded, host bake)
-  B  BVHAggregate.build_two_level_on_device                    every tree built, numbered and baked on the device
+  B  BVHAggregate.build_two_level_on_device                    every tree built, numbered and baked on the device, the
+                                                               object trees in ONE forest pass
+  L  the same with NNBVH_TWO_LEVEL_LOOP=1                      ... the object trees one after another (B before the
+                                                               forest build existed)
 on (i) the 400 placements of the 33 K-triangle killeroo of tools/bench_instances.py and (ii) 2 000 objects of 64
-triangles with 20 000 placements, where the per-object cost of building one tree after another shows."""
+triangles with 20 000 placements, where the per-object cost of building one tree after another shows; with the
+phases of one forest build of the objects alone (build_forest_gpu) and B's peak device memory."""
 import json
 import os
 import sys
@@ -27,7 +31,7 @@ import numpy as np
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from nn_bvh_amd import BVHAggregate, build_tree, build_tree_gpu, make_prims, scene  # noqa: E402
+from nn_bvh_amd import BVHAggregate, build_forest_gpu, build_tree, build_tree_gpu, make_prims, scene  # noqa: E402
 
 
 
@@ -212,9 +216,16 @@ def two_level_section(out_path, rounds=5):
         def route_b():
             return BVHAggregate.build_two_level_on_device(top, verts, objects, placements)
 
-        routes = (route_a0, route_a, route_b)
+        def route_loop():
+            os.environ["NNBVH_TWO_LEVEL_LOOP"] = "1"  # read once per call
+            try:
+                return route_b()
+            finally:
+                del os.environ["NNBVH_TWO_LEVEL_LOOP"]
+
+        routes = (route_a0, route_a, route_loop, route_b)
         ref = None
-        for fn in routes:  # first-call costs outside the timing; and the three scenes are one scene
+        for fn in routes:  # first-call costs outside the timing; and the four scenes are one scene
             agg = fn()
             arrays = (agg.read(0).tobytes(), agg.read(1).tobytes(), agg.info)
             assert ref is None or arrays == ref, f"{fn.__name__} bakes other arrays"
@@ -244,7 +255,12 @@ def two_level_section(out_path, rounds=5):
         th.join()
         kept = base - torch.cuda.mem_get_info()[0]
         agg.close()
-        a_ms, b_ms = ms["route_a"], ms["route_b"]
+        forest = build_forest_gpu(objects, verts)
+        a_ms, b_ms, l_ms, a0_ms = ms["route_a"], ms["route_b"], ms["route_loop"], ms["route_a0"]
+        gain_l = np.median(l_ms) - np.median(b_ms)
+        spread_l = max(max(l_ms) - min(l_ms), max(b_ms) - min(b_ms))
+        verdict_l = ("B ahead of L by more than either spread" if gain_l > spread_l else
+                     "B behind L by more than either spread" if -gain_l > spread_l else "B and L within the spread")
         gain = np.median(a_ms) - np.median(b_ms)
         spread = max(max(a_ms) - min(a_ms), max(b_ms) - min(b_ms))
         verdict = ("B ahead of A by more than either spread" if gain > spread else
@@ -255,12 +271,19 @@ def two_level_section(out_path, rounds=5):
                   f"{info['prim_slots']} slots, depth {info['depth']}",
                   f"  A0 host trees + host bake                 {stats(ms['route_a0'])}",
                   f"  A  device trees, downloaded + host bake   {stats(a_ms)}",
-                  f"  B  build_two_level_on_device              {stats(b_ms)}",
+                  f"  L  build_two_level_on_device, object loop {stats(l_ms)}",
+                  f"  B  build_two_level_on_device, forest      {stats(b_ms)}",
                   f"  median A - median B = {gain:.1f} ms, larger spread {spread:.1f} ms: {verdict}",
+                  f"  median L - median B = {gain_l:.1f} ms, larger spread {spread_l:.1f} ms: {verdict_l}",
+                  f"  median B - median A0 = {np.median(b_ms) - np.median(a0_ms):.1f} ms",
+                  f"  one forest build of the objects alone: upload {forest.gpu_ms[0]:.2f}, big nodes {forest.gpu_ms[1]:.2f}, "
+                  f"subtrees {forest.gpu_ms[2]:.2f}, layout + bounds {forest.gpu_ms[3]:.2f}, download {forest.gpu_ms[4]:.2f} ms; "
+                  f"{forest.n_levels} breadth-first passes, {forest.n_subtrees} subtrees",
                   f"  B device memory: peak {(base - low[0]) / 2**20:.0f} MiB in use during the call (sampled), "
                   f"{kept / 2**20:.0f} MiB kept (scene arrays {info['device_bytes'] / 2**20:.0f} MiB)", ""]
-        result[name] = {"a0_ms": ms["route_a0"], "a_ms": a_ms, "b_ms": b_ms, "peak_bytes": int(base - low[0]),
-                        "scene_bytes": info["device_bytes"], "verdict": verdict}
+        result[name] = {"a0_ms": a0_ms, "a_ms": a_ms, "loop_ms": l_ms, "b_ms": b_ms, "peak_bytes": int(base - low[0]),
+                        "scene_bytes": info["device_bytes"], "verdict": verdict, "verdict_loop": verdict_l,
+                        "forest_phases_ms": forest.gpu_ms}
     text = "\n".join([f"two-level scene creation, {rounds} alternated rounds per scene, one process; "
                       f"{torch.cuda.get_device_name(0)}", ""] + lines)
     print(text)
