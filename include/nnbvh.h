@@ -1058,6 +1058,37 @@ int nnbvh_kd_wavefront_walk_one_random(nnbvh_kd_scene *s, const nnbvh_shading_me
                                        void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum,
                                        int32_t max_surfaces, int32_t *d_unfinished, void *stream);
 
+/* ---- BVH scenes: IntersectShadowTr / IntersectOneRandom walked inside ONE trace launch ---------------------------
+ * nnbvh_kd_wavefront_walk_* above on an nnbvh_scene: the argument lists and outputs of
+ * nnbvh_wavefront_intersect_shadow_tr_bounded / _one_random_bounded with max_surfaces (1..65536) in the place of
+ * max_passes.  The BVH trace kernel's walk instances run the per-item loop inside the lane: a lane
+ * whose closest-hit walk is finished builds the hit record the closest-hit kernel would store, runs one step of the
+ * walk on it and, where the item walks on, re-enters the tree at the root with the spawned ray.  A call is five kernel
+ * launches whatever max_surfaces is: queue-head reset, *d_unfinished reset, init, ONE walk launch, record / finish;
+ * no copy, no memset, no synchronisation and, once the stream's workspace has its size, no allocation: after one
+ * warm-up call with the same max_rays / max_items the call can be captured in a hipGraph.
+ * Finished items get what the bounded and unbounded calls give them, bit for bit.  An item that would start call
+ * max_surfaces + 1 gets the "caller's to finish" mark (state 2 and nothing added to L / instance = -1) and is counted
+ * in *d_unfinished (nullable); so are, uncounted, items whose ray reaches a host-only primitive or a hit the mesh
+ * cannot finish.  Hits inside the instances of a static two-level scene are finished from the mesh's instance table.
+ * max_rays == 0 zeroes *d_unfinished and returns NNBVH_OK.  The walk instances exist at stack window 8 only: the
+ * speed-only option "stack_window" is ignored by these calls.
+ * NNBVH_ERR_ARG with nothing launched: a NULL scene or mesh, max_surfaces outside 1..65536, a negative size, a NULL
+ * array with a non-zero size, a mesh on another device, a scene with AnimatedPrimitive instances, and a scene with
+ * alpha-tested primitives on the device; there are no host-candidate lists.  The bounded and unbounded calls remain
+ * the route for all of these. */
+int nnbvh_wavefront_walk_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                   const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                   const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
+                                   const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                   int64_t n_pixels, uint8_t *d_state, int32_t max_surfaces, int32_t *d_unfinished,
+                                   void *stream);
+int nnbvh_wavefront_walk_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items, const float *d_p0,
+                                    const float *d_p1, const int32_t *d_material, const int32_t *d_size,
+                                    const int32_t *d_prim_material, int64_t n_prim_material, void *d_sel_hits,
+                                    void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum, int32_t max_surfaces,
+                                    int32_t *d_unfinished, void *stream);
+
 /* tuning knobs (speed only, never results): "stack_window" (LDS entries per lane: 4, 8, 16),
  * "blocks_per_cu" (0 = auto), "xcd_queues" (0/1), "prim_weight" / "refill_weight" (1..64: how much a
  * lane waiting on a primitive test / an idle lane counts against a lane waiting on an interior node,

@@ -558,6 +558,27 @@ class HipBVHAggregate {
                                                          stream) != NNBVH_OK)
             fatal("IntersectOneRandomBounded");
     }
+    // ... walked inside ONE trace launch (nnbvh_wavefront_walk_*): the same arguments and outputs with maxSurfaces
+    // (1..65536 Intersect calls per item) for maxPasses; five kernel nodes whatever the bound, hipGraph-capturable after
+    // one warm-up call.  Not for scenes with AnimatedPrimitive instances or alpha-tested primitives (fatal)
+    void WalkShadowTr(const nnbvh_shading_mesh *mesh, int maxRays, const nnbvh_ray_soa &shadowQueue,
+                      const int32_t *dSize, const uint8_t *dPrimClass, int64_t nPrimClass, const float *dLd,
+                      const float *dRu, const float *dRl, const int32_t *dPixelIndex, float *dL, int64_t nPixels,
+                      int maxSurfaces, void *stream, uint8_t *dState = nullptr, int32_t *dUnfinished = nullptr) const {
+        if (nnbvh_wavefront_walk_shadow_tr(scene_, mesh, maxRays, &shadowQueue, dSize, dPrimClass, nPrimClass, dLd, dRu,
+                                           dRl, dPixelIndex, dL, nPixels, dState, maxSurfaces, dUnfinished,
+                                           stream) != NNBVH_OK)
+            fatal("WalkShadowTr");
+    }
+    void WalkOneRandom(const nnbvh_shading_mesh *mesh, int maxItems, const float *dP0, const float *dP1,
+                       const int32_t *dMaterial, const int32_t *dSize, const int32_t *dPrimMaterial,
+                       int64_t nPrimMaterial, void *dSelHits, void *dSelRays, float *dReservoirPdf, int maxSurfaces,
+                       void *stream, float *dWeightSum = nullptr, int32_t *dUnfinished = nullptr) const {
+        if (nnbvh_wavefront_walk_one_random(scene_, mesh, maxItems, dP0, dP1, dMaterial, dSize, dPrimMaterial,
+                                            nPrimMaterial, dSelHits, dSelRays, dReservoirPdf, dWeightSum, maxSurfaces,
+                                            dUnfinished, stream) != NNBVH_OK)
+            fatal("WalkOneRandom");
+    }
 
     nnbvh_scene *handle() const { return scene_; }
 

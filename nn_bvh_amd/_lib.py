@@ -82,6 +82,7 @@ EXPORTS = [
     "nnbvh_wavefront_intersect_shadow_tr", "nnbvh_wavefront_intersect_one_random",
     "nnbvh_wavefront_intersect_shadow_tr_bounded", "nnbvh_wavefront_intersect_one_random_bounded",
     "nnbvh_kd_wavefront_walk_shadow_tr", "nnbvh_kd_wavefront_walk_one_random",
+    "nnbvh_wavefront_walk_shadow_tr", "nnbvh_wavefront_walk_one_random",
     "nnbvh_scene_create_instanced_animated", "nnbvh_wavefront_enqueue_closest_items_device",
     "nnbvh_wavefront_intersect_closest_items", "nnbvh_wavefront_intersect_closest_and_shadow_items",
     "nnbvh_intersect_closest_candidates", "nnbvh_intersect_any_candidates",
@@ -325,6 +326,10 @@ def lib():
     L.nnbvh_kd_wavefront_walk_shadow_tr.argtypes = list(L.nnbvh_wavefront_intersect_shadow_tr_bounded.argtypes)
     L.nnbvh_kd_wavefront_walk_one_random.restype = i32
     L.nnbvh_kd_wavefront_walk_one_random.argtypes = list(L.nnbvh_wavefront_intersect_one_random_bounded.argtypes)
+    L.nnbvh_wavefront_walk_shadow_tr.restype = i32
+    L.nnbvh_wavefront_walk_shadow_tr.argtypes = list(L.nnbvh_wavefront_intersect_shadow_tr_bounded.argtypes)
+    L.nnbvh_wavefront_walk_one_random.restype = i32
+    L.nnbvh_wavefront_walk_one_random.argtypes = list(L.nnbvh_wavefront_intersect_one_random_bounded.argtypes)
     hc = ctypes.POINTER(HostCandidates)
     L.nnbvh_intersect_closest_candidates.restype = i32
     L.nnbvh_intersect_closest_candidates.argtypes = [vp, vp, i64, vp, hc]

@@ -31,6 +31,7 @@
 #include "spawn_math.h"
 #include "stream_access.h"
 #include "trace_math.h"
+#include "walk_math.h"
 
 namespace nnbvh {
 
@@ -124,6 +125,14 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 #ifndef NNBVH_MINW_ALPHA_PATCH
 #define NNBVH_MINW_ALPHA_PATCH 3
 #endif
+// the walk instances (MODE 4 / 5, DESIGN.md §5.5.1: the interaction, the spawn and the reservoir update at retire):
+// bounds chosen from tools/isa_regs.py as the most waves at which no instance spills
+#ifndef NNBVH_MINW_WALK_LEAN
+#define NNBVH_MINW_WALK_LEAN 4
+#endif
+#ifndef NNBVH_MINW_WALK
+#define NNBVH_MINW_WALK 4
+#endif
 // INST = 2: weight of a lane waiting to enter an AnimatedPrimitive in the step selection (interior = 16); 0 = enter
 // at once inside the primitive step (the round-2 form: 11 of 64 lanes active in the interpolation)
 #ifndef NNBVH_ANIM_ENTER_WEIGHT
@@ -136,9 +145,70 @@ __device__ __forceinline__ T pick_batch(const T (&a)[kMaxFusedBatches], int b) {
     return b == 0 ? a[0] : (b == 1 ? a[1] : (b == 2 ? a[2] : a[3]));
 }
 
-template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
-__global__ __launch_bounds__(kBlockThreads, (INST ? 1 : (ALPHA ? (ALPHA == 2 ? NNBVH_MINW_ALPHA_PATCH : NNBVH_MINW_ALPHA) : ((MODE == 0 || MODE == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (PATCH ? 0 : NNBVH_LEAN_EXTRA_WAVES))))
+// A lane takes up the ray {R0, R1} = {o, tMax} {d, time}: the reciprocals and the shear (aggregates.cpp:534-535), cold
+// hit slots, the INST fields, the host flag, the counts (the root is visited), an empty stack and the root slab test.
+// Used at a refill and, in the walk instances, when an item's walk goes on with its spawned ray.  A macro and not a
+// lambda or a function, as KD_BEGIN_RAY (kd_trace.hip): the refill path of the existing instances then compiles to the
+// code it compiled to before the walk instances shared it.
+#define BVH_BEGIN_RAY(R0, R1)                                                                                         \
+    do {                                                                                                              \
+        r.o = {(R0).x, (R0).y, (R0).z};                                                                               \
+        tMax = (R0).w;                                                                                                \
+        const V3 d = {(R1).x, (R1).y, (R1).z};                                                                        \
+        if (PATCH) {                                                                                                  \
+            cold[kColdD][lane] = d.x;                                                                                 \
+            cold[kColdD + 1][lane] = d.y;                                                                             \
+            cold[kColdD + 2][lane] = d.z;                                                                             \
+        }                                                                                                             \
+        /* aggregates.cpp:534-535 */                                                                                  \
+        r.inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};                                                                 \
+        ray_shear(r, d);                                                                                              \
+        if (MODE == 0 || MODE == 3) {                                                                                 \
+            cold[kColdHit][lane] = __int_as_float(-1);                                                                \
+            cold[kColdHit + 1][lane] = 0.0f;                                                                          \
+            cold[kColdHit + 2][lane] = 0.0f;                                                                          \
+            cold[kColdHit + 3][lane] = 0.0f;                                                                          \
+        }                                                                                                             \
+        if (INST) {                                                                                                   \
+            cold[kHitInst][lane] = 0.0f;                                                                              \
+            cold[kCurInst][lane] = 0.0f;                                                                              \
+            cold[kColdTime][lane] = (R1).w; /* ray.time: read by animated instances */                                \
+            floor = -1;                                                                                               \
+        }                                                                                                             \
+        if (!kLean && (HOSTC || p.hasHostPrims)) cold[kColdHost][lane] = 0.0f; /* candidate mode: count 0 */          \
+        if constexpr (WALK != 0) {                                                                                    \
+            cold[kWalkD][lane] = (R1).x;                                                                              \
+            cold[kWalkD + 1][lane] = (R1).y;                                                                          \
+            cold[kWalkD + 2][lane] = (R1).z;                                                                          \
+            cold[kWalkTime][lane] = (R1).w;                                                                           \
+            cold[kWalkTMax][lane] = (R0).w;                                                                           \
+        }                                                                                                             \
+        visited = 1; /* the root */                                                                                   \
+        tests = 0;                                                                                                    \
+        found = false;                                                                                                \
+        sp = base = 0;                                                                                                \
+        float tEntry;                                                                                                 \
+        const bool rootHit = slab_partial(p.rootMin[0], p.rootMin[1], p.rootMin[2], p.rootMax[0], p.rootMax[1],       \
+                                          p.rootMax[2], r, tEntry) &&                                                 \
+                             (tEntry < tMax);                                                                         \
+        cur = rootHit ? p.rootRef : kDone;                                                                            \
+    } while (0)
+
+// MODEW = MODE, or 4 / 5 for the walk instances: MODE 0 (record-reading, one-batch closest hit) with WALK = 1
+// (IntersectShadowTr) / WALK = 2 (IntersectOneRandom); DESIGN.md §5.5.1.  A lane does not retire its ray when the
+// closest-hit walk is finished: it runs one step of the walk for its work item (walk_math.h: the verdicts and arithmetic
+// of the fused pass steps of wavefront2.hip) on the hit record a MODE 0 lane would store and, where the item's walk goes
+// on, re-enters the tree at the root with the spawned ray.  Nothing is written to p.hits.  The ray index a lane fetched
+// is its item.  PATCH = 1 instances compute the interaction with the patch- and instance-capable code (FULL), the lean
+// one with the triangle-only code.  Window 8 only; no ALPHA, SOA, HOSTC or INST = 2 forms.  (WALK rides in the first
+// template argument and not as an eighth one: that would rename every existing instance.)
+template <int MODEW, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
+__global__ __launch_bounds__(kBlockThreads, (MODEW >= 4 ? (INST ? 1 : (PATCH ? NNBVH_MINW_WALK : NNBVH_MINW_WALK_LEAN)) : (INST ? 1 : (ALPHA ? (ALPHA == 2 ? NNBVH_MINW_ALPHA_PATCH : NNBVH_MINW_ALPHA) : ((MODEW == 0 || MODEW == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (PATCH ? 0 : NNBVH_LEAN_EXTRA_WAVES)))))
 void trace_kernel(TraceParams p) {
+    constexpr int WALK = MODEW >= 4 ? MODEW - 3 : 0;
+    constexpr int MODE = WALK ? 0 : MODEW;
+    static_assert(!WALK || (MODEW <= 5 && W == 8 && INST != 2 && !ALPHA && !SOA && !HOSTC),
+                  "walk instances: the plain record-reading closest-hit form at window 8");
     static_assert(PATCH || !INST, "two-level scenes need the ray direction");
     static_assert(PATCH || !ALPHA, "the alpha test hashes the ray direction");
     static_assert(!HOSTC || (PATCH && (MODE == 0 || MODE == 2 || (MODE == 3 && !ALPHA && W == 8)) && !SOA),
@@ -163,7 +233,13 @@ void trace_kernel(TraceParams p) {
                   kSaveKz = kColdBase + 9, kSaveTmax = kColdBase + 10, kSaveD = kColdBase + 11,
                   kResume = kColdBase + 14, kCurInst = kColdBase + 15, kHitInst = kColdBase + 16,
                   kInnerHit = kColdBase + 17, kColdTime = kColdBase + 18, kPendSlot = kColdBase + 19;
-    constexpr int kColdFields = kColdBase + (INST ? 20 : 0);
+    // WALK: six more slots — the direction, time and tMax of the item's current ray (the step needs them for wo, the
+    // selected segment ray and the next ray; the lean instance parks no direction, and an instance overwrites kColdD
+    // while a child tree is traversed) and the number of Intersect calls made for the item
+    constexpr int kColdWalk = kColdBase + (INST ? 20 : 0);
+    [[maybe_unused]] constexpr int kWalkD = kColdWalk, kWalkTime = kColdWalk + 3, kWalkTMax = kColdWalk + 4,
+                                   kWalkCalls = kColdWalk + 5;
+    constexpr int kColdFields = kColdWalk + (WALK ? 6 : 0);
     __shared__ float s_cold[kBlockThreads / 64][kColdFields > 0 ? kColdFields : 1][64];
 
     const int lane = threadIdx.x & 63;
@@ -562,7 +638,49 @@ void trace_kernel(TraceParams p) {
         if (nIdle == 64 || (sR > sI && sR > sP)) {
             // ---- retire finished rays, refill idle lanes -------------------------------
             const int ri = isIdle ? (kLean ? riReg : __float_as_int(cold[kColdRi][lane])) : -1;
-            if constexpr (MODE == 3 && HOSTC) {
+            // WALK: the lane's item walks on from nextO in direction nextD / would start call wMaxSurfaces + 1
+            [[maybe_unused]] bool goOn = false, capped = false;
+            [[maybe_unused]] V3 nextO = {0.0f, 0.0f, 0.0f}, nextD = {0.0f, 0.0f, 0.0f};
+            [[maybe_unused]] float nextTMax = 1.0f, nextTime = 0.0f;  // aggregate.Intersect(r, 1), time 0: WALK 2
+            if constexpr (WALK != 0) {
+                if (ri >= 0) {
+                    // one step of the walk for item ri, on the hit record a MODE 0 lane would store (counters, instance
+                    // word and the "void" rule for host-only primitives included) and the record of the lane's ray
+                    const float4 r0 = {r.o.x, r.o.y, r.o.z, cold[kWalkTMax][lane]};
+                    const float4 r1 = {cold[kWalkD][lane], cold[kWalkD + 1][lane], cold[kWalkD + 2][lane],
+                                       cold[kWalkTime][lane]};
+                    const float4 h0 = {cold[kColdHit][lane], tMax, cold[kColdHit + 1][lane], cold[kColdHit + 2][lane]};
+                    float4 h1 = {cold[kColdHit + 3][lane], __int_as_float(visited), __int_as_float(tests),
+                                 INST ? cold[kHitInst][lane] : 0.0f};
+                    if (!kLean && p.hasHostPrims && cold[kColdHost][lane] != 0.0f) h1.w = __int_as_float(-1);
+                    const ShadingMeshDevice &sm = p.wMesh;
+                    const MeshView wm = {sm.verts, sm.triVerts, sm.patchVerts, sm.normals, sm.uvs, sm.tangents,
+                                         sm.faceIndices, sm.triFlags, sm.nTris, sm.defaultFlags, sm.instances,
+                                         sm.nInstances, sm.anim, sm.animFwd};
+                    if constexpr (WALK == 1) {
+                        goOn = w2_str_item<PATCH != 0>(wm, r0, r1, h0, h1, ri, p.wPrimClass, p.wNPrimClass,
+                                                       p.wPLight, p.wState, nextO, nextD);
+                        nextTMax = r0.w;  // tMax is the work item's, unchanged (intersect.h:175, :187)
+                        nextTime = r1.w;
+                        // the spawned ray has a zero direction: the walk ends, the ray arrives (state stays 0)
+                        if (goOn && nextD.x == 0.0f && nextD.y == 0.0f && nextD.z == 0.0f) goOn = false;
+                    } else {
+                        goOn = w2_or_item<PATCH != 0>(wm, r0, r1, h0, h1, ri, p.wP1, p.wMaterial, p.wPrimMaterial,
+                                                      p.wNPrimMaterial, p.wSt, p.wSelHits, p.wSelRays, nextO, nextD);
+                    }
+                    if (goOn) {
+                        const int calls = __float_as_int(cold[kWalkCalls][lane]);
+                        if (calls >= p.wMaxSurfaces) {  // the caller's to finish, as w2_mark_unfinished marks it
+                            goOn = false;
+                            capped = true;
+                            if constexpr (WALK == 1) p.wState[ri] = 2;
+                            else p.wSelHits[2 * (long)ri + 1].w = __int_as_float(-1);
+                        } else {
+                            cold[kWalkCalls][lane] = __int_as_float(calls + 1);
+                        }
+                    }
+                }
+            } else if constexpr (MODE == 3 && HOSTC) {
                 // candidate mode of the one-launch kernel, a block of its own so that the plain instances' retire
                 // below stays as it is: the count goes to the batch's array; an any-hit ray is the caller's (2) when
                 // it met a host-only primitive, a closest-hit record is void only for count < 0
@@ -650,9 +768,37 @@ void trace_kernel(TraceParams p) {
                 }
             }
             int newRi = -1;  // n < 2^31 is enforced by the ABI
-            if (exhausted) break;  // only reached with every lane idle (sR == 0 otherwise)
+            // the lanes that take a new ray, their number and mask: the idle ones, less (WALK) those that walk on
+            bool takes = isIdle;
+            unsigned long long takeMask = idleMask;
+            int nTake = nIdle;
+            if constexpr (WALK != 0) {
+                const unsigned long long cm = __ballot(capped);
+                if (p.wUnfinished && cm != 0ull && lane == __ffsll((long long)cm) - 1) atomicAdd(p.wUnfinished, __popcll(cm));
+                if (goOn) {  // same item, same lane: the ray index stays
+                    const float4 a = {nextO.x, nextO.y, nextO.z, nextTMax}, b = {nextD.x, nextD.y, nextD.z, nextTime};
+                    BVH_BEGIN_RAY(a, b);
+                }
+                takes = isIdle && !goOn;
+                takeMask = __ballot(takes);
+                nTake = __popcll(takeMask);
+                if (exhausted) {  // every lane was idle: the wave ends when none of them walks on
+                    if (nTake == 64) break;
+                    if (takes) {  // retired: the step must not run on it again
+                        if (kLean) riReg = -1;
+                        else cold[kColdRi][lane] = __int_as_float(-1);
+                    }
+                    if (kLean) masks = ray_masks(r);  // some lanes carry new rays
+                    continue;
+                }
+            } else {
+                if (exhausted) break;  // only reached with every lane idle (sR == 0 otherwise)
+            }
             long start = 0;
             for (;;) {  // find a queue with work left (own XCD's first, then steal)
+                if constexpr (WALK != 0) {
+                    if (nTake == 0) break;  // every idle lane walks on: nothing is drawn
+                }
                 if (MODE == 3) {
                     nRays = p.bN[curBatch];
                     if (const int32_t *nd = p.bNDev[curBatch]) {  // wavefront queues: the size lives on the device
@@ -668,14 +814,14 @@ void trace_kernel(TraceParams p) {
                 unsigned got = 0;
                 if (lane == 0)
                     got = atomicAdd(&p.queue[((MODE == 3 ? curBatch * p.nQueues : 0) + q) * kQueueStrideWords],
-                                    (unsigned)nIdle);
+                                    (unsigned)nTake);
                 got = __builtin_amdgcn_readfirstlane(got);
                 start = qBegin + (long)got;
                 if (start < qEnd) {
                     const int rank = __builtin_amdgcn_mbcnt_hi(
-                        (unsigned)(idleMask >> 32),
-                        __builtin_amdgcn_mbcnt_lo((unsigned)idleMask, 0u));
-                    if (isIdle && start + rank < qEnd) newRi = (int)(start + rank);
+                        (unsigned)(takeMask >> 32),
+                        __builtin_amdgcn_mbcnt_lo((unsigned)takeMask, 0u));
+                    if (takes && start + rank < qEnd) newRi = (int)(start + rank);
                     break;
                 }
                 if (++queuesTried >= p.nQueues) {
@@ -689,7 +835,7 @@ void trace_kernel(TraceParams p) {
                 }
                 q = (q + 1 == p.nQueues) ? 0 : q + 1;
             }
-            if (isIdle) {
+            if (takes) {
                 const int tag = (MODE == 3 && newRi >= 0) ? (newRi | (curBatch << kFusedIndexBits)) : newRi;
                 if (kLean) riReg = tag;
                 else cold[kColdRi][lane] = __int_as_float(tag);
@@ -707,40 +853,19 @@ void trace_kernel(TraceParams p) {
                     r0 = {ld(q.ox), ld(q.oy), ld(q.oz), q.tmax ? ld(q.tmax) : __builtin_inff()};
                     r1 = {ld(q.dx), ld(q.dy), ld(q.dz), q.time ? ld(q.time) : 0.0f};
                 }
-                r.o = {r0.x, r0.y, r0.z};
-                tMax = r0.w;
-                const V3 d = {r1.x, r1.y, r1.z};
-                if (PATCH) {
-                    cold[kColdD][lane] = d.x;
-                    cold[kColdD + 1][lane] = d.y;
-                    cold[kColdD + 2][lane] = d.z;
+                if constexpr (WALK != 0) {
+                    // `while (ray.d != Vector3f(0, 0, 0))`, intersect.h:183 / aggregate.cpp:100: a zero direction makes
+                    // no Intersect call — the item is finished as the init kernel left it, the lane stays idle
+                    if (r1.x == 0.0f && r1.y == 0.0f && r1.z == 0.0f) {
+                        if (kLean) riReg = -1;
+                        else cold[kColdRi][lane] = __int_as_float(-1);
+                    } else {
+                        cold[kWalkCalls][lane] = __int_as_float(1);
+                        BVH_BEGIN_RAY(r0, r1);
+                    }
+                } else {
+                    BVH_BEGIN_RAY(r0, r1);
                 }
-                // aggregates.cpp:534-535
-                r.inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-                ray_shear(r, d);
-                if (MODE == 0 || MODE == 3) {
-                    cold[kColdHit][lane] = __int_as_float(-1);
-                    cold[kColdHit + 1][lane] = 0.0f;
-                    cold[kColdHit + 2][lane] = 0.0f;
-                    cold[kColdHit + 3][lane] = 0.0f;
-                }
-                if (INST) {
-                    cold[kHitInst][lane] = 0.0f;
-                    cold[kCurInst][lane] = 0.0f;
-                    cold[kColdTime][lane] = r1.w;  // ray.time: read by animated instances
-                    floor = -1;
-                }
-                if (!kLean && (HOSTC || p.hasHostPrims)) cold[kColdHost][lane] = 0.0f;  // candidate mode: count 0
-                visited = 1;  // the root
-                tests = 0;
-                found = false;
-                sp = base = 0;
-                float tEntry;
-                const bool rootHit =
-                    slab_partial(p.rootMin[0], p.rootMin[1], p.rootMin[2], p.rootMax[0],
-                                 p.rootMax[1], p.rootMax[2], r, tEntry) &&
-                    (tEntry < tMax);
-                cur = rootHit ? p.rootRef : kDone;
             }
             if (kLean) masks = ray_masks(r);  // some lanes carry new rays
             continue;
@@ -809,6 +934,7 @@ void trace_kernel(TraceParams p) {
         for (int k = 0; k < 16; ++k) atomicAdd(&p.stats[k], st[k]);
 #endif
 }
+#undef BVH_BEGIN_RAY
 
 // ------------------------------------------------------------------------------------
 template <int MODE, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
@@ -911,6 +1037,25 @@ hipError_t launch_trace(int mode, const TraceParams &p, int window, int instance
     case 3: return launch_fused(p, window, instanced, patches, blocks, stream, occupancy);
     default: return hipErrorInvalidValue;
     }
+}
+
+// ---- the walk calls' launchers (capi_wavefront.cpp: nnbvh_wavefront_walk_*).  They stand last in the file so
+// that the kernels above keep their places in the compiler's output ----------------------------------------------------------
+hipError_t launch_trace_walk(int kind, int form, const TraceParams &p, int blocks, hipStream_t stream, int *occupancy) {
+    if (kind == 1) {
+        switch (form) {
+        case 0: return launch_one<4, 8, 0, 0>(p, blocks, stream, occupancy);
+        case 1: return launch_one<4, 8, 0, 1>(p, blocks, stream, occupancy);
+        case 2: return launch_one<4, 8, 1, 1>(p, blocks, stream, occupancy);
+        }
+    } else if (kind == 2) {
+        switch (form) {
+        case 0: return launch_one<5, 8, 0, 0>(p, blocks, stream, occupancy);
+        case 1: return launch_one<5, 8, 0, 1>(p, blocks, stream, occupancy);
+        case 2: return launch_one<5, 8, 1, 1>(p, blocks, stream, occupancy);
+        }
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace nnbvh

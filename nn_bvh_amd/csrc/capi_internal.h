@@ -89,6 +89,9 @@ struct nnbvh_scene {
     int int_repeat = 3;
     int prim_repeat = 2;
     int max_grid_threads = 0;
+    // resident blocks per CU of the walk instances (0 = not asked yet): shadow-tr lean / general / two-level, then
+    // one-random's three
+    int walk_blocks_per_cu[6] = {0, 0, 0, 0, 0, 0};
     double build_ms[1] = {0};  // device build time of nnbvh_scene_create_gpu_build / _instanced_gpu_build
     std::mutex mu;
     std::map<hipStream_t, nnbvh::Workspace> workspaces;
@@ -179,6 +182,34 @@ struct TraceJob {
     bool hc_zeroed = false;
 };
 int launch(nnbvh_scene *s, Workspace *w, hipStream_t stream, const TraceJob &job);
+
+// One launch of a walk instance of the trace kernel (bvh_trace.hip modes 4 / 5) behind its queue
+// reset node, over the items whose first rays are the records `rays`: item i is ray i, and the batch holds
+// min(n, max(*d_n, 0)) of them (d_n nullable).  The caller has checked that the scene has walk instances
+// (walk_refusal) and holds the scene's lock.
+struct WalkJob {
+    int kind = 1;  // 1: IntersectShadowTr's walk, 2: IntersectOneRandom's
+    const ShadingMeshDevice *mesh = nullptr;
+    const void *rays = nullptr;
+    int64_t n = 0;
+    const int32_t *d_n = nullptr;
+    int max_surfaces = 1;           // Intersect calls an item may make; one that would start another is marked
+    int32_t *unfinished = nullptr;  // nullable, zero before the launch: receives the number of marked items
+    // kind 1: state[] is 0 and p_light[] set for every item (str_init)
+    const uint8_t *prim_class = nullptr;
+    long n_prim_class = 0;
+    const float4 *p_light = nullptr;
+    uint8_t *state = nullptr;
+    // kind 2: the arrays launch_kd_or_init_all (kd_trace.h) has set
+    const float *p1 = nullptr;
+    const int32_t *material = nullptr, *prim_material = nullptr;
+    long n_prim_material = 0;
+    OneRandomState st{nullptr, nullptr, nullptr};
+    void *sel_hits = nullptr, *sel_rays = nullptr;
+};
+int launch_walk(nnbvh_scene *s, Workspace *w, hipStream_t stream, const WalkJob &job);
+// why the scene has no walk instance (AnimatedPrimitive instances, alpha-tested primitives), or nullptr
+const char *walk_refusal(const nnbvh_scene *s);
 
 // ... over up to kMaxFusedBatches closest-hit / occlusion-only batches in one mode-3 launch, where batches_fusable
 int launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream, const nnbvh_batch *batches, int n_batches,

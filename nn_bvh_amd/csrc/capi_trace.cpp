@@ -99,6 +99,54 @@ int nnbvh::launch(nnbvh_scene *s, Workspace *w, hipStream_t stream, const TraceJ
     return run_trace(s, stream, job.mode, p, kMaxQueues * kQueueStrideWords, "trace kernel launch");
 }
 
+const char *nnbvh::walk_refusal(const nnbvh_scene *s) {
+    if (s->instanced && s->d_anim)
+        return "the scene holds AnimatedPrimitive instances (the INST = 2 kernels), which have no walk instances";
+    if (s->has_alpha)
+        return "the scene holds alpha-tested primitives on the device (the ALPHA kernels), which have no walk instances";
+    return nullptr;
+}
+
+int nnbvh::launch_walk(nnbvh_scene *s, Workspace *w, hipStream_t stream, const WalkJob &k) {
+    TraceParams p = scene_params(s, w);
+    p.rays = (const nnbvh_ray *)k.rays;
+    p.n = (long)k.n;
+    p.nDev = k.d_n;
+    p.wMesh = *k.mesh;
+    p.wPrimClass = k.prim_class;
+    p.wNPrimClass = k.n_prim_class;
+    p.wPLight = k.p_light;
+    p.wState = k.state;
+    p.wP1 = k.p1;
+    p.wMaterial = k.material;
+    p.wPrimMaterial = k.prim_material;
+    p.wNPrimMaterial = k.n_prim_material;
+    p.wSt = k.st;
+    p.wSelHits = (float4 *)k.sel_hits;
+    p.wSelRays = (float4 *)k.sel_rays;
+    p.wMaxSurfaces = k.max_surfaces;
+    p.wUnfinished = k.unfinished;
+    // the lean instance with the triangle-only interaction where neither the scene nor the mesh holds patches or an
+    // instance table (launch_str_step's choice of FULL) and the scene has no host-only primitives; always window 8
+    const ShadingMeshDevice &m = *k.mesh;
+    const bool lean = !s->instanced && patch_bits(s) == 0 && !s->has_host_prims && scene_fits32(s) && !m.patchVerts &&
+                      !m.instances;
+    const int form = s->instanced ? 2 : (lean ? 0 : 1);
+    int &per_cu = s->walk_blocks_per_cu[3 * (k.kind - 1) + form];
+    if (per_cu == 0) {
+        int occ = 0;
+        const hipError_t e = launch_trace_walk(k.kind, form, p, 0, nullptr, &occ);
+        per_cu = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 2;  // the spill array is sized for 8 blocks per CU
+    }
+    int blocks = s->n_cus * per_cu;
+    const int64_t need = (p.n + kBlockThreads - 1) / kBlockThreads;
+    if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
+    if (!hip_ok(launch_zero_queue(p.queue, kMaxQueues * kQueueStrideWords, stream), "queue reset launch") ||
+        !hip_ok(launch_trace_walk(k.kind, form, p, blocks, stream, nullptr), "walk kernel launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
 // The caller has checked that the scene and the batches allow it (batches_fusable).  d_n: nullable array of nullable
 // device-resident batch sizes.  soas (nullable): soas[i] is batch i's wavefront queue where its d_rays is null.
 // cands (nullable): cands[i] belongs to batches[i], capacity 0 = a plain batch.  Their count / before arrays are zeroed

@@ -1075,4 +1075,100 @@ int nnbvh_kd_wavefront_walk_one_random(nnbvh_kd_scene *s, const nnbvh_shading_me
     return NNBVH_OK;
 }
 
+// ---- the walk calls of a BVH scene: the same two loops inside ONE trace launch (bvh_trace.hip modes 4 / 5, DESIGN.md
+// §5.5.1).  Five kernel nodes whatever max_surfaces is: queue-head reset, unfinished-count reset, init, walk, record /
+// finish; no copy, memset, synchronise or event query.  The scratch is the per-stream workspace's, sized from max_rays /
+// max_items alone: after one warm-up call nothing is allocated and the call can be captured in a hipGraph.
+static bool walk_args_ok(const char *fn, const nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
+                         int64_t n_prim, int32_t max_surfaces, bool arrays) {
+    const char *what = nullptr;
+    if (!s) what = "no scene";
+    else if (!m) what = "no shading mesh";
+    else if (max_surfaces < 1 || max_surfaces > kMaxWalkSurfaces) what = "max_surfaces outside 1..65536";
+    else if (max_items < 0 || n_prim < 0) what = "negative size";
+    else if (max_items > 0 && !arrays) what = "null array";
+    else if (m->device != s->device) what = "scene and shading mesh live on different devices";
+    else what = walk_refusal(s);
+    if (what) set_error(std::string(fn) + ": " + what);
+    return !what;
+}
+
+int nnbvh_wavefront_walk_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                   const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                   const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
+                                   const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                   int64_t n_pixels, uint8_t *d_state, int32_t max_surfaces, int32_t *d_unfinished,
+                                   void *stream_) {
+    const char *fn = "wavefront_walk_shadow_tr";
+    if (!walk_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), max_surfaces,
+                      soa_ok(shadow_queue) && d_Ld && d_r_u && d_r_l && d_pixel_index && d_L))
+        return NNBVH_ERR_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_rays == 0) return NNBVH_OK;
+    const size_t n = (size_t)max_rays;
+    void *rays, *orig, *pLight, *state;
+    if (!scratch(call.w, 0, n * 32, &rays) || !scratch(call.w, 4, n * 4, &orig) ||
+        !scratch(call.w, 6, n * 16, &pLight) || !scratch(call.w, 7, n, &state))
+        return NNBVH_ERR_DEVICE;
+    const WavefrontCount cnt{max_rays, d_size};
+    // str_init: every ray's record, light point and state 0 (its item list is the identity and is not read)
+    if (!hip_ok(launch_str_init(*shadow_queue, cnt, rays, (int32_t *)orig, (float4 *)pLight, (uint8_t *)state, max_blocks,
+                                stream), "shadow-tr init launch"))
+        return NNBVH_ERR_DEVICE;
+    WalkJob walk;
+    walk.kind = 1, walk.mesh = &m->d, walk.rays = rays, walk.n = max_rays, walk.d_n = d_size;
+    walk.max_surfaces = max_surfaces, walk.unfinished = d_unfinished;
+    walk.prim_class = d_prim_class, walk.n_prim_class = (long)n_prim_class;
+    walk.p_light = (const float4 *)pLight, walk.state = (uint8_t *)state;
+    const int rc = launch_walk(s, call.w, stream, walk);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
+                                  d_state, max_blocks, stream), "shadow-tr record launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+int nnbvh_wavefront_walk_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items, const float *d_p0,
+                                    const float *d_p1, const int32_t *d_material, const int32_t *d_size,
+                                    const int32_t *d_prim_material, int64_t n_prim_material, void *d_sel_hits,
+                                    void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum, int32_t max_surfaces,
+                                    int32_t *d_unfinished, void *stream_) {
+    const char *fn = "wavefront_walk_one_random";
+    if (!walk_args_ok(fn, s, m, max_items, n_prim_material, max_surfaces,
+                      d_p0 && d_p1 && d_material && d_sel_hits && d_sel_rays && d_reservoir_pdf))
+        return NNBVH_ERR_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_items == 0) return NNBVH_OK;
+    const size_t n = (size_t)max_items;
+    void *rays, *rng, *weights;
+    if (!scratch(call.w, 0, n * 32, &rays) || !scratch(call.w, 10, n * 16, &rng) || !scratch(call.w, 11, n * 8, &weights))
+        return NNBVH_ERR_DEVICE;
+    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};  // (the base interaction stays in registers)
+    const WavefrontCount cnt{max_items, d_size};
+    // (the kd walk's init-all: nothing in it knows the tree)
+    if (!hip_ok(launch_kd_or_init_all(d_p0, d_p1, cnt, st, rays, d_sel_hits, d_sel_rays, max_blocks, stream),
+                "one-random init launch"))
+        return NNBVH_ERR_DEVICE;
+    WalkJob walk;
+    walk.kind = 2, walk.mesh = &m->d, walk.rays = rays, walk.n = max_items, walk.d_n = d_size;
+    walk.max_surfaces = max_surfaces, walk.unfinished = d_unfinished;
+    walk.p1 = d_p1, walk.material = d_material, walk.prim_material = d_prim_material;
+    walk.n_prim_material = (long)n_prim_material, walk.st = st, walk.sel_hits = d_sel_hits, walk.sel_rays = d_sel_rays;
+    const int rc = launch_walk(s, call.w, stream, walk);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
 }  // extern "C"

@@ -126,6 +126,12 @@ def _unfinished_ptr(t):
     return t.data_ptr()
 
 
+def _one_bound(method, max_passes, max_surfaces):
+    if max_passes is not None and max_surfaces is not None:
+        raise _lib.NNBVHError(f"WavefrontAggregate.{method}: max_passes (the bounded pass form) and max_surfaces (the "
+                              "walk inside one trace launch) are two forms of the call: pass one of them")
+
+
 def _queues_record(queues):
     qrec = np.zeros(1, _lib.CLOSEST_QUEUES_DTYPE)
     for name, q in queues.items():
@@ -228,7 +234,8 @@ class WavefrontAggregate:
     def _kd_only(self, method):
         if self._prefix != "nnbvh_kd_wavefront_":
             raise _lib.NNBVHError(f"WavefrontAggregate.{method} is not offered for BVH scenes (DESIGN.md §8): call "
-                                  f"Intersect{method[len('Walk'):]} with max_passes")
+                                  f"Intersect{method[len('Walk'):]} with max_surfaces (the walk inside one BVH trace "
+                                  "launch) or with max_passes")
 
     def IntersectClosest(self, max_rays, ray_queue, escaped=None, hit_area_light=None,
                          basic_eval_material=None, universal_eval_material=None, medium_sample=None,
@@ -369,7 +376,7 @@ class WavefrontAggregate:
         return hits
 
     def IntersectShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None,
-                          max_passes=None, unfinished=None):
+                          max_passes=None, unfinished=None, max_surfaces=None):
         """IntersectShadowTr (wavefront/aggregate.cpp:70-88, TraceTransmittance of wavefront/intersect.h:
         164-274) without media: shadow rays pass through interface surfaces (CLASS_INTERFACE) and are
         blocked by the first surface with a material; arriving rays add Ld * (1 / (r_u + r_l).Average())
@@ -378,8 +385,12 @@ class WavefrontAggregate:
         max_passes None: the host-driven loop (reads a count per pass; not graph-capturable).  max_passes 1..64:
         nnbvh_wavefront_intersect_shadow_tr_bounded — exactly that many passes, kernel launches only (capturable
         after one warm-up call); a ray whose walk needs more Intersect calls gets state 2 and adds nothing.
-        unfinished: optional int32 [1] device tensor, receives the number of such rays."""
+        unfinished: optional int32 [1] device tensor, receives the number of such rays.
+        max_surfaces 1..65536 (not together with max_passes): nnbvh_wavefront_walk_shadow_tr — the walk inside ONE
+        trace launch, five kernel launches whatever the bound (capturable after one warm-up call); a ray whose walk
+        would start one more Intersect call gets state 2, adds nothing and is counted in unfinished."""
         self._bvh_only("IntersectShadowTr")
+        _one_bound("IntersectShadowTr", max_passes, max_surfaces)
         _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
         soa = shadow_queue._wire()
         pc = self.prim_class
@@ -387,7 +398,10 @@ class WavefrontAggregate:
                 *_ptr_count(pc), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(),
                 L.shape[0], state.data_ptr() if state is not None else None)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if max_passes is None:
+        if max_surfaces is not None:
+            check(_lib.lib().nnbvh_wavefront_walk_shadow_tr(
+                *args, int(max_surfaces), _unfinished_ptr(unfinished), stream), "nnbvh_wavefront_walk_shadow_tr")
+        elif max_passes is None:
             assert unfinished is None, "unfinished belongs to the bounded form: pass max_passes"
             check(_lib.lib().nnbvh_wavefront_intersect_shadow_tr(*args, stream), "nnbvh_wavefront_intersect_shadow_tr")
         else:
@@ -396,7 +410,7 @@ class WavefrontAggregate:
                 "nnbvh_wavefront_intersect_shadow_tr_bounded")
 
     def IntersectOneRandom(self, max_items, p0, p1, material, shading_mesh, prim_material=None, size=None,
-                           max_passes=None, unfinished=None):
+                           max_passes=None, unfinished=None, max_surfaces=None):
         """IntersectOneRandom (wavefront/aggregate.cpp:90-116): p0, p1 float32 [n, 3], material int32 [n]
         device tensors; prim_material int32 per primitive id.  Returns (selected hit records uint8
         [n, 32], their segment rays uint8 [n, 32], reservoir pdf float32 [n], weight sum float32 [n]).
@@ -404,8 +418,11 @@ class WavefrontAggregate:
         max_passes None: the host-driven loop.  max_passes 1..64: nnbvh_wavefront_intersect_one_random_bounded —
         exactly that many passes, kernel launches only; an item whose segment needs more Intersect calls gets
         instance = -1 in its selected hit record (its pdf, weight sum and ray are then unspecified).
-        unfinished: optional int32 [1] device tensor, receives the number of such items."""
+        unfinished: optional int32 [1] device tensor, receives the number of such items.
+        max_surfaces 1..65536 (not together with max_passes): nnbvh_wavefront_walk_one_random — the walk inside ONE
+        trace launch; an item whose segment would start one more Intersect call gets instance = -1 and is counted."""
         self._bvh_only("IntersectOneRandom")
+        _one_bound("IntersectOneRandom", max_passes, max_surfaces)
         for t in (p0, p1):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 3
         assert material.dtype == torch.int32 and material.is_contiguous()
@@ -419,7 +436,10 @@ class WavefrontAggregate:
                 size.data_ptr() if size is not None else None, *_ptr_count(pm), sel_hits.data_ptr(),
                 sel_rays.data_ptr(), pdf.data_ptr(), wsum.data_ptr())
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if max_passes is None:
+        if max_surfaces is not None:
+            check(_lib.lib().nnbvh_wavefront_walk_one_random(
+                *args, int(max_surfaces), _unfinished_ptr(unfinished), stream), "nnbvh_wavefront_walk_one_random")
+        elif max_passes is None:
             assert unfinished is None, "unfinished belongs to the bounded form: pass max_passes"
             check(_lib.lib().nnbvh_wavefront_intersect_one_random(*args, stream), "nnbvh_wavefront_intersect_one_random")
         else:
