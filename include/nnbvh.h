@@ -203,7 +203,8 @@ void nnbvh_build_destroy(nnbvh_build *b);
  *   object_first[n_objects+1]  object k is prims[object_first[k], object_first[k+1]); object_first[0] == 0, the last
  *                              entry == n_prims, no object is empty
  *   prim_bounds                nullable, 6 floats per entry of prims, read for NNBVH_PRIM_HOST entries
- *   split_method               NNBVH_SPLIT_SAH (anything else is refused: the forest build is SAH only)
+ *   split_method               NNBVH_SPLIT_SAH (anything else is refused: this call is SAH only; HLBVH forests are
+ *                              nnbvh_build_forest_create_gpu_hlbvh's, below)
  * NULL + nnbvh_last_error() for every argument fault (null or empty arrays, a malformed object_first, vertex indices,
  * unknown kinds, instance entries, host-only primitives without prim_bounds, the split method: all checked on the
  * host before a device is looked at), for no usable device, and for malformed geometry, where the message is the one
@@ -224,6 +225,16 @@ int nnbvh_forest_gpu_timing(const nnbvh_forest *f, double out_ms[5]);
 int nnbvh_forest_n_levels(const nnbvh_forest *f);
 int nnbvh_forest_n_subtrees(const nnbvh_forest *f);
 void nnbvh_forest_destroy(nnbvh_forest *f);
+/* The same for HLBVH trees: tree k is byte for byte what nnbvh_build_create_gpu(..., NNBVH_SPLIT_HLBVH, ...) makes of
+ * object k alone, from a fixed number of launches and synchronisations however many objects there are.  Arguments,
+ * argument faults (the same, less the split method), the handle, its accessors and its ownership are
+ * nnbvh_build_forest_create_gpu's.  Of the accessors, timing = the phases of nnbvh_build_gpu_timing's HLBVH (upload;
+ * device sort + treelets of every object; the host's upper SAH, object after object; device emit; download),
+ * n_levels = 0 (HLBVH has no breadth-first passes) and n_subtrees = treelets in the forest (primitives of one object
+ * that share the top 12 bits of their Morton code; at most 4096 per object, no bound on the total). */
+nnbvh_forest *nnbvh_build_forest_create_gpu_hlbvh(const nnbvh_prim *prims, int n_prims, const int32_t *object_first,
+                                                  int n_objects, const float *verts, int n_verts,
+                                                  const float *prim_bounds, int max_prims_in_node, int device);
 
 /* ---- device scene ------------------------------------------------------------------ */
 /* Uploads and bakes a flattened tree (the reference's LinearBVHNode[] in its DFS layout, first child
@@ -299,9 +310,10 @@ nnbvh_scene *nnbvh_scene_create_gpu_build_with_attributes(const nnbvh_prim *prim
  * TransformedPrimitive / AnimatedPrimitive per placement) entirely on the device: every object's tree, then the
  * top-level tree, are built there, put into one numbering and baked; no tree visits the host.  The device arrays are
  * byte for byte those of nnbvh_scene_create_instanced_with_attributes on host-built trees of the same split_method
- * (nodes [top, object 0, object 1, ...], primitives [top in leaf order, object 0 in leaf order, ...]).  With
- * NNBVH_SPLIT_SAH all object trees come from one forest pass (nnbvh_build_forest_create_gpu's builder), so a scene of
- * thousands of small objects pays the builder's launches and read-backs once; NNBVH_SPLIT_HLBVH builds them one by one.
+ * (nodes [top, object 0, object 1, ...], primitives [top in leaf order, object 0 in leaf order, ...]).  All object
+ * trees come from one forest pass (the builder of nnbvh_build_forest_create_gpu for NNBVH_SPLIT_SAH, of
+ * nnbvh_build_forest_create_gpu_hlbvh for NNBVH_SPLIT_HLBVH), so a scene of thousands of small objects pays the
+ * builder's launches and read-backs once; the top-level tree is a single build.
  *   prims[n_prims]            the caller's order: [0, n_top_prims) is the top-level list (triangles, patches, the
  *                             alpha kinds, NNBVH_PRIM_HOST and NNBVH_PRIM_INSTANCE entries; for an instance entry
  *                             v[0] is the placement index and id the caller's), then the object definitions one

@@ -102,7 +102,7 @@ EXPORTS = [
     "nnbvh_kd_scene_info", "nnbvh_kd_scene_read", "nnbvh_scene_create_instanced_gpu_build", "nnbvh_scene_read",
     "nnbvh_build_forest_create_gpu", "nnbvh_forest_nodes", "nnbvh_forest_node_first", "nnbvh_forest_depths",
     "nnbvh_forest_ordered_prims", "nnbvh_forest_gpu_timing", "nnbvh_forest_n_levels", "nnbvh_forest_n_subtrees",
-    "nnbvh_forest_destroy",
+    "nnbvh_forest_destroy", "nnbvh_build_forest_create_gpu_hlbvh",
 ]
 
 
@@ -288,6 +288,8 @@ def lib():
     L.nnbvh_scene_read.argtypes = [vp, i32, vp, ctypes.c_size_t]
     L.nnbvh_build_forest_create_gpu.restype = vp
     L.nnbvh_build_forest_create_gpu.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]
+    L.nnbvh_build_forest_create_gpu_hlbvh.restype = vp
+    L.nnbvh_build_forest_create_gpu_hlbvh.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32]
     for name in ("nodes", "node_first", "depths", "ordered_prims"):
         getattr(L, "nnbvh_forest_" + name).restype = vp
         getattr(L, "nnbvh_forest_" + name).argtypes = [vp, vp]

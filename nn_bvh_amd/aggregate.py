@@ -107,16 +107,13 @@ def build_tree_gpu(prims, verts, max_prims_in_node=4, prim_bounds=None, device=0
 
 
 class BuiltForest(list):
-    """build_forest_gpu's result: a list of BuiltTree, one per object, with the pass's own figures as attributes:
-    gpu_ms (the five phases of nnbvh_forest_gpu_timing), n_levels (breadth-first passes run), n_subtrees (subtrees
-    built by one wavefront each) and node_first (where each tree starts in the forest's node array)."""
+    """build_forest_gpu's / build_hlbvh_forest_gpu's result: a list of BuiltTree, one per object, with the pass's own
+    figures as attributes: gpu_ms (the five phases of nnbvh_forest_gpu_timing), n_levels (SAH: breadth-first passes
+    run; HLBVH: 0), n_subtrees (SAH: subtrees built by one wavefront each; HLBVH: treelets in the forest) and
+    node_first (where each tree starts in the forest's node array)."""
 
 
-def build_forest_gpu(objects, verts, max_prims_in_node=4, prim_bounds=None, device=0):
-    """The SAH trees of `objects` (a list of PRIM_DTYPE arrays over ONE vertex array) built in one pass on the GPU
-    (nnbvh_build_forest_create_gpu): tree k is byte for byte build_tree(objects[k], verts, max_prims_in_node, "sah").
-    prim_bounds ([total primitives, 6] float32, the objects' rows one after another) is read for host-only primitives.
-    Returns a BuiltForest."""
+def _forest(name, objects, verts, max_prims_in_node, prim_bounds, tail):
     L = _lib.lib()
     objects = [np.ascontiguousarray(o, PRIM_DTYPE) for o in objects]
     prims = np.ascontiguousarray(np.concatenate(objects), PRIM_DTYPE) if objects else np.zeros(0, PRIM_DTYPE)
@@ -125,11 +122,10 @@ def build_forest_gpu(objects, verts, max_prims_in_node=4, prim_bounds=None, devi
     pb = None
     if prim_bounds is not None:
         pb = np.ascontiguousarray(prim_bounds, np.float32).reshape(len(prims), 6)
-    h = L.nnbvh_build_forest_create_gpu(ptr(prims), len(prims), ptr(first), len(objects), ptr(verts), len(verts),
-                                        ptr(pb) if pb is not None else None, int(max_prims_in_node),
-                                        SPLIT_METHODS["sah"], int(device))
+    h = getattr(L, name)(ptr(prims), len(prims), ptr(first), len(objects), ptr(verts), len(verts),
+                         ptr(pb) if pb is not None else None, int(max_prims_in_node), *tail)
     if not h:
-        raise NNBVHError("nnbvh_build_forest_create_gpu: " + _lib.last_error())
+        raise NNBVHError(name + ": " + _lib.last_error())
     try:
         def array(fn, dtype, extra=0):  # a copy of what an accessor points at: its count + extra elements
             n = ctypes.c_int(0)
@@ -153,6 +149,23 @@ def build_forest_gpu(objects, verts, max_prims_in_node=4, prim_bounds=None, devi
     finally:
         L.nnbvh_forest_destroy(h)
     return forest
+
+
+def build_forest_gpu(objects, verts, max_prims_in_node=4, prim_bounds=None, device=0):
+    """The SAH trees of `objects` (a list of PRIM_DTYPE arrays over ONE vertex array) built in one pass on the GPU
+    (nnbvh_build_forest_create_gpu): tree k is byte for byte build_tree(objects[k], verts, max_prims_in_node, "sah").
+    prim_bounds ([total primitives, 6] float32, the objects' rows one after another) is read for host-only primitives.
+    Returns a BuiltForest."""
+    return _forest("nnbvh_build_forest_create_gpu", objects, verts, max_prims_in_node, prim_bounds,
+                   (SPLIT_METHODS["sah"], int(device)))
+
+
+def build_hlbvh_forest_gpu(objects, verts, max_prims_in_node=4, prim_bounds=None, device=0):
+    """build_forest_gpu for HLBVH trees (nnbvh_build_forest_create_gpu_hlbvh): tree k is byte for byte
+    build_tree(objects[k], verts, max_prims_in_node, "hlbvh").  Of the BuiltForest, gpu_ms are build_tree_gpu's HLBVH
+    phases, n_levels is 0 and n_subtrees counts the treelets of the whole forest."""
+    return _forest("nnbvh_build_forest_create_gpu_hlbvh", objects, verts, max_prims_in_node, prim_bounds,
+                   (int(device),))
 
 
 class BVHAggregate:

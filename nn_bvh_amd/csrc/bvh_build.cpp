@@ -93,12 +93,14 @@ struct BuildNode {
 // node storage of one build thread
 struct Arena {
     std::vector<std::unique_ptr<BuildNode[]>> pools;
-    size_t pool_used = 0;
+    size_t pool_used = 0, pool_size = 0;
     int count = 0;
-    static constexpr size_t kPool = 1 << 14;
+    // pools double up to kPool: a small tree (one of a forest's thousands) pays for a small pool, not for 16 K nodes
+    static constexpr size_t kFirstPool = 64, kPool = 1 << 14;
     BuildNode *alloc() {
-        if (pools.empty() || pool_used == kPool) {
-            pools.emplace_back(new BuildNode[kPool]);
+        if (pool_used == pool_size) {
+            pool_size = pools.empty() ? kFirstPool : std::min(kPool, 2 * pool_size);
+            pools.emplace_back(new BuildNode[pool_size]);
             pool_used = 0;
         }
         ++count;

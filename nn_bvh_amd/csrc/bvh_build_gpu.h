@@ -109,6 +109,14 @@ struct ForestBuildResult {
 };
 bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,
                            std::string *error);
+// The same for HLBVH trees: tree k is byte for byte gpu_hlbvh_device's of object k alone, from a fixed number of launches
+// and synchronisations whatever n_objects is (one radix sort over the key (object << 30) | Morton code; the upper SAH
+// on the host, per object, over one table of every object's treelets).  Of the result, ms has the meaning of
+// gpu_hlbvh's ([1] device pipeline up to the treelet table, [2] host upper trees, [3] device emit), n_levels = 0,
+// n_subtrees = treelets in the forest, n_upper = upper nodes.  A malformed input fails with the message a loop of
+// gpu_hlbvh_device calls over the objects would have stopped at.
+bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,
+                             std::string *error);
 
 // Device-side counterpart of nnbvh_scene_create's baking (bvh_capi.cpp): the 64-B "both children"
 // records and the 16-B-slot primitive stream, straight from device-resident build output.  Triangles,

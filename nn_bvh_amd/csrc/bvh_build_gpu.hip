@@ -25,6 +25,8 @@
 //
 // Everything is integer / min / max work on 4-32 B records: HBM-bound streaming except the two
 // pointer walks (5, 9), which touch a handful of L2-resident words per node.
+// The trees of many objects come from the same ten steps run once over all their primitives, with the object's
+// number above the code in the sort key (gpu_hlbvh_forest_device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,7 +49,7 @@ constexpr int kB = 256;
 constexpr int kTreeletBit = 18;  // bits >= 18 separate treelets (mask 0x3ffc0000, aggregates.cpp:423)
 
 enum : int { kErrVertex = 1, kErrNeedBounds = 2, kErrKind = 3, kErrLeafSize = 4, kErrNonFinite = 5, kErrSahCosts = 6 };
-// The SAH builders' error words, one per kind above: errObj[kind] = the lowest-numbered object that raised it
+// The forest builders' error words (SAH, and HLBVH over many objects), one per kind above: errObj[kind] = the lowest-numbered object that raised it
 // (atomicMin; kNoObject = nobody), so a forest reports what a loop over its objects would have stopped at.
 // errObj[0] is a plain word for the "cannot happen" codes.
 constexpr int kErrWords = 8;
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(kB) void k_prim_bounds(const nnbvh_prim *__restrict
                                                     int *err, const int *__restrict__ objectFirst,
                                                     int nObjects, int *errObj) {
     __shared__ float red[6][kB / 64];
-    // err (HLBVH): one word, the last writer's kind.  errObj (SAH, with objectFirst[nObjects + 1]): see kErrWords
+    // err (one HLBVH tree): one word, the last writer's kind.  errObj (SAH and the HLBVH forest, with objectFirst[nObjects + 1]): see kErrWords
     auto report = [&](int kind, int i) {
         if (!errObj) {
             *err = kind;
@@ -213,16 +215,19 @@ __global__ __launch_bounds__(kB) void k_morton(const Box6 *__restrict__ pb,
 }
 
 // ---- 4: runs of identical codes -------------------------------------------------------------------
-__global__ __launch_bounds__(kB) void k_heads(const unsigned *__restrict__ codes, int n,
-                                              int *__restrict__ head) {
+// Key: unsigned (one tree: the 30-bit code) or unsigned long long (a forest: (object << 30) | code, so a run of
+// identical codes ends at an object boundary and every object is one subtree of the radix tree below)
+template <typename Key>
+__global__ __launch_bounds__(kB) void k_heads(const Key *__restrict__ codes, int n, int *__restrict__ head) {
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB)
         head[i] = (i == 0 || codes[i] != codes[i - 1]) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(kB) void k_compact(const unsigned *__restrict__ codes,
+template <typename Key>
+__global__ __launch_bounds__(kB) void k_compact(const Key *__restrict__ codes,
                                                 const int *__restrict__ head,
                                                 const int *__restrict__ excl, int n,
-                                                int *__restrict__ pstart, unsigned *__restrict__ ucode,
+                                                int *__restrict__ pstart, Key *__restrict__ ucode,
                                                 int *mOut) {
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) {
         if (head[i]) {
@@ -240,15 +245,21 @@ __global__ __launch_bounds__(kB) void k_compact(const unsigned *__restrict__ cod
 // ---- 5: binary radix tree over the m distinct codes.  Internal node i in [0, m-1); node index
 // space "v": internal nodes 0..m-2, atom a -> (m-1)+a.  Split position == the reference's
 // FindInterval result (first element whose bit differs from the range's first, :478-482). --------
-__global__ __launch_bounds__(kB) void k_karras(const unsigned *__restrict__ ucode, int m,
+// A forest's keys split on bits >= 30 above its objects (bit[] then holds 30 .. 60: outside every treelet, like the
+// bits 18 .. 29 between an object's treelets); below an object's root the tree is the one its codes alone give.
+__device__ __forceinline__ int key_clz(unsigned x) { return __clz((int)x); }
+__device__ __forceinline__ int key_clz(unsigned long long x) { return __clzll((long long)x); }
+
+template <typename Key>
+__global__ __launch_bounds__(kB) void k_karras(const Key *__restrict__ ucode, int m,
                                                int *__restrict__ firstA, int *__restrict__ lastA,
                                                int *__restrict__ leftV, int *__restrict__ rightV,
                                                unsigned char *__restrict__ bit,
                                                int *__restrict__ parentV) {
     const int i = blockIdx.x * kB + threadIdx.x;
     if (i >= m - 1) return;
-    const unsigned ci = ucode[i];
-    auto delta = [&](int j) -> int { return (j < 0 || j >= m) ? -1 : __clz((int)(ci ^ ucode[j])); };
+    const Key ci = ucode[i];
+    auto delta = [&](int j) -> int { return (j < 0 || j >= m) ? -1 : key_clz((Key)(ci ^ ucode[j])); };
     const int d = (delta(i + 1) - delta(i - 1)) > 0 ? 1 : -1;
     const int dmin = delta(i - d);
     int lmax = 2;
@@ -271,7 +282,7 @@ __global__ __launch_bounds__(kB) void k_karras(const unsigned *__restrict__ ucod
     lastA[i] = hi;
     leftV[i] = lv;
     rightV[i] = rv;
-    bit[i] = (unsigned char)(31 - dnode);
+    bit[i] = (unsigned char)((int)(8 * sizeof(Key)) - 1 - dnode);
     parentV[lv] = i;
     parentV[rv] = i;
     if (i == 0) parentV[0] = -1;
@@ -468,6 +479,176 @@ __global__ __launch_bounds__(kB) void k_gather_prims(const nnbvh_prim *__restric
                                                      nnbvh_prim *__restrict__ ordered) {
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB)
         ordered[i] = prims[idxSorted[i]];
+}
+
+// ---- the forest form (gpu_hlbvh_forest_device): what differs per object ------------------------------------------------
+// Steps 1, 7 and 10 are the kernels above as they stand; 4 and 5 are their 64-bit instances; the ones below replace
+// k_morton, k_classify, k_treelets and k_emit.  Nothing in them looks outside the object a primitive belongs to.
+
+// Centroid bounds of every object (order-free min / max of the same centroids k_prim_bounds folds for one tree), and
+// the object of every primitive for the kernels after this one.  A wavefront that lies inside one object (every
+// wavefront of a big object, bar two) folds first and sends six atomics instead of 384.
+__global__ __launch_bounds__(kB) void k_object_cbounds(const Box6 *__restrict__ pb, const int *__restrict__ objectFirst,
+                                                       int nObjects, int n, int *__restrict__ objOf, unsigned *cbObj) {
+    const int i = blockIdx.x * kB + threadIdx.x;
+    const bool live = i < n;
+    int obj = -1;
+    float cmin[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f};
+    float cmax[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
+    if (live) {
+        int lo = 0, hi = nObjects - 1;  // the last k with objectFirst[k] <= i
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (objectFirst[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        obj = lo;
+        objOf[i] = obj;
+        const Box6 b = pb[i];
+        for (int k = 0; k < 3; ++k) cmin[k] = cmax[k] = .5f * b.mn[k] + .5f * b.mx[k];  // BVHPrimitive::Centroid()
+    }
+    const int obj0 = __shfl(obj, 0);
+    if (obj0 < 0) return;  // lane 0 holds the wavefront's lowest index: nobody is live
+    if (__all(!live || obj == obj0)) {
+        for (int k = 0; k < 3; ++k)
+            for (int off = 32; off >= 1; off >>= 1) {
+                cmin[k] = fminf(cmin[k], __shfl_xor(cmin[k], off));
+                cmax[k] = fmaxf(cmax[k], __shfl_xor(cmax[k], off));
+            }
+        if ((threadIdx.x & 63) != 0) return;
+    } else if (!live) {
+        return;
+    }
+    for (int k = 0; k < 3; ++k) {
+        atomicMin(&cbObj[6 * (size_t)obj + k], f2key(cmin[k]));
+        atomicMax(&cbObj[6 * (size_t)obj + 3 + k], f2key(cmax[k]));
+    }
+}
+
+__global__ __launch_bounds__(kB) void k_cbounds_init(int nObjects, unsigned *__restrict__ cbObj) {
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (i < 6 * nObjects) cbObj[i] = (i % 6) < 3 ? 0xffffffffu : 0u;  // min keys all-ones, max keys 0
+}
+
+// k_morton against the object's own centroid bounds (the mx > mn guard per object and per axis), the object number
+// above the 30 code bits
+__global__ __launch_bounds__(kB) void k_morton_forest(const Box6 *__restrict__ pb, const unsigned *__restrict__ cbObj,
+                                                      const int *__restrict__ objOf, int n,
+                                                      unsigned long long *__restrict__ keys, int *__restrict__ idx) {
+    for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) {
+        const Box6 b = pb[i];
+        const int obj = objOf[i];
+        const unsigned *cb = cbObj + 6 * (size_t)obj;
+        unsigned q[3];
+        for (int k = 0; k < 3; ++k) {
+            const float mn = key2f(cb[k]), mx = key2f(cb[3 + k]);
+            const float c = .5f * b.mn[k] + .5f * b.mx[k];
+            float o = c - mn;
+            if (mx > mn) o /= mx - mn;
+            q[k] = (unsigned)(o * 1024.0f);  // mortonScale = 1 << 10
+        }
+        const unsigned code = (left_shift3(q[2]) << 2) | (left_shift3(q[1]) << 1) | left_shift3(q[0]);
+        keys[i] = ((unsigned long long)obj << 30) | code;
+        idx[i] = i;
+    }
+}
+
+// k_classify, reporting an oversized leaf with its object (errObj[kErrLeafSize], lowest object wins)
+__global__ __launch_bounds__(kB) void k_classify_forest(int m, int maxPrims, const int *__restrict__ pstart,
+                                                        const int *__restrict__ firstA, const int *__restrict__ lastA,
+                                                        const unsigned char *__restrict__ bit,
+                                                        const int *__restrict__ parentV,
+                                                        const unsigned long long *__restrict__ ukey,
+                                                        unsigned char *__restrict__ kind, int *__restrict__ leafHead,
+                                                        int *__restrict__ treeletHead, int *errObj) {
+    const int v = blockIdx.x * kB + threadIdx.x;
+    if (v >= 2 * m - 1) return;
+    const bool internal = v < m - 1;
+    const int first = internal ? firstA[v] : v - (m - 1);
+    const int last = internal ? lastA[v] : first;
+    const int n = pstart[last + 1] - pstart[first];
+    const int p = parentV[v];
+    const bool inTreelet = !internal || bit[v] < kTreeletBit;
+    const bool parentInTreelet = p >= 0 && bit[p] < kTreeletBit;
+    const bool treeletRoot = inTreelet && !parentInTreelet;
+    const bool realInterior = internal && inTreelet && n >= maxPrims;
+    bool parentInterior = false;
+    if (parentInTreelet) parentInterior = pstart[lastA[p] + 1] - pstart[firstA[p]] >= maxPrims;
+    const bool realLeaf = inTreelet && !realInterior && (treeletRoot || parentInterior);
+    kind[v] = (realInterior ? kRealInterior : 0) | (realLeaf ? kRealLeaf : 0) | (treeletRoot ? kTreeletRoot : 0);
+    if (realLeaf) {
+        leafHead[first] = 1;
+        if (n > 65535) atomicMin(&errObj[kErrLeafSize], (int)(ukey[first] >> 30));
+    }
+    if (treeletRoot) treeletHead[first] = 1;
+}
+
+// k_treelets with the treelet's object: the forest's treelets are numbered object after object, Morton order inside
+__global__ __launch_bounds__(kB) void k_treelets_forest(int m, const unsigned char *__restrict__ kind,
+                                                        const int *__restrict__ firstA, const int *__restrict__ lastA,
+                                                        const int *__restrict__ leafOrd, const int *__restrict__ treeOrd,
+                                                        const Box6 *__restrict__ nodeBox,
+                                                        const unsigned long long *__restrict__ ukey, int tCap,
+                                                        Box6 *__restrict__ tbox, int *__restrict__ tsize,
+                                                        int *__restrict__ tobj) {
+    const int v = blockIdx.x * kB + threadIdx.x;
+    if (v >= 2 * m - 1 || !(kind[v] & kTreeletRoot)) return;
+    const int first = v < m - 1 ? firstA[v] : v - (m - 1);
+    const int t = treeOrd[first];
+    if (t >= tCap) return;  // cannot happen: at most min(m, 4096 per object) treelets
+    tbox[t] = nodeBox[v];
+    tsize[t] = subtree_size(v, m, kind, firstA, lastA, leafOrd);
+    tobj[t] = (int)(ukey[first] >> 30);
+}
+
+// k_emit for trees laid out one after another: tbase[t] already includes the tree's node_first; a second child
+// counts from its own tree's root, a leaf's first primitive from its object's first primitive, the depth is the
+// object's own maximum
+__global__ __launch_bounds__(kB) void k_emit_forest(int m, const unsigned char *__restrict__ kind,
+                                                    const unsigned char *__restrict__ bit,
+                                                    const int *__restrict__ pstart, const int *__restrict__ firstA,
+                                                    const int *__restrict__ lastA, const int *__restrict__ leftV,
+                                                    const int *__restrict__ parentV, const int *__restrict__ leafOrd,
+                                                    const int *__restrict__ treeOrd, const int *__restrict__ tbase,
+                                                    const int *__restrict__ tdepth, const int *__restrict__ tobj,
+                                                    const int *__restrict__ nodeFirst,
+                                                    const int *__restrict__ objectFirst, const Box6 *__restrict__ nodeBox,
+                                                    nnbvh_linear_node *__restrict__ nodes, int *depthObj) {
+    const int v = blockIdx.x * kB + threadIdx.x;
+    if (v >= 2 * m - 1 || !(kind[v] & (kRealInterior | kRealLeaf))) return;
+    const bool internal = v < m - 1;
+    const int first = internal ? firstA[v] : v - (m - 1);
+    const int last = internal ? lastA[v] : first;
+    int cur = v, leftTurns = 0, depth = 0;
+    while (!(kind[cur] & kTreeletRoot)) {
+        const int p = parentV[cur];
+        leftTurns += (leftV[p] == cur) ? 1 : 0;
+        ++depth;
+        cur = p;
+    }
+    const int rootFirst = cur < m - 1 ? firstA[cur] : cur - (m - 1);
+    const int t = treeOrd[rootFirst];
+    const int obj = tobj[t];
+    const int flat = tbase[t] + 2 * (leafOrd[first] - leafOrd[rootFirst]) + leftTurns;
+    const Box6 b = nodeBox[v];
+    nnbvh_linear_node out;
+    for (int k = 0; k < 3; ++k) {
+        out.pmin[k] = b.mn[k];
+        out.pmax[k] = b.mx[k];
+    }
+    out.pad = 0;
+    if (kind[v] & kRealLeaf) {
+        out.offset = pstart[first] - objectFirst[obj];
+        out.nprims = (uint16_t)(pstart[last + 1] - pstart[first]);
+        out.axis = 0;
+        const int d = tdepth[t] + depth;
+        if (depthObj[obj] < d) atomicMax(&depthObj[obj], d);  // (the plain read spares most leaves the atomic)
+    } else {
+        out.offset = flat + 1 + subtree_size(leftV[v], m, kind, firstA, lastA, leafOrd) - nodeFirst[obj];
+        out.nprims = 0;
+        out.axis = (uint8_t)(bit[v] % 3);  // :499
+    }
+    nodes[flat] = out;
 }
 
 __global__ __launch_bounds__(kB) void k_iota(int n, int *__restrict__ perm) {
@@ -669,9 +850,9 @@ bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::stri
     if (!mem.ok) return false;
     GB_CHECK(rocprim::radix_sort_pairs(dTmp, tmpBytes, dCodes, dCodesS, dIdx, dIdxS, (size_t)n, 0u, 30u, stream),
              "radix sort");
-    hipLaunchKernelGGL(k_heads, dim3(grid_for(n)), dim3(kB), 0, stream, dCodesS, n, dHead);
+    hipLaunchKernelGGL(k_heads<unsigned>, dim3(grid_for(n)), dim3(kB), 0, stream, dCodesS, n, dHead);
     GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dHead, dExcl, 0, (size_t)n, rocprim::plus<int>(), stream), "scan");
-    hipLaunchKernelGGL(k_compact, dim3(grid_for(n)), dim3(kB), 0, stream, dCodesS, dHead, dExcl, n, dPstart, dUcode, dM);
+    hipLaunchKernelGGL(k_compact<unsigned>, dim3(grid_for(n)), dim3(kB), 0, stream, dCodesS, dHead, dExcl, n, dPstart, dUcode, dM);
     int scal[16];
     GB_CHECK(hipMemcpyAsync(scal, dScalars, sizeof scal, hipMemcpyDeviceToHost, stream), "read scalars");
     GB_CHECK(hipStreamSynchronize(stream), "sync after sort");
@@ -699,7 +880,7 @@ bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::stri
     GB_CHECK(hipMemsetAsync(dLeafHead, 0, ((size_t)m + 1) * sizeof(int), stream), "memset");
     GB_CHECK(hipMemsetAsync(dTreeHead, 0, ((size_t)m + 1) * sizeof(int), stream), "memset");
     if (m > 1)
-        hipLaunchKernelGGL(k_karras, dim3(grid_all(m - 1)), dim3(kB), 0, stream, dUcode, m, dFirst, dLast, dLeft,
+        hipLaunchKernelGGL(k_karras<unsigned>, dim3(grid_all(m - 1)), dim3(kB), 0, stream, dUcode, m, dFirst, dLast, dLeft,
                            dRight, dBit, dParent);
     hipLaunchKernelGGL(k_classify, dim3(grid_all(nv)), dim3(kB), 0, stream, m, maxPrims, dPstart, dFirst, dLast, dBit,
                        dParent, dKind, dLeafHead, dTreeHead, dErr);
@@ -786,6 +967,248 @@ bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::stri
     out->d_ordered = dOrdered;
     outMem.release(dNodes);
     outMem.release(dOrdered);
+    return true;
+}
+
+namespace {
+
+// What a loop of one-object builds would have reported: the failure of the lowest-numbered object, and within one
+// object the first in the order of the phases.  The forest builders call it in that order, so a tie keeps the earlier.
+struct Refusal {
+    int object = kNoObject;
+    std::string text;
+    void operator()(int o, const std::string &t) {
+        if (o < object) {
+            object = o;
+            text = t;
+        }
+    }
+};
+
+bool check_object_first(const int *objectFirst, int nObjects, int nAll, std::string *error) {
+    if (!objectFirst || nObjects < 1 || objectFirst[0] != 0 || objectFirst[nObjects] != nAll) {
+        *error = "gpu build: malformed object_first (it starts at 0 and ends at n_prims)";
+        return false;
+    }
+    for (int k = 0; k < nObjects; ++k)
+        if (objectFirst[k + 1] <= objectFirst[k]) {
+            *error = "gpu build: malformed object_first (an object is empty or the entries decrease)";
+            return false;
+        }
+    return true;
+}
+
+}  // namespace
+
+// The HLBVH trees of many objects in one pass: the pipeline of gpu_hlbvh_device over the sort key (object << 30) | code.
+// ONE stable radix sort over the bits in use orders every object's primitives by their 30 code bits without moving one
+// across an object boundary; a run of identical keys, a treelet (equal bits >= 18) and a radix-tree range all end
+// where the object does, because the object number is part of the key; the objects themselves hang off radix nodes that
+// split on bits >= 30, which are no more part of a tree than the nodes that split on bits 18 .. 29.  So every step is
+// one launch for the whole forest, and the upper SAH runs on the host per object over one table of treelets.
+// A malformed object's primitives run through the pipeline like any others (no kernel indexes with a coordinate); only
+// its messages count, and only if no lower-numbered object has one.
+bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst, int nObjects, ForestBuildResult *out,
+                             std::string *error) {
+    const int n = in.n_prims, n_verts = in.n_verts;
+    if (!check_object_first(objectFirst, nObjects, n, error)) return false;
+    const nnbvh_prim *dPrims = in.d_prims;
+    const float *dVerts = in.d_verts, *dCaller = in.d_prim_bounds;
+    const int maxPrims = std::min(255, in.max_prims_in_node);  // aggregates.cpp:142
+    hipStream_t stream = (hipStream_t)in.stream;
+    DevMem mem, outMem;  // outMem: the result arrays this call allocates itself
+    mem.error = outMem.error = error;
+    mem.pool = in.pool;
+    Refusal refuse;
+    typedef unsigned long long Key;
+    int objectBits = 0;
+    while (objectBits < 31 && ((long)nObjects - 1) >> objectBits) ++objectBits;
+    const unsigned endBit = 30u + (unsigned)objectBits;
+
+    auto t0 = std::chrono::steady_clock::now();
+    Box6 *dPb = mem.get<Box6>(n);
+    Key *dKeys = mem.get<Key>(n), *dKeysS = mem.get<Key>(n), *dUkey = mem.get<Key>(n);
+    int *dIdx = mem.get<int>(n), *dIdxS = mem.get<int>(n), *dObjOf = mem.get<int>(n);
+    int *dHead = mem.get<int>(n), *dExcl = mem.get<int>(n);
+    int *dPstart = mem.get<int>((size_t)n + 1);
+    int *dObjectFirst = mem.get<int>((size_t)nObjects + 1);
+    unsigned *dCbObj = mem.get<unsigned>(6 * (size_t)nObjects);
+    int *dDepthObj = mem.get<int>(nObjects);
+    int *dScalars = mem.get<int>(8 + kErrWords);  // [0..5] k_prim_bounds' whole-forest centroid keys (unused), 7 m, [8..] errObj
+    if (!mem.ok) return false;
+    int init[8 + kErrWords] = {-1, -1, -1, 0, 0, 0, 0, 0};
+    for (int k = 1; k < kErrWords; ++k) init[8 + k] = kNoObject;
+    GB_CHECK(hipMemcpyAsync(dScalars, init, sizeof init, hipMemcpyHostToDevice, stream), "init scalars");
+    GB_CHECK(hipMemcpyAsync(dObjectFirst, objectFirst, ((size_t)nObjects + 1) * sizeof(int), hipMemcpyHostToDevice, stream),
+             "copy object_first");
+    GB_CHECK(hipMemsetAsync(dDepthObj, 0, (size_t)nObjects * sizeof(int), stream), "memset depths");
+    int *dM = dScalars + 7, *dErrObj = dScalars + 8;
+    hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(n, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts, dCaller, n, dPb,
+                       (unsigned *)dScalars, (int *)nullptr, (const int *)dObjectFirst, nObjects, dErrObj);
+    hipLaunchKernelGGL(k_cbounds_init, dim3(grid_all(6L * nObjects)), dim3(kB), 0, stream, nObjects, dCbObj);
+    hipLaunchKernelGGL(k_object_cbounds, dim3(grid_all(n)), dim3(kB), 0, stream, dPb, dObjectFirst, nObjects, n, dObjOf,
+                       dCbObj);
+    hipLaunchKernelGGL(k_morton_forest, dim3(grid_for(n)), dim3(kB), 0, stream, dPb, dCbObj, dObjOf, n, dKeys, dIdx);
+    size_t tmpBytes = 0, scanBytes = 0;
+    GB_CHECK(rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dKeysS, dIdx, dIdxS, (size_t)n, 0u, endBit, stream),
+             "radix sort (size query)");
+    GB_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, dHead, dExcl, 0, (size_t)n + 1, rocprim::plus<int>(), stream),
+             "scan (size query)");
+    void *dTmp = mem.get<char>(std::max(tmpBytes, scanBytes));
+    if (!mem.ok) return false;
+    GB_CHECK(rocprim::radix_sort_pairs(dTmp, tmpBytes, dKeys, dKeysS, dIdx, dIdxS, (size_t)n, 0u, endBit, stream), "radix sort");
+    hipLaunchKernelGGL(k_heads<Key>, dim3(grid_for(n)), dim3(kB), 0, stream, dKeysS, n, dHead);
+    GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dHead, dExcl, 0, (size_t)n, rocprim::plus<int>(), stream), "scan");
+    hipLaunchKernelGGL(k_compact<Key>, dim3(grid_for(n)), dim3(kB), 0, stream, dKeysS, dHead, dExcl, n, dPstart, dUkey, dM);
+    int scal[8 + kErrWords];
+    GB_CHECK(hipMemcpyAsync(scal, dScalars, sizeof scal, hipMemcpyDeviceToHost, stream), "read scalars");
+    GB_CHECK(hipStreamSynchronize(stream), "sync after sort");
+    const int *errWords = scal + 8;
+    refuse(errWords[kErrVertex], "nnbvh_build_create: vertex index out of range");
+    refuse(errWords[kErrNeedBounds], "nnbvh_build_create: instance / host primitives need prim_bounds");
+    refuse(errWords[kErrNonFinite], "nnbvh_build_create: non-finite vertex or primitive bounds");
+    refuse(errWords[kErrKind], "nnbvh_build_create: unknown primitive kind");
+    if (refuse.object == 0) {  // no lower-numbered object is left to change the message
+        *error = refuse.text;
+        return false;
+    }
+    const int m = scal[7];
+    if (m < nObjects || m > n) {
+        *error = "gpu build: internal error (distinct code count)";
+        return false;
+    }
+    const int nv = 2 * m - 1;
+    const int tCap = (int)std::min<long>(m, 4096L * nObjects);  // an object has at most 4096 treelets, and no more than codes
+
+    int *dFirst = mem.get<int>(m), *dLast = mem.get<int>(m), *dLeft = mem.get<int>(m), *dRight = mem.get<int>(m);
+    unsigned char *dBit = mem.get<unsigned char>(m), *dKind = mem.get<unsigned char>(nv);
+    int *dParent = mem.get<int>(nv);
+    int *dLeafHead = mem.get<int>((size_t)m + 1), *dTreeHead = mem.get<int>((size_t)m + 1);
+    int *dLeafOrd = mem.get<int>((size_t)m + 1), *dTreeOrd = mem.get<int>((size_t)m + 1);
+    Box6 *dNodeBox = mem.get<Box6>(nv);
+    Box6 *dTbox = mem.get<Box6>(tCap);
+    int *dTsize = mem.get<int>(tCap), *dTobj = mem.get<int>(tCap);
+    if (!mem.ok) return false;
+    GB_CHECK(hipMemsetAsync(dParent, 0xff, (size_t)nv * sizeof(int), stream), "memset parents");  // -1: the root
+    GB_CHECK(hipMemsetAsync(dLeafHead, 0, ((size_t)m + 1) * sizeof(int), stream), "memset");
+    GB_CHECK(hipMemsetAsync(dTreeHead, 0, ((size_t)m + 1) * sizeof(int), stream), "memset");
+    if (m > 1)
+        hipLaunchKernelGGL(k_karras<Key>, dim3(grid_all(m - 1)), dim3(kB), 0, stream, dUkey, m, dFirst, dLast, dLeft, dRight,
+                           dBit, dParent);
+    hipLaunchKernelGGL(k_classify_forest, dim3(grid_all(nv)), dim3(kB), 0, stream, m, maxPrims, dPstart, dFirst, dLast, dBit,
+                       dParent, dUkey, dKind, dLeafHead, dTreeHead, dErrObj);
+    GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dLeafHead, dLeafOrd, 0, (size_t)m + 1, rocprim::plus<int>(), stream),
+             "scan leaves");
+    GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dTreeHead, dTreeOrd, 0, (size_t)m + 1, rocprim::plus<int>(), stream),
+             "scan treelets");
+    hipLaunchKernelGGL(k_leaf_bounds, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dPstart, dFirst, dLast, dIdxS, dPb,
+                       dNodeBox);
+    hipLaunchKernelGGL(k_big_leaf_bounds, dim3((nv + kB / 64 - 1) / (kB / 64)), dim3(kB), 0, stream, m, dKind, dPstart,
+                       dFirst, dLast, dIdxS, dPb, dNodeBox);
+    if (m > 1)
+        for (int level = 0; level < kTreeletBit; ++level)
+            hipLaunchKernelGGL(k_interior_bounds, dim3(grid_all(m - 1)), dim3(kB), 0, stream, m, level, dKind, dBit, dLeft,
+                               dRight, dNodeBox);
+    hipLaunchKernelGGL(k_treelets_forest, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dFirst, dLast, dLeafOrd,
+                       dTreeOrd, dNodeBox, dUkey, tCap, dTbox, dTsize, dTobj);
+    int nTreelets = 0, leafSizeObject = kNoObject;
+    GB_CHECK(hipMemcpyAsync(&nTreelets, dTreeOrd + m, sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet count");
+    GB_CHECK(hipMemcpyAsync(&leafSizeObject, dErrObj + kErrLeafSize, sizeof(int), hipMemcpyDeviceToHost, stream), "read error word");
+    GB_CHECK(hipStreamSynchronize(stream), "sync after classify");
+    refuse(leafSizeObject, "nnbvh_build_create: more than 65535 primitives share one Morton code (leaf too large)");
+    if (nTreelets < nObjects || nTreelets > tCap) {
+        *error = "gpu build: internal error (treelet count)";
+        return false;
+    }
+    // one read-back: every object's treelet boxes and sizes
+    std::vector<float> tbox(6 * (size_t)nTreelets);
+    std::vector<int> tsize(nTreelets), tobj(nTreelets);
+    GB_CHECK(hipMemcpyAsync(tbox.data(), dTbox, tbox.size() * sizeof(float), hipMemcpyDeviceToHost, stream), "read treelet bounds");
+    GB_CHECK(hipMemcpyAsync(tsize.data(), dTsize, tsize.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet sizes");
+    GB_CHECK(hipMemcpyAsync(tobj.data(), dTobj, tobj.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet objects");
+    GB_CHECK(hipStreamSynchronize(stream), "sync after treelets");
+    out->ms[1] = ms_since(t0);
+
+    // ---- the upper SAH, per object over its own treelets in Morton order; the trees one after another ----------------
+    t0 = std::chrono::steady_clock::now();
+    // table = [treelet bases | treelet depths | node_first | flat indices of the upper nodes]: one upload
+    std::vector<int> table(2 * (size_t)nTreelets + (size_t)nObjects + 1, 0);
+    int *tbase = table.data(), *tdepth = tbase + nTreelets;
+    std::vector<int> upperIndex;
+    std::vector<nnbvh_linear_node> upperNodes;
+    out->node_first.assign((size_t)nObjects + 1, 0);
+    for (int k = 0, t = 0; k < nObjects && k < refuse.object; ++k) {
+        const int tFirst = t;
+        while (t < nTreelets && tobj[(size_t)t] == k) ++t;
+        const int count = t - tFirst;
+        if (count < 1 || count > 4096) {
+            *error = "gpu build: internal error (treelet count)";
+            return false;
+        }
+        for (int i = tFirst; i < t && k < refuse.object; ++i) {
+            bool fine = tsize[(size_t)i] >= 1 && (tsize[(size_t)i] & 1);
+            for (int c = 0; c < 6; ++c) fine = fine && std::isfinite(tbox[6 * (size_t)i + c]);
+            if (!fine)
+                refuse(k, "nnbvh_build_create: non-finite primitive bounds (or internal error) in treelet " + std::to_string(i - tFirst));
+        }
+        UpperLayout up;
+        std::string text;
+        if (k < refuse.object && !hlbvh_upper_layout(tbox.data() + 6 * (size_t)tFirst, tsize.data() + tFirst, count, &up, &text))
+            refuse(k, text);
+        if (k >= refuse.object) break;  // (no later object changes the message)
+        const long root = out->node_first[(size_t)k];
+        if (root + up.total_nodes >= 0x7fffffffL) {
+            *error = "gpu build: too many nodes";
+            return false;
+        }
+        for (int i = 0; i < count; ++i) {
+            tbase[tFirst + i] = (int)root + up.base[(size_t)i];
+            tdepth[tFirst + i] = up.depth[(size_t)i];
+        }
+        for (size_t i = 0; i < up.upper_index.size(); ++i) upperIndex.push_back((int)root + up.upper_index[i]);
+        upperNodes.insert(upperNodes.end(), up.upper_nodes.begin(), up.upper_nodes.end());  // offsets count from the tree's root
+        out->node_first[(size_t)k + 1] = (int)root + up.total_nodes;
+    }
+    if (refuse.object != kNoObject) {
+        *error = refuse.text;
+        return false;
+    }
+    const int totalNodes = out->node_first[(size_t)nObjects];
+    const size_t nUpper = upperIndex.size();
+    std::copy(out->node_first.begin(), out->node_first.end(), table.begin() + 2 * (size_t)nTreelets);
+    table.insert(table.end(), upperIndex.begin(), upperIndex.end());
+    out->ms[2] = ms_since(t0);
+
+    t0 = std::chrono::steady_clock::now();
+    nnbvh_linear_node *dNodes = in.d_nodes_out ? in.d_nodes_out : outMem.get<nnbvh_linear_node>((size_t)totalNodes);
+    nnbvh_prim *dOrdered = in.d_ordered_out ? in.d_ordered_out : outMem.get<nnbvh_prim>(n);
+    int *dTable = mem.get<int>(table.size());
+    nnbvh_linear_node *dUn = mem.get<nnbvh_linear_node>(nUpper);
+    if (!mem.ok || !outMem.ok) return false;
+    const int *dTbase = dTable, *dTdepth = dTable + nTreelets, *dNodeFirst = dTable + 2 * (size_t)nTreelets;
+    const int *dUi = dNodeFirst + nObjects + 1;
+    GB_CHECK(hipMemcpyAsync(dTable, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, stream), "copy layout");
+    hipLaunchKernelGGL(k_emit_forest, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dBit, dPstart, dFirst, dLast, dLeft,
+                       dParent, dLeafOrd, dTreeOrd, dTbase, dTdepth, dTobj, dNodeFirst, dObjectFirst, dNodeBox, dNodes,
+                       dDepthObj);
+    hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kB), 0, stream, dPrims, dIdxS, n, dOrdered);
+    if (nUpper) {  // the upper nodes join the device array
+        GB_CHECK(hipMemcpyAsync(dUn, upperNodes.data(), nUpper * sizeof(nnbvh_linear_node), hipMemcpyHostToDevice, stream), "copy upper");
+        hipLaunchKernelGGL(k_scatter_nodes, dim3(grid_all((long)nUpper)), dim3(kB), 0, stream, dUi, dUn, (int)nUpper, dNodes);
+    }
+    out->depth.assign((size_t)nObjects, 0);
+    GB_CHECK(hipMemcpyAsync(out->depth.data(), dDepthObj, (size_t)nObjects * sizeof(int), hipMemcpyDeviceToHost, stream), "read depths");
+    GB_CHECK(hipGetLastError(), "kernel launch");
+    GB_CHECK(hipStreamSynchronize(stream), "sync after emit");
+    out->ms[3] = ms_since(t0);
+    out->total_nodes = totalNodes;
+    out->d_nodes = dNodes;
+    out->d_ordered = dOrdered;
+    outMem.release(dNodes);
+    outMem.release(dOrdered);
+    out->n_levels = 0;
+    out->n_subtrees = nTreelets;
+    out->n_upper = (int)nUpper;
     return true;
 }
 
@@ -1550,15 +1973,7 @@ bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string
 bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *objectFirst, int nObjects, ForestBuildResult *out,
                            std::string *error) {
     const int nAll = in.n_prims, n_verts = in.n_verts;
-    if (!objectFirst || nObjects < 1 || objectFirst[0] != 0 || objectFirst[nObjects] != nAll) {
-        *error = "gpu build: malformed object_first (it starts at 0 and ends at n_prims)";
-        return false;
-    }
-    for (int k = 0; k < nObjects; ++k)
-        if (objectFirst[k + 1] <= objectFirst[k]) {
-            *error = "gpu build: malformed object_first (an object is empty or the entries decrease)";
-            return false;
-        }
+    if (!check_object_first(objectFirst, nObjects, nAll, error)) return false;
     const nnbvh_prim *dPrims = in.d_prims;
     const float *dVerts = in.d_verts, *dCaller = in.d_prim_bounds;
     const int maxPrims = std::min(255, in.max_prims_in_node);
@@ -1569,16 +1984,7 @@ bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *objectFirst, i
     mem.error = outMem.error = error;
     mem.pool = in.pool;
 
-    // What a loop of one-object builds would have reported: the failure of the lowest-numbered object, and within
-    // one object the first in the order of the phases.  refuse() is called in that order, so a tie keeps the earlier.
-    int refusedObject = kNoObject;
-    std::string refusal;
-    auto refuse = [&](int object, const std::string &text) {
-        if (object < refusedObject) {
-            refusedObject = object;
-            refusal = text;
-        }
-    };
+    Refusal refuse;
 
     auto t0 = std::chrono::steady_clock::now();
     Box6 *dPb = mem.get<Box6>(nAll);
@@ -1612,9 +2018,9 @@ bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *objectFirst, i
     refuse(errWords[kErrKind], "nnbvh_build_create: unknown primitive kind");
     // Objects from the first malformed one on are not built: only a lower-numbered object can still change the
     // message, and no malformed primitive reaches the phases below.
-    const int nBuild = std::min(nObjects, refusedObject);
+    const int nBuild = std::min(nObjects, refuse.object);
     if (nBuild == 0) {
-        *error = refusal;
+        *error = refuse.text;
         return false;
     }
     const int n = objectFirst[nBuild];
@@ -1802,8 +2208,8 @@ bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *objectFirst, i
             break;  // (no later object changes the message)
         }
     }
-    if (refusedObject != kNoObject) {
-        *error = refusal;
+    if (refuse.object != kNoObject) {
+        *error = refuse.text;
         return false;
     }
     const int totalNodes = out->node_first[(size_t)nBuild];

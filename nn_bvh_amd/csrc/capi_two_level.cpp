@@ -1,8 +1,8 @@
 // capi_two_level.cpp — nnbvh_scene_create_instanced_gpu_build: a two-level scene (object instances as pbrt builds
 // them, scene.cpp:1521-1577) from the caller's primitive lists to traceable without a tree visiting the host.  Every
-// object definition's tree (SAH: all of them in one forest pass; HLBVH: one after another), then the top-level tree
+// object definition's tree (all of them in one forest pass, SAH or HLBVH), then the top-level tree
 // over the instances' transformed bounds, come from the device builders' cores (bvh_build_gpu.hip); the trees are put
-// into one numbering and baked by bvh_bake.hip.  nnbvh_build_forest_create_gpu, at the end, is that forest pass alone.  The device
+// into one numbering and baked by bvh_bake.hip.  nnbvh_build_forest_create_gpu[_hlbvh], at the end, is that forest pass alone.  The device
 // arrays are byte for byte those of nn_bvh_amd.instancing.assemble_two_level + nnbvh_scene_create_instanced_with_attributes.
 // Host code only.
 #include <algorithm>
@@ -34,13 +34,14 @@ struct PrimListCheck {
     const nnbvh_animated_transform *animated = nullptr;
     const float *prim_bounds = nullptr, *normals = nullptr, *uvs = nullptr, *prim_alpha = nullptr;
     bool scene = true;  // false: a forest of trees: attributes are not asked for, instance entries have no place
+    const char *fn = "";  // (forests) the call's name in front of its own message
 };
 bool check_prims(const nnbvh_prim *prims, int n_prims, int n_verts, const PrimListCheck &c) {
     for (int i = 0; i < n_prims; ++i) {
         const nnbvh_prim &p = prims[i];
         int nv = 0;
         if (p.kind == NNBVH_PRIM_INSTANCE) {
-            if (!c.scene) return fault("nnbvh_build_forest_create_gpu: instance entries are not built in a forest");
+            if (!c.scene) return fault(std::string(c.fn) + "instance entries are not built in a forest");
             if (i >= c.n_top_prims) return fault("scene_create: nested instances are not supported");
             if (p.v[0] < 0 || p.v[0] >= c.n_placements) return fault("scene_create: instance index out of range");
             if (c.animated && c.animated[p.v[0]].actually_animated && !c.prim_bounds)
@@ -102,8 +103,8 @@ bool check_arguments(const nnbvh_prim *prims, int n_prims, int n_top_prims, cons
 
 // The forest call's: the same faults in the same words where the two calls share them.
 bool check_forest_arguments(const nnbvh_prim *prims, int n_prims, const int32_t *object_first, int n_objects,
-                            const float *verts, int n_verts, const float *prim_bounds, int split_method) {
-    const char *fn = "nnbvh_build_forest_create_gpu: ";
+                            const float *verts, int n_verts, const float *prim_bounds, int split_method, bool hlbvh) {
+    const char *fn = hlbvh ? "nnbvh_build_forest_create_gpu_hlbvh: " : "nnbvh_build_forest_create_gpu: ";
     if (!prims || !verts || !object_first || n_prims <= 0 || n_verts <= 0 || n_objects <= 0)
         return fault(std::string(fn) + "null or empty input array");
     if (object_first[0] != 0 || object_first[n_objects] != n_prims)
@@ -111,11 +112,13 @@ bool check_forest_arguments(const nnbvh_prim *prims, int n_prims, const int32_t 
     for (int k = 0; k < n_objects; ++k)
         if (object_first[k + 1] <= object_first[k])
             return fault(std::string(fn) + "malformed object_first (an object is empty or the entries decrease)");
-    if (split_method != NNBVH_SPLIT_SAH)
-        return fault(std::string(fn) + "the forest build is SAH only (split_method NNBVH_SPLIT_SAH)");
+    if (!hlbvh && split_method != NNBVH_SPLIT_SAH)
+        return fault(std::string(fn) + "the forest build is SAH only (split_method NNBVH_SPLIT_SAH; HLBVH forests: "
+                                       "nnbvh_build_forest_create_gpu_hlbvh)");
     PrimListCheck c;
     c.prim_bounds = prim_bounds;
     c.scene = false;
+    c.fn = fn;
     return check_prims(prims, n_prims, n_verts, c);
 }
 
@@ -241,10 +244,10 @@ extern "C" nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(
         if (!built) set_error(err);
         return built;
     };
-    // SAH: all objects in one forest pass.  NNBVH_TWO_LEVEL_LOOP=1 keeps the object-by-object loop for them too (speed
-    // only, like NNBVH_SAH_SMALL: the same bytes either way); HLBVH has no forest form and always loops
+    // All objects in one forest pass, SAH or HLBVH.  NNBVH_TWO_LEVEL_LOOP=1 keeps the object-by-object loop reachable
+    // for both (speed only, like NNBVH_SAH_SMALL: the same bytes either way)
     const char *loop_env = std::getenv("NNBVH_TWO_LEVEL_LOOP");
-    const bool forest = split_method == NNBVH_SPLIT_SAH && !(loop_env && std::atoi(loop_env) != 0);
+    const bool forest = !(loop_env && std::atoi(loop_env) != 0);
     if (forest) {
         std::vector<int> local_first((size_t)n_objects + 1);
         for (int k = 0; k <= n_objects; ++k) local_first[(size_t)k] = object_first[k] - n_top_prims;
@@ -260,7 +263,7 @@ extern "C" nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(
         in.stream = stream;
         in.pool = &h.pool;
         ForestBuildResult f;
-        if (!gpu_sah_forest_device(in, local_first.data(), n_objects, &f, &err)) {
+        if (!(split_method == NNBVH_SPLIT_SAH ? gpu_sah_forest_device : gpu_hlbvh_forest_device)(in, local_first.data(), n_objects, &f, &err)) {
             set_error(err);
             return nullptr;
         }
@@ -405,15 +408,17 @@ struct nnbvh_forest {
     int n_levels = 0, n_subtrees = 0;
 };
 
-extern "C" nnbvh_forest *nnbvh_build_forest_create_gpu(const nnbvh_prim *prims, int n_prims, const int32_t *object_first,
-                                                       int n_objects, const float *verts, int n_verts,
-                                                       const float *prim_bounds, int max_prims_in_node, int split_method,
-                                                       int device) {
-    if (!check_forest_arguments(prims, n_prims, object_first, n_objects, verts, n_verts, prim_bounds, split_method))
+namespace {
+
+nnbvh_forest *forest_create(const nnbvh_prim *prims, int n_prims, const int32_t *object_first, int n_objects,
+                            const float *verts, int n_verts, const float *prim_bounds, int max_prims_in_node,
+                            int split_method, int device, bool hlbvh) {
+    if (!check_forest_arguments(prims, n_prims, object_first, n_objects, verts, n_verts, prim_bounds, split_method, hlbvh))
         return nullptr;
     const int n_dev = nnbvh_device_count();
     if (n_dev <= 0 || device < 0 || device >= n_dev) {
-        set_error("nnbvh_build_forest_create_gpu: no usable HIP device (this library has no CPU fallback)");
+        set_error(std::string(hlbvh ? "nnbvh_build_forest_create_gpu_hlbvh" : "nnbvh_build_forest_create_gpu") +
+                  ": no usable HIP device (this library has no CPU fallback)");
         return nullptr;
     }
     DeviceGuard guard(device);
@@ -446,7 +451,7 @@ extern "C" nnbvh_forest *nnbvh_build_forest_create_gpu(const nnbvh_prim *prims, 
     in.pool = &h.pool;
     ForestBuildResult f;
     std::string err;
-    if (!gpu_sah_forest_device(in, (const int *)object_first, n_objects, &f, &err)) {
+    if (!(hlbvh ? gpu_hlbvh_forest_device : gpu_sah_forest_device)(in, (const int *)object_first, n_objects, &f, &err)) {
         set_error(err);
         return nullptr;
     }
@@ -468,6 +473,24 @@ extern "C" nnbvh_forest *nnbvh_build_forest_create_gpu(const nnbvh_prim *prims, 
     out->n_levels = f.n_levels;
     out->n_subtrees = f.n_subtrees;
     return out.release();
+}
+
+}  // namespace
+
+extern "C" nnbvh_forest *nnbvh_build_forest_create_gpu(const nnbvh_prim *prims, int n_prims, const int32_t *object_first,
+                                                       int n_objects, const float *verts, int n_verts,
+                                                       const float *prim_bounds, int max_prims_in_node, int split_method,
+                                                       int device) {
+    return forest_create(prims, n_prims, object_first, n_objects, verts, n_verts, prim_bounds, max_prims_in_node,
+                         split_method, device, false);
+}
+
+extern "C" nnbvh_forest *nnbvh_build_forest_create_gpu_hlbvh(const nnbvh_prim *prims, int n_prims,
+                                                             const int32_t *object_first, int n_objects,
+                                                             const float *verts, int n_verts, const float *prim_bounds,
+                                                             int max_prims_in_node, int device) {
+    return forest_create(prims, n_prims, object_first, n_objects, verts, n_verts, prim_bounds, max_prims_in_node,
+                         NNBVH_SPLIT_HLBVH, device, true);
 }
 
 extern "C" const nnbvh_linear_node *nnbvh_forest_nodes(const nnbvh_forest *f, int *n_nodes) {

@@ -21,7 +21,10 @@ profiles/two_level_device_scene.txt): creating a two-level (instanced) scene, th
                                                                forest build existed)
 on (i) the 400 placements of the 33 K-triangle killeroo of tools/bench_instances.py and (ii) 2 000 objects of 64
 triangles with 20 000 placements, where the per-object cost of building one tree after another shows; with the
-phases of one forest build of the objects alone (build_forest_gpu) and B's peak device memory."""
+phases of one forest build of the objects alone (build_forest_gpu) and B's peak device memory.
+--split=hlbvh runs the four routes with HLBVH trees (phases of one build_hlbvh_forest_gpu; default output
+profiles/two_level_device_scene_hlbvh.txt); --split=sah is the default.  With single-tree scenes named as well, their
+JSON lines follow as usual (gpu_hlbvh_ms_end_to_end is the single HLBVH build's figure)."""
 import json
 import os
 import sys
@@ -31,8 +34,8 @@ import numpy as np
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from nn_bvh_amd import BVHAggregate, build_forest_gpu, build_tree, build_tree_gpu, make_prims, scene  # noqa: E402
-
+from nn_bvh_amd import (BVHAggregate, build_forest_gpu, build_hlbvh_forest_gpu, build_tree, build_tree_gpu, make_prims,  # noqa: E402
+                        scene)
 
 
 def kd_section(names, out_path, rounds=5):
@@ -191,7 +194,7 @@ def assemble_with(builder, top_prims, verts, objects, placements):
     return np.concatenate(nodes), np.concatenate(prims).astype(PRIM_DTYPE), instances, len(top.nodes)
 
 
-def two_level_section(out_path, rounds=5):
+def two_level_section(out_path, rounds=5, split="sah"):
     import threading
 
     import torch
@@ -202,19 +205,28 @@ def two_level_section(out_path, rounds=5):
     def stats(ms):
         return f"{np.median(ms):9.1f} ms  ({min(ms):.1f} .. {max(ms):.1f})"
 
+    def phases(forest):
+        m = forest.gpu_ms
+        if split == "sah":
+            return (f"  one forest build of the objects alone: upload {m[0]:.2f}, big nodes {m[1]:.2f}, subtrees {m[2]:.2f}, "
+                    f"layout + bounds {m[3]:.2f}, download {m[4]:.2f} ms; {forest.n_levels} breadth-first passes, "
+                    f"{forest.n_subtrees} subtrees")
+        return (f"  one forest build of the objects alone: upload {m[0]:.2f}, sort + treelets {m[1]:.2f}, host upper SAH "
+                f"{m[2]:.2f}, emit {m[3]:.2f}, download {m[4]:.2f} ms; {forest.n_subtrees} treelets")
+
     for name, (top, verts, objects, placements) in two_level_scenes().items():
         def from_arrays(nodes, prims, instances, n_top):
             return BVHAggregate.from_tree(nodes, prims, verts, instances=instances, n_top_nodes=n_top)
 
         def route_a0():
-            return from_arrays(*instancing.assemble_two_level(top, verts, objects, placements))
+            return from_arrays(*instancing.assemble_two_level(top, verts, objects, placements, 4, split))
 
         def route_a():
-            gpu = lambda p, v, prim_bounds=None: build_tree_gpu(p, v, 4, prim_bounds, split_method="sah")  # noqa: E731
+            gpu = lambda p, v, prim_bounds=None: build_tree_gpu(p, v, 4, prim_bounds, split_method=split)  # noqa: E731
             return from_arrays(*assemble_with(gpu, top, verts, objects, placements))
 
         def route_b():
-            return BVHAggregate.build_two_level_on_device(top, verts, objects, placements)
+            return BVHAggregate.build_two_level_on_device(top, verts, objects, placements, 4, split)
 
         def route_loop():
             os.environ["NNBVH_TWO_LEVEL_LOOP"] = "1"  # read once per call
@@ -255,7 +267,7 @@ def two_level_section(out_path, rounds=5):
         th.join()
         kept = base - torch.cuda.mem_get_info()[0]
         agg.close()
-        forest = build_forest_gpu(objects, verts)
+        forest = (build_forest_gpu if split == "sah" else build_hlbvh_forest_gpu)(objects, verts)
         a_ms, b_ms, l_ms, a0_ms = ms["route_a"], ms["route_b"], ms["route_loop"], ms["route_a0"]
         gain_l = np.median(l_ms) - np.median(b_ms)
         spread_l = max(max(l_ms) - min(l_ms), max(b_ms) - min(b_ms))
@@ -276,15 +288,13 @@ def two_level_section(out_path, rounds=5):
                   f"  median A - median B = {gain:.1f} ms, larger spread {spread:.1f} ms: {verdict}",
                   f"  median L - median B = {gain_l:.1f} ms, larger spread {spread_l:.1f} ms: {verdict_l}",
                   f"  median B - median A0 = {np.median(b_ms) - np.median(a0_ms):.1f} ms",
-                  f"  one forest build of the objects alone: upload {forest.gpu_ms[0]:.2f}, big nodes {forest.gpu_ms[1]:.2f}, "
-                  f"subtrees {forest.gpu_ms[2]:.2f}, layout + bounds {forest.gpu_ms[3]:.2f}, download {forest.gpu_ms[4]:.2f} ms; "
-                  f"{forest.n_levels} breadth-first passes, {forest.n_subtrees} subtrees",
+                  phases(forest),
                   f"  B device memory: peak {(base - low[0]) / 2**20:.0f} MiB in use during the call (sampled), "
                   f"{kept / 2**20:.0f} MiB kept (scene arrays {info['device_bytes'] / 2**20:.0f} MiB)", ""]
         result[name] = {"a0_ms": a0_ms, "a_ms": a_ms, "loop_ms": l_ms, "b_ms": b_ms, "peak_bytes": int(base - low[0]),
                         "scene_bytes": info["device_bytes"], "verdict": verdict, "verdict_loop": verdict_l,
                         "forest_phases_ms": forest.gpu_ms}
-    text = "\n".join([f"two-level scene creation, {rounds} alternated rounds per scene, one process; "
+    text = "\n".join([f"two-level scene creation, {split} trees, {rounds} alternated rounds per scene, one process; "
                       f"{torch.cuda.get_device_name(0)}", ""] + lines)
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
@@ -299,14 +309,20 @@ kd_out = os.path.join(ROOT, "profiles", "kd_device_scene.txt")
 for f in flags:
     if f.startswith("--kd-out="):
         kd_out = f.split("=", 1)[1]
-two_level_out = os.path.join(ROOT, "profiles", "two_level_device_scene.txt")
+split = "sah"
+for f in flags:
+    if f.startswith("--split="):
+        split = f.split("=", 1)[1]
+if split not in ("sah", "hlbvh"):
+    sys.exit("--split=sah or --split=hlbvh")
+two_level_out = os.path.join(ROOT, "profiles", "two_level_device_scene" + ("" if split == "sah" else "_hlbvh") + ".txt")
 for f in flags:
     if f.startswith("--two-level-out="):
         two_level_out = f.split("=", 1)[1]
 names = args or ["killeroos", "coffee_maker", "bathroom", "crown"]
 out = {}
 if "--two-level" in flags or "--two-level-only" in flags:
-    out["two_level_scene_create"] = two_level_section(two_level_out)
+    out["two_level_scene_create"] = two_level_section(two_level_out, split=split)
 if "--kd" in flags or "--kd-only" in flags:
     out["kd_scene_create"] = kd_section(args or ["bathroom", "crown"], kd_out)
 for name in ([] if "--kd-only" in flags or "--two-level-only" in flags else names):
