@@ -106,15 +106,18 @@ struct ForestBuildResult {
     double ms[5] = {0, 0, 0, 0, 0};  // as gpu_sah's ([0] and [4] are the wrappers')
     int n_levels = 0;                // breadth-first passes run (each works on every object's big nodes of one level)
     int n_subtrees = 0, n_upper = 0;  // subtrees built by wavefronts, nodes built breadth-first
+    int n_codes = 0;                  // HLBVH only: distinct (object, Morton code) keys in the forest
 };
 bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,
                            std::string *error);
-// The same for HLBVH trees: tree k is byte for byte gpu_hlbvh_device's of object k alone, from a fixed number of launches
-// and synchronisations whatever n_objects is (one radix sort over the key (object << 30) | Morton code; the upper SAH
-// on the host, per object, over one table of every object's treelets).  Of the result, ms has the meaning of
-// gpu_hlbvh's ([1] device pipeline up to the treelet table, [2] host upper trees, [3] device emit), n_levels = 0,
-// n_subtrees = treelets in the forest, n_upper = upper nodes.  A malformed input fails with the message a loop of
-// gpu_hlbvh_device calls over the objects would have stopped at.
+// The same for HLBVH trees (gpu_hlbvh_device is its one-object case): tree k is byte for byte that of object k alone,
+// from a fixed number of launches and synchronisations whatever n_objects is (one radix sort over the key
+// (object << 30) | Morton code, 64 bits wide, or the 32-bit code alone when n_objects is 1; the upper SAH on the host,
+// per object, over one table of every object's treelets).  Of the result, ms has the meaning of gpu_hlbvh's ([1] device
+// pipeline up to the treelet table, [2] host upper trees, [3] device emit), n_levels = 0, n_subtrees = treelets in the
+// forest, n_upper = upper nodes, n_codes = distinct keys.  A malformed input fails with the message a loop of
+// gpu_hlbvh_device calls over the objects would have stopped at; an object with several kinds of fault reports the
+// first of: vertex index, missing bounds, non-finite, unknown kind, leaf size, treelet checks.
 bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,
                              std::string *error);
 

@@ -10,23 +10,26 @@
 // common-prefix lengths), cut off where a range gets smaller than maxPrimsInNode:
 //
 //   1  primitive bounds, centroid bounds            k_prim_bounds     (streaming, one pass)
-//   2  30-bit Morton codes (aggregates.cpp:398-408)  k_morton
-//   3  stable radix sort of (code, index)           rocPRIM          (the reference's own 5x6-bit
+//   2  30-bit Morton codes (aggregates.cpp:398-408)  k_morton         (many objects: first their centroid
+//                                                                      bounds, k_cbounds_init + k_object_cbounds)
+//   3  stable radix sort of (key, index)            rocPRIM          (the reference's own 5x6-bit
 //                                                                      LSD sort is stable too)
 //   4  distinct codes ("atoms") and their ranges    k_heads + scan + k_compact
 //   5  radix tree over the atoms                    k_karras
 //   6  which radix nodes survive as real nodes      k_classify + 2 scans (leaf / treelet ordinals)
 //   7  bounds bottom-up: leaves, then interior nodes by split bit 0..17 (children always split at
 //      a lower bit, so 18 dependency-free launches; no atomics, no intra-kernel fences)
-//   8  treelet roots -> host: buildUpperSAH over <= 4096 boxes (aggregates.cpp:626-723, host)
+//   8  treelet roots (k_treelets) -> host: buildUpperSAH over an object's <= 4096 boxes (aggregates.cpp:626-723, host)
 //   9  every node computes its own DFS position   k_emit: preorder = 2 x (leaves to its left in
 //      the treelet) + (ancestors it hangs off on the left side), found by walking <= 18 parents
 //  10  leaf-ordered primitive table = the sorted order  k_gather_prims
 //
 // Everything is integer / min / max work on 4-32 B records: HBM-bound streaming except the two
 // pointer walks (5, 9), which touch a handful of L2-resident words per node.
-// The trees of many objects come from the same ten steps run once over all their primitives, with the object's
-// number above the code in the sort key (gpu_hlbvh_forest_device).
+// The trees of many objects come from the same ten steps run once over all their primitives (gpu_hlbvh_forest_device;
+// one tree is its one-object case).  The sort key is (object << 30) | code: the object's number above the code keeps
+// every primitive, run of equal codes, treelet and radix-tree range inside its object, and steps 2, 6, 8 and 9 read it
+// back to find a node's object (its centroid bounds, its error word, its first node and primitive, its depth).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,7 +52,7 @@ constexpr int kB = 256;
 constexpr int kTreeletBit = 18;  // bits >= 18 separate treelets (mask 0x3ffc0000, aggregates.cpp:423)
 
 enum : int { kErrVertex = 1, kErrNeedBounds = 2, kErrKind = 3, kErrLeafSize = 4, kErrNonFinite = 5, kErrSahCosts = 6 };
-// The forest builders' error words (SAH, and HLBVH over many objects), one per kind above: errObj[kind] = the lowest-numbered object that raised it
+// The builders' error words, one per kind above: errObj[kind] = the lowest-numbered object that raised it
 // (atomicMin; kNoObject = nobody), so a forest reports what a loop over its objects would have stopped at.
 // errObj[0] is a plain word for the "cannot happen" codes.
 constexpr int kErrWords = 8;
@@ -97,15 +100,10 @@ __global__ __launch_bounds__(kB) void k_prim_bounds(const nnbvh_prim *__restrict
                                                     const float *__restrict__ verts, int nVerts,
                                                     const float *__restrict__ callerBounds, int n,
                                                     Box6 *__restrict__ pb, unsigned *cbKeys,
-                                                    int *err, const int *__restrict__ objectFirst,
-                                                    int nObjects, int *errObj) {
+                                                    const int *__restrict__ objectFirst, int nObjects,
+                                                    int *errObj) {
     __shared__ float red[6][kB / 64];
-    // err (one HLBVH tree): one word, the last writer's kind.  errObj (SAH and the HLBVH forest, with objectFirst[nObjects + 1]): see kErrWords
-    auto report = [&](int kind, int i) {
-        if (!errObj) {
-            *err = kind;
-            return;
-        }
+    auto report = [&](int kind, int i) {  // errObj, with objectFirst[nObjects + 1]: see kErrWords
         int lo = 0, hi = nObjects - 1;  // the object of primitive i: the last k with objectFirst[k] <= i
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
@@ -192,31 +190,79 @@ __device__ __forceinline__ unsigned left_shift3(unsigned x) {
     return x;
 }
 
-__global__ __launch_bounds__(kB) void k_morton(const Box6 *__restrict__ pb,
-                                               const unsigned *__restrict__ cbKeys, int n,
-                                               unsigned *__restrict__ codes, int *__restrict__ idx) {
-    float mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) {
-        mn[k] = key2f(cbKeys[k]);
-        mx[k] = key2f(cbKeys[3 + k]);
+// Centroid bounds of every object (order-free min / max of the same centroids k_prim_bounds folds for the whole input;
+// with one object those are the bounds, and this kernel does not run), and the object of every primitive for k_morton.
+// A wavefront that lies inside one object (every wavefront of a big object, bar two) folds first and sends six atomics
+// instead of 384.
+__global__ __launch_bounds__(kB) void k_object_cbounds(const Box6 *__restrict__ pb, const int *__restrict__ objectFirst,
+                                                       int nObjects, int n, int *__restrict__ objOf, unsigned *cbObj) {
+    const int i = blockIdx.x * kB + threadIdx.x;
+    const bool live = i < n;
+    int obj = -1;
+    float cmin[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f};
+    float cmax[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
+    if (live) {
+        int lo = 0, hi = nObjects - 1;  // the last k with objectFirst[k] <= i
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (objectFirst[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        obj = lo;
+        objOf[i] = obj;
+        const Box6 b = pb[i];
+        for (int k = 0; k < 3; ++k) cmin[k] = cmax[k] = .5f * b.mn[k] + .5f * b.mx[k];  // BVHPrimitive::Centroid()
     }
+    const int obj0 = __shfl(obj, 0);
+    if (obj0 < 0) return;  // lane 0 holds the wavefront's lowest index: nobody is live
+    if (__all(!live || obj == obj0)) {
+        for (int k = 0; k < 3; ++k)
+            for (int off = 32; off >= 1; off >>= 1) {
+                cmin[k] = fminf(cmin[k], __shfl_xor(cmin[k], off));
+                cmax[k] = fmaxf(cmax[k], __shfl_xor(cmax[k], off));
+            }
+        if ((threadIdx.x & 63) != 0) return;
+    } else if (!live) {
+        return;
+    }
+    for (int k = 0; k < 3; ++k) {
+        atomicMin(&cbObj[6 * (size_t)obj + k], f2key(cmin[k]));
+        atomicMax(&cbObj[6 * (size_t)obj + 3 + k], f2key(cmax[k]));
+    }
+}
+
+__global__ __launch_bounds__(kB) void k_cbounds_init(int nObjects, unsigned *__restrict__ cbObj) {
+    const int i = blockIdx.x * kB + threadIdx.x;
+    if (i < 6 * nObjects) cbObj[i] = (i % 6) < 3 ? 0xffffffffu : 0u;  // min keys all-ones, max keys 0
+}
+
+// The code against the object's own centroid bounds (cbObj[6 obj ..]: min keys, max keys; the mx > mn guard per object
+// and per axis), the object number above the 30 code bits.  objOf == nullptr: everything is object 0.
+template <typename Key>
+__global__ __launch_bounds__(kB) void k_morton(const Box6 *__restrict__ pb, const unsigned *__restrict__ cbObj,
+                                               const int *__restrict__ objOf, int n, Key *__restrict__ keys,
+                                               int *__restrict__ idx) {
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) {
         const Box6 b = pb[i];
+        const int obj = objOf ? objOf[i] : 0;
+        const unsigned *cb = cbObj + 6 * (size_t)obj;
         unsigned q[3];
         for (int k = 0; k < 3; ++k) {
+            const float mn = key2f(cb[k]), mx = key2f(cb[3 + k]);
             const float c = .5f * b.mn[k] + .5f * b.mx[k];
-            float o = c - mn[k];
-            if (mx[k] > mn[k]) o /= mx[k] - mn[k];
+            float o = c - mn;
+            if (mx > mn) o /= mx - mn;
             q[k] = (unsigned)(o * 1024.0f);  // mortonScale = 1 << 10
         }
-        codes[i] = (left_shift3(q[2]) << 2) | (left_shift3(q[1]) << 1) | left_shift3(q[0]);
+        const unsigned code = (left_shift3(q[2]) << 2) | (left_shift3(q[1]) << 1) | left_shift3(q[0]);
+        keys[i] = ((Key)obj << 30) | code;
         idx[i] = i;
     }
 }
 
 // ---- 4: runs of identical codes -------------------------------------------------------------------
-// Key: unsigned (one tree: the 30-bit code) or unsigned long long (a forest: (object << 30) | code, so a run of
-// identical codes ends at an object boundary and every object is one subtree of the radix tree below)
+// Key = (object << 30) | code: a run of identical keys ends at an object boundary and every object is one subtree of
+// the radix tree below.  unsigned long long; unsigned for one object, whose keys are its 30-bit codes.
 template <typename Key>
 __global__ __launch_bounds__(kB) void k_heads(const Key *__restrict__ codes, int n, int *__restrict__ head) {
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB)
@@ -292,14 +338,13 @@ __global__ __launch_bounds__(kB) void k_karras(const Key *__restrict__ ucode, in
 // internal node: interior iff it lies inside a treelet (split bit < 18) and holds >= maxPrims
 // primitives (emitLBVH's leaf rule, :453).  Any node inside a treelet whose parent is such an
 // interior node (or which is its treelet's root) and which is not interior itself is a leaf.
+// An oversized leaf is reported with its object (errObj[kErrLeafSize], lowest object wins).
+template <typename Key>
 __global__ __launch_bounds__(kB) void k_classify(int m, int maxPrims, const int *__restrict__ pstart,
-                                                 const int *__restrict__ firstA,
-                                                 const int *__restrict__ lastA,
-                                                 const unsigned char *__restrict__ bit,
-                                                 const int *__restrict__ parentV,
-                                                 unsigned char *__restrict__ kind,
-                                                 int *__restrict__ leafHead,
-                                                 int *__restrict__ treeletHead, int *err) {
+                                                 const int *__restrict__ firstA, const int *__restrict__ lastA,
+                                                 const unsigned char *__restrict__ bit, const int *__restrict__ parentV,
+                                                 const Key *__restrict__ ukey, unsigned char *__restrict__ kind,
+                                                 int *__restrict__ leafHead, int *__restrict__ treeletHead, int *errObj) {
     const int v = blockIdx.x * kB + threadIdx.x;
     if (v >= 2 * m - 1) return;
     const bool internal = v < m - 1;
@@ -314,11 +359,10 @@ __global__ __launch_bounds__(kB) void k_classify(int m, int maxPrims, const int 
     bool parentInterior = false;
     if (parentInTreelet) parentInterior = pstart[lastA[p] + 1] - pstart[firstA[p]] >= maxPrims;
     const bool realLeaf = inTreelet && !realInterior && (treeletRoot || parentInterior);
-    kind[v] = (realInterior ? kRealInterior : 0) | (realLeaf ? kRealLeaf : 0) |
-              (treeletRoot ? kTreeletRoot : 0);
+    kind[v] = (realInterior ? kRealInterior : 0) | (realLeaf ? kRealLeaf : 0) | (treeletRoot ? kTreeletRoot : 0);
     if (realLeaf) {
         leafHead[first] = 1;
-        if (n > 65535) *err = kErrLeafSize;  // LinearBVHNode::nPrimitives is 16 bits (:134)
+        if (n > 65535) atomicMin(&errObj[kErrLeafSize], (int)(ukey[first] >> 30));  // LinearBVHNode::nPrimitives is 16 bits (:134)
     }
     if (treeletRoot) treeletHead[first] = 1;
 }
@@ -403,39 +447,37 @@ __device__ __forceinline__ int subtree_size(int v, int m, const unsigned char *k
     return 2 * (leafOrd[lastA[v] + 1] - leafOrd[firstA[v]]) - 1;
 }
 
+// Every treelet's box, node count and object: the treelets are numbered object after object, Morton order inside
+template <typename Key>
 __global__ __launch_bounds__(kB) void k_treelets(int m, const unsigned char *__restrict__ kind,
-                                                 const int *__restrict__ firstA,
-                                                 const int *__restrict__ lastA,
-                                                 const int *__restrict__ leafOrd,
-                                                 const int *__restrict__ treeOrd,
-                                                 const Box6 *__restrict__ nodeBox,
-                                                 Box6 *__restrict__ tbox, int *__restrict__ tsize) {
+                                                 const int *__restrict__ firstA, const int *__restrict__ lastA,
+                                                 const int *__restrict__ leafOrd, const int *__restrict__ treeOrd,
+                                                 const Box6 *__restrict__ nodeBox, const Key *__restrict__ ukey, int tCap,
+                                                 Box6 *__restrict__ tbox, int *__restrict__ tsize, int *__restrict__ tobj) {
     const int v = blockIdx.x * kB + threadIdx.x;
     if (v >= 2 * m - 1 || !(kind[v] & kTreeletRoot)) return;
     const int first = v < m - 1 ? firstA[v] : v - (m - 1);
     const int t = treeOrd[first];
+    if (t >= tCap) return;  // cannot happen: at most min(m, 4096 per object) treelets
     tbox[t] = nodeBox[v];
     tsize[t] = subtree_size(v, m, kind, firstA, lastA, leafOrd);
+    tobj[t] = (int)(ukey[first] >> 30);
 }
 
 // ---- 9: flattenBVH's DFS order (aggregates.cpp:505-522) without a traversal ---------------------------
+// The trees lie one after another: tbase[t] already includes the tree's node_first; a second child counts from its
+// own tree's root, a leaf's first primitive from its object's first primitive, the depth is the object's own maximum
 __global__ __launch_bounds__(kB) void k_emit(int m, const unsigned char *__restrict__ kind,
-                                             const unsigned char *__restrict__ bit,
-                                             const int *__restrict__ pstart,
-                                             const int *__restrict__ firstA,
-                                             const int *__restrict__ lastA,
-                                             const int *__restrict__ leftV,
-                                             const int *__restrict__ parentV,
-                                             const int *__restrict__ leafOrd,
-                                             const int *__restrict__ treeOrd,
-                                             const int *__restrict__ tbase,
-                                             const int *__restrict__ tdepth,
-                                             const Box6 *__restrict__ nodeBox,
-                                             nnbvh_linear_node *__restrict__ nodes, int *maxDepth) {
-    __shared__ int blockDepth;
-    if (threadIdx.x == 0) blockDepth = 0;
-    __syncthreads();
+                                             const unsigned char *__restrict__ bit, const int *__restrict__ pstart,
+                                             const int *__restrict__ firstA, const int *__restrict__ lastA,
+                                             const int *__restrict__ leftV, const int *__restrict__ parentV,
+                                             const int *__restrict__ leafOrd, const int *__restrict__ treeOrd,
+                                             const int *__restrict__ tbase, const int *__restrict__ tdepth,
+                                             const int *__restrict__ tobj, const int *__restrict__ nodeFirst,
+                                             const int *__restrict__ objectFirst, const Box6 *__restrict__ nodeBox,
+                                             nnbvh_linear_node *__restrict__ nodes, int *depthObj) {
     const int v = blockIdx.x * kB + threadIdx.x;
+    int obj = -1, leafDepth = -1;  // of a leaf
     if (v < 2 * m - 1 && (kind[v] & (kRealInterior | kRealLeaf))) {
         const bool internal = v < m - 1;
         const int first = internal ? firstA[v] : v - (m - 1);
@@ -458,19 +500,34 @@ __global__ __launch_bounds__(kB) void k_emit(int m, const unsigned char *__restr
         }
         out.pad = 0;
         if (kind[v] & kRealLeaf) {
-            out.offset = pstart[first];  // leaves are emitted in sorted order: offset = range start
+            obj = tobj[t];
+            out.offset = pstart[first] - objectFirst[obj];
             out.nprims = (uint16_t)(pstart[last + 1] - pstart[first]);
             out.axis = 0;
-            atomicMax(&blockDepth, tdepth[t] + depth);
+            leafDepth = tdepth[t] + depth;
         } else {
-            out.offset = flat + 1 + subtree_size(leftV[v], m, kind, firstA, lastA, leafOrd);
+            out.offset = flat + 1 + subtree_size(leftV[v], m, kind, firstA, lastA, leafOrd) - nodeFirst[tobj[t]];
             out.nprims = 0;
             out.axis = (uint8_t)(bit[v] % 3);  // :499
         }
         nodes[flat] = out;
     }
-    __syncthreads();
-    if (threadIdx.x == 0 && blockDepth > 0) atomicMax(maxDepth, blockDepth);
+    // The object's depth.  A wavefront whose leaves are all of one object (every wavefront inside a big object) folds
+    // first and sends one atomicMax instead of up to 64 to the same word; the plain read spares most of those as well.
+    const unsigned long long leaves = __ballot(leafDepth >= 0);
+    if (!leaves) return;
+    const int obj0 = __shfl(obj, __ffsll((long long)leaves) - 1);
+    if (__all(leafDepth < 0 || obj == obj0)) {
+        for (int off = 32; off >= 1; off >>= 1) {
+            const int o = __shfl_xor(leafDepth, off);
+            leafDepth = o > leafDepth ? o : leafDepth;
+        }
+        if ((threadIdx.x & 63) != 0) return;
+        obj = obj0;
+    } else if (leafDepth < 0) {
+        return;
+    }
+    if (depthObj[obj] < leafDepth) atomicMax(&depthObj[obj], leafDepth);
 }
 
 // ---- 10 ------------------------------------------------------------------------------------------------
@@ -479,176 +536,6 @@ __global__ __launch_bounds__(kB) void k_gather_prims(const nnbvh_prim *__restric
                                                      nnbvh_prim *__restrict__ ordered) {
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB)
         ordered[i] = prims[idxSorted[i]];
-}
-
-// ---- the forest form (gpu_hlbvh_forest_device): what differs per object ------------------------------------------------
-// Steps 1, 7 and 10 are the kernels above as they stand; 4 and 5 are their 64-bit instances; the ones below replace
-// k_morton, k_classify, k_treelets and k_emit.  Nothing in them looks outside the object a primitive belongs to.
-
-// Centroid bounds of every object (order-free min / max of the same centroids k_prim_bounds folds for one tree), and
-// the object of every primitive for the kernels after this one.  A wavefront that lies inside one object (every
-// wavefront of a big object, bar two) folds first and sends six atomics instead of 384.
-__global__ __launch_bounds__(kB) void k_object_cbounds(const Box6 *__restrict__ pb, const int *__restrict__ objectFirst,
-                                                       int nObjects, int n, int *__restrict__ objOf, unsigned *cbObj) {
-    const int i = blockIdx.x * kB + threadIdx.x;
-    const bool live = i < n;
-    int obj = -1;
-    float cmin[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f};
-    float cmax[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
-    if (live) {
-        int lo = 0, hi = nObjects - 1;  // the last k with objectFirst[k] <= i
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (objectFirst[mid] <= i) lo = mid;
-            else hi = mid - 1;
-        }
-        obj = lo;
-        objOf[i] = obj;
-        const Box6 b = pb[i];
-        for (int k = 0; k < 3; ++k) cmin[k] = cmax[k] = .5f * b.mn[k] + .5f * b.mx[k];  // BVHPrimitive::Centroid()
-    }
-    const int obj0 = __shfl(obj, 0);
-    if (obj0 < 0) return;  // lane 0 holds the wavefront's lowest index: nobody is live
-    if (__all(!live || obj == obj0)) {
-        for (int k = 0; k < 3; ++k)
-            for (int off = 32; off >= 1; off >>= 1) {
-                cmin[k] = fminf(cmin[k], __shfl_xor(cmin[k], off));
-                cmax[k] = fmaxf(cmax[k], __shfl_xor(cmax[k], off));
-            }
-        if ((threadIdx.x & 63) != 0) return;
-    } else if (!live) {
-        return;
-    }
-    for (int k = 0; k < 3; ++k) {
-        atomicMin(&cbObj[6 * (size_t)obj + k], f2key(cmin[k]));
-        atomicMax(&cbObj[6 * (size_t)obj + 3 + k], f2key(cmax[k]));
-    }
-}
-
-__global__ __launch_bounds__(kB) void k_cbounds_init(int nObjects, unsigned *__restrict__ cbObj) {
-    const int i = blockIdx.x * kB + threadIdx.x;
-    if (i < 6 * nObjects) cbObj[i] = (i % 6) < 3 ? 0xffffffffu : 0u;  // min keys all-ones, max keys 0
-}
-
-// k_morton against the object's own centroid bounds (the mx > mn guard per object and per axis), the object number
-// above the 30 code bits
-__global__ __launch_bounds__(kB) void k_morton_forest(const Box6 *__restrict__ pb, const unsigned *__restrict__ cbObj,
-                                                      const int *__restrict__ objOf, int n,
-                                                      unsigned long long *__restrict__ keys, int *__restrict__ idx) {
-    for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) {
-        const Box6 b = pb[i];
-        const int obj = objOf[i];
-        const unsigned *cb = cbObj + 6 * (size_t)obj;
-        unsigned q[3];
-        for (int k = 0; k < 3; ++k) {
-            const float mn = key2f(cb[k]), mx = key2f(cb[3 + k]);
-            const float c = .5f * b.mn[k] + .5f * b.mx[k];
-            float o = c - mn;
-            if (mx > mn) o /= mx - mn;
-            q[k] = (unsigned)(o * 1024.0f);  // mortonScale = 1 << 10
-        }
-        const unsigned code = (left_shift3(q[2]) << 2) | (left_shift3(q[1]) << 1) | left_shift3(q[0]);
-        keys[i] = ((unsigned long long)obj << 30) | code;
-        idx[i] = i;
-    }
-}
-
-// k_classify, reporting an oversized leaf with its object (errObj[kErrLeafSize], lowest object wins)
-__global__ __launch_bounds__(kB) void k_classify_forest(int m, int maxPrims, const int *__restrict__ pstart,
-                                                        const int *__restrict__ firstA, const int *__restrict__ lastA,
-                                                        const unsigned char *__restrict__ bit,
-                                                        const int *__restrict__ parentV,
-                                                        const unsigned long long *__restrict__ ukey,
-                                                        unsigned char *__restrict__ kind, int *__restrict__ leafHead,
-                                                        int *__restrict__ treeletHead, int *errObj) {
-    const int v = blockIdx.x * kB + threadIdx.x;
-    if (v >= 2 * m - 1) return;
-    const bool internal = v < m - 1;
-    const int first = internal ? firstA[v] : v - (m - 1);
-    const int last = internal ? lastA[v] : first;
-    const int n = pstart[last + 1] - pstart[first];
-    const int p = parentV[v];
-    const bool inTreelet = !internal || bit[v] < kTreeletBit;
-    const bool parentInTreelet = p >= 0 && bit[p] < kTreeletBit;
-    const bool treeletRoot = inTreelet && !parentInTreelet;
-    const bool realInterior = internal && inTreelet && n >= maxPrims;
-    bool parentInterior = false;
-    if (parentInTreelet) parentInterior = pstart[lastA[p] + 1] - pstart[firstA[p]] >= maxPrims;
-    const bool realLeaf = inTreelet && !realInterior && (treeletRoot || parentInterior);
-    kind[v] = (realInterior ? kRealInterior : 0) | (realLeaf ? kRealLeaf : 0) | (treeletRoot ? kTreeletRoot : 0);
-    if (realLeaf) {
-        leafHead[first] = 1;
-        if (n > 65535) atomicMin(&errObj[kErrLeafSize], (int)(ukey[first] >> 30));
-    }
-    if (treeletRoot) treeletHead[first] = 1;
-}
-
-// k_treelets with the treelet's object: the forest's treelets are numbered object after object, Morton order inside
-__global__ __launch_bounds__(kB) void k_treelets_forest(int m, const unsigned char *__restrict__ kind,
-                                                        const int *__restrict__ firstA, const int *__restrict__ lastA,
-                                                        const int *__restrict__ leafOrd, const int *__restrict__ treeOrd,
-                                                        const Box6 *__restrict__ nodeBox,
-                                                        const unsigned long long *__restrict__ ukey, int tCap,
-                                                        Box6 *__restrict__ tbox, int *__restrict__ tsize,
-                                                        int *__restrict__ tobj) {
-    const int v = blockIdx.x * kB + threadIdx.x;
-    if (v >= 2 * m - 1 || !(kind[v] & kTreeletRoot)) return;
-    const int first = v < m - 1 ? firstA[v] : v - (m - 1);
-    const int t = treeOrd[first];
-    if (t >= tCap) return;  // cannot happen: at most min(m, 4096 per object) treelets
-    tbox[t] = nodeBox[v];
-    tsize[t] = subtree_size(v, m, kind, firstA, lastA, leafOrd);
-    tobj[t] = (int)(ukey[first] >> 30);
-}
-
-// k_emit for trees laid out one after another: tbase[t] already includes the tree's node_first; a second child
-// counts from its own tree's root, a leaf's first primitive from its object's first primitive, the depth is the
-// object's own maximum
-__global__ __launch_bounds__(kB) void k_emit_forest(int m, const unsigned char *__restrict__ kind,
-                                                    const unsigned char *__restrict__ bit,
-                                                    const int *__restrict__ pstart, const int *__restrict__ firstA,
-                                                    const int *__restrict__ lastA, const int *__restrict__ leftV,
-                                                    const int *__restrict__ parentV, const int *__restrict__ leafOrd,
-                                                    const int *__restrict__ treeOrd, const int *__restrict__ tbase,
-                                                    const int *__restrict__ tdepth, const int *__restrict__ tobj,
-                                                    const int *__restrict__ nodeFirst,
-                                                    const int *__restrict__ objectFirst, const Box6 *__restrict__ nodeBox,
-                                                    nnbvh_linear_node *__restrict__ nodes, int *depthObj) {
-    const int v = blockIdx.x * kB + threadIdx.x;
-    if (v >= 2 * m - 1 || !(kind[v] & (kRealInterior | kRealLeaf))) return;
-    const bool internal = v < m - 1;
-    const int first = internal ? firstA[v] : v - (m - 1);
-    const int last = internal ? lastA[v] : first;
-    int cur = v, leftTurns = 0, depth = 0;
-    while (!(kind[cur] & kTreeletRoot)) {
-        const int p = parentV[cur];
-        leftTurns += (leftV[p] == cur) ? 1 : 0;
-        ++depth;
-        cur = p;
-    }
-    const int rootFirst = cur < m - 1 ? firstA[cur] : cur - (m - 1);
-    const int t = treeOrd[rootFirst];
-    const int obj = tobj[t];
-    const int flat = tbase[t] + 2 * (leafOrd[first] - leafOrd[rootFirst]) + leftTurns;
-    const Box6 b = nodeBox[v];
-    nnbvh_linear_node out;
-    for (int k = 0; k < 3; ++k) {
-        out.pmin[k] = b.mn[k];
-        out.pmax[k] = b.mx[k];
-    }
-    out.pad = 0;
-    if (kind[v] & kRealLeaf) {
-        out.offset = pstart[first] - objectFirst[obj];
-        out.nprims = (uint16_t)(pstart[last + 1] - pstart[first]);
-        out.axis = 0;
-        const int d = tdepth[t] + depth;
-        if (depthObj[obj] < d) atomicMax(&depthObj[obj], d);  // (the plain read spares most leaves the atomic)
-    } else {
-        out.offset = flat + 1 + subtree_size(leftV[v], m, kind, firstA, lastA, leafOrd) - nodeFirst[obj];
-        out.nprims = 0;
-        out.axis = (uint8_t)(bit[v] % 3);  // :499
-    }
-    nodes[flat] = out;
 }
 
 __global__ __launch_bounds__(kB) void k_iota(int n, int *__restrict__ perm) {
@@ -786,11 +673,10 @@ struct RestoreDevice {
     ~RestoreDevice() { (void)hipSetDevice(d); }
 };
 
-}  // namespace
-
-bool gpu_hlbvh(const nnbvh_prim *prims, int n, const float *verts, int n_verts,
-               const float *prim_bounds, int max_prims_in_node, int device, GpuBuildResult *out,
-               std::string *error) {
+// gpu_hlbvh / gpu_sah: upload, the device-resident core, hand over or download
+typedef bool (*DeviceCore)(const DeviceBuildInput &, GpuBuildResult *, std::string *);
+bool build_uploaded(DeviceCore core, const nnbvh_prim *prims, int n, const float *verts, int n_verts,
+                    const float *prim_bounds, int max_prims_in_node, int device, GpuBuildResult *out, std::string *error) {
     int prev = 0;
     GB_CHECK(hipGetDevice(&prev), "hipGetDevice");
     GB_CHECK(hipSetDevice(device), "hipSetDevice");
@@ -808,169 +694,29 @@ bool gpu_hlbvh(const nnbvh_prim *prims, int n, const float *verts, int n_verts,
     in.n_verts = n_verts;
     in.d_prim_bounds = up.bounds;
     in.max_prims_in_node = max_prims_in_node;
-    if (!gpu_hlbvh_device(in, out, error)) return false;
+    if (!core(in, out, error)) return false;
     t0 = std::chrono::steady_clock::now();
     const bool ok = finish_build(mem, up, n, out, error);
     out->ms[4] = ms_since(t0);
     return ok;
 }
 
-bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error) {
-    const int n = in.n_prims, n_verts = in.n_verts;
-    const nnbvh_prim *dPrims = in.d_prims;
-    const float *dVerts = in.d_verts, *dCaller = in.d_prim_bounds;
-    const int maxPrims = std::min(255, in.max_prims_in_node);  // aggregates.cpp:142
-    hipStream_t stream = (hipStream_t)in.stream;
-    DevMem mem, outMem;  // outMem: the result arrays this call allocates itself
-    mem.error = outMem.error = error;
-    mem.pool = in.pool;
-
-    auto t0 = std::chrono::steady_clock::now();
-    Box6 *dPb = mem.get<Box6>(n);
-    unsigned *dCodes = mem.get<unsigned>(n), *dCodesS = mem.get<unsigned>(n);
-    int *dIdx = mem.get<int>(n), *dIdxS = mem.get<int>(n);
-    int *dHead = mem.get<int>(n), *dExcl = mem.get<int>(n);
-    int *dPstart = mem.get<int>((size_t)n + 1);
-    unsigned *dUcode = mem.get<unsigned>(n);
-    int *dScalars = mem.get<int>(16);  // [0..5] centroid-bound keys, 6 err, 7 m, 8 maxDepth
-    if (!mem.ok) return false;
-    const int init[16] = {-1, -1, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // min keys all-ones, max keys 0
-    GB_CHECK(hipMemcpyAsync(dScalars, init, sizeof init, hipMemcpyHostToDevice, stream), "init scalars");
-    unsigned *dCb = (unsigned *)dScalars;
-    int *dErr = dScalars + 6, *dM = dScalars + 7, *dMaxDepth = dScalars + 8;
-    hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(n, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts,
-                       dCaller, n, dPb, dCb, dErr, (const int *)nullptr, 0, (int *)nullptr);
-    hipLaunchKernelGGL(k_morton, dim3(grid_for(n)), dim3(kB), 0, stream, dPb, dCb, n, dCodes, dIdx);
-    size_t tmpBytes = 0, scanBytes = 0;
-    GB_CHECK(rocprim::radix_sort_pairs(nullptr, tmpBytes, dCodes, dCodesS, dIdx, dIdxS, (size_t)n, 0u, 30u, stream),
-             "radix sort (size query)");
-    GB_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, dHead, dExcl, 0, (size_t)n + 1, rocprim::plus<int>(), stream),
-             "scan (size query)");
-    void *dTmp = mem.get<char>(std::max(tmpBytes, scanBytes));
-    if (!mem.ok) return false;
-    GB_CHECK(rocprim::radix_sort_pairs(dTmp, tmpBytes, dCodes, dCodesS, dIdx, dIdxS, (size_t)n, 0u, 30u, stream),
-             "radix sort");
-    hipLaunchKernelGGL(k_heads<unsigned>, dim3(grid_for(n)), dim3(kB), 0, stream, dCodesS, n, dHead);
-    GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dHead, dExcl, 0, (size_t)n, rocprim::plus<int>(), stream), "scan");
-    hipLaunchKernelGGL(k_compact<unsigned>, dim3(grid_for(n)), dim3(kB), 0, stream, dCodesS, dHead, dExcl, n, dPstart, dUcode, dM);
-    int scal[16];
-    GB_CHECK(hipMemcpyAsync(scal, dScalars, sizeof scal, hipMemcpyDeviceToHost, stream), "read scalars");
-    GB_CHECK(hipStreamSynchronize(stream), "sync after sort");
-    if (scal[6] != 0) {
-        *error = scal[6] == kErrVertex       ? "nnbvh_build_create: vertex index out of range"
-                 : scal[6] == kErrNeedBounds ? "nnbvh_build_create: instance / host primitives need prim_bounds"
-                 : scal[6] == kErrNonFinite  ? "nnbvh_build_create: non-finite vertex or primitive bounds"
-                                             : "nnbvh_build_create: unknown primitive kind";
-        return false;
-    }
-    const int m = scal[7];
-    out->n_unique_codes = m;
-    const int nv = 2 * m - 1;
-
-    int *dFirst = mem.get<int>(m), *dLast = mem.get<int>(m), *dLeft = mem.get<int>(m), *dRight = mem.get<int>(m);
-    unsigned char *dBit = mem.get<unsigned char>(m), *dKind = mem.get<unsigned char>(nv);
-    int *dParent = mem.get<int>(nv);
-    int *dLeafHead = mem.get<int>((size_t)m + 1), *dTreeHead = mem.get<int>((size_t)m + 1);
-    int *dLeafOrd = mem.get<int>((size_t)m + 1), *dTreeOrd = mem.get<int>((size_t)m + 1);
-    Box6 *dNodeBox = mem.get<Box6>(nv);
-    Box6 *dTbox = mem.get<Box6>(4096);
-    int *dTsize = mem.get<int>(4096), *dTbase = mem.get<int>(4096), *dTdepth = mem.get<int>(4096);
-    if (!mem.ok) return false;
-    GB_CHECK(hipMemsetAsync(dParent, 0xff, (size_t)nv * sizeof(int), stream), "memset parents");  // -1: the root
-    GB_CHECK(hipMemsetAsync(dLeafHead, 0, ((size_t)m + 1) * sizeof(int), stream), "memset");
-    GB_CHECK(hipMemsetAsync(dTreeHead, 0, ((size_t)m + 1) * sizeof(int), stream), "memset");
-    if (m > 1)
-        hipLaunchKernelGGL(k_karras<unsigned>, dim3(grid_all(m - 1)), dim3(kB), 0, stream, dUcode, m, dFirst, dLast, dLeft,
-                           dRight, dBit, dParent);
-    hipLaunchKernelGGL(k_classify, dim3(grid_all(nv)), dim3(kB), 0, stream, m, maxPrims, dPstart, dFirst, dLast, dBit,
-                       dParent, dKind, dLeafHead, dTreeHead, dErr);
-    GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dLeafHead, dLeafOrd, 0, (size_t)m + 1, rocprim::plus<int>(), stream),
-             "scan leaves");
-    GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dTreeHead, dTreeOrd, 0, (size_t)m + 1, rocprim::plus<int>(), stream),
-             "scan treelets");
-    hipLaunchKernelGGL(k_leaf_bounds, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dPstart, dFirst, dLast, dIdxS,
-                       dPb, dNodeBox);
-    hipLaunchKernelGGL(k_big_leaf_bounds, dim3((nv + kB / 64 - 1) / (kB / 64)), dim3(kB), 0, stream, m, dKind, dPstart,
-                       dFirst, dLast, dIdxS, dPb, dNodeBox);
-    if (m > 1)
-        for (int level = 0; level < kTreeletBit; ++level)
-            hipLaunchKernelGGL(k_interior_bounds, dim3(grid_all(m - 1)), dim3(kB), 0, stream, m, level, dKind, dBit,
-                               dLeft, dRight, dNodeBox);
-    hipLaunchKernelGGL(k_treelets, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dFirst, dLast, dLeafOrd, dTreeOrd,
-                       dNodeBox, dTbox, dTsize);
-    int nTreelets = 0, errNow = 0;
-    GB_CHECK(hipMemcpyAsync(&nTreelets, dTreeOrd + m, sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet count");
-    GB_CHECK(hipMemcpyAsync(&errNow, dErr, sizeof(int), hipMemcpyDeviceToHost, stream), "read error flag");
-    GB_CHECK(hipStreamSynchronize(stream), "sync after classify");
-    if (errNow == kErrLeafSize) {
-        *error = "nnbvh_build_create: more than 65535 primitives share one Morton code (leaf too large)";
-        return false;
-    }
-    if (nTreelets < 1 || nTreelets > 4096) {
-        *error = "gpu build: internal error (treelet count)";
-        return false;
-    }
-    std::vector<float> tbox(6 * (size_t)nTreelets);
-    std::vector<int> tsize(nTreelets);
-    GB_CHECK(hipMemcpy(tbox.data(), dTbox, tbox.size() * sizeof(float), hipMemcpyDeviceToHost), "read treelet bounds");
-    GB_CHECK(hipMemcpy(tsize.data(), dTsize, tsize.size() * sizeof(int), hipMemcpyDeviceToHost), "read treelet sizes");
-    out->n_treelets = nTreelets;
-    out->ms[1] = ms_since(t0);
-    if (std::getenv("NNBVH_BUILD_DEBUG")) {
-        int nLeaves = 0;
-        (void)hipMemcpy(&nLeaves, dLeafOrd + m, sizeof(int), hipMemcpyDeviceToHost);
-        std::fprintf(stderr, "gpu build: n %d, distinct codes %d, leaves %d, treelets %d\n", n, m, nLeaves, nTreelets);
-        for (int t = 0; t < std::min(nTreelets, 4); ++t)
-            std::fprintf(stderr, "  treelet %d: size %d box %g %g %g  %g %g %g\n", t, tsize[t], tbox[6 * t], tbox[6 * t + 1],
-                         tbox[6 * t + 2], tbox[6 * t + 3], tbox[6 * t + 4], tbox[6 * t + 5]);
-    }
-    for (int t = 0; t < nTreelets; ++t) {
-        bool fine = tsize[t] >= 1 && (tsize[t] & 1);
-        for (int k = 0; k < 6; ++k) fine = fine && std::isfinite(tbox[6 * (size_t)t + k]);
-        if (!fine) {
-            *error = "nnbvh_build_create: non-finite primitive bounds (or internal error) in treelet " + std::to_string(t);
-            return false;
-        }
-    }
-
-    t0 = std::chrono::steady_clock::now();
-    UpperLayout up;
-    if (!hlbvh_upper_layout(tbox.data(), tsize.data(), nTreelets, &up, error)) return false;
-    out->ms[2] = ms_since(t0);
-
-    t0 = std::chrono::steady_clock::now();
-    nnbvh_linear_node *dNodes = in.d_nodes_out ? in.d_nodes_out : outMem.get<nnbvh_linear_node>(up.total_nodes);
-    nnbvh_prim *dOrdered = in.d_ordered_out ? in.d_ordered_out : outMem.get<nnbvh_prim>(n);
-    if (!outMem.ok) return false;
-    GB_CHECK(hipMemcpyAsync(dTbase, up.base.data(), nTreelets * sizeof(int), hipMemcpyHostToDevice, stream), "copy bases");
-    GB_CHECK(hipMemcpyAsync(dTdepth, up.depth.data(), nTreelets * sizeof(int), hipMemcpyHostToDevice, stream), "copy depths");
-    hipLaunchKernelGGL(k_emit, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dBit, dPstart, dFirst, dLast, dLeft,
-                       dParent, dLeafOrd, dTreeOrd, dTbase, dTdepth, dNodeBox, dNodes, dMaxDepth);
-    hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kB), 0, stream, dPrims, dIdxS, n, dOrdered);
-    // the upper nodes join the device array
-    if (!up.upper_index.empty()) {
-        int *dUi = mem.get<int>(up.upper_index.size());
-        nnbvh_linear_node *dUn = mem.get<nnbvh_linear_node>(up.upper_nodes.size());
-        if (!mem.ok) return false;
-        GB_CHECK(hipMemcpyAsync(dUi, up.upper_index.data(), up.upper_index.size() * sizeof(int), hipMemcpyHostToDevice, stream), "copy upper");
-        GB_CHECK(hipMemcpyAsync(dUn, up.upper_nodes.data(), up.upper_nodes.size() * sizeof(nnbvh_linear_node), hipMemcpyHostToDevice, stream), "copy upper");
-        hipLaunchKernelGGL(k_scatter_nodes, dim3(grid_all((long)up.upper_index.size())), dim3(kB), 0, stream, dUi, dUn,
-                           (int)up.upper_index.size(), dNodes);
-    }
-    out->depth = 0;
-    GB_CHECK(hipMemcpyAsync(&out->depth, dMaxDepth, sizeof(int), hipMemcpyDeviceToHost, stream), "read depth");
-    GB_CHECK(hipGetLastError(), "kernel launch");
-    GB_CHECK(hipStreamSynchronize(stream), "sync after emit");
-    out->ms[3] = ms_since(t0);
-    out->total_nodes = up.total_nodes;
-    out->d_nodes = dNodes;
-    out->d_ordered = dOrdered;
-    outMem.release(dNodes);
-    outMem.release(dOrdered);
+// gpu_hlbvh_device / gpu_sah_device: one tree = a forest of one object.  codes: the member that n_unique_codes reports
+typedef bool (*ForestCore)(const DeviceBuildInput &, const int *, int, ForestBuildResult *, std::string *);
+bool build_one_object(ForestCore forest, int ForestBuildResult::*codes, const DeviceBuildInput &in, GpuBuildResult *out,
+                      std::string *error) {
+    const int object_first[2] = {0, in.n_prims};
+    ForestBuildResult f;
+    if (!forest(in, object_first, 1, &f, error)) return false;
+    out->d_nodes = f.d_nodes;
+    out->d_ordered = f.d_ordered;
+    out->total_nodes = f.total_nodes;
+    out->depth = f.depth[0];
+    for (int k = 1; k <= 3; ++k) out->ms[k] = f.ms[k];
+    out->n_treelets = f.n_subtrees;
+    out->n_unique_codes = f.*codes;
     return true;
 }
-
-namespace {
 
 // What a loop of one-object builds would have reported: the failure of the lowest-numbered object, and within one
 // object the first in the order of the phases.  The forest builders call it in that order, so a tie keeps the earlier.
@@ -998,9 +744,7 @@ bool check_object_first(const int *objectFirst, int nObjects, int nAll, std::str
     return true;
 }
 
-}  // namespace
-
-// The HLBVH trees of many objects in one pass: the pipeline of gpu_hlbvh_device over the sort key (object << 30) | code.
+// The HLBVH pipeline (the ten steps at the top of this file) over the sort key (object << 30) | code.
 // ONE stable radix sort over the bits in use orders every object's primitives by their 30 code bits without moving one
 // across an object boundary; a run of identical keys, a treelet (equal bits >= 18) and a radix-tree range all end
 // where the object does, because the object number is part of the key; the objects themselves hang off radix nodes that
@@ -1008,10 +752,13 @@ bool check_object_first(const int *objectFirst, int nObjects, int nAll, std::str
 // one launch for the whole forest, and the upper SAH runs on the host per object over one table of treelets.
 // A malformed object's primitives run through the pipeline like any others (no kernel indexes with a coordinate); only
 // its messages count, and only if no lower-numbered object has one.
-bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst, int nObjects, ForestBuildResult *out,
-                             std::string *error) {
+// Key = unsigned serves one object alone: its keys are its codes, sorted over bits 0 .. 29 at half the 64-bit key's
+// traffic; k_prim_bounds' centroid bounds of the whole input are the object's, so k_cbounds_init and k_object_cbounds
+// are not launched.
+template <typename Key>
+bool hlbvh_forest(const DeviceBuildInput &in, const int *objectFirst, int nObjects, ForestBuildResult *out,
+                  std::string *error) {
     const int n = in.n_prims, n_verts = in.n_verts;
-    if (!check_object_first(objectFirst, nObjects, n, error)) return false;
     const nnbvh_prim *dPrims = in.d_prims;
     const float *dVerts = in.d_verts, *dCaller = in.d_prim_bounds;
     const int maxPrims = std::min(255, in.max_prims_in_node);  // aggregates.cpp:142
@@ -1020,7 +767,7 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
     mem.error = outMem.error = error;
     mem.pool = in.pool;
     Refusal refuse;
-    typedef unsigned long long Key;
+    const bool many = nObjects > 1;
     int objectBits = 0;
     while (objectBits < 31 && ((long)nObjects - 1) >> objectBits) ++objectBits;
     const unsigned endBit = 30u + (unsigned)objectBits;
@@ -1028,27 +775,33 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
     auto t0 = std::chrono::steady_clock::now();
     Box6 *dPb = mem.get<Box6>(n);
     Key *dKeys = mem.get<Key>(n), *dKeysS = mem.get<Key>(n), *dUkey = mem.get<Key>(n);
-    int *dIdx = mem.get<int>(n), *dIdxS = mem.get<int>(n), *dObjOf = mem.get<int>(n);
+    int *dIdx = mem.get<int>(n), *dIdxS = mem.get<int>(n);
     int *dHead = mem.get<int>(n), *dExcl = mem.get<int>(n);
     int *dPstart = mem.get<int>((size_t)n + 1);
-    int *dObjectFirst = mem.get<int>((size_t)nObjects + 1);
-    unsigned *dCbObj = mem.get<unsigned>(6 * (size_t)nObjects);
-    int *dDepthObj = mem.get<int>(nObjects);
-    int *dScalars = mem.get<int>(8 + kErrWords);  // [0..5] k_prim_bounds' whole-forest centroid keys (unused), 7 m, [8..] errObj
+    // one block, one upload: [0..5] k_prim_bounds' centroid keys of the whole input, 7 m, [8..] errObj | object_first |
+    // the objects' depths, from the next 128-byte line on: k_emit's atomics go there while every leaf reads object_first
+    constexpr int kScalars = 8 + kErrWords;
+    const size_t depthAt = (kScalars + (size_t)nObjects + 1 + 31) / 32 * 32;
+    int *dScalars = mem.get<int>(depthAt + (size_t)nObjects);
+    int *dObjectFirst = dScalars + kScalars, *dDepthObj = dScalars + depthAt;
+    // the objects' centroid keys and every primitive's object: one object's are dScalars[0..5] and 0
+    unsigned *dCbObj = many ? mem.get<unsigned>(6 * (size_t)nObjects) : (unsigned *)dScalars;
+    int *dObjOf = many ? mem.get<int>(n) : nullptr;
     if (!mem.ok) return false;
-    int init[8 + kErrWords] = {-1, -1, -1, 0, 0, 0, 0, 0};
+    std::vector<int> init(depthAt + (size_t)nObjects, 0);
+    init[0] = init[1] = init[2] = -1;  // min keys all-ones, max keys 0
     for (int k = 1; k < kErrWords; ++k) init[8 + k] = kNoObject;
-    GB_CHECK(hipMemcpyAsync(dScalars, init, sizeof init, hipMemcpyHostToDevice, stream), "init scalars");
-    GB_CHECK(hipMemcpyAsync(dObjectFirst, objectFirst, ((size_t)nObjects + 1) * sizeof(int), hipMemcpyHostToDevice, stream),
-             "copy object_first");
-    GB_CHECK(hipMemsetAsync(dDepthObj, 0, (size_t)nObjects * sizeof(int), stream), "memset depths");
+    std::copy(objectFirst, objectFirst + nObjects + 1, init.begin() + kScalars);
+    GB_CHECK(hipMemcpyAsync(dScalars, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice, stream), "init scalars");
     int *dM = dScalars + 7, *dErrObj = dScalars + 8;
     hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(n, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts, dCaller, n, dPb,
-                       (unsigned *)dScalars, (int *)nullptr, (const int *)dObjectFirst, nObjects, dErrObj);
-    hipLaunchKernelGGL(k_cbounds_init, dim3(grid_all(6L * nObjects)), dim3(kB), 0, stream, nObjects, dCbObj);
-    hipLaunchKernelGGL(k_object_cbounds, dim3(grid_all(n)), dim3(kB), 0, stream, dPb, dObjectFirst, nObjects, n, dObjOf,
-                       dCbObj);
-    hipLaunchKernelGGL(k_morton_forest, dim3(grid_for(n)), dim3(kB), 0, stream, dPb, dCbObj, dObjOf, n, dKeys, dIdx);
+                       (unsigned *)dScalars, (const int *)dObjectFirst, nObjects, dErrObj);
+    if (many) {
+        hipLaunchKernelGGL(k_cbounds_init, dim3(grid_all(6L * nObjects)), dim3(kB), 0, stream, nObjects, dCbObj);
+        hipLaunchKernelGGL(k_object_cbounds, dim3(grid_all(n)), dim3(kB), 0, stream, dPb, dObjectFirst, nObjects, n, dObjOf,
+                           dCbObj);
+    }
+    hipLaunchKernelGGL(k_morton<Key>, dim3(grid_for(n)), dim3(kB), 0, stream, dPb, dCbObj, dObjOf, n, dKeys, dIdx);
     size_t tmpBytes = 0, scanBytes = 0;
     GB_CHECK(rocprim::radix_sort_pairs(nullptr, tmpBytes, dKeys, dKeysS, dIdx, dIdxS, (size_t)n, 0u, endBit, stream),
              "radix sort (size query)");
@@ -1060,7 +813,7 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
     hipLaunchKernelGGL(k_heads<Key>, dim3(grid_for(n)), dim3(kB), 0, stream, dKeysS, n, dHead);
     GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dHead, dExcl, 0, (size_t)n, rocprim::plus<int>(), stream), "scan");
     hipLaunchKernelGGL(k_compact<Key>, dim3(grid_for(n)), dim3(kB), 0, stream, dKeysS, dHead, dExcl, n, dPstart, dUkey, dM);
-    int scal[8 + kErrWords];
+    int scal[kScalars];
     GB_CHECK(hipMemcpyAsync(scal, dScalars, sizeof scal, hipMemcpyDeviceToHost, stream), "read scalars");
     GB_CHECK(hipStreamSynchronize(stream), "sync after sort");
     const int *errWords = scal + 8;
@@ -1095,7 +848,7 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
     if (m > 1)
         hipLaunchKernelGGL(k_karras<Key>, dim3(grid_all(m - 1)), dim3(kB), 0, stream, dUkey, m, dFirst, dLast, dLeft, dRight,
                            dBit, dParent);
-    hipLaunchKernelGGL(k_classify_forest, dim3(grid_all(nv)), dim3(kB), 0, stream, m, maxPrims, dPstart, dFirst, dLast, dBit,
+    hipLaunchKernelGGL(k_classify<Key>, dim3(grid_all(nv)), dim3(kB), 0, stream, m, maxPrims, dPstart, dFirst, dLast, dBit,
                        dParent, dUkey, dKind, dLeafHead, dTreeHead, dErrObj);
     GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dLeafHead, dLeafOrd, 0, (size_t)m + 1, rocprim::plus<int>(), stream),
              "scan leaves");
@@ -1109,7 +862,7 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
         for (int level = 0; level < kTreeletBit; ++level)
             hipLaunchKernelGGL(k_interior_bounds, dim3(grid_all(m - 1)), dim3(kB), 0, stream, m, level, dKind, dBit, dLeft,
                                dRight, dNodeBox);
-    hipLaunchKernelGGL(k_treelets_forest, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dFirst, dLast, dLeafOrd,
+    hipLaunchKernelGGL(k_treelets<Key>, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dFirst, dLast, dLeafOrd,
                        dTreeOrd, dNodeBox, dUkey, tCap, dTbox, dTsize, dTobj);
     int nTreelets = 0, leafSizeObject = kNoObject;
     GB_CHECK(hipMemcpyAsync(&nTreelets, dTreeOrd + m, sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet count");
@@ -1125,7 +878,8 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
     std::vector<int> tsize(nTreelets), tobj(nTreelets);
     GB_CHECK(hipMemcpyAsync(tbox.data(), dTbox, tbox.size() * sizeof(float), hipMemcpyDeviceToHost, stream), "read treelet bounds");
     GB_CHECK(hipMemcpyAsync(tsize.data(), dTsize, tsize.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet sizes");
-    GB_CHECK(hipMemcpyAsync(tobj.data(), dTobj, tobj.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet objects");
+    if (many)  // (one object: every treelet is object 0's)
+        GB_CHECK(hipMemcpyAsync(tobj.data(), dTobj, tobj.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet objects");
     GB_CHECK(hipStreamSynchronize(stream), "sync after treelets");
     out->ms[1] = ms_since(t0);
 
@@ -1188,7 +942,7 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
     const int *dTbase = dTable, *dTdepth = dTable + nTreelets, *dNodeFirst = dTable + 2 * (size_t)nTreelets;
     const int *dUi = dNodeFirst + nObjects + 1;
     GB_CHECK(hipMemcpyAsync(dTable, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, stream), "copy layout");
-    hipLaunchKernelGGL(k_emit_forest, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dBit, dPstart, dFirst, dLast, dLeft,
+    hipLaunchKernelGGL(k_emit, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dBit, dPstart, dFirst, dLast, dLeft,
                        dParent, dLeafOrd, dTreeOrd, dTbase, dTdepth, dTobj, dNodeFirst, dObjectFirst, dNodeBox, dNodes,
                        dDepthObj);
     hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kB), 0, stream, dPrims, dIdxS, n, dOrdered);
@@ -1209,7 +963,25 @@ bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst,
     out->n_levels = 0;
     out->n_subtrees = nTreelets;
     out->n_upper = (int)nUpper;
+    out->n_codes = m;
     return true;
+}
+
+}  // namespace
+
+bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *objectFirst, int nObjects, ForestBuildResult *out,
+                             std::string *error) {
+    if (!check_object_first(objectFirst, nObjects, in.n_prims, error)) return false;
+    return (nObjects == 1 ? hlbvh_forest<unsigned> : hlbvh_forest<unsigned long long>)(in, objectFirst, nObjects, out, error);
+}
+
+bool gpu_hlbvh_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error) {
+    return build_one_object(gpu_hlbvh_forest_device, &ForestBuildResult::n_codes, in, out, error);
+}
+
+bool gpu_hlbvh(const nnbvh_prim *prims, int n, const float *verts, int n_verts, const float *prim_bounds,
+               int max_prims_in_node, int device, GpuBuildResult *out, std::string *error) {
+    return build_uploaded(gpu_hlbvh_device, prims, n, verts, n_verts, prim_bounds, max_prims_in_node, device, out, error);
 }
 
 // =================================================================================================
@@ -1931,43 +1703,11 @@ struct HostNode {  // a phase-A node
 
 bool gpu_sah(const nnbvh_prim *prims, int n, const float *verts, int n_verts, const float *prim_bounds,
              int max_prims_in_node, int device, GpuBuildResult *out, std::string *error) {
-    int prev = 0;
-    GB_CHECK(hipGetDevice(&prev), "hipGetDevice");
-    GB_CHECK(hipSetDevice(device), "hipSetDevice");
-    RestoreDevice restore{prev};
-    DevMem mem;
-    mem.error = error;
-    auto t0 = std::chrono::steady_clock::now();
-    Uploaded up;
-    if (!upload_build_input(mem, prims, n, verts, n_verts, prim_bounds, &up, error)) return false;
-    out->ms[0] = ms_since(t0);
-    DeviceBuildInput in;
-    in.d_prims = up.prims;
-    in.n_prims = n;
-    in.d_verts = up.verts;
-    in.n_verts = n_verts;
-    in.d_prim_bounds = up.bounds;
-    in.max_prims_in_node = max_prims_in_node;
-    if (!gpu_sah_device(in, out, error)) return false;
-    t0 = std::chrono::steady_clock::now();
-    const bool ok = finish_build(mem, up, n, out, error);
-    out->ms[4] = ms_since(t0);
-    return ok;
+    return build_uploaded(gpu_sah_device, prims, n, verts, n_verts, prim_bounds, max_prims_in_node, device, out, error);
 }
 
-// one tree = a forest of one object
 bool gpu_sah_device(const DeviceBuildInput &in, GpuBuildResult *out, std::string *error) {
-    const int object_first[2] = {0, in.n_prims};
-    ForestBuildResult f;
-    if (!gpu_sah_forest_device(in, object_first, 1, &f, error)) return false;
-    out->d_nodes = f.d_nodes;
-    out->d_ordered = f.d_ordered;
-    out->total_nodes = f.total_nodes;
-    out->depth = f.depth[0];
-    for (int k = 1; k <= 3; ++k) out->ms[k] = f.ms[k];
-    out->n_treelets = f.n_subtrees;
-    out->n_unique_codes = f.n_upper;
-    return true;
+    return build_one_object(gpu_sah_forest_device, &ForestBuildResult::n_upper, in, out, error);
 }
 
 bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *objectFirst, int nObjects, ForestBuildResult *out,
@@ -2002,7 +1742,7 @@ bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *objectFirst, i
              "copy object_first");
     int *dErrObj = dScalars + 8;
     hipLaunchKernelGGL(k_prim_bounds, dim3(grid_for(nAll, 1024)), dim3(kB), 0, stream, dPrims, dVerts, n_verts, dCaller, nAll,
-                       dPb, (unsigned *)dScalars, (int *)nullptr, (const int *)dObjectFirst, nObjects, dErrObj);
+                       dPb, (unsigned *)dScalars, (const int *)dObjectFirst, nObjects, dErrObj);
     hipLaunchKernelGGL(k_iota, dim3(grid_for(nAll)), dim3(kB), 0, stream, nAll, dPerm);
     size_t scanBytes = 0;
     GB_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, dLfFlag, dLfScan, 0, (size_t)nAll + 1, rocprim::plus<int>(), stream),

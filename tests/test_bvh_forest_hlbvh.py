@@ -186,6 +186,20 @@ def test_hlbvh_neighbours_do_not_leak_in_either_order(max_prims):
     small = build_hlbvh_forest_gpu([objects[k] for k in keep], verts, max_prims)
     assert_forest_is_the_host_trees(small, [hosts[k] for k in keep], "small objects only")
     assert len(keep) > 250 and small.n_levels == 0 and small.n_subtrees >= len(keep)
+    # the two key widths: one object alone sorts its 32-bit codes, beside a one-triangle neighbour (before it or
+    # after it) 64-bit keys.  66 of its 70 triangles share a centroid: a leaf folded by a wavefront beside ordinary ones
+    (v, lump), (w, rest) = ss.coincident_centroids(66, 7), ss.random_soup(4, 0, 81, extent=3.0, size=0.4)
+    x = np.concatenate([lump, shifted(rest, len(v))])
+    verts, (x, one) = join([(np.concatenate([v, w]), x), ss.random_soup(1, 0, 79)])
+    host = build_tree(x, verts, max_prims, "hlbvh")
+    leaves = host.nodes["nprims"][host.nodes["nprims"] > 0]
+    assert len(x) == 70 and leaves.max() == 66 and len(leaves) > 1
+    alone = build_tree_gpu(x, verts, max_prims, split_method="hlbvh")
+    first, second = build_hlbvh_forest_gpu([x, one], verts, max_prims)[0], build_hlbvh_forest_gpu([one, x], verts, max_prims)[1]
+    for t, what in ((alone, "alone"), (first, "object 0 of 2"), (second, "object 1 of 2")):
+        assert t.nodes.tobytes() == host.nodes.tobytes(), f"{what}: nodes differ"
+        assert t.ordered_prims.tobytes() == host.ordered_prims.tobytes(), f"{what}: ordered primitives differ"
+        assert t.depth == host.depth, f"{what}: depth {t.depth} vs {host.depth}"
 
 
 # ---- GPU 3: two-level scenes on the forest route, the loop route and the host route --------------------------------
@@ -340,3 +354,22 @@ def test_hlbvh_refusals_are_the_loops(nonfinite_at, lump_at, words, monkeypatch)
         assert text in str(e.value) and "internal error" not in str(e.value), (env, str(e.value))
     monkeypatch.delenv(LOOP)
     good_builds()
+
+
+@pytest.mark.gpu
+def test_two_kinds_of_fault_in_one_object_are_reported_in_one_order(monkeypatch):
+    """A bad vertex index and an unknown kind in one object: the single build, a forest of one and the loop route all
+    name the vertex index, the first in the builders' fixed order of faults."""
+    verts, prims = ss.random_soup(20, 0, 90)
+    prims = prims.copy()
+    prims["v"][3, 1] = len(verts)
+    prims["kind"][11] = 99
+    monkeypatch.setenv(LOOP, "1")
+    for build in (lambda: build_tree_gpu(prims, verts, 4, split_method="hlbvh"),
+                  lambda: build_hlbvh_forest_gpu([prims], verts),
+                  lambda: BVHAggregate.build_two_level_on_device(prims[:0], verts, [prims], [placement(0, np.eye(4)[:3])],
+                                                                 4, "hlbvh")):
+        with pytest.raises(NNBVHError) as e:
+            build()
+        assert "vertex index out of range" in str(e.value) and "unknown primitive kind" not in str(e.value)
+    monkeypatch.delenv(LOOP)

@@ -24,7 +24,13 @@ triangles with 20 000 placements, where the per-object cost of building one tree
 phases of one forest build of the objects alone (build_forest_gpu) and B's peak device memory.
 --split=hlbvh runs the four routes with HLBVH trees (phases of one build_hlbvh_forest_gpu; default output
 profiles/two_level_device_scene_hlbvh.txt); --split=sah is the default.  With single-tree scenes named as well, their
-JSON lines follow as usual (gpu_hlbvh_ms_end_to_end is the single HLBVH build's figure)."""
+JSON lines follow as usual (gpu_hlbvh_ms_end_to_end is the single HLBVH build's figure).
+
+Scenes come from scene.load_scene: the blob data/<name>.npz, or the procedural stand-in of its size where it is absent.
+
+--hlbvh-only: of the single-tree section only build_tree_gpu(prims, verts, 4) (HLBVH), end to end and by phase, 5 rounds
+after a warm-up as median (min .. max); scenes default to killeroos and crown; --hlbvh-out=PATH also writes the table
+(how profiles/hlbvh_one_pipeline.txt was measured, one process per commit)."""
 import json
 import os
 import sys
@@ -303,6 +309,37 @@ def two_level_section(out_path, rounds=5, split="sah"):
     return result
 
 
+def hlbvh_section(names, out_path, rounds=5):
+    lines, result = [], {}
+
+    def stats(ms):
+        return f"{np.median(ms):9.2f} ms  ({min(ms):.2f} .. {max(ms):.2f})"
+
+    for name in names:
+        verts, tris, source = scene.load_scene(name)
+        prims = make_prims(tris)
+        build_tree_gpu(prims, verts, 4)  # warm-up: module load, allocator
+        total, phases = [], []
+        for _ in range(rounds):
+            t0 = time.perf_counter()
+            tree = build_tree_gpu(prims, verts, 4)
+            total.append((time.perf_counter() - t0) * 1e3)
+            phases.append(tree.gpu_ms)
+        lines += [f"{source}: {len(tris)} triangles, {len(tree.nodes)} nodes",
+                  f"  build_tree_gpu, end to end   {stats(total)}"]
+        lines += [f"    {what:26s} {stats([p[k] for p in phases])}"
+                  for k, what in enumerate(("upload", "device sort + tree", "host upper SAH", "emit", "download"))]
+        lines.append("")
+        result[name] = {"end_to_end_ms": total, "phases_ms": phases}
+    text = "\n".join([f"single HLBVH build on the device, {rounds} rounds after a warm-up, median (min .. max)", ""] + lines)
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+    return result
+
+
 flags = [a for a in sys.argv[1:] if a.startswith("--")]
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 kd_out = os.path.join(ROOT, "profiles", "kd_device_scene.txt")
@@ -325,10 +362,11 @@ if "--two-level" in flags or "--two-level-only" in flags:
     out["two_level_scene_create"] = two_level_section(two_level_out, split=split)
 if "--kd" in flags or "--kd-only" in flags:
     out["kd_scene_create"] = kd_section(args or ["bathroom", "crown"], kd_out)
-for name in ([] if "--kd-only" in flags or "--two-level-only" in flags else names):
-    if not os.path.exists(os.path.join(ROOT, "data", name + ".npz")):
-        continue
-    verts, tris = scene.load_blob(name)
+if "--hlbvh-only" in flags:
+    hlbvh_out = [f.split("=", 1)[1] for f in flags if f.startswith("--hlbvh-out=")]
+    out["single_hlbvh_build"] = hlbvh_section(args or ["killeroos", "crown"], hlbvh_out[0] if hlbvh_out else None)
+for name in ([] if "--kd-only" in flags or "--two-level-only" in flags or "--hlbvh-only" in flags else names):
+    verts, tris, _ = scene.load_scene(name)
     prims = make_prims(tris)
 
     def timed(fn, reps):
