@@ -5,7 +5,7 @@
 
 #include "../../include/nnbvh.h"
 #include "nnbvh_internal.h"
-#include "wavefront2.h"
+#include "walk_math.h"
 
 namespace nnbvh {
 
@@ -66,21 +66,10 @@ struct TraceParams {
     int32_t *bHcPrim[kMaxFusedBatches];
     int32_t *bHcInst[kMaxFusedBatches];
     // walk mode (the WALK instances, modes 4 / 5), appended again so that the fields above keep their
-    // kernel-argument offsets: the shading mesh the hit's pi / n come from and the per-item arrays of the walk.  The
-    // batch is rays / n / nDev; a lane's ray index is its work item
+    // kernel-argument offsets: the shading mesh the hit's pi / n come from and the per-item arrays of the walk
+    // (walk_math.h).  The batch is rays / n / nDev; a lane's ray index is its work item
     ShadingMeshDevice wMesh;
-    const uint8_t *wPrimClass;       // WALK 1: class per primitive id, nullable
-    long wNPrimClass;
-    const float4 *wPLight;           // WALK 1: the light point of each item
-    uint8_t *wState;                 // WALK 1: 0 at launch; 1 blocked, 2 the caller's to finish
-    const float *wP1;                // WALK 2: the segment's end point of each item
-    const int32_t *wMaterial;        // WALK 2: the material each item looks for
-    const int32_t *wPrimMaterial;    // WALK 2: material per primitive id, nullable
-    long wNPrimMaterial;
-    OneRandomState wSt;              // WALK 2: PCG32 state and reservoir weights per item
-    float4 *wSelHits, *wSelRays;     // WALK 2: selected hit record and its segment ray per item
-    int wMaxSurfaces;                // Intersect calls an item may make
-    int32_t *wUnfinished;            // nullable: counts the items that would start one more
+    WalkParams walk;
 };
 
 hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream);

@@ -638,7 +638,7 @@ void trace_kernel(TraceParams p) {
         if (nIdle == 64 || (sR > sI && sR > sP)) {
             // ---- retire finished rays, refill idle lanes -------------------------------
             const int ri = isIdle ? (kLean ? riReg : __float_as_int(cold[kColdRi][lane])) : -1;
-            // WALK: the lane's item walks on from nextO in direction nextD / would start call wMaxSurfaces + 1
+            // WALK: the lane's item walks on from nextO in direction nextD / would start call walk.maxSurfaces + 1
             [[maybe_unused]] bool goOn = false, capped = false;
             [[maybe_unused]] V3 nextO = {0.0f, 0.0f, 0.0f}, nextD = {0.0f, 0.0f, 0.0f};
             [[maybe_unused]] float nextTMax = 1.0f, nextTime = 0.0f;  // aggregate.Intersect(r, 1), time 0: WALK 2
@@ -658,23 +658,24 @@ void trace_kernel(TraceParams p) {
                                          sm.faceIndices, sm.triFlags, sm.nTris, sm.defaultFlags, sm.instances,
                                          sm.nInstances, sm.anim, sm.animFwd};
                     if constexpr (WALK == 1) {
-                        goOn = w2_str_item<PATCH != 0>(wm, r0, r1, h0, h1, ri, p.wPrimClass, p.wNPrimClass,
-                                                       p.wPLight, p.wState, nextO, nextD);
+                        goOn = w2_str_item<PATCH != 0>(wm, r0, r1, h0, h1, ri, p.walk.primClass, p.walk.nPrimClass,
+                                                       p.walk.pLight, p.walk.state, nextO, nextD);
                         nextTMax = r0.w;  // tMax is the work item's, unchanged (intersect.h:175, :187)
                         nextTime = r1.w;
                         // the spawned ray has a zero direction: the walk ends, the ray arrives (state stays 0)
                         if (goOn && nextD.x == 0.0f && nextD.y == 0.0f && nextD.z == 0.0f) goOn = false;
                     } else {
-                        goOn = w2_or_item<PATCH != 0>(wm, r0, r1, h0, h1, ri, p.wP1, p.wMaterial, p.wPrimMaterial,
-                                                      p.wNPrimMaterial, p.wSt, p.wSelHits, p.wSelRays, nextO, nextD);
+                        goOn = w2_or_item<PATCH != 0>(wm, r0, r1, h0, h1, ri, p.walk.p1, p.walk.material,
+                                                      p.walk.primMaterial, p.walk.nPrimMaterial, p.walk.st,
+                                                      p.walk.selHits, p.walk.selRays, nextO, nextD);
                     }
                     if (goOn) {
                         const int calls = __float_as_int(cold[kWalkCalls][lane]);
-                        if (calls >= p.wMaxSurfaces) {  // the caller's to finish, as w2_mark_unfinished marks it
+                        if (calls >= p.walk.maxSurfaces) {  // the caller's to finish, as w2_mark_unfinished marks it
                             goOn = false;
                             capped = true;
-                            if constexpr (WALK == 1) p.wState[ri] = 2;
-                            else p.wSelHits[2 * (long)ri + 1].w = __int_as_float(-1);
+                            if constexpr (WALK == 1) p.walk.state[ri] = 2;
+                            else p.walk.selHits[2 * (long)ri + 1].w = __int_as_float(-1);
                         } else {
                             cold[kWalkCalls][lane] = __int_as_float(calls + 1);
                         }
@@ -774,7 +775,8 @@ void trace_kernel(TraceParams p) {
             int nTake = nIdle;
             if constexpr (WALK != 0) {
                 const unsigned long long cm = __ballot(capped);
-                if (p.wUnfinished && cm != 0ull && lane == __ffsll((long long)cm) - 1) atomicAdd(p.wUnfinished, __popcll(cm));
+                if (p.walk.unfinished && cm != 0ull && lane == __ffsll((long long)cm) - 1)
+                    atomicAdd(p.walk.unfinished, __popcll(cm));
                 if (goOn) {  // same item, same lane: the ray index stays
                     const float4 a = {nextO.x, nextO.y, nextO.z, nextTMax}, b = {nextD.x, nextD.y, nextD.z, nextTime};
                     BVH_BEGIN_RAY(a, b);

@@ -9,9 +9,11 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "bvh_trace.h"
 #include "interaction.h"
+#include "kd_trace.h"
 
 namespace nnbvh {
 
@@ -121,17 +123,22 @@ Workspace *workspace_for(nnbvh_scene *s, hipStream_t stream);
 // one entry of the device's animation table (layout: anim_math.h; bvh_capi.cpp)
 void fill_anim_entry(const nnbvh_animated_transform &a, float *t);
 
-// The prologue of a call on a scene: the scene's device made current and its lock held for the call, and with a
-// stream that stream's workspace.
+// ... and the kd-tree scenes' (kd_trace.h) under the same name, for the code that serves both scene types
+inline KdWorkspace *workspace_for(nnbvh_kd_scene *s, hipStream_t stream) { return kd_workspace_for(s, stream); }
+
+// The prologue of a call on a scene of either type (S: nnbvh_scene with W = Workspace, nnbvh_kd_scene with W =
+// KdWorkspace; `SceneCall call(s, stream)` deduces both): the scene's device made current and its lock held for the
+// call, and with a stream that stream's workspace.
+template <class S, class W = std::remove_pointer_t<decltype(workspace_for((S *)nullptr, hipStream_t()))>>
 struct SceneCall {
     DeviceGuard guard;
     std::unique_lock<std::mutex> lock;
-    Workspace *w = nullptr;
+    W *w = nullptr;
     bool good;
-    explicit SceneCall(nnbvh_scene *s) : guard(s->device), good(guard.ok) {
+    explicit SceneCall(S *s) : guard(s->device), good(guard.ok) {
         if (good) lock = std::unique_lock<std::mutex>(s->mu);
     }
-    SceneCall(nnbvh_scene *s, hipStream_t stream) : SceneCall(s) {
+    SceneCall(S *s, hipStream_t stream) : SceneCall(s) {
         if (good) good = (w = workspace_for(s, stream)) != nullptr;
     }
     bool ok() const { return good; }  // false: NNBVH_ERR_DEVICE, the error text is set
@@ -184,29 +191,8 @@ struct TraceJob {
 int launch(nnbvh_scene *s, Workspace *w, hipStream_t stream, const TraceJob &job);
 
 // One launch of a walk instance of the trace kernel (bvh_trace.hip modes 4 / 5) behind its queue
-// reset node, over the items whose first rays are the records `rays`: item i is ray i, and the batch holds
-// min(n, max(*d_n, 0)) of them (d_n nullable).  The caller has checked that the scene has walk instances
-// (walk_refusal) and holds the scene's lock.
-struct WalkJob {
-    int kind = 1;  // 1: IntersectShadowTr's walk, 2: IntersectOneRandom's
-    const ShadingMeshDevice *mesh = nullptr;
-    const void *rays = nullptr;
-    int64_t n = 0;
-    const int32_t *d_n = nullptr;
-    int max_surfaces = 1;           // Intersect calls an item may make; one that would start another is marked
-    int32_t *unfinished = nullptr;  // nullable, zero before the launch: receives the number of marked items
-    // kind 1: state[] is 0 and p_light[] set for every item (str_init)
-    const uint8_t *prim_class = nullptr;
-    long n_prim_class = 0;
-    const float4 *p_light = nullptr;
-    uint8_t *state = nullptr;
-    // kind 2: the arrays launch_kd_or_init_all (kd_trace.h) has set
-    const float *p1 = nullptr;
-    const int32_t *material = nullptr, *prim_material = nullptr;
-    long n_prim_material = 0;
-    OneRandomState st{nullptr, nullptr, nullptr};
-    void *sel_hits = nullptr, *sel_rays = nullptr;
-};
+// reset node (WalkJob: walk_math.h).  The caller has checked that the scene has walk instances (walk_refusal) and holds
+// the scene's lock.
 int launch_walk(nnbvh_scene *s, Workspace *w, hipStream_t stream, const WalkJob &job);
 // why the scene has no walk instance (AnimatedPrimitive instances, alpha-tested primitives), or nullptr
 const char *walk_refusal(const nnbvh_scene *s);

@@ -113,19 +113,7 @@ int nnbvh::launch_walk(nnbvh_scene *s, Workspace *w, hipStream_t stream, const W
     p.n = (long)k.n;
     p.nDev = k.d_n;
     p.wMesh = *k.mesh;
-    p.wPrimClass = k.prim_class;
-    p.wNPrimClass = k.n_prim_class;
-    p.wPLight = k.p_light;
-    p.wState = k.state;
-    p.wP1 = k.p1;
-    p.wMaterial = k.material;
-    p.wPrimMaterial = k.prim_material;
-    p.wNPrimMaterial = k.n_prim_material;
-    p.wSt = k.st;
-    p.wSelHits = (float4 *)k.sel_hits;
-    p.wSelRays = (float4 *)k.sel_rays;
-    p.wMaxSurfaces = k.max_surfaces;
-    p.wUnfinished = k.unfinished;
+    p.walk = k.a;
     // the lean instance with the triangle-only interaction where neither the scene nor the mesh holds patches or an
     // instance table (launch_str_step's choice of FULL) and the scene has no host-only primitives; always window 8
     const ShadingMeshDevice &m = *k.mesh;

@@ -148,29 +148,25 @@ static bool queue_args_ok(const char *fn, const ClosestSide &a) {
     return true;
 }
 
-// (the scene, of either type, as "is there one" and its device)
-static bool closest_side_ok(const char *fn, bool scene, int device, const ClosestSide &a) {
+// (S: the scene of either type, nnbvh_scene or nnbvh_kd_scene)
+template <class S>
+static bool closest_args_ok(const char *fn, const S *s, const ClosestSide &a) {
     const bool no_hits = a.max_rays > 0 && !a.d_hits;
-    if (a.with_candidates && (!scene || no_hits)) return fail(fn, "bad argument (scene and d_hits are required)");
-    if (!scene || (!a.with_items && no_hits)) return fail(fn, "bad argument");
+    if (a.with_candidates && (!s || no_hits)) return fail(fn, "bad argument (scene and d_hits are required)");
+    if (!s || (!a.with_items && no_hits)) return fail(fn, "bad argument");
     if (!queue_args_ok(fn, a) || (a.with_candidates && !candidates_ok(fn, a.hc, true))) return false;
-    if (a.with_items && device != a.mesh->device) return fail(fn, "scene and shading mesh live on different devices");
+    if (a.with_items && s->device != a.mesh->device) return fail(fn, "scene and shading mesh live on different devices");
     return true;
 }
-static bool closest_args_ok(const char *fn, const nnbvh_scene *s, const ClosestSide &a) {
-    return closest_side_ok(fn, s != nullptr, s ? s->device : 0, a);
-}
 
-static bool shadow_side_ok(const char *fn, bool scene, const ShadowSide &a) {
-    if (!scene) return fail(fn, "bad argument");
+template <class S>
+static bool shadow_args_ok(const char *fn, const S *s, const ShadowSide &a) {
+    if (!s) return fail(fn, "bad argument");
     if (a.max_rays < 0 || a.n_pixels < 0 ||
         (a.max_rays > 0 && (!soa_ok(a.queue) || !a.d_Ld || !a.d_r_u || !a.d_r_l || !a.d_pixel_index || !a.d_L ||
                             (a.with_candidates && !a.d_occluded))))
         return fail(fn, a.with_candidates ? "bad argument (d_occluded is required)" : "bad argument");
     return !a.with_candidates || candidates_ok(fn, a.hc, false);
-}
-static bool shadow_args_ok(const char *fn, const nnbvh_scene *s, const ShadowSide &a) {
-    return shadow_side_ok(fn, s != nullptr, a);
 }
 
 // d_hits == NULL: the records go to a per-stream workspace of the scene's; d_occluded == NULL: likewise
@@ -189,22 +185,33 @@ static uint8_t *occluded_storage(W *w, uint8_t *d_occluded, int32_t max_rays) {
     return (uint8_t *)w->d_out;
 }
 
-// One queue (job.soa) through the trace kernel.  The lean kernels read the queue's SOA slices themselves (no gather
-// pass into nnbvh_ray records); for the others it is gathered into the workspace.  Candidates start from zero; scenes
-// without host-only primitives run the plain kernels over them.  The caller holds the scene's lock.
-static int trace_queue(nnbvh_scene *s, Workspace *w, hipStream_t stream, TraceJob job) {
-    if (job.hc && !zero_candidates(s, job.hc, job.n, job.mode == 0, stream)) return NNBVH_ERR_DEVICE;
-    job.hc_zeroed = true;
+// The trace half of a queue call, per scene type: one queue through the trace kernel, closest hit (out = nnbvh_hit[n]) or
+// any hit (out = uint8[n]), hc nullable.  The caller holds the scene's lock.
+// BVH scenes: the lean kernels read the queue's SOA slices themselves (no gather pass into nnbvh_ray records); for the
+// others it is gathered into the workspace.  Candidates start from zero; scenes without host-only primitives run the
+// plain kernels over them.
+static int trace_queue(nnbvh_scene *s, Workspace *w, hipStream_t stream, bool any, const nnbvh_ray_soa *queue, int32_t n,
+                       const int32_t *d_n, void *out, const nnbvh_host_candidates *hc) {
+    TraceJob job{.mode = any ? 2 : 0, .soa = queue, .n = n, .d_n = d_n, .hits = any ? nullptr : out,
+                 .occluded = any ? out : nullptr, .hc = hc, .hc_zeroed = true};
+    if (hc && !zero_candidates(s, hc, n, !any, stream)) return NNBVH_ERR_DEVICE;
     if (!scene_runs_lean(s)) {
-        if (!grow(&w->d_in, &w->in_bytes, (size_t)job.n * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
+        if (!grow(&w->d_in, &w->in_bytes, (size_t)n * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
             return NNBVH_ERR_DEVICE;
-        if (!hip_ok(launch_wf_gather(*job.soa, WavefrontCount{(int)job.n, job.d_n}, w->d_in, s->n_cus * 8, stream),
-                    "gather kernel launch"))
+        if (!hip_ok(launch_wf_gather(*queue, WavefrontCount{n, d_n}, w->d_in, s->n_cus * 8, stream), "gather kernel launch"))
             return NNBVH_ERR_DEVICE;
         job.rays = w->d_in;
         job.soa = nullptr;
     }
     return launch(s, w, stream, job);
+}
+// kd-tree scenes: kd_trace.hip's batch-mode launch over the one batch (kd_launch_batches gathers, zeroes and picks the
+// candidate-mode instances)
+static int trace_queue(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, bool any, const nnbvh_ray_soa *queue,
+                       int32_t n, const int32_t *d_n, void *out, const nnbvh_host_candidates *hc) {
+    KdBatch batch;
+    batch.any = any, batch.soa = queue, batch.n = n, batch.d_n = d_n, batch.out = out, batch.hc = hc;
+    return kd_launch_batches(s, w, stream, &batch, 1);
 }
 
 // IntersectShadow of one depth and IntersectClosest of the next (wavefront/integrator.cpp: TraceShadowRays(depth),
@@ -254,53 +261,74 @@ static int launch_items(const ClosestSide &a, const void *hits, const int32_t *h
 }
 
 // the second half of each side: hit records -> index queues (and work items), occlusion flags -> L
-static int enqueue_closest(int n_cus, bool has_host_prims, const ClosestSide &a, const void *hits, hipStream_t stream) {
+template <class S>
+static int enqueue_closest(const S *s, const ClosestSide &a, const void *hits, hipStream_t stream) {
     if (a.with_items)
-        return launch_items(a, hits, a.with_candidates && has_host_prims ? a.hc->count : nullptr, stream);
+        return launch_items(a, hits, a.with_candidates && s->has_host_prims ? a.hc->count : nullptr, stream);
     if (!hip_ok(launch_wf_enqueue_closest(hits, WavefrontCount{a.max_rays, a.d_size}, a.queue->has_medium,
-                                          a.d_prim_class, (long)a.n_prim_class, *a.out, n_cus * 8, stream),
+                                          a.d_prim_class, (long)a.n_prim_class, *a.out, s->n_cus * 8, stream),
                 "enqueue kernel launch"))
         return NNBVH_ERR_DEVICE;
     return NNBVH_OK;
 }
-static int enqueue_closest(const nnbvh_scene *s, const ClosestSide &a, const void *hits, hipStream_t stream) {
-    return enqueue_closest(s->n_cus, s->has_host_prims != 0, a, hits, stream);
-}
-static int record_shadow(int n_cus, const ShadowSide &a, const uint8_t *occ, hipStream_t stream) {
+template <class S>
+static int record_shadow(const S *s, const ShadowSide &a, const uint8_t *occ, hipStream_t stream) {
     if (!hip_ok(launch_wf_record_shadow(occ, WavefrontCount{a.max_rays, a.d_size}, a.d_Ld, a.d_r_u, a.d_r_l,
-                                        a.d_pixel_index, a.d_L, (long)a.n_pixels, n_cus * 8, stream),
+                                        a.d_pixel_index, a.d_L, (long)a.n_pixels, s->n_cus * 8, stream),
                 "shadow record kernel launch"))
         return NNBVH_ERR_DEVICE;
     return NNBVH_OK;
 }
-static int record_shadow(const nnbvh_scene *s, const ShadowSide &a, const uint8_t *occ, hipStream_t stream) {
-    return record_shadow(s->n_cus, a, occ, stream);
-}
 
-static int intersect_closest(nnbvh_scene *s, const ClosestSide &a, hipStream_t stream) {
-    if (!closest_args_ok(closest_fn(a), s, a)) return NNBVH_ERR_ARG;
+// What a kd-tree scene checks first, before the scene is looked at (the side checks read its device): a batch-mode
+// launch tags a ray with batch << kKdIndexBits | index, and a candidate call's nnbvh_host_candidates
+static bool kd_size_ok(const char *fn, int32_t max_rays) {
+    if (max_rays < 0) return fail(fn, "bad argument");
+    return max_rays < (1 << kKdIndexBits) || fail(fn, "a queue of 2^28 rays or more");
+}
+static bool kd_candidates_ok(const char *fn, bool scene, bool with_candidates, const nnbvh_host_candidates *hc, bool closest) {
+    if (!with_candidates) return true;
+    return scene ? candidates_ok(fn, hc, closest) : fail(fn, "bad argument (a scene is required)");
+}
+static bool front_ok(const char *fn, const nnbvh_kd_scene *s, int32_t max_rays, bool with_candidates,
+                     const nnbvh_host_candidates *hc, bool closest) {
+    return kd_size_ok(fn, max_rays) && kd_candidates_ok(fn, s != nullptr, with_candidates, hc, closest);
+}
+static bool front_ok(const char *, const nnbvh_scene *, int32_t, bool, const nnbvh_host_candidates *, bool) { return true; }
+
+// IntersectClosest / IntersectShadow on a scene of either type: the argument packs, their checks and the queue kernels
+// behind the launch are the same; the trace half is the type's trace_queue.  Without candidates a host-only primitive
+// voids the ray, and the enqueue sends it to needs_host (or nowhere); with them (the *_candidates calls) the enqueue
+// routes by the per-ray count and the shadow record skips the non-zero flags.
+template <class S>
+static int intersect_closest(S *s, const ClosestSide &a, hipStream_t stream) {
+    const char *fn = closest_fn(a);
+    if (!front_ok(fn, s, a.max_rays, a.with_candidates, a.hc, true) || !closest_args_ok(fn, s, a)) return NNBVH_ERR_ARG;
     if (a.max_rays == 0) return NNBVH_OK;
     SceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
     void *hits = hits_storage(call.w, a.d_hits, a.max_rays);
     if (!hits) return NNBVH_ERR_DEVICE;
-    const int rc = trace_queue(s, call.w, stream,
-                               {.mode = 0, .soa = a.queue, .n = a.max_rays, .d_n = a.d_size, .hits = hits, .hc = a.hc});
+    const int rc = trace_queue(s, call.w, stream, false, a.queue, a.max_rays, a.d_size, hits, a.hc);
     return rc != NNBVH_OK ? rc : enqueue_closest(s, a, hits, stream);
 }
 
-static int intersect_shadow(nnbvh_scene *s, const ShadowSide &a, hipStream_t stream) {
-    if (!shadow_args_ok(shadow_fn(a), s, a)) return NNBVH_ERR_ARG;
+template <class S>
+static int intersect_shadow(S *s, const ShadowSide &a, hipStream_t stream) {
+    const char *fn = shadow_fn(a);
+    if (!front_ok(fn, s, a.max_rays, a.with_candidates, a.hc, false) || !shadow_args_ok(fn, s, a)) return NNBVH_ERR_ARG;
     if (a.max_rays == 0) return NNBVH_OK;
     SceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
     uint8_t *occ = occluded_storage(call.w, a.d_occluded, a.max_rays);
     if (!occ) return NNBVH_ERR_DEVICE;
-    const int rc = trace_queue(s, call.w, stream,
-                               {.mode = 2, .soa = a.queue, .n = a.max_rays, .d_n = a.d_size, .occluded = occ, .hc = a.hc});
+    const int rc = trace_queue(s, call.w, stream, true, a.queue, a.max_rays, a.d_size, occ, a.hc);
     return rc != NNBVH_OK ? rc : record_shadow(s, a, occ, stream);
 }
 
+// The pair call stays one function per scene type: the two check their arguments in deliberately different orders (a
+// BVH scene checks a side under the pair's name only for _items, candidates or the one launch; a kd-tree scene checks
+// everything up front), and their one-launch halves share nothing.
 // Both sides in one launch where the scene and the sizes allow it; both sides have candidates, or neither.
 static int intersect_closest_and_shadow(nnbvh_scene *s, const ClosestSide &c, const ShadowSide &sh,
                                         hipStream_t stream) {
@@ -331,81 +359,22 @@ static int intersect_closest_and_shadow(nnbvh_scene *s, const ClosestSide &c, co
     return rc;
 }
 
-// ---- the same three calls on a kd-tree scene -----------------------------------------------------------------
-// The trace half is kd_trace.hip's batch-mode launch (one for a single queue, ONE for the pair); the argument packs,
-// their checks and the queue kernels behind the launch are the ones above.  Without candidates a host-only primitive
-// voids the ray, and the enqueue sends it to needs_host (or nowhere) as for a BVH scene without them; with them
-// (the *_candidates calls) the launch runs the kernel's candidate-mode instances over the gathered queue, the enqueue
-// routes by the per-ray count and the shadow record skips the non-zero flags, as for a BVH scene.
-struct KdSceneCall {
-    DeviceGuard guard;
-    std::unique_lock<std::mutex> lock;
-    KdWorkspace *w = nullptr;
-    bool good;
-    KdSceneCall(nnbvh_kd_scene *s, hipStream_t stream) : guard(s->device), good(guard.ok) {
-        if (good) lock = std::unique_lock<std::mutex>(s->mu);
-        if (good) good = (w = kd_workspace_for(s, stream)) != nullptr;
-    }
-    bool ok() const { return good; }
-};
-
-// a batch-mode launch tags a ray with batch << kKdIndexBits | index.  Checked first, before the scene is looked at
-static bool kd_size_ok(const char *fn, int32_t max_rays) {
-    if (max_rays < 0) return fail(fn, "bad argument");
-    return max_rays < (1 << kKdIndexBits) || fail(fn, "a queue of 2^28 rays or more");
-}
-
-// ... and so are a candidate call's nnbvh_host_candidates (the side checks below read the scene's device)
-static bool kd_candidates_ok(const char *fn, bool scene, bool with_candidates, const nnbvh_host_candidates *hc, bool closest) {
-    if (!with_candidates) return true;
-    return scene ? candidates_ok(fn, hc, closest) : fail(fn, "bad argument (a scene is required)");
-}
-
-static int kd_intersect_closest(nnbvh_kd_scene *s, const ClosestSide &a, hipStream_t stream) {
-    const char *fn = closest_fn(a);
-    if (!kd_size_ok(fn, a.max_rays) || !kd_candidates_ok(fn, s != nullptr, a.with_candidates, a.hc, true) || !closest_side_ok(fn, s != nullptr, s ? s->device : 0, a)) return NNBVH_ERR_ARG;
-    if (a.max_rays == 0) return NNBVH_OK;
-    KdSceneCall call(s, stream);
-    if (!call.ok()) return NNBVH_ERR_DEVICE;
-    void *hits = hits_storage(call.w, a.d_hits, a.max_rays);
-    if (!hits) return NNBVH_ERR_DEVICE;
-    KdBatch batch;
-    batch.soa = a.queue, batch.n = a.max_rays, batch.d_n = a.d_size, batch.out = hits;
-    batch.hc = a.with_candidates ? a.hc : nullptr;
-    const int rc = kd_launch_batches(s, call.w, stream, &batch, 1);
-    return rc != NNBVH_OK ? rc : enqueue_closest(s->n_cus, s->has_host_prims != 0, a, hits, stream);
-}
-
-static int kd_intersect_shadow(nnbvh_kd_scene *s, const ShadowSide &a, hipStream_t stream) {
-    const char *fn = shadow_fn(a);
-    if (!kd_size_ok(fn, a.max_rays) || !kd_candidates_ok(fn, s != nullptr, a.with_candidates, a.hc, false) || !shadow_side_ok(fn, s != nullptr, a)) return NNBVH_ERR_ARG;
-    if (a.max_rays == 0) return NNBVH_OK;
-    KdSceneCall call(s, stream);
-    if (!call.ok()) return NNBVH_ERR_DEVICE;
-    uint8_t *occ = occluded_storage(call.w, a.d_occluded, a.max_rays);
-    if (!occ) return NNBVH_ERR_DEVICE;
-    KdBatch batch;
-    batch.any = 1, batch.soa = a.queue, batch.n = a.max_rays, batch.d_n = a.d_size, batch.out = occ;
-    batch.hc = a.with_candidates ? a.hc : nullptr;
-    const int rc = kd_launch_batches(s, call.w, stream, &batch, 1);
-    return rc != NNBVH_OK ? rc : record_shadow(s->n_cus, a, occ, stream);
-}
-
 // Both sides checked under the pair's name before anything is launched; one side empty (or the scene set to two
-// launches, "pair_one_launch" 0): the two calls one after the other.
+// launches, "pair_one_launch" 0): the two calls one after the other.  The one launch is kd_trace.hip's batch-mode
+// launch over both queues.
 static int kd_intersect_closest_and_shadow(nnbvh_kd_scene *s, const ClosestSide &c, const ShadowSide &sh,
                                            hipStream_t stream) {
     const char *fn = pair_fn(c);
     if (!kd_size_ok(fn, c.max_rays) || !kd_size_ok(fn, sh.max_rays) ||
         !kd_candidates_ok(fn, s != nullptr, c.with_candidates, c.hc, true) ||
         !kd_candidates_ok(fn, s != nullptr, sh.with_candidates, sh.hc, false) ||
-        !closest_side_ok(fn, s != nullptr, s ? s->device : 0, c) || !shadow_side_ok(fn, s != nullptr, sh))
+        !closest_args_ok(fn, s, c) || !shadow_args_ok(fn, s, sh))
         return NNBVH_ERR_ARG;
     if (c.max_rays == 0 || sh.max_rays == 0 || !s->pair_one_launch) {
-        const int rc = kd_intersect_shadow(s, sh, stream);
-        return rc != NNBVH_OK ? rc : kd_intersect_closest(s, c, stream);
+        const int rc = intersect_shadow(s, sh, stream);
+        return rc != NNBVH_OK ? rc : intersect_closest(s, c, stream);
     }
-    KdSceneCall call(s, stream);
+    SceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
     uint8_t *occ = occluded_storage(call.w, sh.d_occluded, sh.max_rays);
     void *hits = occ ? hits_storage(call.w, c.d_hits, c.max_rays) : nullptr;
@@ -419,9 +388,156 @@ static int kd_intersect_closest_and_shadow(nnbvh_kd_scene *s, const ClosestSide 
     batches[0].hc = c.with_candidates ? c.hc : nullptr;
     batches[1].hc = sh.with_candidates ? sh.hc : nullptr;
     int rc = kd_launch_batches(s, call.w, stream, batches, 2);
-    if (rc == NNBVH_OK) rc = enqueue_closest(s->n_cus, s->has_host_prims != 0, c, hits, stream);
-    if (rc == NNBVH_OK) rc = record_shadow(s->n_cus, sh, occ, stream);
+    if (rc == NNBVH_OK) rc = enqueue_closest(s, c, hits, stream);
+    if (rc == NNBVH_OK) rc = record_shadow(s, sh, occ, stream);
     return rc;
+}
+
+// ---- what the multi-pass and the walk calls below share (C++ linkage: templates) ---------------------------------
+static bool scratch(Workspace *w, int slot, size_t bytes, void **out) {
+    if (!grow(&w->scratch[slot], &w->scratch_bytes[slot], std::max<size_t>(bytes, 16), "hipMalloc(wavefront scratch)"))
+        return false;
+    *out = w->scratch[slot];
+    return true;
+}
+
+static bool read_count(const int32_t *d_counter, hipStream_t stream, int *out) {
+    int32_t v = 0;
+    if (!hip_ok(hipMemcpyAsync(&v, d_counter, 4, hipMemcpyDeviceToHost, stream), "read pass count") ||
+        !hip_ok(hipStreamSynchronize(stream), "wavefront pass"))
+        return false;
+    *out = v;
+    return true;
+}
+
+static constexpr int kMaxBoundedPasses = 64;
+static constexpr int kMaxWalkSurfaces = 65536;
+
+// What a scene type refuses in a walk call on top of the common checks below: `early` between "negative size" and
+// "null array", else last
+static const char *type_refusal(const nnbvh_scene *s, const nnbvh_shading_mesh *, int32_t, bool early) {
+    return early ? nullptr : walk_refusal(s);
+}
+static const char *type_refusal(const nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_items, bool early) {
+    if (early) return max_items >= (1 << kKdIndexBits) ? "a queue of 2^28 items or more" : nullptr;
+    if (m->d.instances) return "the shading mesh carries an instance table (kd-tree scenes have one level)";
+    if (s->d_extras)
+        return "the scene holds alpha-tested smooth triangles or alpha-tested patches on the device (the ATTR kernels), "
+               "which have no walk instances";
+    return nullptr;
+}
+
+// The arguments of a bounded call (bound_name "max_passes", 1..kMaxBoundedPasses) or of a walk call of either scene
+// type ("max_surfaces", 1..kMaxWalkSurfaces; refuse = type_refusal).  arrays: every array the call needs is there
+template <class S>
+static bool bounded_args_ok(const char *fn, const S *s, const nnbvh_shading_mesh *m, int32_t max_items, int64_t n_prim,
+                            const char *bound_name, int32_t bound, int32_t bound_max, bool arrays,
+                            const char *(*refuse)(const S *, const nnbvh_shading_mesh *, int32_t, bool) = nullptr) {
+    std::string what;
+    const char *refusal = nullptr;
+    if (!s) what = "no scene";
+    else if (!m) what = "no shading mesh";
+    else if (bound < 1 || bound > bound_max) what = std::string(bound_name) + " outside 1.." + std::to_string(bound_max);
+    else if (max_items < 0 || n_prim < 0) what = "negative size";
+    else if (refuse && (refusal = refuse(s, m, max_items, true))) what = refusal;
+    else if (max_items > 0 && !arrays) what = "null array";
+    else if (m->device != s->device) what = "scene and shading mesh live on different devices";
+    else if (refuse && (refusal = refuse(s, m, max_items, false))) what = refusal;
+    if (!what.empty()) set_error(std::string(fn) + ": " + what);
+    return what.empty();
+}
+
+// ---- the walk calls: IntersectShadowTr / IntersectOneRandom inside ONE trace launch, for scenes of either type ------
+// The walk instances of the trace kernels (bvh_trace.hip modes 4 / 5; kd_trace.hip, §5.7.1) run the
+// per-item loop inside the lane, so a call is five kernel nodes whatever max_surfaces is: queue-head reset,
+// unfinished-count reset, init, walk, record / finish; no copy, memset, synchronise or event query.  The scratch is the
+// per-stream workspace's, sized from max_rays / max_items alone: after one warm-up call nothing is allocated and the
+// call can be captured in a hipGraph.  Per scene type: the workspace slots, launch_walk and type_refusal.
+enum { kWalkRays, kWalkOrig, kWalkPLight, kWalkState, kWalkRng, kWalkWeights };
+// BVH scenes: the slots the pass forms use for the same arrays; kd-tree scenes: the six walk arrays of their workspace
+static bool walk_scratch(Workspace *w, int which, size_t bytes, void **out) {
+    static constexpr int slot[6] = {0, 4, 6, 7, 10, 11};
+    return scratch(w, slot[which], bytes, out);
+}
+static bool walk_scratch(KdWorkspace *w, int which, size_t bytes, void **out) {
+    return kd_walk_scratch(w, which, bytes, out);
+}
+
+template <class S>
+static int walk_shadow_tr(const char *fn, S *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                          const nnbvh_ray_soa *shadow_queue, const int32_t *d_size, const uint8_t *d_prim_class,
+                          int64_t n_prim_class, const float *d_Ld, const float *d_r_u, const float *d_r_l,
+                          const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_state,
+                          int32_t max_surfaces, int32_t *d_unfinished, hipStream_t stream) {
+    if (!bounded_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), "max_surfaces", max_surfaces,
+                         kMaxWalkSurfaces, soa_ok(shadow_queue) && d_Ld && d_r_u && d_r_l && d_pixel_index && d_L,
+                         type_refusal))
+        return NNBVH_ERR_ARG;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_rays == 0) return NNBVH_OK;
+    const size_t n = (size_t)max_rays;
+    void *rays, *orig, *pLight, *state;
+    if (!walk_scratch(call.w, kWalkRays, n * 32, &rays) || !walk_scratch(call.w, kWalkOrig, n * 4, &orig) ||
+        !walk_scratch(call.w, kWalkPLight, n * 16, &pLight) || !walk_scratch(call.w, kWalkState, n, &state))
+        return NNBVH_ERR_DEVICE;
+    const WavefrontCount cnt{max_rays, d_size};
+    // str_init: every ray's record, light point and state 0 (its item list is the identity and is not read)
+    if (!hip_ok(launch_str_init(*shadow_queue, cnt, rays, (int32_t *)orig, (float4 *)pLight, (uint8_t *)state, max_blocks,
+                                stream), "shadow-tr init launch"))
+        return NNBVH_ERR_DEVICE;
+    WalkJob walk;
+    walk.kind = 1, walk.mesh = &m->d, walk.rays = rays, walk.n = max_rays, walk.d_n = d_size;
+    walk.a.maxSurfaces = max_surfaces, walk.a.unfinished = d_unfinished;
+    walk.a.primClass = d_prim_class, walk.a.nPrimClass = (long)n_prim_class;
+    walk.a.pLight = (const float4 *)pLight, walk.a.state = (uint8_t *)state;
+    const int rc = launch_walk(s, call.w, stream, walk);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
+                                  d_state, max_blocks, stream), "shadow-tr record launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+template <class S>
+static int walk_one_random(const char *fn, S *s, const nnbvh_shading_mesh *m, int32_t max_items, const float *d_p0,
+                           const float *d_p1, const int32_t *d_material, const int32_t *d_size,
+                           const int32_t *d_prim_material, int64_t n_prim_material, void *d_sel_hits, void *d_sel_rays,
+                           float *d_reservoir_pdf, float *d_weight_sum, int32_t max_surfaces, int32_t *d_unfinished,
+                           hipStream_t stream) {
+    if (!bounded_args_ok(fn, s, m, max_items, n_prim_material, "max_surfaces", max_surfaces, kMaxWalkSurfaces,
+                         d_p0 && d_p1 && d_material && d_sel_hits && d_sel_rays && d_reservoir_pdf, type_refusal))
+        return NNBVH_ERR_ARG;
+    SceneCall call(s, stream);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const int max_blocks = s->n_cus * 8;
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (max_items == 0) return NNBVH_OK;
+    const size_t n = (size_t)max_items;
+    void *rays, *rng, *weights;
+    if (!walk_scratch(call.w, kWalkRays, n * 32, &rays) || !walk_scratch(call.w, kWalkRng, n * 16, &rng) ||
+        !walk_scratch(call.w, kWalkWeights, n * 8, &weights))
+        return NNBVH_ERR_DEVICE;
+    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};  // (the base interaction stays in registers)
+    const WavefrontCount cnt{max_items, d_size};
+    if (!hip_ok(launch_or_init_all(d_p0, d_p1, cnt, st, rays, d_sel_hits, d_sel_rays, max_blocks, stream),
+                "one-random init launch"))
+        return NNBVH_ERR_DEVICE;
+    WalkJob walk;
+    walk.kind = 2, walk.mesh = &m->d, walk.rays = rays, walk.n = max_items, walk.d_n = d_size;
+    walk.a.maxSurfaces = max_surfaces, walk.a.unfinished = d_unfinished;
+    walk.a.p1 = d_p1, walk.a.material = d_material, walk.a.primMaterial = d_prim_material;
+    walk.a.nPrimMaterial = (long)n_prim_material, walk.a.st = st;
+    walk.a.selHits = (float4 *)d_sel_hits, walk.a.selRays = (float4 *)d_sel_rays;
+    const int rc = launch_walk(s, call.w, stream, walk);
+    if (rc != NNBVH_OK) return rc;
+    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
 }
 
 extern "C" {
@@ -532,10 +648,10 @@ int nnbvh_wavefront_intersect_closest_and_shadow_items_candidates(
 int nnbvh_kd_wavefront_intersect_closest(nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
                                          const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class,
                                          void *d_hits, const nnbvh_closest_queues *out, void *stream) {
-    return kd_intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
-                                    .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
-                                    .out = out, .kd = true},
-                                (hipStream_t)stream);
+    return intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                 .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
+                                 .out = out, .kd = true},
+                             (hipStream_t)stream);
 }
 
 int nnbvh_kd_wavefront_intersect_closest_items(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
@@ -543,20 +659,20 @@ int nnbvh_kd_wavefront_intersect_closest_items(nnbvh_kd_scene *s, const nnbvh_sh
                                                const uint8_t *d_prim_class, int64_t n_prim_class, void *d_hits,
                                                const nnbvh_closest_queues *out, const nnbvh_closest_items *items,
                                                void *stream) {
-    return kd_intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
-                                    .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
-                                    .out = out, .with_items = true, .mesh = m, .items = items, .kd = true},
-                                (hipStream_t)stream);
+    return intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                 .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
+                                 .out = out, .with_items = true, .mesh = m, .items = items, .kd = true},
+                             (hipStream_t)stream);
 }
 
 int nnbvh_kd_wavefront_intersect_shadow(nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
                                         const int32_t *d_size, const float *d_Ld, const float *d_r_u,
                                         const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
                                         int64_t n_pixels, uint8_t *d_occluded, void *stream) {
-    return kd_intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
-                                   .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
-                                   .n_pixels = n_pixels, .d_occluded = d_occluded, .kd = true},
-                               (hipStream_t)stream);
+    return intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
+                                .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
+                                .n_pixels = n_pixels, .d_occluded = d_occluded, .kd = true},
+                            (hipStream_t)stream);
 }
 
 int nnbvh_kd_wavefront_intersect_closest_and_shadow(
@@ -600,11 +716,11 @@ int nnbvh_kd_wavefront_intersect_closest_items_candidates(nnbvh_kd_scene *s, con
                                                           const nnbvh_closest_queues *out,
                                                           const nnbvh_closest_items *items,
                                                           const nnbvh_host_candidates *c, void *stream) {
-    return kd_intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
-                                    .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
-                                    .out = out, .with_items = true, .mesh = m, .items = items, .with_candidates = true,
-                                    .hc = c, .kd = true},
-                                (hipStream_t)stream);
+    return intersect_closest(s, {.max_rays = max_rays, .queue = ray_queue, .d_size = d_size,
+                                 .d_prim_class = d_prim_class, .n_prim_class = n_prim_class, .d_hits = d_hits,
+                                 .out = out, .with_items = true, .mesh = m, .items = items, .with_candidates = true,
+                                 .hc = c, .kd = true},
+                             (hipStream_t)stream);
 }
 
 int nnbvh_kd_wavefront_intersect_shadow_candidates(nnbvh_kd_scene *s, int32_t max_rays,
@@ -612,11 +728,11 @@ int nnbvh_kd_wavefront_intersect_shadow_candidates(nnbvh_kd_scene *s, int32_t ma
                                                    const float *d_Ld, const float *d_r_u, const float *d_r_l,
                                                    const int32_t *d_pixel_index, float *d_L, int64_t n_pixels,
                                                    uint8_t *d_occluded, const nnbvh_host_candidates *c, void *stream) {
-    return kd_intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
-                                   .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
-                                   .n_pixels = n_pixels, .d_occluded = d_occluded, .with_candidates = true, .hc = c,
-                                   .kd = true},
-                               (hipStream_t)stream);
+    return intersect_shadow(s, {.max_rays = max_rays, .queue = shadow_queue, .d_size = d_size, .d_Ld = d_Ld,
+                                .d_r_u = d_r_u, .d_r_l = d_r_l, .d_pixel_index = d_pixel_index, .d_L = d_L,
+                                .n_pixels = n_pixels, .d_occluded = d_occluded, .with_candidates = true, .hc = c,
+                                .kd = true},
+                            (hipStream_t)stream);
 }
 
 int nnbvh_kd_wavefront_intersect_closest_and_shadow_items_candidates(
@@ -705,22 +821,6 @@ int nnbvh_wavefront_record_shadow_device(const uint8_t *d_occluded, int32_t max_
 // ---- IntersectShadowTr / IntersectOneRandom (wavefront/aggregate.cpp:70-116), media-free -------------
 // Host-driven loops of device passes; the only host round trip per pass is the 4-byte count of
 // items that go on (interface surfaces are rare: the usual shadow batch ends after its first pass).
-static bool scratch(Workspace *w, int slot, size_t bytes, void **out) {
-    if (!grow(&w->scratch[slot], &w->scratch_bytes[slot], std::max<size_t>(bytes, 16), "hipMalloc(wavefront scratch)"))
-        return false;
-    *out = w->scratch[slot];
-    return true;
-}
-
-static bool read_count(const int32_t *d_counter, hipStream_t stream, int *out) {
-    int32_t v = 0;
-    if (!hip_ok(hipMemcpyAsync(&v, d_counter, 4, hipMemcpyDeviceToHost, stream), "read pass count") ||
-        !hip_ok(hipStreamSynchronize(stream), "wavefront pass"))
-        return false;
-    *out = v;
-    return true;
-}
-
 int nnbvh_wavefront_intersect_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
                                         const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
                                         const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
@@ -856,28 +956,13 @@ int nnbvh_wavefront_intersect_one_random(nnbvh_scene *s, const nnbvh_shading_mes
 // once the stream's workspace has its size (a warm-up call with the same max_rays): every pass is sized for
 // max_rays and takes its live count from counters[k], which the step of pass k - 1 has counted up.  The counters
 // are cleared by a kernel node.  A pass over an empty list is a trace and a step whose waves exit at once.
-static constexpr int kMaxBoundedPasses = 64;
-
-static bool bounded_args_ok(const char *fn, const nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
-                            int64_t n_prim, int32_t max_passes, bool arrays) {
-    const char *what = nullptr;
-    if (!s) what = "no scene";
-    else if (!m) what = "no shading mesh";
-    else if (max_passes < 1 || max_passes > kMaxBoundedPasses) what = "max_passes outside 1..64";
-    else if (max_items < 0 || n_prim < 0) what = "negative size";
-    else if (max_items > 0 && !arrays) what = "null array";
-    else if (m->device != s->device) what = "scene and shading mesh live on different devices";
-    if (what) set_error(std::string(fn) + ": " + what);
-    return !what;
-}
-
 int nnbvh_wavefront_intersect_shadow_tr_bounded(
     nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
     const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld, const float *d_r_u,
     const float *d_r_l, const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_state,
     int32_t max_passes, int32_t *d_unfinished, void *stream_) {
     const char *fn = "wavefront_intersect_shadow_tr_bounded";
-    if (!bounded_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), max_passes,
+    if (!bounded_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), "max_passes", max_passes, kMaxBoundedPasses,
                          soa_ok(shadow_queue) && d_Ld && d_r_u && d_r_l && d_pixel_index && d_L))
         return NNBVH_ERR_ARG;
     hipStream_t stream = (hipStream_t)stream_;
@@ -927,7 +1012,7 @@ int nnbvh_wavefront_intersect_one_random_bounded(
     void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum, int32_t max_passes,
     int32_t *d_unfinished, void *stream_) {
     const char *fn = "wavefront_intersect_one_random_bounded";
-    if (!bounded_args_ok(fn, s, m, max_items, n_prim_material, max_passes,
+    if (!bounded_args_ok(fn, s, m, max_items, n_prim_material, "max_passes", max_passes, kMaxBoundedPasses,
                          d_p0 && d_p1 && d_material && d_sel_hits && d_sel_rays && d_reservoir_pdf))
         return NNBVH_ERR_ARG;
     hipStream_t stream = (hipStream_t)stream_;
@@ -972,29 +1057,16 @@ int nnbvh_wavefront_intersect_one_random_bounded(
     return NNBVH_OK;
 }
 
-// ---- the walk calls of a kd-tree scene: IntersectShadowTr / IntersectOneRandom inside ONE trace launch ---------------
-// The walk instances of the kd trace kernel (kd_trace.hip) run the per-item loop inside the lane, so
-// a call is five kernel nodes whatever max_surfaces is: queue-head reset, unfinished-count reset, init, walk, record /
-// finish.  Nothing waits for the device or copies from host memory; once the stream's workspace has its size (a
-// warm-up call with the same max_rays) nothing is allocated and the call can be captured in a hipGraph.
-static constexpr int kMaxWalkSurfaces = 65536;
-
-static bool kd_walk_args_ok(const char *fn, const nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
-                            int64_t n_prim, int32_t max_surfaces, bool arrays) {
-    const char *what = nullptr;
-    if (!s) what = "no scene";
-    else if (!m) what = "no shading mesh";
-    else if (max_surfaces < 1 || max_surfaces > kMaxWalkSurfaces) what = "max_surfaces outside 1..65536";
-    else if (max_items < 0 || n_prim < 0) what = "negative size";
-    else if (max_items >= (1 << kKdIndexBits)) what = "a queue of 2^28 items or more";
-    else if (max_items > 0 && !arrays) what = "null array";
-    else if (m->device != s->device) what = "scene and shading mesh live on different devices";
-    else if (m->d.instances) what = "the shading mesh carries an instance table (kd-tree scenes have one level)";
-    else if (s->d_extras)
-        what = "the scene holds alpha-tested smooth triangles or alpha-tested patches on the device (the ATTR kernels), "
-               "which have no walk instances";
-    if (what) set_error(std::string(fn) + ": " + what);
-    return !what;
+// ---- the walk calls: walk_shadow_tr / walk_one_random (above) under the four names -----------------------------------
+int nnbvh_wavefront_walk_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
+                                   const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
+                                   const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
+                                   const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
+                                   int64_t n_pixels, uint8_t *d_state, int32_t max_surfaces, int32_t *d_unfinished,
+                                   void *stream) {
+    return walk_shadow_tr("wavefront_walk_shadow_tr", s, m, max_rays, shadow_queue, d_size, d_prim_class, n_prim_class,
+                          d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, n_pixels, d_state, max_surfaces, d_unfinished,
+                          (hipStream_t)stream);
 }
 
 int nnbvh_kd_wavefront_walk_shadow_tr(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
@@ -1002,173 +1074,30 @@ int nnbvh_kd_wavefront_walk_shadow_tr(nnbvh_kd_scene *s, const nnbvh_shading_mes
                                       const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
                                       const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
                                       int64_t n_pixels, uint8_t *d_state, int32_t max_surfaces, int32_t *d_unfinished,
-                                      void *stream_) {
-    const char *fn = "kd_wavefront_walk_shadow_tr";
-    if (!kd_walk_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), max_surfaces,
-                         soa_ok(shadow_queue) && d_Ld && d_r_u && d_r_l && d_pixel_index && d_L))
-        return NNBVH_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    KdSceneCall call(s, stream);
-    if (!call.ok()) return NNBVH_ERR_DEVICE;
-    const int max_blocks = s->n_cus * 8;
-    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
-        return NNBVH_ERR_DEVICE;
-    if (max_rays == 0) return NNBVH_OK;
-    const size_t n = (size_t)max_rays;
-    void *rays, *orig, *pLight, *state;
-    if (!kd_walk_scratch(call.w, 0, n * 32, &rays) || !kd_walk_scratch(call.w, 1, n * 4, &orig) ||
-        !kd_walk_scratch(call.w, 2, n * 16, &pLight) || !kd_walk_scratch(call.w, 3, n, &state))
-        return NNBVH_ERR_DEVICE;
-    const WavefrontCount cnt{max_rays, d_size};
-    // str_init: every ray's record, light point and state 0 (its item list is the identity and is not read)
-    if (!hip_ok(launch_str_init(*shadow_queue, cnt, rays, (int32_t *)orig, (float4 *)pLight, (uint8_t *)state, max_blocks,
-                                stream), "shadow-tr init launch"))
-        return NNBVH_ERR_DEVICE;
-    KdWalk walk;
-    walk.kind = 1, walk.mesh = &m->d, walk.rays = rays, walk.n = max_rays, walk.d_n = d_size;
-    walk.maxSurfaces = max_surfaces, walk.unfinished = d_unfinished;
-    walk.primClass = d_prim_class, walk.nPrimClass = (long)n_prim_class;
-    walk.pLight = (const float4 *)pLight, walk.state = (uint8_t *)state;
-    const int rc = kd_launch_walk(s, call.w, stream, walk);
-    if (rc != NNBVH_OK) return rc;
-    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
-                                  d_state, max_blocks, stream), "shadow-tr record launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
-}
-
-int nnbvh_kd_wavefront_walk_one_random(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
-                                       const float *d_p0, const float *d_p1, const int32_t *d_material,
-                                       const int32_t *d_size, const int32_t *d_prim_material, int64_t n_prim_material,
-                                       void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum,
-                                       int32_t max_surfaces, int32_t *d_unfinished, void *stream_) {
-    const char *fn = "kd_wavefront_walk_one_random";
-    if (!kd_walk_args_ok(fn, s, m, max_items, n_prim_material, max_surfaces,
-                         d_p0 && d_p1 && d_material && d_sel_hits && d_sel_rays && d_reservoir_pdf))
-        return NNBVH_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    KdSceneCall call(s, stream);
-    if (!call.ok()) return NNBVH_ERR_DEVICE;
-    const int max_blocks = s->n_cus * 8;
-    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
-        return NNBVH_ERR_DEVICE;
-    if (max_items == 0) return NNBVH_OK;
-    const size_t n = (size_t)max_items;
-    void *rays, *rng, *weights;
-    if (!kd_walk_scratch(call.w, 0, n * 32, &rays) || !kd_walk_scratch(call.w, 4, n * 16, &rng) ||
-        !kd_walk_scratch(call.w, 5, n * 8, &weights))
-        return NNBVH_ERR_DEVICE;
-    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};  // (the base interaction stays in registers)
-    const WavefrontCount cnt{max_items, d_size};
-    if (!hip_ok(launch_kd_or_init_all(d_p0, d_p1, cnt, st, rays, d_sel_hits, d_sel_rays, max_blocks, stream),
-                "one-random init launch"))
-        return NNBVH_ERR_DEVICE;
-    KdWalk walk;
-    walk.kind = 2, walk.mesh = &m->d, walk.rays = rays, walk.n = max_items, walk.d_n = d_size;
-    walk.maxSurfaces = max_surfaces, walk.unfinished = d_unfinished;
-    walk.p1 = d_p1, walk.material = d_material, walk.primMaterial = d_prim_material;
-    walk.nPrimMaterial = (long)n_prim_material, walk.st = st, walk.selHits = d_sel_hits, walk.selRays = d_sel_rays;
-    const int rc = kd_launch_walk(s, call.w, stream, walk);
-    if (rc != NNBVH_OK) return rc;
-    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
-}
-
-// ---- the walk calls of a BVH scene: the same two loops inside ONE trace launch (bvh_trace.hip modes 4 / 5, DESIGN.md
-// §5.5.1).  Five kernel nodes whatever max_surfaces is: queue-head reset, unfinished-count reset, init, walk, record /
-// finish; no copy, memset, synchronise or event query.  The scratch is the per-stream workspace's, sized from max_rays /
-// max_items alone: after one warm-up call nothing is allocated and the call can be captured in a hipGraph.
-static bool walk_args_ok(const char *fn, const nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
-                         int64_t n_prim, int32_t max_surfaces, bool arrays) {
-    const char *what = nullptr;
-    if (!s) what = "no scene";
-    else if (!m) what = "no shading mesh";
-    else if (max_surfaces < 1 || max_surfaces > kMaxWalkSurfaces) what = "max_surfaces outside 1..65536";
-    else if (max_items < 0 || n_prim < 0) what = "negative size";
-    else if (max_items > 0 && !arrays) what = "null array";
-    else if (m->device != s->device) what = "scene and shading mesh live on different devices";
-    else what = walk_refusal(s);
-    if (what) set_error(std::string(fn) + ": " + what);
-    return !what;
-}
-
-int nnbvh_wavefront_walk_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
-                                   const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
-                                   const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
-                                   const float *d_r_u, const float *d_r_l, const int32_t *d_pixel_index, float *d_L,
-                                   int64_t n_pixels, uint8_t *d_state, int32_t max_surfaces, int32_t *d_unfinished,
-                                   void *stream_) {
-    const char *fn = "wavefront_walk_shadow_tr";
-    if (!walk_args_ok(fn, s, m, max_rays, std::min(n_prim_class, n_pixels), max_surfaces,
-                      soa_ok(shadow_queue) && d_Ld && d_r_u && d_r_l && d_pixel_index && d_L))
-        return NNBVH_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    SceneCall call(s, stream);
-    if (!call.ok()) return NNBVH_ERR_DEVICE;
-    const int max_blocks = s->n_cus * 8;
-    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
-        return NNBVH_ERR_DEVICE;
-    if (max_rays == 0) return NNBVH_OK;
-    const size_t n = (size_t)max_rays;
-    void *rays, *orig, *pLight, *state;
-    if (!scratch(call.w, 0, n * 32, &rays) || !scratch(call.w, 4, n * 4, &orig) ||
-        !scratch(call.w, 6, n * 16, &pLight) || !scratch(call.w, 7, n, &state))
-        return NNBVH_ERR_DEVICE;
-    const WavefrontCount cnt{max_rays, d_size};
-    // str_init: every ray's record, light point and state 0 (its item list is the identity and is not read)
-    if (!hip_ok(launch_str_init(*shadow_queue, cnt, rays, (int32_t *)orig, (float4 *)pLight, (uint8_t *)state, max_blocks,
-                                stream), "shadow-tr init launch"))
-        return NNBVH_ERR_DEVICE;
-    WalkJob walk;
-    walk.kind = 1, walk.mesh = &m->d, walk.rays = rays, walk.n = max_rays, walk.d_n = d_size;
-    walk.max_surfaces = max_surfaces, walk.unfinished = d_unfinished;
-    walk.prim_class = d_prim_class, walk.n_prim_class = (long)n_prim_class;
-    walk.p_light = (const float4 *)pLight, walk.state = (uint8_t *)state;
-    const int rc = launch_walk(s, call.w, stream, walk);
-    if (rc != NNBVH_OK) return rc;
-    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
-                                  d_state, max_blocks, stream), "shadow-tr record launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
+                                      void *stream) {
+    return walk_shadow_tr("kd_wavefront_walk_shadow_tr", s, m, max_rays, shadow_queue, d_size, d_prim_class, n_prim_class,
+                          d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, n_pixels, d_state, max_surfaces, d_unfinished,
+                          (hipStream_t)stream);
 }
 
 int nnbvh_wavefront_walk_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items, const float *d_p0,
                                     const float *d_p1, const int32_t *d_material, const int32_t *d_size,
                                     const int32_t *d_prim_material, int64_t n_prim_material, void *d_sel_hits,
                                     void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum, int32_t max_surfaces,
-                                    int32_t *d_unfinished, void *stream_) {
-    const char *fn = "wavefront_walk_one_random";
-    if (!walk_args_ok(fn, s, m, max_items, n_prim_material, max_surfaces,
-                      d_p0 && d_p1 && d_material && d_sel_hits && d_sel_rays && d_reservoir_pdf))
-        return NNBVH_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    SceneCall call(s, stream);
-    if (!call.ok()) return NNBVH_ERR_DEVICE;
-    const int max_blocks = s->n_cus * 8;
-    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
-        return NNBVH_ERR_DEVICE;
-    if (max_items == 0) return NNBVH_OK;
-    const size_t n = (size_t)max_items;
-    void *rays, *rng, *weights;
-    if (!scratch(call.w, 0, n * 32, &rays) || !scratch(call.w, 10, n * 16, &rng) || !scratch(call.w, 11, n * 8, &weights))
-        return NNBVH_ERR_DEVICE;
-    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};  // (the base interaction stays in registers)
-    const WavefrontCount cnt{max_items, d_size};
-    // (the kd walk's init-all: nothing in it knows the tree)
-    if (!hip_ok(launch_kd_or_init_all(d_p0, d_p1, cnt, st, rays, d_sel_hits, d_sel_rays, max_blocks, stream),
-                "one-random init launch"))
-        return NNBVH_ERR_DEVICE;
-    WalkJob walk;
-    walk.kind = 2, walk.mesh = &m->d, walk.rays = rays, walk.n = max_items, walk.d_n = d_size;
-    walk.max_surfaces = max_surfaces, walk.unfinished = d_unfinished;
-    walk.p1 = d_p1, walk.material = d_material, walk.prim_material = d_prim_material;
-    walk.n_prim_material = (long)n_prim_material, walk.st = st, walk.sel_hits = d_sel_hits, walk.sel_rays = d_sel_rays;
-    const int rc = launch_walk(s, call.w, stream, walk);
-    if (rc != NNBVH_OK) return rc;
-    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
+                                    int32_t *d_unfinished, void *stream) {
+    return walk_one_random("wavefront_walk_one_random", s, m, max_items, d_p0, d_p1, d_material, d_size, d_prim_material,
+                           n_prim_material, d_sel_hits, d_sel_rays, d_reservoir_pdf, d_weight_sum, max_surfaces,
+                           d_unfinished, (hipStream_t)stream);
+}
+
+int nnbvh_kd_wavefront_walk_one_random(nnbvh_kd_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
+                                       const float *d_p0, const float *d_p1, const int32_t *d_material,
+                                       const int32_t *d_size, const int32_t *d_prim_material, int64_t n_prim_material,
+                                       void *d_sel_hits, void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum,
+                                       int32_t max_surfaces, int32_t *d_unfinished, void *stream) {
+    return walk_one_random("kd_wavefront_walk_one_random", s, m, max_items, d_p0, d_p1, d_material, d_size,
+                           d_prim_material, n_prim_material, d_sel_hits, d_sel_rays, d_reservoir_pdf, d_weight_sum,
+                           max_surfaces, d_unfinished, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@
 #include <mutex>
 
 #include "../../include/nnbvh.h"
-#include "wavefront2.h"
+#include "walk_math.h"
 
 namespace nnbvh {
 
@@ -27,29 +27,6 @@ struct KdWorkspace {
     static constexpr int kWalk = 6;
     void *walk[kWalk] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t walk_bytes[kWalk] = {0, 0, 0, 0, 0, 0};
-};
-
-// One launch of a walk instance of the trace kernel (kd_trace.hip) over the items whose first rays
-// are the records `rays`: item i is ray i, and the batch holds min(n, max(*d_n, 0)) of them (d_n nullable).
-struct KdWalk {
-    int kind = 1;  // 1: IntersectShadowTr's walk, 2: IntersectOneRandom's
-    const ShadingMeshDevice *mesh = nullptr;
-    const void *rays = nullptr;
-    int64_t n = 0;
-    const int32_t *d_n = nullptr;
-    int maxSurfaces = 1;            // Intersect calls an item may make; one that would start another is marked
-    int32_t *unfinished = nullptr;  // nullable, zero before the launch: receives the number of marked items
-    // kind 1: state[] is 0 and pLight[] set for every item (str_init)
-    const uint8_t *primClass = nullptr;
-    long nPrimClass = 0;
-    const float4 *pLight = nullptr;
-    uint8_t *state = nullptr;
-    // kind 2: the arrays launch_kd_or_init_all has set
-    const float *p1 = nullptr;
-    const int32_t *material = nullptr, *primMaterial = nullptr;
-    long nPrimMaterial = 0;
-    OneRandomState st{nullptr, nullptr, nullptr};
-    void *selHits = nullptr, *selRays = nullptr;
 };
 
 // One batch of a batch-mode launch: nnbvh_ray records, or with rays == nullptr the SOA<Ray> slices of a wavefront
@@ -107,13 +84,10 @@ KdWorkspace *kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream);
 // s->mu.
 int kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdBatch *batches, int n_batches);
 
-// The queue-head reset node and ONE walk launch.  The caller has checked the arguments (a scene without attribute
-// arrays, a mesh without an instance table), made the scene's device current and holds s->mu.
-int kd_launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdWalk &walk);
+// The queue-head reset node and ONE launch of a walk instance.  The caller has checked the arguments
+// (a scene without attribute arrays, a mesh without an instance table), made the scene's device current and holds s->mu.
+int launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const WalkJob &walk);
 // slot 0..KdWorkspace::kWalk-1 of the workspace's walk arrays, grown to `bytes`
 bool kd_walk_scratch(KdWorkspace *w, int slot, size_t bytes, void **out);
-// or_init without compaction: every item's first segment ray, reservoir state and cleared outputs
-hipError_t launch_kd_or_init_all(const float *p0, const float *p1, WavefrontCount cnt, OneRandomState st, void *rays,
-                                 void *selHits, void *selRays, int maxBlocks, hipStream_t stream);
 
 }  // namespace nnbvh

@@ -83,20 +83,9 @@ struct KdParams {
     int32_t *bHcPrim[kKdMaxBatches];
     int32_t *bHcInst[kKdMaxBatches];
     // walk mode (the WALK instances), appended again: the shading mesh the hit's pi / n come from and
-    // the per-item arrays of the walk.  One batch; a lane's ray tag is its work item
+    // the per-item arrays of the walk (walk_math.h).  One batch; a lane's ray tag is its work item
     MeshView wMesh;
-    const uint8_t *wPrimClass;       // WALK 1: class per primitive id, nullable
-    long wNPrimClass;
-    const float4 *wPLight;           // WALK 1: the light point of each item
-    uint8_t *wState;                 // WALK 1: 0 at launch; 1 blocked, 2 the caller's to finish
-    const float *wP1;                // WALK 2: the segment's end point of each item
-    const int32_t *wMaterial;        // WALK 2: the material each item looks for
-    const int32_t *wPrimMaterial;    // WALK 2: material per primitive id, nullable
-    long wNPrimMaterial;
-    OneRandomState wSt;              // WALK 2: PCG32 state and reservoir weights per item
-    float4 *wSelHits, *wSelRays;     // WALK 2: selected hit record and its segment ray per item
-    int wMaxSurfaces;                // Intersect calls an item may make
-    int32_t *wUnfinished;            // nullable: counts the items that would start one more
+    WalkParams walk;
 };
 
 // A lane takes up the ray {R0, R1} = {o, tMax} {d, time}: the reciprocals (aggregates.cpp:980), the shear, the
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
         if (nIdle == 64 || (sR > sI && sR > sP)) {
             // ---- retire finished rays, refill idle lanes ------------------------------------
             const int ri = isIdle ? __float_as_int(cold[kColdRi][lane]) : -1;
-            // WALK: the lane's item walks on from nextO in direction nextD / would start call wMaxSurfaces + 1
+            // WALK: the lane's item walks on from nextO in direction nextD / would start call walk.maxSurfaces + 1
             [[maybe_unused]] bool goOn = false, capped = false;
             [[maybe_unused]] V3 nextO = {0.0f, 0.0f, 0.0f}, nextD = {0.0f, 0.0f, 0.0f};
             [[maybe_unused]] float nextTMax = 1.0f, nextTime = 0.0f;  // aggregate.Intersect(r, 1), time 0: WALK 2
@@ -270,23 +259,24 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                     const float4 h1 = {cold[kColdHit + 3][lane], __int_as_float(visited), __int_as_float(tests),
                                        needHost ? __int_as_float(-1) : 0.0f};
                     if constexpr (WALK == 1) {
-                        goOn = w2_str_item<PATCH != 0>(p.wMesh, r0, r1, h0, h1, ri, p.wPrimClass, p.wNPrimClass,
-                                                       p.wPLight, p.wState, nextO, nextD);
+                        goOn = w2_str_item<PATCH != 0>(p.wMesh, r0, r1, h0, h1, ri, p.walk.primClass, p.walk.nPrimClass,
+                                                       p.walk.pLight, p.walk.state, nextO, nextD);
                         nextTMax = r0.w;  // tMax is the work item's, unchanged (intersect.h:175, :187)
                         nextTime = r1.w;
                         // the spawned ray has a zero direction: the walk ends, the ray arrives (state stays 0)
                         if (goOn && nextD.x == 0.0f && nextD.y == 0.0f && nextD.z == 0.0f) goOn = false;
                     } else {
-                        goOn = w2_or_item<PATCH != 0>(p.wMesh, r0, r1, h0, h1, ri, p.wP1, p.wMaterial, p.wPrimMaterial,
-                                                      p.wNPrimMaterial, p.wSt, p.wSelHits, p.wSelRays, nextO, nextD);
+                        goOn = w2_or_item<PATCH != 0>(p.wMesh, r0, r1, h0, h1, ri, p.walk.p1, p.walk.material,
+                                                      p.walk.primMaterial, p.walk.nPrimMaterial, p.walk.st,
+                                                      p.walk.selHits, p.walk.selRays, nextO, nextD);
                     }
                     if (goOn) {
                         const int calls = __float_as_int(cold[kColdCalls][lane]);
-                        if (calls >= p.wMaxSurfaces) {  // the caller's to finish, as w2_mark_unfinished marks it
+                        if (calls >= p.walk.maxSurfaces) {  // the caller's to finish, as w2_mark_unfinished marks it
                             goOn = false;
                             capped = true;
-                            if constexpr (WALK == 1) p.wState[ri] = 2;
-                            else p.wSelHits[2 * (long)ri + 1].w = __int_as_float(-1);
+                            if constexpr (WALK == 1) p.walk.state[ri] = 2;
+                            else p.walk.selHits[2 * (long)ri + 1].w = __int_as_float(-1);
                         } else {
                             cold[kColdCalls][lane] = __int_as_float(calls + 1);
                         }
@@ -369,7 +359,8 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
             int nTake = nIdle;
             if constexpr (WALK != 0) {
                 const unsigned long long cm = __ballot(capped);
-                if (p.wUnfinished && cm != 0ull && lane == __ffsll((long long)cm) - 1) atomicAdd(p.wUnfinished, __popcll(cm));
+                if (p.walk.unfinished && cm != 0ull && lane == __ffsll((long long)cm) - 1)
+                    atomicAdd(p.walk.unfinished, __popcll(cm));
                 if (goOn) {  // same item, same lane: cold[kColdRi] stays
                     const float4 a = {nextO.x, nextO.y, nextO.z, nextTMax}, b = {nextD.x, nextD.y, nextD.z, nextTime};
                     KD_BEGIN_RAY(a, b);
@@ -1300,54 +1291,7 @@ int nnbvh_kd_intersect_any(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, 
 
 }  // extern "C"
 
-// ---- the walk calls' launchers (capi_wavefront.cpp: nnbvh_kd_wavefront_walk_*).  They stand last in the file so that
-// the kernels above keep their places in the compiler's output ----------------------------------------------------
-namespace nnbvh {
-
-// or_init (wavefront2.hip) for the walk instances: EVERY item's first segment ray goes to rays[i], a zero direction
-// included (the walk kernel ends such an item at its fetch), so there is no list to compact and nothing to count.
-// The per-item base interaction is not kept: the walk step has pi / n in registers.  (A template, so that it is emitted
-// with the walk instances behind the existing kernels.)
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void kd_or_init_all(const float *p0, const float *p1, WavefrontCount cnt,
-                                                      OneRandomState st, float4 *rays, float4 *selHits,
-                                                      float4 *selRays) {
-    int n = cnt.n;
-    if (cnt.nDev) {
-        const int nd = *cnt.nDev;
-        n = nd < 0 ? 0 : (nd < n ? nd : n);
-    }
-    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
-        const V3 a0 = {p0[3 * (long)i], p0[3 * (long)i + 1], p0[3 * (long)i + 2]};
-        const V3 a1 = {p1[3 * (long)i], p1[3 * (long)i + 1], p1[3 * (long)i + 2]};
-        Pcg32 g;  // WeightedReservoirSampler wrs(Hash(w.p0, w.p1)), aggregate.cpp:94-96
-        pcg32_set_sequence(g, hash_6f(a0, a1));
-        st.rng[2 * (long)i] = g.state;
-        st.rng[2 * (long)i + 1] = g.inc;
-        st.weights[2 * (long)i] = 0.0f;
-        st.weights[2 * (long)i + 1] = 0.0f;
-        selHits[2 * (long)i] = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
-        selHits[2 * (long)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        selRays[2 * (long)i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        selRays[2 * (long)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        V3 o, d;
-        spawn_ray_to(a0, a0, {0.0f, 0.0f, 0.0f}, a1, o, d);  // r = Interaction(w.p0).SpawnRayTo(w.p1), :97-99
-        rays[2 * (long)i] = make_float4(o.x, o.y, o.z, 1.0f);  // aggregate.Intersect(r, 1), :102
-        rays[2 * (long)i + 1] = make_float4(d.x, d.y, d.z, 0.0f);
-    }
-}
-
-}  // namespace nnbvh
-
-hipError_t nnbvh::launch_kd_or_init_all(const float *p0, const float *p1, WavefrontCount cnt, OneRandomState st,
-                                        void *rays, void *selHits, void *selRays, int maxBlocks, hipStream_t stream) {
-    int blocks = (cnt.n + 255) / 256;
-    blocks = blocks < 1 ? 1 : (blocks < maxBlocks ? blocks : maxBlocks);
-    hipLaunchKernelGGL(kd_or_init_all<256>, dim3(blocks), dim3(256), 0, stream, p0, p1, cnt, st, (float4 *)rays,
-                       (float4 *)selHits, (float4 *)selRays);
-    return hipGetLastError();
-}
-
+// ---- the walk calls' launchers (capi_wavefront.cpp: nnbvh_kd_wavefront_walk_*) ------------------------------------
 bool nnbvh::kd_walk_scratch(KdWorkspace *w, int slot, size_t bytes, void **out) {
     if (!kd_grow(&w->walk[slot], &w->walk_bytes[slot], std::max<size_t>(bytes, 16), "hipMalloc(walk workspace)"))
         return false;
@@ -1355,7 +1299,7 @@ bool nnbvh::kd_walk_scratch(KdWorkspace *w, int slot, size_t bytes, void **out) 
     return true;
 }
 
-int nnbvh::kd_launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdWalk &k) {
+int nnbvh::launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const WalkJob &k) {
     KdParams p{};
     kd_fill_scene(s, w, p);
     p.nBatches = 1;
@@ -1366,19 +1310,7 @@ int nnbvh::kd_launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream,
     const ShadingMeshDevice &m = *k.mesh;
     p.wMesh = {m.verts, m.triVerts, m.patchVerts, m.normals, m.uvs, m.tangents, m.faceIndices, m.triFlags, m.nTris,
                m.defaultFlags, nullptr, 0, nullptr, nullptr};  // kd scenes have one level
-    p.wPrimClass = k.primClass;
-    p.wNPrimClass = k.nPrimClass;
-    p.wPLight = k.pLight;
-    p.wState = k.state;
-    p.wP1 = k.p1;
-    p.wMaterial = k.material;
-    p.wPrimMaterial = k.primMaterial;
-    p.wNPrimMaterial = k.nPrimMaterial;
-    p.wSt = k.st;
-    p.wSelHits = (float4 *)k.selHits;
-    p.wSelRays = (float4 *)k.selRays;
-    p.wMaxSurfaces = k.maxSurfaces;
-    p.wUnfinished = k.unfinished;
+    p.walk = k.a;
     // the lean instance with the triangle-only interaction where neither the scene nor the mesh holds patches, else the
     // PATCH = 1 instance with the patch-capable one (launch_str_step's choice of FULL); each with both offset widths
     void (*const kernels[8])(KdParams) = {

@@ -1,10 +1,12 @@
-// walk_math.h — one item of one step of the IntersectShadowTr / IntersectOneRandom walks (wavefront/intersect.h:
-// 183-256, wavefront/aggregate.cpp:100-108) for the walk instances of the kd-tree trace kernel (kd_trace.hip), which
-// run the step inside the lane that has just finished the closest-hit walk.  w2_hit_pi_n is shared with the fused
-// pass steps of the bounded BVH calls (wavefront2.hip: str_step, or_step_fused); w2_str_item / w2_or_item are those
-// steps' per-item bodies — the same verdicts in the same order, calling the same functions (w2_hit_pi_n,
-// spawn_ray_to, the PCG32 / reservoir update) — without the list bookkeeping around them.  (The pass kernels keep
-// their own text: routed through these functions they compile to different code, and their ISA is pinned.)
+// walk_math.h — the IntersectShadowTr / IntersectOneRandom walks (wavefront/intersect.h:183-256,
+// wavefront/aggregate.cpp:100-108) as the walk instances of both trace kernels run them (bvh_trace.hip modes 4 / 5,
+// kd_trace.hip modes 4 / 5), inside the lane that has just finished the closest-hit walk: the per-item
+// arrays (WalkParams, one member of either kernel's arguments), the launch job both launchers take (WalkJob) and the
+// per-item bodies of the retire step.  w2_hit_pi_n is shared with the fused pass steps of the bounded BVH calls
+// (wavefront2.hip: str_step, or_step_fused); w2_str_item / w2_or_item are those steps' per-item bodies — the same
+// verdicts in the same order, calling the same functions (w2_hit_pi_n, spawn_ray_to, the PCG32 / reservoir update) —
+// without the list bookkeeping around them.  (The pass kernels keep their own text: routed through these functions
+// they compile to different code, and their ISA is pinned.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +16,37 @@
 #include "wavefront2.h"
 
 namespace nnbvh {
+
+// The per-item arrays of a walk: the last member of TraceParams and of KdParams, behind the kernel's shading mesh.
+struct WalkParams {
+    const uint8_t *primClass;       // WALK 1: class per primitive id, nullable
+    long nPrimClass;
+    const float4 *pLight;           // WALK 1: the light point of each item
+    uint8_t *state;                 // WALK 1: 0 at launch; 1 blocked, 2 the caller's to finish
+    const float *p1;                // WALK 2: the segment's end point of each item
+    const int32_t *material;        // WALK 2: the material each item looks for
+    const int32_t *primMaterial;    // WALK 2: material per primitive id, nullable
+    long nPrimMaterial;
+    OneRandomState st;              // WALK 2: PCG32 state and reservoir weights per item
+    float4 *selHits, *selRays;      // WALK 2: selected hit record and its segment ray per item
+    int maxSurfaces;                // Intersect calls an item may make
+    int32_t *unfinished;            // nullable: counts the items that would start one more
+};
+
+// One launch of a walk instance of a trace kernel behind its queue reset node (launch_walk: capi_trace.cpp for BVH
+// scenes, kd_trace.hip for kd-tree scenes), over the items whose first rays are the records `rays`: item i is ray i,
+// and the batch holds min(n, max(*d_n, 0)) of them (d_n nullable).  The caller has checked the arguments, the type's
+// refusals among them, and holds the scene's lock.
+struct WalkJob {
+    int kind = 1;  // 1: IntersectShadowTr's walk, 2: IntersectOneRandom's
+    const ShadingMeshDevice *mesh = nullptr;
+    const void *rays = nullptr;
+    int64_t n = 0;
+    const int32_t *d_n = nullptr;
+    // kind 1: state[] is 0 and pLight[] set for every item (str_init); kind 2: the arrays launch_or_init_all
+    // (wavefront2.h) has set; unfinished (nullable) is zero before the launch
+    WalkParams a{};
+};
 
 // pi low / high and n of the SurfaceInteraction of hit {h0, h1} of the ray whose second half is r1;
 // false: a hit the device cannot finish (the post-pass's status is neither TRIANGLE nor PATCH)

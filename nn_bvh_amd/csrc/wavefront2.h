@@ -36,6 +36,10 @@ struct OneRandomState {  // per work item, device arrays
 hipError_t launch_or_init(const float *p0, const float *p1, WavefrontCount cnt, OneRandomState st, void *raysOut,
                           int32_t *origOut, int32_t *counter, void *selHits, void *selRays, int maxBlocks,
                           hipStream_t stream);
+// or_init without compaction, for the walk instances of the trace kernels: every item's first segment ray, reservoir
+// state and cleared outputs (st.pi is not written)
+hipError_t launch_or_init_all(const float *p0, const float *p1, WavefrontCount cnt, OneRandomState st, void *rays,
+                              void *selHits, void *selRays, int maxBlocks, hipStream_t stream);
 hipError_t launch_or_step(const void *raysCur, const void *hitsCur, const void *intrCur, const int32_t *origCur,
                           const int32_t *nCur, const float *p1, const int32_t *material,
                           const int32_t *primMaterial, long nPrimMaterial, OneRandomState st, void *raysNext,

@@ -465,6 +465,39 @@ __global__ __launch_bounds__(kW2Block) void w2_mark_unfinished(const float4 *ray
     }
 }
 
+// or_init for the walk instances of the trace kernels (both trees): EVERY item's first segment ray goes to rays[i], a
+// zero direction included (the walk kernel ends such an item at its fetch), so there is no list to compact and nothing
+// to count.  The per-item base interaction is not kept: the walk step has pi / n in registers.  (A template, so that it
+// is emitted behind the kernels above.)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void or_init_all(const float *p0, const float *p1, WavefrontCount cnt,
+                                                   OneRandomState st, float4 *rays, float4 *selHits,
+                                                   float4 *selRays) {
+    int n = cnt.n;
+    if (cnt.nDev) {
+        const int nd = *cnt.nDev;
+        n = nd < 0 ? 0 : (nd < n ? nd : n);
+    }
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const V3 a0 = {p0[3 * (long)i], p0[3 * (long)i + 1], p0[3 * (long)i + 2]};
+        const V3 a1 = {p1[3 * (long)i], p1[3 * (long)i + 1], p1[3 * (long)i + 2]};
+        Pcg32 g;  // WeightedReservoirSampler wrs(Hash(w.p0, w.p1)), aggregate.cpp:94-96
+        pcg32_set_sequence(g, hash_6f(a0, a1));
+        st.rng[2 * (long)i] = g.state;
+        st.rng[2 * (long)i + 1] = g.inc;
+        st.weights[2 * (long)i] = 0.0f;
+        st.weights[2 * (long)i + 1] = 0.0f;
+        selHits[2 * (long)i] = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
+        selHits[2 * (long)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        selRays[2 * (long)i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        selRays[2 * (long)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        V3 o, d;
+        spawn_ray_to(a0, a0, {0.0f, 0.0f, 0.0f}, a1, o, d);  // r = Interaction(w.p0).SpawnRayTo(w.p1), :97-99
+        rays[2 * (long)i] = make_float4(o.x, o.y, o.z, 1.0f);  // aggregate.Intersect(r, 1), :102
+        rays[2 * (long)i + 1] = make_float4(d.x, d.y, d.z, 0.0f);
+    }
+}
+
 // ---- launchers ----------------------------------------------------------------------------------
 hipError_t launch_str_init(const nnbvh_ray_soa &q, WavefrontCount cnt, void *rays, int32_t *orig, float4 *pLight,
                            uint8_t *state, int maxBlocks, hipStream_t stream) {
@@ -563,6 +596,13 @@ hipError_t launch_w2_mark_unfinished(const void *raysLeft, const int32_t *origLe
                                      hipStream_t stream) {
     hipLaunchKernelGGL(w2_mark_unfinished, dim3(w2_grid(left.n, maxBlocks)), dim3(kW2Block), 0, stream,
                        (const float4 *)raysLeft, origLeft, left, state, (float4 *)selHits, unfinished);
+    return hipGetLastError();
+}
+// (last: or_init_all is then emitted behind the kernels above)
+hipError_t launch_or_init_all(const float *p0, const float *p1, WavefrontCount cnt, OneRandomState st, void *rays,
+                              void *selHits, void *selRays, int maxBlocks, hipStream_t stream) {
+    hipLaunchKernelGGL(or_init_all<kW2Block>, dim3(w2_grid(cnt.n, maxBlocks)), dim3(kW2Block), 0, stream, p0, p1, cnt,
+                       st, (float4 *)rays, (float4 *)selHits, (float4 *)selRays);
     return hipGetLastError();
 }
 

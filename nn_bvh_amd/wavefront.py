@@ -375,6 +375,31 @@ class WavefrontAggregate:
             self._name("intersect_closest_and_shadow_items_candidates"))
         return hits
 
+    def _shadow_tr_args(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state):
+        """The arguments every IntersectShadowTr entry point starts with (scene to d_state), and the queue's wire
+        record, which the caller keeps alive over the call."""
+        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
+        soa = shadow_queue._wire()
+        return (self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(),
+                *_ptr_count(self.prim_class), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(),
+                L.data_ptr(), L.shape[0], state.data_ptr() if state is not None else None), soa
+
+    def _one_random_args(self, max_items, p0, p1, material, shading_mesh, prim_material, size):
+        """IntersectOneRandom's inputs checked, its four result tensors, and the arguments every one of its entry
+        points starts with (scene to d_weight_sum)."""
+        for t in (p0, p1):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 3
+        assert material.dtype == torch.int32 and material.is_contiguous()
+        n = int(max_items)
+        sel_hits = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
+        sel_rays = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
+        pdf = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
+        wsum = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
+        args = (self.aggregate._h, shading_mesh._h, n, p0.data_ptr(), p1.data_ptr(), material.data_ptr(),
+                size.data_ptr() if size is not None else None, *_ptr_count(prim_material), sel_hits.data_ptr(),
+                sel_rays.data_ptr(), pdf.data_ptr(), wsum.data_ptr())
+        return (sel_hits, sel_rays, pdf, wsum), args
+
     def IntersectShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None,
                           max_passes=None, unfinished=None, max_surfaces=None):
         """IntersectShadowTr (wavefront/aggregate.cpp:70-88, TraceTransmittance of wavefront/intersect.h:
@@ -391,12 +416,7 @@ class WavefrontAggregate:
         would start one more Intersect call gets state 2, adds nothing and is counted in unfinished."""
         self._bvh_only("IntersectShadowTr")
         _one_bound("IntersectShadowTr", max_passes, max_surfaces)
-        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
-        soa = shadow_queue._wire()
-        pc = self.prim_class
-        args = (self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(),
-                *_ptr_count(pc), Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(),
-                L.shape[0], state.data_ptr() if state is not None else None)
+        args, _soa = self._shadow_tr_args(max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if max_surfaces is not None:
             check(_lib.lib().nnbvh_wavefront_walk_shadow_tr(
@@ -423,18 +443,7 @@ class WavefrontAggregate:
         trace launch; an item whose segment would start one more Intersect call gets instance = -1 and is counted."""
         self._bvh_only("IntersectOneRandom")
         _one_bound("IntersectOneRandom", max_passes, max_surfaces)
-        for t in (p0, p1):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 3
-        assert material.dtype == torch.int32 and material.is_contiguous()
-        n = int(max_items)
-        sel_hits = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
-        sel_rays = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
-        pdf = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
-        wsum = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
-        pm = prim_material
-        args = (self.aggregate._h, shading_mesh._h, n, p0.data_ptr(), p1.data_ptr(), material.data_ptr(),
-                size.data_ptr() if size is not None else None, *_ptr_count(pm), sel_hits.data_ptr(),
-                sel_rays.data_ptr(), pdf.data_ptr(), wsum.data_ptr())
+        results, args = self._one_random_args(max_items, p0, p1, material, shading_mesh, prim_material, size)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if max_surfaces is not None:
             check(_lib.lib().nnbvh_wavefront_walk_one_random(
@@ -446,7 +455,7 @@ class WavefrontAggregate:
             check(_lib.lib().nnbvh_wavefront_intersect_one_random_bounded(
                 *args, int(max_passes), _unfinished_ptr(unfinished), stream),
                 "nnbvh_wavefront_intersect_one_random_bounded")
-        return sel_hits, sel_rays, pdf, wsum
+        return results
 
     def WalkShadowTr(self, max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state=None,
                      max_surfaces=65536, unfinished=None):
@@ -456,14 +465,10 @@ class WavefrontAggregate:
         and is counted in unfinished (optional int32 [1] device tensor).  Kernel launches only: capturable after one
         warm-up call with the same max_rays."""
         self._kd_only("WalkShadowTr")
-        _check_shadow_args(shadow_queue, Ld, r_u, r_l, pixel_index, L)
-        soa = shadow_queue._wire()
-        pc = self.prim_class
+        args, _soa = self._shadow_tr_args(max_rays, shadow_queue, shading_mesh, Ld, r_u, r_l, pixel_index, L, state)
         check(_lib.lib().nnbvh_kd_wavefront_walk_shadow_tr(
-            self.aggregate._h, shading_mesh._h, int(max_rays), ptr(soa), shadow_queue.size.data_ptr(), *_ptr_count(pc),
-            Ld.data_ptr(), r_u.data_ptr(), r_l.data_ptr(), pixel_index.data_ptr(), L.data_ptr(), L.shape[0],
-            state.data_ptr() if state is not None else None, int(max_surfaces), _unfinished_ptr(unfinished),
-            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_kd_wavefront_walk_shadow_tr")
+            *args, int(max_surfaces), _unfinished_ptr(unfinished), torch.cuda.current_stream(self.device).cuda_stream),
+            "nnbvh_kd_wavefront_walk_shadow_tr")
 
     def WalkOneRandom(self, max_items, p0, p1, material, shading_mesh, prim_material=None, size=None,
                       max_surfaces=65536, unfinished=None):
@@ -473,17 +478,8 @@ class WavefrontAggregate:
         passes.  An item whose segment would start one more call gets instance = -1 in its selected hit record and
         is counted in unfinished."""
         self._kd_only("WalkOneRandom")
-        for t in (p0, p1):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 3
-        assert material.dtype == torch.int32 and material.is_contiguous()
-        n = int(max_items)
-        sel_hits = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
-        sel_rays = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=self.device)
-        pdf = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
-        wsum = torch.zeros(max(n, 1), dtype=torch.float32, device=self.device)
+        results, args = self._one_random_args(max_items, p0, p1, material, shading_mesh, prim_material, size)
         check(_lib.lib().nnbvh_kd_wavefront_walk_one_random(
-            self.aggregate._h, shading_mesh._h, n, p0.data_ptr(), p1.data_ptr(), material.data_ptr(),
-            size.data_ptr() if size is not None else None, *_ptr_count(prim_material), sel_hits.data_ptr(),
-            sel_rays.data_ptr(), pdf.data_ptr(), wsum.data_ptr(), int(max_surfaces), _unfinished_ptr(unfinished),
-            torch.cuda.current_stream(self.device).cuda_stream), "nnbvh_kd_wavefront_walk_one_random")
-        return sel_hits, sel_rays, pdf, wsum
+            *args, int(max_surfaces), _unfinished_ptr(unfinished), torch.cuda.current_stream(self.device).cuda_stream),
+            "nnbvh_kd_wavefront_walk_one_random")
+        return results

@@ -178,6 +178,53 @@ def test_walk_calls_reject_bad_arguments_before_any_device_work(nnbvh_lib):
                 ctypes.memset(ctypes.addressof(buf) + at, 0, 8 if at % 8 == 0 else 4)
 
 
+def test_walk_calls_of_both_trees_refuse_common_bad_arguments_in_the_same_words(nnbvh_lib):
+    """The bad arguments that need no per-type field: the BVH call and the kd-tree call of the same walk return
+    NNBVH_ERR_ARG and set the same text behind their own name.  Zeroed stand-in handles: nothing reaches a device."""
+    fake_scene, fake_mesh = ctypes.create_string_buffer(1 << 16), ctypes.create_string_buffer(1 << 16)
+    S, M = ctypes.addressof(fake_scene), ctypes.addressof(fake_mesh)
+    soa = np.zeros(1, _lib.RAY_SOA_DTYPE)
+    for k in ("ox", "oy", "oz", "dx", "dy", "dz", "tmax"):
+        soa[k] = 64  # non-NULL, never read
+    nosoa = soa.copy()
+    nosoa["dx"] = 0
+    Q, A = soa.ctypes.data, 64
+
+    def shadow(prefix, s=S, m=M, n=8, q=Q, npc=0, arrays=(A, A, A, A, A), npx=8, cap=4):
+        fn = getattr(nnbvh_lib, f"nnbvh_{prefix}wavefront_walk_shadow_tr")
+        return fn(s, m, n, q, None, None, npc, *arrays, npx, None, cap, None, None)
+
+    def one_random(prefix, s=S, m=M, n=8, arrays=(A, A, A), npm=0, outs=(A, A, A), cap=4):
+        fn = getattr(nnbvh_lib, f"nnbvh_{prefix}wavefront_walk_one_random")
+        return fn(s, m, n, *arrays, None, None, npm, *outs, None, cap, None, None)
+
+    common = [dict(s=None), dict(m=None), dict(cap=0), dict(cap=65537), dict(cap=-1), dict(n=-1)]
+    cases = {shadow: common + [dict(npc=-1), dict(npx=-1), dict(q=None), dict(q=nosoa.ctypes.data)] +
+             [dict(arrays=tuple(None if j == k else A for j in range(5))) for k in range(5)],
+             one_random: common + [dict(npm=-1)] +
+             [dict(arrays=tuple(None if j == k else A for j in range(3))) for k in range(3)] +
+             [dict(outs=tuple(None if j == k else A for j in range(3))) for k in range(3)]}
+    for call, walk in ((shadow, "wavefront_walk_shadow_tr"), (one_random, "wavefront_walk_one_random")):
+        def refusal(prefix, **kw):
+            assert call(prefix, **kw) == ERR_ARG, (prefix + walk, kw)
+            name, _, text = _lib.last_error().partition(": ")
+            assert name == prefix + walk and text, (_lib.last_error(), kw)
+            return text
+
+        texts = set()
+        for kw in cases[call]:
+            bvh, kd = refusal("", **kw), refusal("kd_", **kw)
+            assert bvh == kd, (walk, kw, bvh, kd)
+            texts.add(bvh)
+        assert len(texts) == 5, texts  # no scene, no mesh, the cap, a negative size, a null array
+        ctypes.memmove(ctypes.addressof(fake_mesh), ctypes.byref(ctypes.c_int32(1)), 4)  # the mesh on another device
+        try:
+            bvh, kd = refusal("", n=0), refusal("kd_", n=0)
+        finally:
+            ctypes.memset(ctypes.addressof(fake_mesh), 0, 4)
+        assert bvh == kd and "different devices" in bvh and bvh not in texts
+
+
 def test_max_surfaces_selects_the_walk_on_bvh_aggregates_only():
     pytest.importorskip("torch")
     from nn_bvh_amd.kdtree import KdTreeAggregate

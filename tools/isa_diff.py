@@ -5,7 +5,8 @@ Usage: python tools/isa_diff.py PARENT_REV [--src bvh_trace.hip,kd_trace.hip,int
 PARENT_REV's nn_bvh_amd/csrc and include are unpacked into a temporary directory (git archive); each source is
 compiled there and in the tree with the product's code generation flags, and per kernel the report says `same` or
 shows the first differing line; the rest of the file (metadata) is covered by a comparison of the whole file.  Lines
-that carry the compilation unit's hash (__hip_cuid_) are left out.
+that carry the compilation unit's hash (__hip_cuid_) are left out, and so is the number the compiler gives a function
+by its place in the file (.LBB28_3, BB28_5, .Lfunc_end28): a kernel that leaves or joins a file renumbers those behind it.
 --kernarg: differences that come from a changed kernel-argument struct (offset of a scalar load from the kernarg
 segment, kernarg size, .offset / .size of the argument metadata) count as `same`; they are counted and reported.
 The register, spill, scratch and LDS figures of the metadata are compared in either mode.  Exit status 1 if a
@@ -27,12 +28,13 @@ KERNARG = [(re.compile(r"^(\s*s_load_dword\w*\s+\S+,\s*s\[\d+:\d+\],\s*)0x[0-9a-
            (re.compile(r"^(\s*\.amdhsa_kernarg_size)\s+\d+"), r"\1 N"),
            (re.compile(r"^(\s*\.kernarg_segment_size:)\s+\d+"), r"\1 N"),
            (re.compile(r"^(\s*-?\s*\.(offset|size):)\s+\d+"), r"\1 N")]
+FUNC_NUMBER = re.compile(r"((?:\.L|\b)BB|\.Lfunc_begin|\.Lfunc_end)\d+")
 
 
 def assemble(root, src, out):
     subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", out, os.path.join(root, CSRC, src)], check=True,
                    stderr=subprocess.DEVNULL)
-    return [ln for ln in open(out).read().splitlines() if "__hip_cuid_" not in ln]
+    return [FUNC_NUMBER.sub(r"\1N", ln) for ln in open(out).read().splitlines() if "__hip_cuid_" not in ln]
 
 
 def kernels(lines):
