@@ -5,7 +5,10 @@
 // the reference's own constructor (src/pbrt/util/mesh.cpp:23-77, identity transform).  No restated
 // arithmetic.  Built by oracle/Makefile into oracle/_ref/ref_interaction (git-ignored); used to
 // validate oracle/nnbvh_oracle.c's orc_triangle_interaction and to generate
-// tests/golden/tri_interaction.npz (tests/golden/make_interaction_golden.py).
+// tests/golden/tri_interaction.npz (tests/golden/make_interaction_golden.py).  The identity transform is not a
+// no-op on signed zeros: the mesh constructors compute (1 * x + 0 * y) + 0 * z (+ 0), which stores a -0 coordinate
+// as +0 and keeps a -0 component of a normal or tangent only next to two negative ones
+// (tests/awkward_cases.py: as_the_reference_mesh_stores).
 //
 // With mode "blp": BilinearPatch::InteractionFromIntersection (shapes.h:1396-1489) on a one-patch
 // BilinearPatchMesh built by the reference's constructor (util/mesh.cpp:183-232).

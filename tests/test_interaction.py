@@ -184,13 +184,25 @@ def instance_oracle(kind, rec, m, mi, d, time, face_index=None):
     return out
 
 
-def assert_interaction_fields(got, exp, what, flags=None, xf_kind=None):
+def words_differ(a, b, nan_equal=False):
+    """float32 arrays word for word as uint32; nan_equal: a NaN of any sign and payload equals any other NaN (x86
+    and gfx950 differ in the sign of the default NaN), and nothing else is tolerated."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    diff = a.view(np.uint32) != b.view(np.uint32)
+    return diff & ~(np.isnan(a) & np.isnan(b)) if nan_equal else diff
+
+
+def assert_interaction_fields(got, exp, what, flags=None, xf_kind=None, nan_equal=False):
     """Device records `got` against instance_oracle's fields, every word as uint32; the message names the field
-    and, of the first differing record, the flag value and the kind of transform."""
+    and, of the first differing record, the flag value and the kind of transform.  nan_equal (opt-in, for inputs
+    that produce NaNs): see words_differ; face_index stays an integer comparison."""
     for name, e in exp.items():
         a = np.ascontiguousarray(got[name]).view(np.uint32).reshape(len(got), -1)
         b = np.ascontiguousarray(e).view(np.uint32).reshape(len(got), -1)
-        bad = np.nonzero((a != b).any(1))[0]
+        diff = a != b
+        if nan_equal and np.asarray(e).dtype == np.float32 and got[name].dtype == np.float32:
+            diff = words_differ(got[name], e, True).reshape(len(got), -1)
+        bad = np.nonzero(diff.any(1))[0]
         if len(bad):
             k = bad[0]
             where = "" if flags is None else f", flags {int(np.asarray(flags)[k])}"

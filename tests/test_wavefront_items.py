@@ -185,8 +185,9 @@ def expected_field(field, queue, rows, intr, hits, d):
     return r[field].T
 
 
-def check_slices(name, q, sl, intr, hits, d, expect_idx=None):
-    """Queue `name`'s index set and every requested slice against the post-pass records."""
+def check_slices(name, q, sl, intr, hits, d, expect_idx=None, nan_equal=False):
+    """Queue `name`'s index set and every requested slice against the post-pass records.  nan_equal (opt-in, for
+    inputs that produce NaNs): a word that is a NaN on both sides counts as equal."""
     size = q.Size()
     k = min(size, q.capacity)
     idx = q.items[:k].cpu().numpy()
@@ -208,7 +209,8 @@ def check_slices(name, q, sl, intr, hits, d, expect_idx=None):
         if field == "face_index":
             assert np.array_equal(g, e), (name, field)
         else:
-            bad = np.nonzero((bits(g) != bits(e)).reshape(-1, hit.sum()).any(0))[0]
+            diff = (bits(g) != bits(e)) & ~(nan_equal & np.isnan(g) & np.isnan(e))
+            bad = np.nonzero(diff.reshape(-1, hit.sum()).any(0))[0]
             assert len(bad) == 0, f"{name}.{field} differs on {len(bad)} of {hit.sum()} items, first {rows[hit][bad[:5]]}"
     return rows
 
