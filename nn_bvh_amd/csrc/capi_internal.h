@@ -43,12 +43,12 @@ struct Workspace {
     size_t in_bytes = 0, out_bytes = 0, aux_bytes = 0;
     void *d_hits = nullptr;  // hit records of the *_items calls made without d_hits
     size_t hits_bytes = 0;
-    // grow-only scratch of the multi-pass entry points (IntersectShadowTr / IntersectOneRandom): ping-pong ray and
-    // hit buffers, per-item state, counters.  Per stream like the queue heads: the calls are asynchronous on their
-    // stream, so two streams must not share them
-    static constexpr int kScratch = 12;
-    void *scratch[kScratch] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[kScratch] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // grow-only scratch of the multi-pass and walk entry points (IntersectShadowTr / IntersectOneRandom): ping-pong
+    // ray records and item lists, the hit records of a pass, per-item state, pass counters.  Per stream like the queue
+    // heads: the calls are asynchronous on their stream, so two streams must not share them
+    enum Slot { kRaysA, kRaysB, kHits, kOrigA, kOrigB, kPLight, kState, kCounters, kRng, kWeights, kScratch };
+    void *scratch[kScratch] = {};
+    size_t scratch_bytes[kScratch] = {};
 };
 
 // one slot of the host-buffer pipeline (nnbvh_intersect_closest / _any): device chunk buffers, events and — for

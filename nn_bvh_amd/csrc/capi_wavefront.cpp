@@ -447,6 +447,132 @@ static bool bounded_args_ok(const char *fn, const S *s, const nnbvh_shading_mesh
     return what.empty();
 }
 
+// ---- the pass calls: one loop per walk, two drivers -----------------------------------------------------------------
+// A pass is the trace of the current list and ONE fused step (wavefront2.hip), which appends the items that go on to
+// the next list and counts them.
+// Bounded driver (max_passes 1..kMaxBoundedPasses): every pass is enqueued up front, sized for the queue, and takes its
+// live count from count[k], which the step of pass k - 1 has counted up; the counters are cleared by one kernel node,
+// and what is left on the last list is marked unfinished.  Nothing inside waits for the device or copies from host
+// memory, so the call can be captured in a hipGraph once the stream's workspace has its size (a warm-up call with the
+// same queue capacity).  A pass over an empty list is a trace and a step whose waves exit at once.
+// Host-driven driver (max_passes == kUnbounded): after each step the host reads the next list's count, stops at zero
+// and sizes the next pass's grids by it; two counter words alternate, each cleared before it is appended to.
+static constexpr int kUnbounded = 0;
+
+// the counter that pass `pass` appends to; nullptr: the launch that clears it failed
+static int32_t *next_count(int32_t *count, int pass, bool bounded, int max_blocks, hipStream_t stream) {
+    if (bounded) return count + pass + 1;
+    int32_t *c = count + ((pass + 1) & 1);
+    return hip_ok(launch_zero_words(c, 1, max_blocks, stream), "pass count reset launch") ? c : nullptr;
+}
+
+// The caller has checked the arguments, holds the scene's lock, has cleared *d_unfinished and max_rays > 0.
+static int shadow_tr_passes(nnbvh_scene *s, Workspace *w, const nnbvh_shading_mesh *m, int32_t max_rays,
+                            const nnbvh_ray_soa *shadow_queue, const int32_t *d_size, const uint8_t *d_prim_class,
+                            int64_t n_prim_class, const float *d_Ld, const float *d_r_u, const float *d_r_l,
+                            const int32_t *d_pixel_index, float *d_L, int64_t n_pixels, uint8_t *d_state,
+                            int32_t max_passes, int32_t *d_unfinished, hipStream_t stream) {
+    const bool bounded = max_passes != kUnbounded;
+    const size_t n = (size_t)max_rays;
+    const int max_blocks = s->n_cus * 8;
+    void *cur, *next, *hits, *ocur, *onext, *pLight, *state, *counters;
+    if (!scratch(w, Workspace::kRaysA, n * 32, &cur) || !scratch(w, Workspace::kRaysB, n * 32, &next) ||
+        !scratch(w, Workspace::kHits, n * 32, &hits) || !scratch(w, Workspace::kOrigA, n * 4, &ocur) ||
+        !scratch(w, Workspace::kOrigB, n * 4, &onext) || !scratch(w, Workspace::kPLight, n * 16, &pLight) ||
+        !scratch(w, Workspace::kState, n, &state) ||
+        !scratch(w, Workspace::kCounters, (kMaxBoundedPasses + 1) * 4, &counters))
+        return NNBVH_ERR_DEVICE;
+    int32_t *count = (int32_t *)counters;  // bounded: count[k] is the size of pass k's list, k >= 1
+    const WavefrontCount cnt{max_rays, d_size};
+    if (bounded && !hip_ok(launch_zero_words(count, max_passes + 1, max_blocks, stream), "pass count reset launch"))
+        return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_str_init(*shadow_queue, cnt, cur, (int32_t *)ocur, (float4 *)pLight, (uint8_t *)state, max_blocks,
+                                stream), "shadow-tr init launch"))
+        return NNBVH_ERR_DEVICE;
+    const int32_t *d_n = d_size;  // pass 0 runs the queue itself: max_rays clamped by *d_size
+    int active = max_rays;
+    for (int pass = 0; bounded ? pass < max_passes : active > 0; ++pass) {
+        if (!bounded && pass > 4096) {
+            set_error("wavefront_intersect_shadow_tr: more than 4096 interface surfaces on one shadow ray");
+            return NNBVH_ERR_ARG;
+        }
+        int32_t *d_next = next_count(count, pass, bounded, max_blocks, stream);
+        if (!d_next) return NNBVH_ERR_DEVICE;
+        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = active, .d_n = d_n, .hits = hits});
+        if (rc != NNBVH_OK) return rc;
+        if (!hip_ok(launch_str_step(m->d, cur, hits, (const int32_t *)ocur, WavefrontCount{active, d_n}, d_prim_class,
+                                    (long)n_prim_class, (const float4 *)pLight, (uint8_t *)state, next,
+                                    (int32_t *)onext, d_next, max_blocks, stream), "shadow-tr step launch"))
+            return NNBVH_ERR_DEVICE;
+        if (!bounded && !read_count(d_next, stream, &active)) return NNBVH_ERR_DEVICE;
+        std::swap(cur, next);
+        std::swap(ocur, onext);
+        d_n = d_next;
+    }
+    if (bounded && !hip_ok(launch_w2_mark_unfinished(cur, (const int32_t *)ocur, WavefrontCount{max_rays, d_n},
+                                                     (uint8_t *)state, nullptr, d_unfinished, max_blocks, stream),
+                           "shadow-tr marking launch"))
+        return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
+                                  d_state, max_blocks, stream), "shadow-tr record launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
+// The caller has checked the arguments, holds the scene's lock, has cleared *d_unfinished and max_items > 0.
+static int one_random_passes(nnbvh_scene *s, Workspace *w, const nnbvh_shading_mesh *m, int32_t max_items,
+                             const float *d_p0, const float *d_p1, const int32_t *d_material, const int32_t *d_size,
+                             const int32_t *d_prim_material, int64_t n_prim_material, void *d_sel_hits,
+                             void *d_sel_rays, float *d_reservoir_pdf, float *d_weight_sum, int32_t max_passes,
+                             int32_t *d_unfinished, hipStream_t stream) {
+    const bool bounded = max_passes != kUnbounded;
+    const size_t n = (size_t)max_items;
+    const int max_blocks = s->n_cus * 8;
+    void *cur, *next, *hits, *ocur, *onext, *rng, *weights, *counters;
+    if (!scratch(w, Workspace::kRaysA, n * 32, &cur) || !scratch(w, Workspace::kRaysB, n * 32, &next) ||
+        !scratch(w, Workspace::kHits, n * 32, &hits) || !scratch(w, Workspace::kOrigA, n * 4, &ocur) ||
+        !scratch(w, Workspace::kOrigB, n * 4, &onext) || !scratch(w, Workspace::kRng, n * 16, &rng) ||
+        !scratch(w, Workspace::kWeights, n * 8, &weights) ||
+        !scratch(w, Workspace::kCounters, (kMaxBoundedPasses + 1) * 4, &counters))
+        return NNBVH_ERR_DEVICE;
+    int32_t *count = (int32_t *)counters;  // bounded: count[k] is the size of pass k's list
+    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};
+    const WavefrontCount cnt{max_items, d_size};
+    if (!hip_ok(launch_zero_words(count, bounded ? max_passes + 1 : 1, max_blocks, stream), "pass count reset launch") ||
+        !hip_ok(launch_or_init(d_p0, d_p1, cnt, st, cur, (int32_t *)ocur, count, d_sel_hits, d_sel_rays, max_blocks,
+                               stream), "one-random init launch"))
+        return NNBVH_ERR_DEVICE;
+    const int32_t *d_n = count;  // pass 0 runs the items whose first direction is not zero
+    int active = max_items;
+    if (!bounded && !read_count(d_n, stream, &active)) return NNBVH_ERR_DEVICE;
+    for (int pass = 0; bounded ? pass < max_passes : active > 0; ++pass) {
+        if (!bounded && pass > 65536) {
+            set_error("wavefront_intersect_one_random: more than 65536 surfaces on one segment");
+            return NNBVH_ERR_ARG;
+        }
+        int32_t *d_next = next_count(count, pass, bounded, max_blocks, stream);
+        if (!d_next) return NNBVH_ERR_DEVICE;
+        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = active, .d_n = d_n, .hits = hits});
+        if (rc != NNBVH_OK) return rc;
+        if (!hip_ok(launch_or_step_fused(m->d, cur, hits, (const int32_t *)ocur, WavefrontCount{active, d_n}, d_p1,
+                                         d_material, d_prim_material, (long)n_prim_material, st, next,
+                                         (int32_t *)onext, d_next, d_sel_hits, d_sel_rays, max_blocks, stream),
+                    "one-random step launch"))
+            return NNBVH_ERR_DEVICE;
+        if (!bounded && !read_count(d_next, stream, &active)) return NNBVH_ERR_DEVICE;
+        std::swap(cur, next);
+        std::swap(ocur, onext);
+        d_n = d_next;
+    }
+    if (bounded && !hip_ok(launch_w2_mark_unfinished(cur, (const int32_t *)ocur, WavefrontCount{max_items, d_n}, nullptr,
+                                                     d_sel_hits, d_unfinished, max_blocks, stream),
+                           "one-random marking launch"))
+        return NNBVH_ERR_DEVICE;
+    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
+        return NNBVH_ERR_DEVICE;
+    return NNBVH_OK;
+}
+
 // ---- the walk calls: IntersectShadowTr / IntersectOneRandom inside ONE trace launch, for scenes of either type ------
 // The walk instances of the trace kernels (bvh_trace.hip modes 4 / 5; kd_trace.hip, §5.7.1) run the
 // per-item loop inside the lane, so a call is five kernel nodes whatever max_surfaces is: queue-head reset,
@@ -456,7 +582,8 @@ static bool bounded_args_ok(const char *fn, const S *s, const nnbvh_shading_mesh
 enum { kWalkRays, kWalkOrig, kWalkPLight, kWalkState, kWalkRng, kWalkWeights };
 // BVH scenes: the slots the pass forms use for the same arrays; kd-tree scenes: the six walk arrays of their workspace
 static bool walk_scratch(Workspace *w, int which, size_t bytes, void **out) {
-    static constexpr int slot[6] = {0, 4, 6, 7, 10, 11};
+    static constexpr int slot[6] = {Workspace::kRaysA, Workspace::kOrigA, Workspace::kPLight,
+                                    Workspace::kState, Workspace::kRng,   Workspace::kWeights};
     return scratch(w, slot[which], bytes, out);
 }
 static bool walk_scratch(KdWorkspace *w, int which, size_t bytes, void **out) {
@@ -522,7 +649,7 @@ static int walk_one_random(const char *fn, S *s, const nnbvh_shading_mesh *m, in
     if (!walk_scratch(call.w, kWalkRays, n * 32, &rays) || !walk_scratch(call.w, kWalkRng, n * 16, &rng) ||
         !walk_scratch(call.w, kWalkWeights, n * 8, &weights))
         return NNBVH_ERR_DEVICE;
-    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};  // (the base interaction stays in registers)
+    OneRandomState st{nullptr, (uint64_t *)rng, (float *)weights};
     const WavefrontCount cnt{max_items, d_size};
     if (!hip_ok(launch_or_init_all(d_p0, d_p1, cnt, st, rays, d_sel_hits, d_sel_rays, max_blocks, stream),
                 "one-random init launch"))
@@ -819,8 +946,9 @@ int nnbvh_wavefront_record_shadow_device(const uint8_t *d_occluded, int32_t max_
 }
 
 // ---- IntersectShadowTr / IntersectOneRandom (wavefront/aggregate.cpp:70-116), media-free -------------
-// Host-driven loops of device passes; the only host round trip per pass is the 4-byte count of
-// items that go on (interface surfaces are rare: the usual shadow batch ends after its first pass).
+// The unbounded calls: shadow_tr_passes / one_random_passes (above) under their host-driven driver.  The only host
+// round trip per pass is the 4-byte count of the items that go on (interface surfaces are rare: the usual shadow batch
+// ends after its first pass).
 int nnbvh_wavefront_intersect_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays,
                                         const nnbvh_ray_soa *shadow_queue, const int32_t *d_size,
                                         const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld,
@@ -839,55 +967,8 @@ int nnbvh_wavefront_intersect_shadow_tr(nnbvh_scene *s, const nnbvh_shading_mesh
     hipStream_t stream = (hipStream_t)stream_;
     SceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
-    Workspace *w = call.w;
-    const size_t n = (size_t)max_rays;
-    void *raysA, *raysB, *hitsA, *hitsB, *origA, *origB, *pLight, *state, *counters, *intr;
-    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hitsA) ||
-        !scratch(w, 3, n * 32, &hitsB) || !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) ||
-        !scratch(w, 6, n * 16, &pLight) || !scratch(w, 7, n, &state) || !scratch(w, 8, 64, &counters))
-        return NNBVH_ERR_DEVICE;
-    int32_t *nCur = (int32_t *)counters, *nNext = nCur + 1;
-    const WavefrontCount cnt{max_rays, d_size};
-    const int max_blocks = s->n_cus * 8;
-    if (!hip_ok(launch_str_init(*shadow_queue, cnt, raysA, (int32_t *)origA, (float4 *)pLight, (uint8_t *)state,
-                                max_blocks, stream), "shadow-tr init launch"))
-        return NNBVH_ERR_DEVICE;
-    // the first pass covers the whole queue: its size is max_rays clamped by *d_size
-    if (d_size) {
-        if (!hip_ok(hipMemcpyAsync(nCur, d_size, 4, hipMemcpyDeviceToDevice, stream), "copy queue size"))
-            return NNBVH_ERR_DEVICE;
-    } else if (!hip_ok(hipMemcpyAsync(nCur, &max_rays, 4, hipMemcpyHostToDevice, stream), "copy queue size")) {
-        return NNBVH_ERR_DEVICE;
-    }
-    int active = max_rays;
-    for (int pass = 0; active > 0; ++pass) {
-        if (pass > 4096) {
-            set_error("wavefront_intersect_shadow_tr: more than 4096 interface surfaces on one shadow ray");
-            return NNBVH_ERR_ARG;
-        }
-        int rc = launch(s, w, stream, {.mode = 0, .rays = raysA, .n = active, .d_n = nCur, .hits = hitsA});
-        if (rc != NNBVH_OK) return rc;
-        if (!hip_ok(hipMemsetAsync(nNext, 0, 4, stream), "reset pass count") ||
-            !hip_ok(launch_str_classify(raysA, hitsA, (const int32_t *)origA, nCur, d_prim_class, (long)n_prim_class,
-                                        (uint8_t *)state, raysB, hitsB, (int32_t *)origB, nNext, active, max_blocks,
-                                        stream), "shadow-tr classify launch"))
-            return NNBVH_ERR_DEVICE;
-        int n_iface = 0;
-        if (!read_count(nNext, stream, &n_iface)) return NNBVH_ERR_DEVICE;
-        if (n_iface <= 0) break;
-        if (!scratch(w, 9, (size_t)n_iface * sizeof(nnbvh_interaction), &intr)) return NNBVH_ERR_DEVICE;
-        if (!hip_ok(launch_triangle_interactions(m->d, raysB, nullptr, hitsB, n_iface, nNext, intr, m->n_cus * 8, stream),
-                    "interaction kernel launch") ||
-            !hip_ok(hipMemsetAsync(nCur, 0, 4, stream), "reset pass count") ||
-            !hip_ok(launch_str_spawn(raysB, intr, (const int32_t *)origB, nNext, (const float4 *)pLight, (uint8_t *)state,
-                                     raysA, (int32_t *)origA, nCur, n_iface, max_blocks, stream), "shadow-tr spawn launch"))
-            return NNBVH_ERR_DEVICE;
-        if (!read_count(nCur, stream, &active)) return NNBVH_ERR_DEVICE;
-    }
-    if (!hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
-                                  d_state, max_blocks, stream), "shadow-tr record launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
+    return shadow_tr_passes(s, call.w, m, max_rays, shadow_queue, d_size, d_prim_class, n_prim_class, d_Ld, d_r_u, d_r_l,
+                            d_pixel_index, d_L, n_pixels, d_state, kUnbounded, nullptr, stream);
 }
 
 int nnbvh_wavefront_intersect_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_items,
@@ -908,54 +989,11 @@ int nnbvh_wavefront_intersect_one_random(nnbvh_scene *s, const nnbvh_shading_mes
     hipStream_t stream = (hipStream_t)stream_;
     SceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
-    Workspace *w = call.w;
-    const size_t n = (size_t)max_items;
-    void *raysA, *raysB, *hits, *origA, *origB, *pi, *rng, *weights, *counters, *intr;
-    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hits) ||
-        !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) || !scratch(w, 6, n * 36, &pi) ||
-        !scratch(w, 10, n * 16, &rng) || !scratch(w, 11, n * 8, &weights) || !scratch(w, 8, 64, &counters))
-        return NNBVH_ERR_DEVICE;
-    int32_t *nCur = (int32_t *)counters, *nNext = nCur + 1;
-    OneRandomState st{(float *)pi, (uint64_t *)rng, (float *)weights};
-    const WavefrontCount cnt{max_items, d_size};
-    const int max_blocks = s->n_cus * 8;
-    if (!hip_ok(hipMemsetAsync(nCur, 0, 4, stream), "reset pass count") ||
-        !hip_ok(launch_or_init(d_p0, d_p1, cnt, st, raysA, (int32_t *)origA, nCur, d_sel_hits, d_sel_rays, max_blocks,
-                               stream), "one-random init launch"))
-        return NNBVH_ERR_DEVICE;
-    int active = 0;
-    if (!read_count(nCur, stream, &active)) return NNBVH_ERR_DEVICE;
-    void *cur = raysA, *next = raysB, *ocur = origA, *onext = origB;
-    for (int pass = 0; active > 0; ++pass) {
-        if (pass > 65536) {
-            set_error("wavefront_intersect_one_random: more than 65536 surfaces on one segment");
-            return NNBVH_ERR_ARG;
-        }
-        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = active, .d_n = nCur, .hits = hits});
-        if (rc != NNBVH_OK) return rc;
-        if (!scratch(w, 9, (size_t)active * sizeof(nnbvh_interaction), &intr)) return NNBVH_ERR_DEVICE;
-        if (!hip_ok(launch_triangle_interactions(m->d, cur, nullptr, hits, active, nCur, intr, m->n_cus * 8, stream),
-                    "interaction kernel launch") ||
-            !hip_ok(hipMemsetAsync(nNext, 0, 4, stream), "reset pass count") ||
-            !hip_ok(launch_or_step(cur, hits, intr, (const int32_t *)ocur, nCur, d_p1, d_material, d_prim_material,
-                                   (long)n_prim_material, st, next, (int32_t *)onext, nNext, d_sel_hits, d_sel_rays,
-                                   active, max_blocks, stream), "one-random step launch"))
-            return NNBVH_ERR_DEVICE;
-        if (!read_count(nNext, stream, &active)) return NNBVH_ERR_DEVICE;
-        std::swap(cur, next);
-        std::swap(ocur, onext);
-        std::swap(nCur, nNext);
-    }
-    if (!hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
+    return one_random_passes(s, call.w, m, max_items, d_p0, d_p1, d_material, d_size, d_prim_material, n_prim_material,
+                             d_sel_hits, d_sel_rays, d_reservoir_pdf, d_weight_sum, kUnbounded, nullptr, stream);
 }
 
-// ---- the bounded forms: max_passes passes enqueued up front, kernel launches only ------------------------------
-// Nothing inside these calls waits for the device or copies from host memory, so they can be captured in a hipGraph
-// once the stream's workspace has its size (a warm-up call with the same max_rays): every pass is sized for
-// max_rays and takes its live count from counters[k], which the step of pass k - 1 has counted up.  The counters
-// are cleared by a kernel node.  A pass over an empty list is a trace and a step whose waves exit at once.
+// ---- the bounded forms: the same loops with max_passes passes enqueued up front, kernel launches only ----------
 int nnbvh_wavefront_intersect_shadow_tr_bounded(
     nnbvh_scene *s, const nnbvh_shading_mesh *m, int32_t max_rays, const nnbvh_ray_soa *shadow_queue,
     const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class, const float *d_Ld, const float *d_r_u,
@@ -968,42 +1006,11 @@ int nnbvh_wavefront_intersect_shadow_tr_bounded(
     hipStream_t stream = (hipStream_t)stream_;
     SceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
-    const int max_blocks = s->n_cus * 8;
-    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, s->n_cus * 8, stream), "unfinished count reset launch"))
         return NNBVH_ERR_DEVICE;
     if (max_rays == 0) return NNBVH_OK;
-    Workspace *w = call.w;
-    const size_t n = (size_t)max_rays;
-    void *raysA, *raysB, *hits, *origA, *origB, *pLight, *state, *counters;
-    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hits) ||
-        !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) || !scratch(w, 6, n * 16, &pLight) ||
-        !scratch(w, 7, n, &state) || !scratch(w, 8, (kMaxBoundedPasses + 1) * 4, &counters))
-        return NNBVH_ERR_DEVICE;
-    int32_t *count = (int32_t *)counters;  // count[k]: the size of pass k's list, k >= 1 (pass 0 runs the queue)
-    const WavefrontCount cnt{max_rays, d_size};
-    if (!hip_ok(launch_zero_words(count, max_passes + 1, max_blocks, stream), "pass count reset launch") ||
-        !hip_ok(launch_str_init(*shadow_queue, cnt, raysA, (int32_t *)origA, (float4 *)pLight, (uint8_t *)state,
-                                max_blocks, stream), "shadow-tr init launch"))
-        return NNBVH_ERR_DEVICE;
-    void *cur = raysA, *next = raysB, *ocur = origA, *onext = origB;
-    for (int pass = 0; pass < max_passes; ++pass) {
-        const int32_t *d_n = pass == 0 ? d_size : count + pass;
-        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = max_rays, .d_n = d_n, .hits = hits});
-        if (rc != NNBVH_OK) return rc;
-        if (!hip_ok(launch_str_step(m->d, cur, hits, (const int32_t *)ocur, WavefrontCount{max_rays, d_n}, d_prim_class,
-                                    (long)n_prim_class, (const float4 *)pLight, (uint8_t *)state, next,
-                                    (int32_t *)onext, count + pass + 1, max_blocks, stream), "shadow-tr step launch"))
-            return NNBVH_ERR_DEVICE;
-        std::swap(cur, next);
-        std::swap(ocur, onext);
-    }
-    if (!hip_ok(launch_w2_mark_unfinished(cur, (const int32_t *)ocur, WavefrontCount{max_rays, count + max_passes},
-                                          (uint8_t *)state, nullptr, d_unfinished, max_blocks, stream),
-                "shadow-tr marking launch") ||
-        !hip_ok(launch_str_record((const uint8_t *)state, cnt, d_Ld, d_r_u, d_r_l, d_pixel_index, d_L, (long)n_pixels,
-                                  d_state, max_blocks, stream), "shadow-tr record launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
+    return shadow_tr_passes(s, call.w, m, max_rays, shadow_queue, d_size, d_prim_class, n_prim_class, d_Ld, d_r_u, d_r_l,
+                            d_pixel_index, d_L, n_pixels, d_state, max_passes, d_unfinished, stream);
 }
 
 int nnbvh_wavefront_intersect_one_random_bounded(
@@ -1018,43 +1025,11 @@ int nnbvh_wavefront_intersect_one_random_bounded(
     hipStream_t stream = (hipStream_t)stream_;
     SceneCall call(s, stream);
     if (!call.ok()) return NNBVH_ERR_DEVICE;
-    const int max_blocks = s->n_cus * 8;
-    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, max_blocks, stream), "unfinished count reset launch"))
+    if (d_unfinished && !hip_ok(launch_zero_words(d_unfinished, 1, s->n_cus * 8, stream), "unfinished count reset launch"))
         return NNBVH_ERR_DEVICE;
     if (max_items == 0) return NNBVH_OK;
-    Workspace *w = call.w;
-    const size_t n = (size_t)max_items;
-    void *raysA, *raysB, *hits, *origA, *origB, *pi, *rng, *weights, *counters;
-    if (!scratch(w, 0, n * 32, &raysA) || !scratch(w, 1, n * 32, &raysB) || !scratch(w, 2, n * 32, &hits) ||
-        !scratch(w, 4, n * 4, &origA) || !scratch(w, 5, n * 4, &origB) || !scratch(w, 6, n * 36, &pi) ||
-        !scratch(w, 10, n * 16, &rng) || !scratch(w, 11, n * 8, &weights) ||
-        !scratch(w, 8, (kMaxBoundedPasses + 1) * 4, &counters))
-        return NNBVH_ERR_DEVICE;
-    int32_t *count = (int32_t *)counters;  // count[k]: the size of pass k's list
-    OneRandomState st{(float *)pi, (uint64_t *)rng, (float *)weights};
-    const WavefrontCount cnt{max_items, d_size};
-    if (!hip_ok(launch_zero_words(count, max_passes + 1, max_blocks, stream), "pass count reset launch") ||
-        !hip_ok(launch_or_init(d_p0, d_p1, cnt, st, raysA, (int32_t *)origA, count, d_sel_hits, d_sel_rays, max_blocks,
-                               stream), "one-random init launch"))
-        return NNBVH_ERR_DEVICE;
-    void *cur = raysA, *next = raysB, *ocur = origA, *onext = origB;
-    for (int pass = 0; pass < max_passes; ++pass) {
-        int rc = launch(s, w, stream, {.mode = 0, .rays = cur, .n = max_items, .d_n = count + pass, .hits = hits});
-        if (rc != NNBVH_OK) return rc;
-        if (!hip_ok(launch_or_step_fused(m->d, cur, hits, (const int32_t *)ocur, WavefrontCount{max_items, count + pass},
-                                         d_p1, d_material, d_prim_material, (long)n_prim_material, st, next,
-                                         (int32_t *)onext, count + pass + 1, d_sel_hits, d_sel_rays, max_blocks, stream),
-                    "one-random step launch"))
-            return NNBVH_ERR_DEVICE;
-        std::swap(cur, next);
-        std::swap(ocur, onext);
-    }
-    if (!hip_ok(launch_w2_mark_unfinished(cur, (const int32_t *)ocur, WavefrontCount{max_items, count + max_passes},
-                                          nullptr, d_sel_hits, d_unfinished, max_blocks, stream),
-                "one-random marking launch") ||
-        !hip_ok(launch_or_finish(cnt, st, d_reservoir_pdf, d_weight_sum, max_blocks, stream), "one-random finish launch"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
+    return one_random_passes(s, call.w, m, max_items, d_p0, d_p1, d_material, d_size, d_prim_material, n_prim_material,
+                             d_sel_hits, d_sel_rays, d_reservoir_pdf, d_weight_sum, max_passes, d_unfinished, stream);
 }
 
 // ---- the walk calls: walk_shadow_tr / walk_one_random (above) under the four names -----------------------------------

@@ -2,11 +2,9 @@
 // wavefront/aggregate.cpp:100-108) as the walk instances of both trace kernels run them (bvh_trace.hip modes 4 / 5,
 // kd_trace.hip modes 4 / 5), inside the lane that has just finished the closest-hit walk: the per-item
 // arrays (WalkParams, one member of either kernel's arguments), the launch job both launchers take (WalkJob) and the
-// per-item bodies of the retire step.  w2_hit_pi_n is shared with the fused pass steps of the bounded BVH calls
-// (wavefront2.hip: str_step, or_step_fused); w2_str_item / w2_or_item are those steps' per-item bodies — the same
-// verdicts in the same order, calling the same functions (w2_hit_pi_n, spawn_ray_to, the PCG32 / reservoir update) —
-// without the list bookkeeping around them.  (The pass kernels keep their own text: routed through these functions
-// they compile to different code, and their ISA is pinned.)
+// per-item bodies of the retire step.  w2_str_item / w2_or_item are the walks' rules, written once: the fused pass
+// steps of the BVH pass calls, bounded and unbounded (wavefront2.hip: str_step, or_step_fused), are the list
+// bookkeeping around the same two bodies.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,8 +65,8 @@ __device__ __forceinline__ bool w2_hit_pi_n(const MeshView &m, float4 h0, float4
     return ok;
 }
 
-// Shadow ray {r0, r1} of work item `item` with the closest hit {h0, h1}: the verdicts of str_classify, in its order,
-// then str_spawn.  true: the walk goes on from o in direction d, tMax and time kept (a zero direction is the
+// Shadow ray {r0, r1} of work item `item` with the closest hit {h0, h1}: one turn of TraceTransmittance's loop
+// (intersect.h:183-256).  true: the walk goes on from o in direction d, tMax and time kept (a zero direction is the
 // caller's to catch: the next step's first verdict); false: the walk has ended, state[item] holds 1 or 2 where the ray
 // does not arrive.
 template <bool FULL>
@@ -78,21 +76,21 @@ __device__ __forceinline__ bool w2_str_item(const MeshView &m, float4 r0, float4
     o = d = {0.0f, 0.0f, 0.0f};
     const bool zeroDir = r1.x == 0.0f && r1.y == 0.0f && r1.z == 0.0f;
     const int prim = __float_as_int(h0.x);
-    if (zeroDir) {
+    if (zeroDir) {  // while (ray.d != Vector3f(0, 0, 0)), :183: a zero direction ends the walk, T stays 1
     } else if (__float_as_int(h1.w) == -1) {
-        state[item] = 2;
+        state[item] = 2;  // a host-only primitive lies on the way
     } else if (prim >= 0) {
         unsigned cls = NNBVH_CLASS_BASIC;
         if (primClass && (long)prim < nPrimClass) cls = primClass[prim];
         if (!(cls & NNBVH_CLASS_INTERFACE)) {
-            state[item] = 1;
-        } else {  // str_spawn
+            state[item] = 1;  // :190-195 hit opaque surface
+        } else {  // result.hit && !result.material
             V3 lo, hi, nn;
             if (!w2_hit_pi_n<FULL>(m, h0, h1, r1, lo, hi, nn)) {
                 state[item] = 2;
             } else {
                 const float4 pl = pLight[item];
-                spawn_ray_to(lo, hi, nn, {pl.x, pl.y, pl.z}, o, d);
+                spawn_ray_to(lo, hi, nn, {pl.x, pl.y, pl.z}, o, d);  // ray = spawnTo(pLight), :255
                 return true;
             }
         }
@@ -100,8 +98,8 @@ __device__ __forceinline__ bool w2_str_item(const MeshView &m, float4 r0, float4
     return false;
 }
 
-// Segment ray {r0, r1} of one-random item `item` with the closest hit {h0, h1}: or_step with the interaction in
-// registers.  true: the walk goes on from o in direction d (never zero), tMax = 1, time = 0.
+// Segment ray {r0, r1} of one-random item `item` with the closest hit {h0, h1}: one turn of IntersectOneRandom's loop
+// (aggregate.cpp:100-108).  true: the walk goes on from o in direction d (never zero), tMax = 1, time = 0.
 template <bool FULL>
 __device__ __forceinline__ bool w2_or_item(const MeshView &m, float4 r0, float4 r1, float4 h0, float4 h1, int item,
                                            const float *p1, const int32_t *material, const int32_t *primMaterial,
@@ -111,18 +109,18 @@ __device__ __forceinline__ bool w2_or_item(const MeshView &m, float4 r0, float4 
     const int prim = __float_as_int(h0.x);
     V3 lo, hi, nn;
     if (prim < 0 && __float_as_int(h1.w) != -1) {
-        // no further surface on the segment: the walk ends
+        // :103-104 no further surface on the segment: the walk ends
     } else if (__float_as_int(h1.w) == -1 || !w2_hit_pi_n<FULL>(m, h0, h1, r1, lo, hi, nn)) {
         selHits[2 * (long)item + 1].w = __int_as_float(-1);  // the item is the caller's
-    } else {  // or_step from here on
+    } else {  // base = si->intr, :105
         const int mat = (primMaterial && (long)prim < nPrimMaterial) ? primMaterial[prim] : 0;
-        if (mat == material[item]) {
+        if (mat == material[item]) {  // :106-107 wrs.Add(SubsurfaceInteraction(si->intr), 1.f)
             Pcg32 g = {st.rng[2 * (long)item], st.rng[2 * (long)item + 1]};
             float weightSum = st.weights[2 * (long)item];
             const float weight = 1.0f;
             weightSum += weight;
             const float p = weight / weightSum;
-            if (pcg32_float(g) < p) {
+            if (pcg32_float(g) < p) {  // util/sampling.h:535-546
                 selHits[2 * (long)item] = h0;
                 selHits[2 * (long)item + 1] = h1;
                 selRays[2 * (long)item] = r0;

@@ -13,23 +13,16 @@ namespace nnbvh {
 // ---- IntersectShadowTr ------------------------------------------------------------------------
 hipError_t launch_str_init(const nnbvh_ray_soa &q, WavefrontCount cnt, void *rays, int32_t *orig, float4 *pLight,
                            uint8_t *state, int maxBlocks, hipStream_t stream);
-// hits of the current rays -> per-item verdicts; rays that hit an interface surface are appended
-// (ray, hit, item) to the next list, *counter counting them
-hipError_t launch_str_classify(const void *raysCur, const void *hitsCur, const int32_t *origCur,
-                               const int32_t *nCur, const uint8_t *primClass, long nPrimClass, uint8_t *state,
-                               void *raysNext, void *hitsNext, int32_t *origNext, int32_t *counter, int maxItems,
-                               int maxBlocks, hipStream_t stream);
-// interactions of the listed hits -> the next segment's ray towards pLight (compacted into raysOut)
-hipError_t launch_str_spawn(const void *raysIn, const void *intr, const int32_t *origIn, const int32_t *nIn,
-                            const float4 *pLight, uint8_t *state, void *raysOut, int32_t *origOut,
-                            int32_t *counter, int maxItems, int maxBlocks, hipStream_t stream);
 hipError_t launch_str_record(const uint8_t *state, WavefrontCount cnt, const float *Ld, const float *ru,
                              const float *rl, const int32_t *pixelIndex, float *L, long nPixels,
                              uint8_t *visibleOut, int maxBlocks, hipStream_t stream);
 
 // ---- IntersectOneRandom -----------------------------------------------------------------------
-struct OneRandomState {  // per work item, device arrays
-    float *pi;           // 9 floats per item: pi low[3], high[3], n[3] of the current base interaction
+struct OneRandomState {  // per work item, device arrays (the base interaction of a segment stays in registers)
+    // Unused, always null: no kernel reads or writes it.  It keeps the members of WalkParams behind `st` at their
+    // kernel-argument offsets: without it the one-random walk instances of both trace kernels allocate registers
+    // differently (tools/isa_diff.py: their SGPR spills move by 4 to 8 either way).
+    float *unused;
     uint64_t *rng;       // 2 per item: PCG32 state, inc
     float *weights;      // 2 per item: weightSum, reservoirWeight
 };
@@ -37,26 +30,21 @@ hipError_t launch_or_init(const float *p0, const float *p1, WavefrontCount cnt, 
                           int32_t *origOut, int32_t *counter, void *selHits, void *selRays, int maxBlocks,
                           hipStream_t stream);
 // or_init without compaction, for the walk instances of the trace kernels: every item's first segment ray, reservoir
-// state and cleared outputs (st.pi is not written)
+// state and cleared outputs
 hipError_t launch_or_init_all(const float *p0, const float *p1, WavefrontCount cnt, OneRandomState st, void *rays,
                               void *selHits, void *selRays, int maxBlocks, hipStream_t stream);
-hipError_t launch_or_step(const void *raysCur, const void *hitsCur, const void *intrCur, const int32_t *origCur,
-                          const int32_t *nCur, const float *p1, const int32_t *material,
-                          const int32_t *primMaterial, long nPrimMaterial, OneRandomState st, void *raysNext,
-                          int32_t *origNext, int32_t *counter, void *selHits, void *selRays, int maxItems,
-                          int maxBlocks, hipStream_t stream);
 hipError_t launch_or_finish(WavefrontCount cnt, OneRandomState st, float *pdf, float *weightSum, int maxBlocks,
                             hipStream_t stream);
 
-// ---- the bounded forms: one fused step per pass, no host round trip ---------------------------------
-// One pass of the shadow walk after its trace: hit -> verdict (str_classify's rules), and for an interface hit the
+// ---- one fused step per pass: the bounded calls enqueue their passes up front, the unbounded ones pass by pass -----
+// One pass of the shadow walk after its trace: hit -> verdict (w2_str_item, walk_math.h), and for an interface hit the
 // interaction in registers and the next segment's ray towards pLight, appended to the next list.  cur: the list's
 // size (the queue's own for the first pass, a counter of the call's for the others).
 hipError_t launch_str_step(const ShadingMeshDevice &m, const void *raysCur, const void *hitsCur,
                            const int32_t *origCur, WavefrontCount cur, const uint8_t *primClass, long nPrimClass,
                            const float4 *pLight, uint8_t *state, void *raysNext, int32_t *origNext, int32_t *counter,
                            int maxBlocks, hipStream_t stream);
-// ... of the one-random walk: or_step with the interaction in registers
+// ... of the one-random walk (w2_or_item)
 hipError_t launch_or_step_fused(const ShadingMeshDevice &m, const void *raysCur, const void *hitsCur,
                                 const int32_t *origCur, WavefrontCount cur, const float *p1, const int32_t *material,
                                 const int32_t *primMaterial, long nPrimMaterial, OneRandomState st, void *raysNext,

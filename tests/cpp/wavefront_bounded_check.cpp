@@ -1,7 +1,10 @@
 // Exercises HipBVHAggregate::IntersectShadowTrBounded / IntersectOneRandomBounded (include/nnbvh_aggregate.hpp)
 // against the unbounded adapter methods IntersectShadowTrQueue / IntersectOneRandomQueue on the same device-resident
 // inputs: with enough passes every output is the unbounded call's, byte for byte, and nothing is unfinished; with one
-// pass the walks that need more are marked as the caller's and counted.  Built by tests/test_wavefront_bounded_cpp.py
+// pass the walks that need more are marked as the caller's and counted.  This checks the adapter (argument order, the
+// two drivers of one pass loop agreeing), not the walk: both methods run the same kernels, and what those compute is
+// held to the oracle by tests/test_wavefront_bounded.py and tests/test_wavefront_tr.py.  Built by
+// tests/test_wavefront_bounded_cpp.py
 // with g++ against libnnbvh_hip.so and the HIP runtime; run only where a GPU is present.
 #include <cmath>
 #include <cstdio>

@@ -4,8 +4,12 @@
 An item is finished iff the reference loop (wavefront/intersect.h:183-256, aggregate.cpp:100-108) makes at most
 max_passes calls of Intersect for it.  The composed oracle of test_wavefront_tr.py, with a counter of those calls per
 item, gives what finished items must hold bit for bit and which items must carry the "caller's to finish" mark
-(state 2 / instance = -1).  Scenes the composed oracle does not cover (bilinear patches, host-only primitives,
-instances) use the unbounded entry points as the reference: independent code that existing tests pin."""
+(state 2 / instance = -1).  The unbounded entry points run the same pass (the trace and one fused step) under a
+host-driven driver, so they are no independent reference: on scenes the composed oracle does not cover (bilinear
+patches, host-only primitives, instances) both forms are held to the loops of test_wavefront_walk_kd.py
+(device_shadow_walk / device_one_random_walk) over calls that exist without either: the flat closest-hit call, the
+public interaction post-pass and the oracle's SpawnRayTo.  The last test runs the unbounded driver past the 64 passes
+the bounded form stops at."""
 import ctypes
 import functools
 import os
@@ -494,6 +498,7 @@ def test_gpu_bounded_calls_equal_the_unbounded_ones_beyond_flat_triangles(make):
     from nn_bvh_amd import BVHAggregate
     from nn_bvh_amd.interaction import ShadingMesh
     from nn_bvh_amd.wavefront import RayQueue, WavefrontAggregate
+    from test_wavefront_walk_kd import device_one_random_walk, device_shadow_walk  # (that module imports this one)
     s = make()
     nodes, prims, verts = s["tree"]
     mesh = ShadingMesh(verts, **s["mesh"])
@@ -513,8 +518,9 @@ def test_gpu_bounded_calls_equal_the_unbounded_ones_beyond_flat_triangles(make):
     rays["time"] = rng.random(n).astype(np.float32)
     q = RayQueue.from_records(rays, dev, shadow=True)
     q.time = t(rays["time"])
-    Ld, ru, rl = (t((rng.random((n, 4), np.float32) + 0.5).astype(np.float32)) for _ in range(3))
-    pixel = t(rng.permutation(n).astype(np.int32))
+    Ld_h, ru_h, rl_h = ((rng.random((n, 4), np.float32) + 0.5).astype(np.float32) for _ in range(3))
+    pixel_h = rng.permutation(n).astype(np.int32)
+    Ld, ru, rl, pixel = t(Ld_h), t(ru_h), t(rl_h), t(pixel_h)
     L0 = rng.random((n, 4), np.float32).astype(np.float32)
     unfinished = torch.full((1,), -3, dtype=torch.int32, device=dev)
 
@@ -526,6 +532,10 @@ def test_gpu_bounded_calls_equal_the_unbounded_ones_beyond_flat_triangles(make):
         return state.cpu().numpy(), L.cpu().numpy()
 
     ref_state, ref_L = shadow(None)
+    # the unbounded call against the loop over the flat closest-hit call, the interaction post-pass and SpawnRayTo
+    walk_state, walk_calls = device_shadow_walk(agg, mesh, rays, cls)
+    assert np.array_equal(ref_state, walk_state) and 1 < walk_calls.max() <= 16
+    assert ref_L.tobytes() == shadow_radiance(ref_state, Ld_h, ru_h, rl_h, pixel_h, L0).tobytes()
     state, L = shadow(16)
     assert np.array_equal(state, ref_state) and L.tobytes() == ref_L.tobytes() and int(unfinished.item()) == 0
     one_state, _ = shadow(1)
@@ -542,14 +552,27 @@ def test_gpu_bounded_calls_equal_the_unbounded_ones_beyond_flat_triangles(make):
     p0 = rng.uniform(-box, box, (m, 3)).astype(np.float32)
     p1 = rng.uniform(-box, box, (m, 3)).astype(np.float32)
     p1[::50] = p0[::50]
-    args = (m, t(p0), t(p1), t(rng.integers(0, 3, m).astype(np.int32)), mesh, t(rng.integers(0, 3, s["n_ids"]).astype(np.int32)))
+    material = rng.integers(0, 3, m).astype(np.int32)
+    prim_material = rng.integers(0, 3, s["n_ids"]).astype(np.int32)
+    args = (m, t(p0), t(p1), t(material), mesh, t(prim_material))
 
     def one_random(max_passes):
         out = wf.IntersectOneRandom(*args, max_passes=max_passes, unfinished=None if max_passes is None else unfinished)
         torch.cuda.synchronize()
         return one_random_numpy(out)
 
-    ref, got = one_random(None), one_random(16)
+    ref = one_random(None)
+    # the unbounded call against the test-side loop, on the items that are not the caller's
+    eh, er, epdf, ewsum, ecalls, host = device_one_random_walk(agg, mesh, p0, p1, material, prim_material)
+    assert ecalls.max() <= 16
+    gh, gr, pdf, wsum = ref
+    assert np.array_equal(gh["instance"] == -1, host)
+    assert np.array_equal(gh["prim"][~host], eh["prim"][~host])
+    assert np.array_equal(pdf[~host].view(np.uint32), epdf[~host].view(np.uint32))
+    assert np.array_equal(wsum[~host].view(np.uint32), ewsum[~host].view(np.uint32))
+    sel = ~host & (eh["prim"] >= 0)
+    assert gh[sel].tobytes() == eh[sel].tobytes() and gr[sel].tobytes() == er[sel].tobytes()
+    got = one_random(16)
     assert int(unfinished.item()) == 0
     for a, b in zip(got, ref):
         assert a.tobytes() == b.tobytes()
@@ -563,5 +586,83 @@ def test_gpu_bounded_calls_equal_the_unbounded_ones_beyond_flat_triangles(make):
         assert (~own).sum() > 20
     if make is two_level_case:
         assert (ref[0]["instance"][own & (ref[0]["prim"] >= 0)] > 0).sum() > 20  # selected hits inside instances
+    agg.close()
+    mesh.close()
+
+
+@functools.lru_cache(maxsize=None)
+def sheets_case():
+    """70 parallel interface quads and 65 rays / segments across all of them (one full wavefront and one lane)."""
+    from test_wavefront_walk_kd import one_random_walk
+    from test_wavefront_walk_kd import shadow_walk as walk
+    c = Case()
+    k, c.n, c.capacity = 70, 65, 128
+    z = (0.1 * np.arange(k)).astype(np.float32)
+    quad = np.array([[-1, -1], [1, -1], [1, 1], [-1, 1]], np.float32)
+    c.verts = np.concatenate([np.concatenate([quad, np.full((4, 1), zz, np.float32)], 1) for zz in z])
+    c.tris = np.concatenate([4 * i + np.array([[0, 1, 2], [0, 2, 3]], np.int32) for i in range(k)]).astype(np.int32)
+    c.tree = build_tree(ss.make_prims(c.tris), c.verts)
+    c.cls = np.full(len(c.tris), 2, np.uint8)  # NNBVH_CLASS_INTERFACE
+    closest = lambda rays: ob.closest(c.tree.nodes, c.tree.ordered_prims, c.verts, rays)  # noqa: E731
+    rng = np.random.default_rng(70)
+    c.p0 = np.concatenate([rng.uniform(-0.8, 0.8, (c.n, 2)), np.full((c.n, 1), -1.0)], 1).astype(np.float32)
+    c.p1 = np.concatenate([rng.uniform(-0.8, 0.8, (c.n, 2)), np.full((c.n, 1), 8.0)], 1).astype(np.float32)
+    c.rays = np.zeros(c.capacity, RAY_DTYPE)  # the queue's allocation; the device-resident size says 65
+    c.rays["o"][:c.n], c.rays["d"][:c.n], c.rays["tmax"] = c.p0, c.p1 - c.p0, 1 - 1e-4
+    c.rays["d"][c.n:] = (0, 0, 1)  # beyond the size: never read
+    c.zero = 33
+    c.rays["d"][c.zero] = 0
+    c.rays["time"] = rng.random(c.capacity).astype(np.float32)
+    c.Ld, c.ru, c.rl = ((rng.random((c.capacity, 4), np.float32) + 0.5).astype(np.float32) for _ in range(3))
+    c.pixel = rng.permutation(c.capacity).astype(np.int32)
+    c.L0 = rng.random((c.capacity, 4), np.float32).astype(np.float32)
+    c.state, c.calls = walk(closest, c.verts, c.tris, c.rays[:c.n], c.cls)
+    # every ray arrives; the crossing ones after 70 hits and the miss behind the last sheet
+    assert (c.state == 0).all() and c.calls[c.zero] == 0 and (np.delete(c.calls, c.zero) == k + 1).all()
+    c.material, c.prim_material = np.zeros(c.n, np.int32), np.zeros(len(c.tris), np.int32)
+    c.hits, c.sel_rays, c.pdf, c.wsum, c.or_calls = one_random_walk(closest, c.verts, c.tris, c.p0, c.p1, c.material,
+                                                                    c.prim_material)
+    assert (c.or_calls == k + 1).all() and (c.wsum == k).all() and (c.hits["prim"] >= 0).all()
+    return c
+
+
+@pytest.mark.gpu
+def test_gpu_unbounded_calls_walk_past_the_64_passes_of_the_bounded_forms():
+    """71 passes of the host-driven driver: its two alternating counters and its host-sized grids, on the only walks
+    that need it.  Expected values: the composed reference of test_wavefront_walk_kd.py over the oracle's closest
+    hit, bit for bit."""
+    import torch
+    from nn_bvh_amd import BVHAggregate
+    from nn_bvh_amd.interaction import ShadingMesh
+    from nn_bvh_amd.wavefront import RayQueue, WavefrontAggregate
+    c = sheets_case()
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    agg = BVHAggregate.from_tree(c.tree.nodes, c.tree.ordered_prims, c.verts)
+    mesh = ShadingMesh(c.verts, c.tris)
+    wf = WavefrontAggregate(agg, c.cls)
+    q = RayQueue.from_records(c.rays, dev, shadow=True)
+    q.time = t(c.rays["time"])
+    q.size.fill_(c.n)
+    L, state = t(c.L0), torch.full((c.capacity,), SENTINEL, dtype=torch.uint8, device=dev)
+    wf.IntersectShadowTr(c.capacity, q, mesh, t(c.Ld), t(c.ru), t(c.rl), t(c.pixel), L, state)
+    torch.cuda.synchronize()
+    state = state.cpu().numpy()
+    assert np.array_equal(state[:c.n], c.state) and (state[c.n:] == SENTINEL).all()
+    live = np.concatenate([c.state, np.ones(c.capacity - c.n, np.uint8)])  # rays beyond the size add nothing
+    assert L.cpu().numpy().tobytes() == shadow_radiance(live, c.Ld, c.ru, c.rl, c.pixel, c.L0).tobytes()
+    # the bounded form at its limit leaves every crossing ray to the caller
+    unfinished = torch.full((1,), -3, dtype=torch.int32, device=dev)
+    st64 = torch.full((c.capacity,), SENTINEL, dtype=torch.uint8, device=dev)
+    wf.IntersectShadowTr(c.capacity, q, mesh, t(c.Ld), t(c.ru), t(c.rl), t(c.pixel), t(c.L0), st64, max_passes=64,
+                         unfinished=unfinished)
+    torch.cuda.synchronize()
+    assert int(unfinished.item()) == c.n - 1 and (np.delete(st64.cpu().numpy()[:c.n], c.zero) == 2).all()
+
+    gh, gr, pdf, wsum = one_random_numpy(wf.IntersectOneRandom(c.n, t(c.p0), t(c.p1), t(c.material), mesh,
+                                                               t(c.prim_material)))
+    assert gh.tobytes() == c.hits.tobytes() and gr.tobytes() == c.sel_rays.tobytes()
+    assert np.array_equal(pdf.view(np.uint32), c.pdf.view(np.uint32))
+    assert np.array_equal(wsum.view(np.uint32), c.wsum.view(np.uint32)) and (wsum == 70).all()
     agg.close()
     mesh.close()

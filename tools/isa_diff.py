@@ -34,7 +34,9 @@ FUNC_NUMBER = re.compile(r"((?:\.L|\b)BB|\.Lfunc_begin|\.Lfunc_end)\d+")
 def assemble(root, src, out):
     subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", out, os.path.join(root, CSRC, src)], check=True,
                    stderr=subprocess.DEVNULL)
-    return [FUNC_NUMBER.sub(r"\1N", ln) for ln in open(out).read().splitlines() if "__hip_cuid_" not in ln]
+    # (a label's comment is padded to a column, so a number that loses a digit moves it: one space there)
+    return [re.sub(r"\s+;", " ;", FUNC_NUMBER.sub(r"\1N", ln)) for ln in open(out).read().splitlines()
+            if "__hip_cuid_" not in ln]
 
 
 def kernels(lines):
