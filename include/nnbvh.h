@@ -71,8 +71,8 @@ typedef struct nnbvh_linear_node {
                                        the device performs that re-test too and, should it ever hit, voids
                                        the ray like a host-only primitive (instance = -1 / occluded = 2).
                                        For meshes WITHOUT per-vertex shading normals (the offset normal
-                                       is the geometric one); alpha-tested meshes with normals and
-                                       textured alpha stay NNBVH_PRIM_HOST */
+                                       is the geometric one); meshes with normals: kinds 6 / 7; an alpha that
+                                       is an image texture: kinds 16 .. 19 */
 #define NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED 5 /* same, mesh->reverseOrientation ^ transformSwapsHandedness */
 #define NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH 6  /* ... of a mesh WITH per-vertex shading normals: the ray re-traced
                                        after a rejected hit is offset along FaceForward(n, ns) (shapes.h:
@@ -98,6 +98,18 @@ typedef struct nnbvh_linear_node {
 #define NNBVH_PRIM_ALPHA_PATCH_UV_FLIPPED 13
 #define NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH 14
 #define NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH_FLIPPED 15
+#define NNBVH_PRIM_ALPHATEX_TRIANGLE 16 /* a Triangle inside a GeometricPrimitive whose alpha is a FloatImageTexture with a
+                                       UVMapping (textures.h:579-590): v[3] = index into the scene's alpha-texture table
+                                       (nnbvh_scene_create_with_alpha_textures).  The texture is evaluated at the hit's
+                                       (u, v) as the reference does for the alpha test, i.e. with zero differentials:
+                                       level 0 of the image only (nnbvh_alpha_texture).  Then as kind 4.
+                                       kind = 16 + flipped + 2 * smooth, flipped and smooth as for kinds 4 .. 7.
+                                       Flat scenes only: two-level and kd scenes, textured alpha on patches, other
+                                       mappings (spherical, cylindrical, planar) and other float textures (scale, mix,
+                                       checkerboard, ...) stay NNBVH_PRIM_HOST */
+#define NNBVH_PRIM_ALPHATEX_TRIANGLE_FLIPPED 17
+#define NNBVH_PRIM_ALPHATEX_TRIANGLE_SMOOTH 18
+#define NNBVH_PRIM_ALPHATEX_TRIANGLE_SMOOTH_FLIPPED 19
 
 /* One entry of BVHAggregate::primitives: the shape handle flattened to global vertex
  * indices (Triangle{meshIndex,triIndex} -> mesh->vertexIndices[3*tri..], shapes.cpp:326-328). */
@@ -355,6 +367,45 @@ nnbvh_scene *nnbvh_scene_create_with_normals(const nnbvh_linear_node *nodes, int
 nnbvh_scene *nnbvh_scene_create_with_attributes(const nnbvh_linear_node *nodes, int n_nodes, const nnbvh_prim *prims,
                                                 int n_prims, const float *verts, const float *normals,
                                                 const float *uvs, const float *prim_alpha, int n_verts, int device);
+/* ---- image-textured alpha (kinds NNBVH_PRIM_ALPHATEX_TRIANGLE*) --------------------------------------------------
+ * One FloatImageTexture as the alpha test sees it.  GeometricPrimitive::Intersect (cpu/primitive.cpp:57-58) evaluates
+ * the texture on the interaction the shape has just made, whose screen-space differentials are still zero, so
+ * MIPMap::Filter (util/mipmap.cpp:229-284) never leaves level 0: bilinear, trilinear and EWA filtering all return
+ * Bilerp(0, st), the point filter one level-0 texel.  No MIP pyramid is needed.  Decoding 8-bit or half texels through
+ * the image's colour encoding is the embedder's (one Image::GetChannel per texel at scene creation). */
+#define NNBVH_WRAP_REPEAT 0 /* WrapMode::Repeat */
+#define NNBVH_WRAP_CLAMP 1  /* WrapMode::Clamp */
+#define NNBVH_WRAP_BLACK 2  /* WrapMode::Black (WrapMode::OctahedralSphere is refused) */
+typedef struct nnbvh_alpha_texture {
+    const float *texels;   /* level 0 only: width*height floats, row-major, row 0 = the image's first row; each the
+                              value Image::GetChannel(p, 0) returns, i.e. already decoded to linear.  Copied */
+    int32_t width, height; /* 1 .. 2^24 */
+    int32_t wrap;          /* NNBVH_WRAP_REPEAT / _CLAMP / _BLACK */
+    int32_t point_filter;  /* 1 = FilterFunction::Point; 0 = bilinear, trilinear, EWA (all Bilerp(0, st) here) */
+    float su, sv, du, dv;  /* UVMapping (textures.h:85-106) */
+    float scale;
+    int32_t invert;
+} nnbvh_alpha_texture;
+/* nnbvh_scene_create_with_attributes / nnbvh_scene_create_gpu_build_with_attributes plus the alpha-texture table the
+ * kinds 16 .. 19 index with v[3].  Both make the same device arrays (nnbvh_scene_read; what = 3: the descriptor table,
+ * 48 bytes per texture, 4: the texel pool, 4 bytes per texel).  uvs (2 floats per vertex) gives a textured triangle its
+ * three (u, v) pairs; uvs == NULL means the mesh has none and EVERY textured triangle takes the reference's default
+ * corners (0,0), (1,0), (1,1) (shapes.h, InteractionFromIntersection) — a scene that mixes textured meshes with and
+ * without (u, v) keeps those without NNBVH_PRIM_HOST.  Kinds 4 .. 7 may be mixed in; alpha-tested patches (kinds
+ * 8 .. 15) may not (refused).  NULL + nnbvh_last_error() naming the call, before a device is looked at, for: a null or
+ * empty texture table with a textured triangle present, a texture index out of range, null texels, a width or height
+ * outside 1 .. 2^24, an unknown wrap mode, a smooth kind without normals — besides every fault of the call without
+ * textures.  The other creation calls refuse kinds 16 .. 19. */
+nnbvh_scene *nnbvh_scene_create_with_alpha_textures(const nnbvh_linear_node *nodes, int n_nodes, const nnbvh_prim *prims,
+                                                    int n_prims, const float *verts, const float *normals,
+                                                    const float *uvs, const float *prim_alpha, int n_verts, int device,
+                                                    const nnbvh_alpha_texture *textures, int n_textures);
+nnbvh_scene *nnbvh_scene_create_gpu_build_with_alpha_textures(const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                              int n_verts, const float *prim_bounds,
+                                                              const float *normals, const float *uvs,
+                                                              const float *prim_alpha, int max_prims_in_node,
+                                                              int split_method, int device,
+                                                              const nnbvh_alpha_texture *textures, int n_textures);
 void nnbvh_scene_destroy(nnbvh_scene *s);
 int nnbvh_scene_bounds(const nnbvh_scene *s, float out_min_max[6]);
 /* what the baked device layout looks like: [0]=interior records, [1]=prim-stream slots,
@@ -362,7 +413,8 @@ int nnbvh_scene_bounds(const nnbvh_scene *s, float out_min_max[6]);
 int nnbvh_scene_info(const nnbvh_scene *s, int64_t out[6]);
 /* the baked device arrays of any scene, however it was created, copied to the host (tests, tools): what 0 = interior
  * records (info[0] * 64 bytes), 1 = primitive stream (info[1] * 16 bytes), 2 = animation table (304 bytes per instance;
- * scenes created with one).  Synchronous.  NNBVH_ERR_ARG for a NULL scene or buffer, an unknown `what`, or a `bytes`
+ * scenes created with one), 3 = alpha-texture descriptor table (48 bytes per texture), 4 = alpha texel pool (scenes
+ * created with alpha textures).  Synchronous.  NNBVH_ERR_ARG for a NULL scene or buffer, an unknown `what`, or a `bytes`
  * that is not the array's size. */
 int nnbvh_scene_read(const nnbvh_scene *s, int what, void *out, size_t bytes);
 

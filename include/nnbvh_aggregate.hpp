@@ -247,6 +247,47 @@ class HipBVHAggregate {
         note_patches(orderedPrims, nPrims);
     }
 
+    // ... whose primitives include triangles with an image-textured alpha (kinds NNBVH_PRIM_ALPHATEX_TRIANGLE*, v[3] =
+    // index into alphaTextures; nnbvh_scene_create_with_alpha_textures).  uvs == nullptr: the meshes have no (u, v)
+    // and every textured triangle takes the default corners.  The texels are copied
+    HipBVHAggregate(const nnbvh_linear_node *nodes, int nNodes, const nnbvh_prim *orderedPrims, int nPrims,
+                    const float *verts, int nVerts, const std::vector<nnbvh_alpha_texture> &alphaTextures, int device = 0,
+                    const float *normals = nullptr, const float *primAlpha = nullptr, const float *uvs = nullptr) {
+        scene_ = nnbvh_scene_create_with_alpha_textures(nodes, nNodes, orderedPrims, nPrims, verts, normals, uvs, primAlpha,
+                                                        nVerts, device, alphaTextures.data(), (int)alphaTextures.size());
+        if (!scene_) fatal("HipBVHAggregate: scene_create_with_alpha_textures");
+        note_patches(orderedPrims, nPrims);
+    }
+
+    // A flat scene with its tree built AND baked on the device (nnbvh_scene_create_gpu_build_with_attributes; with
+    // alphaTextures: nnbvh_scene_create_gpu_build_with_alpha_textures, for the kinds NNBVH_PRIM_ALPHATEX_TRIANGLE*).
+    // primAlpha: per entry of `prims`, the caller's order.  splitMethod "sah" or "hlbvh".
+    static std::unique_ptr<HipBVHAggregate> BuildOnDevice(
+        const std::vector<nnbvh_prim> &prims, const std::vector<float> &verts, int maxPrimsInNode = 4,
+        const std::string &splitMethod = "sah", int device = 0, const std::vector<float> *primBounds = nullptr,
+        const std::vector<float> *normals = nullptr, const std::vector<float> *primAlpha = nullptr,
+        const std::vector<float> *uvs = nullptr, const std::vector<nnbvh_alpha_texture> *alphaTextures = nullptr) {
+        const int method = splitMethod == "sah" ? NNBVH_SPLIT_SAH : splitMethod == "hlbvh" ? NNBVH_SPLIT_HLBVH : -1;
+        const float *pb = primBounds ? primBounds->data() : nullptr, *nrm = normals ? normals->data() : nullptr;
+        const float *uv = uvs ? uvs->data() : nullptr, *pa = primAlpha ? primAlpha->data() : nullptr;
+        nnbvh_scene *scene =
+            alphaTextures
+                ? nnbvh_scene_create_gpu_build_with_alpha_textures(prims.data(), (int)prims.size(), verts.data(),
+                                                                   (int)(verts.size() / 3), pb, nrm, uv, pa, maxPrimsInNode,
+                                                                   method, device, alphaTextures->data(),
+                                                                   (int)alphaTextures->size())
+                : nnbvh_scene_create_gpu_build_with_attributes(prims.data(), (int)prims.size(), verts.data(),
+                                                               (int)(verts.size() / 3), pb, nrm, uv, pa, maxPrimsInNode,
+                                                               method, device);
+        if (!scene) {
+            fatal("HipBVHAggregate::BuildOnDevice");
+            return nullptr;
+        }
+        std::unique_ptr<HipBVHAggregate> agg(new HipBVHAggregate(scene));
+        agg->note_patches(prims.data(), (int)prims.size());
+        return agg;
+    }
+
     // A two-level scene (one BVHAggregate per object definition, one TransformedPrimitive / AnimatedPrimitive per
     // placement, scene.cpp:1521-1577) with every tree built AND baked on the device
     // (nnbvh_scene_create_instanced_gpu_build): the scene of host-built trees, byte for byte.  topPrims: what lives

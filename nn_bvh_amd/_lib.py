@@ -103,6 +103,7 @@ EXPORTS = [
     "nnbvh_build_forest_create_gpu", "nnbvh_forest_nodes", "nnbvh_forest_node_first", "nnbvh_forest_depths",
     "nnbvh_forest_ordered_prims", "nnbvh_forest_gpu_timing", "nnbvh_forest_n_levels", "nnbvh_forest_n_subtrees",
     "nnbvh_forest_destroy", "nnbvh_build_forest_create_gpu_hlbvh",
+    "nnbvh_scene_create_with_alpha_textures", "nnbvh_scene_create_gpu_build_with_alpha_textures",
 ]
 
 
@@ -113,6 +114,39 @@ class HostCandidates(ctypes.Structure):
 
 
 assert ctypes.sizeof(HostCandidates) == 40
+
+WRAP_MODES = {"repeat": 0, "clamp": 1, "black": 2}
+
+
+class AlphaTexture(ctypes.Structure):
+    """nnbvh_alpha_texture (include/nnbvh.h): one FloatImageTexture as the alpha test of a GeometricPrimitive sees
+    it — level 0 of the image (float32 [height, width], row 0 = the image's first row, already decoded to linear), the
+    wrap mode, the filter, the UVMapping, scale and invert.  Primitive kinds 16 .. 19 name one by v[3]."""
+    _fields_ = [("texels", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("wrap", ctypes.c_int32), ("point_filter", ctypes.c_int32), ("su", ctypes.c_float),
+                ("sv", ctypes.c_float), ("du", ctypes.c_float), ("dv", ctypes.c_float), ("scale", ctypes.c_float),
+                ("invert", ctypes.c_int32)]
+
+    def __init__(self, texels, wrap="repeat", point_filter=False, su=1.0, sv=1.0, du=0.0, dv=0.0, scale=1.0,
+                 invert=False):
+        self.image = np.ascontiguousarray(texels, np.float32)  # kept alive with the descriptor
+        if self.image.ndim != 2:
+            raise NNBVHError(f"AlphaTexture: texels must be [height, width], not {self.image.shape}")
+        super().__init__(self.image.ctypes.data if self.image.size else None, self.image.shape[1], self.image.shape[0],
+                         WRAP_MODES[wrap] if isinstance(wrap, str) else int(wrap), int(bool(point_filter)), su, sv,
+                         du, dv, scale, int(bool(invert)))
+
+
+assert ctypes.sizeof(AlphaTexture) == 48
+
+
+def alpha_texture_table(alpha_textures):
+    """(ctypes array or None, count) of a sequence of AlphaTexture"""
+    textures = list(alpha_textures)
+    if not all(isinstance(t, AlphaTexture) for t in textures):
+        raise NNBVHError("alpha_textures: a sequence of nn_bvh_amd.AlphaTexture")
+    return ((AlphaTexture * len(textures))(*textures) if textures else None), len(textures)
+
 
 _lib = None
 
@@ -189,6 +223,10 @@ def lib():
     L.nnbvh_scene_create_gpu_build.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32]
     L.nnbvh_scene_create_gpu_build_with_attributes.restype = vp
     L.nnbvh_scene_create_gpu_build_with_attributes.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32]
+    L.nnbvh_scene_create_with_alpha_textures.restype = vp
+    L.nnbvh_scene_create_with_alpha_textures.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, i32]
+    L.nnbvh_scene_create_gpu_build_with_alpha_textures.restype = vp
+    L.nnbvh_scene_create_gpu_build_with_alpha_textures.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32]
     L.nnbvh_build_create_gpu.restype = vp
     L.nnbvh_build_create_gpu.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32]
     L.nnbvh_build_gpu_timing.restype = i32

@@ -179,24 +179,28 @@ class BVHAggregate:
 
     @classmethod
     def from_tree(cls, nodes, ordered_prims, verts, device=0, instances=None, n_top_nodes=None, animated=None,
-                  normals=None, prim_alpha=None, uvs=None):
+                  normals=None, prim_alpha=None, uvs=None, alpha_textures=None):
         """instances (INSTANCE_DTYPE) + n_top_nodes make a two-level scene: nodes[:n_top_nodes] is
         the top-level tree, the child trees follow (see nn_bvh_amd.instancing).  animated
         (ANIMATED_DTYPE, one per instance) turns instances into AnimatedPrimitives.  normals: per-vertex
         shading normals, needed by alpha-tested triangles / patches of smooth meshes (prim kinds 6 / 7, 10 / 11);
         prim_alpha: one constant alpha per entry of ordered_prims, read for alpha-tested patches (kinds 8 .. 15);
-        uvs: per-vertex (u, v), read for the alpha-tested patches of meshes with uv (kinds 12 .. 15)."""
+        uvs: per-vertex (u, v), read for the alpha-tested patches of meshes with uv (kinds 12 .. 15) and the
+        triangles with an image-textured alpha (kinds 16 .. 19; None: the default corners);
+        alpha_textures: a sequence of AlphaTexture, the table kinds 16 .. 19 index with v[3] (flat scenes only)."""
         self = cls.__new__(cls)
-        self._init(nodes, ordered_prims, verts, device, None, instances, n_top_nodes, animated, normals, prim_alpha, uvs)
+        self._init(nodes, ordered_prims, verts, device, None, instances, n_top_nodes, animated, normals, prim_alpha, uvs,
+                   alpha_textures)
         return self
 
     @classmethod
     def build_on_device(cls, prims, verts, max_prims_in_node=4, split_method="sah", prim_bounds=None,
-                        device=0, normals=None, prim_alpha=None, uvs=None):
+                        device=0, normals=None, prim_alpha=None, uvs=None, alpha_textures=None):
         """Tree built AND baked on the GPU (nnbvh_scene_create_gpu_build): the tree never visits the
         host.  Same traversal results as the host-built aggregate; `nodes` / `ordered_prims` are
         not available on this object.  normals (per vertex) / prim_alpha (per entry of `prims`, the caller's order):
-        what the smooth alpha-tested kinds and the alpha-tested patches read."""
+        what the smooth alpha-tested kinds and the alpha-tested patches read.  alpha_textures: a sequence of
+        AlphaTexture, the table the kinds 16 .. 19 index with v[3]; uvs gives them their (u, v)."""
         if split_method not in ("sah", "hlbvh"):
             raise NNBVHError(f'GPU build supports "sah" and "hlbvh", not "{split_method}"')
         self = cls.__new__(cls)
@@ -212,11 +216,19 @@ class BVHAggregate:
         nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(len(verts), 3)
         pa = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(len(prims))
         uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(len(verts), 2)
-        self._h = L.nnbvh_scene_create_gpu_build_with_attributes(
-            ptr(prims), len(prims), ptr(verts), len(verts), ptr(pb) if pb is not None else None,
-            ptr(nrm) if nrm is not None else None, ptr(uv) if uv is not None else None,
-            ptr(pa) if pa is not None else None,
-            int(max_prims_in_node), SPLIT_METHODS[split_method], self.device)
+        if alpha_textures is not None:
+            self.alpha_textures, n_tex = _lib.alpha_texture_table(alpha_textures)
+            self._h = L.nnbvh_scene_create_gpu_build_with_alpha_textures(
+                ptr(prims), len(prims), ptr(verts), len(verts), ptr(pb) if pb is not None else None,
+                ptr(nrm) if nrm is not None else None, ptr(uv) if uv is not None else None,
+                ptr(pa) if pa is not None else None, int(max_prims_in_node), SPLIT_METHODS[split_method], self.device,
+                self.alpha_textures, n_tex)
+        else:
+            self._h = L.nnbvh_scene_create_gpu_build_with_attributes(
+                ptr(prims), len(prims), ptr(verts), len(verts), ptr(pb) if pb is not None else None,
+                ptr(nrm) if nrm is not None else None, ptr(uv) if uv is not None else None,
+                ptr(pa) if pa is not None else None,
+                int(max_prims_in_node), SPLIT_METHODS[split_method], self.device)
         if not self._h:
             raise NNBVHError("nnbvh_scene_create_gpu_build: " + _lib.last_error())
         self._read_info()
@@ -286,10 +298,18 @@ class BVHAggregate:
     def read(self, what):
         """The baked device arrays (nnbvh_scene_read) as bytes-exact numpy arrays: 0 = interior records
         (uint32 [n, 16]), 1 = primitive stream (uint32 [slots, 4]), 2 = animation table (float32 [instances, 76];
-        None for scenes without one)."""
-        if what not in (0, 1, 2):
-            raise NNBVHError(f"read: unknown array {what!r} (0 interior records, 1 primitive stream, 2 animation table)")
-        if what == 2:
+        None for scenes without one), 3 = alpha-texture descriptor table (uint32 [textures, 12]), 4 = alpha texel pool
+        (float32 [texels]; both None for scenes without alpha textures)."""
+        if what not in (0, 1, 2, 3, 4):
+            raise NNBVHError(f"read: unknown array {what!r} (0 interior records, 1 primitive stream, 2 animation table, "
+                             "3 alpha-texture table, 4 alpha texel pool)")
+        if what in (3, 4):
+            table = getattr(self, "alpha_textures", None)
+            if table is None:
+                return None
+            out = (np.zeros((len(table), 12), np.uint32) if what == 3
+                   else np.zeros(sum(t.width * t.height for t in table), np.float32))
+        elif what == 2:
             n = 0 if getattr(self, "animated", None) is None else len(self.animated)
             if n == 0:
                 return None
@@ -310,13 +330,28 @@ class BVHAggregate:
                      "grid_blocks": int(info[4]), "stack_window": int(info[5])}
 
     def _init(self, nodes, ordered_prims, verts, device, depth, instances=None, n_top_nodes=None, animated=None,
-              normals=None, prim_alpha=None, uvs=None):
+              normals=None, prim_alpha=None, uvs=None, alpha_textures=None):
         L = _lib.lib()
         self.nodes = np.ascontiguousarray(nodes, NODE_DTYPE)
         self.ordered_prims = np.ascontiguousarray(ordered_prims, PRIM_DTYPE)
         self.verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
         self.device = int(device)
-        if instances is not None and len(instances):
+        if alpha_textures is not None:
+            if instances is not None and len(instances):
+                raise NNBVHError("alpha_textures: image-textured alpha is for flat scenes, not two-level ones")
+            self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+            self.prim_alpha = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(-1)
+            self.uvs = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)
+            assert self.prim_alpha is None or len(self.prim_alpha) == len(self.ordered_prims)
+            assert self.normals is None or len(self.normals) == len(self.verts)
+            assert self.uvs is None or len(self.uvs) == len(self.verts)
+            self.alpha_textures, n_tex = _lib.alpha_texture_table(alpha_textures)
+            opt = lambda a: ptr(a) if a is not None else None  # noqa: E731
+            self._h = L.nnbvh_scene_create_with_alpha_textures(
+                ptr(self.nodes), len(self.nodes), ptr(self.ordered_prims), len(self.ordered_prims), ptr(self.verts),
+                opt(self.normals), opt(self.uvs), opt(self.prim_alpha), len(self.verts), self.device,
+                self.alpha_textures, n_tex)
+        elif instances is not None and len(instances):
             self.instances = np.ascontiguousarray(instances, _lib.INSTANCE_DTYPE)
             if normals is not None or prim_alpha is not None or uvs is not None:
                 f32 = lambda a, w: None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, w)  # noqa: E731

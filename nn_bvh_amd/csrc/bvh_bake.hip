@@ -44,6 +44,10 @@ __global__ __launch_bounds__(kBk) void k_bake_slot_counts(const nnbvh_prim *__re
         c = alpha_patch_slots(kind);  // four slots of vertex normals and / or two of (u, v) follow the patch's
         atomicOr(flags, 4 | 8 | 32 | (is_smooth_alpha_patch_kind(kind) ? 16 : 0) | (is_uv_alpha_patch_kind(kind) ? 64 : 0));
     }
+    else if (is_alphatex_kind(kind)) {
+        c = alphatex_slots(kind);  // (three slots of vertex normals and) two of (u, v) follow the triangle's
+        atomicOr(flags, 8 | 128 | (is_smooth_alphatex_kind(kind) ? 16 : 0));
+    }
     else if (kind == NNBVH_PRIM_INSTANCE && instances) c = 6;
     else if (kind != NNBVH_PRIM_TRIANGLE) atomicOr(flags, 2);  // instances are not baked here
     slots[i] = c;
@@ -135,6 +139,26 @@ __global__ __launch_bounds__(kBk) void k_bake_stream(const nnbvh_prim *__restric
         alpha = __int_as_float(p.v[3]);
         for (int j = 0; j < 3; ++j)
             s[3 + j] = make_float4(normals[3 * (long)p.v[j]], normals[3 * (long)p.v[j] + 1], normals[3 * (long)p.v[j] + 2], 0);
+    }
+    if (is_alphatex_kind(p.kind)) {
+        // the texture index where kind 4 keeps alpha; the normals of the smooth kinds; then the three (u, v) pairs, the
+        // reference's default corners for a mesh without (shapes.h, InteractionFromIntersection)
+        flags |= kPrimAlpha | kPrimAlphaTex | (is_flipped_alphatex_kind(p.kind) ? kPrimFlipN : 0u);
+        alpha = __int_as_float(p.v[3]);
+        float4 *u = s + 3;
+        if (is_smooth_alphatex_kind(p.kind)) {
+            flags |= kPrimSmooth;
+            for (int j = 0; j < 3; ++j)
+                s[3 + j] = make_float4(normals[3 * (long)p.v[j]], normals[3 * (long)p.v[j] + 1], normals[3 * (long)p.v[j] + 2], 0);
+            u = s + 6;
+        }
+        if (uvs) {
+            u[0] = make_float4(uvs[2 * (long)p.v[0]], uvs[2 * (long)p.v[0] + 1], uvs[2 * (long)p.v[1]], uvs[2 * (long)p.v[1] + 1]);
+            u[1] = make_float4(uvs[2 * (long)p.v[2]], uvs[2 * (long)p.v[2] + 1], 0, 0);
+        } else {
+            u[0] = make_float4(0, 0, 1, 0);
+            u[1] = make_float4(1, 1, 0, 0);
+        }
     }
     if (is_alpha_patch_kind(p.kind)) {
         flags |= kPrimAlpha | (is_flipped_alpha_patch_kind(p.kind) ? kPrimFlipN : 0u);
@@ -345,6 +369,10 @@ bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int
                  "(nnbvh_scene_create_with_attributes)";
         return false;
     }
+    if ((flags & 128) && (flags & 32)) {
+        *error = "scene_create: image-textured alpha on triangles and alpha-tested patches in one scene are not supported";
+        return false;
+    }
     if (nSlots <= 0 || nSlots >= 0x7ffffffe) {
         *error = "device bake: primitive stream exceeds 2^31 slots";
         return false;
@@ -379,7 +407,8 @@ bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int
     std::memcpy(out->bounds + 3, root.pmax, 12);
     out->has_host_prims = flags & 1;
     out->has_patches = (flags & 4) ? 1 : 0;
-    out->has_alpha = (flags & 32) ? 2 : ((flags & 8) ? 1 : 0);  // 2: alpha-tested PATCHES present (the ALPHA = 2 kernels)
+    // 2: alpha-tested PATCHES present (the ALPHA = 2 kernels), 3: image-textured alpha on triangles (ALPHA = 3)
+    out->has_alpha = (flags & 128) ? 3 : ((flags & 32) ? 2 : ((flags & 8) ? 1 : 0));
     return true;
 }
 

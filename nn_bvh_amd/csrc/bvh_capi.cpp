@@ -9,6 +9,7 @@
 #include <limits>
 #include <vector>
 
+#include "alpha_texture_math.h"
 #include "bvh_build_gpu.h"
 #include "capi_internal.h"
 
@@ -143,6 +144,86 @@ void nnbvh::fill_anim_entry(const nnbvh_animated_transform &a, float *t) {
     t[74] = a.actually_animated ? 1.0f : 0.0f;
 }
 
+// ---- image-textured alpha (kinds 16 .. 19) ---------------------------------------------------------------------
+// Everything the kernel indexes a texture with, checked on the host before a device is looked at; `fn` names the call.
+static bool check_alpha_textures(const char *fn, const nnbvh_prim *prims, int n_prims, const float *normals,
+                                 const nnbvh_alpha_texture *textures, int n_textures) {
+    auto fault = [&](const std::string &what) {
+        set_error(std::string(fn) + ": " + what);
+        return false;
+    };
+    if (n_textures < 0 || (n_textures > 0 && !textures)) return fault("null alpha-texture table");
+    static_assert(NNBVH_WRAP_REPEAT == kWrapRepeat && NNBVH_WRAP_CLAMP == kWrapClamp && NNBVH_WRAP_BLACK == kWrapBlack,
+                  "alpha_texture_math.h restates the wrap modes");
+    for (int k = 0; k < n_textures; ++k) {
+        const nnbvh_alpha_texture &t = textures[k];
+        const std::string which = "alpha texture " + std::to_string(k);
+        if (!t.texels) return fault(which + " has null texels");
+        if (t.width < 1 || t.width > kMaxAlphaTexSize || t.height < 1 || t.height > kMaxAlphaTexSize)
+            return fault(which + ": width and height must be 1 .. 2^24");
+        if (t.wrap != NNBVH_WRAP_REPEAT && t.wrap != NNBVH_WRAP_CLAMP && t.wrap != NNBVH_WRAP_BLACK)
+            return fault(which + ": unknown wrap mode (NNBVH_WRAP_REPEAT, _CLAMP or _BLACK; OctahedralSphere is not supported)");
+    }
+    bool textured = false, patches = false;
+    for (int i = 0; prims && i < n_prims; ++i) {
+        const nnbvh_prim &p = prims[i];
+        patches = patches || is_alpha_patch_kind(p.kind);
+        if (!is_alphatex_kind(p.kind)) continue;
+        textured = true;
+        if (n_textures == 0) return fault("NNBVH_PRIM_ALPHATEX_TRIANGLE primitives need the alpha-texture table");
+        if (p.v[3] < 0 || p.v[3] >= n_textures) return fault("alpha-texture index out of range");
+        if (is_smooth_alphatex_kind(p.kind) && !normals)
+            return fault("NNBVH_PRIM_ALPHATEX_TRIANGLE_SMOOTH primitives need the vertex normals");
+    }
+    if (textured && patches)
+        return fault("image-textured alpha on triangles and alpha-tested patches (kinds 8 .. 15) in one scene are not "
+                     "supported");
+    return true;
+}
+
+// the scene's descriptor table and texel pool (alpha_texture_math.h), uploaded once; false: the scene is destroyed
+static bool attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *textures, int n_textures) {
+    if (!s || n_textures <= 0) return s != nullptr;
+    std::vector<AlphaTexDesc> table((size_t)n_textures);
+    uint64_t total = 0;
+    for (int k = 0; k < n_textures; ++k) {
+        const nnbvh_alpha_texture &t = textures[k];
+        AlphaTexDesc &d = table[(size_t)k];
+        d.texelLo = (uint32_t)total;
+        d.texelHi = (uint32_t)(total >> 32);
+        d.width = t.width;
+        d.height = t.height;
+        d.wrap = t.wrap;
+        d.pointFilter = t.point_filter ? 1 : 0;
+        d.su = t.su, d.sv = t.sv, d.du = t.du, d.dv = t.dv;
+        d.scale = t.scale;
+        d.invert = t.invert ? 1 : 0;
+        total += (uint64_t)t.width * (uint64_t)t.height;
+    }
+    DeviceGuard guard(s->device);
+    bool ok = guard.ok && hip_ok(hipMalloc((void **)&s->d_alpha_tex, table.size() * sizeof(AlphaTexDesc)), "hipMalloc(alpha textures)") &&
+              hip_ok(hipMalloc((void **)&s->d_alpha_texels, (size_t)total * 4), "hipMalloc(alpha texels)") &&
+              hip_ok(hipMemcpy(s->d_alpha_tex, table.data(), table.size() * sizeof(AlphaTexDesc), hipMemcpyHostToDevice),
+                     "hipMemcpy(alpha textures)");
+    uint64_t at = 0;
+    for (int k = 0; ok && k < n_textures; ++k) {
+        const uint64_t n = (uint64_t)textures[k].width * (uint64_t)textures[k].height;
+        ok = hip_ok(hipMemcpy(s->d_alpha_texels + at, textures[k].texels, (size_t)n * 4, hipMemcpyHostToDevice),
+                    "hipMemcpy(alpha texels)");
+        at += n;
+    }
+    if (!ok) {
+        const std::string why = nnbvh_last_error();
+        nnbvh_scene_destroy(s);
+        set_error(why);
+        return false;
+    }
+    s->n_alpha_tex = n_textures;
+    s->n_alpha_texels = (int64_t)total;
+    s->device_bytes += table.size() * sizeof(AlphaTexDesc) + (size_t)total * 4;
+    return true;
+}
+
 extern "C" {
 
 const char *nnbvh_last_error(void) { return g_error.c_str(); }
@@ -248,7 +329,7 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
                                  int n_verts, const nnbvh_instance *instances, int n_instances,
                                  int device, const nnbvh_animated_transform *animated = nullptr,
                                  const float *normals = nullptr, const float *prim_alpha = nullptr,
-                                 const float *uvs = nullptr) {
+                                 const float *uvs = nullptr, bool alpha_textures = false) {
     if (!nodes || !prims || !verts || n_prims <= 0 || n_verts <= 0 || n_instances < 0 ||
         (n_instances > 0 && !instances) || n_top_nodes < 1 || n_top_nodes > n_nodes) {
         set_error("scene_create: null or empty input array");
@@ -304,7 +385,10 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
                 return nullptr;
             }
         } else if (is_triangle_kind(p.kind)) nv = nslots = 3;
-        else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = nslots = 4;
+        else if (alpha_textures && is_alphatex_kind(p.kind)) {  // flat scenes (checked by check_alpha_textures)
+            nv = 3;
+            nslots = alphatex_slots(p.kind);
+        } else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = nslots = 4;
         else if (p.kind == NNBVH_PRIM_HOST) {
             nv = 0;
             nslots = 3;
@@ -316,7 +400,8 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
                 return nullptr;
             }
         } else {
-            set_error("scene_create: unknown primitive kind");
+            set_error(is_alphatex_kind(p.kind) ? std::string("scene_create: ") + kAlphaTexElsewhere
+                                               : std::string("scene_create: unknown primitive kind"));
             return nullptr;
         }
         for (int j = 0; j < nv; ++j)
@@ -489,10 +574,16 @@ nnbvh_scene *nnbvh_scene_create_gpu_build(const nnbvh_prim *prims, int n_prims, 
                                                         nullptr, max_prims_in_node, split_method, device);
 }
 
-nnbvh_scene *nnbvh_scene_create_gpu_build_with_attributes(const nnbvh_prim *prims_in, int n_prims, const float *verts,
-                                                          int n_verts, const float *prim_bounds, const float *normals,
-                                                          const float *uvs, const float *prim_alpha,
-                                                          int max_prims_in_node, int split_method, int device) {
+// (alpha_textures: the caller has checked the table; without it the kinds 16 .. 19 are unknown here)
+static nnbvh_scene *create_scene_gpu_build(const nnbvh_prim *prims_in, int n_prims, const float *verts, int n_verts,
+                                           const float *prim_bounds, const float *normals, const float *uvs,
+                                           const float *prim_alpha, int max_prims_in_node, int split_method, int device,
+                                           bool alpha_textures) {
+    for (int i = 0; prims_in && !alpha_textures && i < n_prims; ++i)
+        if (is_alphatex_kind(prims_in[i].kind)) {
+            set_error(std::string("nnbvh_build_create: ") + kAlphaTexElsewhere);
+            return nullptr;
+        }
     const nnbvh_prim *prims = prims_in;
     // with a per-primitive array to carry along, the build runs with ids = positions; the bake's gather pass puts the
     // caller's ids back (bvh_bake.hip)
@@ -560,6 +651,38 @@ nnbvh_scene *nnbvh_scene_create_gpu_build_with_attributes(const nnbvh_prim *prim
     if (!s) return nullptr;
     s->build_ms[0] = r.ms[0] + r.ms[1] + r.ms[2] + r.ms[3] + r.ms[4];
     return s;
+}
+
+nnbvh_scene *nnbvh_scene_create_gpu_build_with_attributes(const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                          int n_verts, const float *prim_bounds, const float *normals,
+                                                          const float *uvs, const float *prim_alpha,
+                                                          int max_prims_in_node, int split_method, int device) {
+    return create_scene_gpu_build(prims, n_prims, verts, n_verts, prim_bounds, normals, uvs, prim_alpha, max_prims_in_node,
+                                  split_method, device, false);
+}
+
+nnbvh_scene *nnbvh_scene_create_gpu_build_with_alpha_textures(const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                              int n_verts, const float *prim_bounds,
+                                                              const float *normals, const float *uvs,
+                                                              const float *prim_alpha, int max_prims_in_node,
+                                                              int split_method, int device,
+                                                              const nnbvh_alpha_texture *textures, int n_textures) {
+    if (!check_alpha_textures("nnbvh_scene_create_gpu_build_with_alpha_textures", prims, n_prims, normals, textures, n_textures))
+        return nullptr;
+    nnbvh_scene *s = create_scene_gpu_build(prims, n_prims, verts, n_verts, prim_bounds, normals, uvs, prim_alpha,
+                                            max_prims_in_node, split_method, device, true);
+    return attach_alpha_textures(s, textures, n_textures) ? s : nullptr;
+}
+
+nnbvh_scene *nnbvh_scene_create_with_alpha_textures(const nnbvh_linear_node *nodes, int n_nodes, const nnbvh_prim *prims,
+                                                    int n_prims, const float *verts, const float *normals,
+                                                    const float *uvs, const float *prim_alpha, int n_verts, int device,
+                                                    const nnbvh_alpha_texture *textures, int n_textures) {
+    if (!check_alpha_textures("nnbvh_scene_create_with_alpha_textures", prims, n_prims, normals, textures, n_textures))
+        return nullptr;
+    nnbvh_scene *s = create_scene(nodes, n_nodes, n_nodes, prims, n_prims, verts, n_verts, nullptr, 0, device, nullptr,
+                                  normals, prim_alpha, uvs, true);
+    return attach_alpha_textures(s, textures, n_textures) ? s : nullptr;
 }
 
 nnbvh_scene *nnbvh_scene_create(const nnbvh_linear_node *nodes, int n_nodes,
@@ -653,6 +776,8 @@ void nnbvh_scene_destroy(nnbvh_scene *s) {
     if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     (void)hipFree(s->d_wide);  // d_prims points into the same allocation
     if (s->d_anim) (void)hipFree(s->d_anim);
+    if (s->d_alpha_tex) (void)hipFree(s->d_alpha_tex);
+    if (s->d_alpha_texels) (void)hipFree(s->d_alpha_texels);
     if (s->d_stats) (void)hipFree(s->d_stats);
     delete s;
 }
@@ -685,9 +810,27 @@ int nnbvh_scene_read(const nnbvh_scene *s, int what, void *out, size_t bytes) {
         set_error("scene_read: null argument");
         return NNBVH_ERR_ARG;
     }
-    if (what < 0 || what > 2) {
-        set_error("scene_read: unknown array (0 interior records, 1 primitive stream, 2 animation table)");
+    if (what < 0 || what > 4) {
+        set_error("scene_read: unknown array (0 interior records, 1 primitive stream, 2 animation table, 3 alpha-texture "
+                  "table, 4 alpha texel pool)");
         return NNBVH_ERR_ARG;
+    }
+    if (what >= 3) {
+        if (!s->d_alpha_tex) {
+            set_error("scene_read: the scene has no alpha textures");
+            return NNBVH_ERR_ARG;
+        }
+        const void *from = what == 3 ? (const void *)s->d_alpha_tex : (const void *)s->d_alpha_texels;
+        const size_t size = what == 3 ? (size_t)s->n_alpha_tex * 48 : (size_t)s->n_alpha_texels * 4;
+        if (bytes != size) {
+            set_error("scene_read: " + std::to_string(bytes) + " bytes asked for, the array has " + std::to_string(size));
+            return NNBVH_ERR_ARG;
+        }
+        DeviceGuard guard(s->device);
+        if (!guard.ok) return NNBVH_ERR_DEVICE;
+        if (!hip_ok(hipDeviceSynchronize(), "scene_read") || !hip_ok(hipMemcpy(out, from, bytes, hipMemcpyDeviceToHost), "scene_read"))
+            return NNBVH_ERR_DEVICE;
+        return NNBVH_OK;
     }
     if (what == 2 && !s->d_anim) {
         set_error("scene_read: the scene has no animation table");

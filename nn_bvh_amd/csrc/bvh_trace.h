@@ -70,6 +70,10 @@ struct TraceParams {
     // (walk_math.h).  The batch is rays / n / nDev; a lane's ray index is its work item
     ShadingMeshDevice wMesh;
     WalkParams walk;
+    // image-textured alpha (the ALPHA = 3 instances), appended for the same reason: the scene's descriptor table (three
+    // 16-B slots per texture, AlphaTexDesc of alpha_texture_math.h) and its texel pool
+    const float4 *alphaTex;
+    const float *alphaTexels;
 };
 
 hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream);
@@ -79,7 +83,8 @@ hipError_t launch_zero_words(int32_t *words, long n, int maxBlocks, hipStream_t 
 // occupancy != nullptr: do not launch, report resident blocks per CU of that kernel instance
 // patches: bit 0 = the scene holds bilinear patches (0: kernel instances without the parked ray direction),
 // bit 1 = it holds alpha-tested triangles (the ALPHA = 1 kernel instances), bit 2 = alpha-tested bilinear patches
-// too (the ALPHA = 2 instances)
+// too (the ALPHA = 2 instances), bit 3 = triangles with an image-textured alpha (the ALPHA = 3 instances: flat scenes,
+// window 8)
 hipError_t launch_trace(int mode, const TraceParams &p, int window, int instanced, int patches, int blocks,
                         hipStream_t stream, int *occupancy);
 

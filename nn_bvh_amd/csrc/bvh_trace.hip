@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "bvh_trace.h"
+#include "alpha_texture_math.h"
 #include "anim_math.h"
 #include "spawn_math.h"
 #include "stream_access.h"
@@ -83,6 +84,9 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // separately so that other scenes pay nothing for the hash and the re-trace.
 // ALPHA = 2: ... and alpha-tested bilinear patches (the patch's interaction point and normal incl. the (s, t)
 // reparametrisation, the re-trace loop).
+// ALPHA = 3: the scene holds triangles whose alpha is an image texture (kPrimAlphaTex; flat scenes, no alpha-tested
+// patches): the ALPHA = 1 path where, for such a triangle, alpha is FloatImageTexture::Evaluate at the hit's (u, v)
+// (alpha_texture_math.h) instead of the constant in slot 2.  Constant-alpha triangles run as in ALPHA = 1.
 // SOA = 1 (lean instances of modes 0, 2, 3 only): a batch without nnbvh_ray records (rays == nullptr) is read as the
 // SOA<Ray> slices of a wavefront queue — no gather pass.  Its own instances: the mere presence of the second fetch
 // path in the refill trip cost the one-launch step 1.3 % (9.31 -> 9.44 ms).
@@ -124,6 +128,11 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // registers) no faster
 #ifndef NNBVH_MINW_ALPHA_PATCH
 #define NNBVH_MINW_ALPHA_PATCH 3
+#endif
+// ALPHA = 3 (tools/isa_regs.py, profiles/alpha_texture.txt): at 5 waves the closest-hit instances spill 2-6 registers,
+// at 4 none (93-102 VGPRs)
+#ifndef NNBVH_MINW_ALPHA_TEX
+#define NNBVH_MINW_ALPHA_TEX 4
 #endif
 // the walk instances (MODE 4 / 5, DESIGN.md §5.5.1: the interaction, the spawn and the reservoir update at retire):
 // bounds chosen from tools/isa_regs.py as the most waves at which no instance spills
@@ -203,7 +212,7 @@ __device__ __forceinline__ T pick_batch(const T (&a)[kMaxFusedBatches], int b) {
 // one with the triangle-only code.  Window 8 only; no ALPHA, SOA, HOSTC or INST = 2 forms.  (WALK rides in the first
 // template argument and not as an eighth one: that would rename every existing instance.)
 template <int MODEW, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
-__global__ __launch_bounds__(kBlockThreads, (MODEW >= 4 ? (INST ? 1 : (PATCH ? NNBVH_MINW_WALK : NNBVH_MINW_WALK_LEAN)) : (INST ? 1 : (ALPHA ? (ALPHA == 2 ? NNBVH_MINW_ALPHA_PATCH : NNBVH_MINW_ALPHA) : ((MODEW == 0 || MODEW == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (PATCH ? 0 : NNBVH_LEAN_EXTRA_WAVES)))))
+__global__ __launch_bounds__(kBlockThreads, (MODEW >= 4 ? (INST ? 1 : (PATCH ? NNBVH_MINW_WALK : NNBVH_MINW_WALK_LEAN)) : (INST ? 1 : (ALPHA ? (ALPHA == 2 ? NNBVH_MINW_ALPHA_PATCH : (ALPHA == 3 ? NNBVH_MINW_ALPHA_TEX : NNBVH_MINW_ALPHA)) : ((MODEW == 0 || MODEW == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (PATCH ? 0 : NNBVH_LEAN_EXTRA_WAVES)))))
 void trace_kernel(TraceParams p) {
     constexpr int WALK = MODEW >= 4 ? MODEW - 3 : 0;
     constexpr int MODE = WALK ? 0 : MODEW;
@@ -211,6 +220,7 @@ void trace_kernel(TraceParams p) {
                   "walk instances: the plain record-reading closest-hit form at window 8");
     static_assert(PATCH || !INST, "two-level scenes need the ray direction");
     static_assert(PATCH || !ALPHA, "the alpha test hashes the ray direction");
+    static_assert(ALPHA != 3 || (INST == 0 && W == 8 && MODE != 3), "textured alpha: flat scenes, window 8, modes 0 / 1 / 2");
     static_assert(!HOSTC || (PATCH && (MODE == 0 || MODE == 2 || (MODE == 3 && !ALPHA && W == 8)) && !SOA),
                   "candidate mode: general instances of modes 0 / 2 / 3");
     // the stack window: entry k of a lane = (child reference, entry distance), the two words 64 dwords
@@ -430,10 +440,27 @@ void trace_kernel(TraceParams p) {
                                     {s0.x, s0.y, s0.z}, {s1.x, s1.y, s1.z},
                                     {s2.x, s2.y, s2.z}, x0, x1, x2, th, kLean ? &masks : nullptr);
                 next = slot + ((ALPHA && (flags & kPrimSmooth)) ? 6 : 3);
+                if constexpr (ALPHA == 3) next += (flags & kPrimAlphaTex) ? 2 : 0;  // the (u, v) slots
                 if (ALPHA && hit && (flags & kPrimAlpha)) {
                     // GeometricPrimitive::Intersect, cpu/primitive.cpp:57-70 (IntersectP takes
                     // the same route, :79-81): stochastic alpha test on the ray as given
-                    const float a = s2.w;
+                    [[maybe_unused]] float aTex = 0.0f;
+                    if constexpr (ALPHA == 3) {
+                        // alpha.Evaluate(si->intr) of a FloatImageTexture: the (u, v) slots, the descriptor and the
+                        // texels are read here, on a hit only, and are dead before the normals are fetched below
+                        if (flags & kPrimAlphaTex) {
+                            const float4 *uvp = p.prims + slot + ((flags & kPrimSmooth) ? 6 : 3);
+                            const float4 uva = uvp[0], uvb = uvp[1];
+                            const float4 *dp = p.alphaTex + 3 * (long)__float_as_int(s2.w);
+                            const float4 d0 = dp[0], d1 = dp[1], d2 = dp[2];
+                            const AlphaTexDesc desc = {__float_as_uint(d0.x), __float_as_uint(d0.y), __float_as_int(d0.z),
+                                                       __float_as_int(d0.w), __float_as_int(d1.x), __float_as_int(d1.y),
+                                                       d1.z, d1.w, d2.x, d2.y, d2.z, __float_as_int(d2.w)};
+                            aTex = alpha_texture_eval(x0, x1, x2, uva.x, uva.y, uva.z, uva.w, uvb.x, uvb.y, desc,
+                                                      p.alphaTexels);
+                        }
+                    }
+                    const float a = (ALPHA == 3 && (flags & kPrimAlphaTex)) ? aTex : s2.w;
                     if (a < 1) {
                         const V3 rd = {cold[kColdD][lane], cold[kColdD + 1][lane],
                                        cold[kColdD + 2][lane]};
@@ -962,6 +989,8 @@ static hipError_t launch_inst(const TraceParams &p, int instanced, int blocks, h
 template <int MODE, int HOSTC>
 static hipError_t launch_general(const TraceParams &p, int instanced, int patches, int blocks, hipStream_t stream,
                                  int *occupancy) {
+    if (patches & 8)  // triangles with an image-textured alpha: flat scenes only (the creation calls see to it)
+        return instanced ? hipErrorInvalidValue : launch_one<MODE, 8, 0, 1, 3, 0, HOSTC>(p, blocks, stream, occupancy);
     if (patches & 4) return launch_inst<MODE, 2, HOSTC>(p, instanced, blocks, stream, occupancy);  // alpha-tested patches
     if (patches & 2) return launch_inst<MODE, 1, HOSTC>(p, instanced, blocks, stream, occupancy);  // alpha-tested triangles
     return launch_inst<MODE, 0, HOSTC>(p, instanced, blocks, stream, occupancy);

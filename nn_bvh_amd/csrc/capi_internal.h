@@ -86,7 +86,8 @@ struct nnbvh_scene {
     int instanced = 0;      // two-level scene: use the INST kernels
     int has_host_prims = 0;
     int has_patches = 1;    // 0: no bilinear patches, the lean kernels (no ray direction parked in LDS) run
-    int has_alpha = 0;      // 1: alpha-tested triangles present (the ALPHA kernels run), 2: alpha-tested patches too
+    int has_alpha = 0;      // 1: alpha-tested triangles present (the ALPHA kernels run), 2: alpha-tested patches too,
+                            // 3: triangles with an image-textured alpha (and maybe constant ones; no alpha-tested patches)
     int fused_batches = 1;  // nnbvh_trace_batches_device: one mode-3 launch where the batches allow it
     int int_repeat = 3;
     int prim_repeat = 2;
@@ -106,6 +107,12 @@ struct nnbvh_scene {
     hipStream_t side[kSideStreams] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr;
     hipEvent_t ev_join[kSideStreams] = {nullptr, nullptr, nullptr, nullptr};
+    // (last: the members above keep their places)
+    // image-textured alpha (kinds 16 .. 19): descriptor table (AlphaTexDesc, alpha_texture_math.h) and texel pool, or null
+    void *d_alpha_tex = nullptr;
+    float *d_alpha_texels = nullptr;
+    int n_alpha_tex = 0;
+    int64_t n_alpha_texels = 0;
 };
 
 struct nnbvh_shading_mesh {
@@ -155,8 +162,10 @@ inline bool grow(void **ptr, size_t *have, size_t need, const char *what) {
 }
 
 // launch_trace's `patches`: bit 0 patches (or alpha: the parked ray direction), bit 1 alpha-tested triangles,
-// bit 2 alpha-tested patches
-inline int patch_bits(const nnbvh_scene *s) { return s->has_patches + 2 * (s->has_alpha != 0) + 4 * (s->has_alpha == 2); }
+// bit 2 alpha-tested patches, bit 3 triangles with an image-textured alpha (the ALPHA = 3 instances)
+inline int patch_bits(const nnbvh_scene *s) {
+    return s->has_patches + 2 * (s->has_alpha != 0) + 4 * (s->has_alpha == 2) + 8 * (s->has_alpha == 3);
+}
 
 // both device arrays below 4 GiB (64 B per interior record, 16 B per primitive slot): the lean
 // kernel instances reach them with 32-bit byte offsets

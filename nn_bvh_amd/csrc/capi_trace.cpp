@@ -55,6 +55,8 @@ static TraceParams scene_params(const nnbvh_scene *s, const Workspace *w) {
     p.hasHostPrims = s->has_host_prims;
     p.spill = w->spill;
     p.anim = s->d_anim;
+    p.alphaTex = (const float4 *)s->d_alpha_tex;
+    p.alphaTexels = s->d_alpha_texels;
     return p;
 }
 

@@ -62,7 +62,10 @@ bool check_prims(const nnbvh_prim *prims, int n_prims, int n_verts, const PrimLi
                              "(nnbvh_scene_create_with_attributes)");
         } else if (is_triangle_kind(p.kind)) nv = 3;
         else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = 4;
-        else return fault("scene_create: unknown primitive kind");
+        else if (is_alphatex_kind(p.kind)) {  // a triangle for a tree; two-level scenes have no alpha-texture table
+            if (c.scene) return fault(std::string("scene_create: ") + kAlphaTexElsewhere);
+            nv = 3;
+        } else return fault("scene_create: unknown primitive kind");
         for (int j = 0; j < nv; ++j)
             if (p.v[j] < 0 || p.v[j] >= n_verts) return fault("nnbvh_build_create: vertex index out of range");
     }

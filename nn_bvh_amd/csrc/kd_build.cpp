@@ -339,6 +339,11 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_attributes(const nnbvh_prim
         nnbvh::set_error("nnbvh_kd_scene_create_gpu_build: empty primitive or vertex array");
         return nullptr;
     }
+    for (int k = 0; k < n_prims; ++k)
+        if (nnbvh::is_alphatex_kind(prims[k].kind)) {
+            nnbvh::set_error(std::string("nnbvh_kd_scene_create_gpu_build: ") + nnbvh::kAlphaTexElsewhere);
+            return nullptr;
+        }
     if (!kd_resolve_max_depth(n_prims, &max_depth)) return nullptr;
     int n_dev = 0;
     if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {

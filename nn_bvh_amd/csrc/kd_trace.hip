@@ -856,6 +856,11 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes
         set_error("kd_scene_create: null or empty argument");
         return nullptr;
     }
+    for (int k = 0; k < n_prims; ++k)
+        if (is_alphatex_kind(prims[k].kind)) {
+            set_error(std::string("kd_scene_create: ") + kAlphaTexElsewhere);
+            return nullptr;
+        }
     // ---- validate everything the kernel indexes with ---------------------------------------------
     for (int i = 0; i < n_indices; ++i)
         if (prim_indices[i] < 0 || prim_indices[i] >= n_prims) {

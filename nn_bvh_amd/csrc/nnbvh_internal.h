@@ -62,6 +62,10 @@ constexpr uint32_t kPrimAnimated = 128u;
 // (the re-trace after a rejected hit offsets along FaceForward(n, ns), shapes.h:939-951)
 constexpr uint32_t kPrimSmooth = 256u;
 constexpr uint32_t kPrimUV = 512u;  // alpha-tested patch of a mesh with (u, v) coordinates
+// alpha-tested triangle whose alpha is an image texture (kinds 16 .. 19; kPrimAlpha is set too): slot 2's fourth word
+// holds the index into the scene's alpha-texture table instead of alpha; after the triangle's three slots (and the
+// three normal slots of kPrimSmooth) two more follow, {u0, v0, u1, v1} {u2, v2, 0, 0}
+constexpr uint32_t kPrimAlphaTex = 1024u;
 constexpr int kAnimStride = 76;  // floats per entry of the animation table (layout: anim_math.h)
 constexpr bool is_triangle_kind(int kind) {
     return kind == NNBVH_PRIM_TRIANGLE || kind == NNBVH_PRIM_ALPHA_TRIANGLE || kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED ||
@@ -79,6 +83,18 @@ constexpr int alpha_patch_slots(int kind) { return 4 + (is_smooth_alpha_patch_ki
 constexpr bool is_flat_alpha_kind(int kind) {
     return kind == NNBVH_PRIM_ALPHA_TRIANGLE || kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED;
 }
+
+// image-textured alpha on triangles: kind = 16 + flipped + 2 * smooth.  NOT an is_triangle_kind: only the builders and
+// the flat creation calls with an alpha-texture table take them
+constexpr bool is_alphatex_kind(int kind) { return kind >= NNBVH_PRIM_ALPHATEX_TRIANGLE && kind <= NNBVH_PRIM_ALPHATEX_TRIANGLE_SMOOTH_FLIPPED; }
+constexpr bool is_smooth_alphatex_kind(int kind) { return is_alphatex_kind(kind) && ((kind - NNBVH_PRIM_ALPHATEX_TRIANGLE) & 2); }
+constexpr bool is_flipped_alphatex_kind(int kind) { return is_alphatex_kind(kind) && ((kind - NNBVH_PRIM_ALPHATEX_TRIANGLE) & 1); }
+constexpr int alphatex_slots(int kind) { return 5 + (is_smooth_alphatex_kind(kind) ? 3 : 0); }
+constexpr int kMaxAlphaTexSize = 1 << 24;
+// how every creation call without an alpha-texture table refuses them
+constexpr const char *kAlphaTexElsewhere =
+    "unknown primitive kind (image-textured alpha, kinds 16 .. 19, is for flat BVH scenes: "
+    "nnbvh_scene_create_with_alpha_textures / nnbvh_scene_create_gpu_build_with_alpha_textures)";
 
 constexpr int kMaxStack = 64;  // the reference's nodesToVisit[64], aggregates.cpp:538
 

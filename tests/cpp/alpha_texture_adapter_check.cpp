@@ -1,0 +1,71 @@
+// alpha_texture_adapter_check — the HipBVHAggregate overloads for image-textured alpha (include/nnbvh_aggregate.hpp)
+// compile with a plain host compiler and hand their arguments to the C ABI.  No argument: argument faults only (no
+// GPU).  "gpu": a four-triangle scene through both creation routes, whose closest hits must agree.
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "nnbvh_aggregate.hpp"
+
+static std::string g_last;
+
+int main(int argc, char **argv) {
+    nnbvh::HipBVHAggregate::fatal_handler() = [](const char *msg) { g_last = msg; };
+    std::vector<float> verts;
+    std::vector<nnbvh_prim> prims;
+    for (int k = 0; k < 4; ++k) {
+        const float x = 2.0f * k;
+        const float v[9] = {x, 0, 0, x + 1, 0, 0, x + 1, 1, 0};
+        verts.insert(verts.end(), v, v + 9);
+        prims.push_back(nnbvh_prim{k % 2 ? NNBVH_PRIM_ALPHATEX_TRIANGLE : NNBVH_PRIM_TRIANGLE, k, {3 * k, 3 * k + 1, 3 * k + 2, 0}});
+    }
+    const float texels[4] = {1.0f, 1.0f, 0.0f, 0.0f};  // default corners: the upper row only
+    std::vector<nnbvh_alpha_texture> textures{{texels, 2, 2, NNBVH_WRAP_CLAMP, 1, 1, 1, 0, 0, 1, 0}};
+    const bool gpu = argc > 1 && !std::strcmp(argv[1], "gpu");
+    const int device = gpu ? 0 : (1 << 20);
+
+    nnbvh_build *b = nnbvh_build_create(prims.data(), (int)prims.size(), verts.data(), (int)verts.size() / 3, 4, NNBVH_SPLIT_SAH);
+    if (!b) return 1;
+    int nNodes = 0, nPrims = 0;
+    const nnbvh_linear_node *nodes = nnbvh_build_nodes(b, &nNodes);
+    const nnbvh_prim *ordered = nnbvh_build_ordered_prims(b, &nPrims);
+    if (!gpu) {
+        {
+            nnbvh::HipBVHAggregate a(nodes, nNodes, ordered, nPrims, verts.data(), (int)verts.size() / 3, textures, device);
+        }
+        if (g_last.find("no usable HIP device") == std::string::npos) return 2;
+        g_last.clear();
+        auto dev = nnbvh::HipBVHAggregate::BuildOnDevice(prims, verts, 4, "sah", device, nullptr, nullptr, nullptr, nullptr, &textures);
+        if (dev || g_last.find("no usable HIP device") == std::string::npos) return 3;
+        prims[1].v[3] = 5;  // no such texture
+        g_last.clear();
+        dev = nnbvh::HipBVHAggregate::BuildOnDevice(prims, verts, 4, "sah", device, nullptr, nullptr, nullptr, nullptr, &textures);
+        if (dev || g_last.find("nnbvh_scene_create_gpu_build_with_alpha_textures: alpha-texture index out of range") == std::string::npos)
+            return 4;
+        std::printf("alpha texture adapter ok (arguments)\n");
+        nnbvh_build_destroy(b);
+        return 0;
+    }
+    nnbvh::HipBVHAggregate tree(nodes, nNodes, ordered, nPrims, verts.data(), (int)verts.size() / 3, textures, device);
+    auto dev = nnbvh::HipBVHAggregate::BuildOnDevice(prims, verts, 4, "sah", device, nullptr, nullptr, nullptr, nullptr, &textures);
+    if (!dev || !g_last.empty()) {
+        std::fprintf(stderr, "%s\n", g_last.c_str());
+        return 5;
+    }
+    // one ray per triangle, at uvHit = (0.75, 0.25): st.t = 0.75, the lower row of the image, alpha 0: the textured
+    // triangles (1, 3) are never hit, the plain ones are
+    std::vector<nnbvh_ray> rays;
+    for (int k = 0; k < 4; ++k) rays.push_back(nnbvh_ray{{2.0f * k + 0.75f, 0.25f, 1.0f}, 10.0f, {0, 0, -1}, 0});
+    std::vector<nnbvh_hit> h0(4), h1(4);
+    if (nnbvh_intersect_closest(tree.handle(), rays.data(), 4, h0.data()) != NNBVH_OK ||
+        nnbvh_intersect_closest(dev->handle(), rays.data(), 4, h1.data()) != NNBVH_OK)
+        return 6;
+    for (int k = 0; k < 4; ++k) {
+        if (std::memcmp(&h0[k], &h1[k], sizeof(nnbvh_hit)) != 0) return 7;
+        if (h0[k].prim != (k % 2 ? -1 : k)) return 8;
+    }
+    std::printf("alpha texture adapter ok\n");
+    nnbvh_build_destroy(b);
+    return 0;
+}

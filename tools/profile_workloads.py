@@ -3,6 +3,8 @@
 tools/profile_bench.sh --script tools/profile_workloads.py <which> for rocprofv3 evidence (profiles/r03_*).
     patches   soup of 400 K triangles + 400 K bilinear patches: PATCH = 1 instances, closest / any / one-launch
     alpha     1 M-triangle soup, 70 % alpha-tested (kinds 4 / 5): ALPHA = 1 instances
+    alpha_tex the same soup with the alpha-tested triangles textured (kinds 16 / 17, one 1 024 x 1 024 texture): ALPHA = 3
+              instances, and the constant-alpha soup in the same process, runs alternated: median and min .. max
     inst      400 placements of one 33 K-triangle killeroo (tools/bench_instances.py's scene): INST = 1
     anim      36 placements of a small mesh, 24 of them AnimatedPrimitives (tests/test_animated.py's scene): INST = 2
     tr        IntersectShadowTr and IntersectOneRandom over 2 M items on sheets of interface surfaces: str_* / or_*
@@ -87,6 +89,51 @@ def main():
         agg = BVHAggregate.from_tree(tree.nodes, tree.ordered_prims, verts, normals=normals, prim_alpha=prim_alpha)
         rays = scene.random_rays(4_000_000, verts.min(0) - 2, verts.max(0) + 2, 34)
         trace_three(torch, agg, rays, which)
+    elif which == "alpha_tex":
+        from nn_bvh_amd import AlphaTexture
+        verts, prims = ss.random_soup(1_000_000, 0, 32, extent=60.0, size=0.9)
+        rng = np.random.default_rng(33)
+        prims = prims.copy()
+        kinds = rng.choice(np.array([0, 4, 5], np.int32), len(prims), p=[0.3, 0.4, 0.3])
+        values = np.array([0.0, 0.25, 0.5, 0.9, 1.0], np.float32)
+        alpha = rng.choice(values, len(prims))
+        prims["kind"] = kinds
+        prims["v"][:, 3] = np.where(kinds == 0, 0, alpha.view(np.int32))
+        textured = prims.copy()
+        textured["kind"] = np.where(kinds == 0, 0, kinds + 12)
+        textured["v"][:, 3] = 0
+        image = rng.choice(values, (1024, 1024))  # the same alphas, now per texel; no (u, v): the default corners
+        aggs = {"constant": BVHAggregate.build_on_device(prims, verts, 4, "sah"),
+                "textured": BVHAggregate.build_on_device(textured, verts, 4, "sah", alpha_textures=[AlphaTexture(image)])}
+        rays = scene.random_rays(4_000_000, verts.min(0) - 2, verts.max(0) + 2, 34)
+        n = len(rays)
+        d_r = torch.from_numpy(rays.view(np.uint8).reshape(-1)).cuda()
+        d_h = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
+        d_o = torch.empty(n, dtype=torch.uint8, device="cuda")
+        st = torch.cuda.current_stream().cuda_stream
+        calls = {"closest": lambda a: a.intersect_device(d_r.data_ptr(), d_h.data_ptr(), n, st),
+                 "any": lambda a: a.intersect_p_device(d_r.data_ptr(), d_o.data_ptr(), n, stream=st)}
+        times = {(k, c): [] for k in aggs for c in calls}
+        for it in range(8):  # alternated; the first round warms up
+            for k, a in aggs.items():
+                for c, fn in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn(a)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if it:
+                        times[k, c].append(e0.elapsed_time(e1))
+        for (k, c), ts in times.items():
+            print(f"alpha_tex {k} {c}: median {np.median(ts):.3f} ms, {min(ts):.3f} .. {max(ts):.3f} ms over {len(ts)} "
+                  f"alternated runs of {n} rays", flush=True)
+        from nn_bvh_amd import HIT_DTYPE
+        for k, a in aggs.items():
+            calls["closest"](a)
+            torch.cuda.synchronize()
+            h = d_h.cpu().numpy().view(HIT_DTYPE)
+            print(f"alpha_tex {k}: hit {np.mean(h['prim'] >= 0):.2f}, V {h['nodes_visited'].mean():.1f}, "
+                  f"T {h['prim_tests'].mean():.2f}")
     elif which == "anim":
         import test_animated as ta
         verts, prims, _, _, _, _, anims, oa, placements = ta.animated_scene(4, 36)
