@@ -1,5 +1,6 @@
-// capi_internal.h — what the host files of the C ABI share (bvh_capi.cpp, capi_trace.cpp, capi_wavefront.cpp,
-// capi_shading.cpp): the scene object, per-stream workspaces, the call prologue and the trace-job launcher.
+// capi_internal.h — what the host files of the C ABI share (bvh_capi.cpp, capi_trace.cpp, capi_kd.cpp,
+// capi_wavefront.cpp, capi_shading.cpp): the scene object, per-stream workspaces, the call prologue and the trace-job
+// launcher.
 // Included by .cpp files only, never by device code.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -214,7 +215,45 @@ bool batches_fusable(const nnbvh_scene *s, const nnbvh_batch *batches, int n_bat
 
 // candidates_fault (nnbvh_internal.h) reported as fn's
 bool candidates_ok(const char *fn, const nnbvh_host_candidates *c, bool closest);
-// the count (and, closest hit, before) arrays of a candidate call start at zero: kernel nodes on `stream`
-bool zero_candidates(const nnbvh_scene *s, const nnbvh_host_candidates *hc, int64_t n, bool closest, hipStream_t stream);
+// the count (and, closest hit, before) arrays of a candidate call start at zero: kernel nodes on `stream`, of up to
+// 8 blocks per CU of the scene's device
+bool zero_candidates(int n_cus, const nnbvh_host_candidates *hc, int64_t n, bool closest, hipStream_t stream);
+
+// The host-buffer form of a single-batch candidate call on a scene of either type: the rays and the candidate arrays
+// staged in device memory of the call's own, one launch on the null stream, copies out (synchronous).  The caller has
+// checked the arguments and n > 0.  launch_staged(workspace, d_rays, d_out, d) launches over the staged batch, whose
+// candidates are d, and returns NNBVH_OK once the null stream's copies out may follow.
+template <class S, class Launch>
+int candidates_host(S *s, bool closest, const nnbvh_ray *rays, int64_t n, void *out, const nnbvh_host_candidates *c,
+                    Launch launch_staged) {
+    SceneCall<S> call(s);
+    if (!call.ok()) return NNBVH_ERR_DEVICE;
+    const size_t k = (size_t)c->capacity, out_elem = closest ? sizeof(nnbvh_hit) : 1;
+    void *d_rays = nullptr, *d_out = nullptr;
+    nnbvh_host_candidates d{};
+    d.capacity = c->capacity;
+    bool ok = hip_ok(hipMalloc(&d_rays, (size_t)n * sizeof(nnbvh_ray)), "hipMalloc(rays)") &&
+              hip_ok(hipMalloc(&d_out, (size_t)n * out_elem), "hipMalloc(results)") &&
+              hip_ok(hipMalloc((void **)&d.count, (size_t)n * 4), "hipMalloc(count)") &&
+              (!closest || hip_ok(hipMalloc((void **)&d.before, (size_t)n * 4), "hipMalloc(before)")) &&
+              hip_ok(hipMalloc((void **)&d.prim, (size_t)n * k * 4), "hipMalloc(prim)") &&
+              hip_ok(hipMalloc((void **)&d.instance, (size_t)n * k * 4), "hipMalloc(instance)") &&
+              hip_ok(hipMemcpy(d_rays, rays, (size_t)n * sizeof(nnbvh_ray), hipMemcpyHostToDevice), "copy rays") &&
+              // the caller's entries beyond count stay as they were: start from them
+              hip_ok(hipMemcpy(d.prim, c->prim, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy prim") &&
+              hip_ok(hipMemcpy(d.instance, c->instance, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy instance");
+    auto *w = ok ? workspace_for(s, nullptr) : nullptr;
+    int rc = w ? launch_staged(w, d_rays, d_out, d) : NNBVH_ERR_DEVICE;
+    if (rc == NNBVH_OK &&
+        !(hip_ok(hipMemcpy(out, d_out, (size_t)n * out_elem, hipMemcpyDeviceToHost), "copy results") &&
+          hip_ok(hipMemcpy(c->count, d.count, (size_t)n * 4, hipMemcpyDeviceToHost), "copy count") &&
+          (!closest || hip_ok(hipMemcpy(c->before, d.before, (size_t)n * 4, hipMemcpyDeviceToHost), "copy before")) &&
+          hip_ok(hipMemcpy(c->prim, d.prim, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy prim") &&
+          hip_ok(hipMemcpy(c->instance, d.instance, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy instance")))
+        rc = NNBVH_ERR_DEVICE;
+    for (void *q : {d_rays, d_out, (void *)d.count, (void *)d.before, (void *)d.prim, (void *)d.instance})
+        if (q) (void)hipFree(q);
+    return rc;
+}
 
 }  // namespace nnbvh

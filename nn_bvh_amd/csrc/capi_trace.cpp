@@ -29,11 +29,10 @@ int nnbvh::grid_blocks(nnbvh_scene *s, int mode, int candidates) {
     return s->n_cus * per_cu;
 }
 
-bool nnbvh::zero_candidates(const nnbvh_scene *s, const nnbvh_host_candidates *hc, int64_t n, bool closest,
-                            hipStream_t stream) {
-    return hip_ok(launch_zero_words(hc->count, (long)n, s->n_cus * 8, stream), "candidate count reset launch") &&
+bool nnbvh::zero_candidates(int n_cus, const nnbvh_host_candidates *hc, int64_t n, bool closest, hipStream_t stream) {
+    return hip_ok(launch_zero_words(hc->count, (long)n, n_cus * 8, stream), "candidate count reset launch") &&
            (!closest || !hc->before ||
-            hip_ok(launch_zero_words(hc->before, (long)n, s->n_cus * 8, stream), "candidate before reset launch"));
+            hip_ok(launch_zero_words(hc->before, (long)n, n_cus * 8, stream), "candidate before reset launch"));
 }
 
 // the scene and workspace part of a launch's parameters; the launchers add the rays and the outputs
@@ -158,7 +157,7 @@ int nnbvh::launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream
         total += batches[i].n;
         if (cands && cands[i].capacity > 0) {
             const bool closest = batches[i].kind == NNBVH_BATCH_CLOSEST;
-            if (!zero_candidates(s, &cands[i], batches[i].n, closest, stream)) return NNBVH_ERR_DEVICE;
+            if (!zero_candidates(s->n_cus, &cands[i], batches[i].n, closest, stream)) return NNBVH_ERR_DEVICE;
             if (s->has_host_prims) {
                 p.hcCap = 1;  // selects the candidate-mode instances
                 p.bHcCap[b] = cands[i].capacity;
@@ -254,47 +253,17 @@ int nnbvh_intersect_any_candidates_device(nnbvh_scene *s, const void *d_rays, in
 
 }  // extern "C"
 
-// host buffers: one staged copy in, one launch on the null stream, copies out (synchronous)
+// host buffers (candidates_host of capi_internal.h stages them): the one launch is a trace job, mode 0 or 2
 static int candidates_host(const char *fn, nnbvh_scene *s, int mode, const nnbvh_ray *rays, int64_t n, void *out,
                            const nnbvh_host_candidates *c) {
     if (!batch_args_ok(fn, s, n, rays, out, candidates_fault(c, mode == 0))) return NNBVH_ERR_ARG;
     if (n == 0) return NNBVH_OK;
-    SceneCall call(s);
-    if (!call.ok()) return NNBVH_ERR_DEVICE;
-    const size_t k = (size_t)c->capacity, out_elem = mode == 0 ? sizeof(nnbvh_hit) : 1;
-    void *d_rays = nullptr, *d_out = nullptr;
-    nnbvh_host_candidates d{};
-    d.capacity = c->capacity;
-    auto release = [&]() {
-        for (void *q : {d_rays, d_out, (void *)d.count, (void *)d.before, (void *)d.prim, (void *)d.instance})
-            if (q) (void)hipFree(q);
-    };
-    bool ok = hip_ok(hipMalloc(&d_rays, (size_t)n * sizeof(nnbvh_ray)), "hipMalloc(rays)") &&
-              hip_ok(hipMalloc(&d_out, (size_t)n * out_elem), "hipMalloc(results)") &&
-              hip_ok(hipMalloc((void **)&d.count, (size_t)n * 4), "hipMalloc(count)") &&
-              (mode != 0 || hip_ok(hipMalloc((void **)&d.before, (size_t)n * 4), "hipMalloc(before)")) &&
-              hip_ok(hipMalloc((void **)&d.prim, (size_t)n * k * 4), "hipMalloc(prim)") &&
-              hip_ok(hipMalloc((void **)&d.instance, (size_t)n * k * 4), "hipMalloc(instance)") &&
-              hip_ok(hipMemcpy(d_rays, rays, (size_t)n * sizeof(nnbvh_ray), hipMemcpyHostToDevice), "copy rays") &&
-              // the caller's entries beyond count stay as they were: start from them
-              hip_ok(hipMemcpy(d.prim, c->prim, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy prim") &&
-              hip_ok(hipMemcpy(d.instance, c->instance, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy instance");
-    Workspace *w = ok ? workspace_for(s, nullptr) : nullptr;
-    int rc = w ? NNBVH_OK : NNBVH_ERR_DEVICE;
-    if (rc == NNBVH_OK) {
-        TraceJob job{.mode = mode, .rays = d_rays, .n = n, .hc = &d};
-        (mode == 0 ? job.hits : job.occluded) = d_out;
-        rc = launch(s, w, nullptr, job);
-    }
-    if (rc == NNBVH_OK &&
-        !(hip_ok(hipMemcpy(out, d_out, (size_t)n * out_elem, hipMemcpyDeviceToHost), "copy results") &&
-          hip_ok(hipMemcpy(c->count, d.count, (size_t)n * 4, hipMemcpyDeviceToHost), "copy count") &&
-          (mode != 0 || hip_ok(hipMemcpy(c->before, d.before, (size_t)n * 4, hipMemcpyDeviceToHost), "copy before")) &&
-          hip_ok(hipMemcpy(c->prim, d.prim, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy prim") &&
-          hip_ok(hipMemcpy(c->instance, d.instance, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy instance")))
-        rc = NNBVH_ERR_DEVICE;
-    release();
-    return rc;
+    return nnbvh::candidates_host(s, mode == 0, rays, n, out, c,
+                                  [&](Workspace *w, void *d_rays, void *d_out, const nnbvh_host_candidates &d) {
+                                      TraceJob job{.mode = mode, .rays = d_rays, .n = n, .hc = &d};
+                                      (mode == 0 ? job.hits : job.occluded) = d_out;
+                                      return launch(s, w, nullptr, job);
+                                  });
 }
 
 // nnbvh_trace_batches_device and its candidates form (cands nullable; cands[i] belongs to batches[i])
@@ -354,7 +323,7 @@ static int trace_batches(const char *fn, nnbvh_scene *s, const nnbvh_batch *batc
         // one launch per batch (with its candidates: modes 0 / 2), forked and joined like the others
         TraceJob job{.rays = b.d_rays, .n = b.n};
         if (cands && cands[i].capacity > 0) {
-            if (!zero_candidates(s, &cands[i], b.n, closest, s->side[k])) return NNBVH_ERR_DEVICE;
+            if (!zero_candidates(s->n_cus, &cands[i], b.n, closest, s->side[k])) return NNBVH_ERR_DEVICE;
             job.hc = &cands[i];
             job.hc_zeroed = true;
         }

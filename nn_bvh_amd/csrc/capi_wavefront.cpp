@@ -194,7 +194,7 @@ static int trace_queue(nnbvh_scene *s, Workspace *w, hipStream_t stream, bool an
                        const int32_t *d_n, void *out, const nnbvh_host_candidates *hc) {
     TraceJob job{.mode = any ? 2 : 0, .soa = queue, .n = n, .d_n = d_n, .hits = any ? nullptr : out,
                  .occluded = any ? out : nullptr, .hc = hc, .hc_zeroed = true};
-    if (hc && !zero_candidates(s, hc, n, !any, stream)) return NNBVH_ERR_DEVICE;
+    if (hc && !zero_candidates(s->n_cus, hc, n, !any, stream)) return NNBVH_ERR_DEVICE;
     if (!scene_runs_lean(s)) {
         if (!grow(&w->d_in, &w->in_bytes, (size_t)n * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
             return NNBVH_ERR_DEVICE;
@@ -222,8 +222,8 @@ static int trace_queue(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, bo
 static int trace_two_queues(nnbvh_scene *s, Workspace *w, hipStream_t stream, const ClosestSide &c, void *hits,
                             const ShadowSide &sh, uint8_t *occ, const nnbvh_host_candidates *cands) {
     if (cands && !s->has_host_prims) {  // the plain kernels over zeroed arrays; every count stays zero
-        if (!zero_candidates(s, &cands[0], c.max_rays, true, stream) ||
-            !zero_candidates(s, &cands[1], sh.max_rays, false, stream))
+        if (!zero_candidates(s->n_cus, &cands[0], c.max_rays, true, stream) ||
+            !zero_candidates(s->n_cus, &cands[1], sh.max_rays, false, stream))
             return NNBVH_ERR_DEVICE;
         cands = nullptr;
     }

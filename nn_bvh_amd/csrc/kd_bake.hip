@@ -1,8 +1,8 @@
 // kd_bake.hip — a kd-tree scene created entirely on the device (nnbvh_kd_scene_create_gpu_build): the primitive
 // bounds kd_prepare (kd_build.cpp) computes on the host, their union, the device builder (kd_build_gpu.hip) with its
-// result left where it is, and the primitive records nnbvh_kd_scene_create_with_attributes (kd_trace.hip) bakes on the
+// result left where it is, and the primitive records nnbvh_kd_scene_create_with_attributes (capi_kd.cpp) bakes on the
 // host — bit for bit what nnbvh_kd_build_create_stable + nnbvh_kd_scene_create_with_attributes upload, without the
-// tree's round trip through host memory.  Also the read-side calls of a kd scene (bounds / info / read).
+// tree's round trip through host memory.
 //
 //   k_kd_prim_bounds   one lane per primitive: kind and vertex indices are checked BEFORE anything is gathered with
 //                      them (the list is the caller's, unvalidated); Triangle::Bounds / BilinearPatch::Bounds in the
@@ -52,7 +52,7 @@ __device__ __forceinline__ float first_min(float a, float b) { return b < a ? b 
 __device__ __forceinline__ float first_max(float a, float b) { return a < b ? b : a; }
 
 // the alpha-tested kinds that read per-vertex attributes run on the device when the caller gave what they read
-// (kd_trace.hip, on_device)
+// (capi_kd.cpp, on_device)
 __device__ __forceinline__ bool attr_on_device(int kind, bool normals, bool uvs, bool primAlpha) {
     if (is_smooth_alpha_kind(kind)) return normals;
     if (is_alpha_patch_kind(kind))
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kBb) void k_kd_prim_bounds(const nnbvh_prim *__rest
                 if (box_finite(b)) box_keys(b, i, key);
                 else why = kKdNonFinite;
             }
-            // the scene flags of the host bake (kd_trace.hip)
+            // the scene flags of the host bake (capi_kd.cpp)
             const bool attr = attr_on_device(p.kind, have.normals, have.uvs, have.primAlpha);
             if ((is_smooth_alpha_kind(p.kind) || is_alpha_patch_kind(p.kind)) && !attr) flags |= kFlagHasHost;
             else if (attr || is_flat_alpha_kind(p.kind)) flags |= kFlagHasHost | kFlagHasPatch | (attr ? kFlagAnyAttr : 0u);
@@ -344,17 +344,9 @@ nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *
     KB_CHECK(hipGetLastError(), "bake kernel");
     KB_CHECK(hipStreamSynchronize(stream), "bake kernel");
 
-    auto *s = new nnbvh_kd_scene;
-    s->device = in.device;
-    s->n_cus = prop.multiProcessorCount;
-    s->depth = tree.depth;  // <= max_depth <= 64 by the caller's check: the tree is the library's own, nothing to validate
-    s->has_host_prims = (prep.flags & kFlagHasHost) ? 1 : 0;
-    s->has_patches = (prep.flags & kFlagHasPatch) ? 1 : 0;
-    s->n_nodes = tree.n_nodes;
-    s->n_indices = tree.n_indices;
-    s->n_prims = n;
-    s->fits32 = (tree.n_nodes < (1 << 29) && n < (1 << 26) - 1 && tree.n_indices < (1 << 30)) ? 1 : 0;
-    std::memcpy(s->bounds, prep.bounds, 24);
+    // (depth <= max_depth <= 64 by the caller's check: the tree is the library's own, nothing to validate)
+    nnbvh_kd_scene *s = kd_new_scene(in.device, prop.multiProcessorCount, tree.depth, (prep.flags & kFlagHasHost) != 0,
+                                     (prep.flags & kFlagHasPatch) != 0, tree.n_nodes, tree.n_indices, n, prep.bounds);
     s->d_nodes = (uint2 *)tree.d_nodes;
     s->d_indices = tree.d_indices;
     tree.release();
@@ -364,67 +356,3 @@ nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *
 }
 
 }  // namespace nnbvh
-
-using namespace nnbvh;
-
-extern "C" {
-
-int nnbvh_kd_scene_bounds(const nnbvh_kd_scene *s, float out_min_max[6]) {
-    if (!s || !out_min_max) {
-        set_error("nnbvh_kd_scene_bounds: null argument");
-        return NNBVH_ERR_ARG;
-    }
-    std::memcpy(out_min_max, s->bounds, 24);
-    return NNBVH_OK;
-}
-
-static size_t kd_array_bytes(const nnbvh_kd_scene *s, int what) {
-    switch (what) {
-    case 0: return (size_t)s->n_nodes * 8;
-    case 1: return (size_t)s->n_indices * 4;
-    case 2: return (size_t)s->n_prims * 64;
-    default: return s->d_extras ? (size_t)s->n_prims * 96 : 0;
-    }
-}
-
-int nnbvh_kd_scene_info(const nnbvh_kd_scene *s, int64_t out[8]) {
-    if (!s || !out) {
-        set_error("nnbvh_kd_scene_info: null argument");
-        return NNBVH_ERR_ARG;
-    }
-    out[0] = s->n_nodes;
-    out[1] = s->n_indices;
-    out[2] = s->n_prims;
-    out[3] = s->depth;
-    // (the index array is never empty on the device: one entry stands in for none)
-    out[4] = (int64_t)(kd_array_bytes(s, 0) + std::max<size_t>(kd_array_bytes(s, 1), 4) + kd_array_bytes(s, 2) + kd_array_bytes(s, 3));
-    out[5] = s->has_host_prims;
-    out[6] = s->has_patches;
-    out[7] = s->d_extras ? 1 : 0;
-    return NNBVH_OK;
-}
-
-int nnbvh_kd_scene_read(const nnbvh_kd_scene *s, int what, void *out, size_t bytes) {
-    if (!s || what < 0 || what > 3) {
-        set_error("nnbvh_kd_scene_read: null scene or unknown array (0 nodes, 1 primitiveIndices, 2 primitive records, 3 attribute slots)");
-        return NNBVH_ERR_ARG;
-    }
-    const size_t have = kd_array_bytes(s, what);
-    if (bytes != have || (have > 0 && !out)) {
-        set_error("nnbvh_kd_scene_read: the buffer is not the array's exact size (" + std::to_string(have) + " bytes)");
-        return NNBVH_ERR_ARG;
-    }
-    if (have == 0) return NNBVH_OK;
-    const void *src = what == 0 ? (const void *)s->d_nodes : what == 1 ? (const void *)s->d_indices
-                    : what == 2 ? (const void *)s->d_prims : (const void *)s->d_extras;
-    ScopedDevice guard(s->device);
-    hipError_t e = guard.status;
-    if (e == hipSuccess) e = hipMemcpy(out, src, have, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        set_error(std::string("nnbvh_kd_scene_read: ") + hipGetErrorString(e));
-        return NNBVH_ERR_DEVICE;
-    }
-    return NNBVH_OK;
-}
-
-}  // extern "C"

@@ -1,9 +1,11 @@
-// kd_trace.h — what the wavefront queue calls (capi_wavefront.cpp) need of a kd-tree scene: the scene object, its
-// per-stream workspaces and the batch-mode launcher of kd_trace.hip.  Host code only.
+// kd_trace.h — kd-tree scenes between the kernel (kd_trace.hip), their C ABI (capi_kd.cpp), the wavefront queue calls
+// (capi_wavefront.cpp) and the device-side creation (kd_bake.hip): the kernel's arguments and launcher, the scene
+// object, its per-stream workspaces and the batch-mode and walk launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstring>
 #include <map>
 #include <mutex>
 
@@ -12,8 +14,70 @@
 
 namespace nnbvh {
 
+constexpr int kKdBlock = 256;
+constexpr int kKdW = 8;              // LDS window of the to-visit stack, entries per lane (patch instances)
+constexpr int kKdWLean = 4;          // ... of the lean instances: 18 KiB of LDS per block, 8 blocks per CU (measured
+                                     // against 8 entries / 5 blocks: crown +8 %, bathroom +11 %)
+constexpr int kKdQueues = 8;         // one ray queue per XCD
+constexpr int kKdQueueStride = 32;   // words: every queue head on its own 128-B line
 constexpr int kKdMaxBatches = 4;   // batches one batch-mode launch may cover
 constexpr int kKdIndexBits = 28;   // a lane's ray tag = batch << 28 | index: batches below 2^28 rays
+
+struct KdParams {
+    const uint2 *nodes;           // KdTreeNode[], {split | index, flags}
+    const int32_t *primIndices;   // KdTreeAggregate::primitiveIndices
+    const float4 *prims;          // 4 slots of 16 B per primitive, in the caller's primitive order:
+                                  // {p0, id} {p1, flags} {p2, 0} {p3 (patch), 0}
+    float bmin[3], bmax[3];       // KdTreeAggregate::bounds
+    const nnbvh_ray *rays;
+    nnbvh_hit *hits;              // MODE 0
+    uint8_t *occluded;            // MODE 1
+    int32_t *visitedOut, *testsOut;  // MODE 1, nullable
+    long n;
+    unsigned *queue;
+    int nQueues;
+    int primWeight, refillWeight, nodeRepeat;
+    int hasHostPrims;
+    float4 *spill;                // [kMaxStack][grid threads] overflow of the LDS window
+    const float4 *extras;         // ATTR instances: 6 slots per primitive {n0} {n1} {n2} {n3} {uv00, uv10} {uv01, uv11}
+                                  // (per-vertex normals / uvs of the alpha-tested kinds that read them), else null
+    // batch mode (MODE 2 / 3: one launch over several batches, closest-hit and any-hit mixed).  Appended, so that the
+    // fields above keep their kernel-argument offsets.  Batch b's queue heads sit at
+    // queue[(b * nQueues + q) * kKdQueueStride]; bit b of anyMask = batch b is any-hit (bOut = uint8 occluded[]),
+    // else closest (bOut = nnbvh_hit[])
+    int nBatches;
+    unsigned anyMask;
+    const nnbvh_ray *bRays[kKdMaxBatches];   // MODE 2
+    nnbvh_ray_soa bSoa[kKdMaxBatches];       // MODE 3: SOA<Ray> slices (tmax == nullptr: Infinity, time == nullptr: 0)
+    void *bOut[kKdMaxBatches];
+    int32_t *bVisited[kKdMaxBatches], *bTests[kKdMaxBatches];  // any-hit batches, nullable
+    long bN[kKdMaxBatches];
+    const int32_t *bNDev[kKdMaxBatches];     // nullable: device-resident size of batch b, clamped to [0, bN[b]]
+    // candidate mode (the HOSTC instances of MODE 2, scenes with host-only primitives), appended
+    // again: per batch the arrays of its nnbvh_host_candidates.  bHcCap[b] == 0: batch b is a plain batch, a
+    // host-only primitive voids its ray as in the plain instances
+    int bHcCap[kKdMaxBatches];
+    int32_t *bHcCount[kKdMaxBatches];
+    int32_t *bHcBefore[kKdMaxBatches];       // closest batches only
+    int32_t *bHcPrim[kKdMaxBatches];
+    int32_t *bHcInst[kKdMaxBatches];
+    // walk mode (the WALK instances), appended again: the shading mesh the hit's pi / n come from and
+    // the per-item arrays of the walk (walk_math.h).  One batch; a lane's ray tag is its work item
+    MeshView wMesh;
+    WalkParams walk;
+};
+
+// One instance of kd_trace_kernel (kd_trace.hip explains the template parameters of the same names; the window W
+// follows from patch).  The library holds modes 0 / 1 x {lean, patch, patch + attr} x o32, mode 2 the same x hostc,
+// mode 3 lean x o32 and the walk modes 4 / 5 x {lean, patch} x o32.
+struct KdInstance {
+    int mode, patch, o32, attr, hostc;
+};
+// occupancy != nullptr: do not launch, report resident blocks per CU of that instance.  hipErrorInvalidValue for an
+// instance the library does not hold
+hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, hipStream_t stream, int *occupancy);
+// the queue heads cleared by a kernel node (1 block), as launch_zero_queue does for the BVH kernels
+hipError_t launch_kd_zero_queue(unsigned *queue, int words, hipStream_t stream);
 
 struct KdWorkspace {
     unsigned *queue = nullptr;  // kKdMaxBatches x kKdQueues heads
@@ -52,7 +116,7 @@ struct nnbvh_kd_scene {
     int depth = 0;
     int has_host_prims = 0;
     int has_patches = 0;
-    int fits32 = 0;  // nodes (8 B), primitive records (64 B) and indices (4 B) each below 4 GiB
+    int fits32 = 0;  // kd_fits32
     int n_nodes = 0, n_indices = 0, n_prims = 0;  // what nnbvh_kd_scene_info / _read report (d_indices holds max(n_indices, 1))
     float bounds[6];
     uint2 *d_nodes = nullptr;
@@ -72,6 +136,29 @@ struct nnbvh_kd_scene {
 };
 
 namespace nnbvh {
+
+// nodes (8 B), primitive records (64 B) and indices (4 B) each below 4 GiB: the O32 instances reach them
+inline int kd_fits32(int64_t n_nodes, int64_t n_prims, int64_t n_indices) {
+    return (n_nodes < (1 << 29) && n_prims < (1 << 26) - 1 && n_indices < (1 << 30)) ? 1 : 0;
+}
+
+// A new scene object with everything filled in but its device arrays, which either creation route (the caller's tree:
+// capi_kd.cpp; the device's own: kd_bake.hip) attaches.
+inline nnbvh_kd_scene *kd_new_scene(int device, int n_cus, int depth, bool has_host_prims, bool has_patches, int n_nodes,
+                                    int n_indices, int n_prims, const float bounds[6]) {
+    auto *s = new nnbvh_kd_scene;
+    s->device = device;
+    s->n_cus = n_cus;
+    s->depth = depth;
+    s->has_host_prims = has_host_prims ? 1 : 0;
+    s->has_patches = has_patches ? 1 : 0;
+    s->n_nodes = n_nodes;
+    s->n_indices = n_indices;
+    s->n_prims = n_prims;
+    s->fits32 = kd_fits32(n_nodes, n_prims, n_indices);
+    std::memcpy(s->bounds, bounds, 24);
+    return s;
+}
 
 // One workspace per stream, as for the BVH scenes.  The caller holds s->mu.
 KdWorkspace *kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream);

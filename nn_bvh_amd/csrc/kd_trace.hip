@@ -1,4 +1,5 @@
-// kd_trace.hip — KdTreeAggregate::Intersect / IntersectP on gfx950, plus their C ABI.
+// kd_trace.hip — KdTreeAggregate::Intersect / IntersectP on gfx950: the kernel and its launcher (kd_trace.h; the C ABI
+// of kd-tree scenes is capi_kd.cpp).
 //
 // What is computed (reference: /root/reference/src/pbrt/cpu/aggregates.cpp):
 //   closest hit   KdTreeAggregate::Intersect    :973-1067
@@ -16,77 +17,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <string>
-#include <vector>
-
 #include "../../include/nnbvh.h"
 #include "nnbvh_internal.h"
 #include "trace_math.h"
 #include "spawn_math.h"
-#include "bvh_trace.h"
 #include "kd_trace.h"
-#include "wavefront.h"
 #include "walk_math.h"
 
 namespace nnbvh {
 
-constexpr int kKdBlock = 256;
-constexpr int kKdW = 8;              // LDS window of the to-visit stack, entries per lane (patch instances)
-constexpr int kKdWLean = 4;          // ... of the lean instances: 18 KiB of LDS per block, 8 blocks per CU (measured
-                                     // against 8 entries / 5 blocks: crown +8 %, bathroom +11 %)
-constexpr int kKdQueues = 8;         // one ray queue per XCD
-constexpr int kKdQueueStride = 32;   // words: every queue head on its own 128-B line
 constexpr int kKdDone = -1;          // lane carries no ray
 constexpr int kKdLeaf = -2;          // lane is walking the primitives of a leaf
-
-struct KdParams {
-    const uint2 *nodes;           // KdTreeNode[], {split | index, flags}
-    const int32_t *primIndices;   // KdTreeAggregate::primitiveIndices
-    const float4 *prims;          // 4 slots of 16 B per primitive, in the caller's primitive order:
-                                  // {p0, id} {p1, flags} {p2, 0} {p3 (patch), 0}
-    float bmin[3], bmax[3];       // KdTreeAggregate::bounds
-    const nnbvh_ray *rays;
-    nnbvh_hit *hits;              // MODE 0
-    uint8_t *occluded;            // MODE 1
-    int32_t *visitedOut, *testsOut;  // MODE 1, nullable
-    long n;
-    unsigned *queue;
-    int nQueues;
-    int primWeight, refillWeight, nodeRepeat;
-    int hasHostPrims;
-    float4 *spill;                // [kMaxStack][grid threads] overflow of the LDS window
-    const float4 *extras;         // ATTR instances: 6 slots per primitive {n0} {n1} {n2} {n3} {uv00, uv10} {uv01, uv11}
-                                  // (per-vertex normals / uvs of the alpha-tested kinds that read them), else null
-    // batch mode (MODE 2 / 3: one launch over several batches, closest-hit and any-hit mixed).  Appended, so that the
-    // fields above keep their kernel-argument offsets.  Batch b's queue heads sit at
-    // queue[(b * nQueues + q) * kKdQueueStride]; bit b of anyMask = batch b is any-hit (bOut = uint8 occluded[]),
-    // else closest (bOut = nnbvh_hit[])
-    int nBatches;
-    unsigned anyMask;
-    const nnbvh_ray *bRays[kKdMaxBatches];   // MODE 2
-    nnbvh_ray_soa bSoa[kKdMaxBatches];       // MODE 3: SOA<Ray> slices (tmax == nullptr: Infinity, time == nullptr: 0)
-    void *bOut[kKdMaxBatches];
-    int32_t *bVisited[kKdMaxBatches], *bTests[kKdMaxBatches];  // any-hit batches, nullable
-    long bN[kKdMaxBatches];
-    const int32_t *bNDev[kKdMaxBatches];     // nullable: device-resident size of batch b, clamped to [0, bN[b]]
-    // candidate mode (the HOSTC instances of MODE 2, scenes with host-only primitives), appended
-    // again: per batch the arrays of its nnbvh_host_candidates.  bHcCap[b] == 0: batch b is a plain batch, a
-    // host-only primitive voids its ray as in the plain instances
-    int bHcCap[kKdMaxBatches];
-    int32_t *bHcCount[kKdMaxBatches];
-    int32_t *bHcBefore[kKdMaxBatches];       // closest batches only
-    int32_t *bHcPrim[kKdMaxBatches];
-    int32_t *bHcInst[kKdMaxBatches];
-    // walk mode (the WALK instances), appended again: the shading mesh the hit's pi / n come from and
-    // the per-item arrays of the walk (walk_math.h).  One batch; a lane's ray tag is its work item
-    MeshView wMesh;
-    WalkParams walk;
-};
 
 // A lane takes up the ray {R0, R1} = {o, tMax} {d, time}: the reciprocals (aggregates.cpp:980), the shear, the
 // `ray.d[axis] <= 0` bits of aggregates.cpp:1002-1003, cold hit slots, zeroed counts and the root interval (:975-977:
@@ -655,685 +596,47 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
 __global__ void kd_zero_queue_kernel(unsigned *queue, int words) {
     for (int i = threadIdx.x; i < words; i += blockDim.x) queue[i] = 0u;
 }
-
-static bool kd_hip_ok(hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return false;
+hipError_t launch_kd_zero_queue(unsigned *queue, int words, hipStream_t stream) {
+    hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, queue, words);
+    return hipGetLastError();
 }
 
-struct KdDeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit KdDeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = kd_hip_ok(hipSetDevice(dev), "hipSetDevice");
-    }
-    ~KdDeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
+// ---- the instances ---------------------------------------------------------------------------------------------
+struct KdEntry {
+    KdInstance is;
+    void (*kernel)(KdParams);
 };
+template <int MODE, int PATCH, int O32, int ATTR = 0, int HOSTC = 0>
+constexpr KdEntry kd_entry() {  // the window follows from PATCH
+    return {{MODE, PATCH, O32, ATTR, HOSTC}, kd_trace_kernel<MODE, PATCH, PATCH ? kKdW : kKdWLean, O32, ATTR, HOSTC>};
+}
+// Every instance the library holds: what is not listed here is not compiled.  (The order is the order of the kernels in
+// the compiler's output.)
+static const KdEntry kKdInstances[] = {
+    // closest / any hit: lean and patch scenes, with and without 32-bit offsets, then the attribute-reading forms
+    kd_entry<0, 0, 0>(), kd_entry<1, 0, 0>(), kd_entry<0, 1, 0>(), kd_entry<1, 1, 0>(),
+    kd_entry<0, 0, 1>(), kd_entry<1, 0, 1>(), kd_entry<0, 1, 1>(), kd_entry<1, 1, 1>(),
+    kd_entry<0, 1, 0, 1>(), kd_entry<1, 1, 0, 1>(), kd_entry<0, 1, 1, 1>(), kd_entry<1, 1, 1, 1>(),
+    // batches, record form: lean / patches / attributes; SOA form (mode 3): lean only
+    kd_entry<2, 0, 0>(), kd_entry<2, 1, 0>(), kd_entry<2, 1, 0, 1>(), kd_entry<3, 0, 0>(),
+    kd_entry<2, 0, 1>(), kd_entry<2, 1, 1>(), kd_entry<2, 1, 1, 1>(), kd_entry<3, 0, 1>(),
+    // ... and the candidate-mode twins of the record form
+    kd_entry<2, 0, 0, 0, 1>(), kd_entry<2, 1, 0, 0, 1>(), kd_entry<2, 1, 0, 1, 1>(),
+    kd_entry<2, 0, 1, 0, 1>(), kd_entry<2, 1, 1, 0, 1>(), kd_entry<2, 1, 1, 1, 1>(),
+    // the walk instances: IntersectShadowTr's, then IntersectOneRandom's
+    kd_entry<4, 0, 0>(), kd_entry<4, 1, 0>(), kd_entry<4, 0, 1>(), kd_entry<4, 1, 1>(),
+    kd_entry<5, 0, 0>(), kd_entry<5, 1, 0>(), kd_entry<5, 0, 1>(), kd_entry<5, 1, 1>()};
 
-static bool kd_grow(void **ptr, size_t *have, size_t need, const char *what) {
-    if (*have >= need) return true;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have = 0;
-    if (!kd_hip_ok(hipMalloc(ptr, need), what)) return false;
-    *have = need;
-    return true;
+hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, hipStream_t stream, int *occupancy) {
+    for (const KdEntry &e : kKdInstances) {
+        if (e.is.mode != is.mode || e.is.patch != is.patch || e.is.o32 != is.o32 || e.is.attr != is.attr ||
+            e.is.hostc != is.hostc)
+            continue;
+        if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, e.kernel, kKdBlock, 0);
+        hipLaunchKernelGGL(e.kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
+        return hipGetLastError();
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace nnbvh
-
-using namespace nnbvh;
-
-KdWorkspace *nnbvh::kd_workspace_for(nnbvh_kd_scene *s, hipStream_t stream) {
-    auto it = s->workspaces.find(stream);
-    if (it != s->workspaces.end()) return &it->second;
-    KdWorkspace w;
-    // an entry is spilled only when W newer ones sit above it: levels 0 .. depth - W of a lane's list, at the
-    // smallest window any instance runs with
-    const size_t spill_levels = (size_t)std::max(s->depth + 1 - std::min(kKdW, kKdWLean), 1);
-    const size_t spill_bytes = spill_levels * (size_t)s->n_cus * 8 * kKdBlock * sizeof(float4);
-    if (!kd_hip_ok(hipMalloc((void **)&w.queue, kKdMaxBatches * kKdQueues * kKdQueueStride * sizeof(unsigned)), "hipMalloc(queue)"))
-        return nullptr;
-    if (!kd_hip_ok(hipMalloc((void **)&w.spill, spill_bytes), "hipMalloc(spill)")) {
-        (void)hipFree(w.queue);
-        return nullptr;
-    }
-    return &(s->workspaces[stream] = w);
-}
-
-static void kd_fill_scene(const nnbvh_kd_scene *s, const KdWorkspace *w, KdParams &p) {
-    p.nodes = s->d_nodes;
-    p.primIndices = s->d_indices;
-    p.prims = s->d_prims;
-    std::memcpy(p.bmin, s->bounds, 12);
-    std::memcpy(p.bmax, s->bounds + 3, 12);
-    p.queue = w->queue;
-    p.nQueues = kKdQueues;
-    p.primWeight = 12;  // swept on bathroom: 12 / 8 / 4 is the best of 4 x 2 x 3 (+1.5 % over 24 / 8 / 4)
-    p.refillWeight = 8;
-    p.nodeRepeat = 4;
-    p.hasHostPrims = s->has_host_prims;
-    p.spill = w->spill;
-    p.extras = s->d_extras;
-}
-
-// lean scenes (no patches, no attributes): their batch-mode instance has a form that reads SOA slices itself
-static bool kd_scene_reads_soa(const nnbvh_kd_scene *s) { return s->read_soa && !s->has_patches && !s->d_extras; }
-
-static int kd_launch(nnbvh_kd_scene *s, int mode, const void *d_rays, int64_t n, void *d_hits, void *d_occ,
-                     void *d_vis, void *d_tests, hipStream_t stream, KdWorkspace *w) {
-    KdParams p{};
-    kd_fill_scene(s, w, p);
-    p.rays = (const nnbvh_ray *)d_rays;
-    p.hits = (nnbvh_hit *)d_hits;
-    p.occluded = (uint8_t *)d_occ;
-    p.visitedOut = (int32_t *)d_vis;
-    p.testsOut = (int32_t *)d_tests;
-    p.n = (long)n;
-    // the four instances: closest / any hit x scenes with / without bilinear patches
-    void (*const kernels[8])(KdParams) = {
-        kd_trace_kernel<0, 0, kKdWLean, 0>, kd_trace_kernel<1, 0, kKdWLean, 0>, kd_trace_kernel<0, 1, kKdW, 0>,
-        kd_trace_kernel<1, 1, kKdW, 0>,     kd_trace_kernel<0, 0, kKdWLean, 1>, kd_trace_kernel<1, 0, kKdWLean, 1>,
-        kd_trace_kernel<0, 1, kKdW, 1>,     kd_trace_kernel<1, 1, kKdW, 1>};
-    // ... and the attribute-reading forms of the PATCH instances
-    void (*const attr_kernels[4])(KdParams) = {kd_trace_kernel<0, 1, kKdW, 0, 1>, kd_trace_kernel<1, 1, kKdW, 0, 1>,
-                                               kd_trace_kernel<0, 1, kKdW, 1, 1>, kd_trace_kernel<1, 1, kKdW, 1, 1>};
-    void (*const kernel)(KdParams) = s->d_extras ? attr_kernels[mode + 2 * s->fits32]
-                                                 : kernels[mode + 2 * s->has_patches + 4 * s->fits32];
-    if (s->blocks_per_cu[mode] == 0) {
-        int occ = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kKdBlock, 0);
-        s->blocks_per_cu[mode] = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
-    }
-    int blocks = s->n_cus * s->blocks_per_cu[mode];
-    const int64_t need = (n + kKdBlock - 1) / kKdBlock;
-    if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
-    hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, w->queue, kKdQueues * kKdQueueStride);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
-    return kd_hip_ok(hipGetLastError(), "kd trace kernel launch") ? NNBVH_OK : NNBVH_ERR_DEVICE;
-}
-
-int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdBatch *batches, int n_batches) {
-    KdParams p{};
-    kd_fill_scene(s, w, p);
-    bool all_soa = true, candidates = false;
-    int64_t total = 0, soa_rays = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        all_soa = all_soa && !batches[b].rays;
-        if (!batches[b].rays) soa_rays += batches[b].n;
-        total += batches[b].n;
-        candidates = candidates || (batches[b].hc && batches[b].hc->capacity > 0);
-    }
-    // a candidate call always goes through the record form ("read_soa" has no effect on it)
-    const bool read_soa = !candidates && all_soa && kd_scene_reads_soa(s);
-    const bool hostc = candidates && s->has_host_prims;  // else: the plain instances over zeroed counts
-    if (!read_soa && soa_rays > 0 &&
-        !kd_grow(&w->d_in, &w->in_bytes, (size_t)soa_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
-        return NNBVH_ERR_DEVICE;
-    char *gathered = (char *)w->d_in;
-    p.nBatches = n_batches;
-    p.anyMask = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        const KdBatch &k = batches[b];
-        p.anyMask |= k.any ? 1u << b : 0u;
-        p.bOut[b] = k.out;
-        p.bVisited[b] = k.any ? (int32_t *)k.visited : nullptr;
-        p.bTests[b] = k.any ? (int32_t *)k.tests : nullptr;
-        p.bN[b] = (long)k.n;
-        p.bNDev[b] = k.d_n;
-        if (k.hc && k.hc->capacity > 0 && k.n > 0) {
-            const int zero_blocks = s->n_cus * 8;
-            if (!kd_hip_ok(launch_zero_words(k.hc->count, (long)k.n, zero_blocks, stream), "candidate count reset launch") ||
-                (!k.any && !kd_hip_ok(launch_zero_words(k.hc->before, (long)k.n, zero_blocks, stream),
-                                      "candidate before reset launch")))
-                return NNBVH_ERR_DEVICE;
-            if (hostc) {
-                p.bHcCap[b] = k.hc->capacity;
-                p.bHcCount[b] = k.hc->count;
-                p.bHcBefore[b] = k.any ? nullptr : k.hc->before;
-                p.bHcPrim[b] = k.hc->prim;
-                p.bHcInst[b] = k.hc->instance;
-            }
-        }
-        if (read_soa) {
-            if (k.soa) p.bSoa[b] = *k.soa;  // (an empty batch may come without slices)
-        } else if (!k.rays && k.n > 0) {
-            if (!kd_hip_ok(launch_wf_gather(*k.soa, WavefrontCount{(int)k.n, k.d_n}, gathered, s->n_cus * 8, stream),
-                           "gather kernel launch"))
-                return NNBVH_ERR_DEVICE;
-            p.bRays[b] = (const nnbvh_ray *)gathered;
-            gathered += (size_t)k.n * sizeof(nnbvh_ray);
-        } else {
-            p.bRays[b] = (const nnbvh_ray *)k.rays;
-        }
-    }
-    // record form: lean / patches / attributes, each with and without 32-bit offsets; SOA form: lean only
-    void (*const kernels[8])(KdParams) = {
-        kd_trace_kernel<2, 0, kKdWLean, 0>, kd_trace_kernel<2, 1, kKdW, 0>, kd_trace_kernel<2, 1, kKdW, 0, 1>,
-        kd_trace_kernel<3, 0, kKdWLean, 0>, kd_trace_kernel<2, 0, kKdWLean, 1>, kd_trace_kernel<2, 1, kKdW, 1>,
-        kd_trace_kernel<2, 1, kKdW, 1, 1>,  kd_trace_kernel<3, 0, kKdWLean, 1>};
-    // ... and the candidate-mode twins of the record form
-    void (*const hostc_kernels[6])(KdParams) = {
-        kd_trace_kernel<2, 0, kKdWLean, 0, 0, 1>, kd_trace_kernel<2, 1, kKdW, 0, 0, 1>, kd_trace_kernel<2, 1, kKdW, 0, 1, 1>,
-        kd_trace_kernel<2, 0, kKdWLean, 1, 0, 1>, kd_trace_kernel<2, 1, kKdW, 1, 0, 1>, kd_trace_kernel<2, 1, kKdW, 1, 1, 1>};
-    const int form = read_soa ? 3 : (s->d_extras ? 2 : (s->has_patches ? 1 : 0));
-    void (*const kernel)(KdParams) = hostc ? hostc_kernels[form + 3 * s->fits32] : kernels[form + 4 * s->fits32];
-    const int slot = hostc ? 4 : (read_soa ? 3 : 2);
-    if (s->blocks_per_cu[slot] == 0) {
-        int occ = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kKdBlock, 0);
-        s->blocks_per_cu[slot] = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
-    }
-    int blocks = s->n_cus * s->blocks_per_cu[slot];
-    const int64_t need = (total + kKdBlock - 1) / kKdBlock;
-    if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
-    hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, w->queue,
-                       n_batches * kKdQueues * kKdQueueStride);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
-    return kd_hip_ok(hipGetLastError(), "kd batch trace kernel launch") ? NNBVH_OK : NNBVH_ERR_DEVICE;
-}
-
-extern "C" {
-
-nnbvh_kd_scene *nnbvh_kd_scene_create(const nnbvh_kd_node *nodes, int n_nodes, const int32_t *prim_indices,
-                                      int n_indices, const nnbvh_prim *prims, int n_prims, const float *verts,
-                                      int n_verts, const float bounds_min_max[6], int device) {
-    return nnbvh_kd_scene_create_with_attributes(nodes, n_nodes, prim_indices, n_indices, prims, n_prims, verts, n_verts,
-                                                 bounds_min_max, nullptr, nullptr, nullptr, device);
-}
-
-nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes, int n_nodes,
-                                                      const int32_t *prim_indices, int n_indices,
-                                                      const nnbvh_prim *prims, int n_prims, const float *verts,
-                                                      int n_verts, const float bounds_min_max[6], const float *normals,
-                                                      const float *uvs, const float *prim_alpha, int device) {
-    if (!nodes || n_nodes <= 0 || n_indices < 0 || (n_indices > 0 && !prim_indices) || !prims || n_prims <= 0 ||
-        !verts || n_verts <= 0 || !bounds_min_max) {
-        set_error("kd_scene_create: null or empty argument");
-        return nullptr;
-    }
-    for (int k = 0; k < n_prims; ++k)
-        if (is_alphatex_kind(prims[k].kind)) {
-            set_error(std::string("kd_scene_create: ") + kAlphaTexElsewhere);
-            return nullptr;
-        }
-    // ---- validate everything the kernel indexes with ---------------------------------------------
-    for (int i = 0; i < n_indices; ++i)
-        if (prim_indices[i] < 0 || prim_indices[i] >= n_prims) {
-            set_error("kd_scene_create: primitive index out of range in primitiveIndices");
-            return nullptr;
-        }
-    struct Frame {
-        int node, end, depth;
-    };
-    std::vector<Frame> st;
-    st.push_back({0, n_nodes, 0});
-    int visited = 0, max_depth = 0;
-    while (!st.empty()) {
-        const Frame f = st.back();
-        st.pop_back();
-        ++visited;
-        if (f.node < 0 || f.node >= f.end) {
-            set_error("kd_scene_create: node index outside its subtree range");
-            return nullptr;
-        }
-        max_depth = std::max(max_depth, f.depth);
-        const nnbvh_kd_node &nd = nodes[f.node];
-        if ((nd.flags & 3u) == 3u) {
-            if (f.node + 1 != f.end) {
-                set_error("kd_scene_create: leaf does not close its subtree range (not the reference's layout)");
-                return nullptr;
-            }
-            const uint32_t np = nd.flags >> 2;
-            const int32_t v = (int32_t)nd.split_or_index;
-            if (np == 1 && (v < 0 || v >= n_prims)) {
-                set_error("kd_scene_create: leaf primitive index out of range");
-                return nullptr;
-            }
-            if (np > 1 && (v < 0 || (int64_t)v + np > n_indices)) {
-                set_error("kd_scene_create: leaf primitive range out of bounds");
-                return nullptr;
-            }
-        } else {
-            const int64_t above = nd.flags >> 2;
-            if (above <= f.node + 1 || above >= f.end) {
-                set_error("kd_scene_create: above-child link outside its subtree range");
-                return nullptr;
-            }
-            float split;
-            std::memcpy(&split, &nd.split_or_index, 4);
-            if (std::isnan(split)) {
-                set_error("kd_scene_create: NaN split position");
-                return nullptr;
-            }
-            st.push_back({(int)above, f.end, f.depth + 1});
-            st.push_back({f.node + 1, (int)above, f.depth + 1});
-        }
-    }
-    if (visited != n_nodes) {
-        set_error("kd_scene_create: unreachable nodes in the array");
-        return nullptr;
-    }
-    if (max_depth > kMaxStack) {
-        set_error("kd_scene_create: tree deeper than the traversal stack (64 entries, aggregates.cpp:982)");
-        return nullptr;
-    }
-    // ---- primitive records: 4 slots per primitive in the caller's order --------------------------
-    std::vector<float> rec((size_t)n_prims * 16, 0.0f);
-    bool has_host = false, has_patch = false;
-    // the alpha-tested kinds that read per-vertex attributes: on the device when the caller gave what they read
-    // (6 more slots per primitive in a second array), else the host's as before
-    auto on_device = [&](int kind) {
-        if (is_smooth_alpha_kind(kind)) return normals != nullptr;
-        if (is_alpha_patch_kind(kind))
-            return prim_alpha && (!is_smooth_alpha_patch_kind(kind) || normals) && (!is_uv_alpha_patch_kind(kind) || uvs);
-        return false;
-    };
-    bool any_attr = false;
-    for (int k = 0; k < n_prims && !any_attr; ++k) any_attr = on_device(prims[k].kind);
-    std::vector<float> extras(any_attr ? (size_t)n_prims * 24 : 0, 0.0f);
-    for (int k = 0; k < n_prims; ++k) {
-        const nnbvh_prim &pr = prims[k];
-        float *s = &rec[(size_t)k * 16];
-        uint32_t flags = 0;
-        std::memcpy(&s[3], &pr.id, 4);
-        const bool attr = on_device(pr.kind);
-        if (pr.kind == NNBVH_PRIM_HOST || ((is_smooth_alpha_kind(pr.kind) || is_alpha_patch_kind(pr.kind)) && !attr)) {
-            // (alpha-tested triangles of smooth meshes and alpha-tested patches without the arrays they read: the host's)
-            flags |= kPrimHost;
-            has_host = true;
-        } else if (is_triangle_kind(pr.kind) || pr.kind == NNBVH_PRIM_BILINEAR_PATCH || is_alpha_patch_kind(pr.kind)) {
-            const int nv = is_triangle_kind(pr.kind) ? 3 : 4;
-            if (attr) {
-                float *ex = &extras[(size_t)k * 24];
-                const bool smooth = is_smooth_alpha_kind(pr.kind) || is_smooth_alpha_patch_kind(pr.kind);
-                for (int j = 0; j < nv && smooth; ++j)
-                    if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[4 * j], normals + 3 * (size_t)pr.v[j], 12);
-                for (int j = 0; j < 4 && is_uv_alpha_patch_kind(pr.kind); ++j)
-                    if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[16 + 2 * j], uvs + 2 * (size_t)pr.v[j], 8);
-                flags |= kPrimAlpha | (smooth ? kPrimSmooth : 0u) | (is_uv_alpha_patch_kind(pr.kind) ? kPrimUV : 0u);
-                if (pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED || is_flipped_alpha_patch_kind(pr.kind)) flags |= kPrimFlipN;
-                has_host = true;   // a re-trace chain that does not end voids the ray
-                has_patch = true;  // the alpha test hashes the ray direction
-            }
-            if (pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE || pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED) {
-                // the alpha value rides in v[3] (bit pattern) and goes to slot 2's w, as in the BVH scenes;
-                // a re-trace that hits voids the ray like a host primitive, and the test needs the ray
-                // direction: such scenes run the PATCH instances
-                flags |= kPrimAlpha | (pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED ? kPrimFlipN : 0u);
-                has_host = true;
-                has_patch = true;
-            }
-            for (int j = 0; j < nv; ++j) {
-                if (pr.v[j] < 0 || pr.v[j] >= n_verts) {
-                    set_error("kd_scene_create: vertex index out of range");
-                    return nullptr;
-                }
-                std::memcpy(&s[4 * j], verts + 3 * (size_t)pr.v[j], 12);
-            }
-            std::memcpy(&s[3], &pr.id, 4);
-            if (flags & kPrimAlpha) {
-                if (is_alpha_patch_kind(pr.kind)) s[11] = prim_alpha[k];  // a patch needs all four v[]
-                else std::memcpy(&s[11], &pr.v[3], 4);
-            }
-            if (nv == 4) {
-                flags |= kPrimPatch;
-                has_patch = true;
-            }
-            else if (kd_triangle_is_degenerate(&s[0], &s[4], &s[8])) flags |= kPrimDegenerate;
-        } else {
-            set_error("kd_scene_create: unsupported primitive kind (triangles, alpha-tested triangles, patches, host primitives)");
-            return nullptr;
-        }
-        std::memcpy(&s[7], &flags, 4);
-    }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
-        set_error("kd_scene_create: no usable HIP device");
-        return nullptr;
-    }
-    KdDeviceGuard guard(device);
-    if (!guard.ok) return nullptr;
-    hipDeviceProp_t prop;
-    if (!kd_hip_ok(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties")) return nullptr;
-    auto *s = new nnbvh_kd_scene;
-    s->device = device;
-    s->n_cus = prop.multiProcessorCount;
-    s->depth = max_depth;
-    s->has_host_prims = has_host ? 1 : 0;
-    s->has_patches = has_patch ? 1 : 0;
-    s->n_nodes = n_nodes;
-    s->n_indices = n_indices;
-    s->n_prims = n_prims;
-    s->fits32 = (n_nodes < (1 << 29) && n_prims < (1 << 26) - 1 && n_indices < (1 << 30)) ? 1 : 0;
-    std::memcpy(s->bounds, bounds_min_max, 24);
-    const size_t ni = (size_t)std::max(n_indices, 1);
-    bool ok = kd_hip_ok(hipMalloc((void **)&s->d_nodes, (size_t)n_nodes * 8), "hipMalloc(kd nodes)") &&
-              kd_hip_ok(hipMalloc((void **)&s->d_indices, ni * 4), "hipMalloc(kd indices)") &&
-              kd_hip_ok(hipMalloc((void **)&s->d_prims, rec.size() * 4), "hipMalloc(kd prims)") &&
-              kd_hip_ok(hipMemcpy(s->d_nodes, nodes, (size_t)n_nodes * 8, hipMemcpyHostToDevice), "upload kd nodes") &&
-              kd_hip_ok(hipMemcpy(s->d_prims, rec.data(), rec.size() * 4, hipMemcpyHostToDevice), "upload kd prims");
-    if (ok && n_indices > 0)
-        ok = kd_hip_ok(hipMemcpy(s->d_indices, prim_indices, (size_t)n_indices * 4, hipMemcpyHostToDevice),
-                       "upload kd indices");
-    if (ok && any_attr)
-        ok = kd_hip_ok(hipMalloc((void **)&s->d_extras, extras.size() * 4), "hipMalloc(kd attributes)") &&
-             kd_hip_ok(hipMemcpy(s->d_extras, extras.data(), extras.size() * 4, hipMemcpyHostToDevice), "upload kd attributes");
-    if (!ok) {
-        nnbvh_kd_scene_destroy(s);
-        return nullptr;
-    }
-    return s;
-}
-
-void nnbvh_kd_scene_destroy(nnbvh_kd_scene *s) {
-    if (!s) return;
-    KdDeviceGuard guard(s->device);
-    for (auto &kv : s->workspaces) {
-        KdWorkspace &w = kv.second;
-        for (void *ptr : {(void *)w.queue, (void *)w.spill, w.d_in, w.d_out, w.d_aux0, w.d_aux1, w.d_hits})
-            if (ptr) (void)hipFree(ptr);
-        for (void *ptr : w.walk)
-            if (ptr) (void)hipFree(ptr);
-    }
-    if (s->d_nodes) (void)hipFree(s->d_nodes);
-    if (s->d_indices) (void)hipFree(s->d_indices);
-    if (s->d_prims) (void)hipFree(s->d_prims);
-    if (s->d_extras) (void)hipFree(s->d_extras);
-    delete s;
-}
-
-int nnbvh_kd_intersect_closest_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_hits,
-                                      void *stream) {
-    if (!s || n < 0 || n >= 0x7fffffffLL || (n > 0 && (!d_rays || !d_hits))) {
-        set_error("kd_intersect_closest_device: bad argument");
-        return NNBVH_ERR_ARG;
-    }
-    if (n == 0) return NNBVH_OK;
-    KdDeviceGuard guard(s->device);
-    if (!guard.ok) return NNBVH_ERR_DEVICE;
-    std::lock_guard<std::mutex> lock(s->mu);
-    KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
-    if (!w) return NNBVH_ERR_DEVICE;
-    return kd_launch(s, 0, d_rays, n, d_hits, nullptr, nullptr, nullptr, (hipStream_t)stream, w);
-}
-
-int nnbvh_kd_intersect_any_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_occluded,
-                                  void *d_nodes_visited, void *d_prim_tests, void *stream) {
-    if (!s || n < 0 || n >= 0x7fffffffLL || (n > 0 && (!d_rays || !d_occluded))) {
-        set_error("kd_intersect_any_device: bad argument");
-        return NNBVH_ERR_ARG;
-    }
-    if (n == 0) return NNBVH_OK;
-    KdDeviceGuard guard(s->device);
-    if (!guard.ok) return NNBVH_ERR_DEVICE;
-    std::lock_guard<std::mutex> lock(s->mu);
-    KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
-    if (!w) return NNBVH_ERR_DEVICE;
-    return kd_launch(s, 1, d_rays, n, nullptr, d_occluded, d_nodes_visited, d_prim_tests, (hipStream_t)stream, w);
-}
-
-int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value) {
-    if (!s || !key) {
-        set_error("kd_scene_set_option: null argument");
-        return NNBVH_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lock(s->mu);
-    const std::string k(key);
-    if (k == "read_soa") s->read_soa = value != 0;
-    else if (k == "pair_one_launch") s->pair_one_launch = value != 0;
-    else {
-        set_error("kd_scene_set_option: unknown key " + k);
-        return NNBVH_ERR_ARG;
-    }
-    return NNBVH_OK;
-}
-
-}  // extern "C"
-
-// nnbvh_kd_trace_batches_device and its candidates form (cands nullable; cands[b] belongs to batches[b], capacity 0 =
-// a plain batch).  Everything is checked before the scene is looked at.
-static int kd_trace_batches(const char *fn, nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches,
-                            const nnbvh_host_candidates *cands, bool with_candidates, void *stream) {
-    if (!s || !batches || n_batches < 1 || n_batches > kKdMaxBatches || (with_candidates && !cands)) {
-        set_error(std::string(fn) + (with_candidates ? ": bad argument (a scene, 1..4 batches and their candidates)"
-                                                     : ": bad argument (a scene and 1..4 batches)"));
-        return NNBVH_ERR_ARG;
-    }
-    KdBatch jobs[kKdMaxBatches];
-    int64_t total = 0;
-    for (int b = 0; b < n_batches; ++b) {
-        const nnbvh_batch &k = batches[b];
-        if ((k.kind != NNBVH_BATCH_CLOSEST && k.kind != NNBVH_BATCH_ANY) || k.n < 0 || k.n >= (1LL << kKdIndexBits) ||
-            (k.n > 0 && (!k.d_rays || !k.d_out))) {
-            set_error(std::string(fn) + ": bad batch (kind, 0 <= n < 2^28, rays and output)");
-            return NNBVH_ERR_ARG;
-        }
-        if (cands && cands[b].capacity != 0) {
-            const char *why = candidates_fault(&cands[b], k.kind == NNBVH_BATCH_CLOSEST);
-            if (!why && k.kind == NNBVH_BATCH_ANY && (k.d_nodes_visited || k.d_prim_tests))
-                why = "an any-hit batch has exact counts or candidates, not both";
-            if (why) {
-                set_error(std::string(fn) + ": batch candidates: " + why);
-                return NNBVH_ERR_ARG;
-            }
-            jobs[b].hc = &cands[b];
-        }
-        jobs[b].any = k.kind == NNBVH_BATCH_ANY;
-        jobs[b].rays = k.d_rays;
-        jobs[b].n = k.n;
-        jobs[b].out = k.d_out;
-        jobs[b].visited = k.d_nodes_visited;
-        jobs[b].tests = k.d_prim_tests;
-        total += k.n;
-    }
-    if (total == 0) return NNBVH_OK;
-    KdDeviceGuard guard(s->device);
-    if (!guard.ok) return NNBVH_ERR_DEVICE;
-    std::lock_guard<std::mutex> lock(s->mu);
-    KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
-    if (!w) return NNBVH_ERR_DEVICE;
-    return kd_launch_batches(s, w, (hipStream_t)stream, jobs, n_batches);
-}
-
-// the arguments of a single-batch candidate call (a one-batch launch: fewer than 2^28 rays)
-static bool kd_candidate_args_ok(const char *fn, const nnbvh_kd_scene *s, int64_t n, const void *rays, const void *out,
-                                 const nnbvh_host_candidates *c, bool closest) {
-    const char *why = nullptr;
-    if (!s || n < 0 || (n > 0 && (!rays || !out))) why = "bad argument";
-    else if ((why = candidates_fault(c, closest)) != nullptr) {}
-    else if (n >= (1LL << kKdIndexBits)) why = "a batch of 2^28 rays or more";
-    if (why) set_error(std::string(fn) + ": " + why);
-    return !why;
-}
-
-static int kd_candidates_device(const char *fn, nnbvh_kd_scene *s, bool any, const void *d_rays, int64_t n, void *d_out,
-                                const nnbvh_host_candidates *c, void *stream) {
-    if (!kd_candidate_args_ok(fn, s, n, d_rays, d_out, c, !any)) return NNBVH_ERR_ARG;
-    if (n == 0) return NNBVH_OK;
-    KdDeviceGuard guard(s->device);
-    if (!guard.ok) return NNBVH_ERR_DEVICE;
-    std::lock_guard<std::mutex> lock(s->mu);
-    KdWorkspace *w = kd_workspace_for(s, (hipStream_t)stream);
-    if (!w) return NNBVH_ERR_DEVICE;
-    KdBatch batch;
-    batch.any = any, batch.rays = d_rays, batch.n = n, batch.out = d_out, batch.hc = c;
-    return kd_launch_batches(s, w, (hipStream_t)stream, &batch, 1);
-}
-
-// host buffers: one staged copy in, one launch on the null stream, copies out (synchronous)
-static int kd_candidates_host(const char *fn, nnbvh_kd_scene *s, bool any, const nnbvh_ray *rays, int64_t n, void *out,
-                              const nnbvh_host_candidates *c) {
-    if (!kd_candidate_args_ok(fn, s, n, rays, out, c, !any)) return NNBVH_ERR_ARG;
-    if (n == 0) return NNBVH_OK;
-    KdDeviceGuard guard(s->device);
-    if (!guard.ok) return NNBVH_ERR_DEVICE;
-    std::lock_guard<std::mutex> lock(s->mu);
-    const size_t k = (size_t)c->capacity, out_elem = any ? 1 : sizeof(nnbvh_hit);
-    void *d_rays = nullptr, *d_out = nullptr;
-    nnbvh_host_candidates d{};
-    d.capacity = c->capacity;
-    bool ok = kd_hip_ok(hipMalloc(&d_rays, (size_t)n * sizeof(nnbvh_ray)), "hipMalloc(rays)") &&
-              kd_hip_ok(hipMalloc(&d_out, (size_t)n * out_elem), "hipMalloc(results)") &&
-              kd_hip_ok(hipMalloc((void **)&d.count, (size_t)n * 4), "hipMalloc(count)") &&
-              (any || kd_hip_ok(hipMalloc((void **)&d.before, (size_t)n * 4), "hipMalloc(before)")) &&
-              kd_hip_ok(hipMalloc((void **)&d.prim, (size_t)n * k * 4), "hipMalloc(prim)") &&
-              kd_hip_ok(hipMalloc((void **)&d.instance, (size_t)n * k * 4), "hipMalloc(instance)") &&
-              kd_hip_ok(hipMemcpy(d_rays, rays, (size_t)n * sizeof(nnbvh_ray), hipMemcpyHostToDevice), "copy rays") &&
-              // the caller's entries beyond count stay as they were: start from them
-              kd_hip_ok(hipMemcpy(d.prim, c->prim, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy prim") &&
-              kd_hip_ok(hipMemcpy(d.instance, c->instance, (size_t)n * k * 4, hipMemcpyHostToDevice), "copy instance");
-    KdWorkspace *w = ok ? kd_workspace_for(s, nullptr) : nullptr;
-    int rc = w ? NNBVH_OK : NNBVH_ERR_DEVICE;
-    if (rc == NNBVH_OK) {
-        KdBatch batch;
-        batch.any = any, batch.rays = d_rays, batch.n = n, batch.out = d_out, batch.hc = &d;
-        rc = kd_launch_batches(s, w, nullptr, &batch, 1);
-    }
-    if (rc == NNBVH_OK &&
-        !(kd_hip_ok(hipStreamSynchronize(nullptr), "kd trace") &&
-          kd_hip_ok(hipMemcpy(out, d_out, (size_t)n * out_elem, hipMemcpyDeviceToHost), "copy results") &&
-          kd_hip_ok(hipMemcpy(c->count, d.count, (size_t)n * 4, hipMemcpyDeviceToHost), "copy count") &&
-          (any || kd_hip_ok(hipMemcpy(c->before, d.before, (size_t)n * 4, hipMemcpyDeviceToHost), "copy before")) &&
-          kd_hip_ok(hipMemcpy(c->prim, d.prim, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy prim") &&
-          kd_hip_ok(hipMemcpy(c->instance, d.instance, (size_t)n * k * 4, hipMemcpyDeviceToHost), "copy instance")))
-        rc = NNBVH_ERR_DEVICE;
-    for (void *q : {d_rays, d_out, (void *)d.count, (void *)d.before, (void *)d.prim, (void *)d.instance})
-        if (q) (void)hipFree(q);
-    return rc;
-}
-
-extern "C" {
-
-int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches, void *stream) {
-    return kd_trace_batches("kd_trace_batches_device", s, batches, n_batches, nullptr, false, stream);
-}
-
-int nnbvh_kd_trace_batches_candidates_device(nnbvh_kd_scene *s, const nnbvh_batch *batches, int n_batches,
-                                             const nnbvh_host_candidates *cands, void *stream) {
-    return kd_trace_batches("kd_trace_batches_candidates_device", s, batches, n_batches, cands, true, stream);
-}
-
-int nnbvh_kd_intersect_closest_candidates_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_hits,
-                                                 const nnbvh_host_candidates *c, void *stream) {
-    return kd_candidates_device("kd_intersect_closest_candidates_device", s, false, d_rays, n, d_hits, c, stream);
-}
-
-int nnbvh_kd_intersect_any_candidates_device(nnbvh_kd_scene *s, const void *d_rays, int64_t n, void *d_occluded,
-                                             const nnbvh_host_candidates *c, void *stream) {
-    return kd_candidates_device("kd_intersect_any_candidates_device", s, true, d_rays, n, d_occluded, c, stream);
-}
-
-int nnbvh_kd_intersect_closest_candidates(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits,
-                                          const nnbvh_host_candidates *c) {
-    return kd_candidates_host("kd_intersect_closest_candidates", s, false, rays, n, hits, c);
-}
-
-int nnbvh_kd_intersect_any_candidates(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, uint8_t *occluded,
-                                      const nnbvh_host_candidates *c) {
-    return kd_candidates_host("kd_intersect_any_candidates", s, true, rays, n, occluded, c);
-}
-
-int nnbvh_kd_intersect_closest(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, nnbvh_hit *hits) {
-    if (!s || n < 0 || n >= 0x7fffffffLL || (n > 0 && (!rays || !hits))) {
-        set_error("kd_intersect_closest: bad argument");
-        return NNBVH_ERR_ARG;
-    }
-    if (n == 0) return NNBVH_OK;
-    KdDeviceGuard guard(s->device);
-    if (!guard.ok) return NNBVH_ERR_DEVICE;
-    std::lock_guard<std::mutex> lock(s->mu);
-    KdWorkspace *w = kd_workspace_for(s, nullptr);
-    if (!w) return NNBVH_ERR_DEVICE;
-    if (!kd_grow(&w->d_in, &w->in_bytes, (size_t)n * sizeof(nnbvh_ray), "hipMalloc(rays)") ||
-        !kd_grow(&w->d_out, &w->out_bytes, (size_t)n * sizeof(nnbvh_hit), "hipMalloc(hits)"))
-        return NNBVH_ERR_DEVICE;
-    if (!kd_hip_ok(hipMemcpy(w->d_in, rays, (size_t)n * sizeof(nnbvh_ray), hipMemcpyHostToDevice), "copy rays"))
-        return NNBVH_ERR_DEVICE;
-    const int rc = kd_launch(s, 0, w->d_in, n, w->d_out, nullptr, nullptr, nullptr, nullptr, w);
-    if (rc != NNBVH_OK) return rc;
-    if (!kd_hip_ok(hipStreamSynchronize(nullptr), "kd trace") ||
-        !kd_hip_ok(hipMemcpy(hits, w->d_out, (size_t)n * sizeof(nnbvh_hit), hipMemcpyDeviceToHost), "copy hits"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
-}
-
-int nnbvh_kd_intersect_any(nnbvh_kd_scene *s, const nnbvh_ray *rays, int64_t n, uint8_t *occluded,
-                           int32_t *nodes_visited, int32_t *prim_tests) {
-    if (!s || n < 0 || n >= 0x7fffffffLL || (n > 0 && (!rays || !occluded))) {
-        set_error("kd_intersect_any: bad argument");
-        return NNBVH_ERR_ARG;
-    }
-    if (n == 0) return NNBVH_OK;
-    KdDeviceGuard guard(s->device);
-    if (!guard.ok) return NNBVH_ERR_DEVICE;
-    std::lock_guard<std::mutex> lock(s->mu);
-    KdWorkspace *w = kd_workspace_for(s, nullptr);
-    if (!w) return NNBVH_ERR_DEVICE;
-    if (!kd_grow(&w->d_in, &w->in_bytes, (size_t)n * sizeof(nnbvh_ray), "hipMalloc(rays)") ||
-        !kd_grow(&w->d_out, &w->out_bytes, (size_t)n, "hipMalloc(occluded)") ||
-        !kd_grow(&w->d_aux0, &w->aux_bytes, (size_t)n * 8, "hipMalloc(counts)"))
-        return NNBVH_ERR_DEVICE;
-    int32_t *d_vis = (int32_t *)w->d_aux0, *d_tst = d_vis + n;
-    if (!kd_hip_ok(hipMemcpy(w->d_in, rays, (size_t)n * sizeof(nnbvh_ray), hipMemcpyHostToDevice), "copy rays"))
-        return NNBVH_ERR_DEVICE;
-    const int rc = kd_launch(s, 1, w->d_in, n, nullptr, w->d_out, nodes_visited ? d_vis : nullptr,
-                             prim_tests ? d_tst : nullptr, nullptr, w);
-    if (rc != NNBVH_OK) return rc;
-    if (!kd_hip_ok(hipStreamSynchronize(nullptr), "kd trace") ||
-        !kd_hip_ok(hipMemcpy(occluded, w->d_out, (size_t)n, hipMemcpyDeviceToHost), "copy occluded"))
-        return NNBVH_ERR_DEVICE;
-    if (nodes_visited && !kd_hip_ok(hipMemcpy(nodes_visited, d_vis, (size_t)n * 4, hipMemcpyDeviceToHost), "copy counts"))
-        return NNBVH_ERR_DEVICE;
-    if (prim_tests && !kd_hip_ok(hipMemcpy(prim_tests, d_tst, (size_t)n * 4, hipMemcpyDeviceToHost), "copy counts"))
-        return NNBVH_ERR_DEVICE;
-    return NNBVH_OK;
-}
-
-}  // extern "C"
-
-// ---- the walk calls' launchers (capi_wavefront.cpp: nnbvh_kd_wavefront_walk_*) ------------------------------------
-bool nnbvh::kd_walk_scratch(KdWorkspace *w, int slot, size_t bytes, void **out) {
-    if (!kd_grow(&w->walk[slot], &w->walk_bytes[slot], std::max<size_t>(bytes, 16), "hipMalloc(walk workspace)"))
-        return false;
-    *out = w->walk[slot];
-    return true;
-}
-
-int nnbvh::launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const WalkJob &k) {
-    KdParams p{};
-    kd_fill_scene(s, w, p);
-    p.nBatches = 1;
-    p.anyMask = 0;
-    p.bRays[0] = (const nnbvh_ray *)k.rays;
-    p.bN[0] = (long)k.n;
-    p.bNDev[0] = k.d_n;
-    const ShadingMeshDevice &m = *k.mesh;
-    p.wMesh = {m.verts, m.triVerts, m.patchVerts, m.normals, m.uvs, m.tangents, m.faceIndices, m.triFlags, m.nTris,
-               m.defaultFlags, nullptr, 0, nullptr, nullptr};  // kd scenes have one level
-    p.walk = k.a;
-    // the lean instance with the triangle-only interaction where neither the scene nor the mesh holds patches, else the
-    // PATCH = 1 instance with the patch-capable one (launch_str_step's choice of FULL); each with both offset widths
-    void (*const kernels[8])(KdParams) = {
-        kd_trace_kernel<4, 0, kKdWLean, 0>, kd_trace_kernel<4, 1, kKdW, 0>, kd_trace_kernel<4, 0, kKdWLean, 1>,
-        kd_trace_kernel<4, 1, kKdW, 1>,     kd_trace_kernel<5, 0, kKdWLean, 0>, kd_trace_kernel<5, 1, kKdW, 0>,
-        kd_trace_kernel<5, 0, kKdWLean, 1>, kd_trace_kernel<5, 1, kKdW, 1>};
-    const int full = (s->has_patches || m.patchVerts) ? 1 : 0;
-    void (*const kernel)(KdParams) = kernels[4 * (k.kind - 1) + 2 * s->fits32 + full];
-    const int slot = 5 + 2 * (k.kind - 1) + full;
-    if (s->blocks_per_cu[slot] == 0) {
-        int occ = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kKdBlock, 0);
-        s->blocks_per_cu[slot] = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
-    }
-    int blocks = s->n_cus * s->blocks_per_cu[slot];
-    const int64_t need = (k.n + kKdBlock - 1) / kKdBlock;
-    if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
-    hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, w->queue, kKdQueues * kKdQueueStride);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
-    return kd_hip_ok(hipGetLastError(), "kd walk kernel launch") ? NNBVH_OK : NNBVH_ERR_DEVICE;
-}

@@ -100,7 +100,7 @@ constexpr int kMaxStack = 64;  // the reference's nodesToVisit[64], aggregates.c
 
 // The degenerate-triangle test of shapes.cpp:176-177, LengthSquared(Cross(p2 - p0, p1 - p0)) == 0 with
 // DifferenceOfProducts (util/math.h:569-575), in the reference's float32 operations: ONE function for the host bake
-// (kd_trace.hip) and the device bake (kd_bake.hip) of the kd primitive records, so that both set kPrimDegenerate from
+// (capi_kd.cpp) and the device bake (kd_bake.hip) of the kd primitive records, so that both set kPrimDegenerate from
 // the same bits.  The fused multiply-adds are explicit; the build's -ffp-contract=off forms no others.
 #if defined(__HIPCC__)
 #define NNBVH_HD __host__ __device__

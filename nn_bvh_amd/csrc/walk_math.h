@@ -32,7 +32,7 @@ struct WalkParams {
 };
 
 // One launch of a walk instance of a trace kernel behind its queue reset node (launch_walk: capi_trace.cpp for BVH
-// scenes, kd_trace.hip for kd-tree scenes), over the items whose first rays are the records `rays`: item i is ray i,
+// scenes, capi_kd.cpp for kd-tree scenes), over the items whose first rays are the records `rays`: item i is ray i,
 // and the batch holds min(n, max(*d_n, 0)) of them (d_n nullable).  The caller has checked the arguments, the type's
 // refusals among them, and holds the scene's lock.
 struct WalkJob {

@@ -1,8 +1,8 @@
 """Every traversal kernel family at the 64-entry stack limit and through its spill.
 
 Each ray keeps its pending nodes in a per-lane LDS ring window (BVH kernels: 4, 8 or 16 entries, bvh_trace.hip; kd
-kernels: kKdWLean = 4 or kKdW = 8, kd_trace.hip); the oldest entry spills to an HBM array whose size is computed
-exactly (workspace_for in bvh_capi.cpp, kd_workspace_for in kd_trace.hip).  The scenes here (scenes_small: chain_tree
+kernels: kKdWLean = 4 or kKdW = 8, kd_trace.h); the oldest entry spills to an HBM array whose size is computed
+exactly (workspace_for in bvh_capi.cpp, kd_workspace_for in capi_kd.cpp).  The scenes here (scenes_small: chain_tree
 tube form, two_level_chain, kd_chain) make every "deep" ray hold 64 pending entries (63 = a + b in the two-level
 scene, see below), which the CPU tests in this file PROVE with the oracle's pending-depth output and a float64
 margin check — never with the device's own counters.  Every GPU case compares bit for bit with the oracle and
@@ -657,7 +657,7 @@ def test_kd_chain_of_65_is_refused(nnbvh_lib):
 
 
 # ---- GPU: one deep ray in every lane of the largest grid ----------------------------------------------------------------
-# kBlockThreads = 256 (bvh_trace.h) and kKdBlock = 256 (kd_trace.hip); both libraries launch at most 8 blocks per CU
+# kBlockThreads = 256 (bvh_trace.h) and kKdBlock = 256 (kd_trace.h); both libraries launch at most 8 blocks per CU
 BLOCK_THREADS = 256
 N_DISTINCT = 4096
 
@@ -703,12 +703,15 @@ def test_full_grid_bvh_any_hit_with_counts():
         assert (got.reshape(-1, N_DISTINCT) == one[None, :]).all()
     d_rays = upload(rays)
 
-    counts = []  # the counting call (mode 1) on both streams: its counters, per stream
+    import torch
+    # the counting call (mode 1) on both streams: its counters, per stream.  They are zeroed here, ahead of
+    # two_streams' synchronize: a fill on the default stream is not ordered against a launch on another stream
+    counts = [[torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2)] for _ in range(2)]
+    unused = iter(counts)
 
     def call(r, o, m, st):
-        import torch
-        counts.append([torch.zeros(m, dtype=torch.int32, device="cuda") for _ in range(2)])
-        agg.intersect_p_device(r, o, m, counts[-1][0].data_ptr(), counts[-1][1].data_ptr(), stream=st)
+        v, c = next(unused)
+        agg.intersect_p_device(r, o, m, v.data_ptr(), c.data_ptr(), stream=st)
     for flags, (v, c) in zip(two_streams(call, d_rays, n, 1), counts):
         assert (flags.reshape(-1, N_DISTINCT) == eocc[None, :]).all()
         assert (v.cpu().numpy().reshape(-1, N_DISTINCT) == evis[None, :]).all()
