@@ -1159,14 +1159,16 @@ int nnbvh_wavefront_walk_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m,
  * which counts 16, when a wavefront picks its next step), "int_repeat" / "prim_repeat" (1..16
  * interior / primitive steps per scheduling decision; the one-launch kernel of nnbvh_trace_batches_device
  * always takes one primitive step), "fused_batches" (0/1: nnbvh_trace_batches_device as one launch where
- * the batches allow it).  Returns NNBVH_ERR_ARG for unknown keys. */
+ * the batches allow it), "top_table" (0/1: the lean one-launch kernels serve the scene's top records from
+ * LDS).  Returns NNBVH_ERR_ARG for unknown keys. */
 int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value);
 
 /* diagnostics: wavefront scheduling statistics accumulated since the last reset —
  * out = {interior trips, interior lanes, primitive trips, primitive lanes, refill trips,
  * refill lanes, and over the interior trips the sums of lanes waiting on an interior node,
- * on a primitive, idle; one spare; shader cycles spent in interior / primitive / refill trips; one
- * spare; interior steps executed and the lanes that took part}.  All zero unless built with
+ * on a primitive, idle; one spare; shader cycles spent in interior / primitive / refill trips; the
+ * lanes of interior steps whose record came from the LDS top table; interior steps executed and the lanes
+ * that took part}.  All zero unless built with
  * -DNNBVH_STATS. */
 int nnbvh_scene_sched_stats(nnbvh_scene *s, uint64_t out[16], int reset);
 

@@ -422,7 +422,7 @@ class BVHAggregate:
         check(_lib.lib().nnbvh_scene_sched_stats(self._h, ptr(out), int(reset)), "sched_stats")
         return dict(zip(("int_trips", "int_lanes", "prim_trips", "prim_lanes", "refill_trips",
                          "refill_lanes", "i_nint", "i_nprim", "i_nidle", "spare0", "int_cycles",
-                         "prim_cycles", "refill_cycles", "spare1", "int_steps", "int_step_lanes"),
+                         "prim_cycles", "refill_cycles", "int_top_lanes", "int_steps", "int_step_lanes"),
                         (int(x) for x in out)))
 
     # -- reference interface ----------------------------------------------------------

@@ -12,6 +12,7 @@
 #include "alpha_texture_math.h"
 #include "bvh_build_gpu.h"
 #include "capi_internal.h"
+#include "top_table.h"
 
 namespace nnbvh {
 
@@ -224,6 +225,28 @@ static bool attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *tex
     return true;
 }
 
+// The top table of a flat scene that runs the lean instances (top_table.h): the first kTopRecords records breadth-first
+// from the root, read back from the baked array one by one (which is only read) and uploaded as an array of the
+// scene's own.  Other scenes, and a scene whose root is a leaf, have none.  false: a device call failed.
+static bool attach_top_table(nnbvh_scene *s) {
+    if (!scene_runs_lean(s)) return true;
+    std::vector<WideNode> table;
+    std::vector<int32_t> order;
+    const auto fetch = [&](int32_t record, WideNode *out) {
+        return hip_ok(hipMemcpy(out, s->d_wide + 4 * (size_t)record, sizeof(WideNode), hipMemcpyDeviceToHost),
+                      "hipMemcpy(top record)");
+    };
+    if (!build_top_table(fetch, s->root_ref, s->n_interior, kTopRecords, &table, &order)) return false;
+    if (table.empty()) return true;
+    const size_t bytes = table.size() * sizeof(WideNode);
+    if (!hip_ok(hipMalloc((void **)&s->d_top, bytes), "hipMalloc(top table)") ||
+        !hip_ok(hipMemcpy(s->d_top, table.data(), bytes, hipMemcpyHostToDevice), "hipMemcpy(top table)"))
+        return false;
+    s->n_top = (int)table.size();
+    s->device_bytes += bytes;
+    return true;
+}
+
 extern "C" {
 
 const char *nnbvh_last_error(void) { return g_error.c_str(); }
@@ -260,6 +283,12 @@ static nnbvh_scene *scene_from_baked(const BakedScene &b, int depth, int device)
                       std::max<size_t>((size_t)b.n_slots, 1) * 16;
     if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
+    if (!attach_top_table(s)) {
+        const std::string why = nnbvh_last_error();
+        nnbvh_scene_destroy(s);
+        set_error(why);
+        return nullptr;
+    }
     return s;
 }
 
@@ -778,6 +807,7 @@ void nnbvh_scene_destroy(nnbvh_scene *s) {
     if (s->d_anim) (void)hipFree(s->d_anim);
     if (s->d_alpha_tex) (void)hipFree(s->d_alpha_tex);
     if (s->d_alpha_texels) (void)hipFree(s->d_alpha_texels);
+    if (s->d_top) (void)hipFree(s->d_top);
     if (s->d_stats) (void)hipFree(s->d_stats);
     delete s;
 }
@@ -908,6 +938,8 @@ int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value) {
         s->prim_repeat = value;
     } else if (k == "fused_batches") {
         s->fused_batches = value ? 1 : 0;
+    } else if (k == "top_table") {
+        s->use_top = value ? 1 : 0;
     } else if (k == "xcd_queues") {
         s->xcd_queues = value ? 1 : 0;
     } else if (k == "prim_weight") {

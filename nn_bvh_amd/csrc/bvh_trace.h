@@ -76,6 +76,10 @@ struct TraceParams {
     // 16-B slots per texture, AlphaTexDesc of alpha_texture_math.h) and its texel pool
     const float4 *alphaTex;
     const float *alphaTexels;
+    // the scene's top table (top_table.h; the lean mode-3 instances copy it into LDS), appended likewise: nTop records
+    // of four float4 each, at most kTopRecords.  With nTop > 0 rootRef is the tagged root, kTopTag | 0
+    const float4 *top;
+    int nTop;
 };
 
 hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream);

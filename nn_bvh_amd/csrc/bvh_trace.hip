@@ -184,7 +184,10 @@ __device__ __forceinline__ T pick_batch(const T (&a)[kMaxFusedBatches], int b) {
         /* aggregates.cpp:534-535 */                                                                                  \
         r.inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};                                                                 \
         ray_shear(r, d);                                                                                              \
-        if (MODE == 0 || MODE == 3) {                                                                                 \
+        if constexpr (kTop) {                                                                                         \
+            hit0 = __int_as_float(-1);                                                                                \
+            hit1 = hit2 = hit3 = 0.0f;                                                                                \
+        } else if (MODE == 0 || MODE == 3) {                                                                          \
             cold[kColdHit][lane] = __int_as_float(-1);                                                                \
             cold[kColdHit + 1][lane] = 0.0f;                                                                          \
             cold[kColdHit + 2][lane] = 0.0f;                                                                          \
@@ -262,13 +265,29 @@ void trace_kernel(TraceParams p) {
     [[maybe_unused]] constexpr int kWalkD = kColdWalk, kWalkTime = kColdWalk + 3, kWalkTMax = kColdWalk + 4,
                                    kWalkCalls = kColdWalk + 5;
     constexpr int kColdFields = kColdWalk + (WALK ? 6 : 0);
-    __shared__ float s_cold[kBlockThreads / 64][kColdFields > 0 ? kColdFields : 1][64];
+    // The lean one-launch instances keep the four hit words in VGPRs (hit0 .. hit3) and have no cold state at all: the
+    // 4 KiB go to the block's copy of the scene's top table (nnbvh_internal.h kTopRecords), from which a
+    // lane whose `cur` carries kTopTag reads its record instead of from p.wide — the same bytes.  Tagged references
+    // only come out of table records and the tagged root, and pass through the stack and its spill unchanged.
+    constexpr bool kTop = kLean && MODEW == 3;
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int gtid = blockIdx.x * kBlockThreads + threadIdx.x;
     float(*stk)[2][64] = s_stack[wave];
-    float(*cold)[64] = s_cold[wave];
+    float(*cold)[64] = nullptr;
+    [[maybe_unused]] const float4 *top = nullptr;
+    if constexpr (kTop) {
+        __shared__ float4 s_top[kTopRecords * 4];
+        static_assert(kTopRecords * 4 <= kBlockThreads, "one float4 per thread copies the table");
+        if ((int)threadIdx.x < p.nTop * 4) s_top[threadIdx.x] = p.top[threadIdx.x];
+        __syncthreads();  // every thread of every block, whatever the launch has to do
+        top = s_top;
+    } else {
+        __shared__ float s_cold[kBlockThreads / 64][kColdFields > 0 ? kColdFields : 1][64];
+        cold = s_cold[wave];
+    }
+    [[maybe_unused]] float hit0 = 0.0f, hit1 = 0.0f, hit2 = 0.0f, hit3 = 0.0f;  // kTop: the current best hit
     int riReg = -1;  // lean instances: the ray this lane carries, -1 = none
     if (!kLean) cold[kColdRi][lane] = __int_as_float(-1);
     const long spillStride = (long)gridDim.x * kBlockThreads;
@@ -292,7 +311,8 @@ void trace_kernel(TraceParams p) {
 #ifdef NNBVH_STATS
     // trips/lanes per kind (I, P, R); [6..8] = sum nInt,nPrim,nIdle over I trips; [10..12] = shader
     // cycles (s_memtime) spent in I / P / R trips incl. their scheduling decision; [14], [15] =
-    // interior steps executed and the lanes that took part in them
+    // interior steps executed and the lanes that took part in them; [13] = those of the lanes whose record came from
+    // the LDS top table (lean one-launch instances)
     unsigned long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stPrev = __builtin_amdgcn_s_memtime();
     int stKind = 2;
@@ -556,10 +576,17 @@ void trace_kernel(TraceParams p) {
                 closestLane = !((p.anyMask >> ((kLean ? riReg : __float_as_int(cold[kColdRi][lane])) >> kFusedIndexBits)) & 1u);
             if (hit) {
                 if (closestLane) {
-                    cold[kColdHit][lane] = s0.w;  // primitive id bits
-                    cold[kColdHit + 1][lane] = x0;
-                    cold[kColdHit + 2][lane] = x1;
-                    cold[kColdHit + 3][lane] = x2;
+                    if constexpr (kTop) {
+                        hit0 = s0.w;
+                        hit1 = x0;
+                        hit2 = x1;
+                        hit3 = x2;
+                    } else {
+                        cold[kColdHit][lane] = s0.w;  // primitive id bits
+                        cold[kColdHit + 1][lane] = x0;
+                        cold[kColdHit + 2][lane] = x1;
+                        cold[kColdHit + 3][lane] = x2;
+                    }
                     tMax = th;
                     if (INST) {
                         cold[kHitInst][lane] = cold[kCurInst][lane];
@@ -626,8 +653,31 @@ void trace_kernel(TraceParams p) {
 #ifdef NNBVH_STATS
         st[14] += 1;
         st[15] += __popcll(__ballot(cur >= 0));
+        if (kTop) st[13] += __popcll(__ballot(cur >= 0 && (cur & kTopTag) != 0));  // ... of them, served from the top table
 #endif
-        if (cur >= 0) {
+        if constexpr (kTop) {
+            // a tagged lane reads the byte copy of its record from the block's table (slot = cur without the tag: the
+            // shift drops bit 30), the others load from p.wide; both join before the arithmetic
+            if (cur >= 0) {
+                typedef float v4f __attribute__((ext_vector_type(4)));
+                const unsigned at = (unsigned)cur << 6;
+                v4f q0, q1, q2, q3;
+                if (cur & kTopTag) {
+                    const v4f *rec = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(top) + at);
+                    q3 = rec[3];
+                    q0 = rec[0], q1 = rec[1], q2 = rec[2];
+                    // keeps these four ds_read_b128: left alone the compiler selects between the two ADDRESSES and
+                    // issues flat loads for all lanes, 64-bit address arithmetic included (measured: no faster)
+                    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3));
+                } else {
+                    const v4f *rec = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(p.wide) + at);
+                    q3 = rec[3];
+                    q0 = rec[0], q1 = rec[1], q2 = rec[2];
+                }
+                interior_math({q0.x, q0.y, q0.z, q0.w}, {q1.x, q1.y, q1.z, q1.w}, {q2.x, q2.y, q2.z, q2.w},
+                              {q3.x, q3.y, q3.z, q3.w});
+            }
+        } else if (cur >= 0) {
             // lean instances address records and slots with a 32-bit byte offset from a scalar base (one
             // 32-bit shift instead of a 64-bit shift and a 64-bit add per fetch); the launcher only picks
             // them when both arrays are below 4 GiB (p.fits32)
@@ -757,11 +807,11 @@ void trace_kernel(TraceParams p) {
                     store_stream(reinterpret_cast<uint8_t *>(outp) + idx, (uint8_t)(found ? 1 : (needHost ? 2 : 0)));
                 } else {
                     float4 h0, h1;
-                    h0.x = cold[kColdHit][lane];
+                    h0.x = kTop ? hit0 : cold[kColdHit][lane];
                     h0.y = tMax;
-                    h0.z = cold[kColdHit + 1][lane];
-                    h0.w = cold[kColdHit + 2][lane];
-                    h1.x = cold[kColdHit + 3][lane];
+                    h0.z = kTop ? hit1 : cold[kColdHit + 1][lane];
+                    h0.w = kTop ? hit2 : cold[kColdHit + 2][lane];
+                    h1.x = kTop ? hit3 : cold[kColdHit + 3][lane];
                     h1.y = __int_as_float(visited);
                     h1.z = __int_as_float(tests);
                     h1.w = INST ? cold[kHitInst][lane] : 0.0f;

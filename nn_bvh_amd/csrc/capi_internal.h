@@ -114,6 +114,10 @@ struct nnbvh_scene {
     float *d_alpha_texels = nullptr;
     int n_alpha_tex = 0;
     int64_t n_alpha_texels = 0;
+    // the top table of a lean scene (top_table.h): n_top records of 64 B, or null (the root is a leaf; not a lean scene)
+    float4 *d_top = nullptr;
+    int n_top = 0;
+    int use_top = 1;  // option "top_table" (speed only): 0 = the lean one-launch kernels read every record from d_wide
 };
 
 struct nnbvh_shading_mesh {

@@ -166,6 +166,12 @@ int nnbvh::launch_fused_batches(nnbvh_scene *s, Workspace *w, hipStream_t stream
     }
     if (p.nBatches == 0) return NNBVH_OK;
     p.n = (long)total;
+    // the lean instances (record and SOA form) serve the scene's top records from LDS: the walk enters at the tagged root
+    if (s->d_top && s->use_top && !candidates && scene_runs_lean(s)) {
+        p.top = s->d_top;
+        p.nTop = s->n_top;
+        p.rootRef = kTopTag;  // slot 0
+    }
     return run_trace(s, stream, 3, candidates, soa, p, kMaxFusedBatches * kMaxQueues * kQueueStrideWords,
                      "fused trace kernel launch");
 }

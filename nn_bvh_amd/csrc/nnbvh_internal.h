@@ -98,6 +98,14 @@ constexpr const char *kAlphaTexElsewhere =
 
 constexpr int kMaxStack = 64;  // the reference's nodesToVisit[64], aggregates.cpp:538
 
+// The top table of a lean scene (top_table.h): byte copies of the first kTopRecords interior records in
+// breadth-first order from the root, which the lean one-launch kernels serve from LDS.  Inside the copies a reference
+// to another copied record is kTopTag | its table slot: still >= 0 ("interior"), and bit 30 is free because the lean
+// instances only run scenes with fewer than 2^26 records (scene_fits32).  63 records = 4 032 B: the 4 KiB per block
+// that the four hit words occupied.
+constexpr int kTopRecords = 63;
+constexpr int32_t kTopTag = 1 << 30;
+
 // The degenerate-triangle test of shapes.cpp:176-177, LengthSquared(Cross(p2 - p0, p1 - p0)) == 0 with
 // DifferenceOfProducts (util/math.h:569-575), in the reference's float32 operations: ONE function for the host bake
 // (capi_kd.cpp) and the device bake (kd_bake.hip) of the kd primitive records, so that both set kPrimDegenerate from

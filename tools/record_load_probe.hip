@@ -107,7 +107,7 @@ int main() {
         unsigned *out;
         if (hipMalloc(&d, h.size() * 4) != hipSuccess) return 1;
         (void)hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice);
-        for (int blocksPerCu : {6, 4}) {
+        for (int blocksPerCu : {8, 6, 4}) {  // 8: what the lean trace kernels run at
             const int blocks = 256 * blocksPerCu;
             (void)hipMalloc(&out, (size_t)blocks * 256 * 4);
             std::vector<unsigned> ref, got((size_t)blocks * 256);
