@@ -1160,7 +1160,8 @@ int nnbvh_wavefront_walk_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m,
  * interior / primitive steps per scheduling decision; the one-launch kernel of nnbvh_trace_batches_device
  * always takes one primitive step), "fused_batches" (0/1: nnbvh_trace_batches_device as one launch where
  * the batches allow it), "top_table" (0/1: the lean one-launch kernels serve the scene's top records from
- * LDS).  Returns NNBVH_ERR_ARG for unknown keys. */
+ * LDS), "top_burst" (1..65: a wavefront of those kernels with at least this many lanes at a record of the LDS
+ * table advances them in a table step of their own, which loads nothing from memory; 65 = never).  Returns NNBVH_ERR_ARG for unknown keys. */
 int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value);
 
 /* diagnostics: wavefront scheduling statistics accumulated since the last reset —
@@ -1168,9 +1169,10 @@ int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value);
  * refill lanes, and over the interior trips the sums of lanes waiting on an interior node,
  * on a primitive, idle; one spare; shader cycles spent in interior / primitive / refill trips; the
  * lanes of interior steps whose record came from the LDS top table; interior steps executed and the lanes
- * that took part}.  All zero unless built with
+ * that took part; table trips, the lanes that took part in them and their shader cycles (these lanes are not
+ * among those of the interior steps); one spare}.  All zero unless built with
  * -DNNBVH_STATS. */
-int nnbvh_scene_sched_stats(nnbvh_scene *s, uint64_t out[16], int reset);
+int nnbvh_scene_sched_stats(nnbvh_scene *s, uint64_t out[20], int reset);
 
 #ifdef __cplusplus
 }

@@ -281,8 +281,8 @@ static nnbvh_scene *scene_from_baked(const BakedScene &b, int depth, int device)
     s->d_prims = (float4 *)b.d_prims;
     s->device_bytes = (size_t)std::max(b.n_interior, 1) * sizeof(WideNode) +
                       std::max<size_t>((size_t)b.n_slots, 1) * 16;
-    if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
+    if (hipMalloc((void **)&s->d_stats, nnbvh::kSchedStatWords * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
     if (!attach_top_table(s)) {
         const std::string why = nnbvh_last_error();
         nnbvh_scene_destroy(s);
@@ -588,8 +588,8 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
         }
         s->n_anim = n_instances;
     }
-    if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
+    if (hipMalloc((void **)&s->d_stats, nnbvh::kSchedStatWords * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
     return s;
 }
 
@@ -882,20 +882,20 @@ int nnbvh_scene_read(const nnbvh_scene *s, int what, void *out, size_t bytes) {
     return NNBVH_OK;
 }
 
-int nnbvh_scene_sched_stats(nnbvh_scene *s, uint64_t out[16], int reset) {
+int nnbvh_scene_sched_stats(nnbvh_scene *s, uint64_t out[20], int reset) {
     if (!s || !out) {
         set_error("scene_sched_stats: null argument");
         return NNBVH_ERR_ARG;
     }
-    std::memset(out, 0, 16 * sizeof(uint64_t));
+    std::memset(out, 0, nnbvh::kSchedStatWords * sizeof(uint64_t));
     if (!s->d_stats) return NNBVH_OK;
     DeviceGuard guard(s->device);
     if (!guard.ok) return NNBVH_ERR_DEVICE;
     if (!hip_ok(hipDeviceSynchronize(), "scene_sched_stats") ||
-        !hip_ok(hipMemcpy(out, s->d_stats, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost),
+        !hip_ok(hipMemcpy(out, s->d_stats, nnbvh::kSchedStatWords * sizeof(uint64_t), hipMemcpyDeviceToHost),
                 "scene_sched_stats"))
         return NNBVH_ERR_DEVICE;
-    if (reset) (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
+    if (reset) (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
     return NNBVH_OK;
 }
 
@@ -940,6 +940,12 @@ int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value) {
         s->fused_batches = value ? 1 : 0;
     } else if (k == "top_table") {
         s->use_top = value ? 1 : 0;
+    } else if (k == "top_burst") {
+        if (value < 1 || value > 65) {
+            set_error("set_option: top_burst must be 1..65");
+            return NNBVH_ERR_ARG;
+        }
+        s->top_burst = value;
     } else if (k == "xcd_queues") {
         s->xcd_queues = value ? 1 : 0;
     } else if (k == "prim_weight") {

@@ -15,6 +15,7 @@ constexpr int kBlockThreads = 256;   // 4 wavefronts
 constexpr int kMaxQueues = 8;        // one ray queue per XCD
 constexpr int kQueueStrideWords = 32;  // each queue head on its own 128-B line
 constexpr int kMaxFusedBatches = 4;    // batches one mode-3 launch may cover
+constexpr int kSchedStatWords = 20;   // NNBVH_STATS builds: counters per scene (nnbvh_scene_sched_stats)
 constexpr int kFusedIndexBits = 28;    // a lane's ray tag = batch << 28 | index: batches below 2^28 rays
 
 struct TraceParams {
@@ -80,6 +81,7 @@ struct TraceParams {
     // of four float4 each, at most kTopRecords.  With nTop > 0 rootRef is the tagged root, kTopTag | 0
     const float4 *top;
     int nTop;
+    int topBurst;  // tagged interior lanes that make the wave take a table step (1..64; above 64: never)
 };
 
 hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream);

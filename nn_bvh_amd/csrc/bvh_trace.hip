@@ -66,7 +66,10 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // Each trip of the scheduling loop the WAVE picks one kind of step (wave-uniform, from
 // ballots) and the lanes in that state execute it; the others idle for that trip.  A ray's
 // own sequence of steps is exactly the reference's, so results cannot depend on the policy.
-// These four step kinds (refill, enter, primitive, interior) are all there are.
+// These step kinds (refill, enter, primitive, interior and, in the lean one-launch instances, table) are all there are.
+// A table step is an interior step for the lanes whose record is in the block's LDS top table only: no global load, so
+// it does not last a global round trip.  An interior trip begins with table steps while at least p.topBurst lanes wait at
+// a tagged record; the check sits there and not at the head of the loop, where it cost every trip 1.5 % in all.
 //
 // INST = 1: the scene is two-level (TransformedPrimitive leaves, cpu/primitive.cpp:112-131).  An
 // instance primitive saves the lane's ray state in LDS, transforms the ray with the reference's
@@ -312,8 +315,9 @@ void trace_kernel(TraceParams p) {
     // trips/lanes per kind (I, P, R); [6..8] = sum nInt,nPrim,nIdle over I trips; [10..12] = shader
     // cycles (s_memtime) spent in I / P / R trips incl. their scheduling decision; [14], [15] =
     // interior steps executed and the lanes that took part in them; [13] = those of the lanes whose record came from
-    // the LDS top table (lean one-launch instances)
-    unsigned long long st[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // the LDS top table (lean one-launch instances); [16], [17], [18] = table trips, the lanes that took part in them,
+    // their shader cycles (not part of [13] .. [15])
+    unsigned long long st[kSchedStatWords] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stPrev = __builtin_amdgcn_s_memtime();
     int stKind = 2;
 #endif
@@ -325,6 +329,14 @@ void trace_kernel(TraceParams p) {
     int floor = -1;      // INST: stack level the current child traversal must not pop below
     bool found = false;  // MODE 1/2
     bool exhausted = false;
+    // kTop: the table-step threshold, read once and made opaque: left to itself the compiler re-reads p.topBurst from the
+    // kernel arguments wherever it is compared (the SGPRs are full), and the wait for that scalar load is also a wait
+    // for the LDS stack writes in flight
+    [[maybe_unused]] int topBurst = 65;
+    if constexpr (kTop) {
+        topBurst = p.topBurst;
+        asm volatile("" : "+s"(topBurst));
+    }
 
     // pop entries until one whose deferred box test passes with the current tMax
     auto pop_entry = [&](int &ref, float &key) {
@@ -688,6 +700,19 @@ void trace_kernel(TraceParams p) {
             interior_math(q0, q1, q2, q3);
         }
     };
+    // the table step (kTop): the LDS block of interior_step alone, for the lanes at a tagged record.  No global load is
+    // issued and none is waited for (the spill store of a full window and the spill re-load of a pop complete inside
+    // their own branches)
+    [[maybe_unused]] auto table_step = [&]() {
+        if (((unsigned)cur >> 30) == 1u) {  // cur >= 0 && (cur & kTopTag)
+            typedef float v4f __attribute__((ext_vector_type(4)));
+            const v4f *rec = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(top) + ((unsigned)cur << 6));
+            const v4f q3 = rec[3];
+            const v4f q0 = rec[0], q1 = rec[1], q2 = rec[2];
+            interior_math({q0.x, q0.y, q0.z, q0.w}, {q1.x, q1.y, q1.z, q1.w}, {q2.x, q2.y, q2.z, q2.w},
+                          {q3.x, q3.y, q3.z, q3.w});
+        }
+    };
 
     for (;;) {
 #ifdef NNBVH_STATS
@@ -1002,6 +1027,34 @@ void trace_kernel(TraceParams p) {
             // ---- interior step(s): up to p.intRepeat in a row before the next scheduling
             // decision (lanes that leave the interior state sit the remaining ones out) -------
             if (MODE == 3) {
+                if constexpr (kTop) {
+                    // ---- table step(s): an interior trip of a wave with at least p.topBurst lanes at a record of the
+                    // LDS table begins with steps for those lanes alone, on one ballot each, until fewer are left (they
+                    // ride along in the ordinary steps below).  After a refill the new rays so walk down the top levels
+                    // at the refill's lane count and without a global round trip.  (p.topBurst > 64: never)
+#ifdef NNBVH_STATS
+                    unsigned long long stT0 = 0;  // (read only when a table step runs: s_memtime is not free)
+                    bool stTable = false;
+#endif
+                    for (;;) {
+                        const int nTag = __popcll(__ballot(((unsigned)cur >> 30) == 1u));
+                        if (nTag < topBurst) break;
+#ifdef NNBVH_STATS
+                        if (!stTable) stT0 = __builtin_amdgcn_s_memtime();
+                        stTable = true;
+                        st[16] += 1;
+                        st[17] += nTag;
+#endif
+                        table_step();
+                    }
+#ifdef NNBVH_STATS
+                    if (stTable) {
+                        const unsigned long long stT1 = __builtin_amdgcn_s_memtime();
+                        st[18] += stT1 - stT0;
+                        stPrev += stT1 - stT0;  // ... which are not the interior trip's
+                    }
+#endif
+                }
                 // the one-launch kernel: the first three steps (the default int_repeat) written out, no trip
                 // counter to maintain (+0.8 %; the separate-launch kernels lose 1.8 % with it and keep the loop)
                 interior_step();
@@ -1022,7 +1075,7 @@ void trace_kernel(TraceParams p) {
     }
 #ifdef NNBVH_STATS
     if (lane == 0 && p.stats)
-        for (int k = 0; k < 16; ++k) atomicAdd(&p.stats[k], st[k]);
+        for (int k = 0; k < kSchedStatWords; ++k) atomicAdd(&p.stats[k], st[k]);
 #endif
 }
 #undef BVH_BEGIN_RAY

@@ -118,6 +118,8 @@ struct nnbvh_scene {
     float4 *d_top = nullptr;
     int n_top = 0;
     int use_top = 1;  // option "top_table" (speed only): 0 = the lean one-launch kernels read every record from d_wide
+    int top_burst = 24;  // option "top_burst": tagged interior lanes that make a wave take a table step (65 = never);
+                         // crown step: 16 .. 32 within 0.5 % of each other, 8 and 48 slower (profiles/top_table_steps.txt)
 };
 
 struct nnbvh_shading_mesh {

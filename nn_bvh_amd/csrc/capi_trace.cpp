@@ -43,6 +43,7 @@ static TraceParams scene_params(const nnbvh_scene *s, const Workspace *w) {
     p.refillWeight = s->refill_weight;
     p.stats = s->d_stats;
     p.intRepeat = s->int_repeat;
+    p.topBurst = s->top_burst;
     p.primRepeat = s->prim_repeat;
     p.fits32 = scene_fits32(s);
     p.hasHostPrims = s->has_host_prims;

@@ -394,8 +394,8 @@ extern "C" nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(
         }
         s->n_anim = n_placements;
     }
-    if (hipMalloc((void **)&s->d_stats, 16 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(s->d_stats, 0, 16 * sizeof(unsigned long long));
+    if (hipMalloc((void **)&s->d_stats, nnbvh::kSchedStatWords * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
     s->build_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return s;
 }

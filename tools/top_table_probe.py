@@ -5,7 +5,9 @@ and, under a statistics build (NNBVH_LIB=libnnbvh_hip_stats.so, python -c "from 
 build.build_stats()"), the interior lane-steps per launch and how many of them read their record from the LDS table.
 Records per second = interior lane-steps (statistics build) over the launch time (product build): run it once with
 each library and put the two beside tools/record_load_probe's figure of the same session.
-Usage: [NNBVH_LIB=...] python tools/top_table_probe.py [reps]"""
+Then the four-batch step at every top_burst of BURSTS (option "top_burst": the tagged lanes that make a wave take a
+table step) and every refill_weight of REFILLS.
+Usage: [NNBVH_LIB=...] python tools/top_table_probe.py [reps [BURSTS [REFILLS]]]   (7, 65,48,32,24,16,8,1 and 8)"""
 import os
 import sys
 
@@ -17,6 +19,8 @@ sys.path.insert(0, ROOT)
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+    bursts = [int(v) for v in (sys.argv[2] if len(sys.argv) > 2 else "65,48,32,24,16,8,1").split(",")]
+    refills = [int(v) for v in (sys.argv[3] if len(sys.argv) > 3 else "8").split(",")]
     import torch
     from nn_bvh_amd import BVHAggregate, build_tree, make_prims, raygen, scene
     cdev = torch.device("cuda", 0)
@@ -82,7 +86,58 @@ def main():
                 line += (f", interior lane-steps {lanes / 1e6:8.1f} M = {lanes / n:5.1f} per ray, from LDS {top / 1e6:7.1f} M"
                          f" = {top / max(lanes, 1):.4f}, {lanes / ms / 1e6:6.1f} G records/s at this build's time")
         print(line, flush=True)
+    if has_option:
+        agg.set_option("top_table", 1)
+        sweep(agg, work[-1], stream, reps, bursts, refills)
     agg.close()
+
+
+def sweep(agg, step, stream, reps, bursts, refills):
+    """The four-batch step at every (top_burst, refill_weight) setting: `reps` launches each, the settings interleaved
+    (one launch of each per round), median and range; under a statistics build the trips, lanes and shader cycles of the
+    table (T), interior (I), primitive (P) and refill (R) trips per launch."""
+    import torch
+    _, batches, n = step
+    try:
+        agg.set_option("top_burst", 65)
+    except Exception:  # a library from before the table steps
+        print("no top_burst option in this library", flush=True)
+        return
+    settings = [(b, w) for w in refills for b in bursts]
+    ts = {s: [] for s in settings}
+    stats = {}
+
+    def launch(s, timed):
+        agg.set_option("top_burst", s[0])
+        agg.set_option("refill_weight", s[1])
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        agg.trace_batches_device(batches, stream)
+        b.record()
+        torch.cuda.synchronize()
+        if timed:
+            ts[s].append(a.elapsed_time(b))
+    for s in settings:
+        launch(s, False)  # warm-up
+    for _ in range(reps):
+        for s in settings:
+            launch(s, True)
+    for s in settings:  # one more launch each for the counters
+        agg.sched_stats(reset=True)
+        launch(s, False)
+        stats[s] = agg.sched_stats(reset=True)
+    print(f"four-batch step, {reps} launches per setting, interleaved", flush=True)
+    for s in settings:
+        t, st = ts[s], stats[s]
+        line = f"top_burst {s[0]:2d} refill_weight {s[1]:2d}: {float(np.median(t)):7.3f} ms ({min(t):.3f} .. {max(t):.3f})"
+        if st["int_step_lanes"]:
+            for k, name in (("T", "table"), ("I", "int"), ("P", "prim"), ("R", "refill")):
+                trips, lanes, cyc = st[name + "_trips"], st[name + "_lanes"], st[name + "_cycles"]
+                line += (f" | {k} {trips / 1e6:6.2f} M trips, {lanes / max(trips, 1):4.1f} lanes, "
+                         f"{cyc / max(trips, 1):6.0f} cycles")
+            line += (f" | interior lane-steps {(st['int_step_lanes'] + st['table_lanes']) / n:5.1f} per ray, in ordinary "
+                     f"steps from LDS {st['int_top_lanes'] / n:5.1f}, in table steps {st['table_lanes'] / n:5.1f}")
+        print(line, flush=True)
 
 
 if __name__ == "__main__":
