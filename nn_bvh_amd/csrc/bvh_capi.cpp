@@ -12,6 +12,7 @@
 #include "alpha_texture_math.h"
 #include "bvh_build_gpu.h"
 #include "capi_internal.h"
+#include "top_extend.h"
 #include "top_table.h"
 
 namespace nnbvh {
@@ -897,6 +898,50 @@ int nnbvh_scene_sched_stats(nnbvh_scene *s, uint64_t out[20], int reset) {
         return NNBVH_ERR_DEVICE;
     if (reset) (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
     return NNBVH_OK;
+}
+
+// Tests only, not part of include/nnbvh.h: the LDS top table of the lean one-launch kernels (top_extend.h), as each of
+// `blocks` blocks builds it in the kernels' prologue (device_tables: blocks x *capacity records of 64 B, device_counts:
+// the records each block holds) and as the host's extend_top_table builds it from the same scene table and records
+// (host_table: *capacity records, *host_count).  A scene without a table gives counts of 0.
+int nnbvh_debug_top_table(nnbvh_scene *s, int blocks, void *device_tables, int32_t *device_counts, void *host_table,
+                          int32_t *host_count, int32_t *capacity) {
+    if (!s || blocks < 1 || blocks > 4096 || !device_tables || !device_counts || !host_table || !host_count || !capacity) {
+        set_error("debug_top_table: bad argument");
+        return NNBVH_ERR_ARG;
+    }
+    const int cap = top_debug_capacity();
+    *capacity = cap;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return NNBVH_ERR_DEVICE;
+    std::vector<WideNode> table((size_t)s->n_top);
+    std::vector<int32_t> order;
+    if (s->n_top > 0 && !hip_ok(hipMemcpy(table.data(), s->d_top, table.size() * sizeof(WideNode), hipMemcpyDeviceToHost),
+                                "hipMemcpy(top table)"))
+        return NNBVH_ERR_DEVICE;
+    const auto fetch = [&](int32_t record, WideNode *out) {
+        if (record < 0 || record >= s->n_interior) return false;
+        return hip_ok(hipMemcpy(out, s->d_wide + 4 * (size_t)record, sizeof(WideNode), hipMemcpyDeviceToHost),
+                      "hipMemcpy(top record)");
+    };
+    if (!extend_top_table(fetch, cap, &table, &order)) return NNBVH_ERR_DEVICE;
+    *host_count = (int32_t)table.size();
+    std::memcpy(host_table, table.data(), table.size() * sizeof(WideNode));
+    const size_t bytes = (size_t)blocks * (size_t)cap * sizeof(WideNode);
+    float4 *d_out = nullptr;
+    int *d_n = nullptr;
+    bool ok = hip_ok(hipMalloc((void **)&d_out, bytes), "hipMalloc(debug tables)") &&
+              hip_ok(hipMalloc((void **)&d_n, (size_t)blocks * sizeof(int)), "hipMalloc(debug counts)") &&
+              hip_ok(hipMemset(d_out, 0, bytes), "hipMemset(debug tables)") &&
+              hip_ok(launch_top_table_debug(s->d_top, s->n_top, s->d_wide, blocks, d_out, d_n, nullptr),
+                     "top table debug launch") &&
+              hip_ok(hipDeviceSynchronize(), "top table debug kernel") &&
+              hip_ok(hipMemcpy(device_tables, d_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(debug tables)") &&
+              hip_ok(hipMemcpy(device_counts, d_n, (size_t)blocks * sizeof(int), hipMemcpyDeviceToHost),
+                     "hipMemcpy(debug counts)");
+    if (d_out) (void)hipFree(d_out);
+    if (d_n) (void)hipFree(d_n);
+    return ok ? NNBVH_OK : NNBVH_ERR_DEVICE;
 }
 
 int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value) {

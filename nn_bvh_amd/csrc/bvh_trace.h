@@ -11,7 +11,7 @@
 
 namespace nnbvh {
 
-constexpr int kBlockThreads = 256;   // 4 wavefronts
+constexpr int kBlockThreads = 256;   // 4 wavefronts (the two lean one-launch instances: trace_block_threads)
 constexpr int kMaxQueues = 8;        // one ray queue per XCD
 constexpr int kQueueStrideWords = 32;  // each queue head on its own 128-B line
 constexpr int kMaxFusedBatches = 4;    // batches one mode-3 launch may cover
@@ -88,8 +88,21 @@ hipError_t launch_zero_queue(unsigned *queue, int words, hipStream_t stream);
 // ... and the same for a per-ray int32 array (candidate counts, `before`): a kernel node, not a memset
 hipError_t launch_zero_words(int32_t *words, long n, int maxBlocks, hipStream_t stream);
 
-// One launch of the instance `is` (trace_instance.h; hipErrorInvalidValue for one the library does not hold).
+// Threads per block of the instance `is`: kBlockThreads but for the two lean one-launch instances, whose larger blocks
+// share one LDS top table among more waves (bvh_trace.hip block_threads).  Grid sizes on the host side (grid_blocks,
+// the `blocks_per_cu` option, max_grid_threads) stay in units of kBlockThreads lanes; run_instance converts.
+int trace_block_threads(const TraceInstance &is);
+
+// One launch of the instance `is` (trace_instance.h; hipErrorInvalidValue for one the library does not hold) on
+// `blocks` blocks of trace_block_threads(is) threads.
 // occupancy != nullptr: do not launch, report resident blocks per CU of that instance.
 hipError_t launch_trace(const TraceInstance &is, const TraceParams &p, int blocks, hipStream_t stream, int *occupancy);
+
+// Tests only (nnbvh_debug_top_table of bvh_capi.cpp): the prologue of the lean one-launch instances alone.  Every one
+// of `blocks` blocks copies the table it built in LDS to out + block * top_debug_capacity() records and its record
+// count to nOut[block].
+int top_debug_capacity();
+hipError_t launch_top_table_debug(const float4 *top, int nTop, const float4 *wide, int blocks, float4 *out, int *nOut,
+                                  hipStream_t stream);
 
 }  // namespace nnbvh

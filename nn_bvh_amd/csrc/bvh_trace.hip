@@ -34,6 +34,7 @@
 #include "anim_math.h"
 #include "spawn_math.h"
 #include "stream_access.h"
+#include "top_extend.h"
 #include "trace_math.h"
 #include "walk_math.h"
 
@@ -157,6 +158,80 @@ constexpr int min_waves(int modew, int inst, int patch, int alpha) {
     if (alpha) return NNBVH_MINW_ALPHA;             // alpha-tested triangles
     return ((modew == 0 || modew == 3) ? NNBVH_MINW_CLOSEST : NNBVH_MINW_ANY) + (patch ? 0 : NNBVH_LEAN_EXTRA_WAVES);
 }
+// Threads per block of that instance.  The two lean one-launch instances (kTop below) run the CU's 32 waves as two
+// blocks of 1024 threads instead of eight of 256: two copies of the LDS top table per CU instead of eight leave each
+// room for top_lds_records() = 255 records instead of 63 (512: 127 records, A/B builds only).
+#ifndef NNBVH_TOP_BLOCK
+#define NNBVH_TOP_BLOCK 1024
+#endif
+constexpr int block_threads(int modew, int inst, int patch) {
+    return (modew == 3 && !inst && !patch) ? NNBVH_TOP_BLOCK : kBlockThreads;
+}
+int trace_block_threads(const TraceInstance &is) { return block_threads(is.mode, is.inst, is.patch); }
+
+// The prologue of the lean one-launch instances, for a block of BT threads: the scene's nTop records copied into s_top,
+// then the extension of top_extend.h from `wide` up to top_lds_records(BT) records, two barriers per generation (every
+// wave scans every group of pairs itself, so no ballot goes through LDS; nobody patches a word before all have
+// scanned).  Every thread of the block calls it.  Returns the records in the table.
+template <int BT>
+__device__ __forceinline__ int load_top_table(float4 *s_top, const float4 *top, int nTop, const float4 *wide) {
+    constexpr int kCap = top_lds_records(BT);
+    static_assert(kCap >= kTopRecords && kTopRecords * 4 <= BT, "one float4 per thread copies the scene's table");
+    static_assert(2 * kCap <= BT, "one (slot, child) pair per thread in a generation");
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t < nTop * 4) s_top[t] = top[t];
+    __syncthreads();  // every thread of every block, whatever the launch has to do
+    int next = nTop;
+    if constexpr (kCap > kTopRecords) {
+        float *words = reinterpret_cast<float *>(s_top);
+        int begin = 0;
+        while (next < kCap && begin < next) {  // (block-uniform; nTop == 0: no table, no extension)
+            const int end = next, nPairs = 2 * (end - begin), nGroups = (nPairs + 63) >> 6;
+            TopGroupScan scan;
+            int ref = -1;  // the reference of this thread's pair, number t
+            for (int g = 0; g < nGroups; ++g) {
+                const int pair = 64 * g + lane;
+                int r = -1;
+                if (pair < nPairs) r = __float_as_int(words[(begin + (pair >> 1)) * 16 + 12 + (pair & 1)]);
+                scan.add(g, wave, __ballot(top_is_candidate(r)));
+                ref = g == wave ? r : ref;
+            }
+            const int slot = top_is_candidate(ref) ? scan.slot(lane, next, kCap) : -1;
+            __syncthreads();
+            if (slot >= 0) {
+                const float4 *rec = wide + 4 * (long)ref;
+                const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
+                s_top[4 * slot] = q0;
+                s_top[4 * slot + 1] = q1;
+                s_top[4 * slot + 2] = q2;
+                s_top[4 * slot + 3] = q3;
+                words[(begin + (t >> 1)) * 16 + 12 + (t & 1)] = __int_as_float(kTopTag | slot);
+            }
+            __syncthreads();
+            begin = end;
+            next = next + scan.total < kCap ? next + scan.total : kCap;
+        }
+    }
+    return next;
+}
+// ... alone, for tests: block b writes its table to out + b * top_lds_records(BT) * 4 and its record count to nOut[b]
+template <int BT>
+__global__ __launch_bounds__(BT) void top_table_debug_kernel(const float4 *top, int nTop, const float4 *wide,
+                                                             float4 *out, int *nOut) {
+    constexpr int kCap = top_lds_records(BT);
+    __shared__ float4 s_top[kCap * 4];
+    const int n = load_top_table<BT>(s_top, top, nTop, wide);
+    for (int k = threadIdx.x; k < n * 4; k += BT) out[(long)blockIdx.x * kCap * 4 + k] = s_top[k];
+    if (threadIdx.x == 0) nOut[blockIdx.x] = n;
+}
+int top_debug_capacity() { return top_lds_records(NNBVH_TOP_BLOCK); }
+hipError_t launch_top_table_debug(const float4 *top, int nTop, const float4 *wide, int blocks, float4 *out, int *nOut,
+                                  hipStream_t stream) {
+    hipLaunchKernelGGL(top_table_debug_kernel<NNBVH_TOP_BLOCK>, dim3((unsigned)blocks), dim3(NNBVH_TOP_BLOCK), 0,
+                       stream, top, nTop, wide, out, nOut);
+    return hipGetLastError();
+}
+
 // INST = 2: weight of a lane waiting to enter an AnimatedPrimitive in the step selection (interior = 16); 0 = enter
 // at once inside the primitive step (the round-2 form: 11 of 64 lanes active in the interpolation)
 #ifndef NNBVH_ANIM_ENTER_WEIGHT
@@ -230,7 +305,7 @@ __device__ __forceinline__ T pick_batch(const T (&a)[kMaxFusedBatches], int b) {
 // one with the triangle-only code.  Window 8 only; no ALPHA, SOA, HOSTC or INST = 2 forms.  (WALK rides in the first
 // template argument and not as an eighth one: that would rename every existing instance.)
 template <int MODEW, int W, int INST, int PATCH, int ALPHA = 0, int SOA = 0, int HOSTC = 0>
-__global__ __launch_bounds__(kBlockThreads, min_waves(MODEW, INST, PATCH, ALPHA))
+__global__ __launch_bounds__(block_threads(MODEW, INST, PATCH), min_waves(MODEW, INST, PATCH, ALPHA))
 void trace_kernel(TraceParams p) {
     constexpr int WALK = MODEW >= 4 ? MODEW - 3 : 0;
     constexpr int MODE = WALK ? 0 : MODEW;
@@ -241,9 +316,10 @@ void trace_kernel(TraceParams p) {
     static_assert(ALPHA != 3 || (INST == 0 && W == 8 && MODE != 3), "textured alpha: flat scenes, window 8, modes 0 / 1 / 2");
     static_assert(!HOSTC || (PATCH && (MODE == 0 || MODE == 2 || (MODE == 3 && !ALPHA && W == 8)) && !SOA),
                   "candidate mode: general instances of modes 0 / 2 / 3");
+    constexpr int BT = block_threads(MODEW, INST, PATCH);
     // the stack window: entry k of a lane = (child reference, entry distance), the two words 64 dwords
     // apart so that one ds_read2st64 / ds_write2st64 with one address moves both
-    __shared__ float s_stack[kBlockThreads / 64][W][2][64];
+    __shared__ float s_stack[BT / 64][W][2][64];
     // Cold per-ray state parked in LDS ([field][lane], conflict-free) instead of VGPRs: the
     // ray index (read when the ray retires), the direction (read by the patch test only; the
     // triangle test uses the precomputed shear) and, closest hit, the current best hit
@@ -269,31 +345,32 @@ void trace_kernel(TraceParams p) {
                                    kWalkCalls = kColdWalk + 5;
     constexpr int kColdFields = kColdWalk + (WALK ? 6 : 0);
     // The lean one-launch instances keep the four hit words in VGPRs (hit0 .. hit3) and have no cold state at all: the
-    // 4 KiB go to the block's copy of the scene's top table (nnbvh_internal.h kTopRecords), from which a
-    // lane whose `cur` carries kTopTag reads its record instead of from p.wide — the same bytes.  Tagged references
-    // only come out of table records and the tagged root, and pass through the stack and its spill unchanged.
+    // LDS beside the stack windows goes to the block's top table: the scene's table (nnbvh_internal.h
+    // kTopRecords), extended by the block itself from p.wide to top_lds_records(BT) records (load_top_table above).  A
+    // lane whose `cur` carries kTopTag reads its record from there instead of from p.wide — the same bytes.  Tagged
+    // references only come out of table records and the tagged root, and pass through the stack and its spill unchanged.
     constexpr bool kTop = kLean && MODEW == 3;
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int gtid = blockIdx.x * kBlockThreads + threadIdx.x;
+    const int gtid = blockIdx.x * BT + threadIdx.x;
     float(*stk)[2][64] = s_stack[wave];
     float(*cold)[64] = nullptr;
     [[maybe_unused]] const float4 *top = nullptr;
     if constexpr (kTop) {
-        __shared__ float4 s_top[kTopRecords * 4];
-        static_assert(kTopRecords * 4 <= kBlockThreads, "one float4 per thread copies the table");
-        if ((int)threadIdx.x < p.nTop * 4) s_top[threadIdx.x] = p.top[threadIdx.x];
-        __syncthreads();  // every thread of every block, whatever the launch has to do
+        // (the alignment puts the table first in the block's LDS, ahead of the 64 KiB of stack windows: a record's four
+        // ds_read_b128 then take the lane's byte offset as it is, with immediate offsets 0 .. 48)
+        __shared__ __attribute__((aligned(1024))) float4 s_top[top_lds_records(BT) * 4];
+        load_top_table<BT>(s_top, p.top, p.nTop, p.wide);
         top = s_top;
     } else {
-        __shared__ float s_cold[kBlockThreads / 64][kColdFields > 0 ? kColdFields : 1][64];
+        __shared__ float s_cold[BT / 64][kColdFields > 0 ? kColdFields : 1][64];
         cold = s_cold[wave];
     }
     [[maybe_unused]] float hit0 = 0.0f, hit1 = 0.0f, hit2 = 0.0f, hit3 = 0.0f;  // kTop: the current best hit
     int riReg = -1;  // lean instances: the ray this lane carries, -1 = none
     if (!kLean) cold[kColdRi][lane] = __int_as_float(-1);
-    const long spillStride = (long)gridDim.x * kBlockThreads;
+    const long spillStride = (long)gridDim.x * BT;
 
     // which queue this wave drains first: its XCD's share of the batch (speed only)
     int q = 0;
@@ -669,23 +746,40 @@ void trace_kernel(TraceParams p) {
 #endif
         if constexpr (kTop) {
             // a tagged lane reads the byte copy of its record from the block's table (slot = cur without the tag: the
-            // shift drops bit 30), the others load from p.wide; both join before the arithmetic
+            // shift drops bit 30), the others load from p.wide; both join before the arithmetic.  One asm block holds
+            // both load groups, each under its lanes' exec mask, and one wait for both: the two sources write the same
+            // sixteen VGPRs in disjoint lanes, and written as two branches the compiler orders them, so that every
+            // mixed wave-step paid an LDS round trip (s_waitcnt lgkmcnt(0)) before its global loads were issued
+            // (profiles/top_table_255.txt).  The word with the references and the axis is asked for first, as before.
+            // (top's LDS address is the low half of its flat one)
             if (cur >= 0) {
                 typedef float v4f __attribute__((ext_vector_type(4)));
                 const unsigned at = (unsigned)cur << 6;
                 v4f q0, q1, q2, q3;
-                if (cur & kTopTag) {
-                    const v4f *rec = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(top) + at);
-                    q3 = rec[3];
-                    q0 = rec[0], q1 = rec[1], q2 = rec[2];
-                    // keeps these four ds_read_b128: left alone the compiler selects between the two ADDRESSES and
-                    // issues flat loads for all lanes, 64-bit address arithmetic included (measured: no faster)
-                    asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3));
-                } else {
-                    const v4f *rec = reinterpret_cast<const v4f *>(reinterpret_cast<const char *>(p.wide) + at);
-                    q3 = rec[3];
-                    q0 = rec[0], q1 = rec[1], q2 = rec[2];
-                }
+                const unsigned long long tagged = __ballot((cur & kTopTag) != 0);
+                const unsigned ldsAt = at + (unsigned)reinterpret_cast<uintptr_t>(top);
+                unsigned long long active;
+                asm volatile(
+                    "s_mov_b64 %[act], exec\n\t"
+                    "s_andn2_b64 exec, exec, %[tag]\n\t"
+                    "s_cbranch_execz 1f\n\t"
+                    "global_load_dwordx4 %[q3], %[at], %[wide] offset:48\n\t"
+                    "global_load_dwordx4 %[q0], %[at], %[wide]\n\t"
+                    "global_load_dwordx4 %[q1], %[at], %[wide] offset:16\n\t"
+                    "global_load_dwordx4 %[q2], %[at], %[wide] offset:32\n"
+                    "1:\n\t"
+                    "s_and_b64 exec, %[act], %[tag]\n\t"
+                    "s_cbranch_execz 2f\n\t"
+                    "ds_read_b128 %[q3], %[lds] offset:48\n\t"
+                    "ds_read_b128 %[q0], %[lds]\n\t"
+                    "ds_read_b128 %[q1], %[lds] offset:16\n\t"
+                    "ds_read_b128 %[q2], %[lds] offset:32\n"
+                    "2:\n\t"
+                    "s_mov_b64 exec, %[act]\n\t"
+                    "s_waitcnt vmcnt(0) lgkmcnt(0)"
+                    : [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2), [q3] "=&v"(q3), [act] "=&s"(active)
+                    : [at] "v"(at), [lds] "v"(ldsAt), [wide] "s"(p.wide), [tag] "s"(tagged)
+                    : "scc");
                 interior_math({q0.x, q0.y, q0.z, q0.w}, {q1.x, q1.y, q1.z, q1.w}, {q2.x, q2.y, q2.z, q2.w},
                               {q3.x, q3.y, q3.z, q3.w});
             }
@@ -1119,8 +1213,9 @@ static const auto kTraceTable = trace_table(std::make_index_sequence<std::size(k
 hipError_t launch_trace(const TraceInstance &is, const TraceParams &p, int blocks, hipStream_t stream, int *occupancy) {
     for (const TraceEntry &e : kTraceTable) {
         if (std::memcmp(&e.is, &is, sizeof is) != 0) continue;
-        if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, e.kernel, kBlockThreads, 0);
-        hipLaunchKernelGGL(e.kernel, dim3((unsigned)blocks), dim3(kBlockThreads), 0, stream, p);
+        const int threads = trace_block_threads(is);
+        if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, e.kernel, threads, 0);
+        hipLaunchKernelGGL(e.kernel, dim3((unsigned)blocks), dim3(threads), 0, stream, p);
         return hipGetLastError();
     }
     return hipErrorInvalidValue;

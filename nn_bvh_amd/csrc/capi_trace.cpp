@@ -11,6 +11,7 @@ using namespace nnbvh;
 // Persistent grid = what is resident at once (register/LDS limited), asked from the runtime
 // for the exact kernel instance.  The kernel needs no co-residency (no grid barrier; late
 // blocks just find less work in the queues), so a wrong answer costs speed, never results.
+// In units of kBlockThreads lanes, as the `blocks_per_cu` option: an instance with larger blocks counts for as many.
 int nnbvh::grid_blocks(nnbvh_scene *s, int mode, int candidates) {
     int per_cu = s->blocks_per_cu;
     if (per_cu <= 0) {
@@ -18,6 +19,8 @@ int nnbvh::grid_blocks(nnbvh_scene *s, int mode, int candidates) {
         if (!pick_trace_instance(scene_traits(s), mode, candidates > 0, false, &is) ||
             launch_trace(is, TraceParams{}, 0, nullptr, &per_cu) != hipSuccess || per_cu <= 0)
             per_cu = std::max(1, std::min(8, 160 / (s->window * 2)));
+        else
+            per_cu *= trace_block_threads(is) / kBlockThreads;
     }
     per_cu = std::min(per_cu, 8);
     return s->n_cus * per_cu;
@@ -54,11 +57,15 @@ static TraceParams scene_params(const nnbvh_scene *s, const Workspace *w) {
     return p;
 }
 
-// queue heads zeroed, then the instance (have: there is one) over p.n rays, on no more threads than rays (tiny batches)
+// queue heads zeroed, then the instance (have: there is one) over p.n rays, on no more threads than rays (tiny batches).
+// `blocks` counts kBlockThreads lanes (grid_blocks); the instance's own blocks cover no more lanes than that (but one
+// block at least), so the spill array (max_grid_threads = 8 such units per CU) covers every grid.
 static int run_instance(bool have, const TraceInstance &is, const TraceParams &p, int blocks, int queue_words,
                         hipStream_t stream, const char *what) {
     if (!hip_ok(launch_zero_queue(p.queue, queue_words, stream), "queue reset launch")) return NNBVH_ERR_DEVICE;
-    const int64_t need = (p.n + kBlockThreads - 1) / kBlockThreads;
+    const int threads = have ? trace_block_threads(is) : kBlockThreads;
+    blocks = std::max(1, (int)((int64_t)blocks * kBlockThreads / threads));
+    const int64_t need = (p.n + threads - 1) / threads;
     if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
     const hipError_t e = have ? launch_trace(is, p, blocks, stream, nullptr) : hipErrorInvalidValue;
     return hip_ok(e, what) ? NNBVH_OK : NNBVH_ERR_DEVICE;

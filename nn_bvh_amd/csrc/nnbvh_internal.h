@@ -101,8 +101,9 @@ constexpr int kMaxStack = 64;  // the reference's nodesToVisit[64], aggregates.c
 // The top table of a lean scene (top_table.h): byte copies of the first kTopRecords interior records in
 // breadth-first order from the root, which the lean one-launch kernels serve from LDS.  Inside the copies a reference
 // to another copied record is kTopTag | its table slot: still >= 0 ("interior"), and bit 30 is free because the lean
-// instances only run scenes with fewer than 2^26 records (scene_fits32).  63 records = 4 032 B: the 4 KiB per block
-// that the four hit words occupied.
+// instances only run scenes with fewer than 2^26 records (scene_fits32).  63 records = 4 032 B: the 4 KiB per
+// 256-thread block that the four hit words occupied.  (The kernels' larger blocks extend their LDS copy themselves:
+// top_extend.h.)
 constexpr int kTopRecords = 63;
 constexpr int32_t kTopTag = 1 << 30;
 
