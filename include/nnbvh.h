@@ -100,11 +100,12 @@ typedef struct nnbvh_linear_node {
 #define NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH_FLIPPED 15
 #define NNBVH_PRIM_ALPHATEX_TRIANGLE 16 /* a Triangle inside a GeometricPrimitive whose alpha is a FloatImageTexture with a
                                        UVMapping (textures.h:579-590): v[3] = index into the scene's alpha-texture table
-                                       (nnbvh_scene_create_with_alpha_textures).  The texture is evaluated at the hit's
+                                       (nnbvh_scene_create_with_alpha_textures; kd-trees:
+                                       nnbvh_kd_scene_create_with_alpha_textures).  The texture is evaluated at the hit's
                                        (u, v) as the reference does for the alpha test, i.e. with zero differentials:
                                        level 0 of the image only (nnbvh_alpha_texture).  Then as kind 4.
                                        kind = 16 + flipped + 2 * smooth, flipped and smooth as for kinds 4 .. 7.
-                                       Flat scenes only: two-level and kd scenes, textured alpha on patches, other
+                                       Flat BVH scenes and kd scenes: two-level scenes, textured alpha on patches, other
                                        mappings (spherical, cylindrical, planar) and other float textures (scale, mix,
                                        checkerboard, ...) stay NNBVH_PRIM_HOST */
 #define NNBVH_PRIM_ALPHATEX_TRIANGLE_FLIPPED 17
@@ -977,10 +978,42 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_attributes(const nnbvh_prim
                                                                 const float *prim_alpha, int isect_cost,
                                                                 int traversal_cost, float empty_bonus, int max_prims,
                                                                 int max_depth, int device);
+/* nnbvh_kd_scene_create_with_attributes / nnbvh_kd_scene_create_gpu_build_with_attributes plus the alpha-texture table
+ * the kinds 16 .. 19 index with v[3] (nnbvh_alpha_texture; the semantics of nnbvh_scene_create_with_alpha_textures).  A
+ * textured triangle is a triangle for all three kd builders (its v[3] is no vertex index).  Both calls make the same
+ * six device arrays (nnbvh_kd_scene_read): a textured triangle's 64-B record keeps the texture index where kind 4 keeps
+ * alpha, its three (u, v) pairs go into the 96-B attribute slots — which such a scene therefore always has —, and the
+ * scene owns the descriptor table (48 bytes per texture) and the texel pool (4 bytes per texel), which
+ * nnbvh_kd_scene_info counts among the device bytes.  uvs (2 floats per vertex) gives a textured triangle its three
+ * (u, v) pairs; uvs == NULL means the mesh has none and EVERY textured triangle takes the reference's default corners
+ * (0,0), (1,0), (1,1).  Kinds 4 .. 7 may be mixed in; alpha-tested patches (kinds 8 .. 15) beside a textured triangle
+ * may not (refused).  A table given to a scene that holds no textured triangle is kept (read 4 / 5) and changes no
+ * result: such a scene, alpha-tested patches included, traces as the call without textures makes it.  NULL +
+ * nnbvh_last_error() naming the call, before a device is looked at, for: a null or empty texture table with a textured
+ * triangle present, a texture index out of range, null texels, a width or height outside 1 .. 2^24, an unknown wrap
+ * mode, a smooth kind without normals — besides every fault of the call without textures.  The plain calls, the
+ * one-launch batches, the wavefront queue calls and the host-candidate calls all serve such a scene; the walk calls
+ * (nnbvh_kd_wavefront_walk_*) refuse it as they refuse every scene with attribute slots.  The other kd creation calls
+ * refuse kinds 16 .. 19. */
+nnbvh_kd_scene *nnbvh_kd_scene_create_with_alpha_textures(const nnbvh_kd_node *nodes, int n_nodes,
+                                                          const int32_t *prim_indices, int n_indices,
+                                                          const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                          int n_verts, const float bounds_min_max[6],
+                                                          const float *normals, const float *uvs, const float *prim_alpha,
+                                                          int device, const nnbvh_alpha_texture *textures,
+                                                          int n_textures);
+nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_alpha_textures(const nnbvh_prim *prims, int n_prims,
+                                                                    const float *verts, int n_verts,
+                                                                    const float *prim_bounds, const float *normals,
+                                                                    const float *uvs, const float *prim_alpha,
+                                                                    int isect_cost, int traversal_cost, float empty_bonus,
+                                                                    int max_prims, int max_depth, int device,
+                                                                    const nnbvh_alpha_texture *textures, int n_textures);
 /* What a kd scene holds, whichever call created it.  info: n_nodes, n_indices, n_prims, depth, device bytes,
  * has_host_prims, has_patches, has_attribute_slots.  read: `what` 0 = nodes (8 B each), 1 = primitiveIndices, 2 =
- * primitive records (64 B each), 3 = attribute slots (96 B each, scenes that have them); synchronous; NNBVH_ERR_ARG
- * when `bytes` is not the array's exact size. */
+ * primitive records (64 B each), 3 = attribute slots (96 B each, scenes that have them), 4 = alpha-texture descriptor
+ * table (48 B each), 5 = alpha texel pool (4 B each; both empty in scenes without textures); synchronous;
+ * NNBVH_ERR_ARG when `bytes` is not the array's exact size. */
 int nnbvh_kd_scene_bounds(const nnbvh_kd_scene *s, float out_min_max[6]);
 int nnbvh_kd_scene_info(const nnbvh_kd_scene *s, int64_t out[8]);
 int nnbvh_kd_scene_read(const nnbvh_kd_scene *s, int what, void *out, size_t bytes);

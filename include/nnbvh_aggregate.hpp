@@ -711,6 +711,20 @@ class HipKdTreeAggregate {
         if (!scene_) HipBVHAggregate::fatal("HipKdTreeAggregate: scene_create");
         note_patches(prims, nPrims);
     }
+    // ... whose primitives include triangles with an image-textured alpha (kinds NNBVH_PRIM_ALPHATEX_TRIANGLE*, v[3] =
+    // index into alphaTextures; nnbvh_kd_scene_create_with_alpha_textures).  uvs == nullptr: the meshes have no (u, v)
+    // and every textured triangle takes the default corners.  The texels are copied
+    HipKdTreeAggregate(const nnbvh_kd_node *nodes, int nNodes, const int32_t *primIndices, int nIndices,
+                       const nnbvh_prim *prims, int nPrims, const float *verts, int nVerts, const float boundsMinMax[6],
+                       const std::vector<nnbvh_alpha_texture> &alphaTextures, int device = 0,
+                       const float *normals = nullptr, const float *uvs = nullptr, const float *primAlpha = nullptr) {
+        for (int k = 0; k < 6; ++k) bounds_[k] = boundsMinMax[k];
+        scene_ = nnbvh_kd_scene_create_with_alpha_textures(nodes, nNodes, primIndices, nIndices, prims, nPrims, verts,
+                                                           nVerts, boundsMinMax, normals, uvs, primAlpha, device,
+                                                           alphaTextures.data(), (int)alphaTextures.size());
+        if (!scene_) HipBVHAggregate::fatal("HipKdTreeAggregate: scene_create_with_alpha_textures");
+        note_patches(prims, nPrims);
+    }
     // Bounds, tree and primitive records made on the device (nnbvh_kd_scene_create_gpu_build_with_attributes): the
     // same nodes as the building constructor's, with the primitives inside multi-primitive leaves in std::stable_sort
     // order (the scene of nnbvh_kd_build_create_stable + the from-tree constructor, byte for byte).
@@ -723,6 +737,28 @@ class HipKdTreeAggregate {
             prims.data(), (int)prims.size(), verts.data(), (int)(verts.size() / 3),
             primBounds ? primBounds->data() : nullptr, normals ? normals->data() : nullptr, uvs ? uvs->data() : nullptr,
             primAlpha ? primAlpha->data() : nullptr, isectCost, traversalCost, emptyBonus, maxPrims, maxDepth, device);
+        if (!scene) {
+            HipBVHAggregate::fatal("HipKdTreeAggregate::BuildOnDevice");
+            return nullptr;
+        }
+        std::unique_ptr<HipKdTreeAggregate> agg(new HipKdTreeAggregate(scene));
+        agg->note_patches(prims.data(), (int)prims.size());
+        return agg;
+    }
+    // ... with the alpha-texture table of the kinds NNBVH_PRIM_ALPHATEX_TRIANGLE*
+    // (nnbvh_kd_scene_create_gpu_build_with_alpha_textures): the scene of nnbvh_kd_build_create_stable + the from-tree
+    // constructor with alphaTextures, byte for byte
+    static std::unique_ptr<HipKdTreeAggregate> BuildOnDevice(
+        const std::vector<nnbvh_prim> &prims, const std::vector<float> &verts,
+        const std::vector<nnbvh_alpha_texture> &alphaTextures, int isectCost = 5, int traversalCost = 1,
+        float emptyBonus = 0.5f, int maxPrims = 1, int maxDepth = -1, int device = 0,
+        const std::vector<float> *primBounds = nullptr, const std::vector<float> *normals = nullptr,
+        const std::vector<float> *uvs = nullptr, const std::vector<float> *primAlpha = nullptr) {
+        nnbvh_kd_scene *scene = nnbvh_kd_scene_create_gpu_build_with_alpha_textures(
+            prims.data(), (int)prims.size(), verts.data(), (int)(verts.size() / 3),
+            primBounds ? primBounds->data() : nullptr, normals ? normals->data() : nullptr, uvs ? uvs->data() : nullptr,
+            primAlpha ? primAlpha->data() : nullptr, isectCost, traversalCost, emptyBonus, maxPrims, maxDepth, device,
+            alphaTextures.data(), (int)alphaTextures.size());
         if (!scene) {
             HipBVHAggregate::fatal("HipKdTreeAggregate::BuildOnDevice");
             return nullptr;

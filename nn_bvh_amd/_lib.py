@@ -104,6 +104,7 @@ EXPORTS = [
     "nnbvh_forest_ordered_prims", "nnbvh_forest_gpu_timing", "nnbvh_forest_n_levels", "nnbvh_forest_n_subtrees",
     "nnbvh_forest_destroy", "nnbvh_build_forest_create_gpu_hlbvh",
     "nnbvh_scene_create_with_alpha_textures", "nnbvh_scene_create_gpu_build_with_alpha_textures",
+    "nnbvh_kd_scene_create_with_alpha_textures", "nnbvh_kd_scene_create_gpu_build_with_alpha_textures",
 ]
 
 
@@ -315,6 +316,13 @@ def lib():
     L.nnbvh_kd_scene_create_gpu_build_with_attributes.restype = vp
     L.nnbvh_kd_scene_create_gpu_build_with_attributes.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32,
                                                                   ctypes.c_float, i32, i32, i32]
+    # ... and with the alpha-texture table of the kinds 16 .. 19 behind the same arguments
+    L.nnbvh_kd_scene_create_with_alpha_textures.restype = vp
+    L.nnbvh_kd_scene_create_with_alpha_textures.argtypes = (
+        list(L.nnbvh_kd_scene_create_with_attributes.argtypes) + [vp, i32])
+    L.nnbvh_kd_scene_create_gpu_build_with_alpha_textures.restype = vp
+    L.nnbvh_kd_scene_create_gpu_build_with_alpha_textures.argtypes = (
+        list(L.nnbvh_kd_scene_create_gpu_build_with_attributes.argtypes) + [vp, i32])
     L.nnbvh_kd_scene_bounds.restype = i32
     L.nnbvh_kd_scene_bounds.argtypes = [vp, vp]
     L.nnbvh_kd_scene_info.restype = i32

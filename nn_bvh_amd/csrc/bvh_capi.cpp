@@ -148,7 +148,7 @@ void nnbvh::fill_anim_entry(const nnbvh_animated_transform &a, float *t) {
 
 // ---- image-textured alpha (kinds 16 .. 19) ---------------------------------------------------------------------
 // Everything the kernel indexes a texture with, checked on the host before a device is looked at; `fn` names the call.
-static bool check_alpha_textures(const char *fn, const nnbvh_prim *prims, int n_prims, const float *normals,
+bool nnbvh::check_alpha_textures(const char *fn, const nnbvh_prim *prims, int n_prims, const float *normals,
                                  const nnbvh_alpha_texture *textures, int n_textures) {
     auto fault = [&](const std::string &what) {
         set_error(std::string(fn) + ": " + what);
@@ -183,9 +183,11 @@ static bool check_alpha_textures(const char *fn, const nnbvh_prim *prims, int n_
     return true;
 }
 
-// the scene's descriptor table and texel pool (alpha_texture_math.h), uploaded once; false: the scene is destroyed
-static bool attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *textures, int n_textures) {
-    if (!s || n_textures <= 0) return s != nullptr;
+// A descriptor table and texel pool (alpha_texture_math.h) made from the caller's textures and uploaded to `device`: the
+// descriptors in order, the images one after another.  false: the error text is set, and what was allocated stays in
+// the two pointers for the caller to free (they belong to a scene that is then destroyed).  Shared with the kd scenes.
+bool nnbvh::upload_alpha_textures(int device, const nnbvh_alpha_texture *textures, int n_textures, void **d_table,
+                                  float **d_texels, int64_t *n_texels) {
     std::vector<AlphaTexDesc> table((size_t)n_textures);
     uint64_t total = 0;
     for (int k = 0; k < n_textures; ++k) {
@@ -202,27 +204,35 @@ static bool attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *tex
         d.invert = t.invert ? 1 : 0;
         total += (uint64_t)t.width * (uint64_t)t.height;
     }
-    DeviceGuard guard(s->device);
-    bool ok = guard.ok && hip_ok(hipMalloc((void **)&s->d_alpha_tex, table.size() * sizeof(AlphaTexDesc)), "hipMalloc(alpha textures)") &&
-              hip_ok(hipMalloc((void **)&s->d_alpha_texels, (size_t)total * 4), "hipMalloc(alpha texels)") &&
-              hip_ok(hipMemcpy(s->d_alpha_tex, table.data(), table.size() * sizeof(AlphaTexDesc), hipMemcpyHostToDevice),
+    DeviceGuard guard(device);
+    bool ok = guard.ok && hip_ok(hipMalloc(d_table, table.size() * sizeof(AlphaTexDesc)), "hipMalloc(alpha textures)") &&
+              hip_ok(hipMalloc((void **)d_texels, (size_t)total * 4), "hipMalloc(alpha texels)") &&
+              hip_ok(hipMemcpy(*d_table, table.data(), table.size() * sizeof(AlphaTexDesc), hipMemcpyHostToDevice),
                      "hipMemcpy(alpha textures)");
     uint64_t at = 0;
     for (int k = 0; ok && k < n_textures; ++k) {
         const uint64_t n = (uint64_t)textures[k].width * (uint64_t)textures[k].height;
-        ok = hip_ok(hipMemcpy(s->d_alpha_texels + at, textures[k].texels, (size_t)n * 4, hipMemcpyHostToDevice),
+        ok = hip_ok(hipMemcpy(*d_texels + at, textures[k].texels, (size_t)n * 4, hipMemcpyHostToDevice),
                     "hipMemcpy(alpha texels)");
         at += n;
     }
-    if (!ok) {
+    *n_texels = (int64_t)total;
+    return ok;
+}
+
+// the scene's descriptor table and texel pool, uploaded once; false: the scene is destroyed
+static bool attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *textures, int n_textures) {
+    if (!s || n_textures <= 0) return s != nullptr;
+    int64_t total = 0;
+    if (!upload_alpha_textures(s->device, textures, n_textures, &s->d_alpha_tex, &s->d_alpha_texels, &total)) {
         const std::string why = nnbvh_last_error();
         nnbvh_scene_destroy(s);
         set_error(why);
         return false;
     }
     s->n_alpha_tex = n_textures;
-    s->n_alpha_texels = (int64_t)total;
-    s->device_bytes += table.size() * sizeof(AlphaTexDesc) + (size_t)total * 4;
+    s->n_alpha_texels = total;
+    s->device_bytes += (size_t)n_textures * sizeof(AlphaTexDesc) + (size_t)total * 4;
     return true;
 }
 

@@ -137,6 +137,11 @@ Workspace *workspace_for(nnbvh_scene *s, hipStream_t stream);
 // one entry of the device's animation table (layout: anim_math.h; bvh_capi.cpp)
 void fill_anim_entry(const nnbvh_animated_transform &a, float *t);
 
+// the descriptor table (AlphaTexDesc, 48 B each) and the texel pool of a checked alpha-texture table, uploaded to
+// `device` for a scene of either type (bvh_capi.cpp).  false: the error text is set; the pointers hold what was allocated
+bool upload_alpha_textures(int device, const nnbvh_alpha_texture *textures, int n_textures, void **d_table,
+                           float **d_texels, int64_t *n_texels);
+
 // ... and the kd-tree scenes' (kd_trace.h) under the same name, for the code that serves both scene types
 inline KdWorkspace *workspace_for(nnbvh_kd_scene *s, hipStream_t stream) { return kd_workspace_for(s, stream); }
 

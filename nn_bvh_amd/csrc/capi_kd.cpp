@@ -45,6 +45,8 @@ static KdParams scene_params(const nnbvh_kd_scene *s, const KdWorkspace *w) {
     p.hasHostPrims = s->has_host_prims;
     p.spill = w->spill;
     p.extras = s->d_extras;
+    p.alphaTex = (const float4 *)s->d_alpha_tex;
+    p.alphaTexels = s->d_alpha_texels;
     return p;
 }
 
@@ -67,9 +69,12 @@ static int kd_run(nnbvh_kd_scene *s, const KdWorkspace *w, hipStream_t stream, c
 }
 
 // the instance of `mode` a scene's rays run through: lean, with patches (or what else reads the ray direction), with
-// attribute arrays; each with both offset widths
+// attribute arrays (attr 1), with textured triangles among the baked records (attr 2: chosen from what was baked, not
+// from the table — a table beside alpha-tested patches and no textured triangle needs attr 1's patch recursion); each
+// with both offset widths
 static KdInstance scene_instance(const nnbvh_kd_scene *s, int mode) {
-    return {mode, (s->has_patches || s->d_extras) ? 1 : 0, s->fits32, s->d_extras ? 1 : 0, 0};
+    const int attr = s->d_extras ? ((s->has_alpha_tex && s->d_alpha_tex) ? 2 : 1) : 0;
+    return {mode, (s->has_patches || s->d_extras) ? 1 : 0, s->fits32, attr, 0};
 }
 
 // lean scenes (no patches, no attributes): their batch-mode instance has a form that reads SOA slices itself
@@ -170,6 +175,25 @@ int nnbvh::launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, co
                   kKdQueues * kKdQueueStride, "kd walk kernel launch");
 }
 
+bool nnbvh::kd_attach_alpha_textures(nnbvh_kd_scene *s, const nnbvh_alpha_texture *textures, int n_textures) {
+    if (upload_alpha_textures(s->device, textures, n_textures, &s->d_alpha_tex, &s->d_alpha_texels, &s->n_alpha_texels)) {
+        s->n_alpha_tex = n_textures;
+        return true;
+    }
+    const std::string why = nnbvh_last_error();
+    nnbvh_kd_scene_destroy(s);
+    set_error(why);
+    return false;
+}
+
+// nnbvh_kd_scene_create_with_attributes (textures == nullptr: kinds 16 .. 19 are refused) and
+// nnbvh_kd_scene_create_with_alpha_textures (the caller has checked the table with check_alpha_textures)
+static nnbvh_kd_scene *kd_scene_create(const nnbvh_kd_node *nodes, int n_nodes, const int32_t *prim_indices, int n_indices,
+                                       const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts,
+                                       const float bounds_min_max[6], const float *normals, const float *uvs,
+                                       const float *prim_alpha, int device, const nnbvh_alpha_texture *textures,
+                                       int n_textures);
+
 extern "C" {
 
 nnbvh_kd_scene *nnbvh_kd_scene_create(const nnbvh_kd_node *nodes, int n_nodes, const int32_t *prim_indices,
@@ -184,12 +208,37 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes
                                                       const nnbvh_prim *prims, int n_prims, const float *verts,
                                                       int n_verts, const float bounds_min_max[6], const float *normals,
                                                       const float *uvs, const float *prim_alpha, int device) {
+    return kd_scene_create(nodes, n_nodes, prim_indices, n_indices, prims, n_prims, verts, n_verts, bounds_min_max, normals,
+                           uvs, prim_alpha, device, nullptr, 0);
+}
+
+nnbvh_kd_scene *nnbvh_kd_scene_create_with_alpha_textures(const nnbvh_kd_node *nodes, int n_nodes,
+                                                          const int32_t *prim_indices, int n_indices,
+                                                          const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                          int n_verts, const float bounds_min_max[6],
+                                                          const float *normals, const float *uvs, const float *prim_alpha,
+                                                          int device, const nnbvh_alpha_texture *textures,
+                                                          int n_textures) {
+    if (!check_alpha_textures("nnbvh_kd_scene_create_with_alpha_textures", prims, n_prims, normals, textures, n_textures))
+        return nullptr;
+    return kd_scene_create(nodes, n_nodes, prim_indices, n_indices, prims, n_prims, verts, n_verts, bounds_min_max, normals,
+                           uvs, prim_alpha, device, textures, n_textures);
+}
+
+}  // extern "C"
+
+static nnbvh_kd_scene *kd_scene_create(const nnbvh_kd_node *nodes, int n_nodes, const int32_t *prim_indices, int n_indices,
+                                       const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts,
+                                       const float bounds_min_max[6], const float *normals, const float *uvs,
+                                       const float *prim_alpha, int device, const nnbvh_alpha_texture *textures,
+                                       int n_textures) {
     if (!nodes || n_nodes <= 0 || n_indices < 0 || (n_indices > 0 && !prim_indices) || !prims || n_prims <= 0 ||
         !verts || n_verts <= 0 || !bounds_min_max) {
         set_error("kd_scene_create: null or empty argument");
         return nullptr;
     }
-    for (int k = 0; k < n_prims; ++k)
+    const bool alpha_textures = textures && n_textures > 0;  // (else check_alpha_textures has found no kind 16 .. 19)
+    for (int k = 0; k < n_prims && !alpha_textures; ++k)
         if (is_alphatex_kind(prims[k].kind)) {
             set_error(std::string("kd_scene_create: ") + kAlphaTexElsewhere);
             return nullptr;
@@ -261,12 +310,13 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes
     // the alpha-tested kinds that read per-vertex attributes: on the device when the caller gave what they read
     // (6 more slots per primitive in a second array), else the host's as before
     auto on_device = [&](int kind) {
+        if (is_alphatex_kind(kind)) return true;  // (u, v) pairs, and the normals check_alpha_textures asked for
         if (is_smooth_alpha_kind(kind)) return normals != nullptr;
         if (is_alpha_patch_kind(kind))
             return prim_alpha && (!is_smooth_alpha_patch_kind(kind) || normals) && (!is_uv_alpha_patch_kind(kind) || uvs);
         return false;
     };
-    bool any_attr = false;
+    bool any_attr = false, any_alpha_tex = false;  // any_alpha_tex: a kPrimAlphaTex record is baked below
     for (int k = 0; k < n_prims && !any_attr; ++k) any_attr = on_device(prims[k].kind);
     std::vector<float> extras(any_attr ? (size_t)n_prims * 24 : 0, 0.0f);
     for (int k = 0; k < n_prims; ++k) {
@@ -279,17 +329,30 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes
             // (alpha-tested triangles of smooth meshes and alpha-tested patches without the arrays they read: the host's)
             flags |= kPrimHost;
             has_host = true;
-        } else if (is_triangle_kind(pr.kind) || pr.kind == NNBVH_PRIM_BILINEAR_PATCH || is_alpha_patch_kind(pr.kind)) {
-            const int nv = is_triangle_kind(pr.kind) ? 3 : 4;
+        } else if (is_triangle_kind(pr.kind) || is_alphatex_kind(pr.kind) || pr.kind == NNBVH_PRIM_BILINEAR_PATCH ||
+                   is_alpha_patch_kind(pr.kind)) {
+            const int nv = (is_triangle_kind(pr.kind) || is_alphatex_kind(pr.kind)) ? 3 : 4;
             if (attr) {
                 float *ex = &extras[(size_t)k * 24];
-                const bool smooth = is_smooth_alpha_kind(pr.kind) || is_smooth_alpha_patch_kind(pr.kind);
+                const bool smooth = is_smooth_alpha_kind(pr.kind) || is_smooth_alpha_patch_kind(pr.kind) ||
+                                    is_smooth_alphatex_kind(pr.kind);
                 for (int j = 0; j < nv && smooth; ++j)
                     if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[4 * j], normals + 3 * (size_t)pr.v[j], 12);
                 for (int j = 0; j < 4 && is_uv_alpha_patch_kind(pr.kind); ++j)
                     if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[16 + 2 * j], uvs + 2 * (size_t)pr.v[j], 8);
                 flags |= kPrimAlpha | (smooth ? kPrimSmooth : 0u) | (is_uv_alpha_patch_kind(pr.kind) ? kPrimUV : 0u);
                 if (pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED || is_flipped_alpha_patch_kind(pr.kind)) flags |= kPrimFlipN;
+                if (is_alphatex_kind(pr.kind)) {
+                    // the texture index rides in v[3] and goes to slot 2's w; the three (u, v) pairs go to slots 4 / 5:
+                    // the mesh's, or the reference's default corners (shapes.h, InteractionFromIntersection)
+                    static const float kDefaultUV[6] = {0.0f, 0.0f, 1.0f, 0.0f, 1.0f, 1.0f};
+                    for (int j = 0; j < 3; ++j) {
+                        if (!uvs) std::memcpy(&ex[16 + 2 * j], &kDefaultUV[2 * j], 8);
+                        else if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[16 + 2 * j], uvs + 2 * (size_t)pr.v[j], 8);
+                    }
+                    flags |= kPrimAlphaTex | (is_flipped_alphatex_kind(pr.kind) ? kPrimFlipN : 0u);
+                    any_alpha_tex = true;
+                }
                 has_host = true;   // a re-trace chain that does not end voids the ray
                 has_patch = true;  // the alpha test hashes the ray direction
             }
@@ -351,8 +414,12 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_with_attributes(const nnbvh_kd_node *nodes
         nnbvh_kd_scene_destroy(s);
         return nullptr;
     }
+    s->has_alpha_tex = any_alpha_tex ? 1 : 0;
+    if (alpha_textures && !kd_attach_alpha_textures(s, textures, n_textures)) return nullptr;
     return s;
 }
+
+extern "C" {
 
 void nnbvh_kd_scene_destroy(nnbvh_kd_scene *s) {
     if (!s) return;
@@ -368,6 +435,8 @@ void nnbvh_kd_scene_destroy(nnbvh_kd_scene *s) {
     if (s->d_indices) (void)hipFree(s->d_indices);
     if (s->d_prims) (void)hipFree(s->d_prims);
     if (s->d_extras) (void)hipFree(s->d_extras);
+    if (s->d_alpha_tex) (void)hipFree(s->d_alpha_tex);
+    if (s->d_alpha_texels) (void)hipFree(s->d_alpha_texels);
     delete s;
 }
 
@@ -401,7 +470,9 @@ static size_t kd_array_bytes(const nnbvh_kd_scene *s, int what) {
     case 0: return (size_t)s->n_nodes * 8;
     case 1: return (size_t)s->n_indices * 4;
     case 2: return (size_t)s->n_prims * 64;
-    default: return s->d_extras ? (size_t)s->n_prims * 96 : 0;
+    case 3: return s->d_extras ? (size_t)s->n_prims * 96 : 0;
+    case 4: return (size_t)s->n_alpha_tex * 48;
+    default: return (size_t)s->n_alpha_texels * 4;
     }
 }
 
@@ -415,7 +486,8 @@ int nnbvh_kd_scene_info(const nnbvh_kd_scene *s, int64_t out[8]) {
     out[2] = s->n_prims;
     out[3] = s->depth;
     // (the index array is never empty on the device: one entry stands in for none)
-    out[4] = (int64_t)(kd_array_bytes(s, 0) + std::max<size_t>(kd_array_bytes(s, 1), 4) + kd_array_bytes(s, 2) + kd_array_bytes(s, 3));
+    out[4] = (int64_t)(kd_array_bytes(s, 0) + std::max<size_t>(kd_array_bytes(s, 1), 4) + kd_array_bytes(s, 2) + kd_array_bytes(s, 3) +
+                       kd_array_bytes(s, 4) + kd_array_bytes(s, 5));
     out[5] = s->has_host_prims;
     out[6] = s->has_patches;
     out[7] = s->d_extras ? 1 : 0;
@@ -423,8 +495,9 @@ int nnbvh_kd_scene_info(const nnbvh_kd_scene *s, int64_t out[8]) {
 }
 
 int nnbvh_kd_scene_read(const nnbvh_kd_scene *s, int what, void *out, size_t bytes) {
-    if (!s || what < 0 || what > 3) {
-        set_error("nnbvh_kd_scene_read: null scene or unknown array (0 nodes, 1 primitiveIndices, 2 primitive records, 3 attribute slots)");
+    if (!s || what < 0 || what > 5) {
+        set_error("nnbvh_kd_scene_read: null scene or unknown array (0 nodes, 1 primitiveIndices, 2 primitive records, 3 "
+                  "attribute slots, 4 alpha-texture table, 5 alpha texel pool)");
         return NNBVH_ERR_ARG;
     }
     const size_t have = kd_array_bytes(s, what);
@@ -434,7 +507,8 @@ int nnbvh_kd_scene_read(const nnbvh_kd_scene *s, int what, void *out, size_t byt
     }
     if (have == 0) return NNBVH_OK;
     const void *src = what == 0 ? (const void *)s->d_nodes : what == 1 ? (const void *)s->d_indices
-                    : what == 2 ? (const void *)s->d_prims : (const void *)s->d_extras;
+                    : what == 2 ? (const void *)s->d_prims : what == 3 ? (const void *)s->d_extras
+                    : what == 4 ? (const void *)s->d_alpha_tex : (const void *)s->d_alpha_texels;
     ScopedDevice guard(s->device);
     hipError_t e = guard.status;
     if (e == hipSuccess) e = hipMemcpy(out, src, have, hipMemcpyDeviceToHost);

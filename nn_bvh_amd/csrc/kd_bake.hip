@@ -7,7 +7,7 @@
 //   k_kd_prim_bounds   one lane per primitive: kind and vertex indices are checked BEFORE anything is gathered with
 //                      them (the list is the caller's, unvalidated); Triangle::Bounds / BilinearPatch::Bounds in the
 //                      host's operand order; the lowest failing primitive and its reason, the six extremes of the
-//                      union and four scene flags reduced per wave, per block, then one atomic each
+//                      union and five scene flags reduced per wave, per block, then one atomic each
 //   k_kd_host_bounds   scenes with NNBVH_PRIM_HOST entries only: their rows of the caller's prim_bounds
 //   k_kd_union_pick    the union's six floats are the winners' own bit patterns (the sign of a zero is that of the
 //                      lowest-indexed primitive that reaches the extreme, as in the host's sequential union)
@@ -33,6 +33,7 @@ constexpr unsigned kFlagHostKind = 1u;  // an NNBVH_PRIM_HOST entry: the caller'
 constexpr unsigned kFlagAnyAttr = 2u;   // a kind that reads the 96-B attribute slots
 constexpr unsigned kFlagHasHost = 4u;   // nnbvh_kd_scene::has_host_prims
 constexpr unsigned kFlagHasPatch = 8u;  // nnbvh_kd_scene::has_patches
+constexpr unsigned kFlagAlphaTex = 16u;  // nnbvh_kd_scene::has_alpha_tex: a textured triangle (kPrimAlphaTex record)
 
 // what the bounds passes reduce into; uploaded as {~0, {~0 x 6}, 0, ...}
 struct KdPrep {
@@ -43,8 +44,8 @@ struct KdPrep {
     float bounds[6];
 };
 
-struct KdHave {  // which optional arrays the caller gave
-    int primBounds, normals, uvs, primAlpha;
+struct KdHave {  // which optional arrays the caller gave; alphaTex: an alpha-texture table (kinds 16 .. 19 are known)
+    int primBounds, normals, uvs, primAlpha, alphaTex;
 };
 
 // std::min / std::max as kd_build.cpp's KBox code uses them: the FIRST of equals (and of a NaN pair) is kept
@@ -59,8 +60,11 @@ __device__ __forceinline__ bool attr_on_device(int kind, bool normals, bool uvs,
         return primAlpha && (!is_smooth_alpha_patch_kind(kind) || normals) && (!is_uv_alpha_patch_kind(kind) || uvs);
     return false;
 }
-__device__ __forceinline__ int kd_vertex_count(int kind) {  // 0: not a kind with vertices
-    return is_triangle_kind(kind) ? 3 : (kind == NNBVH_PRIM_BILINEAR_PATCH || is_alpha_patch_kind(kind)) ? 4 : 0;
+// 0: not a kind with vertices.  A textured triangle (kinds 16 .. 19, scenes with an alpha-texture table) has three:
+// its v[3] is the texture index, which the host has checked
+__device__ __forceinline__ int kd_vertex_count(int kind, bool alphaTex) {
+    return (is_triangle_kind(kind) || (alphaTex && is_alphatex_kind(kind))) ? 3
+           : (kind == NNBVH_PRIM_BILINEAR_PATCH || is_alpha_patch_kind(kind)) ? 4 : 0;
 }
 
 // block-wide minimum of the seven 64-bit words of a lane, then one atomicMin per word and block
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(kBb) void k_kd_prim_bounds(const nnbvh_prim *__rest
     unsigned flags = 0;
     if (i < n) {
         const nnbvh_prim p = prims[i];
-        const int nv = kd_vertex_count(p.kind);
+        const int nv = kd_vertex_count(p.kind, have.alphaTex != 0);
         int why = kKdPrimOk;
         if (p.kind == NNBVH_PRIM_HOST) {
             // its box comes from the caller's row, in k_kd_host_bounds once that array is on the device
@@ -147,7 +151,8 @@ __global__ __launch_bounds__(kBb) void k_kd_prim_bounds(const nnbvh_prim *__rest
             }
             // the scene flags of the host bake (capi_kd.cpp)
             const bool attr = attr_on_device(p.kind, have.normals, have.uvs, have.primAlpha);
-            if ((is_smooth_alpha_kind(p.kind) || is_alpha_patch_kind(p.kind)) && !attr) flags |= kFlagHasHost;
+            if (is_alphatex_kind(p.kind)) flags |= kFlagHasHost | kFlagHasPatch | kFlagAnyAttr | kFlagAlphaTex;
+            else if ((is_smooth_alpha_kind(p.kind) || is_alpha_patch_kind(p.kind)) && !attr) flags |= kFlagHasHost;
             else if (attr || is_flat_alpha_kind(p.kind)) flags |= kFlagHasHost | kFlagHasPatch | (attr ? kFlagAnyAttr : 0u);
             else if (nv == 4) flags |= kFlagHasPatch;
         }
@@ -183,7 +188,8 @@ __global__ __launch_bounds__(kBb) void k_kd_bake(const nnbvh_prim *__restrict__ 
     if (i >= n) return;
     const nnbvh_prim p = prims[i];
     const bool attr = attr_on_device(p.kind, normals != nullptr, uvs != nullptr, primAlpha != nullptr);
-    const int nv = is_triangle_kind(p.kind) ? 3 : 4;
+    const bool tex = is_alphatex_kind(p.kind);  // (only scenes with an alpha-texture table get this far with one)
+    const int nv = (is_triangle_kind(p.kind) || tex) ? 3 : 4;
     float s[16], ex[24];
     for (int k = 0; k < 16; ++k) s[k] = 0.0f;
     for (int k = 0; k < 24; ++k) ex[k] = 0.0f;
@@ -199,6 +205,18 @@ __global__ __launch_bounds__(kBb) void k_kd_bake(const nnbvh_prim *__restrict__ 
                 for (int c = 0; c < 2; ++c) ex[16 + 2 * j + c] = uvs[2 * (long)p.v[j] + c];
             flags |= kPrimAlpha | (smooth ? kPrimSmooth : 0u) | (is_uv_alpha_patch_kind(p.kind) ? kPrimUV : 0u);
             if (p.kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED || is_flipped_alpha_patch_kind(p.kind)) flags |= kPrimFlipN;
+        }
+        if (tex) {
+            // as capi_kd.cpp bakes it: normals in slots 0 .. 2 (smooth kinds), the three (u, v) pairs — the mesh's or
+            // the default corners (0,0), (1,0), (1,1) — in slots 4 / 5, the texture index (v[3]) in slot 2's w below
+            const bool smooth = is_smooth_alphatex_kind(p.kind);
+            for (int j = 0; j < 3 && smooth; ++j)
+                for (int c = 0; c < 3; ++c) ex[4 * j + c] = normals[3 * (long)p.v[j] + c];
+            for (int j = 0; j < 3; ++j) {
+                ex[16 + 2 * j] = uvs ? uvs[2 * (long)p.v[j]] : (j == 0 ? 0.0f : 1.0f);
+                ex[16 + 2 * j + 1] = uvs ? uvs[2 * (long)p.v[j] + 1] : (j == 2 ? 1.0f : 0.0f);
+            }
+            flags |= kPrimAlpha | kPrimAlphaTex | (smooth ? kPrimSmooth : 0u) | (is_flipped_alphatex_kind(p.kind) ? kPrimFlipN : 0u);
         }
         if (is_flat_alpha_kind(p.kind)) flags |= kPrimAlpha | (p.kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED ? kPrimFlipN : 0u);
         for (int j = 0; j < nv; ++j)
@@ -300,7 +318,8 @@ nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *
     }
 
     // ---- bounds, validation, union ---------------------------------------------------------------------------
-    const KdHave have{in.prim_bounds != nullptr, in.normals != nullptr, in.uvs != nullptr, in.prim_alpha != nullptr};
+    const KdHave have{in.prim_bounds != nullptr, in.normals != nullptr, in.uvs != nullptr, in.prim_alpha != nullptr,
+                      in.textures != nullptr && in.n_textures > 0};
     hipLaunchKernelGGL(k_kd_prim_bounds, dim3(grid_of(n)), dim3(kBb), 0, stream, dPrims, n, dVerts, in.n_verts, have, dPB, dPrep);
     hipLaunchKernelGGL(k_kd_union_pick, dim3(1), dim3(64), 0, stream, dPB, dPrep);
     KB_CHECK(hipGetLastError(), "bounds kernels");
@@ -352,6 +371,12 @@ nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *
     tree.release();
     s->d_prims = (float4 *)mem.take(dRec);
     s->d_extras = (float4 *)mem.take(dExtras);
+    s->has_alpha_tex = (prep.flags & kFlagAlphaTex) ? 1 : 0;
+    // the descriptor table and the texel pool are the only arrays of such a scene that come from the host
+    if (have.alphaTex && !kd_attach_alpha_textures(s, in.textures, in.n_textures)) {
+        *error = nnbvh_last_error();
+        return nullptr;
+    }
     return s;
 }
 

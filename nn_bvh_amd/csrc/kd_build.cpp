@@ -219,7 +219,9 @@ static bool kd_prepare(const nnbvh_prim *prims, int n_prims, const float *verts,
     primBounds->resize((size_t)n_prims);
     for (int i = 0; i < n_prims; ++i) {
         const nnbvh_prim &p = prims[i];
-        const int nv = nnbvh::is_triangle_kind(p.kind) ? 3 : (p.kind == NNBVH_PRIM_BILINEAR_PATCH || nnbvh::is_alpha_patch_kind(p.kind)) ? 4 : 0;  // kinds 4 / 5: alpha-tested triangles
+        // kinds 4 .. 7: alpha-tested triangles; a textured triangle (kinds 16 .. 19, v[3] = texture index) is a triangle
+        // for the builders
+        const int nv = (nnbvh::is_triangle_kind(p.kind) || nnbvh::is_alphatex_kind(p.kind)) ? 3 : (p.kind == NNBVH_PRIM_BILINEAR_PATCH || nnbvh::is_alpha_patch_kind(p.kind)) ? 4 : 0;
         KBox b;
         if (p.kind == NNBVH_PRIM_HOST) {
             if (!prim_bounds) {
@@ -328,18 +330,22 @@ nnbvh_kd_build *nnbvh_kd_build_create_gpu(const nnbvh_prim *prims, int n_prims, 
     return out;
 }
 
-nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_attributes(const nnbvh_prim *prims, int n_prims, const float *verts,
-                                                                int n_verts, const float *prim_bounds,
-                                                                const float *normals, const float *uvs,
-                                                                const float *prim_alpha, int isect_cost,
-                                                                int traversal_cost, float empty_bonus, int max_prims,
-                                                                int max_depth, int device) {
+}  // extern "C"
+
+// nnbvh_kd_scene_create_gpu_build_with_attributes (textures == nullptr: kinds 16 .. 19 are refused) and
+// nnbvh_kd_scene_create_gpu_build_with_alpha_textures (the caller has checked the table with check_alpha_textures)
+static nnbvh_kd_scene *kd_scene_create_gpu_build(const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts,
+                                                 const float *prim_bounds, const float *normals, const float *uvs,
+                                                 const float *prim_alpha, int isect_cost, int traversal_cost,
+                                                 float empty_bonus, int max_prims, int max_depth, int device,
+                                                 const nnbvh_alpha_texture *textures, int n_textures) {
     // everything the host can judge, before any device call; the primitive list itself is judged on the device
     if (!prims || !verts || n_prims <= 0 || n_verts <= 0) {
         nnbvh::set_error("nnbvh_kd_scene_create_gpu_build: empty primitive or vertex array");
         return nullptr;
     }
-    for (int k = 0; k < n_prims; ++k)
+    const bool alpha_textures = textures && n_textures > 0;  // (else check_alpha_textures has found no kind 16 .. 19)
+    for (int k = 0; k < n_prims && !alpha_textures; ++k)
         if (nnbvh::is_alphatex_kind(prims[k].kind)) {
             nnbvh::set_error(std::string("nnbvh_kd_scene_create_gpu_build: ") + nnbvh::kAlphaTexElsewhere);
             return nullptr;
@@ -351,12 +357,39 @@ nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_attributes(const nnbvh_prim
         return nullptr;
     }
     const nnbvh::KdSceneInputs in{prims,      n_prims,        verts,     n_verts,   prim_bounds, normals, uvs,   prim_alpha,
-                                  isect_cost, traversal_cost, max_prims, max_depth, empty_bonus, device};
+                                  isect_cost, traversal_cost, max_prims, max_depth, empty_bonus, device,
+                                  alpha_textures ? textures : nullptr, alpha_textures ? n_textures : 0};
     nnbvh::KdPrimFault fault = nnbvh::kKdPrimOk;
     std::string err;
     nnbvh_kd_scene *s = nnbvh::kd_scene_create_on_device(in, &fault, &err);
     if (!s) nnbvh::set_error(fault != nnbvh::kKdPrimOk ? std::string(kPrimFaultText[fault]) : err);
     return s;
+}
+
+extern "C" {
+
+nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_attributes(const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                                int n_verts, const float *prim_bounds,
+                                                                const float *normals, const float *uvs,
+                                                                const float *prim_alpha, int isect_cost,
+                                                                int traversal_cost, float empty_bonus, int max_prims,
+                                                                int max_depth, int device) {
+    return kd_scene_create_gpu_build(prims, n_prims, verts, n_verts, prim_bounds, normals, uvs, prim_alpha, isect_cost,
+                                     traversal_cost, empty_bonus, max_prims, max_depth, device, nullptr, 0);
+}
+
+nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build_with_alpha_textures(const nnbvh_prim *prims, int n_prims,
+                                                                    const float *verts, int n_verts,
+                                                                    const float *prim_bounds, const float *normals,
+                                                                    const float *uvs, const float *prim_alpha,
+                                                                    int isect_cost, int traversal_cost, float empty_bonus,
+                                                                    int max_prims, int max_depth, int device,
+                                                                    const nnbvh_alpha_texture *textures, int n_textures) {
+    if (!nnbvh::check_alpha_textures("nnbvh_kd_scene_create_gpu_build_with_alpha_textures", prims, n_prims, normals,
+                                     textures, n_textures))
+        return nullptr;
+    return kd_scene_create_gpu_build(prims, n_prims, verts, n_verts, prim_bounds, normals, uvs, prim_alpha, isect_cost,
+                                     traversal_cost, empty_bonus, max_prims, max_depth, device, textures, n_textures);
 }
 
 nnbvh_kd_scene *nnbvh_kd_scene_create_gpu_build(const nnbvh_prim *prims, int n_prims, const float *verts, int n_verts,

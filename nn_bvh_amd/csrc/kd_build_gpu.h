@@ -80,6 +80,10 @@ struct KdSceneInputs {
     int isect_cost, traversal_cost, max_prims, max_depth;   // max_depth resolved and checked by the caller
     float empty_bonus;
     int device;                                             // checked by the caller
+    // the alpha-texture table the kinds 16 .. 19 index with v[3], checked by the caller (check_alpha_textures); null:
+    // the caller has refused those kinds
+    const nnbvh_alpha_texture *textures;
+    int n_textures;
 };
 
 // Triangles in, traceable kd scene out; the tree never visits the host (kd_bake.hip).  nullptr with *fault set for a

@@ -65,11 +65,16 @@ struct KdParams {
     // the per-item arrays of the walk (walk_math.h).  One batch; a lane's ray tag is its work item
     MeshView wMesh;
     WalkParams walk;
+    // image-textured alpha (the ATTR = 2 instances), appended again: the scene's descriptor table (three 16-B slots per
+    // texture, AlphaTexDesc of alpha_texture_math.h) and its texel pool.  A kPrimAlphaTex triangle keeps the texture
+    // index in slot 2's w and its (u, v) pairs in slots 4 / 5 of its extras: {u0, v0, u1, v1} {u2, v2, 0, 0}
+    const float4 *alphaTex;
+    const float *alphaTexels;
 };
 
 // One instance of kd_trace_kernel (kd_trace.hip explains the template parameters of the same names; the window W
-// follows from patch).  The library holds modes 0 / 1 x {lean, patch, patch + attr} x o32, mode 2 the same x hostc,
-// mode 3 lean x o32 and the walk modes 4 / 5 x {lean, patch} x o32.
+// follows from patch).  The library holds modes 0 / 1 x {lean, patch, patch + attr 1, patch + attr 2} x o32, mode 2 the
+// same x hostc, mode 3 lean x o32 and the walk modes 4 / 5 x {lean, patch} x o32.
 struct KdInstance {
     int mode, patch, o32, attr, hostc;
 };
@@ -133,6 +138,15 @@ struct nnbvh_kd_scene {
     int pair_one_launch = 0;  // 1: closest_and_shadow as ONE batch-mode launch over both queues (0: the two calls)
     std::mutex mu;
     std::map<hipStream_t, nnbvh::KdWorkspace> workspaces;
+    // image-textured alpha (kinds 16 .. 19): descriptor table (AlphaTexDesc, alpha_texture_math.h) and texel pool, or
+    // null: the caller's table, attached whenever one was given.  has_alpha_tex: a kPrimAlphaTex record was baked —
+    // such a scene has attribute slots (d_extras), a table and no alpha-tested patch, and runs the ATTR = 2 instances.
+    // A scene with a table but no textured triangle runs the instances it would run without the table
+    void *d_alpha_tex = nullptr;
+    float *d_alpha_texels = nullptr;
+    int n_alpha_tex = 0;
+    int64_t n_alpha_texels = 0;
+    int has_alpha_tex = 0;
 };
 
 namespace nnbvh {
@@ -174,6 +188,10 @@ int kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, con
 // The queue-head reset node and ONE launch of a walk instance.  The caller has checked the arguments
 // (a scene without attribute arrays, a mesh without an instance table), made the scene's device current and holds s->mu.
 int launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const WalkJob &walk);
+
+// The descriptor table and texel pool of a checked alpha-texture table (n_textures > 0) uploaded and attached to a
+// scene either creation route has made (capi_kd.cpp).  false: the scene is destroyed, the error text says why.
+bool kd_attach_alpha_textures(nnbvh_kd_scene *s, const nnbvh_alpha_texture *textures, int n_textures);
 // slot 0..KdWorkspace::kWalk-1 of the workspace's walk arrays, grown to `bytes`
 bool kd_walk_scratch(KdWorkspace *w, int slot, size_t bytes, void **out);
 

@@ -20,6 +20,7 @@
 #include "../../include/nnbvh.h"
 #include "nnbvh_internal.h"
 #include "trace_math.h"
+#include "alpha_texture_math.h"
 #include "spawn_math.h"
 #include "kd_trace.h"
 #include "walk_math.h"
@@ -81,6 +82,12 @@ constexpr int kKdLeaf = -2;          // lane is walking the primitives of a leaf
 // byte offsets from a scalar base (no 64-bit shift / add per fetch).
 // ATTR = 1 (with PATCH = 1): the scene holds alpha-tested triangles of smooth meshes or alpha-tested bilinear patches,
 // whose re-trace reads per-vertex attributes from p.extras (bvh_trace.hip's ALPHA = 1 smooth / ALPHA = 2 code)
+// ATTR = 2 (with PATCH = 1): the scene holds triangles whose alpha is an image texture (kPrimAlphaTex records; the
+// creation calls refuse alpha-tested patches beside them, so the patch recursion is not compiled in; a scene that has
+// a table but no such triangle runs the ATTR = 0 / 1 instances).  The ATTR = 1 triangle path
+// with, for such a triangle, alpha = FloatImageTexture::Evaluate at the hit's (u, v) (alpha_texture_math.h: the (u, v)
+// pairs from slots 4 / 5 of the primitive's extras, the descriptor from p.alphaTex, the texels from p.alphaTexels)
+// instead of the constant in slot 2 (bvh_trace.hip's ALPHA = 3 code)
 // HOSTC = 1 (MODE 2 only, scenes with host-only primitives): candidate mode.  A host-only primitive does not void the
 // ray: its id goes to the ray's list (p.bHcPrim / p.bHcInst of the lane's batch at ray * K, traversal order, the count
 // in the kColdHost slot) unless it stands there already — a kd-tree holds a primitive in every leaf its box overlaps
@@ -433,7 +440,25 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                             // GeometricPrimitive::Intersect / IntersectP with a constant alpha (cpu/primitive.cpp:
                             // 57-70, 79-81), as in the BVH kernels; scenes with such primitives run the PATCH
                             // instances, which keep the ray direction
-                            const float a = s2.w;
+                            [[maybe_unused]] float aTex = 0.0f;
+                            if constexpr (ATTR == 2) {
+                                // alpha.Evaluate(si->intr) of a FloatImageTexture: the (u, v) slots, the descriptor and
+                                // the texels are read here, on a hit only, and are dead before the normals are fetched
+                                // below
+                                if (flags & kPrimAlphaTex) {
+                                    const float4 *uvp = p.extras + 6 * (long)leafIdx + 4;
+                                    const float4 uva = uvp[0], uvb = uvp[1];
+                                    const float4 *dp = p.alphaTex + 3 * (long)__float_as_int(s2.w);
+                                    const float4 d0 = dp[0], d1 = dp[1], d2 = dp[2];
+                                    const AlphaTexDesc desc = {__float_as_uint(d0.x), __float_as_uint(d0.y),
+                                                               __float_as_int(d0.z), __float_as_int(d0.w),
+                                                               __float_as_int(d1.x), __float_as_int(d1.y), d1.z, d1.w,
+                                                               d2.x, d2.y, d2.z, __float_as_int(d2.w)};
+                                    aTex = alpha_texture_eval(x0, x1, x2, uva.x, uva.y, uva.z, uva.w, uvb.x, uvb.y, desc,
+                                                              p.alphaTexels);
+                                }
+                            }
+                            const float a = (ATTR == 2 && (flags & kPrimAlphaTex)) ? aTex : s2.w;
                             if (a < 1) {
                                 const float u = (a <= 0) ? 1.f : hash_float_6f(r.o, d);
                                 if (u > a) {
@@ -460,7 +485,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
                     } else {
                         const float4 s3 = rec[3];
                         x2 = 0.0f;
-                        if constexpr (ATTR != 0) {
+                        if constexpr (ATTR == 1) {
                             // GeometricPrimitive::Intersect around a BilinearPatch: the recursion of cpu/primitive.cpp:
                             // 63-69 followed for up to three re-traces, as in bvh_trace.hip (ALPHA = 2)
                             constexpr int kAlphaPatchDepth = 3;
@@ -623,6 +648,9 @@ static const KdEntry kKdInstances[] = {
     // ... and the candidate-mode twins of the record form
     kd_entry<2, 0, 0, 0, 1>(), kd_entry<2, 1, 0, 0, 1>(), kd_entry<2, 1, 0, 1, 1>(),
     kd_entry<2, 0, 1, 0, 1>(), kd_entry<2, 1, 1, 0, 1>(), kd_entry<2, 1, 1, 1, 1>(),
+    // image-textured alpha (ATTR = 2): closest / any hit, batches, candidate-mode batches; without and with 32-bit offsets
+    kd_entry<0, 1, 0, 2>(), kd_entry<1, 1, 0, 2>(), kd_entry<2, 1, 0, 2>(), kd_entry<2, 1, 0, 2, 1>(),
+    kd_entry<0, 1, 1, 2>(), kd_entry<1, 1, 1, 2>(), kd_entry<2, 1, 1, 2>(), kd_entry<2, 1, 1, 2, 1>(),
     // the walk instances: IntersectShadowTr's, then IntersectOneRandom's
     kd_entry<4, 0, 0>(), kd_entry<4, 1, 0>(), kd_entry<4, 0, 1>(), kd_entry<4, 1, 1>(),
     kd_entry<5, 0, 0>(), kd_entry<5, 1, 0>(), kd_entry<5, 0, 1>(), kd_entry<5, 1, 1>()};

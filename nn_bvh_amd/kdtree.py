@@ -55,11 +55,15 @@ class KdTreeAggregate:
         self._h = handle
         self.bounds = bounds
         self.device = device
+        self.alpha_textures = None  # the ctypes table of a scene with image-textured alpha
 
     @classmethod
-    def from_tree(cls, nodes, prim_indices, prims, verts, bounds, device=0, normals=None, uvs=None, prim_alpha=None):
+    def from_tree(cls, nodes, prim_indices, prims, verts, bounds, device=0, normals=None, uvs=None, prim_alpha=None,
+                  alpha_textures=None):
         """normals / uvs (per vertex) and prim_alpha (per entry of prims): what the alpha-tested kinds of smooth meshes
-        and the alpha-tested patches read; without them such primitives are the host's (void records)."""
+        and the alpha-tested patches read; without them such primitives are the host's (void records).
+        alpha_textures: a sequence of AlphaTexture, the table the kinds 16 .. 19 index with v[3]
+        (nnbvh_kd_scene_create_with_alpha_textures); uvs gives them their (u, v) (None: the default corners)."""
         nodes = np.ascontiguousarray(nodes, KD_NODE_DTYPE)
         idx = np.ascontiguousarray(prim_indices, np.int32)
         prims = np.ascontiguousarray(prims, PRIM_DTYPE)
@@ -69,22 +73,31 @@ class KdTreeAggregate:
         uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(len(verts), 2)
         pa = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(len(prims))
         opt = lambda a: ptr(a) if a is not None else None  # noqa: E731
-        h = _lib.lib().nnbvh_kd_scene_create_with_attributes(
-            ptr(nodes), len(nodes), ptr(idx) if len(idx) else None, len(idx), ptr(prims), len(prims), ptr(verts),
-            len(verts), ptr(bounds), opt(nrm), opt(uv), opt(pa), device)
+        args = (ptr(nodes), len(nodes), ptr(idx) if len(idx) else None, len(idx), ptr(prims), len(prims), ptr(verts),
+                len(verts), ptr(bounds), opt(nrm), opt(uv), opt(pa), device)
+        if alpha_textures is not None:
+            table, n_tex = _lib.alpha_texture_table(alpha_textures)
+            h = _lib.lib().nnbvh_kd_scene_create_with_alpha_textures(*args, table, n_tex)
+        else:
+            table = None
+            h = _lib.lib().nnbvh_kd_scene_create_with_attributes(*args)
         if not h:
             raise _lib.NNBVHError(f"nnbvh_kd_scene_create failed: {_lib.last_error()}")
-        return cls(h, bounds, device)
+        self = cls(h, bounds, device)
+        self.alpha_textures = table  # kept alive with the scene, as BVHAggregate keeps its own
+        return self
 
     @classmethod
-    def build(cls, prims, verts, device=0, normals=None, uvs=None, prim_alpha=None, **kw):
+    def build(cls, prims, verts, device=0, normals=None, uvs=None, prim_alpha=None, alpha_textures=None, **kw):
         t = build_kd_tree(prims, verts, **kw)
-        return cls.from_tree(t.nodes, t.prim_indices, prims, verts, t.bounds, device, normals, uvs, prim_alpha)
+        return cls.from_tree(t.nodes, t.prim_indices, prims, verts, t.bounds, device, normals, uvs, prim_alpha,
+                             alpha_textures)
 
     @classmethod
     def build_on_device(cls, prims, verts, device=0, normals=None, uvs=None, prim_alpha=None, prim_bounds=None,
-                        isect_cost=5, traversal_cost=1, empty_bonus=0.5, max_prims=1, max_depth=-1):
-        """nnbvh_kd_scene_create_gpu_build_with_attributes: primitive bounds, the tree and the primitive records are
+                        isect_cost=5, traversal_cost=1, empty_bonus=0.5, max_prims=1, max_depth=-1, alpha_textures=None):
+        """nnbvh_kd_scene_create_gpu_build_with_attributes (with alpha_textures, a sequence of AlphaTexture:
+        nnbvh_kd_scene_create_gpu_build_with_alpha_textures): primitive bounds, the tree and the primitive records are
         made on the device and stay there.  The scene of build_kd_tree(where="host_stable") + from_tree, byte for byte:
         inside multi-primitive leaves the primitives stand in std::stable_sort order, not in the libstdc++ std::sort
         order of build() (the leaf-order note of build_kd_tree).  prim_bounds: read for host-only primitives only."""
@@ -96,13 +109,19 @@ class KdTreeAggregate:
         pb = None if prim_bounds is None else np.ascontiguousarray(prim_bounds, np.float32).reshape(len(prims), 6)
         opt = lambda a: ptr(a) if a is not None and a.size else None  # noqa: E731
         L = _lib.lib()
-        h = L.nnbvh_kd_scene_create_gpu_build_with_attributes(
-            opt(prims), len(prims), opt(verts), len(verts), opt(pb), opt(nrm), opt(uv), opt(pa), isect_cost,
-            traversal_cost, ctypes.c_float(empty_bonus), max_prims, max_depth, device)
+        args = (opt(prims), len(prims), opt(verts), len(verts), opt(pb), opt(nrm), opt(uv), opt(pa), isect_cost,
+                traversal_cost, ctypes.c_float(empty_bonus), max_prims, max_depth, device)
+        if alpha_textures is not None:
+            table, n_tex = _lib.alpha_texture_table(alpha_textures)
+            h = L.nnbvh_kd_scene_create_gpu_build_with_alpha_textures(*args, table, n_tex)
+        else:
+            table = None
+            h = L.nnbvh_kd_scene_create_gpu_build_with_attributes(*args)
         if not h:
             raise _lib.NNBVHError(f"nnbvh_kd_scene_create_gpu_build failed: {_lib.last_error()}")
         bounds = np.zeros(6, np.float32)
         agg = cls(h, bounds, device)
+        agg.alpha_textures = table
         check(L.nnbvh_kd_scene_bounds(h, ptr(bounds)), "nnbvh_kd_scene_bounds")
         return agg
 
@@ -118,12 +137,17 @@ class KdTreeAggregate:
     def read(self, what):
         """nnbvh_kd_scene_read: the scene's device arrays as numpy arrays.  what: 0 / "nodes" (KD_NODE_DTYPE), 1 /
         "prim_indices" (int32), 2 / "prims" (float32 [n, 16]: the 64-B records), 3 / "attributes" (float32 [n, 24]:
-        the 96-B slots; empty in scenes without them)."""
-        what = {"nodes": 0, "prim_indices": 1, "prims": 2, "attributes": 3}.get(what, what)
+        the 96-B slots; empty in scenes without them), 4 / "alpha_textures" (uint32 [n, 12]: the 48-B descriptors), 5 /
+        "alpha_texels" (float32: the texel pool; both empty in scenes without an alpha-texture table)."""
+        what = {"nodes": 0, "prim_indices": 1, "prims": 2, "attributes": 3, "alpha_textures": 4,
+                "alpha_texels": 5}.get(what, what)
         i = self.info()
+        table = self.alpha_textures if self.alpha_textures is not None else ()
         rows, dtype, width = [(i["n_nodes"], KD_NODE_DTYPE, 1), (i["n_indices"], np.int32, 1),
                               (i["n_prims"], np.float32, 16),
-                              (i["n_prims"] if i["has_attribute_slots"] else 0, np.float32, 24)][what]
+                              (i["n_prims"] if i["has_attribute_slots"] else 0, np.float32, 24),
+                              (len(table), np.uint32, 12),
+                              (sum(t.width * t.height for t in table), np.float32, 1)][what]
         out = np.zeros(rows * width, dtype)
         check(_lib.lib().nnbvh_kd_scene_read(self._h, what, ptr(out) if out.size else None, out.nbytes),
               "nnbvh_kd_scene_read")
@@ -258,8 +282,11 @@ class KdTreeAggregate:
 def prim_bounds_of(prims, verts):
     """Per-primitive bounds (Triangle::Bounds / BilinearPatch::Bounds: min / max over the vertices)."""
     prims = np.asarray(prims)
-    v = np.asarray(verts, np.float32)[prims["v"]]
-    tri = np.isin(prims["kind"], (0, 4, 5))[:, None, None]  # triangles and alpha-tested triangles
+    # triangles, alpha-tested triangles and triangles with an image-textured alpha: v[3] is no vertex index there (the
+    # bits of an alpha, a texture number) and is not followed
+    is_tri = np.isin(prims["kind"], (0, 4, 5, 6, 7, 16, 17, 18, 19))
+    v = np.asarray(verts, np.float32)[np.where(is_tri[:, None], prims["v"][:, [0, 1, 2, 0]], prims["v"])]
+    tri = is_tri[:, None, None]
     lo = np.where(tri, v[:, :3].min(1, keepdims=True), v.min(1, keepdims=True))[:, 0]
     hi = np.where(tri, v[:, :3].max(1, keepdims=True), v.max(1, keepdims=True))[:, 0]
     return lo.astype(np.float32), hi.astype(np.float32)

@@ -5,6 +5,8 @@ tools/profile_bench.sh --script tools/profile_workloads.py <which> for rocprofv3
     alpha     1 M-triangle soup, 70 % alpha-tested (kinds 4 / 5): ALPHA = 1 instances
     alpha_tex the same soup with the alpha-tested triangles textured (kinds 16 / 17, one 1 024 x 1 024 texture): ALPHA = 3
               instances, and the constant-alpha soup in the same process, runs alternated: median and min .. max
+    alpha_tex_kd  the alpha_tex soup as kd-tree scenes (KdTreeAggregate.build_on_device): the ATTR = 2 instances of
+              kd_trace_kernel against the constant-alpha kd scene (PATCH = 1), the same process, runs alternated
     inst      400 placements of one 33 K-triangle killeroo (tools/bench_instances.py's scene): INST = 1
     anim      36 placements of a small mesh, 24 of them AnimatedPrimitives (tests/test_animated.py's scene): INST = 2
     tr        IntersectShadowTr and IntersectOneRandom over 2 M items on sheets of interface surfaces: str_* / or_*
@@ -89,8 +91,9 @@ def main():
         agg = BVHAggregate.from_tree(tree.nodes, tree.ordered_prims, verts, normals=normals, prim_alpha=prim_alpha)
         rays = scene.random_rays(4_000_000, verts.min(0) - 2, verts.max(0) + 2, 34)
         trace_three(torch, agg, rays, which)
-    elif which == "alpha_tex":
+    elif which in ("alpha_tex", "alpha_tex_kd"):
         from nn_bvh_amd import AlphaTexture
+        from nn_bvh_amd.kdtree import KdTreeAggregate
         verts, prims = ss.random_soup(1_000_000, 0, 32, extent=60.0, size=0.9)
         rng = np.random.default_rng(33)
         prims = prims.copy()
@@ -103,8 +106,12 @@ def main():
         textured["kind"] = np.where(kinds == 0, 0, kinds + 12)
         textured["v"][:, 3] = 0
         image = rng.choice(values, (1024, 1024))  # the same alphas, now per texel; no (u, v): the default corners
-        aggs = {"constant": BVHAggregate.build_on_device(prims, verts, 4, "sah"),
-                "textured": BVHAggregate.build_on_device(textured, verts, 4, "sah", alpha_textures=[AlphaTexture(image)])}
+        if which == "alpha_tex_kd":  # KdTreeAggregate::Create's defaults (one primitive per leaf)
+            aggs = {"constant": KdTreeAggregate.build_on_device(prims, verts),
+                    "textured": KdTreeAggregate.build_on_device(textured, verts, alpha_textures=[AlphaTexture(image)])}
+        else:
+            aggs = {"constant": BVHAggregate.build_on_device(prims, verts, 4, "sah"),
+                    "textured": BVHAggregate.build_on_device(textured, verts, 4, "sah", alpha_textures=[AlphaTexture(image)])}
         rays = scene.random_rays(4_000_000, verts.min(0) - 2, verts.max(0) + 2, 34)
         n = len(rays)
         d_r = torch.from_numpy(rays.view(np.uint8).reshape(-1)).cuda()
@@ -125,14 +132,14 @@ def main():
                     if it:
                         times[k, c].append(e0.elapsed_time(e1))
         for (k, c), ts in times.items():
-            print(f"alpha_tex {k} {c}: median {np.median(ts):.3f} ms, {min(ts):.3f} .. {max(ts):.3f} ms over {len(ts)} "
+            print(f"{which} {k} {c}: median {np.median(ts):.3f} ms, {min(ts):.3f} .. {max(ts):.3f} ms over {len(ts)} "
                   f"alternated runs of {n} rays", flush=True)
         from nn_bvh_amd import HIT_DTYPE
         for k, a in aggs.items():
             calls["closest"](a)
             torch.cuda.synchronize()
             h = d_h.cpu().numpy().view(HIT_DTYPE)
-            print(f"alpha_tex {k}: hit {np.mean(h['prim'] >= 0):.2f}, V {h['nodes_visited'].mean():.1f}, "
+            print(f"{which} {k}: hit {np.mean(h['prim'] >= 0):.2f}, V {h['nodes_visited'].mean():.1f}, "
                   f"T {h['prim_tests'].mean():.2f}")
     elif which == "anim":
         import test_animated as ta
