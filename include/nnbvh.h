@@ -1043,7 +1043,12 @@ int nnbvh_kd_trace_batches_device(nnbvh_kd_scene *s, const nnbvh_batch *batches,
 /* tuning knobs (speed only, never results), as nnbvh_scene_set_option: "read_soa" (lean scenes: the kernel reads a
  * queue's SOA slices itself; 0, the default: gathered into records first), "pair_one_launch" (closest_and_shadow traces
  * both queues in one launch; 0, the default: the two calls one after the other).  The defaults follow the measurement
- * rule of DESIGN.md §5.7: a new form becomes the default once a recorded run shows it ahead by more than the spread. */
+ * rule of DESIGN.md §5.7: a new form becomes the default once a recorded run shows it ahead by more than the spread.
+ * "offsets32" (0/1, speed only like the others): 0 runs the kernel instances that reach nodes, primitive records and
+ * indices through 64-bit addressing although the scene fits 32-bit byte offsets; 1, the default, restores the width
+ * computed from the scene's sizes.  The wide instances are correct for every scene, so the key changes speed, never
+ * results, and it can never force 32-bit offsets onto a scene that does not fit them.  Any other value is NNBVH_ERR_ARG
+ * (checked before the scene is looked at). */
 int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value);
 int nnbvh_kd_wavefront_intersect_closest(nnbvh_kd_scene *s, int32_t max_rays, const nnbvh_ray_soa *ray_queue,
                                          const int32_t *d_size, const uint8_t *d_prim_class, int64_t n_prim_class,
@@ -1194,8 +1199,22 @@ int nnbvh_wavefront_walk_one_random(nnbvh_scene *s, const nnbvh_shading_mesh *m,
  * always takes one primitive step), "fused_batches" (0/1: nnbvh_trace_batches_device as one launch where
  * the batches allow it), "top_table" (0/1: the lean one-launch kernels serve the scene's top records from
  * LDS), "top_burst" (1..65: a wavefront of those kernels with at least this many lanes at a record of the LDS
- * table advances them in a table step of their own, which loads nothing from memory; 65 = never).  Returns NNBVH_ERR_ARG for unknown keys. */
+ * table advances them in a table step of their own, which loads nothing from memory; 65 = never), "offsets32" (0/1:
+ * 0 makes the scene behave as if its arrays did not fit 32-bit byte offsets — never the lean instances, no LDS top
+ * table, wavefront queues gathered into records; 1, the default, restores what the scene's sizes say.  The general
+ * instances are correct for every scene, so this too changes speed, never results; it can never force 32-bit offsets
+ * onto a scene that does not fit them; a value other than 0 / 1 is NNBVH_ERR_ARG, checked before the scene is looked
+ * at).  Returns NNBVH_ERR_ARG for unknown keys. */
 int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value);
+
+/* diagnostics: the launch ledger.  How often each trace-kernel instance has been enqueued in this process (a launch
+ * recorded into a graph counts once, at capture; occupancy queries do not count).  family 0: the BVH trace instances,
+ * each row of desc = {mode, window, inst, patch, alpha, soa, hostc}; family 1: the kd-tree ones, each row = {mode, patch,
+ * o32, attr, hostc, 0, 0}.  Fills up to `capacity` rows of desc (7 ints each) and counts (either may be NULL) and returns
+ * the number of instances of the family; reset != 0 zeroes the family's counts after reading them.  The counts are
+ * process-wide relaxed atomics: exact when no other thread launches meanwhile.  Needs no device and no scene.
+ * A negative return is -NNBVH_ERR_ARG (unknown family, negative capacity, capacity > 0 with both arrays NULL). */
+int nnbvh_instance_launches(int family, int32_t *desc, uint64_t *counts, int capacity, int reset);
 
 /* diagnostics: wavefront scheduling statistics accumulated since the last reset —
  * out = {interior trips, interior lanes, primitive trips, primitive lanes, refill trips,

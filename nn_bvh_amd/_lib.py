@@ -105,6 +105,7 @@ EXPORTS = [
     "nnbvh_forest_destroy", "nnbvh_build_forest_create_gpu_hlbvh",
     "nnbvh_scene_create_with_alpha_textures", "nnbvh_scene_create_gpu_build_with_alpha_textures",
     "nnbvh_kd_scene_create_with_alpha_textures", "nnbvh_kd_scene_create_gpu_build_with_alpha_textures",
+    "nnbvh_instance_launches",
 ]
 
 
@@ -408,8 +409,45 @@ def lib():
         kd.argtypes = getattr(L, "nnbvh_" + name).argtypes
     L.nnbvh_scene_sched_stats.restype = i32
     L.nnbvh_scene_sched_stats.argtypes = [vp, vp, i32]
+    L.nnbvh_instance_launches.restype = i32
+    L.nnbvh_instance_launches.argtypes = [i32, vp, vp, i32, i32]
     _lib = L
     return L
+
+
+FAMILY_BVH, FAMILY_KD = 0, 1  # nnbvh_instance_launches
+
+
+def instance_launches(family, reset=False):
+    """The launch ledger of one kernel family -> {instance tuple: launches so far in this process}.  family FAMILY_BVH:
+    (mode, window, inst, patch, alpha, soa, hostc) of trace_kernel; FAMILY_KD: (mode, patch, o32, attr, hostc) of
+    kd_trace_kernel.  Needs no device."""
+    L = lib()
+    n = L.nnbvh_instance_launches(family, None, None, 0, 0)
+    if n < 0:
+        raise NNBVHError(f"nnbvh_instance_launches failed (status {-n}): {last_error()}")
+    desc, counts = np.zeros((n, 7), np.int32), np.zeros(n, np.uint64)
+    L.nnbvh_instance_launches(family, ptr(desc), ptr(counts), n, int(bool(reset)))
+    width = 7 if family == FAMILY_BVH else 5
+    return {tuple(int(x) for x in row[:width]): int(c) for row, c in zip(desc, counts)}
+
+
+class LaunchLedger:
+    """`with LaunchLedger(family) as led:` ... led.launched is then {instance tuple: launches made inside the block},
+    the instances with none left out."""
+
+    def __init__(self, family):
+        self.family = family
+        self.launched = {}
+
+    def __enter__(self):
+        self._before = instance_launches(self.family)
+        return self
+
+    def __exit__(self, *exc):
+        after = instance_launches(self.family)
+        self.launched = {k: v - self._before[k] for k, v in after.items() if v != self._before[k]}
+        return False
 
 
 def last_error():

@@ -413,6 +413,9 @@ class BVHAggregate:
             pass
 
     def set_option(self, key, value):
+        """nnbvh_scene_set_option (include/nnbvh.h lists the keys): speed only, never results.  "offsets32" 0 makes the
+        scene behave as if it did not fit 32-bit offsets (never the lean instances, no LDS top table: the general
+        instances, correct for every scene); 1 restores what the scene's sizes say."""
         check(_lib.lib().nnbvh_scene_set_option(self._h, key.encode(), int(value)),
               f"set_option({key})")
 

@@ -954,7 +954,21 @@ int nnbvh_debug_top_table(nnbvh_scene *s, int blocks, void *device_tables, int32
     return ok ? NNBVH_OK : NNBVH_ERR_DEVICE;
 }
 
+int nnbvh_instance_launches(int family, int32_t *desc, uint64_t *counts, int capacity, int reset) {
+    if ((family != 0 && family != 1) || capacity < 0 || (capacity > 0 && !desc && !counts)) {
+        set_error("instance_launches: family 0 (BVH trace instances) or 1 (kd-tree ones), capacity >= 0 and an array to fill");
+        return -NNBVH_ERR_ARG;
+    }
+    return family == 0 ? trace_instance_launches(desc, counts, capacity, reset)
+                       : kd_instance_launches(desc, counts, capacity, reset);
+}
+
 int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value) {
+    // (checked before the scene is looked at: a bad value is refused whatever the scene is)
+    if (key && std::string(key) == "offsets32" && value != 0 && value != 1) {
+        set_error("set_option: offsets32 must be 0 or 1");
+        return NNBVH_ERR_ARG;
+    }
     if (!s || !key) {
         set_error("set_option: null argument");
         return NNBVH_ERR_ARG;
@@ -993,6 +1007,14 @@ int nnbvh_scene_set_option(nnbvh_scene *s, const char *key, int value) {
         s->prim_repeat = value;
     } else if (k == "fused_batches") {
         s->fused_batches = value ? 1 : 0;
+    } else if (k == "offsets32") {
+        // 0: scene_fits32 reports 0 although the arrays fit; 1: what their sizes say.  The walk instances' resident
+        // blocks per CU are cached per form: dropped, as a width's form may be asked again after a change to the
+        // instance table.  The top table itself (d_top / n_top) depends on the tree alone and stays; whether a launch
+        // uses it is decided per launch from scene_runs_lean
+        if (s->offsets32 != value)
+            for (int &b : s->walk_blocks_per_cu) b = 0;
+        s->offsets32 = value;
     } else if (k == "top_table") {
         s->use_top = value ? 1 : 0;
     } else if (k == "top_burst") {

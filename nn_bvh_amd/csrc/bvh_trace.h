@@ -97,6 +97,11 @@ int trace_block_threads(const TraceInstance &is);
 // `blocks` blocks of trace_block_threads(is) threads.
 // occupancy != nullptr: do not launch, report resident blocks per CU of that instance.
 hipError_t launch_trace(const TraceInstance &is, const TraceParams &p, int blocks, hipStream_t stream, int *occupancy);
+// The launch ledger (nnbvh_instance_launches, family 0): how often launch_trace has enqueued each instance in this
+// process (occupancy queries do not count).  Up to `capacity` rows: desc gets the 7 ints of each TraceInstance, counts
+// its count; either may be null.  reset: the counts are zeroed after they are read.  Returns the number of instances.
+// Host code only; no device is touched.
+int trace_instance_launches(int32_t *desc, uint64_t *counts, int capacity, int reset);
 
 // Tests only (nnbvh_debug_top_table of bvh_capi.cpp): the prologue of the lean one-launch instances alone.  Every one
 // of `blocks` blocks copies the table it built in LDS to out + block * top_debug_capacity() records and its record

@@ -26,7 +26,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <array>
+#include <atomic>
 #include <cstring>
+#include <iterator>
 #include <utility>
 
 #include "bvh_trace.h"
@@ -1210,15 +1212,36 @@ constexpr std::array<TraceEntry, sizeof...(I)> trace_table(std::index_sequence<I
 }
 static const auto kTraceTable = trace_table(std::make_index_sequence<std::size(kTraceInstances)>());
 
+// the launch ledger: one count per entry of kTraceInstances, in its order (host memory, process-wide)
+static std::atomic<uint64_t> g_trace_launches[std::size(kTraceInstances)];
+
 hipError_t launch_trace(const TraceInstance &is, const TraceParams &p, int blocks, hipStream_t stream, int *occupancy) {
-    for (const TraceEntry &e : kTraceTable) {
+    for (size_t i = 0; i < kTraceTable.size(); ++i) {
+        const TraceEntry &e = kTraceTable[i];
         if (std::memcmp(&e.is, &is, sizeof is) != 0) continue;
         const int threads = trace_block_threads(is);
         if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, e.kernel, threads, 0);
         hipLaunchKernelGGL(e.kernel, dim3((unsigned)blocks), dim3(threads), 0, stream, p);
+        g_trace_launches[i].fetch_add(1, std::memory_order_relaxed);
         return hipGetLastError();
     }
     return hipErrorInvalidValue;
+}
+
+int trace_instance_launches(int32_t *desc, uint64_t *counts, int capacity, int reset) {
+    const int n = (int)std::size(kTraceInstances);
+    for (int i = 0; i < n; ++i) {
+        const uint64_t c = reset ? g_trace_launches[i].exchange(0, std::memory_order_relaxed)
+                                 : g_trace_launches[i].load(std::memory_order_relaxed);
+        if (i >= capacity) continue;
+        if (counts) counts[i] = c;
+        if (desc) {
+            const TraceInstance &t = kTraceInstances[i];
+            const int32_t row[7] = {t.mode, t.window, t.inst, t.patch, t.alpha, t.soa, t.hostc};
+            for (int j = 0; j < 7; ++j) desc[7 * i + j] = row[j];
+        }
+    }
+    return n;
 }
 
 }  // namespace nnbvh

@@ -118,6 +118,8 @@ struct nnbvh_scene {
     float4 *d_top = nullptr;
     int n_top = 0;
     int use_top = 1;  // option "top_table" (speed only): 0 = the lean one-launch kernels read every record from d_wide
+    int offsets32 = 1;  // option "offsets32" (speed only): 0 = scene_fits32 reports 0 although the arrays fit, so the scene
+                        // is never lean (the general instances' 64-bit addressing, no LDS top table, p.fits32 = 0)
     int top_burst = 24;  // option "top_burst": tagged interior lanes that make a wave take a table step (65 = never);
                          // crown step: 16 .. 32 within 0.5 % of each other, 8 and 48 slower (profiles/top_table_steps.txt)
 };
@@ -174,9 +176,11 @@ inline bool grow(void **ptr, size_t *have, size_t need, const char *what) {
 }
 
 // both device arrays below 4 GiB (64 B per interior record, 16 B per primitive slot): the lean
-// kernel instances reach them with 32-bit byte offsets
+// kernel instances reach them with 32-bit byte offsets.  The ONE predicate everything that depends on the offset width
+// reads (scene_traits and through it is_lean / scene_runs_lean, the top table, the wavefront gather choice, p.fits32):
+// the "offsets32" option can turn it off for a scene that fits, never on for one that does not
 inline int scene_fits32(const nnbvh_scene *s) {
-    return (int64_t)s->n_interior < (1LL << 26) && s->n_slots < (1LL << 28) - 8;
+    return s->offsets32 && (int64_t)s->n_interior < (1LL << 26) && s->n_slots < (1LL << 28) - 8;
 }
 
 // what the choice of a kernel instance reads from a scene (trace_instance.h)

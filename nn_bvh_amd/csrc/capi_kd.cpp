@@ -74,7 +74,7 @@ static int kd_run(nnbvh_kd_scene *s, const KdWorkspace *w, hipStream_t stream, c
 // with both offset widths
 static KdInstance scene_instance(const nnbvh_kd_scene *s, int mode) {
     const int attr = s->d_extras ? ((s->has_alpha_tex && s->d_alpha_tex) ? 2 : 1) : 0;
-    return {mode, (s->has_patches || s->d_extras) ? 1 : 0, s->fits32, attr, 0};
+    return {mode, (s->has_patches || s->d_extras) ? 1 : 0, kd_scene_fits32(s), attr, 0};
 }
 
 // lean scenes (no patches, no attributes): their batch-mode instance has a form that reads SOA slices itself
@@ -171,7 +171,7 @@ int nnbvh::launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, co
     // the lean instance with the triangle-only interaction where neither the scene nor the mesh holds patches, else the
     // PATCH = 1 instance with the patch-capable one (launch_str_step's choice of FULL); each with both offset widths
     const int full = (s->has_patches || m.patchVerts) ? 1 : 0;
-    return kd_run(s, w, stream, {3 + k.kind, full, s->fits32, 0, 0}, 5 + 2 * (k.kind - 1) + full, p, k.n,
+    return kd_run(s, w, stream, {3 + k.kind, full, kd_scene_fits32(s), 0, 0}, 5 + 2 * (k.kind - 1) + full, p, k.n,
                   kKdQueues * kKdQueueStride, "kd walk kernel launch");
 }
 
@@ -441,6 +441,11 @@ void nnbvh_kd_scene_destroy(nnbvh_kd_scene *s) {
 }
 
 int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value) {
+    // (checked before the scene is looked at: a bad value is refused whatever the scene is)
+    if (key && std::string(key) == "offsets32" && value != 0 && value != 1) {
+        set_error("kd_scene_set_option: offsets32 must be 0 or 1");
+        return NNBVH_ERR_ARG;
+    }
     if (!s || !key) {
         set_error("kd_scene_set_option: null argument");
         return NNBVH_ERR_ARG;
@@ -449,7 +454,13 @@ int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value) {
     const std::string k(key);
     if (k == "read_soa") s->read_soa = value != 0;
     else if (k == "pair_one_launch") s->pair_one_launch = value != 0;
-    else {
+    else if (k == "offsets32") {
+        // 0: the O32 = 0 instances although the scene fits; 1: what kd_fits32 says of its sizes.  The resident blocks
+        // per CU are cached per slot, not per instance: those of the other width are dropped
+        if (s->offsets32 != value)
+            for (int &b : s->blocks_per_cu) b = 0;
+        s->offsets32 = value;
+    } else {
         set_error("kd_scene_set_option: unknown key " + k);
         return NNBVH_ERR_ARG;
     }

@@ -81,6 +81,11 @@ struct KdInstance {
 // occupancy != nullptr: do not launch, report resident blocks per CU of that instance.  hipErrorInvalidValue for an
 // instance the library does not hold
 hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, hipStream_t stream, int *occupancy);
+// The launch ledger (nnbvh_instance_launches, family 1): how often launch_kd_trace has enqueued each instance in this
+// process (occupancy queries do not count).  Up to `capacity` rows: desc gets 7 ints per instance (the KdInstance, zero-
+// padded), counts its count; either may be null.  reset: the counts are zeroed after they are read.  Returns the
+// number of instances.  Host code only; no device is touched.
+int kd_instance_launches(int32_t *desc, uint64_t *counts, int capacity, int reset);
 // the queue heads cleared by a kernel node (1 block), as launch_zero_queue does for the BVH kernels
 hipError_t launch_kd_zero_queue(unsigned *queue, int words, hipStream_t stream);
 
@@ -121,7 +126,8 @@ struct nnbvh_kd_scene {
     int depth = 0;
     int has_host_prims = 0;
     int has_patches = 0;
-    int fits32 = 0;  // kd_fits32
+    int fits32 = 0;  // kd_fits32 of the scene's sizes
+    int offsets32 = 1;  // option "offsets32" (speed only): 0 = run the O32 = 0 instances although the scene fits
     int n_nodes = 0, n_indices = 0, n_prims = 0;  // what nnbvh_kd_scene_info / _read report (d_indices holds max(n_indices, 1))
     float bounds[6];
     uint2 *d_nodes = nullptr;
@@ -151,10 +157,21 @@ struct nnbvh_kd_scene {
 
 namespace nnbvh {
 
-// nodes (8 B), primitive records (64 B) and indices (4 B) each below 4 GiB: the O32 instances reach them
+// nodes (8 B), primitive records (64 B) and indices (4 B) each below 4 GiB: the O32 instances reach them.
+// The O32 = 1 instances form `(unsigned)index * sizeof(element)` and add it to a scalar base, so they are correct as
+// long as that product does not wrap: 2^32 / 8 = 2^29 nodes, 2^32 / 4 = 2^30 indices, 2^32 / 64 = 2^26 primitive
+// records.  The primitive bound keeps two records of slack below 2^26: a primitive step reads slots 0 .. 3 of a record
+// through the one offset, and with the slack the END of the last record (not only its start) stays below 2^32.
+// The O32 = 0 instances index with 64-bit arithmetic throughout (`at` widens before it scales; the attribute slots
+// are reached through `6 * (long)index`), so they are correct for every count the C ABI can express: n_nodes,
+// n_indices and n_prims are `int`, at most 2^31 - 1 each.  (Before the scale moved into `at`, the wide path formed
+// 4 * index in int and was wrong from 2^29 primitive records on.)
 inline int kd_fits32(int64_t n_nodes, int64_t n_prims, int64_t n_indices) {
     return (n_nodes < (1 << 29) && n_prims < (1 << 26) - 1 && n_indices < (1 << 30)) ? 1 : 0;
 }
+// the offset width a scene's launches run with: what its sizes allow, unless the "offsets32" option asks for the wide
+// instances (the option can never force 32-bit offsets onto a scene that does not fit them)
+inline int kd_scene_fits32(const nnbvh_kd_scene *s) { return (s->fits32 && s->offsets32) ? 1 : 0; }
 
 // A new scene object with everything filled in but its device arrays, which either creation route (the caller's tree:
 // capi_kd.cpp; the device's own: kd_bake.hip) attaches.

@@ -17,6 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <iterator>
+
 #include "../../include/nnbvh.h"
 #include "nnbvh_internal.h"
 #include "trace_math.h"
@@ -110,10 +113,11 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
     auto pick_batch = [](const auto &arr, int b) {  // arr[b] of a kernel-argument array
         return b == 0 ? arr[0] : (b == 1 ? arr[1] : (b == 2 ? arr[2] : arr[3]));
     };
-    auto at = [](const auto *base, int index) {  // &base[index]
+    auto at = [](const auto *base, int index, int scale = 1) {  // &base[index * scale]; the wide form widens first
         using T = decltype(base);
-        return O32 ? reinterpret_cast<T>(reinterpret_cast<const char *>(base) + (unsigned)index * (unsigned)sizeof(*base))
-                   : base + (long)index;
+        return O32 ? reinterpret_cast<T>(reinterpret_cast<const char *>(base) +
+                                         (unsigned)(scale * index) * (unsigned)sizeof(*base))
+                   : base + (long)index * scale;
     };
     // KdNodeToVisit {node, tMin, tMax}: the three words of an entry 64 dwords apart
     __shared__ float s_stack[kKdBlock / 64][W][3][64];
@@ -395,7 +399,7 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
             if (cur == kKdLeaf) {
                 // one trip to memory: the primitive's three slots and — if the leaf goes on — the index of
                 // the primitive after it, all issued before anything is looked at
-                const float4 *rec = at(p.prims, 4 * leafIdx);
+                const float4 *rec = at(p.prims, leafIdx, 4);
                 float4 s0 = rec[0], s1 = rec[1], s2 = rec[2];
                 int nextIdx = 0;
                 if (leafLeft > 1) nextIdx = *at(p.primIndices, leafPos);
@@ -655,16 +659,37 @@ static const KdEntry kKdInstances[] = {
     kd_entry<4, 0, 0>(), kd_entry<4, 1, 0>(), kd_entry<4, 0, 1>(), kd_entry<4, 1, 1>(),
     kd_entry<5, 0, 0>(), kd_entry<5, 1, 0>(), kd_entry<5, 0, 1>(), kd_entry<5, 1, 1>()};
 
+// the launch ledger: one count per entry of kKdInstances, in its order (host memory, process-wide)
+static std::atomic<uint64_t> g_kd_launches[std::size(kKdInstances)];
+
 hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, hipStream_t stream, int *occupancy) {
-    for (const KdEntry &e : kKdInstances) {
+    for (size_t i = 0; i < std::size(kKdInstances); ++i) {
+        const KdEntry &e = kKdInstances[i];
         if (e.is.mode != is.mode || e.is.patch != is.patch || e.is.o32 != is.o32 || e.is.attr != is.attr ||
             e.is.hostc != is.hostc)
             continue;
         if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, e.kernel, kKdBlock, 0);
         hipLaunchKernelGGL(e.kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
+        g_kd_launches[i].fetch_add(1, std::memory_order_relaxed);
         return hipGetLastError();
     }
     return hipErrorInvalidValue;
+}
+
+int kd_instance_launches(int32_t *desc, uint64_t *counts, int capacity, int reset) {
+    const int n = (int)std::size(kKdInstances);
+    for (int i = 0; i < n; ++i) {
+        const uint64_t c = reset ? g_kd_launches[i].exchange(0, std::memory_order_relaxed)
+                                 : g_kd_launches[i].load(std::memory_order_relaxed);
+        if (i >= capacity) continue;
+        if (counts) counts[i] = c;
+        if (desc) {
+            const KdInstance &k = kKdInstances[i].is;
+            const int32_t row[7] = {k.mode, k.patch, k.o32, k.attr, k.hostc, 0, 0};
+            for (int j = 0; j < 7; ++j) desc[7 * i + j] = row[j];
+        }
+    }
+    return n;
 }
 
 }  // namespace nnbvh

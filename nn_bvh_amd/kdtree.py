@@ -197,7 +197,9 @@ class KdTreeAggregate:
               "nnbvh_kd_intersect_any_device")
 
     def set_option(self, key, value):
-        """nnbvh_kd_scene_set_option: "read_soa", "pair_one_launch" (speed only, never results)."""
+        """nnbvh_kd_scene_set_option: "read_soa", "pair_one_launch", "offsets32" (speed only, never results).
+        "offsets32" 0 runs the kernel instances with 64-bit addressing (those of scenes beyond 4 GiB, correct for every
+        scene) although this scene fits 32-bit offsets; 1 restores the width computed from the scene's sizes."""
         check(_lib.lib().nnbvh_kd_scene_set_option(self._h, key.encode(), int(value)), f"kd set_option({key})")
 
     def trace_batches_device(self, batches, stream=0):

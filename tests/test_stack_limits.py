@@ -9,7 +9,9 @@ margin check — never with the device's own counters.  Every GPU case compares 
 asserts that at least half of its deep rays exceeded the instance's window by 2 or more.
 
 Which template instance a case reaches (trace_kernel<MODE, W, INST, PATCH, ALPHA, SOA, HOSTC>; pick_trace_instance of
-trace_instance.h picks it from the scene's content, the "stack_window" option and the call):
+trace_instance.h picks it from the scene's content, the "stack_window" option and the call).  The table LEDGER below
+states the same per case as data, and every GPU case asserts it with the launch ledger (nnbvh_instance_launches): its
+device calls launch exactly the instances listed for it, each at least once, and no other instance of the family:
 
   test_bvh_single_level[lean-8]      triangles only, window 8: the lean instances <0,8,0,0>, <1,8,0,0>, <2,8,0,0>
                                      for Intersect / IntersectP(counts) / IntersectP and <3,8,0,0> for the
@@ -42,6 +44,8 @@ trace_instance.h picks it from the scene's content, the "stack_window" option an
                                      IntersectClosestAndShadow with read_soa 1 (lean: batch mode 3, the kernel reads
                                      the SOA slices; patch / attr: always gathered) and read_soa 0 (gathered into
                                      records: batch mode 2), pair_one_launch 1 and 0
+  test_kd_chain[*-wide]              the same three scenes with the option "offsets32" 0: the O32 = 0 twins of those
+                                     instances (64-bit addressing; tests/test_wide_offsets.py), through the same spill
   test_full_grid_*                   lean <1,8,0,0> with blocks_per_cu 8 and kd lean <0,0,4,1>: one deep ray per
                                      lane of the largest grid the library launches, which addresses the END of the
                                      spill arrays
@@ -57,15 +61,72 @@ refused.
 The animated scene writes its own AnimatedTransforms (a turn about the chain axis and a slide along it): the committed
 golden ones are arbitrary affine maps, which take a ray off the child's axis, and then no depth could be proved.
 """
+import contextlib
+
 import numpy as np
 import pytest
 
 import oracle_binding as ob
 import scenes_small as ss
-from nn_bvh_amd import HIT_DTYPE, BVHAggregate, NNBVHError, scene
+from nn_bvh_amd import HIT_DTYPE, BVHAggregate, NNBVHError, _lib, scene
 from nn_bvh_amd.kdtree import KdTreeAggregate
 
 gpu = pytest.mark.gpu
+BVH, KD = _lib.FAMILY_BVH, _lib.FAMILY_KD
+
+
+def _bvh(modes, window=8, inst=0, patch=1, alpha=0, soa=0, hostc=0):
+    return {(m, window, inst, patch, alpha, soa, hostc) for m in modes}
+
+
+def _kd(modes, patch, o32, attr=0):
+    return {(m, patch, o32, attr, 0) for m in modes}
+
+
+# case -> (kernel family, the instances its device calls launch): BVH (mode, window, inst, patch, alpha, soa, hostc), kd
+# (mode, patch, o32, attr, hostc).  Asserted by `reaches`; tests/test_wide_offsets.py takes its census from it.
+LEDGER = {
+    "test_bvh_single_level[lean-8]": (BVH, _bvh((0, 1, 2, 3), patch=0)),
+    "test_bvh_single_level[lean-4]": (BVH, _bvh((0, 1, 2), window=4)),
+    "test_bvh_single_level[lean-16]": (BVH, _bvh((0, 1, 2), window=16)),
+    "test_bvh_single_level[general-4]": (BVH, _bvh((0, 1, 2), window=4)),
+    "test_bvh_single_level[general-8]": (BVH, _bvh((0, 1, 2, 3))),
+    "test_bvh_single_level[general-16]": (BVH, _bvh((0, 1, 2), window=16)),
+    "test_bvh_wavefront_soa": (BVH, _bvh((0, 2, 3), patch=0, soa=1)),
+    "test_bvh_alpha[tri]": (BVH, _bvh((0, 1, 2), alpha=1)),
+    "test_bvh_alpha[patch]": (BVH, _bvh((0, 1, 2), alpha=2)),
+    "test_bvh_host_only_chain": (BVH, _bvh((0, 1, 2, 3)) | _bvh((0, 2, 3), hostc=1)),
+    "test_two_level_chain": (BVH, _bvh((0, 1, 2, 3), inst=1)),
+    "test_animated_two_level_chain": (BVH, _bvh((0, 1, 2, 3), inst=2)),
+    "test_kd_chain[lean]": (KD, _kd((0, 1, 2, 3), 0, 1)),
+    "test_kd_chain[patch]": (KD, _kd((0, 1, 2), 1, 1)),
+    "test_kd_chain[attr]": (KD, _kd((0, 1, 2), 1, 1, attr=1)),
+    "test_kd_chain[lean-wide]": (KD, _kd((0, 1, 2, 3), 0, 0)),
+    "test_kd_chain[patch-wide]": (KD, _kd((0, 1, 2), 1, 0)),
+    "test_kd_chain[attr-wide]": (KD, _kd((0, 1, 2), 1, 0, attr=1)),
+    "test_full_grid_bvh_any_hit_with_counts": (BVH, _bvh((1,), patch=0)),
+    "test_full_grid_kd_closest": (KD, _kd((0,), 0, 1)),
+    "test_deep_results_independent_of_tuning_and_order[two_level]": (BVH, _bvh((0, 1, 2), inst=1)),
+    "test_deep_results_independent_of_tuning_and_order[alpha]": (BVH, _bvh((0, 1, 2), alpha=2)),
+}
+
+
+def ledger_start(case):
+    return _lib.instance_launches(LEDGER[case][0])
+
+
+def assert_reached(case, start):
+    """the device calls since ledger_start(case) launched exactly the instances LEDGER lists for `case`"""
+    family, want = LEDGER[case]
+    launched = {k: v - start[k] for k, v in _lib.instance_launches(family).items() if v != start[k]}
+    assert set(launched) == want, f"{case}: launched {sorted(launched.items())}, LEDGER says {sorted(want)}"
+
+
+@contextlib.contextmanager
+def reaches(case):
+    start = ledger_start(case)
+    yield
+    assert_reached(case, start)
 N_DEEP, N_RANDOM = 1500, 500
 # share of chain_rays / kd_chain_rays that are "deep": all BVH chain rays (every box is crossed whatever tMax is);
 # the kd rays with an infinite tMax (a finite one ends the interval before the far split planes)
@@ -341,7 +402,8 @@ def test_bvh_single_level(leaves, window):
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
     assert agg.info["depth"] == 64
     agg.set_option("stack_window", window)
-    check_all_modes(agg, rays, exp, eany, f"{leaves} window {window}")
+    with reaches(f"test_bvh_single_level[{'lean' if leaves == 'tri' else 'general'}-{window}]"):
+        check_all_modes(agg, rays, exp, eany, f"{leaves} window {window}")
     agg.close()
 
 
@@ -357,7 +419,8 @@ def test_bvh_wavefront_soa():
             res = (ob.closest if kind == "closest" else ob.any_hit)(ch.nodes, ch.prims, ch.verts, r)
         return res, d.depth[:, 0]
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
-    check_queue_calls(agg, walk, rays, deep, 8, "lean SOA")
+    with reaches("test_bvh_wavefront_soa"):
+        check_queue_calls(agg, walk, rays, deep, 8, "lean SOA")
     agg.close()
 
 
@@ -387,7 +450,8 @@ def test_bvh_alpha(leaves):
     assert rejected.sum() >= 200, "rays whose walk differs from the walk without alpha: a hit was rejected"
     kw = dict(normals=ch.normals, prim_alpha=ch.prim_alpha, uvs=ch.uvs)
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts, **kw)
-    check_all_modes(agg, rays, exp, eany, leaves, batches=False)
+    with reaches(f"test_bvh_alpha[{'tri' if leaves == 'alpha_tri' else 'patch'}]"):
+        check_all_modes(agg, rays, exp, eany, leaves, batches=False)
     agg.close()
 
 
@@ -417,6 +481,7 @@ def test_bvh_host_only_chain():
     assert_exceeds_window(da, deep, 8, "any")
     assert (exp["instance"][deep] == -1).sum() > 50 and (eany[0][deep] == 2).sum() > 20
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
+    start = ledger_start("test_bvh_host_only_chain")
     check_all_modes(agg, rays, exp, eany, "host-only chain")
     host_ids = np.sort(ch.prims["id"][ch.prims["kind"] == 3])[::-1]
     assert len(host_ids) == 13 and host_ids.min() < 8 and host_ids.max() > 56
@@ -529,6 +594,7 @@ def test_bvh_host_only_chain():
     check_any(rays[:m], h_occ[:m], sc.numpy()[:m], "wavefront shadow")
     first = ob.record_shadow(np.where(h_occ[:m] == 0, 0, 1).astype(np.uint8), Ld[:m], r_u[:m], r_l[:m], px[:m], L)
     assert np.array_equal(d_l.cpu().numpy().view(np.uint32), first.view(np.uint32))
+    assert_reached("test_bvh_host_only_chain", start)
     mesh.close()
     agg.close()
 
@@ -550,7 +616,8 @@ def test_two_level_chain():
         assert both.sum() >= N_DEEP, "every deep ray enters an instance with > 8 outer entries and goes > 8 deep in it"
     agg = BVHAggregate.from_tree(t.nodes, t.prims, t.verts, instances=t.instances, n_top_nodes=t.n_top)
     assert agg.info["depth"] == 64
-    check_all_modes(agg, rays, exp, eany, "two-level chain")
+    with reaches("test_two_level_chain"):
+        check_all_modes(agg, rays, exp, eany, "two-level chain")
     assert (exp["instance"][deep] > 0).sum() > 500
     agg.close()
 
@@ -578,7 +645,8 @@ def test_animated_two_level_chain():
     assert (tm < 0).sum() > 50 and (tm > 1).sum() > 50
     agg = BVHAggregate.from_tree(t.nodes, t.prims, t.verts, instances=t.instances, n_top_nodes=t.n_top, animated=anims)
     assert agg.info["depth"] == 64
-    check_all_modes(agg, rays, exp, eany, "animated two-level chain")
+    with reaches("test_animated_two_level_chain"):
+        check_all_modes(agg, rays, exp, eany, "animated two-level chain")
     moving = oa["actually_animated"][np.maximum(exp["instance"] - 1, 0)] != 0
     assert ((exp["instance"] > 0) & moving & deep & (rays["time"] > 0) & (rays["time"] < 1)).sum() > 100
     agg.close()
@@ -607,8 +675,12 @@ def kd_oracle(k, rays):
 
 
 @gpu
-@pytest.mark.parametrize("form,window", [("lean", 4), ("patch", 8), ("attr", 8)], ids=["lean", "patch", "attr"])
-def test_kd_chain(form, window):
+@pytest.mark.parametrize("form,window,offsets32",
+                         [("lean", 4, 1), ("patch", 8, 1), ("attr", 8, 1), ("lean", 4, 0), ("patch", 8, 0), ("attr", 8, 0)],
+                         ids=["lean", "patch", "attr", "lean-wide", "patch-wide", "attr-wide"])
+def test_kd_chain(form, window, offsets32):
+    """offsets32 0 (the *-wide cases): the same scene, calls and assertions through the O32 = 0 instances — the HBM
+    spill and the 64-bit addressing, the two rarely-run mechanisms, in one walk."""
     import torch
     k = ss.kd_chain(64, 7, form)
     rays, deep = kd_ray_set(k, 9)
@@ -617,6 +689,8 @@ def test_kd_chain(form, window):
     assert_exceeds_window(da, deep, window, "kd any")
     agg = KdTreeAggregate.from_tree(k.nodes, k.prim_indices, k.prims, k.verts, k.bounds, normals=k.normals, uvs=k.uvs,
                                     prim_alpha=k.prim_alpha)
+    agg.set_option("offsets32", offsets32)
+    start = ledger_start(f"test_kd_chain[{form}{'' if offsets32 else '-wide'}]")
     assert agg.Intersect(rays).tobytes() == exp.tobytes()
     occ, vis, tst = agg.IntersectP(rays, counts=True)
     assert np.array_equal(occ, eany[0]) and np.array_equal(vis, eany[1]) and np.array_equal(tst, eany[2])
@@ -647,6 +721,7 @@ def test_kd_chain(form, window):
         agg.set_option("read_soa", read_soa)
         agg.set_option("pair_one_launch", pair)
         check_queue_calls(agg, walk, rays, deep, window, f"kd {form} read_soa {read_soa} pair_one_launch {pair}")
+    assert_reached(f"test_kd_chain[{form}{'' if offsets32 else '-wide'}]", start)
     agg.close()
 
 
@@ -695,6 +770,7 @@ def test_full_grid_bvh_any_hit_with_counts():
     rays = np.tile(distinct, n // N_DISTINCT)
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
     agg.set_option("blocks_per_cu", 8)
+    start = ledger_start("test_full_grid_bvh_any_hit_with_counts")
     occ, vis, tst = agg.IntersectP(rays, counts=True)
     idx = np.random.default_rng(53).choice(n, 60000, replace=False)
     assert np.array_equal(occ[idx], eocc[idx % N_DISTINCT]) and np.array_equal(vis[idx], evis[idx % N_DISTINCT])
@@ -716,6 +792,7 @@ def test_full_grid_bvh_any_hit_with_counts():
         assert (flags.reshape(-1, N_DISTINCT) == eocc[None, :]).all()
         assert (v.cpu().numpy().reshape(-1, N_DISTINCT) == evis[None, :]).all()
         assert (c.cpu().numpy().reshape(-1, N_DISTINCT) == etst[None, :]).all()
+    assert_reached("test_full_grid_bvh_any_hit_with_counts", start)
     agg.close()
 
 
@@ -731,6 +808,7 @@ def test_full_grid_kd_closest():
     n = full_grid_count()
     rays = np.tile(distinct, n // N_DISTINCT)
     agg = KdTreeAggregate.from_tree(k.nodes, k.prim_indices, k.prims, k.verts, k.bounds)
+    start = ledger_start("test_full_grid_kd_closest")
     got = agg.Intersect(rays)
     idx = np.random.default_rng(55).choice(n, 60000, replace=False)
     assert got[idx].tobytes() == exp[idx % N_DISTINCT].tobytes()
@@ -739,6 +817,7 @@ def test_full_grid_kd_closest():
     d_rays = upload(rays)
     for rec in two_streams(agg.intersect_device, d_rays, n, 32):
         assert (rec.reshape(n // N_DISTINCT, -1) == one).all()
+    assert_reached("test_full_grid_kd_closest", start)
     agg.close()
 
 
@@ -763,6 +842,7 @@ def test_deep_results_independent_of_tuning_and_order(which):
     def run(r):
         occ, vis, tst = agg.IntersectP(r, counts=True)
         return agg.Intersect(r), occ, vis, tst, agg.IntersectP(r)
+    start = ledger_start(f"test_deep_results_independent_of_tuning_and_order[{which}]")
     base = run(rays)
     perm = np.random.default_rng(0).permutation(len(rays))
     for a, b in zip(run(rays[perm]), base):
@@ -771,4 +851,5 @@ def test_deep_results_independent_of_tuning_and_order(which):
         agg.set_option(key, val)
         for a, b in zip(run(rays), base):
             assert a.tobytes() == b.tobytes(), f"{key}={val} changed a result"
+    assert_reached(f"test_deep_results_independent_of_tuning_and_order[{which}]", start)
     agg.close()
