@@ -26,7 +26,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <array>
-#include <atomic>
 #include <cstring>
 #include <iterator>
 #include <utility>
@@ -34,6 +33,7 @@
 #include "bvh_trace.h"
 #include "alpha_texture_math.h"
 #include "anim_math.h"
+#include "launch_ledger.h"
 #include "spawn_math.h"
 #include "stream_access.h"
 #include "top_extend.h"
@@ -1212,8 +1212,8 @@ constexpr std::array<TraceEntry, sizeof...(I)> trace_table(std::index_sequence<I
 }
 static const auto kTraceTable = trace_table(std::make_index_sequence<std::size(kTraceInstances)>());
 
-// the launch ledger: one count per entry of kTraceInstances, in its order (host memory, process-wide)
-static std::atomic<uint64_t> g_trace_launches[std::size(kTraceInstances)];
+// the launch ledger: one count per entry of kTraceInstances, in its order
+static LaunchLedger<(int)std::size(kTraceInstances)> g_trace_ledger;
 
 hipError_t launch_trace(const TraceInstance &is, const TraceParams &p, int blocks, hipStream_t stream, int *occupancy) {
     for (size_t i = 0; i < kTraceTable.size(); ++i) {
@@ -1222,26 +1222,17 @@ hipError_t launch_trace(const TraceInstance &is, const TraceParams &p, int block
         const int threads = trace_block_threads(is);
         if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, e.kernel, threads, 0);
         hipLaunchKernelGGL(e.kernel, dim3((unsigned)blocks), dim3(threads), 0, stream, p);
-        g_trace_launches[i].fetch_add(1, std::memory_order_relaxed);
+        g_trace_ledger.count((int)i);
         return hipGetLastError();
     }
     return hipErrorInvalidValue;
 }
 
 int trace_instance_launches(int32_t *desc, uint64_t *counts, int capacity, int reset) {
-    const int n = (int)std::size(kTraceInstances);
-    for (int i = 0; i < n; ++i) {
-        const uint64_t c = reset ? g_trace_launches[i].exchange(0, std::memory_order_relaxed)
-                                 : g_trace_launches[i].load(std::memory_order_relaxed);
-        if (i >= capacity) continue;
-        if (counts) counts[i] = c;
-        if (desc) {
-            const TraceInstance &t = kTraceInstances[i];
-            const int32_t row[7] = {t.mode, t.window, t.inst, t.patch, t.alpha, t.soa, t.hostc};
-            for (int j = 0; j < 7; ++j) desc[7 * i + j] = row[j];
-        }
-    }
-    return n;
+    return g_trace_ledger.read(desc, counts, capacity, reset, [](int i) {
+        const TraceInstance &t = kTraceInstances[i];
+        return std::array<int32_t, 7>{{t.mode, t.window, t.inst, t.patch, t.alpha, t.soa, t.hostc}};
+    });
 }
 
 }  // namespace nnbvh

@@ -50,35 +50,26 @@ static KdParams scene_params(const nnbvh_kd_scene *s, const KdWorkspace *w) {
     return p;
 }
 
-// The queue heads zeroed, then the instance over total_rays rays in all.  slot: the instance's entry of
-// s->blocks_per_cu.  Persistent grid = what is resident at once, asked from the runtime for the exact instance and
-// capped at the 8 blocks per CU the spill array is sized for; never more threads than rays to start with.
-static int kd_run(nnbvh_kd_scene *s, const KdWorkspace *w, hipStream_t stream, const KdInstance &is, int slot,
-                  const KdParams &p, int64_t total_rays, int queue_words, const char *what) {
-    if (s->blocks_per_cu[slot] == 0) {
+// The queue heads zeroed, then the instance over total_rays rays in all.  Persistent grid = what is resident at once,
+// asked from the runtime for the exact instance (once: s->blocks_per_cu keeps it by the instance's row of kKdInstances)
+// and capped at the 8 blocks per CU the spill array is sized for; never more threads than rays to start with.
+static int kd_run(nnbvh_kd_scene *s, const KdWorkspace *w, hipStream_t stream, const KdInstance &is, const KdParams &p,
+                  int64_t total_rays, int queue_words, const char *what) {
+    const int row = kd_instance_index(is);
+    if (row < 0) return hip_ok(hipErrorInvalidValue, what) ? NNBVH_OK : NNBVH_ERR_DEVICE;  // the library does not hold it
+    int &per_cu = s->blocks_per_cu[row];
+    if (per_cu == 0) {
         int occ = 0;
         const hipError_t e = launch_kd_trace(is, p, 0, nullptr, &occ);
-        s->blocks_per_cu[slot] = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
+        per_cu = (e == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
     }
-    int blocks = s->n_cus * s->blocks_per_cu[slot];
+    int blocks = s->n_cus * per_cu;
     const int64_t need = (total_rays + kKdBlock - 1) / kKdBlock;
     if (need < blocks) blocks = (int)std::max<int64_t>(need, 1);
-    hipError_t e = launch_kd_zero_queue(w->queue, queue_words, stream);
+    hipError_t e = launch_zero_queue(w->queue, queue_words, stream);  // (bvh_trace.h: a kernel node)
     if (e == hipSuccess) e = launch_kd_trace(is, p, blocks, stream, nullptr);
     return hip_ok(e, what) ? NNBVH_OK : NNBVH_ERR_DEVICE;
 }
-
-// the instance of `mode` a scene's rays run through: lean, with patches (or what else reads the ray direction), with
-// attribute arrays (attr 1), with textured triangles among the baked records (attr 2: chosen from what was baked, not
-// from the table — a table beside alpha-tested patches and no textured triangle needs attr 1's patch recursion); each
-// with both offset widths
-static KdInstance scene_instance(const nnbvh_kd_scene *s, int mode) {
-    const int attr = s->d_extras ? ((s->has_alpha_tex && s->d_alpha_tex) ? 2 : 1) : 0;
-    return {mode, (s->has_patches || s->d_extras) ? 1 : 0, kd_scene_fits32(s), attr, 0};
-}
-
-// lean scenes (no patches, no attributes): their batch-mode instance has a form that reads SOA slices itself
-static bool kd_scene_reads_soa(const nnbvh_kd_scene *s) { return s->read_soa && !s->has_patches && !s->d_extras; }
 
 // one batch of records, mode 0: closest hit (out = nnbvh_hit[n]), mode 1: any hit (out = uint8[n], counts nullable)
 static int kd_launch(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, int mode, const void *d_rays, int64_t n,
@@ -90,7 +81,8 @@ static int kd_launch(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, int 
     p.visitedOut = (int32_t *)d_vis;
     p.testsOut = (int32_t *)d_tests;
     p.n = (long)n;
-    return kd_run(s, w, stream, scene_instance(s, mode), mode, p, n, kKdQueues * kKdQueueStride, "kd trace kernel launch");
+    return kd_run(s, w, stream, pick_kd_instance(kd_scene_traits(s), mode), p, n, kKdQueues * kKdQueueStride,
+                  "kd trace kernel launch");
 }
 
 int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, const KdBatch *batches, int n_batches) {
@@ -103,9 +95,9 @@ int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stre
         total += batches[b].n;
         candidates = candidates || (batches[b].hc && batches[b].hc->capacity > 0);
     }
-    // a candidate call always goes through the record form ("read_soa" has no effect on it)
-    const bool read_soa = !candidates && all_soa && kd_scene_reads_soa(s);
-    const bool hostc = candidates && s->has_host_prims;  // else: the plain instances over zeroed counts
+    // record form (mode 2): the scene's instance or its candidate-mode twin; SOA form (mode 3): lean only
+    bool read_soa = false;
+    const KdInstance is = pick_kd_batch_instance(kd_scene_traits(s), all_soa, candidates, &read_soa);
     if (!read_soa && soa_rays > 0 &&
         !grow(&w->d_in, &w->in_bytes, (size_t)soa_rays * sizeof(nnbvh_ray), "hipMalloc(wavefront rays)"))
         return NNBVH_ERR_DEVICE;
@@ -122,7 +114,7 @@ int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stre
         p.bNDev[b] = k.d_n;
         if (k.hc && k.hc->capacity > 0 && k.n > 0) {
             if (!zero_candidates(s->n_cus, k.hc, k.n, !k.any, stream)) return NNBVH_ERR_DEVICE;
-            if (hostc) {
+            if (is.hostc) {  // else: the plain instance over the zeroed counts
                 p.bHcCap[b] = k.hc->capacity;
                 p.bHcCount[b] = k.hc->count;
                 p.bHcBefore[b] = k.any ? nullptr : k.hc->before;
@@ -142,11 +134,7 @@ int nnbvh::kd_launch_batches(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stre
             p.bRays[b] = (const nnbvh_ray *)k.rays;
         }
     }
-    // record form (mode 2): the scene's instance or its candidate-mode twin; SOA form (mode 3): lean only
-    KdInstance is = scene_instance(s, read_soa ? 3 : 2);
-    is.hostc = hostc ? 1 : 0;
-    return kd_run(s, w, stream, is, hostc ? 4 : (read_soa ? 3 : 2), p, total, n_batches * kKdQueues * kKdQueueStride,
-                  "kd batch trace kernel launch");
+    return kd_run(s, w, stream, is, p, total, n_batches * kKdQueues * kKdQueueStride, "kd batch trace kernel launch");
 }
 
 // ---- the walk calls' launchers (capi_wavefront.cpp: nnbvh_kd_wavefront_walk_*) ------------------------------------
@@ -168,10 +156,7 @@ int nnbvh::launch_walk(nnbvh_kd_scene *s, KdWorkspace *w, hipStream_t stream, co
     p.wMesh = {m.verts, m.triVerts, m.patchVerts, m.normals, m.uvs, m.tangents, m.faceIndices, m.triFlags, m.nTris,
                m.defaultFlags, nullptr, 0, nullptr, nullptr};  // kd scenes have one level
     p.walk = k.a;
-    // the lean instance with the triangle-only interaction where neither the scene nor the mesh holds patches, else the
-    // PATCH = 1 instance with the patch-capable one (launch_str_step's choice of FULL); each with both offset widths
-    const int full = (s->has_patches || m.patchVerts) ? 1 : 0;
-    return kd_run(s, w, stream, {3 + k.kind, full, kd_scene_fits32(s), 0, 0}, 5 + 2 * (k.kind - 1) + full, p, k.n,
+    return kd_run(s, w, stream, pick_kd_walk_instance(kd_scene_traits(s), k.kind, m.patchVerts != nullptr), p, k.n,
                   kKdQueues * kKdQueueStride, "kd walk kernel launch");
 }
 
@@ -456,7 +441,7 @@ int nnbvh_kd_scene_set_option(nnbvh_kd_scene *s, const char *key, int value) {
     else if (k == "pair_one_launch") s->pair_one_launch = value != 0;
     else if (k == "offsets32") {
         // 0: the O32 = 0 instances although the scene fits; 1: what kd_fits32 says of its sizes.  The resident blocks
-        // per CU are cached per slot, not per instance: those of the other width are dropped
+        // per CU are dropped with the width (the cache is per instance: this only asks again)
         if (s->offsets32 != value)
             for (int &b : s->blocks_per_cu) b = 0;
         s->offsets32 = value;

@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "../../include/nnbvh.h"
+#include "kd_instance.h"
 #include "walk_math.h"
 
 namespace nnbvh {
@@ -72,12 +73,7 @@ struct KdParams {
     const float *alphaTexels;
 };
 
-// One instance of kd_trace_kernel (kd_trace.hip explains the template parameters of the same names; the window W
-// follows from patch).  The library holds modes 0 / 1 x {lean, patch, patch + attr 1, patch + attr 2} x o32, mode 2 the
-// same x hostc, mode 3 lean x o32 and the walk modes 4 / 5 x {lean, patch} x o32.
-struct KdInstance {
-    int mode, patch, o32, attr, hostc;
-};
+// One instance of kd_trace_kernel (KdInstance; kKdInstances of kd_instance.h lists those the library holds).
 // occupancy != nullptr: do not launch, report resident blocks per CU of that instance.  hipErrorInvalidValue for an
 // instance the library does not hold
 hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, hipStream_t stream, int *occupancy);
@@ -86,8 +82,6 @@ hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, 
 // padded), counts its count; either may be null.  reset: the counts are zeroed after they are read.  Returns the
 // number of instances.  Host code only; no device is touched.
 int kd_instance_launches(int32_t *desc, uint64_t *counts, int capacity, int reset);
-// the queue heads cleared by a kernel node (1 block), as launch_zero_queue does for the BVH kernels
-hipError_t launch_kd_zero_queue(unsigned *queue, int words, hipStream_t stream);
 
 struct KdWorkspace {
     unsigned *queue = nullptr;  // kKdMaxBatches x kKdQueues heads
@@ -134,9 +128,7 @@ struct nnbvh_kd_scene {
     int32_t *d_indices = nullptr;
     float4 *d_prims = nullptr;
     float4 *d_extras = nullptr;  // 6 slots per primitive, scenes with attribute-reading alpha kinds only
-    // closest, any, batches of records, batches of SOA slices, batches with host candidates, then the walk instances:
-    // shadow-tr lean / full, one-random lean / full
-    int blocks_per_cu[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int blocks_per_cu[nnbvh::kKdInstanceCount] = {};  // resident blocks per CU, by row of kKdInstances (0: not asked yet)
     // tuning (speed only, never results; nnbvh_kd_scene_set_option "read_soa" / "pair_one_launch"; DESIGN.md §5.7
     // holds the measurement behind the defaults)
     // both 0 until a recorded probe run shows the new form ahead by more than the spread of either form
@@ -169,9 +161,11 @@ namespace nnbvh {
 inline int kd_fits32(int64_t n_nodes, int64_t n_prims, int64_t n_indices) {
     return (n_nodes < (1 << 29) && n_prims < (1 << 26) - 1 && n_indices < (1 << 30)) ? 1 : 0;
 }
-// the offset width a scene's launches run with: what its sizes allow, unless the "offsets32" option asks for the wide
-// instances (the option can never force 32-bit offsets onto a scene that does not fit them)
-inline int kd_scene_fits32(const nnbvh_kd_scene *s) { return (s->fits32 && s->offsets32) ? 1 : 0; }
+// what the choice of an instance reads from a scene (the pickers of kd_instance.h)
+inline KdTraits kd_scene_traits(const nnbvh_kd_scene *s) {
+    return {s->has_patches, s->d_extras != nullptr, s->has_alpha_tex, s->d_alpha_tex != nullptr, s->has_host_prims,
+            s->fits32, s->offsets32, s->read_soa};
+}
 
 // A new scene object with everything filled in but its device arrays, which either creation route (the caller's tree:
 // capi_kd.cpp; the device's own: kd_bake.hip) attaches.

@@ -17,8 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-#include <iterator>
+#include <array>
+#include <utility>
 
 #include "../../include/nnbvh.h"
 #include "nnbvh_internal.h"
@@ -26,6 +26,7 @@
 #include "alpha_texture_math.h"
 #include "spawn_math.h"
 #include "kd_trace.h"
+#include "launch_ledger.h"
 #include "walk_math.h"
 
 namespace nnbvh {
@@ -622,74 +623,35 @@ __global__ __launch_bounds__(kKdBlock, PATCH ? 1 : 2) void kd_trace_kernel(KdPar
 
 #undef KD_BEGIN_RAY
 
-__global__ void kd_zero_queue_kernel(unsigned *queue, int words) {
-    for (int i = threadIdx.x; i < words; i += blockDim.x) queue[i] = 0u;
+// ---- the instances: one kernel per entry of kKdInstances (kd_instance.h), in its order and under its row number ------
+template <size_t I>
+constexpr auto kd_kernel() {  // the window follows from patch
+    constexpr KdInstance k = kKdInstances[I];
+    return kd_trace_kernel<k.mode, k.patch, k.patch ? kKdW : kKdWLean, k.o32, k.attr, k.hostc>;
 }
-hipError_t launch_kd_zero_queue(unsigned *queue, int words, hipStream_t stream) {
-    hipLaunchKernelGGL(kd_zero_queue_kernel, dim3(1), dim3(256), 0, stream, queue, words);
+template <size_t... I>
+constexpr std::array<void (*)(KdParams), sizeof...(I)> kd_kernels(std::index_sequence<I...>) {
+    return {{kd_kernel<I>()...}};
+}
+static const auto kKdKernels = kd_kernels(std::make_index_sequence<kKdInstanceCount>());
+
+// the launch ledger: one count per entry of kKdInstances, in its order
+static LaunchLedger<kKdInstanceCount> g_kd_ledger;
+
+hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, hipStream_t stream, int *occupancy) {
+    const int row = kd_instance_index(is);
+    if (row < 0) return hipErrorInvalidValue;
+    if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, kKdKernels[row], kKdBlock, 0);
+    hipLaunchKernelGGL(kKdKernels[row], dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
+    g_kd_ledger.count(row);
     return hipGetLastError();
 }
 
-// ---- the instances ---------------------------------------------------------------------------------------------
-struct KdEntry {
-    KdInstance is;
-    void (*kernel)(KdParams);
-};
-template <int MODE, int PATCH, int O32, int ATTR = 0, int HOSTC = 0>
-constexpr KdEntry kd_entry() {  // the window follows from PATCH
-    return {{MODE, PATCH, O32, ATTR, HOSTC}, kd_trace_kernel<MODE, PATCH, PATCH ? kKdW : kKdWLean, O32, ATTR, HOSTC>};
-}
-// Every instance the library holds: what is not listed here is not compiled.  (The order is the order of the kernels in
-// the compiler's output.)
-static const KdEntry kKdInstances[] = {
-    // closest / any hit: lean and patch scenes, with and without 32-bit offsets, then the attribute-reading forms
-    kd_entry<0, 0, 0>(), kd_entry<1, 0, 0>(), kd_entry<0, 1, 0>(), kd_entry<1, 1, 0>(),
-    kd_entry<0, 0, 1>(), kd_entry<1, 0, 1>(), kd_entry<0, 1, 1>(), kd_entry<1, 1, 1>(),
-    kd_entry<0, 1, 0, 1>(), kd_entry<1, 1, 0, 1>(), kd_entry<0, 1, 1, 1>(), kd_entry<1, 1, 1, 1>(),
-    // batches, record form: lean / patches / attributes; SOA form (mode 3): lean only
-    kd_entry<2, 0, 0>(), kd_entry<2, 1, 0>(), kd_entry<2, 1, 0, 1>(), kd_entry<3, 0, 0>(),
-    kd_entry<2, 0, 1>(), kd_entry<2, 1, 1>(), kd_entry<2, 1, 1, 1>(), kd_entry<3, 0, 1>(),
-    // ... and the candidate-mode twins of the record form
-    kd_entry<2, 0, 0, 0, 1>(), kd_entry<2, 1, 0, 0, 1>(), kd_entry<2, 1, 0, 1, 1>(),
-    kd_entry<2, 0, 1, 0, 1>(), kd_entry<2, 1, 1, 0, 1>(), kd_entry<2, 1, 1, 1, 1>(),
-    // image-textured alpha (ATTR = 2): closest / any hit, batches, candidate-mode batches; without and with 32-bit offsets
-    kd_entry<0, 1, 0, 2>(), kd_entry<1, 1, 0, 2>(), kd_entry<2, 1, 0, 2>(), kd_entry<2, 1, 0, 2, 1>(),
-    kd_entry<0, 1, 1, 2>(), kd_entry<1, 1, 1, 2>(), kd_entry<2, 1, 1, 2>(), kd_entry<2, 1, 1, 2, 1>(),
-    // the walk instances: IntersectShadowTr's, then IntersectOneRandom's
-    kd_entry<4, 0, 0>(), kd_entry<4, 1, 0>(), kd_entry<4, 0, 1>(), kd_entry<4, 1, 1>(),
-    kd_entry<5, 0, 0>(), kd_entry<5, 1, 0>(), kd_entry<5, 0, 1>(), kd_entry<5, 1, 1>()};
-
-// the launch ledger: one count per entry of kKdInstances, in its order (host memory, process-wide)
-static std::atomic<uint64_t> g_kd_launches[std::size(kKdInstances)];
-
-hipError_t launch_kd_trace(const KdInstance &is, const KdParams &p, int blocks, hipStream_t stream, int *occupancy) {
-    for (size_t i = 0; i < std::size(kKdInstances); ++i) {
-        const KdEntry &e = kKdInstances[i];
-        if (e.is.mode != is.mode || e.is.patch != is.patch || e.is.o32 != is.o32 || e.is.attr != is.attr ||
-            e.is.hostc != is.hostc)
-            continue;
-        if (occupancy) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occupancy, e.kernel, kKdBlock, 0);
-        hipLaunchKernelGGL(e.kernel, dim3((unsigned)blocks), dim3(kKdBlock), 0, stream, p);
-        g_kd_launches[i].fetch_add(1, std::memory_order_relaxed);
-        return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-}
-
 int kd_instance_launches(int32_t *desc, uint64_t *counts, int capacity, int reset) {
-    const int n = (int)std::size(kKdInstances);
-    for (int i = 0; i < n; ++i) {
-        const uint64_t c = reset ? g_kd_launches[i].exchange(0, std::memory_order_relaxed)
-                                 : g_kd_launches[i].load(std::memory_order_relaxed);
-        if (i >= capacity) continue;
-        if (counts) counts[i] = c;
-        if (desc) {
-            const KdInstance &k = kKdInstances[i].is;
-            const int32_t row[7] = {k.mode, k.patch, k.o32, k.attr, k.hostc, 0, 0};
-            for (int j = 0; j < 7; ++j) desc[7 * i + j] = row[j];
-        }
-    }
-    return n;
+    return g_kd_ledger.read(desc, counts, capacity, reset, [](int i) {
+        const KdInstance &k = kKdInstances[i];
+        return std::array<int32_t, 7>{{k.mode, k.patch, k.o32, k.attr, k.hostc}};
+    });
 }
 
 }  // namespace nnbvh
