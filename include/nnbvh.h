@@ -100,12 +100,13 @@ typedef struct nnbvh_linear_node {
 #define NNBVH_PRIM_ALPHA_PATCH_UV_SMOOTH_FLIPPED 15
 #define NNBVH_PRIM_ALPHATEX_TRIANGLE 16 /* a Triangle inside a GeometricPrimitive whose alpha is a FloatImageTexture with a
                                        UVMapping (textures.h:579-590): v[3] = index into the scene's alpha-texture table
-                                       (nnbvh_scene_create_with_alpha_textures; kd-trees:
+                                       (nnbvh_scene_create_with_alpha_textures; two-level scenes:
+                                       nnbvh_scene_create_instanced_with_alpha_textures; kd-trees:
                                        nnbvh_kd_scene_create_with_alpha_textures).  The texture is evaluated at the hit's
                                        (u, v) as the reference does for the alpha test, i.e. with zero differentials:
                                        level 0 of the image only (nnbvh_alpha_texture).  Then as kind 4.
                                        kind = 16 + flipped + 2 * smooth, flipped and smooth as for kinds 4 .. 7.
-                                       Flat BVH scenes and kd scenes: two-level scenes, textured alpha on patches, other
+                                       BVH scenes of one or two levels and kd scenes: textured alpha on patches, other
                                        mappings (spherical, cylindrical, planar) and other float textures (scale, mix,
                                        checkerboard, ...) stay NNBVH_PRIM_HOST */
 #define NNBVH_PRIM_ALPHATEX_TRIANGLE_FLIPPED 17
@@ -407,6 +408,28 @@ nnbvh_scene *nnbvh_scene_create_gpu_build_with_alpha_textures(const nnbvh_prim *
                                                               const float *prim_alpha, int max_prims_in_node,
                                                               int split_method, int device,
                                                               const nnbvh_alpha_texture *textures, int n_textures);
+/* Two-level scenes: nnbvh_scene_create_instanced_with_attributes (host-built trees) / nnbvh_scene_create_instanced_gpu_build
+ * (every tree built on the device) plus the alpha-texture table.  Both make byte-identical device arrays, the table and
+ * the pool included (nnbvh_scene_read, what = 3 / 4), and both are counted in the scene's device bytes.  A textured
+ * triangle may sit in an object definition or in the top-level list.  Inside an instance the texture is evaluated at
+ * the barycentrics of the INSTANCE-space ray, the ray the alpha hash and the re-trace already use there
+ * (TransformedPrimitive / AnimatedPrimitive::Intersect hand the transformed ray to the child aggregate,
+ * cpu/primitive.cpp:112-131); one object placed twice can so give one triangle two alphas along one render-space line.
+ * uvs == NULL, the kinds 4 .. 7 and the argument faults (named after these calls, raised before a device is looked
+ * at) are those of the calls above; here alpha-tested patches (kinds 8 .. 15) MAY share the scene with textured
+ * triangles.  n_instances must be at least 1.  The other instanced calls refuse kinds 16 .. 19. */
+nnbvh_scene *nnbvh_scene_create_instanced_with_alpha_textures(const nnbvh_linear_node *nodes, int n_nodes, int n_top_nodes,
+                                                              const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                              int n_verts, const nnbvh_instance *instances,
+                                                              int n_instances, const nnbvh_animated_transform *animated,
+                                                              const float *normals, const float *uvs,
+                                                              const float *prim_alpha, int device,
+                                                              const nnbvh_alpha_texture *textures, int n_textures);
+nnbvh_scene *nnbvh_scene_create_instanced_gpu_build_with_alpha_textures(
+    const nnbvh_prim *prims, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects, const float *verts,
+    int n_verts, const float *normals, const float *uvs, const float *prim_alpha, const float *prim_bounds,
+    const nnbvh_placement *placements, int n_placements, const nnbvh_animated_transform *animated, int max_prims_in_node,
+    int split_method, int device, const nnbvh_alpha_texture *textures, int n_textures);
 void nnbvh_scene_destroy(nnbvh_scene *s);
 int nnbvh_scene_bounds(const nnbvh_scene *s, float out_min_max[6]);
 /* what the baked device layout looks like: [0]=interior records, [1]=prim-stream slots,

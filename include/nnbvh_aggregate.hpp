@@ -259,6 +259,22 @@ class HipBVHAggregate {
         note_patches(orderedPrims, nPrims);
     }
 
+    // ... and a TWO-LEVEL scene of host-built trees with such triangles, in object definitions or in the top-level list
+    // (nnbvh_scene_create_instanced_with_alpha_textures): nodes[0, nTopNodes) is the top-level tree, the child trees
+    // follow; animated (nullable) has one entry per instance.  Inside an instance the texture is evaluated on the
+    // instance-space ray.  Alpha-tested patches may share the scene
+    HipBVHAggregate(const nnbvh_linear_node *nodes, int nNodes, int nTopNodes, const nnbvh_prim *orderedPrims, int nPrims,
+                    const float *verts, int nVerts, const std::vector<nnbvh_instance> &instances,
+                    const std::vector<nnbvh_alpha_texture> &alphaTextures, int device = 0,
+                    const nnbvh_animated_transform *animated = nullptr, const float *normals = nullptr,
+                    const float *primAlpha = nullptr, const float *uvs = nullptr) {
+        scene_ = nnbvh_scene_create_instanced_with_alpha_textures(
+            nodes, nNodes, nTopNodes, orderedPrims, nPrims, verts, nVerts, instances.data(), (int)instances.size(), animated,
+            normals, uvs, primAlpha, device, alphaTextures.data(), (int)alphaTextures.size());
+        if (!scene_) fatal("HipBVHAggregate: scene_create_instanced_with_alpha_textures");
+        note_patches(orderedPrims, nPrims);
+    }
+
     // A flat scene with its tree built AND baked on the device (nnbvh_scene_create_gpu_build_with_attributes; with
     // alphaTextures: nnbvh_scene_create_gpu_build_with_alpha_textures, for the kinds NNBVH_PRIM_ALPHATEX_TRIANGLE*).
     // primAlpha: per entry of `prims`, the caller's order.  splitMethod "sah" or "hlbvh".
@@ -294,14 +310,15 @@ class HipBVHAggregate {
     // directly in the top-level tree (may be empty); one instance entry per placement is generated behind them (kind
     // NNBVH_PRIM_INSTANCE, v[0] = j, id = topPrims.size() + j).  primBounds / primAlpha: per entry of the list
     // [topPrims, the generated instance entries, objects[0], objects[1], ...]; primBounds is read for host-only
-    // entries and the instances of animated placements only.  splitMethod "sah" or "hlbvh".
+    // entries and the instances of animated placements only.  splitMethod "sah" or "hlbvh".  alphaTextures: the table
+    // of the kinds NNBVH_PRIM_ALPHATEX_TRIANGLE* (nnbvh_scene_create_instanced_gpu_build_with_alpha_textures).
     static std::unique_ptr<HipBVHAggregate> BuildTwoLevelOnDevice(
         const std::vector<nnbvh_prim> &topPrims, const std::vector<float> &verts,
         const std::vector<std::vector<nnbvh_prim>> &objects, const std::vector<nnbvh_placement> &placements,
         int maxPrimsInNode = 4, const std::string &splitMethod = "sah", int device = 0,
         const std::vector<nnbvh_animated_transform> *animated = nullptr, const std::vector<float> *primBounds = nullptr,
         const std::vector<float> *normals = nullptr, const std::vector<float> *primAlpha = nullptr,
-        const std::vector<float> *uvs = nullptr) {
+        const std::vector<float> *uvs = nullptr, const std::vector<nnbvh_alpha_texture> *alphaTextures = nullptr) {
         std::vector<nnbvh_prim> prims(topPrims);
         for (size_t j = 0; j < placements.size(); ++j)
             prims.push_back(nnbvh_prim{NNBVH_PRIM_INSTANCE, (int32_t)(topPrims.size() + j), {(int32_t)j, 0, 0, 0}});
@@ -312,11 +329,19 @@ class HipBVHAggregate {
             first.push_back((int32_t)prims.size());
         }
         const int method = splitMethod == "sah" ? NNBVH_SPLIT_SAH : splitMethod == "hlbvh" ? NNBVH_SPLIT_HLBVH : -1;
-        nnbvh_scene *scene = nnbvh_scene_create_instanced_gpu_build(
-            prims.data(), (int)prims.size(), nTop, first.data(), (int)objects.size(), verts.data(),
-            (int)(verts.size() / 3), normals ? normals->data() : nullptr, uvs ? uvs->data() : nullptr,
-            primAlpha ? primAlpha->data() : nullptr, primBounds ? primBounds->data() : nullptr, placements.data(),
-            (int)placements.size(), animated ? animated->data() : nullptr, maxPrimsInNode, method, device);
+        const float *nrm = normals ? normals->data() : nullptr, *uv = uvs ? uvs->data() : nullptr;
+        const float *pa = primAlpha ? primAlpha->data() : nullptr, *pb = primBounds ? primBounds->data() : nullptr;
+        const nnbvh_animated_transform *an = animated ? animated->data() : nullptr;
+        nnbvh_scene *scene =
+            alphaTextures
+                ? nnbvh_scene_create_instanced_gpu_build_with_alpha_textures(
+                      prims.data(), (int)prims.size(), nTop, first.data(), (int)objects.size(), verts.data(),
+                      (int)(verts.size() / 3), nrm, uv, pa, pb, placements.data(), (int)placements.size(), an,
+                      maxPrimsInNode, method, device, alphaTextures->data(), (int)alphaTextures->size())
+                : nnbvh_scene_create_instanced_gpu_build(
+                      prims.data(), (int)prims.size(), nTop, first.data(), (int)objects.size(), verts.data(),
+                      (int)(verts.size() / 3), nrm, uv, pa, pb, placements.data(), (int)placements.size(), an,
+                      maxPrimsInNode, method, device);
         if (!scene) {
             fatal("HipBVHAggregate::BuildTwoLevelOnDevice");
             return nullptr;

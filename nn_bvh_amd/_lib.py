@@ -106,6 +106,7 @@ EXPORTS = [
     "nnbvh_scene_create_with_alpha_textures", "nnbvh_scene_create_gpu_build_with_alpha_textures",
     "nnbvh_kd_scene_create_with_alpha_textures", "nnbvh_kd_scene_create_gpu_build_with_alpha_textures",
     "nnbvh_instance_launches",
+    "nnbvh_scene_create_instanced_with_alpha_textures", "nnbvh_scene_create_instanced_gpu_build_with_alpha_textures",
 ]
 
 
@@ -333,6 +334,13 @@ def lib():
                                                          i32, i32, i32]
     L.nnbvh_scene_read.restype = i32
     L.nnbvh_scene_read.argtypes = [vp, i32, vp, ctypes.c_size_t]
+    # ... and the two-level calls with the alpha-texture table behind the same arguments
+    L.nnbvh_scene_create_instanced_with_alpha_textures.restype = vp
+    L.nnbvh_scene_create_instanced_with_alpha_textures.argtypes = (
+        list(L.nnbvh_scene_create_instanced_with_attributes.argtypes) + [vp, i32])
+    L.nnbvh_scene_create_instanced_gpu_build_with_alpha_textures.restype = vp
+    L.nnbvh_scene_create_instanced_gpu_build_with_alpha_textures.argtypes = (
+        list(L.nnbvh_scene_create_instanced_gpu_build.argtypes) + [vp, i32])
     L.nnbvh_build_forest_create_gpu.restype = vp
     L.nnbvh_build_forest_create_gpu.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32]
     L.nnbvh_build_forest_create_gpu_hlbvh.restype = vp

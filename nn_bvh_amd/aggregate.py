@@ -187,7 +187,9 @@ class BVHAggregate:
         prim_alpha: one constant alpha per entry of ordered_prims, read for alpha-tested patches (kinds 8 .. 15);
         uvs: per-vertex (u, v), read for the alpha-tested patches of meshes with uv (kinds 12 .. 15) and the
         triangles with an image-textured alpha (kinds 16 .. 19; None: the default corners);
-        alpha_textures: a sequence of AlphaTexture, the table kinds 16 .. 19 index with v[3] (flat scenes only)."""
+        alpha_textures: a sequence of AlphaTexture, the table kinds 16 .. 19 index with v[3]; with instances the
+        scene is two-level (nnbvh_scene_create_instanced_with_alpha_textures) and a textured triangle inside an object
+        is evaluated on the instance-space ray."""
         self = cls.__new__(cls)
         self._init(nodes, ordered_prims, verts, device, None, instances, n_top_nodes, animated, normals, prim_alpha, uvs,
                    alpha_textures)
@@ -252,7 +254,8 @@ class BVHAggregate:
 
     @classmethod
     def build_two_level_on_device(cls, top_prims, verts, objects, placements, max_prims_in_node=4, split_method="sah",
-                                  animated=None, prim_bounds=None, normals=None, prim_alpha=None, uvs=None, device=0):
+                                  animated=None, prim_bounds=None, normals=None, prim_alpha=None, uvs=None, device=0,
+                                  alpha_textures=None):
         """A two-level scene (instancing.assemble_two_level's inputs: top-level primitives, object definitions,
         placements (object index, render_from_prim 3x4, prim_from_render 3x4)) with every tree built AND baked on
         the GPU (nnbvh_scene_create_instanced_gpu_build); byte-identical device arrays and the same results as
@@ -260,7 +263,9 @@ class BVHAggregate:
         list, the generated instance entries, then the objects); prim_bounds is read for host-only primitives and
         the instances of animated placements only.  animated: ANIMATED_DTYPE, one per placement.  `nodes` /
         `ordered_prims` are not available on this object; `instances` is the placement table in the form
-        ShadingMesh.set_instances takes (root / n_nodes zero: the trees live on the device)."""
+        ShadingMesh.set_instances takes (root / n_nodes zero: the trees live on the device).  alpha_textures: a
+        sequence of AlphaTexture, the table the kinds 16 .. 19 index with v[3], in objects and in the top-level list
+        (nnbvh_scene_create_instanced_gpu_build_with_alpha_textures); uvs gives them their (u, v)."""
         if split_method not in ("sah", "hlbvh"):
             raise NNBVHError(f'GPU build supports "sah" and "hlbvh", not "{split_method}"')
         self = cls.__new__(cls)
@@ -281,15 +286,24 @@ class BVHAggregate:
         self.animated = None if animated is None else np.ascontiguousarray(animated, _lib.ANIMATED_DTYPE)
         if self.animated is not None and len(self.animated) != len(placements):
             raise NNBVHError(f"animated has {len(self.animated)} entries for {len(placements)} placements")
+        if alpha_textures is not None:  # (the length faults as NNBVHError, not as reshape's ValueError)
+            for name, a, n, w in (("normals", normals, len(verts), 3), ("uvs", uvs, len(verts), 2),
+                                  ("prim_alpha", prim_alpha, len(prims), 1)):
+                if a is not None and np.asarray(a).size != n * w:
+                    raise NNBVHError(f"{name} has {np.asarray(a).size // w} entries where the scene has {n}")
         pb = None if prim_bounds is None else np.ascontiguousarray(prim_bounds, np.float32).reshape(len(prims), 6)
         nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(len(verts), 3)
         pa = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(len(prims))
         uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(len(verts), 2)
         opt = lambda a: ptr(a) if a is not None and len(a) else None  # noqa: E731
-        self._h = L.nnbvh_scene_create_instanced_gpu_build(
-            opt(prims), len(prims), n_top, ptr(first), len(objects), opt(verts), len(verts), opt(nrm), opt(uv), opt(pa),
-            opt(pb), opt(table), len(table), opt(self.animated), int(max_prims_in_node), SPLIT_METHODS[split_method],
-            self.device)
+        args = (opt(prims), len(prims), n_top, ptr(first), len(objects), opt(verts), len(verts), opt(nrm), opt(uv), opt(pa),
+                opt(pb), opt(table), len(table), opt(self.animated), int(max_prims_in_node), SPLIT_METHODS[split_method],
+                self.device)
+        if alpha_textures is not None:
+            self.alpha_textures, n_tex = _lib.alpha_texture_table(alpha_textures)
+            self._h = L.nnbvh_scene_create_instanced_gpu_build_with_alpha_textures(*args, self.alpha_textures, n_tex)
+        else:
+            self._h = L.nnbvh_scene_create_instanced_gpu_build(*args)
         if not self._h:
             raise NNBVHError("nnbvh_scene_create_instanced_gpu_build: " + _lib.last_error())
         self._read_info()
@@ -336,9 +350,24 @@ class BVHAggregate:
         self.ordered_prims = np.ascontiguousarray(ordered_prims, PRIM_DTYPE)
         self.verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
         self.device = int(device)
-        if alpha_textures is not None:
-            if instances is not None and len(instances):
-                raise NNBVHError("alpha_textures: image-textured alpha is for flat scenes, not two-level ones")
+        if alpha_textures is not None and instances is not None and len(instances):
+            self.instances = np.ascontiguousarray(instances, _lib.INSTANCE_DTYPE)
+            f32 = lambda a, w: None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, w)  # noqa: E731
+            self.normals, self.uvs = f32(normals, 3), f32(uvs, 2)
+            self.prim_alpha = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(-1)
+            self.animated = None if animated is None else np.ascontiguousarray(animated, _lib.ANIMATED_DTYPE)
+            for name, a, n in (("normals", self.normals, len(self.verts)), ("uvs", self.uvs, len(self.verts)),
+                               ("prim_alpha", self.prim_alpha, len(self.ordered_prims)),
+                               ("animated", self.animated, len(self.instances))):
+                if a is not None and len(a) != n:
+                    raise NNBVHError(f"{name} has {len(a)} entries where the scene has {n}")
+            self.alpha_textures, n_tex = _lib.alpha_texture_table(alpha_textures)
+            opt = lambda a: ptr(a) if a is not None else None  # noqa: E731
+            self._h = L.nnbvh_scene_create_instanced_with_alpha_textures(
+                ptr(self.nodes), len(self.nodes), int(n_top_nodes), ptr(self.ordered_prims), len(self.ordered_prims),
+                ptr(self.verts), len(self.verts), ptr(self.instances), len(self.instances), opt(self.animated),
+                opt(self.normals), opt(self.uvs), opt(self.prim_alpha), self.device, self.alpha_textures, n_tex)
+        elif alpha_textures is not None:
             self.normals = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
             self.prim_alpha = None if prim_alpha is None else np.ascontiguousarray(prim_alpha, np.float32).reshape(-1)
             self.uvs = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(-1, 2)

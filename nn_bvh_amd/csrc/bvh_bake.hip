@@ -369,7 +369,7 @@ bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int
                  "(nnbvh_scene_create_with_attributes)";
         return false;
     }
-    if ((flags & 128) && (flags & 32)) {
+    if ((flags & 128) && (flags & 32) && !instances) {  // (a two-level scene's ALPHA = 2 instances run both)
         *error = "scene_create: image-textured alpha on triangles and alpha-tested patches in one scene are not supported";
         return false;
     }
@@ -408,7 +408,8 @@ bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int
     out->has_host_prims = flags & 1;
     out->has_patches = (flags & 4) ? 1 : 0;
     // 2: alpha-tested PATCHES present (the ALPHA = 2 kernels), 3: image-textured alpha on triangles (ALPHA = 3)
-    out->has_alpha = (flags & 128) ? 3 : ((flags & 32) ? 2 : ((flags & 8) ? 1 : 0));
+    // (a two-level scene has no ALPHA = 3 instances: its ALPHA = 2 ones evaluate the textures, so it reports 2)
+    out->has_alpha = (flags & 128) ? (instances ? 2 : 3) : ((flags & 32) ? 2 : ((flags & 8) ? 1 : 0));
     return true;
 }
 

@@ -149,7 +149,7 @@ void nnbvh::fill_anim_entry(const nnbvh_animated_transform &a, float *t) {
 // ---- image-textured alpha (kinds 16 .. 19) ---------------------------------------------------------------------
 // Everything the kernel indexes a texture with, checked on the host before a device is looked at; `fn` names the call.
 bool nnbvh::check_alpha_textures(const char *fn, const nnbvh_prim *prims, int n_prims, const float *normals,
-                                 const nnbvh_alpha_texture *textures, int n_textures) {
+                                 const nnbvh_alpha_texture *textures, int n_textures, bool with_patches) {
     auto fault = [&](const std::string &what) {
         set_error(std::string(fn) + ": " + what);
         return false;
@@ -177,7 +177,7 @@ bool nnbvh::check_alpha_textures(const char *fn, const nnbvh_prim *prims, int n_
         if (is_smooth_alphatex_kind(p.kind) && !normals)
             return fault("NNBVH_PRIM_ALPHATEX_TRIANGLE_SMOOTH primitives need the vertex normals");
     }
-    if (textured && patches)
+    if (textured && patches && !with_patches)  // (two-level scenes run both through their ALPHA = 2 instances)
         return fault("image-textured alpha on triangles and alpha-tested patches (kinds 8 .. 15) in one scene are not "
                      "supported");
     return true;
@@ -221,7 +221,7 @@ bool nnbvh::upload_alpha_textures(int device, const nnbvh_alpha_texture *texture
 }
 
 // the scene's descriptor table and texel pool, uploaded once; false: the scene is destroyed
-static bool attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *textures, int n_textures) {
+bool nnbvh::attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *textures, int n_textures) {
     if (!s || n_textures <= 0) return s != nullptr;
     int64_t total = 0;
     if (!upload_alpha_textures(s->device, textures, n_textures, &s->d_alpha_tex, &s->d_alpha_texels, &total)) {
@@ -425,7 +425,7 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
                 return nullptr;
             }
         } else if (is_triangle_kind(p.kind)) nv = nslots = 3;
-        else if (alpha_textures && is_alphatex_kind(p.kind)) {  // flat scenes (checked by check_alpha_textures)
+        else if (alpha_textures && is_alphatex_kind(p.kind)) {  // (checked by check_alpha_textures)
             nv = 3;
             nslots = alphatex_slots(p.kind);
         } else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = nslots = 4;
@@ -468,7 +468,7 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
                                     : (int32_t) ~(uint32_t)slot_of[(size_t)nodes[i].offset];
     };
     std::vector<float> stream((size_t)n_slots * 4, 0.0f);
-    bool has_host = false, has_alpha = false, has_alpha_patch = false;
+    bool has_host = false, has_alpha = false, has_alpha_patch = false, has_alpha_tex = false;
     for (int k = 0; k < n_prims; ++k) {
         const nnbvh_prim &p = prims[k];
         float *s = &stream[(size_t)slot_of[(size_t)k] * 4];
@@ -494,7 +494,8 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
             std::memcpy(&s[7], &flags, 4);
             continue;
         }
-        const int nv = is_triangle_kind(p.kind) ? 3 : 4;
+        const bool tri = is_triangle_kind(p.kind) || is_alphatex_kind(p.kind);
+        const int nv = tri ? 3 : 4;
         for (int j = 0; j < nv; ++j) put3(s, 4 * j, verts + 3 * (size_t)p.v[j]);
         if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) flags |= kPrimPatch;
         if (is_alpha_patch_kind(p.kind)) {  // as k_bake_stream lays them out (bvh_bake.hip)
@@ -524,7 +525,24 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
                 for (int j = 0; j < 3; ++j) put3(s, 12 + 4 * j, normals + 3 * (size_t)p.v[j]);
             }
         }
-        if (is_triangle_kind(p.kind) &&
+        if (is_alphatex_kind(p.kind)) {  // as k_bake_stream lays them out (bvh_bake.hip)
+            flags |= kPrimAlpha | kPrimAlphaTex | (is_flipped_alphatex_kind(p.kind) ? kPrimFlipN : 0u);
+            std::memcpy(&s[11], &p.v[3], 4);  // the texture index where kind 4 keeps alpha
+            has_alpha = has_alpha_tex = true;
+            float *u = s + 12;
+            if (is_smooth_alphatex_kind(p.kind)) {
+                flags |= kPrimSmooth;
+                for (int j = 0; j < 3; ++j) put3(s, 12 + 4 * j, normals + 3 * (size_t)p.v[j]);
+                u = s + 24;
+            }
+            // the three (u, v) pairs; the reference's default corners for a mesh without
+            const float corners[6] = {0, 0, 1, 0, 1, 1};
+            for (int j = 0; j < 3; ++j) {
+                u[2 * j] = uvs ? uvs[2 * (size_t)p.v[j]] : corners[2 * j];
+                u[2 * j + 1] = uvs ? uvs[2 * (size_t)p.v[j] + 1] : corners[2 * j + 1];
+            }
+        }
+        if (tri &&
             triangle_is_degenerate(verts + 3 * (size_t)p.v[0], verts + 3 * (size_t)p.v[1],
                                    verts + 3 * (size_t)p.v[2]))
             flags |= kPrimDegenerate;
@@ -569,7 +587,8 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
     s->root_ref = ref_of(0);
     s->instanced = n_instances > 0 ? 1 : 0;
     s->has_host_prims = (has_host || has_alpha) ? 1 : 0;  // an alpha re-trace that hits voids the ray like a host primitive
-    s->has_alpha = has_alpha_patch ? 2 : (has_alpha ? 1 : 0);
+    // (textured triangles: 2 as well, the two-level ALPHA = 2 instances evaluate them; 3 is the flat scenes')
+    s->has_alpha = (has_alpha_patch || has_alpha_tex) ? 2 : (has_alpha ? 1 : 0);
     s->has_patches = 1;  // two-level scenes always run the general kernels
     s->max_grid_threads = s->n_cus * 8 * kBlockThreads;
     // one allocation, as bake_on_device makes it: records, then the 256-B aligned primitive stream + 64 B
@@ -781,6 +800,44 @@ nnbvh_scene *nnbvh_scene_create_instanced_with_attributes(const nnbvh_linear_nod
             }
     return create_scene(nodes, n_nodes, n_top_nodes, prims, n_prims, verts, n_verts, instances, n_instances, device,
                         animated, normals, prim_alpha, uvs);
+}
+
+nnbvh_scene *nnbvh_scene_create_instanced_with_alpha_textures(const nnbvh_linear_node *nodes, int n_nodes, int n_top_nodes,
+                                                              const nnbvh_prim *prims, int n_prims, const float *verts,
+                                                              int n_verts, const nnbvh_instance *instances,
+                                                              int n_instances, const nnbvh_animated_transform *animated,
+                                                              const float *normals, const float *uvs,
+                                                              const float *prim_alpha, int device,
+                                                              const nnbvh_alpha_texture *textures, int n_textures) {
+    const char *fn = "nnbvh_scene_create_instanced_with_alpha_textures";
+    if (!check_alpha_textures(fn, prims, n_prims, normals, textures, n_textures, true)) return nullptr;
+    if (n_instances <= 0 || !instances) {  // (create_scene bakes a scene without instances as a flat one)
+        set_error(std::string(fn) + ": a two-level scene needs its instance table (flat scenes: "
+                                    "nnbvh_scene_create_with_alpha_textures)");
+        return nullptr;
+    }
+    if (animated)
+        for (int k = 0; k < n_instances; ++k)
+            if (animated[k].actually_animated && !(animated[k].end_time > animated[k].start_time)) {
+                set_error("scene_create: animated instance with an empty time range");
+                return nullptr;
+            }
+    nnbvh_scene *s = create_scene(nodes, n_nodes, n_top_nodes, prims, n_prims, verts, n_verts, instances, n_instances,
+                                  device, animated, normals, prim_alpha, uvs, true);
+    return attach_alpha_textures(s, textures, n_textures) ? s : nullptr;
+}
+
+nnbvh_scene *nnbvh_scene_create_instanced_gpu_build_with_alpha_textures(
+    const nnbvh_prim *prims, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects, const float *verts,
+    int n_verts, const float *normals, const float *uvs, const float *prim_alpha, const float *prim_bounds,
+    const nnbvh_placement *placements, int n_placements, const nnbvh_animated_transform *animated, int max_prims_in_node,
+    int split_method, int device, const nnbvh_alpha_texture *textures, int n_textures) {
+    const char *fn = "nnbvh_scene_create_instanced_gpu_build_with_alpha_textures";
+    if (!check_alpha_textures(fn, prims, n_prims, normals, textures, n_textures, true)) return nullptr;
+    nnbvh_scene *s = create_instanced_gpu_build(prims, n_prims, n_top_prims, object_first, n_objects, verts, n_verts,
+                                                normals, uvs, prim_alpha, prim_bounds, placements, n_placements, animated,
+                                                max_prims_in_node, split_method, device, true);
+    return attach_alpha_textures(s, textures, n_textures) ? s : nullptr;
 }
 
 void nnbvh_transform_bounds(const float m[12], const float in[6], float out[6]) {

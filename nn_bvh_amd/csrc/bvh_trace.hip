@@ -96,6 +96,10 @@ constexpr int kEnter = (int)0x80000002;   // INST = 2: the lane waits to enter a
 // ALPHA = 3: the scene holds triangles whose alpha is an image texture (kPrimAlphaTex; flat scenes, no alpha-tested
 // patches): the ALPHA = 1 path where, for such a triangle, alpha is FloatImageTexture::Evaluate at the hit's (u, v)
 // (alpha_texture_math.h) instead of the constant in slot 2.  Constant-alpha triangles run as in ALPHA = 1.
+// Two-level scenes have no ALPHA = 3 instances: a two-level scene with a textured triangle reports has_alpha = 2 and
+// runs the INST = 1 / 2 x ALPHA = 2 instances, which carry the same branch (kAlphaTex below) beside the patches' one.
+// There the barycentrics and the hash are those of the instance-space ray (the top-level list: the ray as given),
+// and textured triangles and alpha-tested patches may share a scene.  The flat ALPHA = 2 instances do not have it.
 // SOA = 1 (lean instances of modes 0, 2, 3 only): a batch without nnbvh_ray records (rays == nullptr) is read as the
 // SOA<Ray> slices of a wavefront queue — no gather pass.  Its own instances: the mere presence of the second fetch
 // path in the refill trip cost the one-launch step 1.3 % (9.31 -> 9.44 ms).
@@ -318,6 +322,9 @@ void trace_kernel(TraceParams p) {
     static_assert(ALPHA != 3 || (INST == 0 && W == 8 && MODE != 3), "textured alpha: flat scenes, window 8, modes 0 / 1 / 2");
     static_assert(!HOSTC || (PATCH && (MODE == 0 || MODE == 2 || (MODE == 3 && !ALPHA && W == 8)) && !SOA),
                   "candidate mode: general instances of modes 0 / 2 / 3");
+    // the instance evaluates image-textured alpha (kPrimAlphaTex): the flat ALPHA = 3 instances, and the ALPHA = 2
+    // instances of two-level scenes, which are the ones such a scene gets when it holds a textured triangle
+    constexpr bool kAlphaTex = ALPHA == 3 || (ALPHA == 2 && INST != 0);
     constexpr int BT = block_threads(MODEW, INST, PATCH);
     // the stack window: entry k of a lane = (child reference, entry distance), the two words 64 dwords
     // apart so that one ds_read2st64 / ds_write2st64 with one address moves both
@@ -563,12 +570,12 @@ void trace_kernel(TraceParams p) {
                                     {s0.x, s0.y, s0.z}, {s1.x, s1.y, s1.z},
                                     {s2.x, s2.y, s2.z}, x0, x1, x2, th, kLean ? &masks : nullptr);
                 next = slot + ((ALPHA && (flags & kPrimSmooth)) ? 6 : 3);
-                if constexpr (ALPHA == 3) next += (flags & kPrimAlphaTex) ? 2 : 0;  // the (u, v) slots
+                if constexpr (kAlphaTex) next += (flags & kPrimAlphaTex) ? 2 : 0;  // the (u, v) slots
                 if (ALPHA && hit && (flags & kPrimAlpha)) {
                     // GeometricPrimitive::Intersect, cpu/primitive.cpp:57-70 (IntersectP takes
                     // the same route, :79-81): stochastic alpha test on the ray as given
                     [[maybe_unused]] float aTex = 0.0f;
-                    if constexpr (ALPHA == 3) {
+                    if constexpr (kAlphaTex) {
                         // alpha.Evaluate(si->intr) of a FloatImageTexture: the (u, v) slots, the descriptor and the
                         // texels are read here, on a hit only, and are dead before the normals are fetched below
                         if (flags & kPrimAlphaTex) {
@@ -583,7 +590,7 @@ void trace_kernel(TraceParams p) {
                                                       p.alphaTexels);
                         }
                     }
-                    const float a = (ALPHA == 3 && (flags & kPrimAlphaTex)) ? aTex : s2.w;
+                    const float a = (kAlphaTex && (flags & kPrimAlphaTex)) ? aTex : s2.w;
                     if (a < 1) {
                         const V3 rd = {cold[kColdD][lane], cold[kColdD + 1][lane],
                                        cold[kColdD + 2][lane]};

@@ -88,7 +88,8 @@ struct nnbvh_scene {
     int has_host_prims = 0;
     int has_patches = 1;    // 0: no bilinear patches, the lean kernels (no ray direction parked in LDS) run
     int has_alpha = 0;      // 1: alpha-tested triangles present (the ALPHA kernels run), 2: alpha-tested patches too,
-                            // 3: triangles with an image-textured alpha (and maybe constant ones; no alpha-tested patches)
+                            // 3: triangles with an image-textured alpha (and maybe constant ones; no alpha-tested patches);
+                            // a two-level scene reports 2 for textured triangles too (its ALPHA = 2 instances evaluate them)
     int fused_batches = 1;  // nnbvh_trace_batches_device: one mode-3 launch where the batches allow it
     int int_repeat = 3;
     int prim_repeat = 2;
@@ -143,6 +144,20 @@ void fill_anim_entry(const nnbvh_animated_transform &a, float *t);
 // `device` for a scene of either type (bvh_capi.cpp).  false: the error text is set; the pointers hold what was allocated
 bool upload_alpha_textures(int device, const nnbvh_alpha_texture *textures, int n_textures, void **d_table,
                            float **d_texels, int64_t *n_texels);
+
+// the descriptor table and texel pool of a BVH scene (flat or two-level), uploaded once and counted in device_bytes
+// (bvh_capi.cpp).  s == nullptr or no texture: nothing to do, s != nullptr is returned.  false after a failed upload:
+// the scene is destroyed, the error text is set
+bool attach_alpha_textures(nnbvh_scene *s, const nnbvh_alpha_texture *textures, int n_textures);
+
+// nnbvh_scene_create_instanced_gpu_build and its twin with an alpha-texture table (capi_two_level.cpp).  alpha_textures:
+// the caller has checked the table (check_alpha_textures) and attaches it; without it the kinds 16 .. 19 are refused
+nnbvh_scene *create_instanced_gpu_build(const nnbvh_prim *prims, int n_prims, int n_top_prims,
+                                        const int32_t *object_first, int n_objects, const float *verts, int n_verts,
+                                        const float *normals, const float *uvs, const float *prim_alpha,
+                                        const float *prim_bounds, const nnbvh_placement *placements, int n_placements,
+                                        const nnbvh_animated_transform *animated, int max_prims_in_node,
+                                        int split_method, int device, bool alpha_textures);
 
 // ... and the kd-tree scenes' (kd_trace.h) under the same name, for the code that serves both scene types
 inline KdWorkspace *workspace_for(nnbvh_kd_scene *s, hipStream_t stream) { return kd_workspace_for(s, stream); }

@@ -4,6 +4,7 @@
 // over the instances' transformed bounds, come from the device builders' cores (bvh_build_gpu.hip); the trees are put
 // into one numbering and baked by bvh_bake.hip.  nnbvh_build_forest_create_gpu[_hlbvh], at the end, is that forest pass alone.  The device
 // arrays are byte for byte those of nn_bvh_amd.instancing.assemble_two_level + nnbvh_scene_create_instanced_with_attributes.
+// create_instanced_gpu_build is the body of that call and of its twin with an alpha-texture table (bvh_capi.cpp).
 // Host code only.
 #include <algorithm>
 #include <chrono>
@@ -34,6 +35,7 @@ struct PrimListCheck {
     const nnbvh_animated_transform *animated = nullptr;
     const float *prim_bounds = nullptr, *normals = nullptr, *uvs = nullptr, *prim_alpha = nullptr;
     bool scene = true;  // false: a forest of trees: attributes are not asked for, instance entries have no place
+    bool alpha_textures = false;  // the scene call with an alpha-texture table: check_alpha_textures has seen kinds 16 .. 19
     const char *fn = "";  // (forests) the call's name in front of its own message
 };
 bool check_prims(const nnbvh_prim *prims, int n_prims, int n_verts, const PrimListCheck &c) {
@@ -62,8 +64,8 @@ bool check_prims(const nnbvh_prim *prims, int n_prims, int n_verts, const PrimLi
                              "(nnbvh_scene_create_with_attributes)");
         } else if (is_triangle_kind(p.kind)) nv = 3;
         else if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) nv = 4;
-        else if (is_alphatex_kind(p.kind)) {  // a triangle for a tree; two-level scenes have no alpha-texture table
-            if (c.scene) return fault(std::string("scene_create: ") + kAlphaTexElsewhere);
+        else if (is_alphatex_kind(p.kind)) {  // a triangle for a tree; a scene needs the call with an alpha-texture table
+            if (c.scene && !c.alpha_textures) return fault(std::string("scene_create: ") + kAlphaTexElsewhere);
             nv = 3;
         } else return fault("scene_create: unknown primitive kind");
         for (int j = 0; j < nv; ++j)
@@ -76,7 +78,7 @@ bool check_prims(const nnbvh_prim *prims, int n_prims, int n_verts, const PrimLi
 bool check_arguments(const nnbvh_prim *prims, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects,
                      const float *verts, int n_verts, const float *normals, const float *uvs, const float *prim_alpha,
                      const float *prim_bounds, const nnbvh_placement *placements, int n_placements,
-                     const nnbvh_animated_transform *animated, int split_method) {
+                     const nnbvh_animated_transform *animated, int split_method, bool alpha_textures) {
     if (!prims || !verts || !object_first || !placements || n_prims <= 0 || n_verts <= 0 || n_top_prims <= 0 ||
         n_objects <= 0 || n_placements <= 0)
         return fault(std::string(kFn) + "null or empty input array");
@@ -101,6 +103,7 @@ bool check_arguments(const nnbvh_prim *prims, int n_prims, int n_top_prims, cons
     c.normals = normals;
     c.uvs = uvs;
     c.prim_alpha = prim_alpha;
+    c.alpha_textures = alpha_textures;
     return check_prims(prims, n_prims, n_verts, c);
 }
 
@@ -160,12 +163,24 @@ bool put(T *dst, const T *src, size_t count, hipStream_t stream, const char *wha
 }  // namespace
 
 extern "C" nnbvh_scene *nnbvh_scene_create_instanced_gpu_build(
-    const nnbvh_prim *prims_in, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects,
+    const nnbvh_prim *prims, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects,
     const float *verts, int n_verts, const float *normals, const float *uvs, const float *prim_alpha,
     const float *prim_bounds, const nnbvh_placement *placements, int n_placements,
     const nnbvh_animated_transform *animated, int max_prims_in_node, int split_method, int device) {
+    return create_instanced_gpu_build(prims, n_prims, n_top_prims, object_first, n_objects, verts, n_verts, normals, uvs,
+                                      prim_alpha, prim_bounds, placements, n_placements, animated, max_prims_in_node,
+                                      split_method, device, false);
+}
+
+// (nnbvh_scene_create_instanced_gpu_build_with_alpha_textures is beside the other calls with a table, bvh_capi.cpp)
+nnbvh_scene *nnbvh::create_instanced_gpu_build(
+    const nnbvh_prim *prims_in, int n_prims, int n_top_prims, const int32_t *object_first, int n_objects,
+    const float *verts, int n_verts, const float *normals, const float *uvs, const float *prim_alpha,
+    const float *prim_bounds, const nnbvh_placement *placements, int n_placements,
+    const nnbvh_animated_transform *animated, int max_prims_in_node, int split_method, int device,
+    bool alpha_textures) {
     if (!check_arguments(prims_in, n_prims, n_top_prims, object_first, n_objects, verts, n_verts, normals, uvs,
-                         prim_alpha, prim_bounds, placements, n_placements, animated, split_method))
+                         prim_alpha, prim_bounds, placements, n_placements, animated, split_method, alpha_textures))
         return nullptr;
     const int n_dev = nnbvh_device_count();
     if (n_dev <= 0 || device < 0 || device >= n_dev) {

@@ -85,7 +85,7 @@ constexpr bool is_flat_alpha_kind(int kind) {
 }
 
 // image-textured alpha on triangles: kind = 16 + flipped + 2 * smooth.  NOT an is_triangle_kind: only the builders and
-// the creation calls with an alpha-texture table (flat BVH scenes, kd scenes) take them
+// the creation calls with an alpha-texture table (flat and two-level BVH scenes, kd scenes) take them
 constexpr bool is_alphatex_kind(int kind) { return kind >= NNBVH_PRIM_ALPHATEX_TRIANGLE && kind <= NNBVH_PRIM_ALPHATEX_TRIANGLE_SMOOTH_FLIPPED; }
 constexpr bool is_smooth_alphatex_kind(int kind) { return is_alphatex_kind(kind) && ((kind - NNBVH_PRIM_ALPHATEX_TRIANGLE) & 2); }
 constexpr bool is_flipped_alphatex_kind(int kind) { return is_alphatex_kind(kind) && ((kind - NNBVH_PRIM_ALPHATEX_TRIANGLE) & 1); }
@@ -95,11 +95,14 @@ constexpr int kMaxAlphaTexSize = 1 << 24;
 constexpr const char *kAlphaTexElsewhere =
     "unknown primitive kind (image-textured alpha, kinds 16 .. 19, is for flat BVH scenes: "
     "nnbvh_scene_create_with_alpha_textures / nnbvh_scene_create_gpu_build_with_alpha_textures, and kd scenes: "
-    "nnbvh_kd_scene_create_with_alpha_textures / nnbvh_kd_scene_create_gpu_build_with_alpha_textures)";
+    "nnbvh_kd_scene_create_with_alpha_textures / nnbvh_kd_scene_create_gpu_build_with_alpha_textures, and two-level "
+    "scenes: nnbvh_scene_create_instanced_with_alpha_textures / "
+    "nnbvh_scene_create_instanced_gpu_build_with_alpha_textures)";
 // Everything a kernel indexes a texture with, checked on the host before a device is looked at; `fn` names the call
-// (bvh_capi.cpp; shared by the flat BVH and the kd creation calls)
+// (bvh_capi.cpp; shared by the flat BVH, the two-level and the kd creation calls).  with_patches: alpha-tested patches
+// (kinds 8 .. 15) may share the scene with the textured triangles (two-level scenes only)
 bool check_alpha_textures(const char *fn, const nnbvh_prim *prims, int n_prims, const float *normals,
-                          const nnbvh_alpha_texture *textures, int n_textures);
+                          const nnbvh_alpha_texture *textures, int n_textures, bool with_patches = false);
 
 constexpr int kMaxStack = 64;  // the reference's nodesToVisit[64], aggregates.cpp:538
 

@@ -53,7 +53,7 @@ inline bool pick_trace_instance(const TraceTraits &t, int mode, bool candidates,
     if (mode < 0 || mode > 3 || (mode == 3 && (t.window != 8 || t.has_alpha))) return false;  // mode 3: no such forms
     const int hostc = candidates && mode != 1;
     if (hostc || t.instanced || t.has_alpha) {              // the general window-8 forms: INST x ALPHA x HOSTC
-        if (t.has_alpha == 3 && t.instanced) return false;  // image-textured alpha: flat scenes only
+        if (t.has_alpha == 3 && t.instanced) return false;  // no such form: a two-level scene with textured triangles reports 2
         *out = {mode, 8, !t.instanced ? 0 : (t.animated ? 2 : 1), 1, t.has_alpha, 0, hostc};
     } else if (is_lean(t) && !(soa && mode == 1)) {
         *out = {mode, 8, 0, 0, 0, soa, 0};
