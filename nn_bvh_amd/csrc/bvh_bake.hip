@@ -1,10 +1,10 @@
 // bvh_bake.hip — the traversal kernels' data layout (nnbvh_internal.h) produced on the device from
-// a device-resident LinearBVHNode array + leaf-ordered primitive table: the counterpart of the
-// host baking in bvh_capi.cpp (create_scene), bit for bit, for scenes of triangles, bilinear
-// patches and host-only primitives.  With the device builders (bvh_build_gpu.hip) a scene goes
-// from triangles to traceable without its tree ever visiting the host.  Two-level scenes
-// (capi_two_level.cpp) add the bounds an instance presents to the top-level builder, the child trees'
-// move into the scene's numbering, and the instance-aware form of the bake (InstanceBake).
+// a device-resident LinearBVHNode array + leaf-ordered primitive table.  The ONE writer of that layout: every BVH
+// creation route ends in bake_on_device, the caller's validated tree uploaded by bvh_capi.cpp (create_scene) as well as
+// the trees of the device builders (bvh_build_gpu.hip), which go from triangles to traceable without visiting the
+// host.  tests/test_bake_golden.py holds the bytes to a recording.  Two-level scenes add the bounds an instance
+// presents to the top-level builder and the child trees' move into the scene's numbering (capi_two_level.cpp), and
+// the instance-aware form of the bake (InstanceBake).
 //
 // Four streaming passes over 24-32-B records plus three prefix sums; HBM-bound.
 #include <hip/hip_runtime.h>
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(kBk) void k_bake_node_flags(const nnbvh_linear_node
     if (i >= n) return;
     const nnbvh_linear_node nd = nodes[i];
     interior[i] = nd.nprims == 0 ? 1 : 0;
-    // (two-level scenes: create_scene walks, and marks, only the trees a placement names)
+    // (two-level scenes: a leaf closes its primitives only in the trees a placement names, the ones ever walked)
     if (nd.nprims != 0 && !(unnamed && unnamed[i])) leafLast[nd.offset + nd.nprims - 1] = 1;
 }
 
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kBk) void k_bake_stream(const nnbvh_prim *__restric
     float4 *s = stream + slotOf[i];
     unsigned flags = leafLast[i] ? kPrimLast : 0u;
     if (p.kind == NNBVH_PRIM_INSTANCE) {
-        // the 6-slot record of create_scene (bvh_capi.cpp): the child root's box, the placement index, the flags,
+        // the 6-slot instance record (nnbvh_internal.h): the child root's box, the placement index, the flags,
         // prim_from_render and the child root's ref.  Reached in the instance-aware form only (k_bake_slot_counts),
         // with p.v[0] and the placement's object range-checked by the caller
         const nnbvh_placement *pl = inst.d_placements + p.v[0];
@@ -384,14 +384,19 @@ bool bake_on_device(const void *d_nodes_, int n_nodes, const void *d_prims_, int
     const size_t wideBytes = (((size_t)std::max(nInterior, 1) * sizeof(WideNode)) + 255) & ~(size_t)255;
     BK_CHECK(hipMalloc(&dWide, wideBytes + (size_t)nSlots * 16 + 64), "hipMalloc(nodes + primitives)");
     dStream = (char *)dWide + wideBytes;
-    BK_CHECK(hipMemsetAsync((char *)dStream + (size_t)nSlots * 16, 0, 64, stream), "memset");
+    hipError_t e = hipMemsetAsync((char *)dStream + (size_t)nSlots * 16, 0, 64, stream);
+    if (e != hipSuccess) {
+        (void)hipFree(dWide);
+        *error = std::string("device bake: memset: ") + hipGetErrorString(e);
+        return false;
+    }
     hipLaunchKernelGGL(k_bake_stream, dim3(gp), dim3(kBk), 0, stream, dPrims, n_prims, dVerts, (const float *)d_normals_, (const float *)d_uvs_, (const float *)d_prim_alpha_, dSlotOf, dLeafLast,
                        (float4 *)dStream, dNodes, dOrd, inst);
     hipLaunchKernelGGL(k_bake_wide, dim3(gn), dim3(kBk), 0, stream, dNodes, n_nodes, dOrd, dSlotOf, (float4 *)dWide);
     int rootSlot = 0;
     if (root.nprims != 0)
         (void)hipMemcpyAsync(&rootSlot, dSlotOf + root.offset, sizeof(int), hipMemcpyDeviceToHost, stream);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) {
         (void)hipFree(dWide);

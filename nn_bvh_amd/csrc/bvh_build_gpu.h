@@ -1,5 +1,5 @@
-// bvh_build_gpu.h — interface between the host builder (bvh_build.cpp) and the device HLBVH
-// pipeline (bvh_build_gpu.hip).
+// bvh_build_gpu.h — interface between the host code of the C ABI (bvh_build.cpp, bvh_capi.cpp, capi_two_level.cpp)
+// and the device builders (bvh_build_gpu.hip) and the device baker of every BVH scene (bvh_bake.hip).
 #pragma once
 #include <stdint.h>
 
@@ -121,9 +121,9 @@ bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *object_first, 
 bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,
                              std::string *error);
 
-// Device-side counterpart of nnbvh_scene_create's baking (bvh_capi.cpp): the 64-B "both children"
-// records and the 16-B-slot primitive stream, straight from device-resident build output.  Triangles,
-// bilinear patches and host-only primitives; instance entries with an InstanceBake (two-level scenes).
+// The baking of every BVH scene (bvh_bake.hip): the 64-B "both children" records and the 16-B-slot primitive
+// stream from a device-resident tree, the device builders' output or the caller's validated tree uploaded by
+// bvh_capi.cpp.  Every primitive kind; instance entries with an InstanceBake (two-level scenes).
 struct BakedScene {
     void *d_wide = nullptr, *d_prims = nullptr;  // float4 arrays, owned by the caller afterwards
     int n_interior = 0;
@@ -142,8 +142,8 @@ struct InstanceBake {
     const nnbvh_placement *d_placements = nullptr;  // v[0] of an instance entry indexes this (the caller has checked it)
     const int *d_object_root = nullptr;             // [n_objects] node index of each object's root (placement.object indexes it)
     const unsigned char *d_animated = nullptr;      // nullable, [n_placements]: 1 = kPrimAnimated
-    // [n_nodes]: 1 = a node of an object no placement names.  The host route (create_scene) walks only the trees that
-    // placements name, so only their leaves mark a last primitive; such an object is baked, and never reached
+    // [n_nodes]: 1 = a node of an object no placement names.  Only the trees that placements name are validated and
+    // walked, so only their leaves mark a last primitive; such an object is baked, and never reached
     const unsigned char *d_node_unnamed = nullptr;
 };
 bool bake_on_device(const void *d_nodes, int n_nodes, const void *d_ordered_prims, int n_prims, const void *d_verts,

@@ -1,5 +1,7 @@
-// bvh_capi.cpp — the C ABI of include/nnbvh.h, scene part: tree validation, baking of the device
-// layout, scene queries and options, workspaces.  The calls that launch kernels are in capi_trace.cpp
+// bvh_capi.cpp — the C ABI of include/nnbvh.h, scene part: validation of the caller's trees and primitives, their
+// upload to the device baker (bvh_bake.hip: the one writer of the device layout, for flat and two-level scenes, host-
+// and device-built trees alike), the scene object around what it made, scene queries and options, workspaces.  The
+// calls that launch kernels are in capi_trace.cpp
 // (ray batches), capi_wavefront.cpp (queues) and capi_shading.cpp (shading meshes).  Host code only
 // (compiled with hipcc for the HIP runtime API).  There is deliberately no CPU traversal in this
 // library: if no HIP device is usable the intersect entry points fail with NNBVH_ERR_DEVICE.
@@ -27,11 +29,10 @@ using namespace nnbvh;
 // -------------------------------------------------------------------------------------
 // Tree validation: everything the kernels index with is range-checked here once, so a
 // malformed tree is an NNBVH_ERR_ARG at create time, never a device fault.
-// Validates the DFS-laid-out tree occupying nodes[root, root + n_tree).  `covered` / `leaf_last`
-// are shared by all trees of a scene (top level + instanced children).
+// Validates the DFS-laid-out tree occupying nodes[root, root + n_tree).  `covered`
+// is shared by all trees of a scene (top level + instanced children).
 static bool validate_tree(const nnbvh_linear_node *nodes, int root, int n_tree, const nnbvh_prim *prims,
-                          int n_prims, bool allow_instances, std::vector<uint8_t> &covered,
-                          std::vector<uint8_t> &leaf_last, int *depth_out) {
+                          int n_prims, bool allow_instances, std::vector<uint8_t> &covered, int *depth_out) {
     if (n_tree < 1) {
         set_error("scene_create: tree has no nodes");
         return false;
@@ -82,7 +83,6 @@ static bool validate_tree(const nnbvh_linear_node *nodes, int root, int n_tree, 
                     return false;
                 }
             }
-            leaf_last[(size_t)nd.offset + nd.nprims - 1] = 1;
         } else {
             if (nd.axis > 2) {
                 set_error("scene_create: interior node axis > 2");
@@ -105,34 +105,26 @@ static bool validate_tree(const nnbvh_linear_node *nodes, int root, int n_tree, 
     return true;
 }
 
-// The reference's degenerate-triangle test (shapes.cpp:176-177) with its exact float32
-// arithmetic: Cross via DifferenceOfProducts (util/vecmath.h:999-1004, util/math.h:569-575,
-// fmaf where the reference has FMA), LengthSquared as x*x + y*y + z*z (vecmath.h:948-950).
-// This translation unit is compiled with -ffp-contract=off.
-static float dop_host(float a, float b, float c, float d) {
-    float cd = c * d;
-    float diff = std::fma(a, b, -cd);
-    float err = std::fma(-c, d, cd);
-    return diff + err;
+// AngleBetween(Quaternion, Quaternion) (util/vecmath.h:1138-1143) and SinXOverX (util/math.h:340-344) with
+// the host's libm, as the reference's Slerp evaluates them; they depend on the transform only
+static float quat_dot_host(const float a[4], const float b[4]) {
+    return (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]) + a[3] * b[3];
 }
-static bool triangle_is_degenerate(const float *p0, const float *p1, const float *p2) {
-    float v[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
-    float w[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-    float cx = dop_host(v[1], w[2], v[2], w[1]);
-    float cy = dop_host(v[2], w[0], v[0], w[2]);
-    float cz = dop_host(v[0], w[1], v[1], w[0]);
-    return cx * cx + cy * cy + cz * cz == 0.0f;
+static float quat_angle_between_host(const float q1[4], const float q2[4]) {
+    float t[4];
+    const bool neg = quat_dot_host(q1, q2) < 0;
+    for (int k = 0; k < 4; ++k) t[k] = neg ? q1[k] + q2[k] : q2[k] - q1[k];
+    float x = std::sqrt(quat_dot_host(t, t)) / 2;
+    x = x < -1 ? -1 : (x > 1 ? 1 : x);
+    return neg ? 3.14159265358979323846f - 2 * std::asin(x) : 2 * std::asin(x);
 }
 
-static void put3(float *q, int at, const float *v) {
-    q[at] = v[0];
-    q[at + 1] = v[1];
-    q[at + 2] = v[2];
+static float sin_x_over_x_host(float x) {
+    if (1 - x * x == 1) return 1;
+    return std::sin(x) / x;
 }
 
 // one entry of the device's animation table (layout: anim_math.h)
-static float quat_angle_between_host(const float a[4], const float b[4]);
-static float sin_x_over_x_host(float x);
 void nnbvh::fill_anim_entry(const nnbvh_animated_transform &a, float *t) {
     std::memcpy(t, a.T, 24);
     std::memcpy(t + 6, a.R, 32);
@@ -258,18 +250,11 @@ static bool attach_top_table(nnbvh_scene *s) {
     return true;
 }
 
-extern "C" {
-
-const char *nnbvh_last_error(void) { return g_error.c_str(); }
-
-int nnbvh_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-// a scene object around arrays baked on the device (bvh_bake.hip)
-static nnbvh_scene *scene_from_baked(const BakedScene &b, int depth, int device) {
+// A scene object around arrays baked on the device (bvh_bake.hip): every creation route ends here, with the scene's
+// device current.  instanced: a two-level scene, which always runs the general kernels (so it has no top table) and
+// counts its one allocation as it was made, records 256-B aligned and the stream's 64 B of padding; a flat scene counts
+// the two arrays.  nullptr: the error text is set, the arrays are freed.
+nnbvh_scene *nnbvh::scene_from_baked(const BakedScene &b, int depth, int device, bool instanced) {
     hipDeviceProp_t prop;
     if (!hip_ok(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties")) {
         (void)hipFree(b.d_wide);  // one allocation: d_prims points into it
@@ -283,18 +268,20 @@ static nnbvh_scene *scene_from_baked(const BakedScene &b, int depth, int device)
     s->depth = depth;
     std::memcpy(s->bounds, b.bounds, sizeof b.bounds);
     s->root_ref = b.root_ref;
-    s->instanced = 0;
-    s->has_host_prims = (b.has_host_prims || b.has_alpha) ? 1 : 0;
-    s->has_patches = (b.has_patches || b.has_alpha) ? 1 : 0;  // the alpha test hashes the ray direction, parked with the patches' one
+    s->instanced = instanced ? 1 : 0;
+    s->has_host_prims = (b.has_host_prims || b.has_alpha) ? 1 : 0;  // an alpha re-trace that hits voids the ray like a host primitive
+    // (the alpha test hashes the ray direction, parked with the patches' one)
+    s->has_patches = (instanced || b.has_patches || b.has_alpha) ? 1 : 0;
     s->has_alpha = b.has_alpha;
     s->max_grid_threads = s->n_cus * 8 * kBlockThreads;
     s->d_wide = (float4 *)b.d_wide;
     s->d_prims = (float4 *)b.d_prims;
-    s->device_bytes = (size_t)std::max(b.n_interior, 1) * sizeof(WideNode) +
-                      std::max<size_t>((size_t)b.n_slots, 1) * 16;
+    const size_t records = (size_t)std::max(b.n_interior, 1) * sizeof(WideNode),
+                 slots = std::max<size_t>((size_t)b.n_slots, 1) * 16;
+    s->device_bytes = instanced ? ((records + 255) & ~(size_t)255) + slots + 64 : records + slots;
     if (hipMalloc((void **)&s->d_stats, nnbvh::kSchedStatWords * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
-    if (!attach_top_table(s)) {
+    if (!instanced && !attach_top_table(s)) {
         const std::string why = nnbvh_last_error();
         nnbvh_scene_destroy(s);
         set_error(why);
@@ -303,65 +290,30 @@ static nnbvh_scene *scene_from_baked(const BakedScene &b, int depth, int device)
     return s;
 }
 
-// Single-level scenes: the validated tree is uploaded as it is and baked on the device (the same
-// arrays the host code below produces for two-level scenes, without the host pass over every node
-// and primitive).
-static nnbvh_scene *create_scene_device_bake(const nnbvh_linear_node *nodes, int n_nodes, const nnbvh_prim *prims,
-                                             int n_prims, const float *verts, int n_verts, int depth, int device,
-                                             const float *normals, const float *prim_alpha, const float *uvs) {
-    int n_dev = nnbvh_device_count();
-    if (n_dev <= 0 || device < 0 || device >= n_dev) {
-        set_error("scene_create: no usable HIP device (this library has no CPU fallback)");
-        return nullptr;
+// the animation table of a two-level scene, one entry per instance, uploaded (not counted in device_bytes).  false:
+// the scene is destroyed, the error text is set
+bool nnbvh::upload_anim_table(nnbvh_scene *s, const nnbvh_animated_transform *animated, int n_instances) {
+    std::vector<float> table((size_t)n_instances * kAnimStride, 0.0f);
+    for (int k = 0; k < n_instances; ++k) fill_anim_entry(animated[k], &table[(size_t)k * kAnimStride]);
+    if (hip_ok(hipMalloc((void **)&s->d_anim, table.size() * 4), "hipMalloc(animation table)") &&
+        hip_ok(hipMemcpy(s->d_anim, table.data(), table.size() * 4, hipMemcpyHostToDevice), "hipMemcpy(animation table)")) {
+        s->n_anim = n_instances;
+        return true;
     }
-    DeviceGuard guard(device);
-    if (!guard.ok) return nullptr;
-    void *d_nodes = nullptr, *d_prims = nullptr, *d_verts = nullptr, *d_normals = nullptr, *d_alpha = nullptr,
-         *d_uvs = nullptr;
-    const size_t nb = (size_t)n_nodes * sizeof(nnbvh_linear_node), pbytes = (size_t)n_prims * sizeof(nnbvh_prim),
-                 vb = (size_t)n_verts * 12;
-    BakedScene b;
-    std::string err;
-    bool ok = hip_ok(hipMalloc(&d_nodes, nb), "hipMalloc(tree)") && hip_ok(hipMalloc(&d_prims, pbytes), "hipMalloc(primitives)") &&
-              hip_ok(hipMalloc(&d_verts, vb), "hipMalloc(vertices)") &&
-              hip_ok(hipMemcpy(d_nodes, nodes, nb, hipMemcpyHostToDevice), "hipMemcpy(tree)") &&
-              hip_ok(hipMemcpy(d_prims, prims, pbytes, hipMemcpyHostToDevice), "hipMemcpy(primitives)") &&
-              hip_ok(hipMemcpy(d_verts, verts, vb, hipMemcpyHostToDevice), "hipMemcpy(vertices)");
-    if (ok && normals)
-        ok = hip_ok(hipMalloc(&d_normals, vb), "hipMalloc(normals)") &&
-             hip_ok(hipMemcpy(d_normals, normals, vb, hipMemcpyHostToDevice), "hipMemcpy(normals)");
-    if (ok && prim_alpha)
-        ok = hip_ok(hipMalloc(&d_alpha, (size_t)n_prims * 4), "hipMalloc(primitive alpha)") &&
-             hip_ok(hipMemcpy(d_alpha, prim_alpha, (size_t)n_prims * 4, hipMemcpyHostToDevice), "hipMemcpy(primitive alpha)");
-    if (ok && uvs)
-        ok = hip_ok(hipMalloc(&d_uvs, (size_t)n_verts * 8), "hipMalloc(uvs)") &&
-             hip_ok(hipMemcpy(d_uvs, uvs, (size_t)n_verts * 8, hipMemcpyHostToDevice), "hipMemcpy(uvs)");
-    if (ok && !bake_on_device(d_nodes, n_nodes, d_prims, n_prims, d_verts, device, &b, &err, d_normals, d_alpha, d_uvs)) {
-        set_error(err);
-        ok = false;
-    }
-    for (void *p : {d_nodes, d_prims, d_verts, d_normals, d_alpha, d_uvs})
-        if (p) (void)hipFree(p);
-    return ok ? scene_from_baked(b, depth, device) : nullptr;
+    const std::string why = nnbvh_last_error();
+    nnbvh_scene_destroy(s);
+    set_error(why);
+    return false;
 }
 
-// AngleBetween(Quaternion, Quaternion) (util/vecmath.h:1138-1143) and SinXOverX (util/math.h:340-344) with
-// the host's libm, as the reference's Slerp evaluates them; they depend on the transform only
-static float quat_dot_host(const float a[4], const float b[4]) {
-    return (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]) + a[3] * b[3];
-}
-static float quat_angle_between_host(const float q1[4], const float q2[4]) {
-    float t[4];
-    const bool neg = quat_dot_host(q1, q2) < 0;
-    for (int k = 0; k < 4; ++k) t[k] = neg ? q1[k] + q2[k] : q2[k] - q1[k];
-    float x = std::sqrt(quat_dot_host(t, t)) / 2;
-    x = x < -1 ? -1 : (x > 1 ? 1 : x);
-    return neg ? 3.14159265358979323846f - 2 * std::asin(x) : 2 * std::asin(x);
-}
+extern "C" {
 
-static float sin_x_over_x_host(float x) {
-    if (1 - x * x == 1) return 1;
-    return std::sin(x) / x;
+const char *nnbvh_last_error(void) { return g_error.c_str(); }
+
+int nnbvh_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
 }
 
 static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, int n_top_nodes,
@@ -375,14 +327,14 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
         set_error("scene_create: null or empty input array");
         return nullptr;
     }
-    std::vector<uint8_t> leaf_last((size_t)n_prims, 0), covered((size_t)n_prims, 0);
+    std::vector<uint8_t> covered((size_t)n_prims, 0);
     int depth = 0;
-    if (!validate_tree(nodes, 0, n_top_nodes, prims, n_prims, n_instances > 0, covered, leaf_last,
-                       &depth))
-        return nullptr;
-    // instanced children: trees in nodes[n_top_nodes, n_nodes); several instances may share one
+    if (!validate_tree(nodes, 0, n_top_nodes, prims, n_prims, n_instances > 0, covered, &depth)) return nullptr;
+    // instanced children: trees in nodes[n_top_nodes, n_nodes); several instances may share one.  unnamed: the nodes
+    // behind the top tree that no walk below sees (an object no instance places)
     int child_depth = 0;
-    std::vector<uint8_t> tree_seen((size_t)n_nodes, 0);
+    std::vector<uint8_t> tree_seen((size_t)n_nodes, 0), unnamed((size_t)n_nodes, 0);
+    std::fill(unnamed.begin() + n_top_nodes, unnamed.end(), 1);
     for (int k = 0; k < n_instances; ++k) {
         const nnbvh_instance &in = instances[k];
         if (in.root < n_top_nodes || in.n_nodes < 1 || (int64_t)in.root + in.n_nodes > n_nodes) {
@@ -392,8 +344,8 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
         if (tree_seen[(size_t)in.root]) continue;
         tree_seen[(size_t)in.root] = 1;
         int d = 0;
-        if (!validate_tree(nodes, in.root, in.n_nodes, prims, n_prims, false, covered, leaf_last, &d))
-            return nullptr;
+        if (!validate_tree(nodes, in.root, in.n_nodes, prims, n_prims, false, covered, &d)) return nullptr;
+        std::fill(unnamed.begin() + in.root, unnamed.begin() + in.root + in.n_nodes, 0);
         child_depth = std::max(child_depth, d + 1);
     }
     depth += child_depth;  // pending entries of the outer walk + those of the child walk
@@ -402,8 +354,8 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
         set_error("scene_create: tree deeper than the 64-entry traversal stack");
         return nullptr;
     }
-    // prim stream
-    std::vector<int64_t> slot_of((size_t)n_prims + 1, 0);
+    // what the bake (bvh_bake.hip) indexes with, and the arrays a kind reads; the stream's slots are only counted
+    int64_t n_slots = 0;
     for (int k = 0; k < n_prims; ++k) {
         const nnbvh_prim &p = prims[k];
         int nv, nslots;
@@ -449,121 +401,22 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
                 set_error("scene_create: vertex index out of range");
                 return nullptr;
             }
-        slot_of[(size_t)k + 1] = slot_of[(size_t)k] + nslots;
+        n_slots += nslots;
     }
-    const int64_t n_slots = slot_of[(size_t)n_prims];
     if (n_slots >= 0x7ffffffeLL) {
         set_error("scene_create: primitive stream exceeds 2^31 slots");
         return nullptr;
     }
-    if (n_instances == 0)
-        return create_scene_device_bake(nodes, n_nodes, prims, n_prims, verts, n_verts, depth, device, normals, prim_alpha, uvs);
-    // interior record numbers (global over all trees) and node refs
-    std::vector<int> ord((size_t)n_nodes, -1);
-    int n_interior = 0;
-    for (int i = 0; i < n_nodes; ++i)
-        if (nodes[i].nprims == 0) ord[(size_t)i] = n_interior++;
-    auto ref_of = [&](int i) -> int32_t {
-        return nodes[i].nprims == 0 ? ord[(size_t)i]
-                                    : (int32_t) ~(uint32_t)slot_of[(size_t)nodes[i].offset];
-    };
-    std::vector<float> stream((size_t)n_slots * 4, 0.0f);
-    bool has_host = false, has_alpha = false, has_alpha_patch = false, has_alpha_tex = false;
-    for (int k = 0; k < n_prims; ++k) {
-        const nnbvh_prim &p = prims[k];
-        float *s = &stream[(size_t)slot_of[(size_t)k] * 4];
-        uint32_t flags = leaf_last[(size_t)k] ? kPrimLast : 0u;
-        if (p.kind == NNBVH_PRIM_INSTANCE) {
-            const nnbvh_instance &in = instances[p.v[0]];
-            const nnbvh_linear_node &root = nodes[in.root];
-            flags |= kPrimInstance;
-            if (animated && animated[p.v[0]].actually_animated) flags |= kPrimAnimated;
-            put3(s, 0, root.pmin);
-            put3(s, 4, root.pmax);
-            std::memcpy(&s[3], &p.v[0], 4);  // instance index (reported +1 in nnbvh_hit.instance)
-            std::memcpy(&s[7], &flags, 4);
-            std::memcpy(&s[8], in.prim_from_render, 48);
-            const int32_t rref = ref_of(in.root);
-            std::memcpy(&s[20], &rref, 4);
-            continue;
+    // the bake makes a record of every interior node and looks up every leaf's slot, the unnamed ones' too: their
+    // children and primitive ranges, which validate_tree never saw, must lie inside the arrays
+    for (int i = n_top_nodes; i < n_nodes; ++i) {
+        const nnbvh_linear_node &nd = nodes[i];
+        if (!unnamed[(size_t)i]) continue;
+        if (nd.nprims == 0 ? !(nd.axis <= 2 && nd.offset > i + 1 && nd.offset < n_nodes)
+                           : !(nd.offset >= 0 && (int64_t)nd.offset + nd.nprims <= n_prims)) {
+            set_error("scene_create: malformed node outside every instance's tree");
+            return nullptr;
         }
-        if (p.kind == NNBVH_PRIM_HOST) {
-            flags |= kPrimHost;
-            has_host = true;
-            std::memcpy(&s[3], &p.id, 4);
-            std::memcpy(&s[7], &flags, 4);
-            continue;
-        }
-        const bool tri = is_triangle_kind(p.kind) || is_alphatex_kind(p.kind);
-        const int nv = tri ? 3 : 4;
-        for (int j = 0; j < nv; ++j) put3(s, 4 * j, verts + 3 * (size_t)p.v[j]);
-        if (p.kind == NNBVH_PRIM_BILINEAR_PATCH) flags |= kPrimPatch;
-        if (is_alpha_patch_kind(p.kind)) {  // as k_bake_stream lays them out (bvh_bake.hip)
-            flags |= kPrimPatch | kPrimAlpha | (is_flipped_alpha_patch_kind(p.kind) ? kPrimFlipN : 0u);
-            s[11] = prim_alpha[k];
-            has_alpha = has_alpha_patch = true;
-            if (is_smooth_alpha_patch_kind(p.kind)) {
-                flags |= kPrimSmooth;
-                for (int j = 0; j < 4; ++j) put3(s, 16 + 4 * j, normals + 3 * (size_t)p.v[j]);
-            }
-            if (is_uv_alpha_patch_kind(p.kind)) {
-                flags |= kPrimUV;
-                float *u = s + (is_smooth_alpha_patch_kind(p.kind) ? 32 : 16);
-                for (int j = 0; j < 4; ++j) {
-                    u[2 * j] = uvs[2 * (size_t)p.v[j]];
-                    u[2 * j + 1] = uvs[2 * (size_t)p.v[j] + 1];
-                }
-            }
-        }
-        if (is_flat_alpha_kind(p.kind) || is_smooth_alpha_kind(p.kind)) {
-            flags |= kPrimAlpha;
-            if (p.kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED || p.kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED) flags |= kPrimFlipN;
-            std::memcpy(&s[11], &p.v[3], 4);  // alpha (float bit pattern) in slot 2's fourth word
-            has_alpha = true;
-            if (is_smooth_alpha_kind(p.kind)) {  // the three vertex normals in slots 3..5
-                flags |= kPrimSmooth;
-                for (int j = 0; j < 3; ++j) put3(s, 12 + 4 * j, normals + 3 * (size_t)p.v[j]);
-            }
-        }
-        if (is_alphatex_kind(p.kind)) {  // as k_bake_stream lays them out (bvh_bake.hip)
-            flags |= kPrimAlpha | kPrimAlphaTex | (is_flipped_alphatex_kind(p.kind) ? kPrimFlipN : 0u);
-            std::memcpy(&s[11], &p.v[3], 4);  // the texture index where kind 4 keeps alpha
-            has_alpha = has_alpha_tex = true;
-            float *u = s + 12;
-            if (is_smooth_alphatex_kind(p.kind)) {
-                flags |= kPrimSmooth;
-                for (int j = 0; j < 3; ++j) put3(s, 12 + 4 * j, normals + 3 * (size_t)p.v[j]);
-                u = s + 24;
-            }
-            // the three (u, v) pairs; the reference's default corners for a mesh without
-            const float corners[6] = {0, 0, 1, 0, 1, 1};
-            for (int j = 0; j < 3; ++j) {
-                u[2 * j] = uvs ? uvs[2 * (size_t)p.v[j]] : corners[2 * j];
-                u[2 * j + 1] = uvs ? uvs[2 * (size_t)p.v[j] + 1] : corners[2 * j + 1];
-            }
-        }
-        if (tri &&
-            triangle_is_degenerate(verts + 3 * (size_t)p.v[0], verts + 3 * (size_t)p.v[1],
-                                   verts + 3 * (size_t)p.v[2]))
-            flags |= kPrimDegenerate;
-        std::memcpy(&s[3], &p.id, 4);
-        std::memcpy(&s[7], &flags, 4);
-    }
-    // interior records
-    std::vector<WideNode> wide((size_t)std::max(n_interior, 1));
-    std::memset(wide.data(), 0, wide.size() * sizeof(WideNode));
-    for (int i = 0; i < n_nodes; ++i) {
-        if (nodes[i].nprims != 0) continue;
-        WideNode &w = wide[(size_t)ord[(size_t)i]];
-        const nnbvh_linear_node &c0 = nodes[i + 1], &c1 = nodes[nodes[i].offset];
-        put3(w.q, 0, c0.pmin);
-        put3(w.q, 3, c0.pmax);
-        put3(w.q, 6, c1.pmin);
-        put3(w.q, 9, c1.pmax);
-        w.ref0 = ref_of(i + 1);
-        w.ref1 = ref_of(nodes[i].offset);
-        w.axis = nodes[i].axis;
-        w.pad = 0;
     }
 
     int n_dev = nnbvh_device_count();
@@ -573,53 +426,44 @@ static nnbvh_scene *create_scene(const nnbvh_linear_node *nodes, int n_nodes, in
     }
     DeviceGuard guard(device);
     if (!guard.ok) return nullptr;
-    hipDeviceProp_t prop;
-    if (!hip_ok(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties")) return nullptr;
-
-    auto *s = new nnbvh_scene;
-    s->device = device;
-    s->n_cus = prop.multiProcessorCount;
-    s->n_interior = n_interior;
-    s->n_slots = n_slots;
-    s->depth = depth;
-    std::memcpy(s->bounds, nodes[0].pmin, 12);
-    std::memcpy(s->bounds + 3, nodes[0].pmax, 12);
-    s->root_ref = ref_of(0);
-    s->instanced = n_instances > 0 ? 1 : 0;
-    s->has_host_prims = (has_host || has_alpha) ? 1 : 0;  // an alpha re-trace that hits voids the ray like a host primitive
-    // (textured triangles: 2 as well, the two-level ALPHA = 2 instances evaluate them; 3 is the flat scenes')
-    s->has_alpha = (has_alpha_patch || has_alpha_tex) ? 2 : (has_alpha ? 1 : 0);
-    s->has_patches = 1;  // two-level scenes always run the general kernels
-    s->max_grid_threads = s->n_cus * 8 * kBlockThreads;
-    // one allocation, as bake_on_device makes it: records, then the 256-B aligned primitive stream + 64 B
-    const size_t wide_bytes = (wide.size() * sizeof(WideNode) + 255) & ~(size_t)255;
-    const size_t prim_bytes = std::max<size_t>((size_t)n_slots, 1) * 16 + 64;
-    bool ok = hip_ok(hipMalloc((void **)&s->d_wide, wide_bytes + prim_bytes), "hipMalloc(nodes + prims)");
-    if (ok) s->d_prims = (float4 *)((char *)s->d_wide + wide_bytes);
-    ok = ok && hip_ok(hipMemset((char *)s->d_prims + prim_bytes - 64, 0, 64), "hipMemset(pad)") &&
-         hip_ok(hipMemcpy(s->d_wide, wide.data(), wide.size() * sizeof(WideNode), hipMemcpyHostToDevice),
-                "hipMemcpy(nodes)") &&
-         hip_ok(hipMemcpy(s->d_prims, stream.data(), (size_t)n_slots * 16, hipMemcpyHostToDevice),
-                "hipMemcpy(prims)");
-    if (!ok) {
-        if (s->d_wide) (void)hipFree(s->d_wide);
-        delete s;
+    // the caller's arrays go up as they are; the bake's passes over them run on the device (two-level scenes: the
+    // instance table in the form the device-built route hands over, object k = instance k's tree)
+    Uploads up;
+    const void *d_nodes = up.put(nodes, (size_t)n_nodes * sizeof(nnbvh_linear_node), "tree");
+    const void *d_prims = up.put(prims, (size_t)n_prims * sizeof(nnbvh_prim), "primitives");
+    const void *d_verts = up.put(verts, (size_t)n_verts * 12, "vertices");
+    const void *d_normals = up.put(normals, (size_t)n_verts * 12, "normals");
+    const void *d_alpha = up.put(prim_alpha, (size_t)n_prims * 4, "primitive alpha");
+    const void *d_uvs = up.put(uvs, (size_t)n_verts * 8, "uvs");
+    InstanceBake inst;
+    if (n_instances > 0) {
+        std::vector<nnbvh_placement> placements((size_t)n_instances);
+        std::vector<int32_t> roots((size_t)n_instances);
+        std::vector<unsigned char> moving((size_t)n_instances, 0);
+        for (int k = 0; k < n_instances; ++k) {
+            nnbvh_placement &pl = placements[(size_t)k];
+            std::memcpy(pl.render_from_prim, instances[k].render_from_prim, sizeof pl.render_from_prim);
+            std::memcpy(pl.prim_from_render, instances[k].prim_from_render, sizeof pl.prim_from_render);
+            pl.object = k;
+            pl.pad = 0;
+            roots[(size_t)k] = instances[k].root;
+            moving[(size_t)k] = animated && animated[k].actually_animated ? 1 : 0;
+        }
+        inst.d_placements = (const nnbvh_placement *)up.put(placements.data(), placements.size() * sizeof(nnbvh_placement), "instances");
+        inst.d_object_root = (const int *)up.put(roots.data(), roots.size() * sizeof(int32_t), "instances");
+        inst.d_animated = (const unsigned char *)up.put(animated ? moving.data() : nullptr, moving.size(), "instances");
+        inst.d_node_unnamed = (const unsigned char *)up.put(unnamed.data(), unnamed.size(), "tree");
+    }
+    if (!up.ok) return nullptr;
+    BakedScene b;
+    std::string err;
+    if (!bake_on_device(d_nodes, n_nodes, d_prims, n_prims, d_verts, device, &b, &err, d_normals, d_alpha, d_uvs,
+                        n_instances > 0 ? &inst : nullptr)) {
+        set_error(err);
         return nullptr;
     }
-    s->device_bytes = wide_bytes + prim_bytes;
-    if (animated && n_instances > 0) {
-        std::vector<float> table((size_t)n_instances * kAnimStride, 0.0f);
-        for (int k = 0; k < n_instances; ++k) fill_anim_entry(animated[k], &table[(size_t)k * kAnimStride]);
-        if (!hip_ok(hipMalloc((void **)&s->d_anim, table.size() * 4), "hipMalloc(animation table)") ||
-            !hip_ok(hipMemcpy(s->d_anim, table.data(), table.size() * 4, hipMemcpyHostToDevice),
-                    "hipMemcpy(animation table)")) {
-            nnbvh_scene_destroy(s);
-            return nullptr;
-        }
-        s->n_anim = n_instances;
-    }
-    if (hipMalloc((void **)&s->d_stats, nnbvh::kSchedStatWords * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
+    nnbvh_scene *s = scene_from_baked(b, depth, device, n_instances > 0);
+    if (s && animated && n_instances > 0 && !upload_anim_table(s, animated, n_instances)) return nullptr;
     return s;
 }
 
@@ -706,7 +550,7 @@ static nnbvh_scene *create_scene_gpu_build(const nnbvh_prim *prims_in, int n_pri
         set_error(err);
         return nullptr;
     }
-    nnbvh_scene *s = scene_from_baked(b, r.depth, device);
+    nnbvh_scene *s = scene_from_baked(b, r.depth, device, false);
     if (!s) return nullptr;
     s->build_ms[0] = r.ms[0] + r.ms[1] + r.ms[2] + r.ms[3] + r.ms[4];
     return s;

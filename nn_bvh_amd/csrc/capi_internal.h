@@ -5,12 +5,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <map>
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "bvh_trace.h"
 #include "interaction.h"
@@ -33,6 +35,24 @@ struct DeviceGuard {
     }
     ~DeviceGuard() {
         if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// device copies of a creation call's host arrays (the current device's), freed on every way out
+struct Uploads {
+    std::vector<void *> ptrs;
+    bool ok = true;
+    // src == nullptr (an array the caller did not give): nullptr, and nothing is wrong
+    const void *put(const void *src, size_t bytes, const char *what) {
+        void *d = nullptr;
+        if (!src || !ok) return nullptr;
+        ok = hip_ok(hipMalloc(&d, std::max<size_t>(bytes, 16)), (std::string("hipMalloc(") + what + ")").c_str());
+        if (ok) ptrs.push_back(d);
+        ok = ok && hip_ok(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice), (std::string("hipMemcpy(") + what + ")").c_str());
+        return d;
+    }
+    ~Uploads() {
+        for (void *p : ptrs) (void)hipFree(p);
     }
 };
 
@@ -139,6 +159,13 @@ Workspace *workspace_for(nnbvh_scene *s, hipStream_t stream);
 
 // one entry of the device's animation table (layout: anim_math.h; bvh_capi.cpp)
 void fill_anim_entry(const nnbvh_animated_transform &a, float *t);
+
+// The end of every BVH creation route (bvh_capi.cpp): the scene object around the arrays bake_on_device made
+// (bvh_build_gpu.h), and for a two-level scene with AnimatedPrimitive instances its animation table.  Both are called
+// with the scene's device current; after a failure nothing is left allocated and the error text is set.
+struct BakedScene;
+nnbvh_scene *scene_from_baked(const BakedScene &b, int depth, int device, bool instanced);
+bool upload_anim_table(nnbvh_scene *s, const nnbvh_animated_transform *animated, int n_instances);
 
 // the descriptor table (AlphaTexDesc, 48 B each) and the texel pool of a checked alpha-texture table, uploaded to
 // `device` for a scene of either type (bvh_capi.cpp).  false: the error text is set; the pointers hold what was allocated

@@ -1,5 +1,5 @@
-// capi_kd.cpp — the C ABI of include/nnbvh.h, kd-tree scenes: creation from the caller's tree (its validation and the
-// host bake of the primitive records), the read-side calls, the launchers of kd_trace.hip's instances and the ray-batch
+// capi_kd.cpp — the C ABI of include/nnbvh.h, kd-tree scenes: creation from the caller's tree (its validation, the
+// upload, and the primitive records baked by kd_bake.hip as for a device-built tree), the read-side calls, the launchers of kd_trace.hip's instances and the ray-batch
 // calls on device and host buffers.  (The queue calls: capi_wavefront.cpp; the builders: kd_build.cpp.)  Host code only.
 #include <algorithm>
 #include <cmath>
@@ -289,88 +289,35 @@ static nnbvh_kd_scene *kd_scene_create(const nnbvh_kd_node *nodes, int n_nodes, 
         set_error("kd_scene_create: tree deeper than the traversal stack (64 entries, aggregates.cpp:982)");
         return nullptr;
     }
-    // ---- primitive records: 4 slots per primitive in the caller's order --------------------------
-    std::vector<float> rec((size_t)n_prims * 16, 0.0f);
-    bool has_host = false, has_patch = false;
-    // the alpha-tested kinds that read per-vertex attributes: on the device when the caller gave what they read
-    // (6 more slots per primitive in a second array), else the host's as before
-    auto on_device = [&](int kind) {
-        if (is_alphatex_kind(kind)) return true;  // (u, v) pairs, and the normals check_alpha_textures asked for
-        if (is_smooth_alpha_kind(kind)) return normals != nullptr;
-        if (is_alpha_patch_kind(kind))
-            return prim_alpha && (!is_smooth_alpha_patch_kind(kind) || normals) && (!is_uv_alpha_patch_kind(kind) || uvs);
-        return false;
-    };
-    bool any_attr = false, any_alpha_tex = false;  // any_alpha_tex: a kPrimAlphaTex record is baked below
-    for (int k = 0; k < n_prims && !any_attr; ++k) any_attr = on_device(prims[k].kind);
-    std::vector<float> extras(any_attr ? (size_t)n_prims * 24 : 0, 0.0f);
+    // ---- the primitive list: kinds and vertex indices, and the scene's flags --------------------------
+    bool has_host = false, has_patch = false, any_attr = false, any_alpha_tex = false;
     for (int k = 0; k < n_prims; ++k) {
         const nnbvh_prim &pr = prims[k];
-        float *s = &rec[(size_t)k * 16];
-        uint32_t flags = 0;
-        std::memcpy(&s[3], &pr.id, 4);
-        const bool attr = on_device(pr.kind);
+        // a kind with attribute slots: the textured triangles ((u, v) pairs, and the normals check_alpha_textures asked
+        // for) and the alpha-tested kinds whose arrays the caller gave
+        const bool tex = is_alphatex_kind(pr.kind);
+        const bool attr = tex || kd_attr_on_device(pr.kind, normals != nullptr, uvs != nullptr, prim_alpha != nullptr);
         if (pr.kind == NNBVH_PRIM_HOST || ((is_smooth_alpha_kind(pr.kind) || is_alpha_patch_kind(pr.kind)) && !attr)) {
-            // (alpha-tested triangles of smooth meshes and alpha-tested patches without the arrays they read: the host's)
-            flags |= kPrimHost;
-            has_host = true;
-        } else if (is_triangle_kind(pr.kind) || is_alphatex_kind(pr.kind) || pr.kind == NNBVH_PRIM_BILINEAR_PATCH ||
-                   is_alpha_patch_kind(pr.kind)) {
-            const int nv = (is_triangle_kind(pr.kind) || is_alphatex_kind(pr.kind)) ? 3 : 4;
-            if (attr) {
-                float *ex = &extras[(size_t)k * 24];
-                const bool smooth = is_smooth_alpha_kind(pr.kind) || is_smooth_alpha_patch_kind(pr.kind) ||
-                                    is_smooth_alphatex_kind(pr.kind);
-                for (int j = 0; j < nv && smooth; ++j)
-                    if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[4 * j], normals + 3 * (size_t)pr.v[j], 12);
-                for (int j = 0; j < 4 && is_uv_alpha_patch_kind(pr.kind); ++j)
-                    if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[16 + 2 * j], uvs + 2 * (size_t)pr.v[j], 8);
-                flags |= kPrimAlpha | (smooth ? kPrimSmooth : 0u) | (is_uv_alpha_patch_kind(pr.kind) ? kPrimUV : 0u);
-                if (pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED || is_flipped_alpha_patch_kind(pr.kind)) flags |= kPrimFlipN;
-                if (is_alphatex_kind(pr.kind)) {
-                    // the texture index rides in v[3] and goes to slot 2's w; the three (u, v) pairs go to slots 4 / 5:
-                    // the mesh's, or the reference's default corners (shapes.h, InteractionFromIntersection)
-                    static const float kDefaultUV[6] = {0.0f, 0.0f, 1.0f, 0.0f, 1.0f, 1.0f};
-                    for (int j = 0; j < 3; ++j) {
-                        if (!uvs) std::memcpy(&ex[16 + 2 * j], &kDefaultUV[2 * j], 8);
-                        else if (pr.v[j] >= 0 && pr.v[j] < n_verts) std::memcpy(&ex[16 + 2 * j], uvs + 2 * (size_t)pr.v[j], 8);
-                    }
-                    flags |= kPrimAlphaTex | (is_flipped_alphatex_kind(pr.kind) ? kPrimFlipN : 0u);
-                    any_alpha_tex = true;
-                }
-                has_host = true;   // a re-trace chain that does not end voids the ray
-                has_patch = true;  // the alpha test hashes the ray direction
-            }
-            if (pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE || pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED) {
-                // the alpha value rides in v[3] (bit pattern) and goes to slot 2's w, as in the BVH scenes;
-                // a re-trace that hits voids the ray like a host primitive, and the test needs the ray
-                // direction: such scenes run the PATCH instances
-                flags |= kPrimAlpha | (pr.kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED ? kPrimFlipN : 0u);
-                has_host = true;
-                has_patch = true;
-            }
-            for (int j = 0; j < nv; ++j) {
-                if (pr.v[j] < 0 || pr.v[j] >= n_verts) {
-                    set_error("kd_scene_create: vertex index out of range");
-                    return nullptr;
-                }
-                std::memcpy(&s[4 * j], verts + 3 * (size_t)pr.v[j], 12);
-            }
-            std::memcpy(&s[3], &pr.id, 4);
-            if (flags & kPrimAlpha) {
-                if (is_alpha_patch_kind(pr.kind)) s[11] = prim_alpha[k];  // a patch needs all four v[]
-                else std::memcpy(&s[11], &pr.v[3], 4);
-            }
-            if (nv == 4) {
-                flags |= kPrimPatch;
-                has_patch = true;
-            }
-            else if (kd_triangle_is_degenerate(&s[0], &s[4], &s[8])) flags |= kPrimDegenerate;
-        } else {
+            has_host = true;  // (... without the arrays they read: the host's, a record without geometry)
+            continue;
+        }
+        const int nv = (is_triangle_kind(pr.kind) || tex) ? 3
+                       : (pr.kind == NNBVH_PRIM_BILINEAR_PATCH || is_alpha_patch_kind(pr.kind)) ? 4 : 0;
+        if (!nv) {
             set_error("kd_scene_create: unsupported primitive kind (triangles, alpha-tested triangles, patches, host primitives)");
             return nullptr;
         }
-        std::memcpy(&s[7], &flags, 4);
+        for (int j = 0; j < nv; ++j)
+            if (pr.v[j] < 0 || pr.v[j] >= n_verts) {
+                set_error("kd_scene_create: vertex index out of range");
+                return nullptr;
+            }
+        any_attr = any_attr || attr;
+        any_alpha_tex = any_alpha_tex || tex;
+        // an alpha re-trace chain that does not end voids the ray like a host primitive, and the alpha test hashes the
+        // ray direction: such scenes run the PATCH instances
+        if (attr || is_flat_alpha_kind(pr.kind)) has_host = has_patch = true;
+        if (nv == 4) has_patch = true;
     }
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
@@ -386,17 +333,30 @@ static nnbvh_kd_scene *kd_scene_create(const nnbvh_kd_node *nodes, int n_nodes, 
     const size_t ni = (size_t)std::max(n_indices, 1);
     bool ok = hip_ok(hipMalloc((void **)&s->d_nodes, (size_t)n_nodes * 8), "hipMalloc(kd nodes)") &&
               hip_ok(hipMalloc((void **)&s->d_indices, ni * 4), "hipMalloc(kd indices)") &&
-              hip_ok(hipMalloc((void **)&s->d_prims, rec.size() * 4), "hipMalloc(kd prims)") &&
-              hip_ok(hipMemcpy(s->d_nodes, nodes, (size_t)n_nodes * 8, hipMemcpyHostToDevice), "upload kd nodes") &&
-              hip_ok(hipMemcpy(s->d_prims, rec.data(), rec.size() * 4, hipMemcpyHostToDevice), "upload kd prims");
+              hip_ok(hipMemcpy(s->d_nodes, nodes, (size_t)n_nodes * 8, hipMemcpyHostToDevice), "upload kd nodes");
     if (ok && n_indices > 0)
         ok = hip_ok(hipMemcpy(s->d_indices, prim_indices, (size_t)n_indices * 4, hipMemcpyHostToDevice),
                     "upload kd indices");
-    if (ok && any_attr)
-        ok = hip_ok(hipMalloc((void **)&s->d_extras, extras.size() * 4), "hipMalloc(kd attributes)") &&
-             hip_ok(hipMemcpy(s->d_extras, extras.data(), extras.size() * 4, hipMemcpyHostToDevice), "upload kd attributes");
+    // ---- primitive records and attribute slots: baked on the device from the caller's arrays (kd_bake.hip) ----
+    if (ok) {
+        Uploads up;
+        const auto *d_prims = (const nnbvh_prim *)up.put(prims, (size_t)n_prims * sizeof(nnbvh_prim), "kd primitives");
+        const auto *d_verts = (const float *)up.put(verts, (size_t)n_verts * 12, "kd vertices");
+        const auto *d_normals = (const float *)up.put(normals, (size_t)n_verts * 12, "kd normals");
+        const auto *d_uvs = (const float *)up.put(uvs, (size_t)n_verts * 8, "kd uvs");
+        const auto *d_alpha = (const float *)up.put(prim_alpha, (size_t)n_prims * 4, "kd primitive alpha");
+        std::string err;
+        ok = up.ok;
+        if (ok && !kd_bake_records(d_prims, n_prims, d_verts, d_normals, d_uvs, d_alpha, any_attr, nullptr,
+                                   (void **)&s->d_prims, (void **)&s->d_extras, &err)) {
+            set_error(err);
+            ok = false;
+        }
+    }
     if (!ok) {
+        const std::string why = nnbvh_last_error();
         nnbvh_kd_scene_destroy(s);
+        set_error(why);
         return nullptr;
     }
     s->has_alpha_tex = any_alpha_tex ? 1 : 0;

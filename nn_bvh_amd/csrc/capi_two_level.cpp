@@ -189,8 +189,6 @@ nnbvh_scene *nnbvh::create_instanced_gpu_build(
     }
     DeviceGuard guard(device);
     if (!guard.ok) return nullptr;
-    hipDeviceProp_t prop;
-    if (!hip_ok(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties")) return nullptr;
     const auto t_start = std::chrono::steady_clock::now();
 
     // with a per-primitive array to carry along, the builds run with ids = positions in the caller's array; the
@@ -303,7 +301,7 @@ nnbvh_scene *nnbvh::create_instanced_gpu_build(
         if (!build(in, &r)) return nullptr;
         child_base[(size_t)k] = child_total;
         child_total += r.total_nodes;
-        // (create_scene walks only the trees a placement names: an object nobody places adds nothing to the depth)
+        // (only the trees a placement names are ever walked: an object nobody places adds nothing to the depth)
         if (named[(size_t)k]) child_depth = std::max(child_depth, r.depth + 1);
     }
     // the top tree over the instances' bounds, straight into the front of the scene's node array
@@ -380,37 +378,8 @@ nnbvh_scene *nnbvh::create_instanced_gpu_build(
         return nullptr;
     }
 
-    // the scene object, filled as create_scene (bvh_capi.cpp) fills it for a two-level scene
-    auto *s = new nnbvh_scene;
-    s->device = device;
-    s->n_cus = prop.multiProcessorCount;
-    s->n_interior = b.n_interior;
-    s->n_slots = b.n_slots;
-    s->depth = depth;
-    std::memcpy(s->bounds, b.bounds, sizeof b.bounds);
-    s->root_ref = b.root_ref;
-    s->instanced = 1;
-    s->has_host_prims = (b.has_host_prims || b.has_alpha) ? 1 : 0;
-    s->has_alpha = b.has_alpha;
-    s->has_patches = 1;  // two-level scenes always run the general kernels
-    s->max_grid_threads = s->n_cus * 8 * kBlockThreads;
-    s->d_wide = (float4 *)b.d_wide;
-    s->d_prims = (float4 *)b.d_prims;
-    s->device_bytes = ((((size_t)std::max(b.n_interior, 1) * sizeof(WideNode)) + 255) & ~(size_t)255) +
-                      std::max<size_t>((size_t)b.n_slots, 1) * 16 + 64;
-    if (animated) {
-        std::vector<float> table((size_t)n_placements * kAnimStride, 0.0f);
-        for (int k = 0; k < n_placements; ++k) fill_anim_entry(animated[k], &table[(size_t)k * kAnimStride]);
-        if (!hip_ok(hipMalloc((void **)&s->d_anim, table.size() * 4), "hipMalloc(animation table)") ||
-            !hip_ok(hipMemcpy(s->d_anim, table.data(), table.size() * 4, hipMemcpyHostToDevice),
-                    "hipMemcpy(animation table)")) {
-            nnbvh_scene_destroy(s);
-            return nullptr;
-        }
-        s->n_anim = n_placements;
-    }
-    if (hipMalloc((void **)&s->d_stats, nnbvh::kSchedStatWords * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(s->d_stats, 0, nnbvh::kSchedStatWords * sizeof(unsigned long long));
+    nnbvh_scene *s = scene_from_baked(b, depth, device, true);
+    if (!s || (animated && !upload_anim_table(s, animated, n_placements))) return nullptr;
     s->build_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     return s;
 }

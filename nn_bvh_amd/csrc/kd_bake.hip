@@ -1,8 +1,10 @@
-// kd_bake.hip — a kd-tree scene created entirely on the device (nnbvh_kd_scene_create_gpu_build): the primitive
-// bounds kd_prepare (kd_build.cpp) computes on the host, their union, the device builder (kd_build_gpu.hip) with its
-// result left where it is, and the primitive records nnbvh_kd_scene_create_with_attributes (capi_kd.cpp) bakes on the
-// host — bit for bit what nnbvh_kd_build_create_stable + nnbvh_kd_scene_create_with_attributes upload, without the
-// tree's round trip through host memory.
+// kd_bake.hip — the primitive records and attribute slots of every kd-tree scene (kd_bake_records: the ONE writer of
+// that layout, for the caller's tree uploaded by capi_kd.cpp and for the device-built one; tests/test_bake_golden.py
+// holds its bytes to a recording), and a kd-tree scene created entirely on the device
+// (nnbvh_kd_scene_create_gpu_build): the primitive bounds kd_prepare (kd_build.cpp) computes on the host, their union,
+// the device builder (kd_build_gpu.hip) with its result left where it is, and the records — bit for bit the scene of
+// nnbvh_kd_build_create_stable + nnbvh_kd_scene_create_with_attributes, without the tree's round trip through host
+// memory.
 //
 //   k_kd_prim_bounds   one lane per primitive: kind and vertex indices are checked BEFORE anything is gathered with
 //                      them (the list is the caller's, unvalidated); Triangle::Bounds / BilinearPatch::Bounds in the
@@ -52,14 +54,6 @@ struct KdHave {  // which optional arrays the caller gave; alphaTex: an alpha-te
 __device__ __forceinline__ float first_min(float a, float b) { return b < a ? b : a; }
 __device__ __forceinline__ float first_max(float a, float b) { return a < b ? b : a; }
 
-// the alpha-tested kinds that read per-vertex attributes run on the device when the caller gave what they read
-// (capi_kd.cpp, on_device)
-__device__ __forceinline__ bool attr_on_device(int kind, bool normals, bool uvs, bool primAlpha) {
-    if (is_smooth_alpha_kind(kind)) return normals;
-    if (is_alpha_patch_kind(kind))
-        return primAlpha && (!is_smooth_alpha_patch_kind(kind) || normals) && (!is_uv_alpha_patch_kind(kind) || uvs);
-    return false;
-}
 // 0: not a kind with vertices.  A textured triangle (kinds 16 .. 19, scenes with an alpha-texture table) has three:
 // its v[3] is the texture index, which the host has checked
 __device__ __forceinline__ int kd_vertex_count(int kind, bool alphaTex) {
@@ -149,8 +143,8 @@ __global__ __launch_bounds__(kBb) void k_kd_prim_bounds(const nnbvh_prim *__rest
                 if (box_finite(b)) box_keys(b, i, key);
                 else why = kKdNonFinite;
             }
-            // the scene flags of the host bake (capi_kd.cpp)
-            const bool attr = attr_on_device(p.kind, have.normals, have.uvs, have.primAlpha);
+            // the scene flags, as capi_kd.cpp computes them for a caller's tree
+            const bool attr = kd_attr_on_device(p.kind, have.normals, have.uvs, have.primAlpha);
             if (is_alphatex_kind(p.kind)) flags |= kFlagHasHost | kFlagHasPatch | kFlagAnyAttr | kFlagAlphaTex;
             else if ((is_smooth_alpha_kind(p.kind) || is_alpha_patch_kind(p.kind)) && !attr) flags |= kFlagHasHost;
             else if (attr || is_flat_alpha_kind(p.kind)) flags |= kFlagHasHost | kFlagHasPatch | (attr ? kFlagAnyAttr : 0u);
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(kBb) void k_kd_bake(const nnbvh_prim *__restrict__ 
     const int i = blockIdx.x * kBb + threadIdx.x;
     if (i >= n) return;
     const nnbvh_prim p = prims[i];
-    const bool attr = attr_on_device(p.kind, normals != nullptr, uvs != nullptr, primAlpha != nullptr);
+    const bool attr = kd_attr_on_device(p.kind, normals != nullptr, uvs != nullptr, primAlpha != nullptr);
     const bool tex = is_alphatex_kind(p.kind);  // (only scenes with an alpha-texture table get this far with one)
     const int nv = (is_triangle_kind(p.kind) || tex) ? 3 : 4;
     float s[16], ex[24];
@@ -207,7 +201,7 @@ __global__ __launch_bounds__(kBb) void k_kd_bake(const nnbvh_prim *__restrict__ 
             if (p.kind == NNBVH_PRIM_ALPHA_TRIANGLE_SMOOTH_FLIPPED || is_flipped_alpha_patch_kind(p.kind)) flags |= kPrimFlipN;
         }
         if (tex) {
-            // as capi_kd.cpp bakes it: normals in slots 0 .. 2 (smooth kinds), the three (u, v) pairs — the mesh's or
+            // normals in slots 0 .. 2 (smooth kinds), the three (u, v) pairs — the mesh's or
             // the default corners (0,0), (1,0), (1,1) — in slots 4 / 5, the texture index (v[3]) in slot 2's w below
             const bool smooth = is_smooth_alphatex_kind(p.kind);
             for (int j = 0; j < 3 && smooth; ++j)
@@ -281,6 +275,29 @@ inline int grid_of(long n) { return (int)((n + kBb - 1) / kBb); }
         }                                                                                    \
     } while (0)
 
+bool kd_bake_records(const nnbvh_prim *d_prims, int n_prims, const float *d_verts, const float *d_normals,
+                     const float *d_uvs, const float *d_prim_alpha, bool any_attr, hipStream_t stream, void **d_rec,
+                     void **d_extras, std::string *error) {
+    DevMem mem;
+    auto *dRec = (float4 *)mem.get((size_t)n_prims * 64);
+    auto *dExtras = any_attr ? (float4 *)mem.get((size_t)n_prims * 96) : nullptr;
+    if (!dRec || (any_attr && !dExtras)) {
+        *error = "device kd scene: hipMalloc(primitive records) failed";
+        return false;
+    }
+    hipLaunchKernelGGL(k_kd_bake, dim3(grid_of(n_prims)), dim3(kBb), 0, stream, d_prims, n_prims, d_verts, d_normals, d_uvs,
+                       d_prim_alpha, dRec, dExtras);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        *error = std::string("device kd scene: bake kernel: ") + hipGetErrorString(e);
+        return false;
+    }
+    *d_rec = mem.take(dRec);
+    *d_extras = mem.take(dExtras);
+    return true;
+}
+
 nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *fault, std::string *error) {
     *fault = kKdPrimOk;
     const int n = in.n_prims;
@@ -353,15 +370,10 @@ nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *
     mem.free_one(dPrep);
 
     // ---- primitive records -------------------------------------------------------------------------------------
-    auto *dRec = (float4 *)mem.get((size_t)n * 64);
-    auto *dExtras = (prep.flags & kFlagAnyAttr) ? (float4 *)mem.get((size_t)n * 96) : nullptr;
-    if (!dRec || ((prep.flags & kFlagAnyAttr) && !dExtras)) {
-        *error = "device kd scene: hipMalloc(primitive records) failed";
+    void *dRec = nullptr, *dExtras = nullptr;
+    if (!kd_bake_records(dPrims, n, dVerts, dNormals, dUVs, dAlpha, (prep.flags & kFlagAnyAttr) != 0, stream, &dRec, &dExtras,
+                         error))
         return nullptr;
-    }
-    hipLaunchKernelGGL(k_kd_bake, dim3(grid_of(n)), dim3(kBb), 0, stream, dPrims, n, dVerts, dNormals, dUVs, dAlpha, dRec, dExtras);
-    KB_CHECK(hipGetLastError(), "bake kernel");
-    KB_CHECK(hipStreamSynchronize(stream), "bake kernel");
 
     // (depth <= max_depth <= 64 by the caller's check: the tree is the library's own, nothing to validate)
     nnbvh_kd_scene *s = kd_new_scene(in.device, prop.multiProcessorCount, tree.depth, (prep.flags & kFlagHasHost) != 0,
@@ -369,8 +381,8 @@ nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *
     s->d_nodes = (uint2 *)tree.d_nodes;
     s->d_indices = tree.d_indices;
     tree.release();
-    s->d_prims = (float4 *)mem.take(dRec);
-    s->d_extras = (float4 *)mem.take(dExtras);
+    s->d_prims = (float4 *)dRec;
+    s->d_extras = (float4 *)dExtras;
     s->has_alpha_tex = (prep.flags & kFlagAlphaTex) ? 1 : 0;
     // the descriptor table and the texel pool are the only arrays of such a scene that come from the host
     if (have.alphaTex && !kd_attach_alpha_textures(s, in.textures, in.n_textures)) {

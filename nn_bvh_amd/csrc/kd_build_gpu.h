@@ -86,6 +86,13 @@ struct KdSceneInputs {
     int n_textures;
 };
 
+// The 64-B primitive records of a kd scene, in the order of d_prims, and with any_attr its 96-B attribute slots (else
+// *d_extras = nullptr), baked from device arrays on `stream` (kd_bake.hip; the device is current, the list and what its
+// kinds read have been checked).  Both results are hipMalloc'ed and the caller's; the stream is idle on return.
+bool kd_bake_records(const nnbvh_prim *d_prims, int n_prims, const float *d_verts, const float *d_normals,
+                     const float *d_uvs, const float *d_prim_alpha, bool any_attr, hipStream_t stream, void **d_rec,
+                     void **d_extras, std::string *error);
+
 // Triangles in, traceable kd scene out; the tree never visits the host (kd_bake.hip).  nullptr with *fault set for a
 // bad primitive list, else nullptr with *error set.
 nnbvh_kd_scene *kd_scene_create_on_device(const KdSceneInputs &in, KdPrimFault *fault, std::string *error);

@@ -84,6 +84,16 @@ constexpr bool is_flat_alpha_kind(int kind) {
     return kind == NNBVH_PRIM_ALPHA_TRIANGLE || kind == NNBVH_PRIM_ALPHA_TRIANGLE_FLIPPED;
 }
 
+// kd scenes: the alpha-tested kinds that read per-vertex or per-primitive arrays run on the device when the caller
+// gave what they read (their geometry and attribute slots are baked); without, they are the host's (a record without
+// geometry).  ONE rule for the scene flags capi_kd.cpp computes and for the device baker (kd_bake.hip)
+constexpr bool kd_attr_on_device(int kind, bool normals, bool uvs, bool prim_alpha) {
+    if (is_smooth_alpha_kind(kind)) return normals;
+    if (is_alpha_patch_kind(kind))
+        return prim_alpha && (!is_smooth_alpha_patch_kind(kind) || normals) && (!is_uv_alpha_patch_kind(kind) || uvs);
+    return false;
+}
+
 // image-textured alpha on triangles: kind = 16 + flipped + 2 * smooth.  NOT an is_triangle_kind: only the builders and
 // the creation calls with an alpha-texture table (flat and two-level BVH scenes, kd scenes) take them
 constexpr bool is_alphatex_kind(int kind) { return kind >= NNBVH_PRIM_ALPHATEX_TRIANGLE && kind <= NNBVH_PRIM_ALPHATEX_TRIANGLE_SMOOTH_FLIPPED; }
@@ -116,9 +126,9 @@ constexpr int kTopRecords = 63;
 constexpr int32_t kTopTag = 1 << 30;
 
 // The degenerate-triangle test of shapes.cpp:176-177, LengthSquared(Cross(p2 - p0, p1 - p0)) == 0 with
-// DifferenceOfProducts (util/math.h:569-575), in the reference's float32 operations: ONE function for the host bake
-// (capi_kd.cpp) and the device bake (kd_bake.hip) of the kd primitive records, so that both set kPrimDegenerate from
-// the same bits.  The fused multiply-adds are explicit; the build's -ffp-contract=off forms no others.
+// DifferenceOfProducts (util/math.h:569-575), in the reference's float32 operations, for the bake of the kd primitive
+// records (kd_bake.hip) and host code that wants the same bits.  The fused multiply-adds are explicit; the build's
+// -ffp-contract=off forms no others.
 #if defined(__HIPCC__)
 #define NNBVH_HD __host__ __device__
 #else

@@ -63,9 +63,13 @@ def test_tie_order_changes_nothing_but_the_order_inside_leaves(max_prims):
 @pytest.mark.gpu
 @pytest.mark.parametrize("max_prims,max_depth", [(1, -1), (4, -1), (1, 6), (2, 3)])
 def test_device_kd_build_equals_the_host_builder(max_prims, max_depth):
+    import torch
+    # the build runs on the last device: on a machine with several, not the one that is current
+    device, before = torch.cuda.device_count() - 1, torch.cuda.current_device()
     for name, (verts, prims) in scenes():
         h = build_kd_tree(prims, verts, max_prims=max_prims, max_depth=max_depth, where="host_stable")
-        g = build_kd_tree(prims, verts, max_prims=max_prims, max_depth=max_depth, where="gpu")
+        g = build_kd_tree(prims, verts, max_prims=max_prims, max_depth=max_depth, where="gpu", device=device)
+        assert torch.cuda.current_device() == before, f"{name}: the build left device {torch.cuda.current_device()} current"
         assert g.nodes.tobytes() == h.nodes.tobytes(), f"{name}: node arrays differ"
         assert g.prim_indices.tobytes() == h.prim_indices.tobytes(), f"{name}: primitiveIndices differ"
         assert g.depth == h.depth and np.array_equal(g.bounds, h.bounds)

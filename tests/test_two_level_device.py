@@ -271,6 +271,41 @@ def test_argument_faults_are_reported_before_any_device_call(nnbvh_lib):
     refused("only the sah and hlbvh", split=3)
 
 
+def test_host_tree_call_refuses_a_malformed_node_outside_every_instances_tree(nnbvh_lib):
+    """The nodes of an object no instance names are not walked by the tree validation, yet the bake makes a record of
+    each and looks up each leaf's slot: what they index with is range-checked before anything goes to a device
+    (device = an index no machine has; the well-formed scene gets as far as the device check)."""
+    pt, verts, objects, pl, _ = edge_shape("unnamed object")
+    h = host_route(pt, verts, objects, pl)
+    named = np.zeros(len(h["nodes"]), bool)
+    named[:h["n_top"]] = True
+    for inst in h["instances"]:
+        named[inst["root"]:inst["root"] + inst["n_nodes"]] = True
+    unnamed = np.nonzero(~named)[0]
+    interior = unnamed[h["nodes"]["nprims"][unnamed] == 0]
+    leaves = unnamed[h["nodes"]["nprims"][unnamed] != 0]
+    assert len(interior) > 2 and len(leaves) > 2
+
+    def create(nodes):
+        return nnbvh_lib.nnbvh_scene_create_instanced(ptr(nodes), len(nodes), h["n_top"], ptr(h["prims"]), len(h["prims"]),
+                                                     ptr(verts), len(verts), ptr(h["instances"]), len(h["instances"]),
+                                                     1 << 20)
+
+    assert not create(h["nodes"]) and "no usable HIP device" in _lib.last_error()
+    bad = [(interior[1], "offset", len(h["nodes"])), (interior[1], "offset", 1 << 30), (interior[0], "offset", -1),
+           (interior[2], "offset", interior[2] + 1), (interior[0], "axis", 3),
+           (leaves[0], "offset", len(h["prims"])), (leaves[1], "offset", -1), (leaves[-1], "nprims", 60000)]
+    for node, field, value in bad:
+        nodes = h["nodes"].copy()
+        nodes[field][node] = value
+        assert not create(nodes), (node, field, value)
+        assert "scene_create: malformed node outside every instance's tree" in _lib.last_error(), (node, field, value)
+    # the same damage inside a named tree is the tree validation's to report, as before
+    nodes = h["nodes"].copy()
+    nodes["offset"][h["instances"]["root"][0]] = len(nodes)
+    assert not create(nodes) and "outside the node's subtree range" in _lib.last_error()
+
+
 def test_scene_read_refuses_a_null_scene(nnbvh_lib):
     out = np.zeros(16, np.uint32)
     assert nnbvh_lib.nnbvh_scene_read(None, 0, ptr(out), out.nbytes) == 1  # NNBVH_ERR_ARG

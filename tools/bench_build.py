@@ -6,15 +6,15 @@ HLBVH.  Prints one JSON object.  usage: tools/bench_build.py [scene ...]
 kd section (--kd: both sections, --kd-only: this one alone; scenes default to bathroom and crown; --kd-out=PATH
 writes the table, default profiles/kd_device_scene.txt): creating a kd-tree scene, in one process alternated
 A B A B ..., medians with min..max:
-  A  build_kd_tree(where="gpu") + KdTreeAggregate.from_tree   the tree downloaded, validated and baked on the host
+  A  build_kd_tree(where="gpu") + KdTreeAggregate.from_tree   the tree downloaded, validated, uploaded again and baked
   B  KdTreeAggregate.build_on_device                          bounds, tree and records made and kept on the device
   C  build_kd_tree(where="host") + from_tree, once, for the record
 and the peak of the device memory in use during one B (sampled from a second thread) beside what the scene keeps.
 
 two-level section (--two-level: with the other sections, --two-level-only: alone; --two-level-out=PATH, default
 profiles/two_level_device_scene.txt): creating a two-level (instanced) scene, the same way:
-  A0 instancing.assemble_two_level + BVHAggregate.from_tree   every tree from the host builder, host bake
-  A  the same with the child and top trees from build_tree_gpu (built on the device, downloaded, host bake)
+  A0 instancing.assemble_two_level + BVHAggregate.from_tree   every tree from the host builder, uploaded and baked
+  A  the same with the child and top trees from build_tree_gpu (built on the device, downloaded, uploaded and baked)
   B  BVHAggregate.build_two_level_on_device                    every tree built, numbered and baked on the device, the
                                                                object trees in ONE forest pass
   L  the same with NNBVH_TWO_LEVEL_LOOP=1                      ... the object trees one after another (B before the
@@ -106,11 +106,11 @@ def kd_section(names, out_path, rounds=5):
                    "B behind A by more than either spread" if -gain > spread else "B and A within the spread")
         lines += [f"{name}: {source}",
                   f"  {len(tris)} triangles, {info['n_nodes']} nodes, {info['n_indices']} indices, depth {info['depth']}",
-                  f"  A  device build + download + host bake   {stats(a_ms)}",
+                  f"  A  device build, down, up again + bake   {stats(a_ms)}",
                   f"     of which the builder itself           {stats([m[0] for m in a_dev])} on the device, "
                   f"{np.median([m[1] for m in a_dev]):.1f} ms with the download",
                   f"  B  build_on_device                       {stats(b_ms)}",
-                  f"  C  host build + host bake (once)         {c_ms:9.1f} ms  (build {c_build:.1f})",
+                  f"  C  host build + upload + bake (once)     {c_ms:9.1f} ms  (build {c_build:.1f})",
                   f"  median A - median B = {gain:.1f} ms, larger spread {spread:.1f} ms: {verdict}",
                   f"  B device memory: peak {(base - low[0]) / 2**20:.0f} MiB in use during the call (sampled), "
                   f"{kept / 2**20:.0f} MiB kept (scene arrays {info['device_bytes'] / 2**20:.0f} MiB)", ""]
@@ -287,8 +287,8 @@ def two_level_section(out_path, rounds=5, split="sah"):
                   f"  {sum(len(o) for o in objects)} object + {len(top)} top-level primitives, {len(objects)} objects, "
                   f"{len(placements)} placements; {info['interior_records']} interior records, "
                   f"{info['prim_slots']} slots, depth {info['depth']}",
-                  f"  A0 host trees + host bake                 {stats(ms['route_a0'])}",
-                  f"  A  device trees, downloaded + host bake   {stats(a_ms)}",
+                  f"  A0 host trees, uploaded + baked           {stats(ms['route_a0'])}",
+                  f"  A  device trees, down, up again + baked   {stats(a_ms)}",
                   f"  L  build_two_level_on_device, object loop {stats(l_ms)}",
                   f"  B  build_two_level_on_device, forest      {stats(b_ms)}",
                   f"  median A - median B = {gain:.1f} ms, larger spread {spread:.1f} ms: {verdict}",
