@@ -6,7 +6,17 @@ import pytest
 
 import oracle_binding as ob
 import scenes_small as ss
+from ledger_cases import BVH, bvh, reaches
 from nn_bvh_amd import build_tree, scene
+
+# case -> (kernel family, the instances its device calls launch), asserted by `reaches` (tests/ledger_cases.py):
+# Intersect, IntersectP with counts and the plain IntersectP inside static (INST = 1) and animated (INST = 2) instances,
+# on constant-alpha triangles alone (ALPHA = 1) and beside alpha-tested patches (ALPHA = 2)
+LEDGER = {
+    "test_device_alpha_inside_instances": (BVH, bvh((0, 1, 2), inst=1, alpha=1)),
+    "test_device_alpha_patches_and_smooth_triangles_inside_instances[False]": (BVH, bvh((0, 1, 2), inst=1, alpha=2)),
+    "test_device_alpha_patches_and_smooth_triangles_inside_instances[True]": (BVH, bvh((0, 1, 2), inst=2, alpha=2)),
+}
 
 
 def alpha_scene(seed=4, n=3000):
@@ -116,16 +126,19 @@ def test_device_alpha_inside_instances():
     placements = [(0, M[j, :3].reshape(12), Mi[j, :3].reshape(12)) for j in range(n_place)]
     top = prims[:0]
     nodes, aprims, instances, n_top = instancing.assemble_two_level(top, verts, [prims], placements)
-    agg = BVHAggregate.from_tree(nodes, aprims, verts, instances=instances, n_top_nodes=n_top)
     rays = scene.random_rays(40000, [-25, -25, -25], [25, 25, 25], 13)
-    got = agg.Intersect(rays)
+    with reaches(LEDGER, "test_device_alpha_inside_instances"):
+        agg = BVHAggregate.from_tree(nodes, aprims, verts, instances=instances, n_top_nodes=n_top)
+        got = agg.Intersect(rays)
+        occ, vis, tst = agg.IntersectP(rays, counts=True)
+        occ2 = agg.IntersectP(rays)
+        agg.close()
     exp = ob.closest_inst(nodes, aprims, verts, instances, rays, 4)
     assert (got["instance"] == -1).sum() == 0 and got.tobytes() == exp.tobytes()
     assert (got["instance"] > 0).mean() > 0.1
-    occ, vis, tst = agg.IntersectP(rays, counts=True)
     eo, ev, et = ob.any_hit_inst(nodes, aprims, verts, instances, rays, 4)
     assert np.array_equal(occ, eo) and np.array_equal(vis, ev) and np.array_equal(tst, et)
-    agg.close()
+    assert np.array_equal(occ2, eo)
 
 
 def smooth_alpha_scene(seed=21, n=5000):
@@ -406,10 +419,12 @@ def test_device_alpha_patches_and_smooth_triangles_inside_instances(animated):
     rays = scene.random_rays(60000, [-25, -25, -25], [25, 25, 25], 13)
     if animated:
         rays["time"] = np.random.default_rng(6).uniform(-0.2, 1.2, len(rays)).astype(np.float32)
-    agg = BVHAggregate.from_tree(nodes, aprims, verts, instances=instances, n_top_nodes=n_top, animated=anims,
-                                 normals=normals, uvs=uvs, prim_alpha=a_ord)
-    got = agg.Intersect(rays)
-    occ, vis, tst = agg.IntersectP(rays, counts=True)
+    with reaches(LEDGER, f"test_device_alpha_patches_and_smooth_triangles_inside_instances[{animated}]"):
+        agg = BVHAggregate.from_tree(nodes, aprims, verts, instances=instances, n_top_nodes=n_top, animated=anims,
+                                     normals=normals, uvs=uvs, prim_alpha=a_ord)
+        got = agg.Intersect(rays)
+        occ, vis, tst = agg.IntersectP(rays, counts=True)
+        occ2 = agg.IntersectP(rays)
     try:
         ob.set_vertex_normals(normals)
         ob.set_vertex_uvs(uvs)
@@ -428,6 +443,7 @@ def test_device_alpha_patches_and_smooth_triangles_inside_instances(animated):
         ob.set_prim_alpha(None)
     assert got.tobytes() == exp.tobytes()
     assert np.array_equal(occ, eo) and np.array_equal(vis, ev) and np.array_equal(tst, et)
+    assert np.array_equal(occ2, eo)
     hit_kind = prims["kind"][np.maximum(exp["prim"], 0)]
     inside = (exp["prim"] >= 0) & (exp["instance"] > 0)
     for k in (6, 7, 8, 11, 12, 15):

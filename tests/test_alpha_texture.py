@@ -16,6 +16,7 @@ import pytest
 import alpha_texture_oracle as ato
 import oracle_binding as ob
 import scenes_small as ss
+from ledger_cases import BVH, bvh, reaches
 from nn_bvh_amd import AlphaTexture, BVHAggregate, NNBVHError, _lib, build, build_tree, scene
 from nn_bvh_amd._lib import ptr
 
@@ -359,6 +360,16 @@ def test_the_oracle_alone_rejects_and_accepts_enough(name):
 
 # ---- GPU: the kernels against the per-ray oracle ---------------------------------------------------------------------------
 CASES = [("soup", 4, True), ("soup", 1, True), ("soup", 4, False), ("grid", 4, True), ("grid", 1, True), ("grid", 4, False)]
+# case -> (kernel family, the instances its device calls launch), asserted by `reaches` (tests/ledger_cases.py): the
+# ALPHA = 3 instances <M,8,0,1,3> and, beside host-only primitives, their HOSTC twins <0/2,8,0,1,3,0,1>
+LEDGER = {f"test_device_equals_the_per_ray_oracle[{name}-{max_prims}-{with_uvs}-{route}]": (BVH, bvh((0, 1, 2), alpha=3))
+          for name, max_prims, with_uvs in CASES for route in ("host_tree", "device_build")}
+LEDGER.update({
+    # an alpha scene has no mode-3 form: the batches and the gathered queues run as modes 0 and 2
+    "test_batches_call_and_wavefront_queues": (BVH, bvh((0, 2), alpha=3)),
+    # the plain Intersect beside the two candidate calls
+    "test_mixed_with_host_only_primitives_through_candidates": (BVH, bvh((0, 2), alpha=3, hostc=1) | bvh((0,), alpha=3)),
+})
 
 
 def make_aggregate(c, route, max_prims):
@@ -379,21 +390,22 @@ def first_bad(got, exp):
 def test_device_equals_the_per_ray_oracle(name, max_prims, with_uvs, route):
     """closest (prim, t, b, both counters, void mark), any hit with counts (mode 1) and without (mode 2)"""
     c = case(name, max_prims, with_uvs)
-    agg = make_aggregate(c, route, max_prims)
-    try:
-        got = agg.Intersect(c.rays)
-        assert got.tobytes() == c.closest.tobytes(), first_bad(got, c.closest)
-        eo, ev, et = c.any_hit
-        occ, vis, tst = agg.IntersectP(c.rays, counts=True)
-        assert np.array_equal(occ, eo) and np.array_equal(vis, ev) and np.array_equal(tst, et)
-        assert np.array_equal(agg.IntersectP(c.rays), eo)
-        for k in (1, 63, 64, 65, 257):  # batches below, at and above one wavefront, and above one block
-            assert agg.Intersect(c.rays[:k]).tobytes() == c.closest[:k].tobytes(), k
-            assert np.array_equal(agg.IntersectP(c.rays[:k]), eo[:k]), k
-            o2, v2, t2 = agg.IntersectP(c.rays[-k:], counts=True)
-            assert np.array_equal(o2, eo[-k:]) and np.array_equal(v2, ev[-k:]) and np.array_equal(t2, et[-k:]), k
-    finally:
-        agg.close()
+    with reaches(LEDGER, f"test_device_equals_the_per_ray_oracle[{name}-{max_prims}-{with_uvs}-{route}]"):
+        agg = make_aggregate(c, route, max_prims)
+        try:
+            got = agg.Intersect(c.rays)
+            assert got.tobytes() == c.closest.tobytes(), first_bad(got, c.closest)
+            eo, ev, et = c.any_hit
+            occ, vis, tst = agg.IntersectP(c.rays, counts=True)
+            assert np.array_equal(occ, eo) and np.array_equal(vis, ev) and np.array_equal(tst, et)
+            assert np.array_equal(agg.IntersectP(c.rays), eo)
+            for k in (1, 63, 64, 65, 257):  # batches below, at and above one wavefront, and above one block
+                assert agg.Intersect(c.rays[:k]).tobytes() == c.closest[:k].tobytes(), k
+                assert np.array_equal(agg.IntersectP(c.rays[:k]), eo[:k]), k
+                o2, v2, t2 = agg.IntersectP(c.rays[-k:], counts=True)
+                assert np.array_equal(o2, eo[-k:]) and np.array_equal(v2, ev[-k:]) and np.array_equal(t2, et[-k:]), k
+        finally:
+            agg.close()
     textured = ato.is_textured(c.prims["kind"])
     assert (textured[np.maximum(c.closest["prim"], 0)] & (c.closest["prim"] >= 0)).mean() > 0.1
 
@@ -431,41 +443,42 @@ def test_batches_call_and_wavefront_queues():
     from test_wavefront import QUEUES, shadow_inputs
     c = case("soup", 4, True)
     dev = torch.device("cuda", 0)
-    agg = make_aggregate(c, "host_tree", 4)
-    try:
-        n = len(c.rays)
-        d_rays = torch.from_numpy(c.rays.view(np.uint8).reshape(n, 32)).to(dev)
-        d_hits = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
-        d_occ = torch.full((n,), 9, dtype=torch.uint8, device=dev)
-        agg.trace_batches_device([("closest", d_rays.data_ptr(), n, d_hits.data_ptr()),
-                                  ("any", d_rays.data_ptr(), n, d_occ.data_ptr())])
-        torch.cuda.synchronize()
-        got = d_hits.cpu().numpy().view(_lib.HIT_DTYPE).reshape(-1)
-        assert got.tobytes() == c.closest.tobytes(), first_bad(got, c.closest)
-        assert np.array_equal(d_occ.cpu().numpy(), c.any_hit[0])
-        # the wavefront call: the same rays without their tMax in the closest queue, with it in the shadow queue
-        far = c.rays.copy()
-        far["tmax"] = np.inf
-        per = ato.PerRayOracle.__new__(ato.PerRayOracle)
-        per.nodes, per.prims, per.verts, per.rays = c.tree.nodes, np.ascontiguousarray(c.tree.ordered_prims), c.verts, far
-        per.normals, per.alpha, per.tex = c.normals, c.alpha, c.tex  # alpha does not depend on tMax
-        exp_far = per.closest()
-        Ld, r_u, r_l, px, L = shadow_inputs(n, n + 100, 7)
-        t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-        rq, sq = RayQueue.from_records(far, dev), RayQueue.from_records(c.rays, dev, shadow=True)
-        wf = WavefrontAggregate(agg)
-        queues = {k: WorkQueue(n, dev) for k in QUEUES}
-        hits_t = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
-        L_t, occ_t = t(L), torch.full((n,), 9, dtype=torch.uint8, device=dev)
-        wf.IntersectClosestAndShadow(n, rq, n, sq, t(Ld), t(r_u), t(r_l), t(px), L_t, hits=hits_t, occluded=occ_t, **queues)
-        torch.cuda.synchronize()
-        got = hits_t.cpu().numpy().view(_lib.HIT_DTYPE).reshape(-1)
-        assert got.tobytes() == exp_far.tobytes(), first_bad(got, exp_far)
-        assert np.array_equal(occ_t.cpu().numpy(), c.any_hit[0])
-        expL = ob.record_shadow(c.any_hit[0], Ld, r_u, r_l, px, L)
-        assert np.array_equal(L_t.cpu().numpy().view(np.uint32), expL.view(np.uint32))
-    finally:
-        agg.close()
+    with reaches(LEDGER, "test_batches_call_and_wavefront_queues"):
+        agg = make_aggregate(c, "host_tree", 4)
+        try:
+            n = len(c.rays)
+            d_rays = torch.from_numpy(c.rays.view(np.uint8).reshape(n, 32)).to(dev)
+            d_hits = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+            d_occ = torch.full((n,), 9, dtype=torch.uint8, device=dev)
+            agg.trace_batches_device([("closest", d_rays.data_ptr(), n, d_hits.data_ptr()),
+                                      ("any", d_rays.data_ptr(), n, d_occ.data_ptr())])
+            torch.cuda.synchronize()
+            got = d_hits.cpu().numpy().view(_lib.HIT_DTYPE).reshape(-1)
+            assert got.tobytes() == c.closest.tobytes(), first_bad(got, c.closest)
+            assert np.array_equal(d_occ.cpu().numpy(), c.any_hit[0])
+            # the wavefront call: the same rays without their tMax in the closest queue, with it in the shadow queue
+            far = c.rays.copy()
+            far["tmax"] = np.inf
+            per = ato.PerRayOracle.__new__(ato.PerRayOracle)
+            per.nodes, per.prims, per.verts, per.rays = c.tree.nodes, np.ascontiguousarray(c.tree.ordered_prims), c.verts, far
+            per.normals, per.alpha, per.tex = c.normals, c.alpha, c.tex  # alpha does not depend on tMax
+            exp_far = per.closest()
+            Ld, r_u, r_l, px, L = shadow_inputs(n, n + 100, 7)
+            t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+            rq, sq = RayQueue.from_records(far, dev), RayQueue.from_records(c.rays, dev, shadow=True)
+            wf = WavefrontAggregate(agg)
+            queues = {k: WorkQueue(n, dev) for k in QUEUES}
+            hits_t = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+            L_t, occ_t = t(L), torch.full((n,), 9, dtype=torch.uint8, device=dev)
+            wf.IntersectClosestAndShadow(n, rq, n, sq, t(Ld), t(r_u), t(r_l), t(px), L_t, hits=hits_t, occluded=occ_t, **queues)
+            torch.cuda.synchronize()
+            got = hits_t.cpu().numpy().view(_lib.HIT_DTYPE).reshape(-1)
+            assert got.tobytes() == exp_far.tobytes(), first_bad(got, exp_far)
+            assert np.array_equal(occ_t.cpu().numpy(), c.any_hit[0])
+            expL = ob.record_shadow(c.any_hit[0], Ld, r_u, r_l, px, L)
+            assert np.array_equal(L_t.cpu().numpy().view(np.uint32), expL.view(np.uint32))
+        finally:
+            agg.close()
 
 
 @pytest.mark.gpu
@@ -486,9 +499,10 @@ def test_mixed_with_host_only_primitives_through_candidates():
     agg = BVHAggregate.from_tree(tree_h.nodes, tree_h.ordered_prims, c.verts, normals=c.normals, uvs=c.uvs,
                                  alpha_textures=c.textures)
     try:
-        hits, cands = agg.intersect_with_host_candidates(c.rays, capacity=16)
-        occ, cands_any = agg.intersect_p_with_host_candidates(c.rays, capacity=16)
-        plain = agg.Intersect(c.rays)
+        with reaches(LEDGER, "test_mixed_with_host_only_primitives_through_candidates"):
+            hits, cands = agg.intersect_with_host_candidates(c.rays, capacity=16)
+            occ, cands_any = agg.intersect_p_with_host_candidates(c.rays, capacity=16)
+            plain = agg.Intersect(c.rays)
     finally:
         agg.close()
     cnt = cands["count"]

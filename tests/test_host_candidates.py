@@ -12,12 +12,19 @@ import pytest
 
 import oracle_binding as ob
 import scenes_small as ss
+from ledger_cases import BVH, bvh, reaches
 from nn_bvh_amd import (BVHAggregate, _lib, build_tree, candidates_dtype, instancing, resolve_host_candidates,
                         resolve_host_candidates_any, scene)
 from nn_bvh_amd._lib import HIT_DTYPE, RAY_DTYPE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = 1
+# case -> (kernel family, the instances its device calls launch), asserted by `reaches` (tests/ledger_cases.py): the
+# candidate twins <0/2,8,INST,1,0,0,1> of the two-level forms; the static case also makes the plain Intersect call
+LEDGER = {
+    "test_two_level_static_closest_and_any_hit": (BVH, bvh((0, 2), inst=1, hostc=1) | bvh((0,), inst=1)),
+    "test_two_level_animated_closest_and_any_hit": (BVH, bvh((0, 2), inst=2, hostc=1)),
+}
 
 
 # ---- the merge rule, CPU ---------------------------------------------------------------------------------
@@ -366,11 +373,12 @@ def test_two_level_static_closest_and_any_hit():
     lo = np.array([-30, -30, -30.0])
     rays = np.concatenate([scene.random_rays(25000, lo, -lo, 21),
                            scene.random_rays(5000, lo, -lo, 22, tmax=np.float32(0.5))])
-    agg = BVHAggregate.from_tree(nodes, hp, verts, instances=instances, n_top_nodes=n_top)
-    hits, cands = agg.intersect_with_host_candidates(rays, capacity=16)
-    plain = agg.Intersect(rays)
-    occ, acands = agg.intersect_p_with_host_candidates(rays, capacity=16)
-    agg.close()
+    with reaches(LEDGER, "test_two_level_static_closest_and_any_hit"):
+        agg = BVHAggregate.from_tree(nodes, hp, verts, instances=instances, n_top_nodes=n_top)
+        hits, cands = agg.intersect_with_host_candidates(rays, capacity=16)
+        plain = agg.Intersect(rays)
+        occ, acands = agg.intersect_p_with_host_candidates(rays, capacity=16)
+        agg.close()
     assert (cands["count"] >= 0).mean() > 0.99 and (cands["count"] > 0).mean() > 0.02
     assert_same_but_instance(hits, plain)
     assert np.array_equal(plain["instance"] == -1, cands["count"] != 0)
@@ -399,10 +407,11 @@ def test_two_level_animated_closest_and_any_hit():
     n = 20000
     rays = scene.random_rays(n, [-25, -25, -25], [25, 25, 25], 5)
     rays["time"] = np.random.default_rng(6).uniform(-0.2, 1.2, n).astype(np.float32)
-    agg = BVHAggregate.from_tree(nodes, hp, verts, instances=instances, n_top_nodes=n_top, animated=anims)
-    hits, cands = agg.intersect_with_host_candidates(rays, capacity=16)
-    occ, acands = agg.intersect_p_with_host_candidates(rays, capacity=16)
-    agg.close()
+    with reaches(LEDGER, "test_two_level_animated_closest_and_any_hit"):
+        agg = BVHAggregate.from_tree(nodes, hp, verts, instances=instances, n_top_nodes=n_top, animated=anims)
+        hits, cands = agg.intersect_with_host_candidates(rays, capacity=16)
+        occ, acands = agg.intersect_p_with_host_candidates(rays, capacity=16)
+        agg.close()
     assert (cands["count"] >= 0).mean() > 0.99 and (cands["count"] > 0).mean() > 0.02
     check_instances_entered(cands, placements, [prims0], top_level=False)
 

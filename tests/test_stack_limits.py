@@ -61,13 +61,12 @@ refused.
 The animated scene writes its own AnimatedTransforms (a turn about the chain axis and a slide along it): the committed
 golden ones are arbitrary affine maps, which take a ray off the child's axis, and then no depth could be proved.
 """
-import contextlib
-
 import numpy as np
 import pytest
 
 import oracle_binding as ob
 import scenes_small as ss
+from ledger_cases import assert_reached, ledger_start, reaches
 from nn_bvh_amd import HIT_DTYPE, BVHAggregate, NNBVHError, _lib, scene
 from nn_bvh_amd.kdtree import KdTreeAggregate
 
@@ -84,7 +83,8 @@ def _kd(modes, patch, o32, attr=0):
 
 
 # case -> (kernel family, the instances its device calls launch): BVH (mode, window, inst, patch, alpha, soa, hostc), kd
-# (mode, patch, o32, attr, hostc).  Asserted by `reaches`; tests/test_wide_offsets.py takes its census from it.
+# (mode, patch, o32, attr, hostc).  Asserted by `reaches` (tests/ledger_cases.py); tests/test_wide_offsets.py takes
+# its census from it.
 LEDGER = {
     "test_bvh_single_level[lean-8]": (BVH, _bvh((0, 1, 2, 3), patch=0)),
     "test_bvh_single_level[lean-4]": (BVH, _bvh((0, 1, 2), window=4)),
@@ -111,22 +111,6 @@ LEDGER = {
 }
 
 
-def ledger_start(case):
-    return _lib.instance_launches(LEDGER[case][0])
-
-
-def assert_reached(case, start):
-    """the device calls since ledger_start(case) launched exactly the instances LEDGER lists for `case`"""
-    family, want = LEDGER[case]
-    launched = {k: v - start[k] for k, v in _lib.instance_launches(family).items() if v != start[k]}
-    assert set(launched) == want, f"{case}: launched {sorted(launched.items())}, LEDGER says {sorted(want)}"
-
-
-@contextlib.contextmanager
-def reaches(case):
-    start = ledger_start(case)
-    yield
-    assert_reached(case, start)
 N_DEEP, N_RANDOM = 1500, 500
 # share of chain_rays / kd_chain_rays that are "deep": all BVH chain rays (every box is crossed whatever tMax is);
 # the kd rays with an infinite tMax (a finite one ends the interval before the far split planes)
@@ -402,7 +386,7 @@ def test_bvh_single_level(leaves, window):
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
     assert agg.info["depth"] == 64
     agg.set_option("stack_window", window)
-    with reaches(f"test_bvh_single_level[{'lean' if leaves == 'tri' else 'general'}-{window}]"):
+    with reaches(LEDGER, f"test_bvh_single_level[{'lean' if leaves == 'tri' else 'general'}-{window}]"):
         check_all_modes(agg, rays, exp, eany, f"{leaves} window {window}")
     agg.close()
 
@@ -419,7 +403,7 @@ def test_bvh_wavefront_soa():
             res = (ob.closest if kind == "closest" else ob.any_hit)(ch.nodes, ch.prims, ch.verts, r)
         return res, d.depth[:, 0]
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
-    with reaches("test_bvh_wavefront_soa"):
+    with reaches(LEDGER, "test_bvh_wavefront_soa"):
         check_queue_calls(agg, walk, rays, deep, 8, "lean SOA")
     agg.close()
 
@@ -450,7 +434,7 @@ def test_bvh_alpha(leaves):
     assert rejected.sum() >= 200, "rays whose walk differs from the walk without alpha: a hit was rejected"
     kw = dict(normals=ch.normals, prim_alpha=ch.prim_alpha, uvs=ch.uvs)
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts, **kw)
-    with reaches(f"test_bvh_alpha[{'tri' if leaves == 'alpha_tri' else 'patch'}]"):
+    with reaches(LEDGER, f"test_bvh_alpha[{'tri' if leaves == 'alpha_tri' else 'patch'}]"):
         check_all_modes(agg, rays, exp, eany, leaves, batches=False)
     agg.close()
 
@@ -481,7 +465,7 @@ def test_bvh_host_only_chain():
     assert_exceeds_window(da, deep, 8, "any")
     assert (exp["instance"][deep] == -1).sum() > 50 and (eany[0][deep] == 2).sum() > 20
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
-    start = ledger_start("test_bvh_host_only_chain")
+    start = ledger_start(LEDGER, "test_bvh_host_only_chain")
     check_all_modes(agg, rays, exp, eany, "host-only chain")
     host_ids = np.sort(ch.prims["id"][ch.prims["kind"] == 3])[::-1]
     assert len(host_ids) == 13 and host_ids.min() < 8 and host_ids.max() > 56
@@ -594,7 +578,7 @@ def test_bvh_host_only_chain():
     check_any(rays[:m], h_occ[:m], sc.numpy()[:m], "wavefront shadow")
     first = ob.record_shadow(np.where(h_occ[:m] == 0, 0, 1).astype(np.uint8), Ld[:m], r_u[:m], r_l[:m], px[:m], L)
     assert np.array_equal(d_l.cpu().numpy().view(np.uint32), first.view(np.uint32))
-    assert_reached("test_bvh_host_only_chain", start)
+    assert_reached(LEDGER, "test_bvh_host_only_chain", start)
     mesh.close()
     agg.close()
 
@@ -616,7 +600,7 @@ def test_two_level_chain():
         assert both.sum() >= N_DEEP, "every deep ray enters an instance with > 8 outer entries and goes > 8 deep in it"
     agg = BVHAggregate.from_tree(t.nodes, t.prims, t.verts, instances=t.instances, n_top_nodes=t.n_top)
     assert agg.info["depth"] == 64
-    with reaches("test_two_level_chain"):
+    with reaches(LEDGER, "test_two_level_chain"):
         check_all_modes(agg, rays, exp, eany, "two-level chain")
     assert (exp["instance"][deep] > 0).sum() > 500
     agg.close()
@@ -645,7 +629,7 @@ def test_animated_two_level_chain():
     assert (tm < 0).sum() > 50 and (tm > 1).sum() > 50
     agg = BVHAggregate.from_tree(t.nodes, t.prims, t.verts, instances=t.instances, n_top_nodes=t.n_top, animated=anims)
     assert agg.info["depth"] == 64
-    with reaches("test_animated_two_level_chain"):
+    with reaches(LEDGER, "test_animated_two_level_chain"):
         check_all_modes(agg, rays, exp, eany, "animated two-level chain")
     moving = oa["actually_animated"][np.maximum(exp["instance"] - 1, 0)] != 0
     assert ((exp["instance"] > 0) & moving & deep & (rays["time"] > 0) & (rays["time"] < 1)).sum() > 100
@@ -690,7 +674,7 @@ def test_kd_chain(form, window, offsets32):
     agg = KdTreeAggregate.from_tree(k.nodes, k.prim_indices, k.prims, k.verts, k.bounds, normals=k.normals, uvs=k.uvs,
                                     prim_alpha=k.prim_alpha)
     agg.set_option("offsets32", offsets32)
-    start = ledger_start(f"test_kd_chain[{form}{'' if offsets32 else '-wide'}]")
+    start = ledger_start(LEDGER, f"test_kd_chain[{form}{'' if offsets32 else '-wide'}]")
     assert agg.Intersect(rays).tobytes() == exp.tobytes()
     occ, vis, tst = agg.IntersectP(rays, counts=True)
     assert np.array_equal(occ, eany[0]) and np.array_equal(vis, eany[1]) and np.array_equal(tst, eany[2])
@@ -721,7 +705,7 @@ def test_kd_chain(form, window, offsets32):
         agg.set_option("read_soa", read_soa)
         agg.set_option("pair_one_launch", pair)
         check_queue_calls(agg, walk, rays, deep, window, f"kd {form} read_soa {read_soa} pair_one_launch {pair}")
-    assert_reached(f"test_kd_chain[{form}{'' if offsets32 else '-wide'}]", start)
+    assert_reached(LEDGER, f"test_kd_chain[{form}{'' if offsets32 else '-wide'}]", start)
     agg.close()
 
 
@@ -770,7 +754,7 @@ def test_full_grid_bvh_any_hit_with_counts():
     rays = np.tile(distinct, n // N_DISTINCT)
     agg = BVHAggregate.from_tree(ch.nodes, ch.prims, ch.verts)
     agg.set_option("blocks_per_cu", 8)
-    start = ledger_start("test_full_grid_bvh_any_hit_with_counts")
+    start = ledger_start(LEDGER, "test_full_grid_bvh_any_hit_with_counts")
     occ, vis, tst = agg.IntersectP(rays, counts=True)
     idx = np.random.default_rng(53).choice(n, 60000, replace=False)
     assert np.array_equal(occ[idx], eocc[idx % N_DISTINCT]) and np.array_equal(vis[idx], evis[idx % N_DISTINCT])
@@ -792,7 +776,7 @@ def test_full_grid_bvh_any_hit_with_counts():
         assert (flags.reshape(-1, N_DISTINCT) == eocc[None, :]).all()
         assert (v.cpu().numpy().reshape(-1, N_DISTINCT) == evis[None, :]).all()
         assert (c.cpu().numpy().reshape(-1, N_DISTINCT) == etst[None, :]).all()
-    assert_reached("test_full_grid_bvh_any_hit_with_counts", start)
+    assert_reached(LEDGER, "test_full_grid_bvh_any_hit_with_counts", start)
     agg.close()
 
 
@@ -808,7 +792,7 @@ def test_full_grid_kd_closest():
     n = full_grid_count()
     rays = np.tile(distinct, n // N_DISTINCT)
     agg = KdTreeAggregate.from_tree(k.nodes, k.prim_indices, k.prims, k.verts, k.bounds)
-    start = ledger_start("test_full_grid_kd_closest")
+    start = ledger_start(LEDGER, "test_full_grid_kd_closest")
     got = agg.Intersect(rays)
     idx = np.random.default_rng(55).choice(n, 60000, replace=False)
     assert got[idx].tobytes() == exp[idx % N_DISTINCT].tobytes()
@@ -817,7 +801,7 @@ def test_full_grid_kd_closest():
     d_rays = upload(rays)
     for rec in two_streams(agg.intersect_device, d_rays, n, 32):
         assert (rec.reshape(n // N_DISTINCT, -1) == one).all()
-    assert_reached("test_full_grid_kd_closest", start)
+    assert_reached(LEDGER, "test_full_grid_kd_closest", start)
     agg.close()
 
 
@@ -842,7 +826,7 @@ def test_deep_results_independent_of_tuning_and_order(which):
     def run(r):
         occ, vis, tst = agg.IntersectP(r, counts=True)
         return agg.Intersect(r), occ, vis, tst, agg.IntersectP(r)
-    start = ledger_start(f"test_deep_results_independent_of_tuning_and_order[{which}]")
+    start = ledger_start(LEDGER, f"test_deep_results_independent_of_tuning_and_order[{which}]")
     base = run(rays)
     perm = np.random.default_rng(0).permutation(len(rays))
     for a, b in zip(run(rays[perm]), base):
@@ -851,5 +835,5 @@ def test_deep_results_independent_of_tuning_and_order(which):
         agg.set_option(key, val)
         for a, b in zip(run(rays), base):
             assert a.tobytes() == b.tobytes(), f"{key}={val} changed a result"
-    assert_reached(f"test_deep_results_independent_of_tuning_and_order[{which}]", start)
+    assert_reached(LEDGER, f"test_deep_results_independent_of_tuning_and_order[{which}]", start)
     agg.close()

@@ -16,6 +16,7 @@ import alpha_texture_oracle as ato
 import oracle_binding as ob
 import scenes_small as ss
 import two_level_alpha_oracle as tlo
+from ledger_cases import BVH, assert_reached, ledger_start
 from nn_bvh_amd import AlphaTexture, BVHAggregate, NNBVHError, _lib, build_tree, scene
 from nn_bvh_amd._lib import ptr
 
@@ -441,6 +442,20 @@ def alpha_rows(inst, hostc_modes=()):
 
 
 CASES = [(True, 4, "sah"), (True, 1, "sah"), (False, 4, "sah"), (True, 4, "hlbvh"), (True, 1, "hlbvh")]
+# case -> (kernel family, the instances ALL its device calls launch), asserted by ledger_start / assert_reached
+# (tests/ledger_cases.py) around the whole case; the LaunchLedger blocks inside the tests assert the same per call
+LEDGER = {f"test_device_equals_the_per_ray_oracle[{with_uvs}-{max_prims}-{split}-{route}]": (BVH, alpha_rows(1))
+          for with_uvs, max_prims, split in CASES for route in ("host_tree", "device_build")}
+LEDGER.update({
+    "test_animated_placements_equal_the_per_ray_oracle": (BVH, alpha_rows(2)),
+    # the two candidate calls and the plain Intersect
+    "test_candidate_calls_with_host_only_triangles[static]":
+        (BVH, {(0, 8, 1, 1, 2, 0, 1), (2, 8, 1, 1, 2, 0, 1), (0, 8, 1, 1, 2, 0, 0)}),
+    "test_candidate_calls_with_host_only_triangles[animated]":
+        (BVH, {(0, 8, 2, 1, 2, 0, 1), (2, 8, 2, 1, 2, 0, 1), (0, 8, 2, 1, 2, 0, 0)}),
+    # an alpha scene has no mode-3 form: the batches and the gathered queues run as modes 0 and 2
+    "test_batches_call_and_wavefront_queues": (BVH, {(0, 8, 1, 1, 2, 0, 0), (2, 8, 1, 1, 2, 0, 0)}),
+})
 
 
 @pytest.mark.gpu
@@ -450,6 +465,8 @@ def test_device_equals_the_per_ray_oracle(with_uvs, max_prims, split, route):
     """closest (prim, t, b, both counters, instance), any hit with counts (mode 1) and without (mode 2), whole batches
     and batches of 1, 63, 64, 65 and 257; the INST = 1 x ALPHA = 2 instances are the ones launched"""
     c = case("static", with_uvs, max_prims, split)
+    key = f"test_device_equals_the_per_ray_oracle[{with_uvs}-{max_prims}-{split}-{route}]"
+    start = ledger_start(LEDGER, key)
     agg = make_aggregate(c.s, route)
     try:
         with _lib.LaunchLedger(_lib.FAMILY_BVH) as led:
@@ -468,6 +485,7 @@ def test_device_equals_the_per_ray_oracle(with_uvs, max_prims, split, route):
             assert np.array_equal(o2, eo[-k:]) and np.array_equal(v2, ev[-k:]) and np.array_equal(t2, et[-k:]), k
     finally:
         agg.close()
+    assert_reached(LEDGER, key, start)
     kinds, inside = c.hit_kind(), c.closest["instance"] > 0
     assert all((inside & (kinds == k)).sum() > 20 for k in (16, 17, 18, 19))
     assert c.rejected_by_hash().sum() > 20 and c.two_placements().sum() > 20 and c.accepted_behind_rejected().sum() > 20
@@ -505,6 +523,7 @@ def test_animated_placements_equal_the_per_ray_oracle():
     """five placements, three actually animated, ray times below, inside and above the range: the INST = 2 x ALPHA = 2
     instances"""
     c = case("animated")
+    start = ledger_start(LEDGER, "test_animated_placements_equal_the_per_ray_oracle")
     for route in ("host_tree", "device_build"):
         agg = make_aggregate(c.s, route)
         try:
@@ -519,6 +538,7 @@ def test_animated_placements_equal_the_per_ray_oracle():
             assert np.array_equal(occ2, eo)
         finally:
             agg.close()
+    assert_reached(LEDGER, "test_animated_placements_equal_the_per_ray_oracle", start)
     an = c.s.anims
     moving = (c.closest["instance"] > 0) & (an["actually_animated"][np.maximum(c.closest["instance"] - 1, 0)] != 0)
     within = (c.rays["time"] > 0) & (c.rays["time"] < 1)
@@ -539,6 +559,7 @@ def test_candidate_calls_with_host_only_triangles(name):
     hp = prims.copy()
     plain = np.nonzero(hp["kind"] == 0)[0]
     hp["kind"][plain[::2]] = 3
+    start = ledger_start(LEDGER, f"test_candidate_calls_with_host_only_triangles[{name}]")
     agg = BVHAggregate.from_tree(nodes, hp, s.verts, instances=instances, n_top_nodes=n_top, animated=s.anims,
                                  normals=s.normals, uvs=s.uvs, prim_alpha=tlo.ordered_alpha(s, prims),
                                  alpha_textures=s.textures)
@@ -553,6 +574,7 @@ def test_candidate_calls_with_host_only_triangles(name):
         assert set(led.launched) == {(0, 8, inst, 1, 2, 0, 0)}, led.launched
     finally:
         agg.close()
+    assert_reached(LEDGER, f"test_candidate_calls_with_host_only_triangles[{name}]", start)
     cnt = cands["count"]
     assert (cnt > 0).sum() > 100 and (cnt >= 0).all()
     assert np.array_equal(void["instance"] == -1, cnt != 0)
@@ -591,6 +613,7 @@ def test_batches_call_and_wavefront_queues():
     from test_wavefront import QUEUES, shadow_inputs
     c = case("static")
     dev = torch.device("cuda", 0)
+    start = ledger_start(LEDGER, "test_batches_call_and_wavefront_queues")
     agg = make_aggregate(c.s, "device_build")
     try:
         n = len(c.rays)
@@ -626,6 +649,7 @@ def test_batches_call_and_wavefront_queues():
         assert np.array_equal(L_t.cpu().numpy().view(np.uint32), expL.view(np.uint32))
     finally:
         agg.close()
+    assert_reached(LEDGER, "test_batches_call_and_wavefront_queues", start)
 
 
 @pytest.mark.gpu

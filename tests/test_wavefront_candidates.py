@@ -11,9 +11,12 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
-from nn_bvh_amd import (BVHAggregate, _lib, resolve_host_candidates, resolve_host_candidates_any, scene)
+from ledger_cases import BVH, assert_reached, bvh, ledger_start
+from nn_bvh_amd import (BVHAggregate, _lib, candidates_dtype, resolve_host_candidates, resolve_host_candidates_any,
+                        scene)
 from nn_bvh_amd._lib import HIT_DTYPE, RAY_DTYPE
-from test_host_candidates import declare_host, flat_host_scene, tri_callback, tri_table, unique_id_two_level
+from test_host_candidates import (assert_resolved_equal, declare_host, flat_host_scene, tri_callback, tri_table,
+                                  unique_id_two_level)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = 1
@@ -81,6 +84,19 @@ def test_python_layer_has_the_new_calls():
 # ---------------------------------------------------------------------------------------------------- GPU
 K = 16
 SCENES = ("flat", "two_level", "animated")
+BATCHES_TEST = "test_batches_equal_the_single_batch_candidate_calls"
+# case and part of the case -> (kernel family, the instances its device calls launch), asserted with the launch ledger
+# (tests/ledger_cases.py); a key is the pytest id followed by the part.  Per scene form INST = 0 / 1 / 2: the
+# single-batch candidate calls run the twins of modes 0 / 2; with "fused_batches" 1 the candidate batches and the plain
+# batches beside them run in ONE launch each, the mode-3 twin and the plain mode-3 form; with 0 every batch runs alone
+# on a side stream as mode 0 or 2, twin or plain
+LEDGER = {}
+for _name, _inst in zip(SCENES, (0, 1, 2)):
+    LEDGER.update({
+        f"{BATCHES_TEST}[{_name}] single calls": (BVH, bvh((0, 2), inst=_inst, hostc=1)),
+        f"{BATCHES_TEST}[{_name}] fused_batches 1": (BVH, bvh((3,), inst=_inst, hostc=1) | bvh((3,), inst=_inst)),
+        f"{BATCHES_TEST}[{_name}] fused_batches 0": (BVH, bvh((0, 2), inst=_inst, hostc=1) | bvh((0, 2), inst=_inst)),
+    })
 
 
 class Case:
@@ -236,9 +252,13 @@ def test_batches_equal_the_single_batch_candidate_calls(name):
     agg, rays = case.agg, case.rays
     parts = [("closest", rays[:4000]), ("any", rays[4000:7000].copy()), ("closest", rays[7000:])]
     parts[1][1]["tmax"] = np.float32(0.7)
+    start = ledger_start(LEDGER, f"{BATCHES_TEST}[{name}] single calls")
     refs = [single_batch_reference(agg, r, kind) for kind, r in parts]
+    assert_reached(LEDGER, f"{BATCHES_TEST}[{name}] single calls", start)
+    oracle = [case.oracle(case.oracle_closest if kind == "closest" else case.oracle_any, r) for kind, r in parts]
     assert (refs[0][1][0] > 0).any() and (refs[1][1][0] > 0).any() and (refs[2][1][1] > 0).any()  # the paths are exercised
     for fused in (1, 0):
+        start = ledger_start(LEDGER, f"{BATCHES_TEST}[{name}] fused_batches {fused}")
         agg.set_option("fused_batches", fused)
         d_rays = [upload(r) for _, r in parts]
         outs = [torch.zeros((len(r), 32) if kind == "closest" else (len(r),), dtype=torch.uint8, device=dev0())
@@ -252,6 +272,17 @@ def test_batches_equal_the_single_batch_candidate_calls(name):
             what = f"{name} fused={fused} batch {b} ({kind})"
             assert o.cpu().numpy().tobytes() == ref[0].tobytes(), what + ": output"
             assert_cands_equal(c.host(), ref[1], kind == "closest", what)
+            # ... and, resolved with the host's triangle test, the oracle on the all-triangle scene
+            packed = np.zeros(len(r), candidates_dtype(K))
+            packed["count"], packed["before"], packed["prim"], packed["instance"] = c.host()
+            ok = packed["count"] >= 0
+            if kind == "closest":
+                res = case.oracle(resolve_host_candidates, r, o.cpu().numpy().view(HIT_DTYPE).reshape(-1), packed,
+                                  case.callback(r), np.zeros(len(case.is_host), np.int32))
+                assert_resolved_equal(res[ok], oracle[b][ok], what + " against the oracle")
+            else:
+                res = case.oracle(resolve_host_candidates_any, r, o.cpu().numpy(), packed, case.callback(r))
+                assert np.array_equal(res[res != 2], oracle[b][res != 2]), what + " against the oracle"
         # a batch with capacity 0 is a plain batch: nnbvh_trace_batches_device's output, arrays untouched
         plain = [torch.zeros_like(o) for o in outs]
         agg.trace_batches_device([(kind, d.data_ptr(), len(r), o.data_ptr())
@@ -266,6 +297,7 @@ def test_batches_equal_the_single_batch_candidate_calls(name):
             assert (cs2[b].count == 77).all()
         assert outs2[1].cpu().numpy().tobytes() == refs[1][0].tobytes()
         assert_cands_equal(cs2[1].host(), refs[1][1], False, f"{name} fused={fused}: mixed call")
+        assert_reached(LEDGER, f"{BATCHES_TEST}[{name}] fused_batches {fused}", start)
     case.close()
 
 

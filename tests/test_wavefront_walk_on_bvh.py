@@ -20,6 +20,7 @@ import pytest
 
 import oracle_binding as ob
 import scenes_small as ss
+from ledger_cases import BVH, assert_reached, bvh, ledger_start
 from nn_bvh_amd import NNBVHError, _lib, build_tree, scene
 from test_wavefront_bounded import (SENTINEL, host_prim_scene, one_random_numpy, patch_scene, shadow_radiance,
                                     two_level_case)
@@ -536,6 +537,17 @@ def test_gpu_walk_calls_are_hip_graph_capturable():
 # ---- beyond flat triangles: expected values from calls that exist without the walk ----------------------------------
 # (device_shadow_walk / device_one_random_walk of the kd test: host loops over the aggregate's Intersect, the
 # interaction post-pass and ob.offset_batch; a BVHAggregate serves them as a KdTreeAggregate does)
+# case -> (kernel family, the instances its device calls launch), asserted with the launch ledger (tests/ledger_cases.py).
+# pick_walk_instance gives the walks <4,8,INST,1> / <5,8,INST,1> (form 1, or 2 in the two-level scene); the unbounded
+# and bounded calls and the host loops over Intersect that compose the expected values run the closest-hit form of
+# the same scene, <0,8,INST,1>
+LEDGER = {
+    "test_gpu_walks_beyond_flat_triangles[patch_scene]": (BVH, bvh((0, 4, 5))),
+    "test_gpu_walks_beyond_flat_triangles[host_prim_scene]": (BVH, bvh((0, 4, 5))),
+    "test_gpu_walks_beyond_flat_triangles[two_level_case]": (BVH, bvh((0, 4, 5), inst=1)),
+}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("make", [patch_scene, host_prim_scene, two_level_case])
 def test_gpu_walks_beyond_flat_triangles(make):
@@ -544,6 +556,7 @@ def test_gpu_walks_beyond_flat_triangles(make):
     from nn_bvh_amd.interaction import ShadingMesh
     from nn_bvh_amd.wavefront import RayQueue, WavefrontAggregate
     s = make()
+    start = ledger_start(LEDGER, f"test_gpu_walks_beyond_flat_triangles[{make.__name__}]")
     nodes, prims, verts = s["tree"]
     mesh = ShadingMesh(verts, **s["mesh"])
     if "instances" in s:
@@ -630,3 +643,4 @@ def test_gpu_walks_beyond_flat_triangles(make):
         assert a[fin].tobytes() == b[fin].tobytes()
     agg.close()
     mesh.close()
+    assert_reached(LEDGER, f"test_gpu_walks_beyond_flat_triangles[{make.__name__}]", start)

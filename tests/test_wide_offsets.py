@@ -19,8 +19,8 @@ narrow test asks of more rays is asked here as the same share of the rays (the h
 composes its expected values from device calls that exist without the walk (the walks on a scene with patches:
 tests/test_wavefront_walk_kd.py), those calls are made at the narrow width, outside the ledger's block.
 
-The census at the end computes, from the expected-instance tables here and in tests/test_stack_limits.py, which of the
-75 + 42 instances a ledger-asserted oracle comparison reaches, and pins the rest to an explicit list."""
+The census at the end computes, from the expected-instance tables here and the LEDGER tables of the modules that
+tests/ledger_cases.py names, which of the 75 + 42 instances a ledger-asserted oracle comparison reaches: all of them."""
 import contextlib
 import ctypes
 import functools
@@ -849,49 +849,50 @@ def test_bvh_wide_offsets(case_id, wide, narrow):
 
 
 # ---- the census ---------------------------------------------------------------------------------------------------------
-# Instances no ledger-asserted oracle comparison reaches (tests/test_stack_limits.py LEDGER and the tables above), with
-# the un-instrumented test believed to reach each (DESIGN.md §5.15 prints the same list).  It can only shrink on purpose.
-BVH_NOT_LEDGER_ASSERTED = {
-    # image-textured alpha, flat scenes (tests/test_alpha_texture.py; the twins: its candidates test)
-    (0, 8, 0, 1, 3, 0, 0), (1, 8, 0, 1, 3, 0, 0), (2, 8, 0, 1, 3, 0, 0),
-    (0, 8, 0, 1, 3, 0, 1), (2, 8, 0, 1, 3, 0, 1),
-    # alpha-tested primitives inside two-level scenes (tests/test_interaction_instances.py, tests/test_alpha.py)
-    (0, 8, 1, 1, 1, 0, 0), (1, 8, 1, 1, 1, 0, 0), (2, 8, 1, 1, 1, 0, 0),
-    (0, 8, 2, 1, 1, 0, 0), (1, 8, 2, 1, 1, 0, 0), (2, 8, 2, 1, 1, 0, 0),
-    (0, 8, 1, 1, 2, 0, 0), (1, 8, 1, 1, 2, 0, 0), (2, 8, 1, 1, 2, 0, 0),
-    (0, 8, 2, 1, 2, 0, 0), (1, 8, 2, 1, 2, 0, 0), (2, 8, 2, 1, 2, 0, 0),
-    # the candidate twins of the alpha and two-level forms (tests/test_host_candidates.py,
-    # tests/test_wavefront_candidates.py)
-    (0, 8, 0, 1, 1, 0, 1), (2, 8, 0, 1, 1, 0, 1), (0, 8, 0, 1, 2, 0, 1), (2, 8, 0, 1, 2, 0, 1),
-    (0, 8, 1, 1, 0, 0, 1), (2, 8, 1, 1, 0, 0, 1), (3, 8, 1, 1, 0, 0, 1),
-    (0, 8, 2, 1, 0, 0, 1), (2, 8, 2, 1, 0, 0, 1), (3, 8, 2, 1, 0, 0, 1),
-    (0, 8, 1, 1, 1, 0, 1), (2, 8, 1, 1, 1, 0, 1), (0, 8, 2, 1, 1, 0, 1), (2, 8, 2, 1, 1, 0, 1),
-    (0, 8, 1, 1, 2, 0, 1), (2, 8, 1, 1, 2, 0, 1), (0, 8, 2, 1, 2, 0, 1), (2, 8, 2, 1, 2, 0, 1),
-    # the walk through a static two-level scene (tests/test_wavefront_walk_on_bvh.py two_level_case)
-    (4, 8, 1, 1, 0, 0, 0), (5, 8, 1, 1, 0, 0, 0),
-}
-KD_NOT_LEDGER_ASSERTED = {
-    # narrow only: the attribute-reading batch form is asserted by test_kd_chain[attr]; every narrow twin of a wide case
-    # is asserted by that case.  Nothing is left.
-}
+# Instances no ledger-asserted oracle comparison reaches: the LEDGER tables of the modules ledger_cases.MODULES names
+# and the tables above leave none.  (Until tests/test_alpha_candidates.py the BVH list held 37)
+BVH_NOT_LEDGER_ASSERTED = set()
+KD_NOT_LEDGER_ASSERTED = set()
+
+
+def ledger_tables():
+    """{module name: its LEDGER table}, the modules listed by name in tests/ledger_cases.py"""
+    import importlib
+
+    import ledger_cases
+    return {name: importlib.import_module(name).LEDGER for name in ledger_cases.MODULES}
+
+
+def test_every_ledger_key_names_a_gpu_test_of_its_module():
+    import importlib
+    for name, table in ledger_tables().items():
+        module = importlib.import_module(name)
+        assert table, name
+        for key, (family, instances) in table.items():
+            fn = getattr(module, key.split("[")[0], None)
+            assert callable(fn) and fn.__name__.startswith("test_"), f"{name}: {key} names no test function"
+            marks = {m.name for m in getattr(fn, "pytestmark", [])}
+            assert "gpu" in marks, f"{name}: {key} is not marked gpu"
+            assert family in (BVH, KD) and instances, f"{name}: {key}"
+            assert all(len(i) == (7 if family == BVH else 5) for i in instances), f"{name}: {key}"
 
 
 def test_census_of_ledger_asserted_instances(nnbvh_lib):
-    import test_stack_limits as sl
     covered = {BVH: set(), KD: set()}
     for _, inst in KD_CASES:
         covered[KD] |= {inst, narrow_twin(inst)}
     for _, wide, narrow in BVH_CASES:
         covered[BVH] |= wide | narrow
-    for family, instances in sl.LEDGER.values():
-        covered[family] |= set(instances)
+    for table in ledger_tables().values():
+        for family, instances in table.values():
+            covered[family] |= set(instances)
     all_bvh, all_kd = set(_lib.instance_launches(BVH)), set(_lib.instance_launches(KD))
     assert covered[BVH] <= all_bvh and covered[KD] <= all_kd, "a table names an instance the library does not hold"
-    assert {k for k in all_kd if k[2] == 0} <= covered[KD], "a wide kd instance without a ledger-asserted case"
+    assert {k for k in all_kd if k[2] == 0} <= {inst for _, inst in KD_CASES}, \
+        "a wide kd instance without a ledger-asserted case of its own"
     rest_bvh, rest_kd = all_bvh - covered[BVH], all_kd - covered[KD]
     print(f"ledger-asserted: {len(covered[BVH])} of 75 BVH and {len(covered[KD])} of 42 kd instances")
     print("BVH rest:", sorted(rest_bvh))
     print("kd rest:", sorted(rest_kd))
-    assert rest_bvh == BVH_NOT_LEDGER_ASSERTED, (sorted(rest_bvh - BVH_NOT_LEDGER_ASSERTED),
-                                                 sorted(BVH_NOT_LEDGER_ASSERTED - rest_bvh))
-    assert rest_kd == set(KD_NOT_LEDGER_ASSERTED)
+    assert len(covered[BVH]) == 75 and len(covered[KD]) == 42
+    assert rest_bvh == BVH_NOT_LEDGER_ASSERTED and rest_kd == KD_NOT_LEDGER_ASSERTED
