@@ -1249,6 +1249,45 @@ int nnbvh_instance_launches(int family, int32_t *desc, uint64_t *counts, int cap
  * -DNNBVH_STATS. */
 int nnbvh_scene_sched_stats(nnbvh_scene *s, uint64_t out[20], int reset);
 
+/* == Tree quality: the two scores the fork's machine_learning/ code judges a split tree by, SAH(head_node) and
+ * EPO(head_node) (machine_learning/nn_loss.py:165-192, 119-135), of a flat tree as nnbvh_build_nodes produces it.
+ *   A(n) = 2 (xy + xz + yz) of node n's box, in double from its float32 corners
+ *   sah  = (c_inner * sum over inner nodes of A(n) + c_leaf * sum over leaves of A(n) * nprims(n)) / A(root)
+ *   ext(n) = the primitives that are not in n's subtree and have at least one vertex inside n's closed box
+ *            (all six comparisons >= / <=; a triangle counts whole, unclipped; the root has none)
+ *   epo  = (c_inner * sum over inner nodes of area(ext(n)) + c_leaf * sum over leaves of area(ext(n)))
+ *          / area(all primitives),   area = 1/2 |(p1 - p0) x (p2 - p0)| in double
+ * The fork's constants are c_inner = 1.2, c_leaf = 1.0 (nn_loss.py:113-117).  The divisions are IEEE double divisions:
+ * a zero root area or a zero total area gives the NaN or inf the formula gives.  The sums before the constants are
+ * returned too; they do not depend on the constants. */
+typedef struct nnbvh_tree_quality {
+    double sah, epo;
+    double inner_area, leaf_area_weighted, root_area; /* the SAH sums before the constants */
+    double prim_area, ext_area_inner, ext_area_leaf;  /* the EPO sums before the constants */
+    int64_t ext_pairs_inner, ext_pairs_leaf;          /* (primitive, inner node) and (primitive, leaf) external pairs */
+    int32_t n_inner, n_leaves, depth, pad;            /* depth: edges from the root to the deepest leaf */
+    float gpu_ms[4];                                  /* prepare, walk, reduce; upload + the three */
+} nnbvh_tree_quality;
+
+/* Scores a tree on `device`.  Host arrays in, host arrays out; the call runs on a stream of its own and returns when
+ * the results are there (synchronous).  prim_ext_inner / prim_ext_leaf [n_prims], nullable: per ORDERED POSITION the
+ * number of inner nodes / leaves that hold that primitive as an external.  node_external [n_nodes], nullable: the
+ * number of externals of each node.  All integers are exact; the doubles come from sums of a fixed shape, so two calls
+ * on the same input return the same bits.
+ * The tree is checked on the host first, in O(nodes + primitives), before any device is looked at; NNBVH_ERR_ARG with
+ * *out and the arrays untouched for: a null or empty array; c_inner or c_leaf not finite; a primitive that is not a
+ * triangle (kinds 0, 4 .. 7 and 16 .. 19 are; the fork defines both scores on triangles only); a vertex index outside
+ * [0, n_verts); a non-finite vertex or box corner; a second-child offset not in (i + 1, n_nodes) or not where the
+ * first child's subtree ends; a leaf range outside [0, n_prims); an ordered position covered by no leaf or by two; a
+ * node count that is not 2 * leaves - 1; a depth over 64; a child box not inside its parent's, or a primitive with a
+ * vertex outside its own leaf's box (the walk prunes by the first and both make the set definition above equal to the
+ * fork's pruned search).  A one-node tree is accepted.  NNBVH_ERR_DEVICE: no usable device, or a failed allocation,
+ * copy or launch. */
+int nnbvh_tree_quality_create(const nnbvh_linear_node *nodes, int n_nodes, const nnbvh_prim *ordered_prims, int n_prims,
+                              const float *verts, int n_verts, double c_inner, double c_leaf, int device,
+                              nnbvh_tree_quality *out, int32_t *prim_ext_inner, int32_t *prim_ext_leaf,
+                              int32_t *node_external);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,7 @@ EXPORTS = [
     "nnbvh_kd_scene_create_with_alpha_textures", "nnbvh_kd_scene_create_gpu_build_with_alpha_textures",
     "nnbvh_instance_launches",
     "nnbvh_scene_create_instanced_with_alpha_textures", "nnbvh_scene_create_instanced_gpu_build_with_alpha_textures",
+    "nnbvh_tree_quality_create",
 ]
 
 
@@ -117,6 +118,19 @@ class HostCandidates(ctypes.Structure):
 
 
 assert ctypes.sizeof(HostCandidates) == 40
+
+
+class TreeQuality(ctypes.Structure):
+    """nnbvh_tree_quality (include/nnbvh.h): the fork's SAH and EPO of a baked tree and the sums behind them."""
+    _fields_ = [("sah", ctypes.c_double), ("epo", ctypes.c_double), ("inner_area", ctypes.c_double),
+                ("leaf_area_weighted", ctypes.c_double), ("root_area", ctypes.c_double),
+                ("prim_area", ctypes.c_double), ("ext_area_inner", ctypes.c_double),
+                ("ext_area_leaf", ctypes.c_double), ("ext_pairs_inner", ctypes.c_int64),
+                ("ext_pairs_leaf", ctypes.c_int64), ("n_inner", ctypes.c_int32), ("n_leaves", ctypes.c_int32),
+                ("depth", ctypes.c_int32), ("pad", ctypes.c_int32), ("gpu_ms", ctypes.c_float * 4)]
+
+
+assert ctypes.sizeof(TreeQuality) == 112
 
 WRAP_MODES = {"repeat": 0, "clamp": 1, "black": 2}
 
@@ -419,6 +433,9 @@ def lib():
     L.nnbvh_scene_sched_stats.argtypes = [vp, vp, i32]
     L.nnbvh_instance_launches.restype = i32
     L.nnbvh_instance_launches.argtypes = [i32, vp, vp, i32, i32]
+    L.nnbvh_tree_quality_create.restype = i32
+    L.nnbvh_tree_quality_create.argtypes = [vp, i32, vp, i32, vp, i32, ctypes.c_double, ctypes.c_double, i32,
+                                            ctypes.POINTER(TreeQuality), vp, vp, vp]
     _lib = L
     return L
 

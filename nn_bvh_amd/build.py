@@ -14,8 +14,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnnbvh_hip.so")
-SOURCES = ["bvh_trace.hip", "wavefront.hip", "wavefront2.hip", "wavefront_items.hip", "bvh_build_gpu.hip", "bvh_bake.hip", "interaction.hip", "film.hip", "kd_trace.hip", "kd_build_gpu.hip", "kd_bake.hip", "bvh_capi.cpp", "capi_two_level.cpp", "capi_trace.cpp", "capi_kd.cpp", "capi_wavefront.cpp", "capi_shading.cpp", "bvh_build.cpp", "kd_build.cpp"]
-HEADERS = ["bvh_trace.h", "trace_instance.h", "top_table.h", "top_extend.h", "trace_math.h", "stream_access.h", "spawn_math.h", "anim_math.h", "alpha_texture_math.h", "wavefront2.h", "walk_math.h", "wavefront.h", "bvh_build_gpu.h", "interaction.h", "interaction_math.h", "wavefront_items.h", "kd_trace.h", "kd_instance.h", "launch_ledger.h", "kd_build_gpu.h", "kd_device_util.h", "nnbvh_internal.h", "capi_internal.h", os.path.join("..", "..", "include", "nnbvh.h")]
+SOURCES = ["bvh_trace.hip", "wavefront.hip", "wavefront2.hip", "wavefront_items.hip", "bvh_build_gpu.hip", "bvh_bake.hip", "interaction.hip", "film.hip", "kd_trace.hip", "kd_build_gpu.hip", "kd_bake.hip", "tree_quality.hip", "bvh_capi.cpp", "capi_two_level.cpp", "capi_trace.cpp", "capi_kd.cpp", "capi_wavefront.cpp", "capi_shading.cpp", "capi_quality.cpp", "bvh_build.cpp", "kd_build.cpp"]
+HEADERS = ["bvh_trace.h", "trace_instance.h", "top_table.h", "top_extend.h", "trace_math.h", "stream_access.h", "spawn_math.h", "anim_math.h", "alpha_texture_math.h", "wavefront2.h", "walk_math.h", "wavefront.h", "bvh_build_gpu.h", "interaction.h", "interaction_math.h", "wavefront_items.h", "kd_trace.h", "kd_instance.h", "launch_ledger.h", "kd_build_gpu.h", "kd_device_util.h", "tree_quality.h", "nnbvh_internal.h", "capi_internal.h", os.path.join("..", "..", "include", "nnbvh.h")]
 CFLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17",
           "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
 FLAGS = CFLAGS + ["-shared"]  # kept for the tools that print the command line

@@ -3,7 +3,8 @@ LinearBVHNode layout the traversal path consumes (BASELIN
 config 5: "NN_BVH learned-split tree ... baked to LinearBVHNode").
 
 The reference has no such baker: its Python side builds `BVHNode` objects and
-scores them; nothing reaches pbrt.  This module restates, in numpy, the three pieces that
+scores them; nothing reaches pbrt.  (The scoring is here too: SAH(head_node) / EPO(head_node) of nn_loss.py on any
+baked tree, nn_bvh_amd.quality.tree_quality)  This module restates, in numpy, the three pieces that
 define a tree there —
   * BVHNode.split                   /root/reference/machine_learning/nn_BVH.py:32-101
     (primitive -> left if max <= pos; right if min > pos; a straddler goes left iff
