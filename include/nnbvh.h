@@ -193,14 +193,16 @@ nnbvh_build *nnbvh_build_create_with_bounds(const nnbvh_prim *prims, int n_prims
  *         whole-grid kernels, every smaller subtree by one wavefront; std::partition's exact
  *         element order is reproduced from ballots / prefix sums.
  *   HLBVH (buildHLBVH, aggregates.cpp:389-503 with treelets emitted in Morton order): Morton codes,
- *         radix sort, the treelets' radix trees, bounds and the DFS layout on the device, only
- *         buildUpperSAH over the <= 4096 treelet roots (aggregates.cpp:626-723) on the host.
+ *         radix sort, the treelets' radix trees, bounds and the DFS layout on the device, and
+ *         buildUpperSAH over the <= 4096 treelet roots (aggregates.cpp:626-723) there too: ranges above
+ *         64 treelets in passes over the grid, every smaller one by one wavefront.
+ * On neither builder does tree data cross to the host before the finished tree is read back.
  * NULL + nnbvh_last_error() on failure (no device, allocation, malformed input). */
 nnbvh_build *nnbvh_build_create_gpu(const nnbvh_prim *prims, int n_prims, const float *verts,
                                     int n_verts, const float *prim_bounds, int max_prims_in_node,
                                     int split_method, int device);
 /* milliseconds of the last GPU build's phases (all zero for host builds) — HLBVH: upload, device
- * sort + tree, host upper SAH, device emit, download; SAH: upload, big nodes breadth-first,
+ * sort + tree, device upper SAH, device emit, download; SAH: upload, big nodes breadth-first,
  * wavefront subtrees, layout + bounds, download */
 int nnbvh_build_gpu_timing(const nnbvh_build *b, double out_ms[5]);
 const nnbvh_linear_node *nnbvh_build_nodes(const nnbvh_build *b, int *n_nodes);
@@ -243,12 +245,22 @@ void nnbvh_forest_destroy(nnbvh_forest *f);
  * object k alone, from a fixed number of launches and synchronisations however many objects there are.  Arguments,
  * argument faults (the same, less the split method), the handle, its accessors and its ownership are
  * nnbvh_build_forest_create_gpu's.  Of the accessors, timing = the phases of nnbvh_build_gpu_timing's HLBVH (upload;
- * device sort + treelets of every object; the host's upper SAH, object after object; device emit; download),
+ * device sort + treelets of every object; the upper SAH of every object, on the device; device emit; download),
  * n_levels = 0 (HLBVH has no breadth-first passes) and n_subtrees = treelets in the forest (primitives of one object
- * that share the top 12 bits of their Morton code; at most 4096 per object, no bound on the total). */
+ * that share the top 12 bits of their Morton code; at most 4096 per object, no bound on the total).  No treelet
+ * table, layout or upper node crosses to the host. */
 nnbvh_forest *nnbvh_build_forest_create_gpu_hlbvh(const nnbvh_prim *prims, int n_prims, const int32_t *object_first,
                                                   int n_objects, const float *verts, int n_verts,
                                                   const float *prim_bounds, int max_prims_in_node, int device);
+/* What the builders' upper levels came to.  n_upper: HLBVH, the upper nodes (buildUpperSAH's: an object's treelets
+ * less one, so the forest's treelets less its objects); SAH, the nodes built breadth-first.  n_upper_passes: launches
+ * of the HLBVH upper build's pass kernel, each of which works on every open range of every object: 0 for SAH and
+ * when no object has two treelets, 1 when no object has more than 64, more for larger objects (a range above 64
+ * treelets is split once per pass).  The nnbvh_build_ forms report the same of a single GPU build (0 for host builds). */
+int nnbvh_forest_n_upper_passes(const nnbvh_forest *f);
+int nnbvh_forest_n_upper(const nnbvh_forest *f);
+int nnbvh_build_n_upper(const nnbvh_build *b);
+int nnbvh_build_n_upper_passes(const nnbvh_build *b);
 
 /* ---- device scene ------------------------------------------------------------------ */
 /* Uploads and bakes a flattened tree (the reference's LinearBVHNode[] in its DFS layout, first child
@@ -322,7 +334,8 @@ nnbvh_scene *nnbvh_scene_create_gpu_build_with_attributes(const nnbvh_prim *prim
                                                           int max_prims_in_node, int split_method, int device);
 /* A two-level scene (object instances, scene.cpp:1521-1577: one BVHAggregate per object definition, one
  * TransformedPrimitive / AnimatedPrimitive per placement) entirely on the device: every object's tree, then the
- * top-level tree, are built there, put into one numbering and baked; no tree visits the host.  The device arrays are
+ * top-level tree, are built there, put into one numbering and baked; no tree visits the host, and with either split
+ * method no part of one does (HLBVH's upper levels over the treelets are built on the device too).  The device arrays are
  * byte for byte those of nnbvh_scene_create_instanced_with_attributes on host-built trees of the same split_method
  * (nodes [top, object 0, object 1, ...], primitives [top in leaf order, object 0 in leaf order, ...]).  All object
  * trees come from one forest pass (the builder of nnbvh_build_forest_create_gpu for NNBVH_SPLIT_SAH, of

@@ -108,6 +108,7 @@ EXPORTS = [
     "nnbvh_instance_launches",
     "nnbvh_scene_create_instanced_with_alpha_textures", "nnbvh_scene_create_instanced_gpu_build_with_alpha_textures",
     "nnbvh_tree_quality_create",
+    "nnbvh_forest_n_upper", "nnbvh_forest_n_upper_passes", "nnbvh_build_n_upper", "nnbvh_build_n_upper_passes",
 ]
 
 
@@ -200,6 +201,9 @@ def lib():
     L.nnbvh_build_ordered_prims.argtypes = [vp, ctypes.POINTER(i32)]
     L.nnbvh_build_depth.restype = i32
     L.nnbvh_build_depth.argtypes = [vp]
+    for fn in (L.nnbvh_build_n_upper, L.nnbvh_build_n_upper_passes, L.nnbvh_forest_n_upper, L.nnbvh_forest_n_upper_passes):
+        fn.restype = i32
+        fn.argtypes = [vp]
     L.nnbvh_build_destroy.restype = None
     L.nnbvh_build_destroy.argtypes = [vp]
     L.nnbvh_scene_create.restype = vp

@@ -65,6 +65,8 @@ def _take_build(L, h, what):
         ms = np.zeros(5, np.float64)
         L.nnbvh_build_gpu_timing(h, ptr(ms))
         tree.gpu_ms = [float(x) for x in ms]  # phases: see nnbvh_build_gpu_timing
+        tree.n_upper = L.nnbvh_build_n_upper(h)  # see nnbvh_forest_n_upper; both 0 for host builds
+        tree.n_upper_passes = L.nnbvh_build_n_upper_passes(h)
     finally:
         L.nnbvh_build_destroy(h)
     return tree
@@ -109,8 +111,10 @@ def build_tree_gpu(prims, verts, max_prims_in_node=4, prim_bounds=None, device=0
 class BuiltForest(list):
     """build_forest_gpu's / build_hlbvh_forest_gpu's result: a list of BuiltTree, one per object, with the pass's own
     figures as attributes: gpu_ms (the five phases of nnbvh_forest_gpu_timing), n_levels (SAH: breadth-first passes
-    run; HLBVH: 0), n_subtrees (SAH: subtrees built by one wavefront each; HLBVH: treelets in the forest) and
-    node_first (where each tree starts in the forest's node array)."""
+    run; HLBVH: 0), n_subtrees (SAH: subtrees built by one wavefront each; HLBVH: treelets in the forest), n_upper
+    (SAH: nodes built breadth-first; HLBVH: upper nodes, treelets less objects), n_upper_passes (HLBVH: device passes of
+    the upper SAH build, 0 when no object has two treelets; SAH: 0) and node_first (where each tree starts in the
+    forest's node array)."""
 
 
 def _forest(name, objects, verts, max_prims_in_node, prim_bounds, tail):
@@ -145,6 +149,8 @@ def _forest(name, objects, verts, max_prims_in_node, prim_bounds, tail):
         forest.gpu_ms = [float(x) for x in ms]
         forest.n_levels = L.nnbvh_forest_n_levels(h)
         forest.n_subtrees = L.nnbvh_forest_n_subtrees(h)
+        forest.n_upper = L.nnbvh_forest_n_upper(h)
+        forest.n_upper_passes = L.nnbvh_forest_n_upper_passes(h)
         forest.node_first = node_first
     finally:
         L.nnbvh_forest_destroy(h)

@@ -495,6 +495,19 @@ bool hlbvh_upper_layout(const float *treelet_bounds, const int *treelet_sizes, i
     return true;
 }
 
+bool hlbvh_upper_refusal(const float *treelet_bounds, const int *treelet_sizes, int n_treelets, std::string *text) {
+    for (int i = 0; i < n_treelets; ++i) {
+        bool fine = treelet_sizes[i] >= 1 && (treelet_sizes[i] & 1);
+        for (int c = 0; c < 6; ++c) fine = fine && std::isfinite(treelet_bounds[6 * (size_t)i + c]);
+        if (!fine) {
+            *text = "nnbvh_build_create: non-finite primitive bounds (or internal error) in treelet " + std::to_string(i);
+            return true;
+        }
+    }
+    UpperLayout up;
+    return !hlbvh_upper_layout(treelet_bounds, treelet_sizes, n_treelets, &up, text);
+}
+
 }  // namespace nnbvh
 
 struct nnbvh_build {
@@ -503,6 +516,7 @@ struct nnbvh_build {
     int depth = 0;
     double gpu_ms[5] = {0, 0, 0, 0, 0};
     int n_treelets = 0, n_unique_codes = 0;
+    int n_upper = 0, n_upper_passes = 0;
 };
 
 extern "C" {
@@ -634,11 +648,13 @@ nnbvh_build *nnbvh_build_create_gpu(const nnbvh_prim *prims, int n_prims, const 
     std::memcpy(out->gpu_ms, r.ms, sizeof r.ms);
     out->n_treelets = r.n_treelets;
     out->n_unique_codes = r.n_unique_codes;
+    out->n_upper = r.n_upper;
+    out->n_upper_passes = r.n_upper_passes;
     if (std::getenv("NNBVH_BUILD_TIMING"))
         std::fprintf(stderr, split_method == NNBVH_SPLIT_SAH
                                  ? "nnbvh_build (gpu sah): upload %.1f ms, big nodes %.1f ms, subtrees %.1f ms, layout+bounds "
                                    "%.1f ms, download %.1f ms; %d breadth-first nodes, %d subtrees\n"
-                                 : "nnbvh_build (gpu hlbvh): upload %.1f ms, device sort+tree %.1f ms, upper SAH (host) "
+                                 : "nnbvh_build (gpu hlbvh): upload %.1f ms, device sort+tree %.1f ms, upper SAH (device) "
                                    "%.1f ms, emit %.1f ms, download %.1f ms; %d distinct codes, %d treelets\n",
                      r.ms[0], r.ms[1], r.ms[2], r.ms[3], r.ms[4], r.n_unique_codes, r.n_treelets);
     return out;
@@ -663,6 +679,8 @@ const nnbvh_prim *nnbvh_build_ordered_prims(const nnbvh_build *b, int *n_prims) 
 }
 
 int nnbvh_build_depth(const nnbvh_build *b) { return b ? b->depth : -1; }
+int nnbvh_build_n_upper(const nnbvh_build *b) { return b ? b->n_upper : -1; }
+int nnbvh_build_n_upper_passes(const nnbvh_build *b) { return b ? b->n_upper_passes : -1; }
 
 void nnbvh_build_destroy(nnbvh_build *b) { delete b; }
 

@@ -23,15 +23,20 @@ struct UpperLayout {
 };
 bool hlbvh_upper_layout(const float *treelet_bounds, const int *treelet_sizes, int n_treelets,
                         UpperLayout *out, std::string *error);
+// The words for a treelet table the device's upper build refused (bvh_build_gpu.hip, step 8b): the host's checks of the
+// table in the host's order, then hlbvh_upper_layout, whose first failure in its left-first recursion is the message.
+// false: the host builder refuses nothing here.
+bool hlbvh_upper_refusal(const float *treelet_bounds, const int *treelet_sizes, int n_treelets, std::string *text);
 
 struct GpuBuildResult {
     std::vector<nnbvh_linear_node> nodes;
     std::vector<nnbvh_prim> ordered;
     int depth = 0;
-    // milliseconds: host->device copies, device pipeline up to the treelet table, host upper tree,
+    // milliseconds: host->device copies, device pipeline up to the treelet table, device upper trees,
     // device emit, device->host copies
     double ms[5] = {0, 0, 0, 0, 0};
     int n_treelets = 0, n_unique_codes = 0;
+    int n_upper = 0, n_upper_passes = 0;  // as ForestBuildResult's
     // keep_on_device (in): do not download; hand the device arrays to the caller instead (who frees
     // them with hipFree): LinearBVHNode[total_nodes], leaf-ordered nnbvh_prim[n_prims], float3 verts
     bool keep_on_device = false;
@@ -106,16 +111,18 @@ struct ForestBuildResult {
     double ms[5] = {0, 0, 0, 0, 0};  // as gpu_sah's ([0] and [4] are the wrappers')
     int n_levels = 0;                // breadth-first passes run (each works on every object's big nodes of one level)
     int n_subtrees = 0, n_upper = 0;  // subtrees built by wavefronts, nodes built breadth-first
+    int n_upper_passes = 0;           // HLBVH only: launches of the upper build's pass kernel (0: no object has two treelets)
     int n_codes = 0;                  // HLBVH only: distinct (object, Morton code) keys in the forest
 };
 bool gpu_sah_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,
                            std::string *error);
 // The same for HLBVH trees (gpu_hlbvh_device is its one-object case): tree k is byte for byte that of object k alone,
 // from a fixed number of launches and synchronisations whatever n_objects is (one radix sort over the key
-// (object << 30) | Morton code, 64 bits wide, or the 32-bit code alone when n_objects is 1; the upper SAH on the host,
-// per object, over one table of every object's treelets).  Of the result, ms has the meaning of gpu_hlbvh's ([1] device
-// pipeline up to the treelet table, [2] host upper trees, [3] device emit), n_levels = 0, n_subtrees = treelets in the
-// forest, n_upper = upper nodes, n_codes = distinct keys.  A malformed input fails with the message a loop of
+// (object << 30) | Morton code, 64 bits wide, or the 32-bit code alone when n_objects is 1) plus the passes of the upper
+// SAH, which runs on the device over one table of every object's treelets: one pass when no object has more than 64
+// treelets, a few more for larger ones.  No tree data visits the host.  Of the result, ms has the meaning of
+// gpu_hlbvh's ([1] device pipeline up to the treelet table, [2] device upper trees, [3] device emit), n_levels = 0,
+// n_subtrees = treelets in the forest, n_upper = upper nodes, n_upper_passes = those passes, n_codes = distinct keys.  A malformed input fails with the message a loop of
 // gpu_hlbvh_device calls over the objects would have stopped at; an object with several kinds of fault reports the
 // first of: vertex index, missing bounds, non-finite, unknown kind, leaf size, treelet checks.
 bool gpu_hlbvh_forest_device(const DeviceBuildInput &in, const int *object_first, int n_objects, ForestBuildResult *out,

@@ -19,7 +19,8 @@
 //   6  which radix nodes survive as real nodes      k_classify + 2 scans (leaf / treelet ordinals)
 //   7  bounds bottom-up: leaves, then interior nodes by split bit 0..17 (children always split at
 //      a lower bit, so 18 dependency-free launches; no atomics, no intra-kernel fences)
-//   8  treelet roots (k_treelets) -> host: buildUpperSAH over an object's <= 4096 boxes (aggregates.cpp:626-723, host)
+//   8  treelet roots (k_treelets), then buildUpperSAH over an object's <= 4096 boxes (aggregates.cpp:626-723):
+//      k_upper_treelets, k_upper_seed, k_upper_pass per pass; the upper nodes join the array with k_upper_nodes
 //   9  every node computes its own DFS position   k_emit: preorder = 2 x (leaves to its left in
 //      the treelet) + (ancestors it hangs off on the left side), found by walking <= 18 parents
 //  10  leaf-ordered primitive table = the sorted order  k_gather_prims
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(kB) void k_interior_bounds(int m, int level,
     nodeBox[i] = b;
 }
 
-// ---- 8: treelet table for the host's upper SAH build -------------------------------------------------
+// ---- 8: treelet table for the upper SAH build (8b below) -------------------------------------------------
 __device__ __forceinline__ int subtree_size(int v, int m, const unsigned char *kind, const int *firstA,
                                             const int *lastA, const int *leafOrd) {
     if (!(kind[v] & kRealInterior)) return 1;
@@ -542,11 +543,334 @@ __global__ __launch_bounds__(kB) void k_iota(int n, int *__restrict__ perm) {
     for (int i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) perm[i] = i;
 }
 
-__global__ __launch_bounds__(kB) void k_scatter_nodes(const int *__restrict__ index,
-                                                      const nnbvh_linear_node *__restrict__ src, int n,
-                                                      nnbvh_linear_node *__restrict__ nodes) {
-    const int i = blockIdx.x * kB + threadIdx.x;
-    if (i < n) nodes[index[i]] = src[i];
+// ---- 8b: buildUpperSAH (aggregates.cpp:626-723) over every object's treelets, on the device ---------------------------
+// The host's upper() (bvh_build.cpp) top-down, without knowing the tree below a node: a range of n treelets yields
+// n - 1 upper nodes, so the subtree of the range [s, e) of the permuted treelet order holds sum(tsize) + (e - s - 1)
+// nodes, a first child stands at its parent's index + 1 and a second child behind the first child's subtree.
+//   k_upper_treelets  per treelet: its object's first treelet and node total, the host's checks of the table
+//   (scan)            node_first = exclusive sum of the objects' node totals
+//   k_upper_seed      per object: one treelet = its root; more = one range for the first pass
+//   k_upper_pass      one wavefront per range.  A range of at most 64 treelets: its whole subtree (pending second
+//                     children on a stack in LDS, at most 63).  A larger one: one split, the children go to the
+//                     next pass's queue.  Every pass works on all such ranges of all objects.
+//   k_upper_nodes     (after the node array exists) one wavefront per upper node: its box, and the node
+// Decisions (split dimension, the 11 costs, the first minimum, bucket <= best) depend on VALUES only: min / max of the
+// range's boxes and centroids, integer counts, and the host's float expressions operation for operation
+// (-ffp-contract=off); the sign of a zero changes no comparison, and a zero surface area of the range's bounds makes
+// every cost NaN whatever its sign.  Two things depend on ORDER.  The treelets' order, which std::partition leaves
+// behind: libstdc++'s closed form, as in the SAH builder below (left-part offenders from the left trade places with
+// right-part offenders from the right).  And a stored box's zero signs: the host folds child 0 then child 1 with
+// Box::add (first of equals kept), which is the in-order fold over the node's range in the FINAL treelet order;
+// k_upper_nodes does that fold after the last pass.
+// Every loop is bounded: a split with an empty side, or coinciding centroids, flags the object (errUpper, lowest object
+// wins) and queues nothing, so each range a pass takes up is strictly smaller than the one it came from.
+constexpr int kUpperBuckets = 12;
+constexpr int kUpperWave = 64;        // a range of at most this many treelets is finished by one wavefront
+constexpr int kUpperMaxTreelets = 4096;  // an object's treelets: 12 Morton bits
+constexpr int kUpperMaxPasses = kUpperMaxTreelets;  // every pass shrinks every range by at least one treelet
+
+struct UpperRange {
+    int s, e;    // positions in the permuted treelet order
+    int rel;     // the subtree's root, counted from its tree's root
+    int depth;
+};
+struct UpperSplit {  // of the upper node that splits [s, e) at position mid: stored at [mid], e == 0 = none
+    int s, e, rel, second, axis;
+};
+enum : int { kUpErrCount = 0, kUpErrTable = 1, kUpErrInternal = 2, kUpQueue = 4 };  // words of the upper build's scalars
+
+__device__ __forceinline__ float box_area(const Box6 &b) {  // util/vecmath.h:1293-1296
+    const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
+    return 2 * (dx * dy + dx * dz + dy * dz);
+}
+__device__ __forceinline__ int box_maxdim(const Box6 &b) {  // util/vecmath.h:1305-1313
+    const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
+    if (dx > dy && dx > dz) return 0;
+    else if (dy > dz) return 1;
+    else return 2;
+}
+// bucket_of in upper(): the centroid is (mn + mx) * 0.5f here, not BVHPrimitive::Centroid()
+__device__ __forceinline__ int upper_bucket(const Box6 &b, int dim, float cmn, float cmx) {
+    const float centroid = (b.mn[dim] + b.mx[dim]) * 0.5f;
+    int k = kUpperBuckets * ((centroid - cmn) / (cmx - cmn));
+    if (k == kUpperBuckets) k = kUpperBuckets - 1;
+    // beyond only where the centroids overflow (the host indexes out of range there): no index leaves the table
+    return k < 0 ? 0 : (k > kUpperBuckets - 1 ? kUpperBuckets - 1 : k);
+}
+
+__global__ __launch_bounds__(kB) void k_upper_treelets(int nTreelets, int nObjects, const Box6 *__restrict__ tbox,
+                                                       const int *__restrict__ tsize, const int *__restrict__ tobj,
+                                                       int *__restrict__ perm, int *__restrict__ objTreelet,
+                                                       unsigned *objNodes, int *scal) {
+    const int t = blockIdx.x * kB + threadIdx.x;
+    if (t >= nTreelets) return;
+    perm[t] = t;
+    const int obj = tobj[t];
+    if (obj < 0 || obj >= nObjects) {  // cannot happen
+        scal[kUpErrInternal] = 1;
+        return;
+    }
+    if (t == 0 || tobj[t - 1] != obj) objTreelet[obj] = t;
+    if (t == nTreelets - 1) objTreelet[nObjects] = nTreelets;
+    const Box6 b = tbox[t];
+    const int size = tsize[t];
+    bool fine = size >= 1 && (size & 1);
+    for (int k = 0; k < 3; ++k) fine = fine && __builtin_isfinite(b.mn[k]) && __builtin_isfinite(b.mx[k]);
+    if (!fine) atomicMin(&scal[kUpErrTable], obj);
+    atomicAdd(&objNodes[obj], (unsigned)size + 1u);  // from -1: sum(tsize) + treelets - 1, the tree's node count
+}
+
+__global__ __launch_bounds__(kB) void k_upper_seed(int nObjects, const int *__restrict__ objTreelet,
+                                                   const unsigned *__restrict__ nodeFirst, int *__restrict__ tbase,
+                                                   int *__restrict__ tdepth, UpperRange *__restrict__ queue, int *scal) {
+    const int k = blockIdx.x * kB + threadIdx.x;
+    if (k >= nObjects) return;
+    const int first = objTreelet[k], count = objTreelet[k + 1] - first;
+    if (first < 0 || count < 1 || count > kUpperMaxTreelets) {
+        atomicMin(&scal[kUpErrCount], k);
+        return;
+    }
+    if (count == 1) {  // the treelet's root is the tree's
+        tbase[first] = (int)nodeFirst[k];
+        tdepth[first] = 0;
+        return;
+    }
+    queue[atomicAdd(&scal[kUpQueue], 1)] = UpperRange{first, first + count, 0, 0};  // at most one per object
+}
+
+__global__ __launch_bounds__(kUpperWave) void k_upper_pass(const UpperRange *__restrict__ queueIn, const int *nIn,
+                                                           UpperRange *__restrict__ queueOut, int *nOut, int queueCap,
+                                                           const Box6 *__restrict__ tbox, const int *__restrict__ tsize,
+                                                           const int *__restrict__ tobj, const unsigned *__restrict__ nodeFirst,
+                                                           int *perm, int *lfPos, int *rtPos, int *__restrict__ tbase,
+                                                           int *__restrict__ tdepth, UpperSplit *__restrict__ splits,
+                                                           int *scal) {
+    __shared__ int bcount[kUpperBuckets], bnodes[kUpperBuckets];
+    __shared__ unsigned bkeys[kUpperBuckets * 6];
+    __shared__ UpperRange stack[kUpperWave];
+    if ((int)blockIdx.x >= *nIn) return;
+    const int lane = threadIdx.x;
+    UpperRange r = queueIn[blockIdx.x];
+    const int obj = tobj[perm[r.s]];
+    const int treeRoot = (int)nodeFirst[obj];
+    const bool whole = r.e - r.s <= kUpperWave;
+    int sp = 0;
+    // (whole: every trip makes one of the range's at most 63 upper nodes; else one trip)
+    for (int trip = 0; trip < kUpperWave; ++trip) {
+        const int n = r.e - r.s;
+        // bounds and centroid bounds of the range (values)
+        float v[12];
+        for (int k = 0; k < 3; ++k) {
+            v[k] = v[6 + k] = 3.402823466e+38f;
+            v[3 + k] = v[9 + k] = -3.402823466e+38f;
+        }
+        for (int j = lane; j < n; j += 64) {
+            const Box6 b = tbox[perm[r.s + j]];
+            for (int k = 0; k < 3; ++k) {
+                v[k] = fminf(v[k], b.mn[k]);
+                v[3 + k] = fmaxf(v[3 + k], b.mx[k]);
+                const float c = (b.mn[k] + b.mx[k]) * 0.5f;
+                v[6 + k] = fminf(v[6 + k], c);
+                v[9 + k] = fmaxf(v[9 + k], c);
+            }
+        }
+        for (int q = 0; q < 12; ++q) {
+            const bool isMin = (q % 6) < 3;
+            for (int off = 32; off >= 1; off >>= 1) {
+                const float o = __shfl_xor(v[q], off);
+                v[q] = isMin ? fminf(v[q], o) : fmaxf(v[q], o);
+            }
+            v[q] = __shfl(v[q], 0);  // one value for the whole wavefront (a zero's sign may differ per lane)
+        }
+        Box6 bounds, cb;
+        for (int k = 0; k < 3; ++k) {
+            bounds.mn[k] = v[k], bounds.mx[k] = v[3 + k];
+            cb.mn[k] = v[6 + k], cb.mx[k] = v[9 + k];
+        }
+        const int dim = box_maxdim(cb);
+        const float cmn = cb.mn[dim], cmx = cb.mx[dim];
+        bool failed = cmx == cmn;  // "treelet centroids coincide"
+        int mid = 0, leftNodes = 0;
+        if (!failed) {
+            if (lane < kUpperBuckets) bcount[lane] = bnodes[lane] = 0;
+            // an empty bucket is the host's Box(): max float, lowest float
+            for (int q = lane; q < kUpperBuckets * 6; q += 64) bkeys[q] = f2key((q % 6) < 3 ? 3.402823466e+38f : -3.402823466e+38f);
+            __syncthreads();
+            for (int j = lane; j < n; j += 64) {
+                const int t = perm[r.s + j];
+                const Box6 b = tbox[t];
+                const int bk = upper_bucket(b, dim, cmn, cmx);
+                atomicAdd(&bcount[bk], 1);
+                atomicAdd(&bnodes[bk], tsize[t]);
+                for (int k = 0; k < 3; ++k) {
+                    atomicMin(&bkeys[bk * 6 + k], f2key(b.mn[k]));
+                    atomicMax(&bkeys[bk * 6 + 3 + k], f2key(b.mx[k]));
+                }
+            }
+            __syncthreads();
+            // lane i: cost[i], folded from the buckets as the host folds it
+            float cost = 0;
+            if (lane < kUpperBuckets - 1) {
+                Box6 b0, b1;
+                box_init(b0);
+                box_init(b1);
+                int c0 = 0, c1 = 0;
+#pragma unroll 1
+                for (int j = 0; j < kUpperBuckets; ++j) {
+                    Box6 bj;
+                    for (int k = 0; k < 3; ++k) {
+                        bj.mn[k] = key2f(bkeys[j * 6 + k]);
+                        bj.mx[k] = key2f(bkeys[j * 6 + 3 + k]);
+                    }
+                    if (j <= lane) {
+                        box_add(b0, bj);
+                        c0 += bcount[j];
+                    } else {
+                        box_add(b1, bj);
+                        c1 += bcount[j];
+                    }
+                }
+                cost = .125f + (c0 * box_area(b0) + c1 * box_area(b1)) / box_area(bounds);
+            }
+            float minCost = __shfl(cost, 0);
+            int best = 0;
+            for (int i = 1; i < kUpperBuckets - 1; ++i) {
+                const float ci = __shfl(cost, i);
+                if (ci < minCost) {  // the first minimum; a NaN cost[0] keeps best = 0
+                    minCost = ci;
+                    best = i;
+                }
+            }
+            for (int j = 0; j <= best; ++j) {
+                mid += bcount[j];
+                leftNodes += bnodes[j];
+            }
+            __syncthreads();  // everyone has read the buckets before the next range clears them
+            if (mid <= 0 || mid >= n) {
+                failed = true;  // "degenerate upper-level SAH split"
+            } else {
+                // std::partition(bucket <= best) by ranks: offenders of the left part from the left ...
+                int nl = 0;
+                for (int base = 0; base < mid; base += 64) {
+                    const int j = base + lane;
+                    bool f = false;
+                    if (j < mid) f = upper_bucket(tbox[perm[r.s + j]], dim, cmn, cmx) > best;
+                    const unsigned long long mask = __ballot(f);
+                    if (f) lfPos[r.s + nl + __popcll(mask & ((1ull << lane) - 1ull))] = r.s + j;
+                    nl += __popcll(mask);
+                }
+                // ... trade places with the offenders of the right part from the right
+                int nr = 0;
+                for (int top = n; top > mid; top -= 64) {
+                    const int j = top - 1 - lane;
+                    bool f = false;
+                    if (j >= mid) f = upper_bucket(tbox[perm[r.s + j]], dim, cmn, cmx) <= best;
+                    const unsigned long long mask = __ballot(f);
+                    if (f) rtPos[r.s + nr + __popcll(mask & ((1ull << lane) - 1ull))] = r.s + j;
+                    nr += __popcll(mask);
+                }
+                if (nl != nr) {  // cannot happen: both equal the number of swaps
+                    if (lane == 0) scal[kUpErrInternal] = 2;
+                    nl = nl < nr ? nl : nr;
+                }
+                __syncthreads();
+                for (int k = lane; k < nl; k += 64) {
+                    const int a = lfPos[r.s + k], b = rtPos[r.s + k];
+                    const int va = perm[a], vb = perm[b];
+                    perm[a] = vb;
+                    perm[b] = va;
+                }
+                __syncthreads();
+            }
+        }
+        if (failed) {
+            if (lane == 0) atomicMin(&scal[kUpErrTable], obj);
+        } else {
+            // the left subtree: mid treelets' nodes and mid - 1 upper nodes
+            const UpperRange left{r.s, r.s + mid, r.rel + 1, r.depth + 1};
+            const UpperRange right{r.s + mid, r.e, r.rel + 1 + leftNodes + (mid - 1), r.depth + 1};
+            if (lane == 0) {
+                splits[r.s + mid] = UpperSplit{r.s, r.e, r.rel, right.rel, dim};
+                if (mid == 1) {
+                    const int t = perm[left.s];
+                    tbase[t] = treeRoot + left.rel;
+                    tdepth[t] = left.depth;
+                }
+                if (n - mid == 1) {
+                    const int t = perm[right.s];
+                    tbase[t] = treeRoot + right.rel;
+                    tdepth[t] = right.depth;
+                }
+            }
+            if (whole) {
+                // left first, as the host recurses; the pending second children of one root-to-leaf path: at most 63
+                if (n - mid > 1) {
+                    if (sp < kUpperWave) {
+                        if (lane == 0) stack[sp] = right;
+                        ++sp;
+                    } else if (lane == 0) {
+                        scal[kUpErrInternal] = 4;  // cannot happen
+                    }
+                }
+                if (mid > 1) {
+                    r = left;
+                    continue;
+                }
+            } else if (lane == 0) {
+                for (int c = 0; c < 2; ++c) {
+                    const UpperRange child = c ? right : left;
+                    if (child.e - child.s < 2) continue;
+                    const int at = atomicAdd(nOut, 1);
+                    if (at < queueCap) queueOut[at] = child;
+                    else scal[kUpErrInternal] = 3;  // cannot happen: the ranges are disjoint, two treelets or more each
+                }
+            }
+        }
+        if (!whole || sp == 0) break;
+        __syncthreads();  // lane 0's pushes
+        r = stack[--sp];
+        __syncthreads();  // every lane has read the entry before lane 0 writes it again
+    }
+}
+
+// The upper nodes themselves: one wavefront per position of the treelet order, for the node that was split there.
+// The box is the in-order fold over the node's range in the final order (see above): lanes fold contiguous chunks, the
+// cross-lane steps keep (lower lane = earlier treelets) on the left, as k_big_leaf_bounds does.
+__global__ __launch_bounds__(kB) void k_upper_nodes(int nTreelets, const UpperSplit *__restrict__ splits,
+                                                    const int *__restrict__ perm, const Box6 *__restrict__ tbox,
+                                                    const int *__restrict__ tobj, const int *__restrict__ nodeFirst,
+                                                    nnbvh_linear_node *__restrict__ nodes) {
+    const int p = blockIdx.x * (kB / 64) + (threadIdx.x >> 6);  // wave-uniform
+    if (p >= nTreelets) return;
+    const UpperSplit sp = splits[p];
+    if (sp.e == 0) return;  // the first treelet of an object: nothing was split here
+    const int lane = threadIdx.x & 63;
+    const int n = sp.e - sp.s;
+    const int chunk = (n + 63) / 64;
+    const int lo = lane * chunk, hi = (lo + chunk < n) ? lo + chunk : n;
+    Box6 b;
+    box_init(b);
+    for (int j = lo; j < hi; ++j) box_add(b, tbox[perm[sp.s + j]]);
+    for (int off = 1; off < 64; off <<= 1) {
+        Box6 o;
+        for (int k = 0; k < 3; ++k) {
+            o.mn[k] = __shfl_down(b.mn[k], off);
+            o.mx[k] = __shfl_down(b.mx[k], off);
+        }
+        if (lane + off < 64) box_add(b, o);  // b = earlier treelets (kept on ties), o = later ones
+    }
+    if (lane == 0) {
+        nnbvh_linear_node out;
+        for (int k = 0; k < 3; ++k) {
+            out.pmin[k] = b.mn[k];
+            out.pmax[k] = b.mx[k];
+        }
+        out.offset = sp.second;  // counted from the tree's root, like every second child
+        out.nprims = 0;
+        out.axis = (uint8_t)sp.axis;
+        out.pad = 0;
+        nodes[nodeFirst[tobj[perm[sp.s]]] + sp.rel] = out;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -715,6 +1039,8 @@ bool build_one_object(ForestCore forest, int ForestBuildResult::*codes, const De
     for (int k = 1; k <= 3; ++k) out->ms[k] = f.ms[k];
     out->n_treelets = f.n_subtrees;
     out->n_unique_codes = f.*codes;
+    out->n_upper = f.n_upper;
+    out->n_upper_passes = f.n_upper_passes;
     return true;
 }
 
@@ -749,7 +1075,7 @@ bool check_object_first(const int *objectFirst, int nObjects, int nAll, std::str
 // across an object boundary; a run of identical keys, a treelet (equal bits >= 18) and a radix-tree range all end
 // where the object does, because the object number is part of the key; the objects themselves hang off radix nodes that
 // split on bits >= 30, which are no more part of a tree than the nodes that split on bits 18 .. 29.  So every step is
-// one launch for the whole forest, and the upper SAH runs on the host per object over one table of treelets.
+// one launch for the whole forest, and the upper SAH runs in passes over one table of every object's treelets (8b).
 // A malformed object's primitives run through the pipeline like any others (no kernel indexes with a coordinate); only
 // its messages count, and only if no lower-numbered object has one.
 // Key = unsigned serves one object alone: its keys are its codes, sorted over bits 0 .. 29 at half the 64-bit key's
@@ -873,83 +1199,112 @@ bool hlbvh_forest(const DeviceBuildInput &in, const int *objectFirst, int nObjec
         *error = "gpu build: internal error (treelet count)";
         return false;
     }
-    // one read-back: every object's treelet boxes and sizes
-    std::vector<float> tbox(6 * (size_t)nTreelets);
-    std::vector<int> tsize(nTreelets), tobj(nTreelets);
-    GB_CHECK(hipMemcpyAsync(tbox.data(), dTbox, tbox.size() * sizeof(float), hipMemcpyDeviceToHost, stream), "read treelet bounds");
-    GB_CHECK(hipMemcpyAsync(tsize.data(), dTsize, tsize.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet sizes");
-    if (many)  // (one object: every treelet is object 0's)
-        GB_CHECK(hipMemcpyAsync(tobj.data(), dTobj, tobj.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet objects");
-    GB_CHECK(hipStreamSynchronize(stream), "sync after treelets");
     out->ms[1] = ms_since(t0);
 
-    // ---- the upper SAH, per object over its own treelets in Morton order; the trees one after another ----------------
+    // ---- the upper SAH of every object over its own treelets, on the device (8b): the treelet table stays there -------
     t0 = std::chrono::steady_clock::now();
-    // table = [treelet bases | treelet depths | node_first | flat indices of the upper nodes]: one upload
-    std::vector<int> table(2 * (size_t)nTreelets + (size_t)nObjects + 1, 0);
-    int *tbase = table.data(), *tdepth = tbase + nTreelets;
-    std::vector<int> upperIndex;
-    std::vector<nnbvh_linear_node> upperNodes;
-    out->node_first.assign((size_t)nObjects + 1, 0);
-    for (int k = 0, t = 0; k < nObjects && k < refuse.object; ++k) {
-        const int tFirst = t;
-        while (t < nTreelets && tobj[(size_t)t] == k) ++t;
-        const int count = t - tFirst;
-        if (count < 1 || count > 4096) {
+    const int nUpper = nTreelets - nObjects;  // a tree of c treelets has c - 1 upper nodes
+    const int queueCap = nTreelets / 2 + 1;   // the ranges of a pass are disjoint and hold two treelets or more
+    constexpr int kUpScalars = kUpQueue + kUpperMaxPasses + 2;
+    int *dPerm = mem.get<int>(nTreelets), *dLfPos = mem.get<int>(nTreelets), *dRtPos = mem.get<int>(nTreelets);
+    int *dTbase = mem.get<int>(nTreelets), *dTdepth = mem.get<int>(nTreelets);
+    int *dObjTreelet = mem.get<int>((size_t)nObjects + 1);
+    unsigned *dObjNodes = mem.get<unsigned>((size_t)nObjects + 1), *dNodeFirst = mem.get<unsigned>((size_t)nObjects + 1);
+    UpperSplit *dSplits = mem.get<UpperSplit>(nTreelets);
+    UpperRange *dQueue[2] = {mem.get<UpperRange>(queueCap), mem.get<UpperRange>(queueCap)};
+    int *dUp = mem.get<int>(kUpScalars);
+    if (!mem.ok) return false;
+    static const int kNobody[2] = {kNoObject, kNoObject};
+    GB_CHECK(hipMemsetAsync(dObjTreelet, 0xff, ((size_t)nObjects + 1) * sizeof(int), stream), "memset");  // -1: no treelet
+    GB_CHECK(hipMemsetAsync(dObjNodes, 0xff, ((size_t)nObjects + 1) * sizeof(unsigned), stream), "memset");  // -1: see k_upper_treelets
+    GB_CHECK(hipMemsetAsync(dSplits, 0, (size_t)nTreelets * sizeof(UpperSplit), stream), "memset");
+    GB_CHECK(hipMemsetAsync(dUp, 0, kUpScalars * sizeof(int), stream), "memset");
+    GB_CHECK(hipMemcpyAsync(dUp, kNobody, sizeof kNobody, hipMemcpyHostToDevice, stream), "init error words");
+    hipLaunchKernelGGL(k_upper_treelets, dim3(grid_all(nTreelets)), dim3(kB), 0, stream, nTreelets, nObjects, dTbox, dTsize,
+                       dTobj, dPerm, dObjTreelet, dObjNodes, dUp);
+    // (2 n_prims bounds the forest's nodes: an unsigned sum does not wrap)
+    GB_CHECK(rocprim::exclusive_scan(dTmp, scanBytes, dObjNodes, dNodeFirst, 0u, (size_t)nObjects + 1, rocprim::plus<unsigned>(), stream),
+             "scan node counts");
+    hipLaunchKernelGGL(k_upper_seed, dim3(grid_all(nObjects)), dim3(kB), 0, stream, nObjects, dObjTreelet, dNodeFirst, dTbase,
+                       dTdepth, dQueue[0], dUp);
+    // pass 0 takes up one range per object of two treelets or more (the kernel reads how many: no read-back before
+    // it); a later pass what the one before queued.  Every range a pass queues is smaller than the one it came from.
+    int nPasses = 0;
+    for (int queued = nUpper ? std::min(nObjects, nTreelets / 2) : 0; queued > 0; ++nPasses) {
+        if (nPasses > kUpperMaxPasses) {
+            *error = "gpu build: internal error (upper build does not end)";
+            return false;
+        }
+        int *dCount = dUp + kUpQueue + nPasses;
+        hipLaunchKernelGGL(k_upper_pass, dim3(queued), dim3(kUpperWave), 0, stream, dQueue[nPasses & 1], dCount,
+                           dQueue[(nPasses + 1) & 1], dCount + 1, queueCap, dTbox, dTsize, dTobj, dNodeFirst, dPerm, dLfPos,
+                           dRtPos, dTbase, dTdepth, dSplits, dUp);
+        GB_CHECK(hipMemcpyAsync(&queued, dCount + 1, sizeof(int), hipMemcpyDeviceToHost, stream), "read queue length");
+        GB_CHECK(hipStreamSynchronize(stream), "sync after upper pass");
+        queued = std::min(queued, queueCap);
+    }
+    int upErr[3];
+    std::vector<unsigned> nodeFirst((size_t)nObjects + 1);
+    GB_CHECK(hipMemcpyAsync(upErr, dUp, sizeof upErr, hipMemcpyDeviceToHost, stream), "read upper error words");
+    GB_CHECK(hipMemcpyAsync(nodeFirst.data(), dNodeFirst, nodeFirst.size() * sizeof(unsigned), hipMemcpyDeviceToHost, stream), "read node_first");
+    GB_CHECK(hipGetLastError(), "kernel launch");
+    GB_CHECK(hipStreamSynchronize(stream), "sync after upper build");
+    if (upErr[kUpErrInternal]) {
+        *error = "gpu build: internal error (upper build " + std::to_string(upErr[kUpErrInternal]) + ")";
+        return false;
+    }
+    // What the host's loop over the objects would have stopped at: the lowest-numbered object of all.  The words of an
+    // object the device refused are the host builder's own, from that object's treelet table alone.
+    if (upErr[kUpErrCount] < refuse.object && upErr[kUpErrCount] <= upErr[kUpErrTable]) {
+        *error = "gpu build: internal error (treelet count)";
+        return false;
+    }
+    if (upErr[kUpErrTable] < refuse.object) {
+        const int k = upErr[kUpErrTable];
+        int range[2];
+        GB_CHECK(hipMemcpyAsync(range, dObjTreelet + k, sizeof range, hipMemcpyDeviceToHost, stream), "read treelet range");
+        GB_CHECK(hipStreamSynchronize(stream), "sync after treelet range");
+        const int count = range[1] - range[0];
+        if (range[0] < 0 || count < 1 || range[1] > nTreelets) {
             *error = "gpu build: internal error (treelet count)";
             return false;
         }
-        for (int i = tFirst; i < t && k < refuse.object; ++i) {
-            bool fine = tsize[(size_t)i] >= 1 && (tsize[(size_t)i] & 1);
-            for (int c = 0; c < 6; ++c) fine = fine && std::isfinite(tbox[6 * (size_t)i + c]);
-            if (!fine)
-                refuse(k, "nnbvh_build_create: non-finite primitive bounds (or internal error) in treelet " + std::to_string(i - tFirst));
-        }
-        UpperLayout up;
+        std::vector<float> tbox(6 * (size_t)count);
+        std::vector<int> tsize((size_t)count);
+        GB_CHECK(hipMemcpyAsync(tbox.data(), dTbox + range[0], tbox.size() * sizeof(float), hipMemcpyDeviceToHost, stream), "read treelet bounds");
+        GB_CHECK(hipMemcpyAsync(tsize.data(), dTsize + range[0], tsize.size() * sizeof(int), hipMemcpyDeviceToHost, stream), "read treelet sizes");
+        GB_CHECK(hipStreamSynchronize(stream), "sync after treelet table");
         std::string text;
-        if (k < refuse.object && !hlbvh_upper_layout(tbox.data() + 6 * (size_t)tFirst, tsize.data() + tFirst, count, &up, &text))
-            refuse(k, text);
-        if (k >= refuse.object) break;  // (no later object changes the message)
-        const long root = out->node_first[(size_t)k];
-        if (root + up.total_nodes >= 0x7fffffffL) {
+        if (!hlbvh_upper_refusal(tbox.data(), tsize.data(), count, &text)) {
+            *error = "gpu build: internal error (the host builder accepts a treelet table the device refused)";
+            return false;
+        }
+        refuse(k, text);
+    }
+    for (int k = 0; k < nObjects && k < refuse.object; ++k)
+        if (nodeFirst[(size_t)k + 1] >= 0x7fffffffu) {
             *error = "gpu build: too many nodes";
             return false;
         }
-        for (int i = 0; i < count; ++i) {
-            tbase[tFirst + i] = (int)root + up.base[(size_t)i];
-            tdepth[tFirst + i] = up.depth[(size_t)i];
-        }
-        for (size_t i = 0; i < up.upper_index.size(); ++i) upperIndex.push_back((int)root + up.upper_index[i]);
-        upperNodes.insert(upperNodes.end(), up.upper_nodes.begin(), up.upper_nodes.end());  // offsets count from the tree's root
-        out->node_first[(size_t)k + 1] = (int)root + up.total_nodes;
-    }
     if (refuse.object != kNoObject) {
         *error = refuse.text;
         return false;
     }
+    out->node_first.assign(nodeFirst.begin(), nodeFirst.end());
     const int totalNodes = out->node_first[(size_t)nObjects];
-    const size_t nUpper = upperIndex.size();
-    std::copy(out->node_first.begin(), out->node_first.end(), table.begin() + 2 * (size_t)nTreelets);
-    table.insert(table.end(), upperIndex.begin(), upperIndex.end());
     out->ms[2] = ms_since(t0);
 
     t0 = std::chrono::steady_clock::now();
     nnbvh_linear_node *dNodes = in.d_nodes_out ? in.d_nodes_out : outMem.get<nnbvh_linear_node>((size_t)totalNodes);
     nnbvh_prim *dOrdered = in.d_ordered_out ? in.d_ordered_out : outMem.get<nnbvh_prim>(n);
-    int *dTable = mem.get<int>(table.size());
-    nnbvh_linear_node *dUn = mem.get<nnbvh_linear_node>(nUpper);
     if (!mem.ok || !outMem.ok) return false;
-    const int *dTbase = dTable, *dTdepth = dTable + nTreelets, *dNodeFirst = dTable + 2 * (size_t)nTreelets;
-    const int *dUi = dNodeFirst + nObjects + 1;
-    GB_CHECK(hipMemcpyAsync(dTable, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, stream), "copy layout");
+    if (nUpper)
+        hipLaunchKernelGGL(k_upper_nodes, dim3((nTreelets + kB / 64 - 1) / (kB / 64)), dim3(kB), 0, stream, nTreelets, dSplits,
+                           dPerm, dTbox, dTobj, (const int *)dNodeFirst, dNodes);
     hipLaunchKernelGGL(k_emit, dim3(grid_all(nv)), dim3(kB), 0, stream, m, dKind, dBit, dPstart, dFirst, dLast, dLeft,
-                       dParent, dLeafOrd, dTreeOrd, dTbase, dTdepth, dTobj, dNodeFirst, dObjectFirst, dNodeBox, dNodes,
-                       dDepthObj);
+                       dParent, dLeafOrd, dTreeOrd, dTbase, dTdepth, dTobj, (const int *)dNodeFirst, dObjectFirst, dNodeBox,
+                       dNodes, dDepthObj);
     hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kB), 0, stream, dPrims, dIdxS, n, dOrdered);
-    if (nUpper) {  // the upper nodes join the device array
-        GB_CHECK(hipMemcpyAsync(dUn, upperNodes.data(), nUpper * sizeof(nnbvh_linear_node), hipMemcpyHostToDevice, stream), "copy upper");
-        hipLaunchKernelGGL(k_scatter_nodes, dim3(grid_all((long)nUpper)), dim3(kB), 0, stream, dUi, dUn, (int)nUpper, dNodes);
-    }
     out->depth.assign((size_t)nObjects, 0);
     GB_CHECK(hipMemcpyAsync(out->depth.data(), dDepthObj, (size_t)nObjects * sizeof(int), hipMemcpyDeviceToHost, stream), "read depths");
     GB_CHECK(hipGetLastError(), "kernel launch");
@@ -962,7 +1317,8 @@ bool hlbvh_forest(const DeviceBuildInput &in, const int *objectFirst, int nObjec
     outMem.release(dOrdered);
     out->n_levels = 0;
     out->n_subtrees = nTreelets;
-    out->n_upper = (int)nUpper;
+    out->n_upper = nUpper;
+    out->n_upper_passes = nPasses;
     out->n_codes = m;
     return true;
 }

@@ -392,7 +392,7 @@ struct nnbvh_forest {
     std::vector<nnbvh_prim> ordered;
     std::vector<int32_t> node_first, depths;
     double ms[5] = {0, 0, 0, 0, 0};
-    int n_levels = 0, n_subtrees = 0;
+    int n_levels = 0, n_subtrees = 0, n_upper = 0, n_upper_passes = 0;
 };
 
 namespace {
@@ -459,6 +459,8 @@ nnbvh_forest *forest_create(const nnbvh_prim *prims, int n_prims, const int32_t 
     out->depths.assign(f.depth.begin(), f.depth.end());
     out->n_levels = f.n_levels;
     out->n_subtrees = f.n_subtrees;
+    out->n_upper = f.n_upper;
+    out->n_upper_passes = f.n_upper_passes;
     return out.release();
 }
 
@@ -507,4 +509,6 @@ extern "C" int nnbvh_forest_gpu_timing(const nnbvh_forest *f, double out_ms[5]) 
 }
 extern "C" int nnbvh_forest_n_levels(const nnbvh_forest *f) { return f ? f->n_levels : -1; }
 extern "C" int nnbvh_forest_n_subtrees(const nnbvh_forest *f) { return f ? f->n_subtrees : -1; }
+extern "C" int nnbvh_forest_n_upper(const nnbvh_forest *f) { return f ? f->n_upper : -1; }
+extern "C" int nnbvh_forest_n_upper_passes(const nnbvh_forest *f) { return f ? f->n_upper_passes : -1; }
 extern "C" void nnbvh_forest_destroy(nnbvh_forest *f) { delete f; }

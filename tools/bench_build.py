@@ -217,7 +217,7 @@ def two_level_section(out_path, rounds=5, split="sah"):
             return (f"  one forest build of the objects alone: upload {m[0]:.2f}, big nodes {m[1]:.2f}, subtrees {m[2]:.2f}, "
                     f"layout + bounds {m[3]:.2f}, download {m[4]:.2f} ms; {forest.n_levels} breadth-first passes, "
                     f"{forest.n_subtrees} subtrees")
-        return (f"  one forest build of the objects alone: upload {m[0]:.2f}, sort + treelets {m[1]:.2f}, host upper SAH "
+        return (f"  one forest build of the objects alone: upload {m[0]:.2f}, sort + treelets {m[1]:.2f}, upper SAH "
                 f"{m[2]:.2f}, emit {m[3]:.2f}, download {m[4]:.2f} ms; {forest.n_subtrees} treelets")
 
     for name, (top, verts, objects, placements) in two_level_scenes().items():
@@ -328,7 +328,7 @@ def hlbvh_section(names, out_path, rounds=5):
         lines += [f"{source}: {len(tris)} triangles, {len(tree.nodes)} nodes",
                   f"  build_tree_gpu, end to end   {stats(total)}"]
         lines += [f"    {what:26s} {stats([p[k] for p in phases])}"
-                  for k, what in enumerate(("upload", "device sort + tree", "host upper SAH", "emit", "download"))]
+                  for k, what in enumerate(("upload", "device sort + tree", "upper SAH", "emit", "download"))]
         lines.append("")
         result[name] = {"end_to_end_ms": total, "phases_ms": phases}
     text = "\n".join([f"single HLBVH build on the device, {rounds} rounds after a warm-up, median (min .. max)", ""] + lines)
